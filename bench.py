@@ -17,7 +17,10 @@ over 64 images TOTAL, sharded over the ranks -- strong scaling).
 `--gpus N` without a torchrun environment launches the N ranks itself (fresh child processes, before anything touches the
 GPU); under torchrun WORLD_SIZE must equal --gpus.
 
-Prints ONE JSON line (rank 0).  Extra objects:
+A plain run sets up, warms up, times --steps steps, writes the last step's outputs when --dump-outputs DIR is given, and prints ONE
+JSON line (rank 0): metric, value, unit, higher_is_better, dtype, ms_per_step and the run's configuration.  Everything else it measures
+runs only with --full (implied by --full-cpu-baseline and --scaling-proxy); the objects below are null / empty without it:
+  host_inclusive  pipeline workload: CircuitPipeline.run_batch on host images, with and without the crop dependency;
   roofline      the dominant launch SHAPE of the workload, selected by MEASURED time share: launches of the profiling pass are grouped by
                 (kernel the library dispatched to -- cvmi_last_kernel(), the name rocprofv3 lists --, flops, bytes) and the group with the largest
                 summed duration wins (today: Hiera stage-3 fc2 = gemm256x192_kernel<float> or fc1 = tok_linear_kernel<576, 1, ...>);
@@ -50,6 +53,7 @@ HBM_PEAK_GBS = 8000.0            # MI355X_MICROARCH.md: 8 TB/s spec (6.3 TB/s ac
 SAM_FLOP_PER_IMAGE = 1.83e12     # trunk linear 1606 G + attention 203 G + conv/neck/decoder/refine
 MFMA_PEAK_TFLOPS = 2500.0        # dense fp16/bf16 (MI355X_MICROARCH.md)
 YOLO_STACK_KINDS = ("stem", "conv", "head", "dwconv", "pool", "attention")
+DUMP_BUDGET_BYTES = 64 * 10**6   # --dump-outputs: all arrays together
 
 
 def parse():
@@ -79,7 +83,14 @@ def parse():
                     help="SAM 2.1-L CPU leg as BASELINE.md section 3 states it: the whole batch (B = 16), 1 warm-up + 5 timed iterations (~10 minutes of "
                          "host time; the default is a bounded batch-1 sample)")
     ap.add_argument("--no-profile-pass", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline figure does not need: per-stage timings, the per-launch profiling "
+                         "pass (roofline objects), the CPU baseline and, for the pipeline workload, the host-inclusive path")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (the arrays a caller of each stage receives) to DIR/<name>.npy, float32, "
+                         f"at most {DUMP_BUDGET_BYTES // 10**6} MB in all: an array too large for its share is a fixed, seeded sample of its elements")
     a = ap.parse_args()
+    a.full = a.full or a.full_cpu_baseline or a.scaling_proxy > 1
     sam_heavy = a.workload in ("circuit", "sam2l", "sam2l_box", "pipeline")
     if a.steps is None:
         a.steps = 5 if sam_heavy else 50
@@ -222,6 +233,27 @@ def check_replicas(tensors, what):
         raise SystemExit(f"bench.py: {what} weight replicas differ between ranks after the broadcast ({lo.tolist()} vs {hi.tolist()})")
 
 
+def dump_outputs(stages, out_dir):
+    """--dump-outputs: every stage's outputs() as DIR/<stage>_<name>.npy, float32.  Smallest array first, each takes at most an equal share
+    of what the arrays before it left of DUMP_BUDGET_BYTES (npy headers included); a larger array is written as a fixed, seeded sample of
+    its elements: the sorted, de-duplicated flat indices drawn by torch.randint from seed 0, one-dimensional."""
+    import numpy as np
+    import torch
+    arrays = [(f"{sname.replace('[', '_').rstrip(']')}_{k}", t) for sname, st in stages for k, t in st.outputs().items()]
+    arrays.sort(key=lambda kv: (kv[1].numel(), kv[0]))
+    os.makedirs(out_dir, exist_ok=True)
+    left = (DUMP_BUDGET_BYTES - 1024 * len(arrays)) // 4
+    for i, (name, t) in enumerate(arrays):
+        t = t.detach()
+        cap = left // (len(arrays) - i)
+        if t.numel() > cap:
+            idx = torch.randint(t.numel(), (cap,), generator=torch.Generator().manual_seed(0)).unique()
+            t = t.reshape(-1)[idx.to(t.device)]
+        out = t.float().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), out)
+        left -= out.size
+
+
 # ---- stages ------------------------------------------------------------------------------------------------------------------
 class YoloStage:
     """YOLO11 forward + decode + NMS on B resident images (one captured graph)."""
@@ -269,6 +301,14 @@ class YoloStage:
 
     def run(self):
         self.plan.run()
+
+    def outputs(self):
+        """What a caller of the detector receives: per image the kept detections [max_det, 6] (x1, y1, x2, y2, conf, cls; rows past the
+        image's count zeroed) and the count."""
+        import torch
+        n = self.yp.det_count.long()
+        keep = torch.arange(self.yp.max_det, device=n.device)[None, :] < n[:, None]
+        return {"det": torch.where(keep[..., None], self.yp.det, 0.0), "det_count": n}
 
     def profile(self, reps=5):
         acc = {}
@@ -356,6 +396,10 @@ class SamStage:
 
     def run(self):
         self.plan.run()
+
+    def outputs(self):
+        """What `infer_masks` returns for the batch: high- and low-resolution logits of the selected mask and its predicted IoU."""
+        return {"high_res": self.sp.high_res, "low_res": self.sp.low_res, "iou": self.sp.iou}
 
     # launch kinds whose bound is the matrix pipe (flops / duration vs the dense MFMA peak); everything else is priced against HBM
     MFMA_KINDS = ("gemm", "mlp_fused", "attn_global", "attn_window", "attention")
@@ -531,7 +575,7 @@ def main():
         if a.total_images % a.scaling_proxy or share % 2:
             raise SystemExit("--scaling-proxy N: total-images / N must be a whole, even number of images")
         cmd = [sys.executable, os.path.abspath(__file__), "--workload", "pipeline", "--total-images", str(share), "--seg-batch", str(a.seg_batch),
-               "--dtype", a.dtype, "--streams", str(a.streams), "--steps", str(a.steps * 4), "--warmup", str(a.warmup * 2), "--no-cpu-baseline", "--no-profile-pass"]
+               "--dtype", a.dtype, "--streams", str(a.streams), "--steps", str(a.steps * 4), "--warmup", str(a.warmup * 2), "--full", "--no-cpu-baseline", "--no-profile-pass"]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise SystemExit(f"bench.py: the --scaling-proxy child failed:\n{r.stderr[-2000:]}")
@@ -598,8 +642,9 @@ def main():
             off += b_
         images_per_step = n
         scaling = "strong"
-        host_pipe = HostPipeline(a, stages[0][1], stages[1][1], n, seed0, crop=True)
-        host_pipe_nocrop = HostPipeline(a, stages[0][1], stages[1][1], n, seed0, crop=False)
+        if a.full:
+            host_pipe = HostPipeline(a, stages[0][1], stages[1][1], n, seed0, crop=True)
+            host_pipe_nocrop = HostPipeline(a, stages[0][1], stages[1][1], n, seed0, crop=False)
         name = (f"full pipeline YOLO11-l 640x640 + SAM2.1 Hiera-L 1024x1024, {a.total_images} circuit images per step sharded over {world} GPU(s) "
                 f"({n} per GPU: detector batch {n}, segmenter batches {sam_sizes}), {a.dtype} (BASELINE configs[3]); `value` = graph replays on "
                 "resident tensors, `host_inclusive` = CircuitPipeline.run_batch(crop=True) on u8 host images (H2D, letterbox, detector, D2H + glue + "
@@ -628,6 +673,8 @@ def main():
         dist.barrier()
     ms_per_step = dt / a.steps * 1e3
     value = world * images_per_step * a.steps / dt
+    if a.dump_outputs and rank == 0:
+        dump_outputs(stages, a.dump_outputs)
     host_info = None
     if host_pipe is not None:                                     # every rank runs its shard through the host-visible path too; MAX over ranks
         if world > 1:
@@ -645,7 +692,7 @@ def main():
 
     # ---- per-stage timing (graph replays alone) + per-launch timing pass (un-captured, event pairs on the engine stream)
     stage_info, rooflines, cpu_parts = {}, {}, {}
-    if rank == 0:
+    if rank == 0 and a.full:
         for sname, st in stages:
             if sname.endswith("]") and not sname.endswith("[0]"):
                 continue                                           # identical second SAM stage

@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 for r in 1 2; do
   for v in "$@"; do
     echo -n "$v: "
-    env $v python bench.py $ARGS --no-cpu-baseline 2>/dev/null | python -c "
+    env $v python bench.py $ARGS --full --no-cpu-baseline 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 st=d['stages']

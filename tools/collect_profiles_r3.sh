@@ -6,8 +6,8 @@ for w in circuit yolo11n yolo11l sam2l sam2l_bf16 sam2l_box sam2l_box_bf16 pipel
   [ -s $O/bench_$w.json ] && tail -1 $O/bench_$w.json > profiles/${P}_bench_$w.json
 done
 line() { python3 -c "import json,sys; d=json.loads(open('$1').read().strip().splitlines()[-1]); print(d['value'], d['unit'], d['ms_per_step'], 'ms/step')" 2>/dev/null; }
-python3 tools/prof_summary.py $O/prof_yolo profiles/${P}_yolo11n_b32_kernel_stats.md "Command: rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --workload yolo11n --steps 20 --warmup 5 --no-cpu-baseline (YOLO11-n, B=32, fp16; graph replays + eager profiling passes).  Kernel names demangled (tools/kname.py).  Same run's bench line: $(line $O/prof_yolo.log)"
-python3 tools/prof_summary.py $O/prof_sam profiles/${P}_sam2l_b16_kernel_stats.md "Command: rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --workload sam2l --steps 3 --warmup 1 --no-cpu-baseline (SAM 2.1 Hiera-L, B=16, fp16 operands / f32 residual stream).  Kernel names demangled (tools/kname.py): the spelling bench.py's roofline objects use.  Same run's bench line: $(line $O/prof_sam.log)"
+python3 tools/prof_summary.py $O/prof_yolo profiles/${P}_yolo11n_b32_kernel_stats.md "Command: rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --workload yolo11n --steps 20 --warmup 5 --full --no-cpu-baseline (YOLO11-n, B=32, fp16; graph replays + eager profiling passes).  Kernel names demangled (tools/kname.py).  Same run's bench line: $(line $O/prof_yolo.log)"
+python3 tools/prof_summary.py $O/prof_sam profiles/${P}_sam2l_b16_kernel_stats.md "Command: rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --workload sam2l --steps 3 --warmup 1 --full --no-cpu-baseline (SAM 2.1 Hiera-L, B=16, fp16 operands / f32 residual stream).  Kernel names demangled (tools/kname.py): the spelling bench.py's roofline objects use.  Same run's bench line: $(line $O/prof_sam.log)"
 python3 - <<PY
 import json
 t = json.load(open("$O/traffic.json"))

@@ -7,6 +7,6 @@ mkdir -p gpurun_out/$TAG
 for v in "$@"; do
   export $v
   d=gpurun_out/$TAG/$(echo $v | tr '=' '_')
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $d -- python bench.py $ARGS --steps 5 --warmup 2 --no-cpu-baseline > $d.json 2> $d.err || exit 1
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $d -- python bench.py $ARGS --steps 5 --warmup 2 --full --no-cpu-baseline > $d.json 2> $d.err || exit 1
   python tools/prof_summary.py $d $d.md "$v" && rm -rf $d
 done
