@@ -123,6 +123,10 @@ SIGNATURES = {
     "cvmi_mask_extent": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "cvmi_mask_postprocess": (_i, [_vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
     "cvmi_mask_postprocess_sizes": (_i, [_vp, _i, _i, _i, _vp, _f, _vp, _vp, _vp]),
+    "cvmi_node_prepare": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cvmi_enhance_lines": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
+    "cvmi_contours_workspace": (C.c_size_t, [_i, _vp]),
+    "cvmi_external_contours": (_i, [_vp, _vp, _i, _vp, _i, _vp, C.c_size_t, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "cvmi_upsample_refine": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, C.POINTER(_i), _i, _i, _vp]),
     "cvmi_sam2_transform": (_i, [_vp, _i, _i, _vp, _i, _i, _vp]),
     "cvmi_sam2_transform_batch": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _vp]),

@@ -73,6 +73,22 @@ template <typename T> inline const char* cvmi_tyname() { return sizeof(T) == 4 ?
     if (e_ != hipSuccess) CVMI_FAIL("kernel launch failed: %s", hipGetErrorString(e_)); \
   } while (0)
 
+
+// ---- OpenCV's 8-bit INTER_LINEAR axis table (11-bit fixed-point coefficients) --------------------------------------------
+// destination index d of an axis resized src -> dst: source taps s0, s1 and weights a0 + a1 = 2048 (letterbox_kernel, node_resize_kernel)
+__device__ __forceinline__ void lb_axis(int d, int dst, int src, int& s0, int& s1, int& a0, int& a1) {
+  const double scale = (double)src / (double)dst;
+  float f = (float)(((double)d + 0.5) * scale - 0.5);
+  int s = (int)floorf(f);
+  f -= (float)s;
+  if (s < 0) { f = 0.f; s = 0; }
+  if (s >= src - 1) { f = 0.f; s = src - 1; }
+  a1 = (int)rintf(f * 2048.f);
+  a0 = (int)rintf((1.f - f) * 2048.f);
+  s0 = s;
+  s1 = s + 1 < src ? s + 1 : src - 1;
+}
+
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
 // ---- exact division of n < 65536 by d <= 65536 via one 64-bit multiply --------------------------

@@ -302,19 +302,7 @@ __global__ __launch_bounds__(256) void detect_decode_kernel(const DetectArgs d, 
 
 // ------------------------------------------------------------------------------------------------
 // Letterbox: OpenCV-style 8-bit fixed-point bilinear (11-bit coefficients) + pad 114 + channel
-// flip + /255, written NHWC with 3 channels.
-__device__ __forceinline__ void lb_axis(int d, int dst, int src, int& s0, int& s1, int& a0, int& a1) {
-  const double scale = (double)src / (double)dst;
-  float f = (float)(((double)d + 0.5) * scale - 0.5);
-  int s = (int)floorf(f);
-  f -= (float)s;
-  if (s < 0) { f = 0.f; s = 0; }
-  if (s >= src - 1) { f = 0.f; s = src - 1; }
-  a1 = (int)rintf(f * 2048.f);
-  a0 = (int)rintf((1.f - f) * 2048.f);
-  s0 = s;
-  s1 = s + 1 < src ? s + 1 : src - 1;
-}
+// flip + /255, written NHWC with 3 channels.  The coefficient tables are lb_axis (common.hpp).
 
 // s2d = 1: the output is written space-to-depth(2) with 16 channels per 2x2 block,
 // dst[(y/2, x/2)][((y&1)*2 + (x&1))*3 + c] (channels 12..15 zero), so that the stride-2 3x3 stem conv becomes a

@@ -52,12 +52,14 @@ class CircuitPipeline:
     segmenter: `SAM2Model`-like (`infer_masks(x, boxes=None)`, `.image_size`); transforms: `SAM2Transforms`-like."""
 
     def __init__(self, detector, segmenter, transforms, stage2_iou=0.6, max_prompts=32, crop_fn=None, swap_channels=True, seg_batch=16, crop=False,
-                 crop_padding=80):
+                 crop_padding=80, nodes=False):
         """crop=True: the reference's chain -- detector -> stage-2 NMS -> crop window from the boxes (crop.py) -> segmenter on the window
         (analysis_pipeline.py:177 -> :206); False: the segmenter sees the whole image.  crop_fn overrides the built-in crop.
         swap_channels: segment_with_sam2 applies cv2.COLOR_BGR2RGB to whatever it is given (circuit_analyzer.py:343), and the
         pipeline hands it RGB (analysis_pipeline.py:199-203) -- i.e. the reference's segmenter sees the channels reversed.
-        seg_batch: images per segmenter launch (BASELINE configs[2] runs SAM 2.1-L at 16)."""
+        seg_batch: images per segmenter launch (BASELINE configs[2] runs SAM 2.1-L at 16).
+        nodes=True (learned prompts only): each result also carries get_node_connections' front end on its mask and boxes
+        (circuit_analyzer.py:1325-1365, wires.node_contours): "emptied_mask", "resized_bboxes", "enhanced", "contours"."""
         self.det, self.seg, self.tr = detector, segmenter, transforms
         self.stage2_iou, self.max_prompts, self.swap = stage2_iou, max_prompts, swap_channels
         self.crop_padding = int(crop_padding)
@@ -65,6 +67,7 @@ class CircuitPipeline:
         self.crop_fn = crop_fn if crop_fn is not None else ((lambda im, bb: crop_image_and_adjust_bboxes(im, bb, padding=self.crop_padding)) if crop else None)
         self.seg_batch = max(1, int(seg_batch))
         self.seg_slots = 2                         # segmenter plan instances (each with its own stream) the overlapped path alternates between
+        self.nodes = bool(nodes)
         self.timings = defaultdict(float)          # wall seconds per phase, accumulated over calls (bench.py prints them per step)
 
     def _tick(self, name, t0):
@@ -161,6 +164,8 @@ class CircuitPipeline:
     def run_batch(self, images, prompts="learned", rank=0, world=1):
         """The share [lo, hi) of `images` that belongs to `rank`: detection, stage-2 NMS, (crop), segmentation.
         Returns [(global image index, result dict)]."""
+        if self.nodes and prompts != "learned":
+            raise ValueError("nodes=True needs prompts='learned': node analysis reads the one mask per image of the learned prompts")
         lo, hi = shard_range(len(images), rank, world)
         mine = list(images[lo:hi])
         if not mine:
@@ -172,7 +177,20 @@ class CircuitPipeline:
         else:
             bboxes = self.detect(mine)
             res = self.segment(mine, bboxes, prompts)
+        if self.nodes:
+            self._add_nodes(res)
         return [(lo + i, r) for i, r in enumerate(res)]
+
+    # ---- run_node_analysis (analysis_pipeline.py:227) -> get_node_connections up to get_contours, on the masks left on the device
+    def _add_nodes(self, res):
+        from .wires import node_contours
+        t = time.perf_counter()
+        dev = self.seg.dev if hasattr(self.seg, "dev") else None
+        with torch.cuda.device(dev if dev is not None else torch.cuda.current_device()):
+            nodes = node_contours([r["mask"] for r in res], [r["bboxes"] for r in res])
+        for r, n in zip(res, nodes):
+            r.update(n)
+        self._tick("nodes (empty boxes + resize + enhance_lines + external contours + D2H of the points)", t)
 
     # ---- learned prompts, no crop: the segmenter does not depend on the detector's boxes (analysis_pipeline.py:168-225 passes the
     #      image, not the boxes, to segment_with_sam2), so the whole batch is ENQUEUED -- segmenter chunks on the segmenter's stream, the

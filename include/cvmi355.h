@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define CVMI_VERSION 121
+#define CVMI_VERSION 122
 
 typedef void* cvmi_stream_t; /* hipStream_t */
 
@@ -409,6 +409,36 @@ int cvmi_sam2_transform_batch(const uint8_t* src, int B, int H, int W, void* dst
  * (B x 4 ints, read during the call; it travels in the kernel arguments).  The source may be the buffer the detector's letterbox read. */
 int cvmi_sam2_transform_rects(const uint8_t* src, long long src_image_stride, int H, int W, const int* rects, int B, void* dst, int R,
                               int dst_dtype, int swap_rb, cvmi_stream_t stream);
+
+/* ---- node analysis (CircuitAnalyzer.get_node_connections, circuit_analyzer.py:1286-1370): N u8 planes of different sizes, packed back to
+ * back (plane n at sum over m < n of its predecessors' pixels), sizes in HOST arrays read during the call. */
+
+/* Mask preparation (:1327-1345 + resize_image_keep_aspect :787-809): src -> emptied (the boxes zeroed) -> resized (cv2.resize INTER_LINEAR,
+ * 8-bit fixed point, the letterbox's coefficient tables).  sizes: HOST N x {H, W, new_h, new_w}; resized is packed by {new_h, new_w}.
+ * boxes: DEVICE i32 [box_start[N], 4] {xmin, ymin, xmax, ymax} = int() of the reference's values, only the boxes it empties (classes
+ * other than crossover / junction / circuit / vss); plane n owns boxes [box_start[n], box_start[n + 1]) (HOST, N + 1 ints). */
+int cvmi_node_prepare(const uint8_t* src, int N, const int* sizes, const int* boxes, const int* box_start, uint8_t* emptied,
+                      uint8_t* resized, cvmi_stream_t stream);
+
+/* enhance_lines (:289-311) fused: cv2.GaussianBlur((5,5), 1) (bit-exact 8-bit path, BORDER_REFLECT_101) -> cv2.dilate(ones(3,3), 2) ->
+ * cv2.erode(ones(3,3), 2) (5 x 5 max / min, border replicated).  sizes: HOST N x {H, W}; dst packed like src (no aliasing).
+ * sums: DEVICE u64 [N], each plane's exact pixel sum of dst (get_contours' cv2.mean(img)[0] > 127 is sum > 127 * H * W). */
+int cvmi_enhance_lines(const uint8_t* src, int N, const int* sizes, uint8_t* dst, unsigned long long* sums, cvmi_stream_t stream);
+
+/* get_contours' cv2.findContours(img, RETR_EXTERNAL, CHAIN_APPROX_SIMPLE) (:388-405) on N packed u8 planes (sizes: HOST N x {H, W}).
+ * Foreground = non-zero, or != 255 where sums (DEVICE u64 [N], from cvmi_enhance_lines; NULL = never) says the plane inverts (:398).
+ * binarize = 1 writes the reference's img[img == 255] = 1 (:401) into planes that do not invert.  workspace: DEVICE, at least
+ * cvmi_contours_workspace(N, sizes) bytes.  Outputs (DEVICE):
+ *   counts i32 [N + 3]: contours per plane, then the total contours, the total points, the longest traced border (steps);
+ *   per contour c < min(total, cap_contours), plane by plane, each plane's contours in REVERSE raster order of their start pixels (cv2's
+ *   list order): info i32 [cap_contours, 8] {plane, npts, first point, x, y, w, h, steps} (x .. h = cv2.boundingRect of the points) and
+ *   area2 i64 [cap_contours] = twice the signed shoelace area of the points; points i32 [cap_points, 2] (x, y), plane-relative.
+ * Nothing is truncated silently: when the totals exceed the capacities, the outputs past them are not written and the caller repeats
+ * the call with capacities of at least the totals. */
+size_t cvmi_contours_workspace(int N, const int* sizes);
+int cvmi_external_contours(uint8_t* planes, const unsigned long long* sums, int N, const int* sizes, int binarize, void* workspace,
+                           size_t workspace_bytes, int cap_contours, int cap_points, int* counts, int* info, long long* area2,
+                           int* points, cvmi_stream_t stream);
 
 #ifdef __cplusplus
 }
