@@ -9,12 +9,10 @@
 //                                   accumulator itself, converted to fp16 in place)
 // Each lane owns ONE query column, so the online-softmax state (max, sum) is a per-lane scalar and
 // the row reductions are 15 in-register ops + one cross-half shuffle.
-// K/V tiles (32 keys) are staged through LDS by a loader group of GS threads: GS = 256 shares one
-// tile among the 4 waves of a workgroup (same batch/head, long sequences), GS = 64 gives every wave
-// its own item (many small windows).
+// attn_f16_kernel: every wave has its own item (many small windows) and stages its K/V tiles (32 keys)
+// through its own LDS slice; long sequences go to the shared-tile kernels (attn64_kernel and the head_dim 72 ones).
 // f32 (parity mode): plain VALU kernel, one wave per query.
 #include "common.hpp"
-#include <stdlib.h>
 
 namespace {
 
@@ -27,10 +25,7 @@ struct AttnArgs {
   int q_bdiv, kv_bdiv;   // batch sharing (no window): q rows of batch entry b come from entry b / q_bdiv, k / v rows from b / kv_bdiv
   int qtiles;      // ceil(Nq / 32)
   int items;       // B * heads * qtiles
-  int diag;        // CVMI_ATTN_DIAG, timing experiments ONLY (results are wrong): bit 0 = attn_res256 skips its key-tile loop, bit 1 = skips its K / V DMA
-  float defer;     // deferred-rescale threshold in log2 units (DEFER_LOG2; CVMI_ATTN_DEFER=0 restores "rescale on every new maximum" for A/B runs)
   int q_log2;      // cvmi_attn_desc.q_log2: q already carries scale * log2(e) (the dispatcher then passes scale = 1 / log2(e): every kernel's c = scale * log2(e) is 1 to one ulp; attn_dma72_kernel<.., QL = true> uses exactly 1)
-  int xcd;         // 1: XCD-aware workgroup order (xcd_order below); 0: natural order (CVMI_ATTN_XCD=0, A/B runs only)
   FastDiv div_win; // window mode: key -> (row, column) inside the window without a hardware division
   // window mode, attn_res256_kernel: every integer division of its prologue / epilogue as a multiply (they were ~180 of the ~1100 vector
   // instructions a wave of that kernel issues; the vector issue port is what bounds it)
@@ -95,8 +90,7 @@ __device__ __forceinline__ float softmax_tiles(const f32x16 (&sacc)[2], float c,
 // window launch against 226 MB of q + k + v), and the query groups that stream the SAME K / V of a global-attention head re-fetch it
 // through 8 L2s.  Here XCD x owns a contiguous run of logical workgroups, walked in dispatch order: the heads of a window and the query
 // groups of a head are neighbours in space (one L2) and in time.
-__device__ __forceinline__ int xcd_order(int wg, int nwg, int on = 1) {
-  if (!on) return wg;
+__device__ __forceinline__ int xcd_order(int wg, int nwg) {
   const int q = nwg >> 3, r = nwg & 7, xcd = wg & 7, j = wg >> 3;
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
 }
@@ -122,40 +116,31 @@ __device__ __forceinline__ long long tok_off_fast(const AttnArgs& p, int b, int 
   return pix * st;
 }
 
+// GS: threads of a loader group.  One group per wave (GS = 64) is the only form left; the shared 256-thread loader went to attn64_kernel.
 template <int DQKP, int DVP, int GS>
 __global__ __launch_bounds__(256) void attn_f16_kernel(const AttnArgs p) {
+  static_assert(GS == 64, "one loader group per wave (its threads are the lanes): every wave stages its own item's tiles");
   constexpr int KROW = DQKP * 2 + 16;          // K tile row stride (bytes): odd multiple of 16
   constexpr int VROW = 32 * 2 + 8;             // V^T tile row stride (bytes): 72
   constexpr int KTILE = 32 * KROW;
   constexpr int VTILE = DVP * VROW;
-  constexpr int NGRP = 256 / GS;               // loader groups per workgroup
   constexpr int QS = DQKP / 16;                // k16 steps of the S product
   constexpr int DT = DVP / 32;                 // 32-row tiles of O^T
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
   const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
   const int lr = lane & 31, lh = lane >> 5;
-  const int grp = tid / GS, gt = tid % GS;
-  char* const Ks = smem + grp * (KTILE + VTILE);
+  char* const Ks = smem + wv * (KTILE + VTILE);
   char* const Vs = Ks + KTILE;
 
   // work item of this wave
-  int item, qt;
-  if (GS == 256) {                             // workgroup = 4 consecutive q-tiles of one (b, h)
-    const int qgroups = (p.qtiles + 3) / 4;
-    const int bh = blockIdx.x / qgroups;
-    qt = (blockIdx.x - bh * qgroups) * 4 + wv;
-    item = bh;
-  } else {
-    const int it = blockIdx.x * 4 + wv;
-    item = it / p.qtiles;
-    qt = it - item * p.qtiles;
-  }
+  const int it = blockIdx.x * 4 + wv;
+  const int item = it / p.qtiles;
+  const int qt = it - item * p.qtiles;
   const int nbh = p.B * p.heads;
   const bool live = item < nbh && qt < p.qtiles;
   const int itc = item < nbh ? item : nbh - 1;
   const int b = itc / p.heads, h = itc - b * p.heads;
-  // loader group's (b, h): for GS == 64 it is the wave's own; for GS == 256 all waves agree
   const int qwin = p.q_pool ? p.win / 2 : p.win;
 
   // ---- Q fragments (B operand of S^T = K Q^T): lane (q = lr, half lh) holds Q[q][16s + 8lh .. +7]
@@ -201,34 +186,24 @@ __global__ __launch_bounds__(256) void attn_f16_kernel(const AttnArgs p) {
   float m_run = -INFINITY, l_run = 0.f;
   const float c = p.scale * 1.44269504088896340736f;   // softmax in base 2
 
-  // loader identity: group grp loads for item of wave (grp * GS / 64)
-  int lb, lhd;
-  {
-    int litem;
-    if (GS == 256) litem = item; else litem = (blockIdx.x * 4 + grp) / p.qtiles;
-    if (litem >= nbh) litem = nbh - 1;
-    lb = litem / p.heads; lhd = litem - lb * p.heads;
-  }
-
   const int nkt = (p.Nk + 31) / 32;
-  // Staging: the next K / V^T tile is fetched into registers (branch-free, clamped addresses) BEFORE the MFMAs of
-  // the current tile and written to LDS after them, so the global latency overlaps the compute.
+  // Staging: the wave's loader group fetches a K / V^T tile into registers (branch-free, clamped addresses) and writes it to LDS.
   constexpr int KN = (32 * (DQKP / 8) + GS - 1) / GS, VN = (32 * (DVP / 8) + GS - 1) / GS;
   u32x4 kreg[KN], vreg[VN];
   bool kok[KN], vok[VN];
-  // Loader addressing, hoisted: everything that depends only on the loader's (batch entry, head) is computed once --
+  // Loader addressing, hoisted: everything that depends only on the wave's (batch entry, head) is computed once --
   // tok_off() costs five integer divisions, i.e. > 100 VALU instructions per 16-byte chunk if left in the key loop.
   const char *kbase, *vbase;
   {
     long long korg, vorg;
     if (p.win > 0) {
-      const long long pix0 = tok_off(lb, 0, 1, 1, p.win, p.grid_h, p.grid_w);      // window origin, in pixels
+      const long long pix0 = tok_off(b, 0, 1, 1, p.win, p.grid_h, p.grid_w);      // window origin, in pixels
       korg = pix0 * p.k_st; vorg = pix0 * p.v_st;
     } else {
-      korg = (long long)(lb / p.kv_bdiv) * p.k_sb; vorg = (long long)(lb / p.kv_bdiv) * p.v_sb;
+      korg = (long long)(b / p.kv_bdiv) * p.k_sb; vorg = (long long)(b / p.kv_bdiv) * p.v_sb;
     }
-    kbase = p.k + (korg + (long long)lhd * p.k_sh) * 2;
-    vbase = p.v + (vorg + (long long)lhd * p.v_sh) * 2;
+    kbase = p.k + (korg + (long long)h * p.k_sh) * 2;
+    vbase = p.v + (vorg + (long long)h * p.v_sh) * 2;
   }
   const int kst = (int)p.k_st, vst = (int)p.v_st;
   auto key_pix = [&](int key) -> int {                     // pixel offset of a key token from the window origin
@@ -236,45 +211,24 @@ __global__ __launch_bounds__(256) void attn_f16_kernel(const AttnArgs p) {
     const int ty = (int)p.div_win.div((unsigned)key);
     return ty * p.grid_w + (key - ty * p.win);
   };
-  // 32 consecutive keys advance the pixel offset by a constant when 32 is a whole number of window rows (or no window):
-  // the per-chunk offsets are then "offset at tile 0 + kt * stride" (wave-uniform choice; windows 14 / 7 take the general path)
-  // (shared-tile kernels only: the per-wave-tile kernels run 1-2 key tiles and cannot spare the registers)
-  const bool linear = GS == 256 && (p.win <= 0 || (32 % p.win) == 0);
-  const int tile_pix = p.win <= 0 ? 32 : (32 / (p.win > 0 ? p.win : 1)) * p.grid_w;
-  constexpr int KNL = GS == 256 ? KN : 1, VNL = GS == 256 ? VN : 1;
-  int koff0[KNL], voff0[VNL];
-  if constexpr (GS == 256) {
-#pragma unroll
-    for (int i = 0; i < KN; ++i) {
-      const int idx = gt + i * GS;
-      const int row = idx / (DQKP / 8), ch = idx - row * (DQKP / 8);
-      koff0[i] = key_pix(row) * kst + ch * 8;
-    }
-#pragma unroll
-    for (int i = 0; i < VN; ++i) {
-      const int idx = gt + i * GS;
-      const int ch = idx / 32, key_l = idx - ch * 32;
-      voff0[i] = key_pix(key_l) * vst + ch * 8;
-    }
-  }
   auto fetch = [&](int kt) {
 #pragma unroll
     for (int i = 0; i < KN; ++i) {
-      const int idx = gt + i * GS;
+      const int idx = lane + i * GS;
       const int row = idx / (DQKP / 8), ch = idx - row * (DQKP / 8);
       const int key = kt * 32 + row;
       const bool ok = idx < 32 * (DQKP / 8) && key < p.Nk && ch * 8 < p.dqk;
-      const int off = linear ? koff0[GS == 256 ? i : 0] + kt * tile_pix * kst : key_pix(key) * kst + ch * 8;
+      const int off = key_pix(key) * kst + ch * 8;
       kreg[i] = *reinterpret_cast<const u32x4*>(kbase + (long long)(ok ? off : 0) * 2);
       kok[i] = ok;
     }
 #pragma unroll
     for (int i = 0; i < VN; ++i) {
-      const int idx = gt + i * GS;
+      const int idx = lane + i * GS;
       const int ch = idx / 32, key_l = idx - ch * 32;       // consecutive threads -> consecutive keys
       const int key = kt * 32 + key_l;
       const bool ok = idx < 32 * (DVP / 8) && key < p.Nk && ch * 8 < p.dv;
-      const int off = linear ? voff0[GS == 256 ? i : 0] + kt * tile_pix * vst : key_pix(key) * vst + ch * 8;
+      const int off = key_pix(key) * vst + ch * 8;
       vreg[i] = *reinterpret_cast<const u32x4*>(vbase + (long long)(ok ? off : 0) * 2);
       vok[i] = ok;
     }
@@ -282,13 +236,13 @@ __global__ __launch_bounds__(256) void attn_f16_kernel(const AttnArgs p) {
   auto commit = [&]() {
 #pragma unroll
     for (int i = 0; i < KN; ++i) {
-      const int idx = gt + i * GS;
+      const int idx = lane + i * GS;
       const int row = idx / (DQKP / 8), ch = idx - row * (DQKP / 8);
       if (idx < 32 * (DQKP / 8)) *reinterpret_cast<u32x4*>(Ks + row * KROW + ch * 16) = kok[i] ? kreg[i] : u32x4{0u, 0u, 0u, 0u};
     }
 #pragma unroll
     for (int i = 0; i < VN; ++i) {
-      const int idx = gt + i * GS;
+      const int idx = lane + i * GS;
       const int ch = idx / 32, key_l = idx - ch * 32;
       if (idx < 32 * (DVP / 8)) {
         const f16x8 v = __builtin_bit_cast(f16x8, vok[i] ? vreg[i] : u32x4{0u, 0u, 0u, 0u});
@@ -297,21 +251,12 @@ __global__ __launch_bounds__(256) void attn_f16_kernel(const AttnArgs p) {
       }
     }
   };
-  constexpr bool PREFETCH = (GS == 256);        // per-wave tiles (GS = 64) would need 12 staging registers x 4: not worth a wave of occupancy
-  if constexpr (PREFETCH) {
-    fetch(0);
+  // (no register prefetch of the next tile: per-wave tiles would need 12 staging registers x 4, not worth a wave of occupancy)
+  for (int kt = 0; kt < nkt; ++kt) {
+    __syncthreads();                           // previous tile fully consumed
+    fetch(kt);
     commit();
     __syncthreads();
-  }
-  for (int kt = 0; kt < nkt; ++kt) {
-    if constexpr (PREFETCH) {
-      if (kt + 1 < nkt) fetch(kt + 1);
-    } else {
-      __syncthreads();                         // previous tile fully consumed
-      fetch(kt);
-      commit();
-      __syncthreads();
-    }
 
     // ---- S^T tile: 32 keys x 32 queries ------------------------------------------------------------
     f32x16 sacc;
@@ -368,11 +313,6 @@ __global__ __launch_bounds__(256) void attn_f16_kernel(const AttnArgs p) {
         oacc[t] = CVMI_MFMA_32X32X16(__builtin_bit_cast(f16x8, vv), pf[s], oacc[t], 0, 0, 0);
       }
     }
-    if constexpr (PREFETCH) {
-      __syncthreads();                         // every wave is done reading this tile
-      if (kt + 1 < nkt) commit();
-      __syncthreads();
-    }
   }
 
   // ---- normalise and store O[q][d] (lane holds runs of 4 consecutive d) ---------------------------
@@ -402,8 +342,8 @@ __global__ __launch_bounds__(256) void attn_f16_kernel(const AttnArgs p) {
 }
 
 // ---- long-sequence variant: 64-key tiles, V kept row-major and transposed by the LDS read --------------------------
-// Same products and online softmax as attn_f16_kernel<.., 256> (workgroup = 4 q-tiles of one (b, h) sharing the K / V
-// tile), but (1) a tile holds 64 keys, so the two barriers, the staging bookkeeping and the accumulator rescale are
+// Same products and online softmax as attn_f16_kernel, but the workgroup's q-tiles are of one (b, h) and share the K / V
+// tile, and (1) a tile holds 64 keys, so the two barriers, the staging bookkeeping and the accumulator rescale are
 // paid once per 24 MFMAs instead of once per 12, and (2) V is written to LDS as it comes from HBM ([key][d], 16-byte
 // stores) and the V^T operand is gathered by ds_read_b64_tr_b16 (per 16-lane group: a 4-key x 16-d block delivered
 // column-major), which removes the 8 scalar 2-byte LDS stores per staged chunk the transposed image needed.
@@ -431,7 +371,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn64_kernel(const 
   const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
   const int lr = lane & 31, lh = lane >> 5;
   const int qgroups = (p.qtiles + NW - 1) / NW;
-  const int wgx = xcd_order((int)blockIdx.x, (int)gridDim.x, p.xcd);
+  const int wgx = xcd_order((int)blockIdx.x, (int)gridDim.x);
   const int item = wgx / qgroups;                        // (b, h) of the workgroup
   const int qt = (wgx - item * qgroups) * NW + wv;
   const bool live = qt < p.qtiles;
@@ -710,7 +650,7 @@ __global__ __launch_bounds__(NW * 64, (AV8 || NW != 8) ? 2 : 4) void attn_res256
   const int tid = threadIdx.x, wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   const int lr = lane & 31, lh = lane >> 5;
   const int qgroups = (p.qtiles + NW - 1) / NW;
-  const int wgx = xcd_order((int)blockIdx.x, (int)gridDim.x, p.xcd);
+  const int wgx = xcd_order((int)blockIdx.x, (int)gridDim.x);
   const int item = qgroups == 1 ? wgx : wgx / qgroups;      // (16 x 16 windows, 8 waves: one group per item)
   const int qt = (wgx - item * qgroups) * NW + wv;
   const bool live = qt < p.qtiles;
@@ -730,7 +670,7 @@ __global__ __launch_bounds__(NW * 64, (AV8 || NW != 8) ? 2 : 4) void attn_res256
     const char* vbase = p.v + (vorg + (long long)h * p.v_sh) * 2;
 #pragma unroll
     for (int j = 0; j < (36 + NW - 1) / NW; ++j) {
-      if (j * NW + wv >= 36 || (p.diag & 2)) break;           // 36 wave-instructions per matrix (wave-uniform)
+      if (j * NW + wv >= 36) break;           // 36 wave-instructions per matrix (wave-uniform)
       const int L = (j * NW + wv) * 64 + lane;
       const int row = L / CH, ch = L - row * CH;
       int pix = row;
@@ -835,7 +775,7 @@ __global__ __launch_bounds__(NW * 64, (AV8 || NW != 8) ? 2 : 4) void attn_res256
   }
 
 #pragma unroll 1
-  for (int kc = 0; kc < ((p.diag & 1) ? 0 : NK / 64); ++kc) {
+  for (int kc = 0; kc < NK / 64; ++kc) {
     f32x16 sacc[2];
 #pragma unroll
     for (int u = 0; u < 2; ++u)
@@ -858,7 +798,7 @@ __global__ __launch_bounds__(NW * 64, (AV8 || NW != 8) ? 2 : 4) void attn_res256
     if constexpr (QL) {
       static_assert(!AV8, "QL is the 16-bit form");
       const float top = xhalf_max(mx);                          // the tile's maximum RELATIVE to m_ref (the MFMA subtracted it)
-      const bool grow = kc == 0 || top > p.defer;
+      const bool grow = kc == 0 || top > DEFER_LOG2;
       if (__any(grow)) {                                      // (a real branch: the first tile, then rare)
         const float m_new = grow ? (float)(f16)(m_ref + top) : m_ref;
         const float dlt = m_new - m_ref;
@@ -886,7 +826,7 @@ __global__ __launch_bounds__(NW * 64, (AV8 || NW != 8) ? 2 : 4) void attn_res256
         for (int r = 0; r < 16; ++r) pf[u][r >> 3][r & 7] = (f16)__builtin_amdgcn_exp2f(sacc[u][r]);
     } else {
     const float m_top = fmaxf(m_run, xhalf_max(mx));
-    const bool grow = (m_top - m_run) * c > (AV8 ? 0.f : p.defer);      // first tile: m_run = -inf -> true
+    const bool grow = (m_top - m_run) * c > (AV8 ? 0.f : DEFER_LOG2);      // first tile: m_run = -inf -> true
     const float m_new = grow ? m_top : m_run;
     const float mc = m_new * c;
     const float alpha = grow ? __builtin_amdgcn_exp2f(fmaf(m_run, c, -mc)) : 1.0f;
@@ -989,7 +929,7 @@ __global__ __launch_bounds__(QT * 128, 4) void attn_res64_kernel(const AttnArgs 
   char* const Vs = Ks + NK * ROW;
   const int lr = lane & 31, lh = lane >> 5;
   const int nitems = p.B * p.heads;
-  const int item_raw = xcd_order((int)blockIdx.x, (int)gridDim.x, p.xcd) * 2 + sub;
+  const int item_raw = xcd_order((int)blockIdx.x, (int)gridDim.x) * 2 + sub;
   const int item = item_raw < nitems ? item_raw : nitems - 1;
   const int qt = wv;
   const bool live = item_raw < nitems && qt < p.qtiles;
@@ -1089,7 +1029,7 @@ __global__ __launch_bounds__(QT * 128, 4) void attn_res64_kernel(const AttnArgs 
     for (int r = 2; r < 8; ++r) { mxa = max3f(mxa, sacc[0][r], sacc[1][r]); mxb = max3f(mxb, sacc[0][r + 7], sacc[1][r + 7]); }
     const float mx = max3f(mxa, mxb, max3f(sacc[0][15], sacc[1][15], mxa));
     const float m_top = fmaxf(m_run, xhalf_max(mx));
-    const bool grow = (m_top - m_run) * c > p.defer;      // first tile: m_run = -inf -> true
+    const bool grow = (m_top - m_run) * c > DEFER_LOG2;      // first tile: m_run = -inf -> true
     const float m_new = grow ? m_top : m_run;
     const float mc = m_new * c;
     const float alpha = grow ? __builtin_amdgcn_exp2f(fmaf(m_run, c, -mc)) : 1.0f;
@@ -1171,7 +1111,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 4 : 2) void attn_dma72_kernel(co
   const int tid = threadIdx.x, wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   const int lr = lane & 31, lh = lane >> 5;
   const int qgroups = (p.qtiles + NW - 1) / NW;
-  const int wgx = xcd_order((int)blockIdx.x, (int)gridDim.x, p.xcd);
+  const int wgx = xcd_order((int)blockIdx.x, (int)gridDim.x);
   const int item = wgx / qgroups;
   const int qt = (wgx - item * qgroups) * NW + wv;
   const bool live = qt < p.qtiles;
@@ -1343,7 +1283,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 4 : 2) void attn_dma72_kernel(co
     if constexpr (QL) {
       static_assert(!AV8, "QL is the 16-bit form");
       const float top = xhalf_max(mx);                          // the tile's maximum RELATIVE to m_ref (the MFMA subtracted it)
-      const bool grow = kt == 0 || top > p.defer;
+      const bool grow = kt == 0 || top > DEFER_LOG2;
       if (__any(grow)) {                                      // (a real branch: the first tile, then rare)
         const float m_new = grow ? (float)(f16)(m_ref + top) : m_ref;       // representable in the operand type, so the Q slot holds it exactly
         const float dlt = m_new - m_ref;                        // exact in f32 (both are 16-bit values of similar magnitude or m_ref = 0)
@@ -1369,7 +1309,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 4 : 2) void attn_dma72_kernel(co
         for (int r = 0; r < 16; ++r) pf[u][r >> 3][r & 7] = (f16)__builtin_amdgcn_exp2f(sacc[u][r]);
     } else {
     const float m_top = fmaxf(m_run, xhalf_max(mx));
-    const bool grow = (m_top - m_run) * c > (AV8 ? 0.f : p.defer);      // first tile: m_run = -inf -> true
+    const bool grow = (m_top - m_run) * c > (AV8 ? 0.f : DEFER_LOG2);      // first tile: m_run = -inf -> true
     const float m_new = grow ? m_top : m_run;
     const float mc = m_new * c;
     const float alpha = grow ? __builtin_amdgcn_exp2f(fmaf(m_run, c, -mc)) : 1.0f;
@@ -1505,7 +1445,7 @@ __global__ __launch_bounds__(128) void attn_win16_kernel(const AttnArgs p) {
   char* const Kl = lds + wv * 2 * IPW * ITEM_B;
   char* const Vl = Kl + IPW * ITEM_B;
   const int nitems = p.B * p.heads;
-  const int item0 = (xcd_order((int)blockIdx.x, (int)gridDim.x, p.xcd) * 2 + wv) * IPW;   // first item of this wave
+  const int item0 = (xcd_order((int)blockIdx.x, (int)gridDim.x) * 2 + wv) * IPW;   // first item of this wave
   // ---- per-lane item for the compute phase: lane = ti * NQ + tq, ti < IPW
   const int ti = lane / NQ, tq = lane - ti * NQ;
   const bool active = ti < IPW && item0 + ti < nitems;
@@ -1694,22 +1634,20 @@ __global__ __launch_bounds__(256) void attn_f32_kernel(const AttnArgs p) {
   if (valid && lane + 64 < p.dv) O[obase + lane + 64] = o1 * inv;
 }
 
-template <int DQKP, int DVP, int GS>
+template <int DQKP, int DVP>
 int launch_f16(const AttnArgs& a, hipStream_t stream) {
   constexpr int KROW = DQKP * 2 + 16, VROW = 72;
-  constexpr size_t lds = (size_t)(256 / GS) * (32 * KROW + DVP * VROW);
-  long long blocks;
-  if (GS == 256) blocks = (long long)a.B * a.heads * ((a.qtiles + 3) / 4);
-  else blocks = ((long long)a.items + 3) / 4;
+  constexpr size_t lds = (size_t)4 * (32 * KROW + DVP * VROW);
+  const long long blocks = ((long long)a.items + 3) / 4;
   CVMI_CHECK(blocks > 0 && blocks < (1ll << 31), "attention: bad grid");
   static bool attr_done = false;
   if (!attr_done && lds > 64 * 1024) {
-    CVMI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_f16_kernel<DQKP, DVP, GS>),
+    CVMI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_f16_kernel<DQKP, DVP, 64>),
                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr_done = true;
   }
-  cvmi_note_kernel("attn_f16_kernel<%d, %d, %d>", DQKP, DVP, GS);
-  hipLaunchKernelGGL((attn_f16_kernel<DQKP, DVP, GS>), dim3((unsigned)blocks), dim3(256), lds, stream, a);
+  cvmi_note_kernel("attn_f16_kernel<%d, %d, 64>", DQKP, DVP);
+  hipLaunchKernelGGL((attn_f16_kernel<DQKP, DVP, 64>), dim3((unsigned)blocks), dim3(256), lds, stream, a);
   CVMI_LAUNCH_CHECK();
   return 0;
 }
@@ -1717,14 +1655,12 @@ int launch_f16(const AttnArgs& a, hipStream_t stream) {
 template <int DQKP, int DVP>
 int launch_f16_gs(const AttnArgs& a, hipStream_t stream) {
   // share K/V tiles across the workgroup when each (batch, head) has >= 4 query tiles
-  static const int use64 = getenv("CVMI_ATTN64") ? atoi(getenv("CVMI_ATTN64")) : 2;      // tuning experiments only: 0 old, 1 four waves, 2 eight
-  if (a.qtiles >= 8 && use64 == 2) return launch_attn64<DQKP, DVP, 8>(a, stream);
-  if (a.qtiles >= 4) return use64 ? launch_attn64<DQKP, DVP, 4>(a, stream) : launch_f16<DQKP, DVP, 256>(a, stream);
+  if (a.qtiles >= 8) return launch_attn64<DQKP, DVP, 8>(a, stream);
+  if (a.qtiles >= 4) return launch_attn64<DQKP, DVP, 4>(a, stream);
   // two or three query tiles against a LONG key axis (mask-decoder token -> image attention: 38 tokens x 4096 positions): alone, each wave
   // walks 128 key tiles through its private LDS slice; in the shared-tile kernel the idle waves of the workgroup help to stage the tiles
-  static const int longk = getenv("CVMI_ATTN64_LONGK") ? atoi(getenv("CVMI_ATTN64_LONGK")) : 1;         // tuning experiments only
-  if (longk && use64 && a.qtiles >= 2 && a.Nk >= 2048 && a.win == 0) return longk == 2 ? launch_attn64<DQKP, DVP, 8>(a, stream) : launch_attn64<DQKP, DVP, 4>(a, stream);
-  return launch_f16<DQKP, DVP, 64>(a, stream);
+  if (a.qtiles >= 2 && a.Nk >= 2048 && a.win == 0) return launch_attn64<DQKP, DVP, 4>(a, stream);
+  return launch_f16<DQKP, DVP>(a, stream);
 }
 
 }  // namespace
@@ -1758,12 +1694,6 @@ extern "C" int CVMI_ENTRY(cvmi_attention)(const cvmi_attn_desc* d, cvmi_stream_t
   a.div_ow.init(d->win > 0 ? (unsigned)(d->q_pool ? (d->win / 2 > 0 ? d->win / 2 : 1) : d->win) : 1u);
   a.div_heads.init((unsigned)(d->heads > 0 ? d->heads : 1));
   a.items = d->B * d->heads * a.qtiles;
-  static const int use_xcd = getenv("CVMI_ATTN_XCD") ? atoi(getenv("CVMI_ATTN_XCD")) : 1;                 // A/B runs only
-  a.xcd = use_xcd;
-  static const float defer = getenv("CVMI_ATTN_DEFER") ? (float)atof(getenv("CVMI_ATTN_DEFER")) : DEFER_LOG2;   // A/B runs only
-  a.defer = defer;
-  static const int diag = getenv("CVMI_ATTN_DIAG") ? atoi(getenv("CVMI_ATTN_DIAG")) : 0;
-  a.diag = diag;
   if (d->win > 0) {
     CVMI_CHECK(d->grid_h % d->win == 0 && d->grid_w % d->win == 0, "attention: grid %dx%d not divisible by window %d", d->grid_h, d->grid_w, d->win);
     CVMI_CHECK(d->Nk == d->win * d->win, "attention: window mode needs Nk == win^2");
@@ -1791,8 +1721,7 @@ extern "C" int CVMI_ENTRY(cvmi_attention)(const cvmi_attn_desc* d, cvmi_stream_t
              d->q_sb % 8 == 0 && d->k_sb % 8 == 0 && d->v_sb % 8 == 0, "attention(f16): q/k/v strides must be multiples of 8 elements");
   CVMI_CHECK((((uintptr_t)d->q | (uintptr_t)d->k | (uintptr_t)d->v) & 15) == 0 && ((uintptr_t)d->o & 7) == 0, "attention(f16): misaligned pointer");
   // 4 x 4 windows of Hiera's head_dim 72: the per-thread VALU kernel
-  static const int use_win16 = getenv("CVMI_ATTN_WIN16") ? atoi(getenv("CVMI_ATTN_WIN16")) : 1;           // tuning experiments only
-  if (use_win16 && d->win == 4 && d->Nk == 16 && d->dqk == 72 && d->dv == 72 && (d->Nq == 16 || (d->q_pool && d->Nq == 4)) &&
+  if (d->win == 4 && d->Nk == 16 && d->dqk == 72 && d->dv == 72 && (d->Nq == 16 || (d->q_pool && d->Nq == 4)) &&
       ((uintptr_t)d->o & 15) == 0 && d->o_st % 8 == 0 && d->o_sh % 8 == 0) {
     const long long items = (long long)d->B * d->heads;
     const unsigned blocks = (unsigned)((items + 7) / 8);
@@ -1802,26 +1731,23 @@ extern "C" int CVMI_ENTRY(cvmi_attention)(const cvmi_attn_desc* d, cvmi_stream_t
     CVMI_LAUNCH_CHECK();
     return 0;
   }
-  static const int use_res256 = getenv("CVMI_ATTN_RES256") ? atoi(getenv("CVMI_ATTN_RES256")) : 2;      // tuning experiments only: 0 off, 1 four waves, 2 eight waves (4 per SIMD at 125 VGPRs)
-  if (use_res256 && d->Nk == 256 && d->dqk == 72 && d->dv == 72 && d->k_st % 8 == 0 && d->v_st % 8 == 0) {
+  // 16 x 16 windows: eight waves (4 per SIMD at 125 VGPRs) from eight query tiles up, four below
+  if (d->Nk == 256 && d->dqk == 72 && d->dv == 72 && d->k_st % 8 == 0 && d->v_st % 8 == 0) {
     if (d->av_fp8 && a.qtiles >= 8) return launch_res256<8, true>(a, stream);          // block-scaled fp8 AV product (configs[4])
-    if (d->q_log2) return (use_res256 == 2 && a.qtiles >= 8) ? launch_res256<8, false, true>(a, stream) : launch_res256<4, false, true>(a, stream);
-    return (use_res256 == 2 && a.qtiles >= 8) ? launch_res256<8>(a, stream) : launch_res256<4>(a, stream);
+    if (d->q_log2) return a.qtiles >= 8 ? launch_res256<8, false, true>(a, stream) : launch_res256<4, false, true>(a, stream);
+    return a.qtiles >= 8 ? launch_res256<8>(a, stream) : launch_res256<4>(a, stream);
   }
-  static const int use_res64 = getenv("CVMI_ATTN_RES64") ? atoi(getenv("CVMI_ATTN_RES64")) : 1;          // tuning experiments only
-  if (use_res64 && d->Nk == 64 && d->dqk == 72 && d->dv == 72 && d->k_st % 8 == 0 && d->v_st % 8 == 0 && (a.qtiles == 1 || a.qtiles == 2))
+  if (d->Nk == 64 && d->dqk == 72 && d->dv == 72 && d->k_st % 8 == 0 && d->v_st % 8 == 0 && (a.qtiles == 1 || a.qtiles == 2))
     return a.qtiles == 2 ? launch_res64<2>(a, stream) : launch_res64<1>(a, stream);
-  static const int use_dma72 = getenv("CVMI_ATTN_DMA72") ? atoi(getenv("CVMI_ATTN_DMA72")) : 1;          // tuning experiments only
-  if (use_dma72 && d->Nk >= 512 && d->Nk % 64 == 0 && d->win == 0 && a.qtiles >= 8 && d->dqk == 72 && d->dv == 72 && d->k_st % 8 == 0 && d->v_st % 8 == 0 && !d->q_pool &&
+  if (d->Nk >= 512 && d->Nk % 64 == 0 && d->win == 0 && a.qtiles >= 8 && d->dqk == 72 && d->dv == 72 && d->k_st % 8 == 0 && d->v_st % 8 == 0 && !d->q_pool &&
       (long long)d->Nk * d->k_st * 2 < (1ll << 31) && (long long)d->Nk * d->v_st * 2 < (1ll << 31))
   {
     // 8 waves x 2 workgroups per CU (4 waves per SIMD: the kernel holds 127 registers since its DMA went to buffer addressing; at 139 it ran ONE
     // workgroup per CU, 830 us per Hiera-L global block at B = 16).  4-wave workgroups, four per CU, were the stop-gap that showed it (-12 %);
-    // they stream K / V from L2 twice as often and are kept for A/B runs.
-    static const int nw = getenv("CVMI_ATTN_DMA72_NW") ? atoi(getenv("CVMI_ATTN_DMA72_NW")) : 8;
+    // they stream K / V from L2 twice as often.
     if (d->av_fp8) return launch_dma72<8, true>(a, stream);
-    if (d->q_log2) return nw == 4 ? launch_dma72<4, false, true>(a, stream) : launch_dma72<8, false, true>(a, stream);
-    return nw == 4 ? launch_dma72<4>(a, stream) : launch_dma72<8>(a, stream);
+    if (d->q_log2) return launch_dma72<8, false, true>(a, stream);
+    return launch_dma72<8>(a, stream);
   }
   if (d->dqk <= 32 && d->dv <= 32) return launch_f16_gs<32, 32>(a, stream);
   if (d->dqk <= 32 && d->dv <= 64) return launch_f16_gs<32, 64>(a, stream);

@@ -8,7 +8,6 @@
 // instead of from L2.  Weights of the current channel chunk ([BN][KS*KS*CC]) sit in LDS next to the patch.
 // Operand roles, accumulator layout and the transposing epilogue are those of igemm.hip.
 #include "common.hpp"
-#include <stdlib.h>
 
 namespace {
 
@@ -280,8 +279,7 @@ int launch_tile_n(TileArgs& a, int B, hipStream_t stream) {
   if (a.N <= 64) {
     // small maps (the 20 x 20 level at batch 32: 192 tiles of 8 x 16 for 256 CUs): 4 x 16 tiles double the workgroups and
     // halve each one's dependent chain (stage, barrier, 9 taps of MFMAs, store)
-    static const int th4 = getenv("CVMI_TILE_TH4") ? atoi(getenv("CVMI_TILE_TH4")) : 1;       // tuning experiments only
-    if (th4 && sizeof(T) == 2 && (long long)B * cdiv(a.OH, 8) * a.tiles_x <= 256) return launch_tile<T, KS, S, CC, 64, 2, 2, 4>(a, B, stream);
+    if (sizeof(T) == 2 && (long long)B * cdiv(a.OH, 8) * a.tiles_x <= 256) return launch_tile<T, KS, S, CC, 64, 2, 2, 4>(a, B, stream);
     return launch_tile<T, KS, S, CC, 64, 2, 2, 8>(a, B, stream);
   }
   return launch_tile<T, KS, S, CC, 128, 2, 2, 8>(a, B, stream);
@@ -317,8 +315,7 @@ int cvmi_conv_tile_try(const cvmi_conv_desc* d, hipStream_t stream) {
   if (d->KH != d->KW || !((d->KH == 3 && (d->stride == 1 || d->stride == 2)) || (d->KH == 2 && d->stride == 1))) return -1;
   // measured on YOLO11-n B=32: the tile kernel wins up to 128 input channels at stride 1 and 64 at stride 2; deeper
   // layers are MFMA-bound and the LDS-tiled GEMM pipeline of igemm.hip is the better fit
-  static const int s2max = getenv("CVMI_TILE_S2MAX") ? atoi(getenv("CVMI_TILE_S2MAX")) : 64;       // tuning experiments only
-  static const int s1max = getenv("CVMI_TILE_S1MAX") ? atoi(getenv("CVMI_TILE_S1MAX")) : 128;
+  constexpr int s2max = 64, s1max = 128;
   if (d->c0 > (d->stride == 1 ? s1max : s2max) || d->N > 128) return -1;
   const int es = d->dtype == CVMI_F16 ? 2 : 4;
   if (d->c0 % (16 / es) != 0) return -1;

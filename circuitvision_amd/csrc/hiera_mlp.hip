@@ -49,9 +49,10 @@ template <int I, int N, typename F> __device__ __forceinline__ void static_for(F
 }
 
 // VAR 1: 4-wave workgroups, two waves per SIMD coming from two INDEPENDENT workgroups (C = 144: instead of one 8-wave workgroup; C = 288:
-// instead of one wave per SIMD, at 256 registers with ~20 spilled).  SLOTS: depth of the weight ring.  Both measured in r04 (profiles/r04_ab_runs.md).
-// VAR 2: one wave per SIMD with the chunk loop software-pipelined inside the wave (see `pipelined chunk loop` in the kernel).
-template <int C, int VAR = 0, int SLOTS_ = 2> struct MlpCfg {
+// instead of one wave per SIMD, at 256 registers with ~20 spilled; measured in r04, profiles/r04_ab_runs.md).  C = 144 runs VAR 1.
+// VAR 2: one wave per SIMD with the chunk loop software-pipelined inside the wave (see `pipelined chunk loop` in the kernel).  C = 288 runs VAR 2;
+// VAR 0 (the chunk-order loop) is kept as the bit-exact reference of the pipelined loop (CVMI_MLP_PIPE=0, a test hook).
+template <int C, int VAR = 0> struct MlpCfg {
   static constexpr int KS = C / 16;                 // k-steps of fc1
   static constexpr int KS1 = KS + 1;                // + the bias step
   static constexpr int NT = (C + 31) / 32;          // 32-channel output tiles of fc2
@@ -60,21 +61,20 @@ template <int C, int VAR = 0, int SLOTS_ = 2> struct MlpCfg {
   static constexpr int CHB = FR * 1024;             // bytes per chunk
   static constexpr int NW = VAR >= 1 ? 4 : (C <= 144 ? 8 : 4);       // waves per workgroup
   static constexpr int WPS = VAR == 2 ? (C <= 144 ? 2 : 1) : VAR == 1 ? 2 : (C <= 144 ? 2 : 1);      // waves per SIMD the register budget is set for
-  static constexpr int SLOTS = SLOTS_;
+  static constexpr int SLOTS = 2;                   // weight ring depth
   static constexpr int CNT = (FR + NW - 1) / NW;    // LDS-DMA instructions every wave issues per chunk (the same count in every wave: counted waits)
   static constexpr int LDS = SLOTS * CHB + 1024;    // + a dump piece for the padding instructions of the waves with fewer real pieces
 };
 
 // DIAG (timing-only builds, -DCVMI_MLP_DIAGS; results are wrong by design): 1 no GELU, 2 no MFMAs, 3 no weight DMA inside the loop, 4 no LDS reads,
 // 5 = 1 + 3 + 4 (MFMAs and barriers only).  A template parameter so that the shipped instantiation's code is untouched.
-template <int C, int VAR = 0, int SLOTS = 2, int DIAG = 0>
-__global__ __launch_bounds__((MlpCfg<C, VAR, SLOTS>::NW * 64), (MlpCfg<C, VAR, SLOTS>::WPS)) void hiera_mlp_kernel(float* __restrict__ x, int x_ld, const float* __restrict__ gamma,
+template <int C, int VAR = 0, int DIAG = 0>
+__global__ __launch_bounds__((MlpCfg<C, VAR>::NW * 64), (MlpCfg<C, VAR>::WPS)) void hiera_mlp_kernel(float* __restrict__ x, int x_ld, const float* __restrict__ gamma,
                                                                                       const float* __restrict__ beta, float eps,
                                                                                       const char* __restrict__ wp, const float* __restrict__ b2,
                                                                                       long long rows, float* __restrict__ stats_out, float stats_eps) {
-  using Cfg = MlpCfg<C, VAR, SLOTS>;
-  constexpr int KS = Cfg::KS, KS1 = Cfg::KS1, NT = Cfg::NT, NCH = Cfg::NCH, FR = Cfg::FR, CHB = Cfg::CHB, NW = Cfg::NW, CNT = Cfg::CNT;
-  static_assert(SLOTS == 2 || SLOTS == 3, "ring depth");
+  using Cfg = MlpCfg<C, VAR>;
+  constexpr int KS = Cfg::KS, KS1 = Cfg::KS1, NT = Cfg::NT, NCH = Cfg::NCH, FR = Cfg::FR, CHB = Cfg::CHB, NW = Cfg::NW, CNT = Cfg::CNT, SLOTS = Cfg::SLOTS;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   const int lr = lane & 31, lh = lane >> 5;
@@ -292,11 +292,8 @@ __global__ __launch_bounds__((MlpCfg<C, VAR, SLOTS>::NW * 64), (MlpCfg<C, VAR, S
     // Every wave waits for its OWN DMA pieces (hipcc puts no vmcnt wait in front of a barrier for LDS-DMA writes: without this
     // explicit wait the chunk is read before it has landed -- rare, load-dependent wrong results), then the barrier publishes
     // chunk j to the workgroup and retires the reads of slot (j + 1) & 1.
-    // Ring of SLOTS chunks: chunk j + SLOTS - 1 is issued here, after the barrier that retires the reads of chunk j - 1 (its slot); with three
-    // slots a chunk has TWO chunk times to land (measured r04: with two slots and one wave per SIMD the loop waited ~1600 of ~2800 cycles per
-    // chunk on this wait), and the wait counts: all but the youngest chunk's CNT instructions of this wave.
-    if (SLOTS == 2 || j == NCH - 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CNT) : "memory");
+    // Two-slot ring: chunk j + 1 is issued here, after the barrier that retires the reads of chunk j - 1 (its slot).
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (j + SLOTS - 1 < NCH) issue_chunk(j + SLOTS - 1);
     const char* const buf = smem + (j % SLOTS) * CHB + lane * 16;
@@ -380,15 +377,15 @@ __global__ __launch_bounds__((MlpCfg<C, VAR, SLOTS>::NW * 64), (MlpCfg<C, VAR, S
   }
 }
 
-template <int C, int VAR = 0, int SLOTS = 2, int DIAG = 0>
+template <int C, int VAR = 0, int DIAG = 0>
 int launch_mlp(float* x, int x_ld, const float* gamma, const float* beta, float eps, const void* wp, const float* b2, long long rows, hipStream_t s,
                float* stats_out, float stats_eps) {
-  using Cfg = MlpCfg<C, VAR, SLOTS>;
-  static hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&hiera_mlp_kernel<C, VAR, SLOTS, DIAG>), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS);
+  using Cfg = MlpCfg<C, VAR>;
+  static hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&hiera_mlp_kernel<C, VAR, DIAG>), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS);
   CVMI_HIP(attr);
   const long long per = (long long)Cfg::NW * 32;
-  cvmi_note_kernel("hiera_mlp_kernel<%d, %d, %d>", C, VAR, SLOTS);
-  hipLaunchKernelGGL((hiera_mlp_kernel<C, VAR, SLOTS, DIAG>), dim3((unsigned)((rows + per - 1) / per)), dim3(Cfg::NW * 64), Cfg::LDS, s, x, x_ld, gamma, beta, eps,
+  cvmi_note_kernel("hiera_mlp_kernel<%d, %d>", C, VAR);
+  hipLaunchKernelGGL((hiera_mlp_kernel<C, VAR, DIAG>), dim3((unsigned)((rows + per - 1) / per)), dim3(Cfg::NW * 64), Cfg::LDS, s, x, x_ld, gamma, beta, eps,
                      (const char*)wp, b2, rows, stats_out, stats_eps);
   CVMI_LAUNCH_CHECK();
   return 0;
@@ -425,30 +422,18 @@ extern "C" int CVMI_ENTRY(cvmi_hiera_mlp_stats)(void* x, int x_ld, const float* 
              "hiera_mlp: pointers / ld must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream_;
   float* xf = (float*)x;
-  // A/B switches (measured r04, profiles/r04_ab_runs.md): CVMI_MLP_PIPE bit 1 (default on) -> C = 288 on the software-pipelined loop (VAR 2);
-  // CVMI_MLP_VAR bit 0 -> C = 144, bit 1 -> C = 288 (with PIPE = 0) in 4-wave workgroups at two waves per SIMD; CVMI_MLP_SLOTS = 2 | 3, the ring
-  // depth of the chunk-order loops
-  static const int var = getenv("CVMI_MLP_VAR") ? atoi(getenv("CVMI_MLP_VAR")) : 1;
-  const char* const slots_env = getenv("CVMI_MLP_SLOTS");
-  const int slots = slots_env ? atoi(slots_env) : 2;
-  const char* const pipe_env = getenv("CVMI_MLP_PIPE");        // (read per call: tests/test_ops_gpu.py switches it between two launches)
-  const int pipe = pipe_env ? atoi(pipe_env) : 2;
-#define CVMI_MLP_GO(CC, VV, SS) return launch_mlp<CC, VV, SS>(xf, x_ld, gamma, beta, eps, w_packed, b2, rows, s, ln_stats_out, ln_stats_eps)
-  if (C == 144) {
-    if (var & 1) { if (slots == 3) CVMI_MLP_GO(144, 1, 3); CVMI_MLP_GO(144, 1, 2); }
-    if (slots == 3) CVMI_MLP_GO(144, 0, 3);
-    CVMI_MLP_GO(144, 0, 2);
-  }
+  if (C == 144) return launch_mlp<144, 1>(xf, x_ld, gamma, beta, eps, w_packed, b2, rows, s, ln_stats_out, ln_stats_eps);
 #ifdef CVMI_MLP_DIAGS
   static const int diag = getenv("CVMI_MLP_DIAG") ? atoi(getenv("CVMI_MLP_DIAG")) : 0;
-#define CVMI_MLP_DIAG_GO(D) if (C == 288 && diag == D) return launch_mlp<288, 2, 2, D>(xf, x_ld, gamma, beta, eps, w_packed, b2, rows, s, ln_stats_out, ln_stats_eps)
+#define CVMI_MLP_DIAG_GO(D) if (diag == D) return launch_mlp<288, 2, D>(xf, x_ld, gamma, beta, eps, w_packed, b2, rows, s, ln_stats_out, ln_stats_eps)
   CVMI_MLP_DIAG_GO(1); CVMI_MLP_DIAG_GO(2); CVMI_MLP_DIAG_GO(3); CVMI_MLP_DIAG_GO(4); CVMI_MLP_DIAG_GO(5);
+#undef CVMI_MLP_DIAG_GO
 #endif
-  if (pipe & 2) CVMI_MLP_GO(288, 2, 2);
-  if (var & 2) CVMI_MLP_GO(288, 1, 2);                  // (two workgroups per CU leave room for two slots of 37 KiB each only)
-  if (slots == 3) CVMI_MLP_GO(288, 0, 3);
-  CVMI_MLP_GO(288, 0, 2);
-#undef CVMI_MLP_GO
+  // Test hook, not a tuning switch: CVMI_MLP_PIPE=0 runs C = 288 on the chunk-order loop (VAR 0), the bit-exact reference the pipelined
+  // loop is tested against (tests/test_ops_gpu.py switches it between two launches, so it is read per call).
+  const char* const pipe = getenv("CVMI_MLP_PIPE");
+  if (pipe && !(atoi(pipe) & 2)) return launch_mlp<288, 0>(xf, x_ld, gamma, beta, eps, w_packed, b2, rows, s, ln_stats_out, ln_stats_eps);
+  return launch_mlp<288, 2>(xf, x_ld, gamma, beta, eps, w_packed, b2, rows, s, ln_stats_out, ln_stats_eps);
 }
 
 extern "C" int CVMI_ENTRY(cvmi_hiera_mlp)(void* x, int x_ld, const float* gamma, const float* beta, float eps, const void* w_packed, const float* b2,

@@ -18,8 +18,6 @@
 // Pipeline: register-staged double buffer (global loads for tile t+1 are issued before the MFMAs
 // of tile t and written to the other LDS buffer after them; one barrier per K-tile).
 #include "common.hpp"
-#include <stdlib.h>
-#include <string.h>
 
 namespace {
 
@@ -36,9 +34,7 @@ struct ConvKArgs {
   int rows2;                             // 1x1 / s1 / p0 over two concatenated sources with channel counts that are K-tile multiples
   int nb_n;
   int bias_off;                          // igemm_kernel: LDS byte offset of the parked bias row
-  int rev_m;                             // gemm256x192: 1 = walk the row blocks last-to-first (see launch_g256x192)
   int per_xcd;                           // gemm256x192r: tiles per XCD
-  int diag;                              // gemm256x192r, CVMI_G192_DIAG, timing experiments ONLY (results are wrong): bit 0 = no DMA behind the prologue, bit 1 = no MFMAs, bit 2 = no residual loads
   float* stats;                          // gemm256x192 (f32 out): per row and 96-column slice (mean, sum of squared deviations from it) of the values written, or null
   int im2col_shift;                      // gemm256_kernel<.., IM2COL = true>: log2(K-tiles of 64 channels per 3 x 3 tap) = log2(Cin / 64)
   FastDiv div_ctot, div_kw;
@@ -658,8 +654,11 @@ int launch_glds(ConvKArgs& a, hipStream_t stream) {
 // (the output pixel's top-left input pixel, computed once) moves by a wave-uniform tap offset per K-tile, and a lane whose tap falls outside
 // the image (zero padding) points its DMA at 16 zero bytes instead -- one bit test and one select per DMA instruction, nothing else changes:
 // W rows, LDS image, swizzle, phases, counted waits and the epilogue are those of the plain GEMM.
+// STAGGER: the two wave groups run one barrier apart (above).  The lock-step form (STAGGER = false) is retired; the parameter stays in the
+// kernel's name, which tests and profiles key on.
 template <typename TO, bool STAGGER, bool IM2COL = false>
 __global__ __launch_bounds__(512, 1) void gemm256_kernel(const ConvKArgs p) {
+  static_assert(STAGGER, "only the staggered schedule is built");
   using T = f16;
   constexpr int BM = 256, BN = 256, BKB = 128;
   constexpr int STAGE = (BM + BN) * BKB;                  // 64 KiB
@@ -759,7 +758,7 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(const ConvKArgs p) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
   __builtin_amdgcn_s_barrier();
-  if (STAGGER && wr == 1) __builtin_amdgcn_s_barrier();
+  if (wr == 1) __builtin_amdgcn_s_barrier();
 
   u32x4 xf[2][4], wf[2][4];
 #define G256_READ_X(slot_, j)                                                                                            \
@@ -829,7 +828,7 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(const ConvKArgs p) {
     G256_MMA(0, 2);
     G256_SYNC_OUT();
   }
-  if (STAGGER && wr == 0) __builtin_amdgcn_s_barrier();
+  if (wr == 0) __builtin_amdgcn_s_barrier();
 #undef G256_ISSUE
 #undef G256_READ_X
 #undef G256_READ_W
@@ -1157,14 +1156,13 @@ int launch_g256p(ConvKArgs& a, hipStream_t stream) {
 //     phase (t,1): WC2(t+1)      (t,2): X0(t+2), WC0(t+2)      (t,3): X1(t+2), WC1(t+2)
 // and one counted wait per K-tile, vmcnt(6) in phase 3 (all but the six instructions of phases 2 and 3, i.e. all of tile
 // t+1, has landed).  Hazard argument as for gemm256_kernel (reads retired before a phase's first barrier).
-// M16 = true: the same tile, DMA schedule and barriers on v_mfma_f32_16x16x32 (16 per phase instead of 8 of 32x32x16: equal cycles per
-// flop, equal LDS bytes -- every lane still reads 16 bytes per fragment -- but the chip holds a higher clock on this shape under the
-// power limit: MI355X_MICROARCH.md, DVFS give-back item 7).  Fragment (16 rows x 32 k): lane (r16 = lane & 15, g = lane >> 4) reads chunk
-// 4 ks + g of row r16; with the source swizzle slot = chunk ^ ((row >> 1) & 7) a 16-lane ds_read_b128 group still covers the 16 slots of
-// a 256-byte bank period once.  C / D: lane holds channels 4 g .. 4 g + 3 (rows, from the weight operand) of pixel r16.
-template <typename TO, bool M16 = false>
+// MFMA shape v_mfma_f32_16x16x32 (16 per phase; 32x32x16 has equal cycles per flop and equal LDS bytes -- every lane still reads 16 bytes
+// per fragment -- but the chip holds a higher clock on this shape under the power limit: MI355X_MICROARCH.md, DVFS give-back item 7).
+// Fragment (16 rows x 32 k): lane (r16 = lane & 15, g = lane >> 4) reads chunk 4 ks + g of row r16; with the source swizzle
+// slot = chunk ^ ((row >> 1) & 7) a 16-lane ds_read_b128 group still covers the 16 slots of a 256-byte bank period once.
+// C / D: lane holds channels 4 g .. 4 g + 3 (rows, from the weight operand) of pixel r16.
+template <typename TO>
 __global__ __launch_bounds__(512, 1) void gemm256x192_kernel(const ConvKArgs p) {
-  using T = f16;
   constexpr int BM = 256, BN = 192, BKB = 128;
   constexpr int STAGE = (BM + BN) * BKB;                  // 56 KiB
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1175,11 +1173,10 @@ __global__ __launch_bounds__(512, 1) void gemm256x192_kernel(const ConvKArgs p) 
     wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
   }
   const int bn = wg % p.nb_n;
-  const int bm = p.rev_m ? (int)(gridDim.x / p.nb_n) - 1 - wg / p.nb_n : wg / p.nb_n;
+  const int bm = wg / p.nb_n;
   const int m0 = bm * BM, n0 = bn * BN;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   const int wp = wv & 3, wh = wv >> 2;                    // pixel quarter, channel half (= stagger group; wv and wv + 4 share a SIMD)
-  const int lr = lane & 31, lh = lane >> 5;
 
   // DMA: unit 0 X0, 1 X1 (pieces 2 wv, 2 wv + 1 of 16), 2..4 WC0..WC2 (piece wv of 8: half wv >> 2, 8-row group wv & 3)
   const int nk = (p.K + 63) / 64, krem = p.K & 63;
@@ -1212,28 +1209,20 @@ __global__ __launch_bounds__(512, 1) void gemm256x192_kernel(const ConvKArgs p) 
 #define G192_X1(stage, kt) do { G192_ISSUE1(2, stage, kt); G192_ISSUE1(3, stage, kt); } while (0)
 #define G192_WC(k, stage, kt) G192_ISSUE1(4 + (k), stage, kt)
 
-  f32x16 acc[3][2];                                       // 32x32x16: [channel block][pixel block]
-  f32x4 acc16[3][2][4];                                   // 16x16x32: [channel block][16-channel half][16-pixel block]
+  f32x4 acc16[3][2][4];                                   // [channel block][16-channel half][16-pixel block]
 #pragma unroll
   for (int i = 0; i < 3; ++i)
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      if constexpr (M16) {
+    for (int j = 0; j < 2; ++j)
 #pragma unroll
-        for (int q = 0; q < 4; ++q) acc16[i][j][q] = (f32x4){0.f, 0.f, 0.f, 0.f};
-      } else {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-      }
-    }
+      for (int q = 0; q < 4; ++q) acc16[i][j][q] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
   const int r16 = lane & 15, g16 = lane >> 4;
-  const int sw = M16 ? (r16 >> 1) & 7 : (lr >> 1) & 7;
+  const int sw = (r16 >> 1) & 7;
   int ko[4];
 #pragma unroll
-  for (int s2 = 0; s2 < 4; ++s2) ko[s2] = M16 ? (((4 * (s2 & 1) + g16) ^ sw) << 4) + (s2 >> 1) * 16 * BKB      // s2 = ks + 2 * (16-row half)
-                                             : ((2 * s2 + lh) ^ sw) << 4;
-  const int xbase = (wp * 64 + (M16 ? r16 : lr)) * BKB, wbase = (BM + wh * 96 + (M16 ? r16 : lr)) * BKB;
+  for (int s2 = 0; s2 < 4; ++s2) ko[s2] = (((4 * (s2 & 1) + g16) ^ sw) << 4) + (s2 >> 1) * 16 * BKB;      // s2 = ks + 2 * (16-row half)
+  const int xbase = (wp * 64 + r16) * BKB, wbase = (BM + wh * 96 + r16) * BKB;
 
   G192_X0(0, 0); G192_WC(0, 0, 0); G192_X1(0, 0); G192_WC(1, 0, 0); G192_WC(2, 0, 0);
   if (nk > 1) {
@@ -1267,24 +1256,16 @@ __global__ __launch_bounds__(512, 1) void gemm256x192_kernel(const ConvKArgs p) 
     __builtin_amdgcn_s_barrier();                                                                                        \
     __builtin_amdgcn_sched_barrier(0);                                                                                   \
   } while (0)
-  // M16: wf[ks + 2 hh] = channels 16 hh .. of block i, k-step ks; xf[j][ks + 2 ph] = pixels 32 j + 16 ph .., k-step ks
+  // wf[ks + 2 hh] = channels 16 hh .. of block i, k-step ks; xf[j][ks + 2 ph] = pixels 32 j + 16 ph .., k-step ks
 #define G192_MMA(i)                                                                                                      \
   asm volatile("" : "+v"(wf[0]), "+v"(wf[1]), "+v"(wf[2]), "+v"(wf[3]));                                                 \
-  if constexpr (M16) {                                                                                                   \
-    _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                                                                     \
-    _Pragma("unroll") for (int hh = 0; hh < 2; ++hh)                                                                     \
-    _Pragma("unroll") for (int pq = 0; pq < 4; ++pq)                                                                     \
-      acc16[i][hh][pq] = CVMI_MFMA_16X16X32(__builtin_bit_cast(f16x8, wf[ks + 2 * hh]),                                  \
-                                            __builtin_bit_cast(f16x8, xf[pq >> 1][ks + 2 * (pq & 1)]), acc16[i][hh][pq], 0, 0, 0); \
-    asm volatile("" : "+v"(acc16[i][0][0]), "+v"(acc16[i][0][1]), "+v"(acc16[i][0][2]), "+v"(acc16[i][0][3]),            \
-                      "+v"(acc16[i][1][0]), "+v"(acc16[i][1][1]), "+v"(acc16[i][1][2]), "+v"(acc16[i][1][3]));           \
-  } else {                                                                                                               \
-    _Pragma("unroll") for (int s2 = 0; s2 < 4; ++s2) {                                                                   \
-      Mma<T>::run(wf[s2], xf[0][s2], acc[i][0]);                                                                         \
-      Mma<T>::run(wf[s2], xf[1][s2], acc[i][1]);                                                                         \
-    }                                                                                                                    \
-    asm volatile("" : "+v"(acc[i][0]), "+v"(acc[i][1]));                                                                 \
-  }
+  _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                                                                       \
+  _Pragma("unroll") for (int hh = 0; hh < 2; ++hh)                                                                       \
+  _Pragma("unroll") for (int pq = 0; pq < 4; ++pq)                                                                       \
+    acc16[i][hh][pq] = CVMI_MFMA_16X16X32(__builtin_bit_cast(f16x8, wf[ks + 2 * hh]),                                    \
+                                          __builtin_bit_cast(f16x8, xf[pq >> 1][ks + 2 * (pq & 1)]), acc16[i][hh][pq], 0, 0, 0); \
+  asm volatile("" : "+v"(acc16[i][0][0]), "+v"(acc16[i][0][1]), "+v"(acc16[i][0][2]), "+v"(acc16[i][0][3]),              \
+                    "+v"(acc16[i][1][0]), "+v"(acc16[i][1][1]), "+v"(acc16[i][1][2]), "+v"(acc16[i][1][3]));
 
   for (int kt = 0; kt < nk; ++kt) {
     const int b = kt & 1;
@@ -1327,13 +1308,13 @@ __global__ __launch_bounds__(512, 1) void gemm256x192_kernel(const ConvKArgs p) 
 #undef G192_SYNC_OUT
 #undef G192_MMA
 
-  // ---- M16, f32 output + residual on a full tile (Hiera stage-3 fc2, the dominant launch): NO LDS transposition, no barriers.  In the
+  // ---- f32 output + residual on a full tile (Hiera stage-3 fc2, the dominant launch): NO LDS transposition, no barriers.  In the
   //      16x16x32 C / D layout a lane holds 4 consecutive channels of a pixel and the four lanes g = 0..3 hold 16 consecutive ones:
   //      residual loads and stores are 64-byte row pieces as they stand.  Row statistics for the next LayerNorm (p.stats): per pixel and
   //      96-channel slice (= this wave's channel half) the slice MEAN and the sum of squared deviations from it, two passes over the 24
   //      values in registers -- no E[x^2] - E[x]^2 cancellation however far the row sits from zero; the consumer combines the
   //      slices as Chan et al. do (tok_linear16.hip / tok_linear.hip, stats_parts).
-  if constexpr (M16 && sizeof(TO) == 4) {
+  if constexpr (sizeof(TO) == 4) {
     if (p.res && p.act == CVMI_ACT_NONE && !p.act_after_res && p.res_mod == 0 && m0 + BM <= p.M && n0 + BN <= p.N) {      // (uniform)
       const int slices = p.N / 96;
       f32x4 bv[3][2];
@@ -1407,46 +1388,20 @@ __global__ __launch_bounds__(512, 1) void gemm256x192_kernel(const ConvKArgs p) 
     if (NPASS == 1 || wh == pass) {
       const int cbase = NPASS == 1 ? wh * 96 : 0;
       with_act<true>(p.act_after_res ? CVMI_ACT_NONE : p.act, [&](auto actf) {
-        if constexpr (M16) {
 #pragma unroll
-          for (int i = 0; i < 3; ++i)
+        for (int i = 0; i < 3; ++i)
 #pragma unroll
-            for (int hh = 0; hh < 2; ++hh) {
-              const int nl = cbase + i * 32 + hh * 16 + 4 * g16;
-              const int n = n0 + pass * CW + nl;
-              f32x4 bv = {0.f, 0.f, 0.f, 0.f};
-              if (n < p.N) bv = *reinterpret_cast<const f32x4*>(p.bias + n);
-#pragma unroll
-              for (int pq = 0; pq < 4; ++pq) {
-                const int ml = wp * 64 + pq * 16 + r16;
-                float v[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = actf(acc16[i][hh][pq][e] + bv[e]);
-                char* d = Ct + ml * CROWB + nl * OES;
-                if constexpr (OES == 2) {
-                  f16x4 hv = {(f16)v[0], (f16)v[1], (f16)v[2], (f16)v[3]};
-                  *reinterpret_cast<f16x4*>(d) = hv;
-                } else {
-                  f32x4 fv = {v[0], v[1], v[2], v[3]};
-                  *reinterpret_cast<f32x4*>(d) = fv;
-                }
-              }
-            }
-        } else
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const int nl = cbase + i * 32 + 8 * q + 4 * lh;
+          for (int hh = 0; hh < 2; ++hh) {
+            const int nl = cbase + i * 32 + hh * 16 + 4 * g16;
             const int n = n0 + pass * CW + nl;
             f32x4 bv = {0.f, 0.f, 0.f, 0.f};
             if (n < p.N) bv = *reinterpret_cast<const f32x4*>(p.bias + n);
 #pragma unroll
-            for (int j = 0; j < 2; ++j) {
-              const int ml = wp * 64 + j * 32 + lr;
+            for (int pq = 0; pq < 4; ++pq) {
+              const int ml = wp * 64 + pq * 16 + r16;
               float v[4];
 #pragma unroll
-              for (int e = 0; e < 4; ++e) v[e] = actf(acc[i][j][4 * q + e] + bv[e]);
+              for (int e = 0; e < 4; ++e) v[e] = actf(acc16[i][hh][pq][e] + bv[e]);
               char* d = Ct + ml * CROWB + nl * OES;
               if constexpr (OES == 2) {
                 f16x4 hv = {(f16)v[0], (f16)v[1], (f16)v[2], (f16)v[3]};
@@ -1457,7 +1412,6 @@ __global__ __launch_bounds__(512, 1) void gemm256x192_kernel(const ConvKArgs p) 
               }
             }
           }
-        }
       });
     }
     __syncthreads();
@@ -1510,7 +1464,7 @@ __global__ __launch_bounds__(512, 1) void gemm256x192_kernel(const ConvKArgs p) 
             mean_ += dl * (4.0f / (nn + 4.0f));
             m2_ += t.y + dl * dl * (nn * 4.0f / (nn + 4.0f));
           }
-          const int slices = p.N / CW;                      // (slice mean, sum of squared deviations): the format the direct M16 epilogue writes
+          const int slices = p.N / CW;                      // (slice mean, sum of squared deviations): the format the direct epilogue writes
           *reinterpret_cast<float2*>(p.stats + ((size_t)(m0 + tid) * slices + (n0 / CW + pass)) * 2) = make_float2(mean_, m2_);
         }
       }
@@ -1519,7 +1473,7 @@ __global__ __launch_bounds__(512, 1) void gemm256x192_kernel(const ConvKArgs p) 
   }
 }
 
-// ---- Row-block-persistent form of gemm256x192_kernel<float, true> for the launch it is dominant in (Hiera-L stage-3 fc2: M = 65536,
+// ---- Row-block-persistent form of gemm256x192_kernel<float> for the launch it is dominant in (Hiera-L stage-3 fc2: M = 65536,
 //      N = 576 = 3 tiles, K = 2304, f32 output + f32 residual + row statistics).  Measured on the one-tile-per-workgroup kernel (r03): a
 //      round of 256 tiles is ~43 us of K-loop at the matrix pipe's limit followed by ~20 us in which every CU reads its 196 KB of residual
 //      and writes its 196 KB of output at the same moment -- the launch pays its MFMA bound and its HBM bound in series.  Here a persistent
@@ -1658,7 +1612,7 @@ __global__ __launch_bounds__(512, 1) void gemm256x192r_kernel(const ConvKArgs p)
       for (int j = 0; j < nseg; ++j, ++g) {
         const int b = g & 1;
         const char* st = smem + b * STAGE;
-        const bool dma = !(p.diag & 1), more1 = dma && g + 1 < ng, more2 = dma && g + 2 < ng;
+        const bool more1 = g + 1 < ng, more2 = g + 2 < ng;
         if (j == nseg - 1) {                                // the same K-tile in EVERY workgroup (the rounding sequence of a row must not depend on where its image sits in the batch); the batch was retired by the counted wait of K-tile ji + 1 <= nseg - 2
 #pragma unroll
           for (int i = 0; i < 3; ++i)
@@ -1671,20 +1625,20 @@ __global__ __launch_bounds__(512, 1) void gemm256x192r_kernel(const ConvKArgs p)
         R192_READ_X(1);
         if (more1) R192_WC(2, b ^ 1, wo1);
         R192_SYNC_IN();
-        if (!(p.diag & 2)) { R192_MMA(0) }
+        R192_MMA(0)
         R192_SYNC_OUT();
         // ---- phase 2
         R192_READ_W(1);
         // (both X halves of stage b were read in phase 1: X1 goes out here, a phase earlier than in gemm256x192_kernel -- the A rows are the
-        //  loads that come from HBM, and CVMI_G192_DIAG shows the loop waiting on its DMA, not on the matrix pipe: r03, 181 us WITHOUT the MFMAs)
+        //  loads that come from HBM, and the loop waits on its DMA, not on the matrix pipe: r03, 181 us WITHOUT the MFMAs)
         if (more2) { R192_X0(b, xo2); R192_X1(b, xo2); R192_WC(0, b, wo2); }
         R192_SYNC_IN();
-        if (!(p.diag & 2)) { R192_MMA(1) }
+        R192_MMA(1)
         R192_SYNC_OUT();
         // ---- phase 3
         R192_READ_W(2);
         if (more2) { R192_WC(1, b, wo2); }
-        if (j == ji && !(p.diag & 4)) {                     // (uniform) six more loads in flight behind the DMA: one counted wait covers both
+        if (j == ji) {                                      // (uniform) six more loads in flight behind the DMA: one counted wait covers both
           R192_RLOAD(0, 0); R192_RLOAD(1, 64); R192_RLOAD(2, 128); R192_RLOAD(3, 192); R192_RLOAD(4, 256); R192_RLOAD(5, 320);
           if (more2) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
           else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");          // (cannot happen for ji + 2 < nseg; kept exact anyway)
@@ -1693,7 +1647,7 @@ __global__ __launch_bounds__(512, 1) void gemm256x192r_kernel(const ConvKArgs p)
           else if (more1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
         R192_SYNC_IN();
-        if (!(p.diag & 2)) { R192_MMA(2) }
+        R192_MMA(2)
         R192_SYNC_OUT();
         xo1 = xo2; wo1 = wo2;
         if (++kt2 == nk) {
@@ -1761,27 +1715,22 @@ int launch_g256x192(ConvKArgs& a, hipStream_t stream) {
   constexpr int bytes = lds > epi ? lds : epi;
   static bool attr_done = false;
   if (!attr_done) {
-    CVMI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256x192_kernel<TO, false>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    CVMI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256x192_kernel<TO, true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    CVMI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256x192_kernel<TO>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
     attr_done = true;
   }
   a.nb_n = cdiv(a.N, 192);
   const long long blocks = (long long)cdiv(a.M, 256) * a.nb_n;
   CVMI_CHECK(blocks > 0 && blocks < (1ll << 31), "conv2d: bad grid %lld", blocks);
-  static const int m16 = getenv("CVMI_G192_M16") ? atoi(getenv("CVMI_G192_M16")) : 1;        // MFMA shape: 1 = 16x16x32, 0 = 32x32x16 (A/B runs)
-  // Row blocks last-to-first: the A operand (the fp16 hidden activation, 302 MB at B = 16: more than the 256 MiB Infinity Cache) was written
-  // first-to-last by the launch in front of this one, so its LAST rows are the ones still on the die when this launch starts.
-  static const int rev = getenv("CVMI_G192_REV") ? atoi(getenv("CVMI_G192_REV")) : 0;   // measured r03 (call r3j): no effect (207.6 vs 206.3 us) -- off
-  a.rev_m = rev;
+  // (Walking the row blocks last-to-first, so that the A rows the launch in front wrote last -- still in the Infinity Cache -- are read
+  //  first, measured r03: no effect, 207.6 vs 206.3 us.)
   if constexpr (sizeof(TO) == 4) {
-    static const int persist = getenv("CVMI_G192_PERSIST") ? atoi(getenv("CVMI_G192_PERSIST")) : 1;     // A/B runs only
     static const int ncu = [] {                                  // one persistent workgroup per CU of THIS device (MI355X: 256 = 8 XCDs x 32)
       int dev = 0;
       hipDeviceProp_t prop;
       if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 256;
       return prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     }();
-    if (persist && m16 && a.res && a.act == CVMI_ACT_NONE && !a.act_after_res && a.res_mod == 0 && a.M % 256 == 0 && a.N % 192 == 0 &&
+    if (a.res && a.act == CVMI_ACT_NONE && !a.act_after_res && a.res_mod == 0 && a.M % 256 == 0 && a.N % 192 == 0 &&
         a.K % 256 == 0 && a.K / 256 >= 9 && ncu % 8 == 0 && blocks % ncu == 0) {  // whole rounds of tiles: one workgroup per CU
       static bool attr_r = false;
       if (!attr_r) {
@@ -1790,44 +1739,34 @@ int launch_g256x192(ConvKArgs& a, hipStream_t stream) {
       }
       cvmi_note_kernel("gemm256x192r_kernel");
       a.per_xcd = (int)(blocks / 8);
-      static const int diag = getenv("CVMI_G192_DIAG") ? atoi(getenv("CVMI_G192_DIAG")) : 0;
-      a.diag = diag;
       hipLaunchKernelGGL(gemm256x192r_kernel, dim3((unsigned)ncu), dim3(512), lds, stream, a);
       CVMI_LAUNCH_CHECK();
       return 0;
     }
   }
-  cvmi_note_kernel("gemm256x192_kernel<%s, %s>", sizeof(TO) == 2 ? CVMI_F16NAME : "float", CVMI_BOOLNAME(m16));
-  if (m16) hipLaunchKernelGGL((gemm256x192_kernel<TO, true>), dim3((unsigned)blocks), dim3(512), bytes, stream, a);
-  else hipLaunchKernelGGL((gemm256x192_kernel<TO, false>), dim3((unsigned)blocks), dim3(512), bytes, stream, a);
+  cvmi_note_kernel("gemm256x192_kernel<%s>", sizeof(TO) == 2 ? CVMI_F16NAME : "float");
+  hipLaunchKernelGGL((gemm256x192_kernel<TO>), dim3((unsigned)blocks), dim3(512), bytes, stream, a);
   CVMI_LAUNCH_CHECK();
   return 0;
 }
 
 template <typename TO>
-int launch_g256(ConvKArgs& a, hipStream_t stream, int stagger, bool im2col = false) {
+int launch_g256(ConvKArgs& a, hipStream_t stream, bool im2col = false) {
   constexpr int lds = 2 * 512 * 128;                     // two stages; the epilogue tile (256 x 528 B) is larger: 135168
   constexpr int epi = 256 * ((sizeof(TO) == 4 ? 128 : 256) * (int)sizeof(TO) + 16);
   constexpr int bytes = lds > epi ? lds : epi;
   static bool attr_done = false;
   if (!attr_done) {
     CVMI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256_kernel<TO, true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    CVMI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256_kernel<TO, false>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
     CVMI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256_kernel<TO, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
     attr_done = true;
   }
   a.nb_n = cdiv(a.N, 256);
   const long long blocks = (long long)cdiv(a.M, 256) * a.nb_n;
   CVMI_CHECK(blocks > 0 && blocks < (1ll << 31), "conv2d: bad grid %lld", blocks);
-  if (im2col) {
-    cvmi_note_kernel("gemm256_kernel<%s, true, true>", sizeof(TO) == 2 ? CVMI_F16NAME : "float");
-    hipLaunchKernelGGL((gemm256_kernel<TO, true, true>), dim3((unsigned)blocks), dim3(512), bytes, stream, a);
-    CVMI_LAUNCH_CHECK();
-    return 0;
-  }
-  cvmi_note_kernel("gemm256_kernel<%s, %s>", sizeof(TO) == 2 ? CVMI_F16NAME : "float", CVMI_BOOLNAME(stagger));
-  if (stagger) hipLaunchKernelGGL((gemm256_kernel<TO, true>), dim3((unsigned)blocks), dim3(512), bytes, stream, a);
-  else hipLaunchKernelGGL((gemm256_kernel<TO, false>), dim3((unsigned)blocks), dim3(512), bytes, stream, a);
+  cvmi_note_kernel(im2col ? "gemm256_kernel<%s, true, true>" : "gemm256_kernel<%s, true>", sizeof(TO) == 2 ? CVMI_F16NAME : "float");
+  if (im2col) hipLaunchKernelGGL((gemm256_kernel<TO, true, true>), dim3((unsigned)blocks), dim3(512), bytes, stream, a);
+  else hipLaunchKernelGGL((gemm256_kernel<TO, true>), dim3((unsigned)blocks), dim3(512), bytes, stream, a);
   CVMI_LAUNCH_CHECK();
   return 0;
 }
@@ -1874,9 +1813,7 @@ template <typename T, typename TO, int BM, int BN, int WM, int WN>
 int launch_cfg(ConvKArgs& a, hipStream_t stream) {
   const bool plain = a.plain != 0;
   if constexpr (sizeof(T) == 2 && sizeof(TO) == 2 && BM == 64 && WM * WN == 4) {
-    static const int ks_env = getenv("CVMI_KSPLIT") ? atoi(getenv("CVMI_KSPLIT")) : -1;        // tuning experiments only: 0 off, 2 / 4 forced
-    static const int ks4_mink = getenv("CVMI_KS4_MINK") ? atoi(getenv("CVMI_KS4_MINK")) : 32;
-    static const int ks2_mink = getenv("CVMI_KS2_MINK") ? atoi(getenv("CVMI_KS2_MINK")) : 12;
+    constexpr int ks4_mink = 32, ks2_mink = 12;                                                // K-tiles
     const long long blocks = (long long)cdiv(a.M, BM) * cdiv(a.N, BN);
     const int nkt = a.Kpad / 32;                                                              // 64-byte K-tiles
     // measured on the YOLO11-n B=32 layers (us, 1 / 2 / 4 groups): Detect cv2.2.0 (200 tiles of 64x64, 72 K-tiles) 51 / 34 / 28;
@@ -1885,21 +1822,17 @@ int launch_cfg(ConvKArgs& a, hipStream_t stream) {
     int ks = 1;
     if (BN == 64 && blocks <= 256 && nkt >= ks4_mink) ks = 4;
     else if (blocks <= 512 && nkt >= ks2_mink) ks = 2;
-    if (ks_env >= 0) ks = (ks_env == 2 || ks_env == 4) && nkt >= 2 * ks_env ? ks_env : 1;
     if (ks > 1 && a.Kpad % 32 == 0) {
       const int rc = launch_ksplit<T, TO, BM, BN, WM, WN>(a, stream, ks);
       if (rc >= 0) return rc;
     }
   }
   // 128-byte K-tiles halve the barrier count; 64-byte tiles only when K is too short to fill one
-  static const int force_bkb = getenv("CVMI_BKB") ? atoi(getenv("CVMI_BKB")) : 0;      // tuning experiments only
   // measured (tools/gemm_bench.py): 128-byte tiles pay for deep K (>= 2 KB per row: fewer barriers) and for rows
   // that are exactly one tile; in between, 64-byte tiles win through higher occupancy (40 KB vs 74 KB of LDS)
   const int kbytes = a.Kpad * (int)sizeof(T);
-  bool wide = plain && kbytes % 128 == 0 && (kbytes >= 2048 || kbytes == 128);
-  if (force_bkb == 64) wide = false;
-  if (force_bkb == 128) wide = a.Kpad * (int)sizeof(T) >= 256 && (a.Kpad * (int)sizeof(T)) % 128 == 0;
-  if (wide) return plain ? launch_cfg2<T, TO, BM, BN, WM, WN, 128, true>(a, stream) : launch_cfg2<T, TO, BM, BN, WM, WN, 128, false>(a, stream);
+  const bool wide = plain && kbytes % 128 == 0 && (kbytes >= 2048 || kbytes == 128);
+  if (wide) return launch_cfg2<T, TO, BM, BN, WM, WN, 128, true>(a, stream);
   return plain ? launch_cfg2<T, TO, BM, BN, WM, WN, 64, true>(a, stream) : launch_cfg2<T, TO, BM, BN, WM, WN, 64, false>(a, stream);
 }
 
@@ -1908,18 +1841,16 @@ int launch_cfg(ConvKArgs& a, hipStream_t stream) {
 // a round of tiles, at least half of the column tiles used (measured r04, YOLO11-l B = 64: model.3 1353 -> 529 us, model.5 1285 -> 526, .7 / .20
 // 360 / 379 -> 129, model.1 -- N = 128, half of every tile's columns idle -- 957 -> see profiles/r04_ab_runs.md).
 bool im2col_256_ok(const ConvKArgs& a) {
-  static const int use_g256 = getenv("CVMI_G256") ? atoi(getenv("CVMI_G256")) : 1;
-  static const int use_i2c = getenv("CVMI_G256_IM2COL") ? atoi(getenv("CVMI_G256_IM2COL")) : 1;      // A/B runs only
-  static const double i2c_eff = getenv("CVMI_G256_I2C_EFF") ? atof(getenv("CVMI_G256_I2C_EFF")) : 0.75;     // tuning experiments only
+  constexpr double i2c_eff = 0.75;
+  constexpr int i2c_tiles = 128;
   const int tpt = a.ctot / 64;
-  if (!(use_g256 && use_i2c && !a.plain && !a.rows2 && a.x1 == nullptr && a.up0 == 0 && !a.scalar_gather && a.KW == 3 && a.K == 9 * a.ctot &&
+  if (a.plain || !(!a.rows2 && a.x1 == nullptr && a.up0 == 0 && !a.scalar_gather && a.KW == 3 && a.K == 9 * a.ctot &&
         a.ctot % 64 == 0 && tpt >= 1 && (tpt & (tpt - 1)) == 0 && a.Kpad == a.K && a.N % 8 == 0 && a.shuf_c == 0 && a.res_rep <= 1 && !a.stats && a.res_mod == 0))
     return false;
   const long long tiles = (long long)cdiv(a.M, 256) * cdiv(a.N, 256);
   // (N = 128 fills half of every tile's columns: still a gain over conv_tile_kernel for the 64-channel model.1, 957 -> 633 us, a loss against the
   //  128 x 128 kernel for the 128-channel bottlenecks: YOLO11-l step 12.69 -> 12.82 ms with all of them rerouted)
   const double eff = (double)a.N / (cdiv(a.N, 256) * 256);
-  static const int i2c_tiles = getenv("CVMI_G256_I2C_TILES") ? atoi(getenv("CVMI_G256_I2C_TILES")) : 128;      // tuning experiments only
   return (eff >= i2c_eff || (tpt == 1 && eff >= 0.5)) && tiles >= i2c_tiles;
 }
 
@@ -1927,64 +1858,46 @@ template <typename T, typename TO>
 int launch_typed(ConvKArgs& a, hipStream_t stream) {
   const long long M = a.M;
   const int N = a.N;
-  static const int use_glds = getenv("CVMI_GLDS") ? atoi(getenv("CVMI_GLDS")) : 1;           // tuning experiments only
-  static const int use_g256 = getenv("CVMI_G256") ? atoi(getenv("CVMI_G256")) : 1;           // 0 off, 1 staggered, 2 lock-step
   if constexpr (sizeof(T) == 2) {
     if (im2col_256_ok(a)) {
       const int tpt = a.ctot / 64;
       a.im2col_shift = 0;
       while ((1 << a.im2col_shift) < tpt) ++a.im2col_shift;
-      return launch_g256<TO>(a, stream, 1, true);
+      return launch_g256<TO>(a, stream, true);
     }
     // big plain f16 GEMMs: >= one 256^2 tile per CU and little column-tile waste (N = 576 -> 3 tiles, 75 % used)
     // measured on Hiera-L shapes: wins when >= 80 % of the column tiles and of the last round of 256 tiles is used
     // (N = 576 -> 75 % of 3 column tiles: ties / loses against the 128-row kernels below)
-    static const int g256_mink = getenv("CVMI_G256_MINK") ? atoi(getenv("CVMI_G256_MINK")) : 128;     // tuning experiments only
-    static const int g256_minn = getenv("CVMI_G256_MINN") ? atoi(getenv("CVMI_G256_MINN")) : 256;      // (r04: 384 -> 256, YOLO11-l model.2.cv2 654 -> 424 us; Hiera unaffected)
-    if (use_g256 && a.plain && a.K % 8 == 0 && a.K >= g256_mink && a.Kpad % 64 == 0 && N % 8 == 0 && N >= g256_minn && a.shuf_c == 0 && a.res_rep <= 1) {
+    constexpr int g256_mink = 128;
+    constexpr int g256_minn = 256;      // (r04: 384 -> 256, YOLO11-l model.2.cv2 654 -> 424 us; Hiera unaffected)
+    if (a.plain && a.K % 8 == 0 && a.K >= g256_mink && a.Kpad % 64 == 0 && N % 8 == 0 && N >= g256_minn && a.shuf_c == 0 && a.res_rep <= 1) {
       const long long tiles = (long long)cdiv(M, 256) * cdiv(N, 256);
       const double col_eff = (double)N / (cdiv(N, 256) * 256), wave_eff = (double)tiles / (double)(cdiv(tiles, 256) * 256);
-      if (!a.stats && tiles >= 256 && ((col_eff >= 0.8 && wave_eff >= 0.8) || use_g256 >= 3)) {
-        static const int use_p = getenv("CVMI_G256P") ? atoi(getenv("CVMI_G256P")) : 1;             // tuning experiments only
+      if (!a.stats && tiles >= 256 && col_eff >= 0.8 && wave_eff >= 0.8) {
         if constexpr (sizeof(TO) == 2) {
-          if (use_p && !a.res && !a.act_after_res) return launch_g256p(a, stream);
+          if (!a.res && !a.act_after_res) return launch_g256p(a, stream);
         }
-        return launch_g256<TO>(a, stream, use_g256 != 2);
+        return launch_g256<TO>(a, stream);
       }
       // N a multiple of 192 that the 256-wide tiling wastes (576 = 3 x 192)
-      static const int use_g192 = getenv("CVMI_G192") ? atoi(getenv("CVMI_G192")) : 1;
       const long long tiles192 = (long long)cdiv(M, 256) * cdiv(N, 192);
       // (measured: K = 2304 309 -> 226 us; at K = 576 the 128 x 64 kernel's two workgroups per CU hide the f32 + residual epilogue better)
-      static const int g192_mink = getenv("CVMI_G192_MINK") ? atoi(getenv("CVMI_G192_MINK")) : 1024;   // tuning experiments only
+      constexpr int g192_mink = 1024;
       // (the last round of tiles at least 3/4 used: 384 tiles -- SAM 2.1-L stage-3 fc2 at 8 images, one rank's share of an 8-GPU job -- run 119 us
       //  here against 140 us on the 128 x 64 kernel, r04; the 128 x 192 variant of that kernel: 145 us)
-      static const double g192_eff = getenv("CVMI_G192_EFF") ? atof(getenv("CVMI_G192_EFF")) : 0.75;     // tuning experiments only
-      if (use_g192 && N % 192 == 0 && a.K >= g192_mink && tiles192 >= 256 && (double)tiles192 / (double)(cdiv(tiles192, 256) * 256) >= g192_eff)
+      constexpr double g192_eff = 0.75;
+      if (N % 192 == 0 && a.K >= g192_mink && tiles192 >= 256 && (double)tiles192 / (double)(cdiv(tiles192, 256) * 256) >= g192_eff)
         return launch_g256x192<TO>(a, stream);
     }
   }
   CVMI_CHECK(!a.stats, "conv2d: row_stats is produced by the 256 x 192 GEMM only (plain f16 GEMM, N %% 192 == 0, K >= 1024, >= 256 tiles)");
-  static const int glds_min_tiles = getenv("CVMI_GLDS_MINTILES") ? atoi(getenv("CVMI_GLDS_MINTILES")) : 512;   // tuning experiments only
+  constexpr int glds_min_tiles = 512;
   // (K not a multiple of the 128-byte tile: only from K = 256 elements up -- at K = 144 the padded third tile costs more than the DMA saves)
-  if (use_glds && (a.plain || a.rows2) && a.K % (16 / (int)sizeof(T)) == 0 && (a.Kpad * (int)sizeof(T)) % 128 == 0 && a.K * (int)sizeof(T) >= 256 &&
+  if ((a.plain || a.rows2) && a.K % (16 / (int)sizeof(T)) == 0 && (a.Kpad * (int)sizeof(T)) % 128 == 0 && a.K * (int)sizeof(T) >= 256 &&
       ((a.K * (int)sizeof(T)) % 128 == 0 || a.K >= 256) && N >= (a.rows2 ? 64 : 96) &&
       (long long)cdiv(M, 128) * cdiv(N, 128) >= glds_min_tiles) {                      // large GEMMs only: small grids need the smaller tiles below
-    static const int glds_bn = getenv("CVMI_GLDS_BN") ? atoi(getenv("CVMI_GLDS_BN")) : 0;      // tuning experiments only
-    if constexpr (sizeof(T) == 2 && sizeof(TO) == 4) {
-      if (glds_bn == 192 && N % 192 == 0 && a.plain) return launch_glds<T, TO, 128, 192, 4, 2>(a, stream);
-    }
-    if (use_glds == 2 || N <= 640) return launch_glds<T, TO, 128, 64, 2, 2>(a, stream);      // measured: wins up to N = 576
+    if (N <= 640) return launch_glds<T, TO, 128, 64, 2, 2>(a, stream);      // measured: wins up to N = 576
     return launch_glds<T, TO, 128, 128, 2, 2>(a, stream);
-  }
-  static const char* force_tile = getenv("CVMI_TILE");                         // tuning experiments only: "BMxBN"
-  if (force_tile && strchr(force_tile, (int)120)) {
-    const int bm = atoi(force_tile), bnn = atoi(strchr(force_tile, 'x') + 1);
-    if (bm == 256 && bnn == 32) return launch_cfg<T, TO, 256, 32, 4, 1>(a, stream);
-    if (bm == 128 && bnn == 32) return launch_cfg<T, TO, 128, 32, 4, 1>(a, stream);
-    if (bm == 128 && bnn == 64) return launch_cfg<T, TO, 128, 64, 2, 2>(a, stream);
-    if (bm == 64 && bnn == 64) return launch_cfg<T, TO, 64, 64, 2, 2>(a, stream);
-    if (bm == 128 && bnn == 128) return launch_cfg<T, TO, 128, 128, 2, 2>(a, stream);
-    if (bm == 64 && bnn == 128) return launch_cfg<T, TO, 64, 128, 2, 2>(a, stream);
   }
   // Tile choice: BN covers Cout where it can (each gathered pixel row is then read once); BM
   // shrinks when the grid would not fill 256 CUs x 2.

@@ -1,4 +1,4 @@
-// Token-stationary linear layer for the short-K GEMMs of Hiera (K = C <= 576):
+// Token-stationary linear layer for the short-K GEMMs of Hiera (K = C = 144 and 288; K = 576 is tok_linear16.hip):
 //     y[r, n] = act( sum_k in[r, k] * W[n, k] + b[n] )        in = LayerNorm(x[r, :]) (f32 stream, fused) or an fp16 matrix
 //     out: fp16 [rows, N]   or   f32 residual stream updated in place:  res[r, n] += y[r, n]
 // (sam2 hieradet MultiScaleBlock: `qkv(norm1(x))`, `x = shortcut + proj(attn)`, `mlp.layers[0](norm2(x))` + GELU; behind
@@ -15,7 +15,6 @@
 // MFMAs beside the other in its epilogue VALU, stores and weight prefetch.
 #include "common.hpp"
 #include <type_traits>
-#include <stdlib.h>
 
 namespace {
 
@@ -32,9 +31,6 @@ template <int K> struct TlCfg {
 // LN = 1: `in` is the f32 stream (ld in_ld), normalised with gamma / beta / eps.  LN = 0: `in` is fp16 [rows, in_ld].  LN = 2: f32 rows
 // converted as they are (the neck's lateral convs read the stage outputs of the f32 stream: no cast pass).
 // RES = true: out is f32 (ld out_ld), out[r, n] += y.  RES = false: out is fp16.
-// STAMP: diagnostic build (CVMI_TOKLIN_STAMP=1): wave 0 of workgroup 0 accumulates s_memtime differences of the loop's segments into
-// g_tl_stamp (read by cvmi_debug_stamps).  Never used for timing runs: the stamps serialise what the real kernel overlaps.
-__device__ unsigned long long g_tl_stamp[24];
 
 // Optional extras of a launch.  pool_*: the POOL form's token grid.  stats_in: LN = 1 only -- per-row (mean, rstd) of the LayerNorm, written by the
 // launch that produced the rows (the prologue then reads every row ONCE instead of twice).  stats_out: RES only -- after the in-place update, the
@@ -47,7 +43,7 @@ struct TlExtra {
   int stats_parts;          // 0: stats_in holds (mean, rstd) per row; P > 0: P raw (sum, sum of squares) partials per row (cvmi_conv_desc.row_stats)
 };
 
-template <int K, int LN, bool RES, bool GELU, bool TSTORE, bool STAMP = false, bool PP = false, bool POOL = false>
+template <int K, int LN, bool RES, bool GELU, bool TSTORE, bool POOL = false>
 __global__ __launch_bounds__(TL_NW * 64, 2) void tok_linear_kernel(const void* __restrict__ in, int in_ld, const float* __restrict__ gamma,
                                                                    const float* __restrict__ beta, float eps, const char* __restrict__ wp,
                                                                    void* __restrict__ out, int out_ld, long long rows, int N, const TlExtra ex) {
@@ -270,20 +266,18 @@ __global__ __launch_bounds__(TL_NW * 64, 2) void tok_linear_kernel(const void* _
       }
     }
   };
-  constexpr int PF = K >= 576 ? 6 : 8;          // ring depth (K = 576: the 148 Xn registers leave less room)
+  constexpr int PF = 8;                         // ring depth
   // The K/16 + 1 MFMAs of chunk j.  A-fragment ring: PF ds_read_b128 stay in flight ahead of the MFMA that consumes them.  The reads and
   // their COUNTED waits are inline asm: left to hipcc the same source becomes read -> lgkmcnt(0) -> MFMA (every MFMA then waits a full LDS
   // round trip, and the matrix pipe idles two thirds of the time).  LDS returns data in issue order, so before MFMA f at most
   // min(PF - 1, KS1 - 1 - f) younger reads may still be outstanding; nothing else of the wave may touch LDS inside the sequence, and no
   // run-time branch may sit between a read and its wait (hipcc may copy values that live across a block boundary, in-flight or not).
-  // `head()` runs after the ring's first reads are issued, `mid()` after MFMA KS1 / 2.
-  auto mfma_seq = [&](int j, auto&& head, auto&& mid) -> f32x16 {
+  auto mfma_seq = [&](int j) -> f32x16 {
     const char* const buf = smem + (j % SLOTS) * CHB + lane * 16;
     u32x4 ring[PF];
     const unsigned lbase = (unsigned)(size_t)((const __attribute__((address_space(3))) char*)buf);
 #pragma unroll
     for (int f = 0; f < PF; ++f) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(ring[f]) : "v"(lbase), "i"(f * 1024));
-    head();
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
@@ -303,141 +297,67 @@ __global__ __launch_bounds__(TL_NW * 64, 2) void tok_linear_kernel(const void* _
       const f16x8 a = __builtin_bit_cast(f16x8, ring[f % PF]);
       acc = CVMI_MFMA_32X32X16(a, __builtin_bit_cast(f16x8, xn[f]), acc, 0, 0, 0);
       if (f + PF < KS1) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(ring[f % PF]) : "v"(lbase), "i"((f + PF) * 1024));
-      if (f == KS1 / 2) mid();
     }
     return acc;
   };
-  auto nothing = [] {};
-  unsigned long long seg[6] = {0, 0, 0, 0, 0, 0};
-  auto stamp = [&]() -> unsigned long long {
-    unsigned long long t;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
-    return t;
+  // ---- ping-pong schedule ------------------------------------------------------------------------------------------------------
+  // The two waves of a SIMD (w and w + 4) share its matrix pipe and its VALU issue.  Under one barrier per chunk both run the same
+  // program in phase -- epilogue beside epilogue, MFMAs beside MFMAs -- and a timer-stamped build (r02) showed what that costs: per chunk
+  // 1325 cycles in the 37 MFMAs, 1254 in epilogue + prefetch issue, and 1827 + 655 waiting (the partner's MFMAs): 5061 cycles for 2 x 1184
+  // cycles of matrix work per SIMD.  Here every chunk interval has TWO barriers and the halves run half an interval apart:
+  //     waves 0-3:  b1 | MFMAs(j)                | b2 | prefetch, epilogue(j)     |
+  //     waves 4-7:  b1 | prefetch, epilogue(j-1) | b2 | MFMAs(j)                  |
+  // so a SIMD always holds one wave in its matrix phase beside one in its VALU / memory phase, and the accumulator of a chunk is
+  // consumed by the phase right after it (no copy).  Ring invariants: chunk c is written to slot c % SLOTS after b1 of interval
+  // c - SLOTS + 1 -- the last reads of chunk c - SLOTS (trailing half, second phase of interval c - SLOTS) ended before that barrier
+  // -- and every wave waits for its own pieces (vmcnt(0), explicit: hipcc puts no wait in front of a barrier for LDS-DMA writes) at
+  // the end of its NEXT matrix phase, at least one barrier before b1 of interval c.  That wait also covers the wave's epilogue stores
+  // and residual loads, all issued a full phase earlier.
+  auto bar = [] {
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
   };
-  const unsigned long long t_begin = STAMP ? stamp() : 0ull;
-
-  if constexpr (PP) {
-    // ---- ping-pong schedule ------------------------------------------------------------------------------------------------------
-    // The two waves of a SIMD (w and w + 4) share its matrix pipe and its VALU issue.  Under one barrier per chunk both run the same
-    // program in phase -- epilogue beside epilogue, MFMAs beside MFMAs -- and a stamped build showed what that costs: per chunk 1325
-    // cycles in the 37 MFMAs, 1254 in epilogue + prefetch issue, and 1827 + 655 waiting (the partner's MFMAs): 5061 cycles for 2 x 1184
-    // cycles of matrix work per SIMD.  Here every chunk interval has TWO barriers and the halves run half an interval apart:
-    //     waves 0-3:  b1 | MFMAs(j)                | b2 | prefetch, epilogue(j)     |
-    //     waves 4-7:  b1 | prefetch, epilogue(j-1) | b2 | MFMAs(j)                  |
-    // so a SIMD always holds one wave in its matrix phase beside one in its VALU / memory phase, and the accumulator of a chunk is
-    // consumed by the phase right after it (no copy).  Ring invariants: chunk c is written to slot c % SLOTS after b1 of interval
-    // c - SLOTS + 1 -- the last reads of chunk c - SLOTS (trailing half, second phase of interval c - SLOTS) ended before that barrier
-    // -- and every wave waits for its own pieces (vmcnt(0), explicit: hipcc puts no wait in front of a barrier for LDS-DMA writes) at
-    // the end of its NEXT matrix phase, at least one barrier before b1 of interval c.  That wait also covers the wave's epilogue stores
-    // and residual loads, all issued a full phase earlier.
-    auto bar = [] {
-      asm volatile("" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-    };
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // chunks 0 .. SLOTS - 2
-    f32x16 acc;
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // chunks 0 .. SLOTS - 2
+  f32x16 acc;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    // STAMP: segment sums of wave 0 (leading half) -> g_tl_stamp[0 .. 11], of wave 4 (trailing half) -> [12 .. 23]
-    auto tick = [&](int k, unsigned long long& t) {
-      if constexpr (STAMP) { const unsigned long long n = stamp(); seg[k] += n - t; t = n; }
-    };
-    unsigned long long t = t_begin;
-    if (wv < TL_NW / 2) {
+  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+  if (wv < TL_NW / 2) {
 #pragma unroll 1
-      for (int j = 0; j < nch; ++j) {
-        bar();
-        tick(0, t);
-        if constexpr (RES) res_load(j);
-        acc = mfma_seq(j, nothing, nothing);
-        if constexpr (STAMP) { asm volatile("" : "+v"(acc)); tick(1, t); }
-        asm volatile("s_waitcnt vmcnt(0)" : "+v"(acc) :: "memory");
-        tick(2, t);
-        bar();
-        tick(3, t);
-        if (j + SLOTS - 1 < nch) issue_chunk(j + SLOTS - 1);
-        tick(5, t);
-        epilogue(acc, j);
-        tick(4, t);
-      }
-    } else {
+    for (int j = 0; j < nch; ++j) {
+      bar();
+      if constexpr (RES) res_load(j);
+      acc = mfma_seq(j);
+      asm volatile("s_waitcnt vmcnt(0)" : "+v"(acc) :: "memory");
+      bar();
+      if (j + SLOTS - 1 < nch) issue_chunk(j + SLOTS - 1);
+      epilogue(acc, j);
+    }
+  } else {
 #pragma unroll 1
-      for (int j = 0; j < nch; ++j) {
-        bar();
-        tick(0, t);
-        if (j + SLOTS - 1 < nch) issue_chunk(j + SLOTS - 1);
-        tick(5, t);
-        if (j > 0) epilogue(acc, j - 1);
-        if constexpr (RES) res_load(j);
-        tick(1, t);
-        bar();
-        tick(2, t);
-        acc = mfma_seq(j, nothing, nothing);
-        if constexpr (STAMP) { asm volatile("" : "+v"(acc)); tick(3, t); }
-        asm volatile("s_waitcnt vmcnt(0)" : "+v"(acc) :: "memory");
-        tick(4, t);
-      }
-      epilogue(acc, nch - 1);
+    for (int j = 0; j < nch; ++j) {
+      bar();
+      if (j + SLOTS - 1 < nch) issue_chunk(j + SLOTS - 1);
+      if (j > 0) epilogue(acc, j - 1);
+      if constexpr (RES) res_load(j);
+      bar();
+      acc = mfma_seq(j);
+      asm volatile("s_waitcnt vmcnt(0)" : "+v"(acc) :: "memory");
     }
-    stats_tail();
-    if constexpr (STAMP) {
-      if (blockIdx.x == 0 && (tid == 0 || tid == 256)) {
-        unsigned long long* g = g_tl_stamp + (tid ? 12 : 0);
-        for (int k = 0; k < 6; ++k) g[k] += seg[k];
-        g[6] += stamp() - t_begin; g[7] += (unsigned long long)nch; g[8] += 1;
-      }
-    }
-    return;
+    epilogue(acc, nch - 1);
   }
-
-  f32x16 prev;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) prev[r] = 0.f;
-#pragma unroll 1
-  for (int j = 0; j < nch; ++j) {
-    unsigned long long t0 = 0, t1 = 0, t2 = 0, t3 = 0;
-    if constexpr (STAMP) t0 = stamp();
-    // Every wave waits for its OWN DMA pieces (explicitly: hipcc puts no vmcnt wait in front of a barrier for LDS-DMA writes),
-    // then the barrier publishes chunk j and frees slot (j - 1) % SLOTS.  vmcnt(0) also covers the wave's own stores, which is
-    // why the epilogue of chunk j - 1 is issued AFTER this barrier: its stores then have a whole chunk of MFMAs to complete in.
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if constexpr (STAMP) t1 = stamp();
-    __syncthreads();
-    if constexpr (STAMP) t2 = stamp();
-    if constexpr (RES) { if (j > 0) res_load(j - 1); }
-    if constexpr (!RES && TSTORE) { if (j > 0) epilogue(prev, j - 1); }      // (its LDS round trip ends before the ring's counted waits begin)
-    if (j + SLOTS - 1 < nch) issue_chunk(j + SLOTS - 1);
-    if constexpr (STAMP) t3 = stamp();
-    prev = mfma_seq(
-        j, [&] { if constexpr (!RES && !TSTORE) { if (j > 0) epilogue(prev, j - 1); } },
-        [&] { if constexpr (RES) { if (j > 0) epilogue(prev, j - 1); } });
-    if constexpr (STAMP) {
-      asm volatile("" : "+v"(prev));
-      const unsigned long long t4 = stamp();
-      seg[0] += t1 - t0; seg[1] += t2 - t1; seg[2] += t3 - t2; seg[3] += t4 - t3;
-    }
-  }
-  if constexpr (STAMP) {
-    const unsigned long long t_end = stamp();
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-      g_tl_stamp[0] += seg[0]; g_tl_stamp[1] += seg[1]; g_tl_stamp[2] += seg[2]; g_tl_stamp[3] += seg[3];
-      g_tl_stamp[4] += t_end - t_begin; g_tl_stamp[5] += (unsigned long long)nch; g_tl_stamp[6] += 1;
-    }
-  }
-  if constexpr (RES) res_load(nch - 1);
-  epilogue(prev, nch - 1);
   stats_tail();
+
 }
 
-template <int K, int LN, bool RES, bool GELU, bool TSTORE, bool STAMP = false, bool PP = false, bool POOL = false>
+template <int K, int LN, bool RES, bool GELU, bool TSTORE, bool POOL = false>
 int launch_tl1(const void* in, int in_ld, const float* gamma, const float* beta, float eps, const void* wp, void* out, int out_ld, long long rows,
               int N, hipStream_t s, const TlExtra& ex) {
   using Cfg = TlCfg<K>;
-  static hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&tok_linear_kernel<K, LN, RES, GELU, TSTORE, STAMP, PP, POOL>), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS);
+  static hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&tok_linear_kernel<K, LN, RES, GELU, TSTORE, POOL>), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS);
   CVMI_HIP(attr);
-  cvmi_note_kernel("tok_linear_kernel<%d, %d, %s, %s, %s, %s, %s, %s>", K, LN, CVMI_BOOLNAME(RES), CVMI_BOOLNAME(GELU), CVMI_BOOLNAME(TSTORE), CVMI_BOOLNAME(STAMP), CVMI_BOOLNAME(PP), CVMI_BOOLNAME(POOL));
-  hipLaunchKernelGGL((tok_linear_kernel<K, LN, RES, GELU, TSTORE, STAMP, PP, POOL>), dim3((unsigned)(rows / 256)), dim3(TL_NW * 64), Cfg::LDS, s, in, in_ld, gamma, beta, eps,
+  cvmi_note_kernel("tok_linear_kernel<%d, %d, %s, %s, %s, %s>", K, LN, CVMI_BOOLNAME(RES), CVMI_BOOLNAME(GELU), CVMI_BOOLNAME(TSTORE), CVMI_BOOLNAME(POOL));
+  hipLaunchKernelGGL((tok_linear_kernel<K, LN, RES, GELU, TSTORE, POOL>), dim3((unsigned)(rows / 256)), dim3(TL_NW * 64), Cfg::LDS, s, in, in_ld, gamma, beta, eps,
                      (const char*)wp, out, out_ld, rows, N, ex);
   CVMI_LAUNCH_CHECK();
   return 0;
@@ -446,43 +366,18 @@ int launch_tl1(const void* in, int in_ld, const float* gamma, const float* beta,
 template <int K, int LN, bool RES, bool GELU>
 int launch_tl(const void* in, int in_ld, const float* gamma, const float* beta, float eps, const void* wp, void* out, int out_ld, long long rows,
               int N, hipStream_t s, const TlExtra& ex) {
-  static const int pp = getenv("CVMI_TOKLIN_PP") ? atoi(getenv("CVMI_TOKLIN_PP")) : 1;                 // 0 = one barrier per chunk (A/B measurements)
-  static const int ts = getenv("CVMI_TOKLIN_TSTORE") ? atoi(getenv("CVMI_TOKLIN_TSTORE")) : 1;         // 0 = direct stores (A/B measurements)
-  const bool tstore = !RES && ts && N % 8 == 0 && out_ld % 8 == 0;
-#ifndef CVMI_OPERAND_BF16
-  static const int st = getenv("CVMI_TOKLIN_STAMP") ? atoi(getenv("CVMI_TOKLIN_STAMP")) : 0;           // diagnostic build, never for timing
-  if constexpr (K == 576 && LN == 1 && !RES) {
-    if (st && tstore && (st == 1 || (st == 2) == GELU)) {       // 2: only the GELU launches (fc1), 3: only the plain ones (qkv)
-      if (pp) return launch_tl1<K, LN, RES, GELU, true, true, true>(in, in_ld, gamma, beta, eps, wp, out, out_ld, rows, N, s, ex);
-      return launch_tl1<K, LN, RES, GELU, true, true>(in, in_ld, gamma, beta, eps, wp, out, out_ld, rows, N, s, ex);
-    }
-  }
-#endif
+  // TSTORE: chunks leave through the wave's LDS stage as whole 64-byte row pieces; the residual form and unaligned outputs store directly
   if constexpr (!RES) {
-    if (tstore) {
-      if (pp) return launch_tl1<K, LN, RES, GELU, true, false, true>(in, in_ld, gamma, beta, eps, wp, out, out_ld, rows, N, s, ex);
-      return launch_tl1<K, LN, RES, GELU, true>(in, in_ld, gamma, beta, eps, wp, out, out_ld, rows, N, s, ex);
-    }
+    if (N % 8 == 0 && out_ld % 8 == 0) return launch_tl1<K, LN, RES, GELU, true>(in, in_ld, gamma, beta, eps, wp, out, out_ld, rows, N, s, ex);
   }
-  // The one-barrier schedule runs the RES epilogue in the MIDDLE of the MFMA sequence, where hipcc re-loads a kernel argument (s_load:
-  // the same counter as the ring's counted lgkmcnt waits -- tools/check_ring_asm.py found it): the residual form always takes the ping-pong
-  // schedule, whose epilogue sits outside the ring window.
-  if constexpr (RES) {
-    return launch_tl1<K, LN, RES, GELU, false, false, true>(in, in_ld, gamma, beta, eps, wp, out, out_ld, rows, N, s, ex);
-  } else {
-    if (pp) return launch_tl1<K, LN, RES, GELU, false, false, true>(in, in_ld, gamma, beta, eps, wp, out, out_ld, rows, N, s, ex);
-    return launch_tl1<K, LN, RES, GELU, false>(in, in_ld, gamma, beta, eps, wp, out, out_ld, rows, N, s, ex);
-  }
+  return launch_tl1<K, LN, RES, GELU, false>(in, in_ld, gamma, beta, eps, wp, out, out_ld, rows, N, s, ex);
 }
 
 template <int K>
 int dispatch_tl(int ln, bool res, int act, const void* in, int in_ld, const float* gamma, const float* beta, float eps, const void* wp, void* out,
                 int out_ld, long long rows, int N, hipStream_t s, const TlExtra& ex) {
   const bool gelu = act == CVMI_ACT_GELU;
-  if (ln == 2) {
-    if constexpr (K <= 288) return launch_tl<K, 2, false, false>(in, in_ld, gamma, beta, eps, wp, out, out_ld, rows, N, s, ex);
-    CVMI_FAIL("tok_linear: plain f32 input is built for K = 144 and 288");
-  }
+  if (ln == 2) return launch_tl<K, 2, false, false>(in, in_ld, gamma, beta, eps, wp, out, out_ld, rows, N, s, ex);
   if (res) {
     if (ln) return launch_tl<K, 1, true, false>(in, in_ld, gamma, beta, eps, wp, out, out_ld, rows, N, s, ex);
     return launch_tl<K, 0, true, false>(in, in_ld, gamma, beta, eps, wp, out, out_ld, rows, N, s, ex);
@@ -497,14 +392,11 @@ int dispatch_tl(int ln, bool res, int act, const void* in, int in_ld, const floa
 
 }  // namespace
 
-// K = 576 is served by tok_linear16.hip (16x16x32 MFMA shape, its own packed-weight format) unless CVMI_TOKLIN_M16=0 (A/B runs)
+// K = 576 is served by tok_linear16.hip (16x16x32 MFMA shape, its own packed-weight format)
 int CVMI_ENTRY(cvmi_tok_linear16_launch)(int K, int ln, bool res, bool gelu, const void* in, int in_ld, const float* gamma, const float* beta, float eps,
                                          const void* wp, void* out, int out_ld, long long rows, int N, int pool_w, int pool_hw2, const float* stats_in,
                                          int stats_parts, float* stats_out, float stats_eps, hipStream_t s);
-static int tl_format(int K) {
-  static const int m16 = getenv("CVMI_TOKLIN_M16") ? atoi(getenv("CVMI_TOKLIN_M16")) : 1;
-  return (m16 && K == 576) ? 16 : 32;
-}
+static int tl_format(int K) { return K == 576 ? 16 : 32; }
 
 #ifndef CVMI_OPERAND_BF16
 extern "C" int cvmi_tok_linear_format(int K) { return tl_format(K); }
@@ -513,16 +405,6 @@ extern "C" int cvmi_tok_linear_stats_parts(long long rows, int K, int N) {
   if (rows <= 0 || rows % 256 || N <= 0 || tl_format(K) != 16) return 0;
   const int ns = CVMI_ENTRY(cvmi_tok_linear16_splits)(rows, N);
   return ns > 1 ? ns : 0;
-}
-
-// diagnostic: read and clear the segment sums of the CVMI_TOKLIN_STAMP build.  Ping-pong schedule: [0 .. 8] = wave 0 {b1 wait, MFMAs, vmcnt wait,
-// b2 wait, epilogue, prefetch issue, total, chunks, launches}, [12 .. 20] = wave 4 {b1 wait, epilogue, b2 wait, MFMAs, vmcnt wait, prefetch issue,
-// total, chunks, launches}.  One-barrier schedule (CVMI_TOKLIN_PP=0): [0 .. 6] = {vmcnt wait, barrier, issue, MFMAs, total, chunks, launches}.
-extern "C" int cvmi_debug_stamps(unsigned long long* out24) {
-  CVMI_HIP(hipMemcpyFromSymbol(out24, HIP_SYMBOL(g_tl_stamp), 24 * sizeof(unsigned long long)));
-  unsigned long long z[24] = {};
-  CVMI_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_tl_stamp), z, sizeof(z)));
-  return 0;
 }
 
 extern "C" int cvmi_tok_linear_supported(int K) { return K == 144 || K == 288 || K == 576; }
@@ -572,11 +454,8 @@ extern "C" int CVMI_ENTRY(cvmi_tok_linear_stats)(const void* in, int in_ld, int 
     return CVMI_ENTRY(cvmi_tok_linear16_launch)(K, ln, res, act == CVMI_ACT_GELU, in, in_ld, gamma, beta, eps, w_packed, out, out_ld, rows, N, 0, 0, ln_stats_in,
                                                 ln_stats_in_parts, ln_stats_out, ln_stats_eps, s);
   const TlExtra ex{0, 0, ln_stats_in, ln_stats_out, ln_stats_eps, ln_stats_in_parts};
-  switch (K) {
-    case 144: return dispatch_tl<144>(ln, res, act, in, in_ld, gamma, beta, eps, w_packed, out, out_ld, rows, N, s, ex);
-    case 288: return dispatch_tl<288>(ln, res, act, in, in_ld, gamma, beta, eps, w_packed, out, out_ld, rows, N, s, ex);
-    default: return dispatch_tl<576>(ln, res, act, in, in_ld, gamma, beta, eps, w_packed, out, out_ld, rows, N, s, ex);
-  }
+  if (K == 144) return dispatch_tl<144>(ln, res, act, in, in_ld, gamma, beta, eps, w_packed, out, out_ld, rows, N, s, ex);
+  return dispatch_tl<288>(ln, res, act, in, in_ld, gamma, beta, eps, w_packed, out, out_ld, rows, N, s, ex);
 }
 
 extern "C" int CVMI_ENTRY(cvmi_tok_linear)(const void* in, int in_ld, int in_f32_layernorm, const float* gamma, const float* beta, float eps,
@@ -614,11 +493,9 @@ extern "C" int CVMI_ENTRY(cvmi_tok_linear_pool_stats)(const void* in, int in_ld,
   const int hw2 = (H / 2) * (W / 2);
   if (tl_format(K) == 16)
     return CVMI_ENTRY(cvmi_tok_linear16_launch)(K, 1, false, false, in, in_ld, gamma, beta, eps, w_packed, out, out_ld, rows, N, W, hw2, ln_stats_in, 0, nullptr, 0.f, s);
-  switch (K) {
-    case 144: return launch_tl1<144, 1, false, false, false, false, true, true>(in, in_ld, gamma, beta, eps, w_packed, out, out_ld, rows, N, s, TlExtra{W, hw2, ln_stats_in, nullptr, 0.f, 0});
-    case 288: return launch_tl1<288, 1, false, false, false, false, true, true>(in, in_ld, gamma, beta, eps, w_packed, out, out_ld, rows, N, s, TlExtra{W, hw2, ln_stats_in, nullptr, 0.f, 0});
-    default: return launch_tl1<576, 1, false, false, false, false, true, true>(in, in_ld, gamma, beta, eps, w_packed, out, out_ld, rows, N, s, TlExtra{W, hw2, ln_stats_in, nullptr, 0.f, 0});
-  }
+  const TlExtra ex{W, hw2, ln_stats_in, nullptr, 0.f, 0};
+  if (K == 144) return launch_tl1<144, 1, false, false, false, true>(in, in_ld, gamma, beta, eps, w_packed, out, out_ld, rows, N, s, ex);
+  return launch_tl1<288, 1, false, false, false, true>(in, in_ld, gamma, beta, eps, w_packed, out, out_ld, rows, N, s, ex);
 }
 
 extern "C" int CVMI_ENTRY(cvmi_tok_linear_pool)(const void* in, int in_ld, const float* gamma, const float* beta, float eps, const void* w_packed,

@@ -14,13 +14,9 @@
 //   * C / D: lane (c16, g) holds channels 4 g .. 4 g + 3 (registers) of token c16: residual-stream stores are 64 contiguous bytes per row
 //     (four lanes) instead of 16-byte pieces of 32 rows.
 #include "common.hpp"
-#include <stdlib.h>
 
 // CVMI_TL16_DIAG (compile time, timing-only builds -- tools/r3_call32.sh links them into alternative libraries; results are wrong): bit 0 = no
 // weight DMA behind the first chunks, bit 1 = no MFMAs (the ring reads stay), bit 2 = no epilogue (no GELU, no stores).  0 in the shipped library.
-#ifndef CVMI_TL16_PRIO
-#define CVMI_TL16_PRIO 0               /* A/B builds: 1 = static s_setprio 1 for the younger half (waves 4-7); 2 = s_setprio 1 in every epilogue phase */
-#endif
 #ifndef CVMI_TL16_DIAG
 #define CVMI_TL16_DIAG 0
 #endif
@@ -359,18 +355,14 @@ __global__ __launch_bounds__(TL_NW * 64, 2) void tok_linear16_kernel(const void*
   for (int hh = 0; hh < 2; ++hh)
 #pragma unroll
     for (int tg = 0; tg < 2; ++tg) acc.v[hh][tg] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  if (CVMI_TL16_PRIO == 1 && wv >= TL_NW / 2) __builtin_amdgcn_s_setprio(1);
-  if (CVMI_TL16_PRIO == 4 && wv < TL_NW / 2) __builtin_amdgcn_s_setprio(1);
   if (wv < TL_NW / 2) {
 #pragma unroll 1
     for (int j = j0; j < nch; ++j) {
       bar();
-      if (CVMI_TL16_PRIO == 2) __builtin_amdgcn_s_setprio(0); else if (CVMI_TL16_PRIO == 3) __builtin_amdgcn_s_setprio(1);
       if constexpr (RES) res_load(j);
       acc = mfma_seq(j);
       asm volatile("s_waitcnt vmcnt(0)" : "+v"(acc.v[0][0]), "+v"(acc.v[0][1]), "+v"(acc.v[1][0]), "+v"(acc.v[1][1]) :: "memory");
       bar();
-      if (CVMI_TL16_PRIO == 2) __builtin_amdgcn_s_setprio(1); else if (CVMI_TL16_PRIO == 3) __builtin_amdgcn_s_setprio(0);
       if (!(CVMI_TL16_DIAG & 1) && j + SLOTS - 1 < nch) issue_chunk(j + SLOTS - 1);
       if (!(CVMI_TL16_DIAG & 4)) epilogue(acc, j);
     }
@@ -378,12 +370,10 @@ __global__ __launch_bounds__(TL_NW * 64, 2) void tok_linear16_kernel(const void*
 #pragma unroll 1
     for (int j = j0; j < nch; ++j) {
       bar();
-      if (CVMI_TL16_PRIO == 2) __builtin_amdgcn_s_setprio(1); else if (CVMI_TL16_PRIO == 3) __builtin_amdgcn_s_setprio(0);
       if (!(CVMI_TL16_DIAG & 1) && j + SLOTS - 1 < nch) issue_chunk(j + SLOTS - 1);
       if (!(CVMI_TL16_DIAG & 4) && j > j0) epilogue(acc, j - 1);
       if constexpr (RES) res_load(j);
       bar();
-      if (CVMI_TL16_PRIO == 2) __builtin_amdgcn_s_setprio(0); else if (CVMI_TL16_PRIO == 3) __builtin_amdgcn_s_setprio(1);
       acc = mfma_seq(j);
       asm volatile("s_waitcnt vmcnt(0)" : "+v"(acc.v[0][0]), "+v"(acc.v[0][1]), "+v"(acc.v[1][0]), "+v"(acc.v[1][1]) :: "memory");
     }
@@ -396,10 +386,9 @@ __global__ __launch_bounds__(TL_NW * 64, 2) void tok_linear16_kernel(const void*
 // (fewer than 256 row blocks, a multiple of 8 of them); then the divisor of the chunk count that fills most of one round of 256 CUs.
 // With LayerNorm statistics out (RES form) the slices must be whole, equal chunk ranges (N % 32 == 0).
 int tl16_splits(long long rows, int N, bool stats_out) {
-  static const int on = getenv("CVMI_TL16_SPLIT") ? atoi(getenv("CVMI_TL16_SPLIT")) : 1;      // A/B runs only
   const long long wg = rows / 256;
   const int nch = (N + 31) / 32;
-  if (!on || wg >= 256 || wg % 8 != 0 || (stats_out && N % 32 != 0)) return 1;
+  if (wg >= 256 || wg % 8 != 0 || (stats_out && N % 32 != 0)) return 1;
   int best = 1;
   for (int ns = 2; ns <= 8 && ns <= nch; ++ns)
     if (nch % ns == 0 && wg * ns <= 256) best = ns;            // one round of at most 256 workgroups, as full as the divisors of nch allow

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define CVMI_VERSION 122
+#define CVMI_VERSION 123
 
 typedef void* cvmi_stream_t; /* hipStream_t */
 
@@ -316,13 +316,6 @@ int cvmi_tok_linear_pool(const void* in, int in_ld, const float* gamma, const fl
 /* same, with the rows' LayerNorm statistics supplied (float[2 * B*H*W] of (mean, rstd) pairs, or NULL) */
 int cvmi_tok_linear_pool_stats(const void* in, int in_ld, const float* gamma, const float* beta, float eps, const void* w_packed, void* out,
                                int out_ld, int B, int H, int W, int K, int N, int dtype, const float* ln_stats_in, cvmi_stream_t stream);
-
-/* Diagnostic only (CVMI_TOKLIN_STAMP=1 selects a stamped build of the K = 576 LayerNorm form of cvmi_tok_linear, never for timing
- * runs): reads and clears 24 s_memtime sums (shader cycles) of workgroup 0.  Ping-pong schedule: [0..8] = wave 0 {b1 wait, MFMAs,
- * vmcnt wait, b2 wait, epilogue, prefetch issue, whole kernel, chunks, launches}, [12..20] = wave 4 {b1 wait, epilogue, b2 wait,
- * MFMAs, vmcnt wait, prefetch issue, whole kernel, chunks, launches}.  One-barrier schedule (CVMI_TOKLIN_PP=0): [0..6] = {vmcnt wait,
- * barrier, issue (epilogue + prefetch), MFMAs, whole kernel, chunks, launches}. */
-int cvmi_debug_stamps(unsigned long long* out24);
 
 /* 2x2 / stride 2 max-pool, NHWC (Hiera shortcut path of the q-pooling blocks: do_pool(proj(x))). */
 int cvmi_maxpool2x2(const void* x, int x_ld, void* y, int y_ld, int B, int H, int W, int C, int dtype,

@@ -25,6 +25,29 @@ def attention_families(csrc=CSRC):
     return {re.match(r"\s*(\w+)", s).group(1) for s in re.findall(r'cvmi_note_kernel\(\s*"([^"]*)"', src)}
 
 
+def stray_getenv(sources):
+    """(file, line) of every getenv in {file name: text} other than the two the library keeps: hiera_mlp.hip's per-call read of the
+    CVMI_MLP_PIPE test hook, and reads inside `#ifdef CVMI_MLP_DIAGS` (a timing-only build that never reaches the shipped library)."""
+    hits = []
+    for name, text in sorted(sources.items()):
+        diag_depth = 0                                  # > 0: inside #ifdef CVMI_MLP_DIAGS (counting the #if blocks nested in it)
+        for no, line in enumerate(text.splitlines(), 1):
+            directive = line.strip()
+            if diag_depth:
+                if directive.startswith("#if"):
+                    diag_depth += 1
+                elif directive.startswith("#endif"):
+                    diag_depth -= 1
+                continue
+            if directive == "#ifdef CVMI_MLP_DIAGS":
+                diag_depth = 1
+                continue
+            for m in re.finditer(r"getenv\s*\(([^)]*)\)", line):
+                if not (name == "hiera_mlp.hip" and m.group(1).strip() == '"CVMI_MLP_PIPE"'):
+                    hits.append((name, no))
+    return hits
+
+
 def _test_functions(module):
     tree = ast.parse(open(os.path.join(HERE, module)).read())
     return {n.name: n for n in tree.body if isinstance(n, ast.FunctionDef)}
@@ -83,3 +106,14 @@ def test_matrix_rows_are_well_formed():
             assert r["gh"] % r["win"] == 0 and r["gw"] % r["win"] == 0 and r["Nk"] == r["win"] ** 2, r["id"]
         if r["dtypes"] != ("f32",):
             assert r["dqk"] % 8 == 0 and r["dv"] % 8 == 0 and r["o_pad"] % 8 == 0, r["id"]      # the 16-bit kernels' alignment contract
+
+
+def test_the_native_library_reads_no_tuning_switch():
+    """Dispatch depends on shapes alone: a getenv in the HIP sources would bring back a run-time A/B switch (and the kernel variants only it
+    reaches, shipped untested).  A/B runs load a second build through CVMI_LIB_PATH instead."""
+    sources = {os.path.basename(p): open(p).read() for p in glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.hpp"))}
+    assert "getenv(\"CVMI_MLP_PIPE\")" in sources["hiera_mlp.hip"]          # the scan sees the one allowed read
+    assert stray_getenv(sources) == [], stray_getenv(sources)
+    probe = {"x.hip": 'int a = atoi(getenv("CVMI_X"));\n#ifdef CVMI_MLP_DIAGS\n#if 1\n#endif\ngetenv("D");\n#endif\ngetenv ("Y");\n',
+             "hiera_mlp.hip": 'getenv("CVMI_MLP_PIPE"); getenv("CVMI_MLP_VAR");\n'}
+    assert stray_getenv(probe) == [("hiera_mlp.hip", 1), ("x.hip", 1), ("x.hip", 7)]

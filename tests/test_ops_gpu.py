@@ -474,7 +474,7 @@ def test_attention_global_fp8_av_product(dtype, N):
         op_attention(plan, "t", desc, (qd, kd, vd, od))
         lib.cvmi_last_kernel()
         run(plan)
-        assert lib.cvmi_last_kernel().decode() in (("attn_dma72_kernel<8, true, false>",) if fp8 else ("attn_dma72_kernel<4, false, false>", "attn_dma72_kernel<8, false, false>"))
+        assert lib.cvmi_last_kernel().decode() in (("attn_dma72_kernel<8, true, false>",) if fp8 else ("attn_dma72_kernel<8, false, false>",))
         outs[fp8] = od.float().cpu().view(B, N, Hh, hd).permute(0, 2, 1, 3)
     _check_fp8_av(f"global N = {N}", outs[1], outs[0], ref, emu, dtype, _attn_ref(q, k, v.abs(), scale))
 

@@ -240,7 +240,7 @@ def test_asm_loads_of_the_persistent_fc2_kernel_are_not_touched_before_their_wai
 
 
 def test_asm_mfmas_of_the_pipelined_mlp_loop_keep_their_wait_states():
-    """hiera_mlp_kernel<288, 2, 2> issues its MFMAs from inline asm, where hipcc's hazard recogniser sees nothing: a VALU result needs wait states
+    """hiera_mlp_kernel<288, 2> issues its MFMAs from inline asm, where hipcc's hazard recogniser sees nothing: a VALU result needs wait states
     before an MFMA reads it, an MFMA result before anything else reads it.  The source provides them by construction (`s_nop` statements the operands
     pass through); tools/check_asm_mfma.py verifies on the device assembly of both operand-type builds that hipcc left them intact -- it moved a
     LayerNorm conversion to 0 wait states in front of a consuming block in r04 (wrong results in whole waves).  The checker is exercised on

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Guard for the MFMAs that hiera_mlp_kernel<288, 2, 2> issues from inline asm (the software-pipelined chunk loop).  hipcc's hazard recogniser
+"""Guard for the MFMAs that hiera_mlp_kernel<288, 2> issues from inline asm (the software-pipelined chunk loop).  hipcc's hazard recogniser
 inserts the wait states an MFMA needs around it -- for MFMAs it can see.  Inside an asm statement it sees nothing, so this check reads the device
 assembly of the shipped kernel (both operand-type builds) and fails when
   (a) a VGPR that a VALU instruction wrote is read by an MFMA fewer than MIN_VALU_TO_MFMA wait states later.  Measured r04 on gfx950: a
@@ -22,7 +22,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "circuitvision_amd", "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-KERNEL = "hiera_mlp_kernelILi288ELi2ELi2ELi0"          # <288, VAR 2, SLOTS 2, DIAG 0>
+KERNEL = "hiera_mlp_kernelILi288ELi2ELi0"          # <288, VAR 2, DIAG 0>
 MIN_VALU_TO_MFMA, MIN_MFMA_TO_VALU = 2, 12
 # (source, kernel name fragment, MFMAs expected at least, wait states an MFMA result needs before a non-MFMA read: 32x32x16 = 8 passes -> 12,
 #  16x16x32 = 4 passes -> 8 in what hipcc emits for the builtins)

@@ -54,4 +54,4 @@ N = 20
 for _ in range(N): plan.run_eager()
 plan.stream.synchronize()
 dt_us = (time.perf_counter() - t0) / N * 1e6
-print(f"C={C_} rows={rows} {'bf16' if dt == BF16 else 'f16'} PIPE={os.environ.get('CVMI_MLP_PIPE','-')} VAR={os.environ.get('CVMI_MLP_VAR','-')}: sha {h}  {dt_us:.1f} us/launch  finite={bool(torch.isfinite(xb.t).all())}")
+print(f"C={C_} rows={rows} {'bf16' if dt == BF16 else 'f16'} PIPE={os.environ.get('CVMI_MLP_PIPE','-')}: sha {h}  {dt_us:.1f} us/launch  finite={bool(torch.isfinite(xb.t).all())}")
