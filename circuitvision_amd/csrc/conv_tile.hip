@@ -267,6 +267,7 @@ int launch_tile(TileArgs& a, int B, hipStream_t stream) {
   a.tiles_y = cdiv(a.OH, TH);
   const long long blocks = (long long)B * a.tiles_y * a.tiles_x * a.nb_n;
   CVMI_CHECK(blocks > 0 && blocks < (1ll << 31), "conv_tile: bad grid");
+  cvmi_note_kernel("conv_tile_kernel<%s, %d, %d, %d, %d, %d, %d, %d>", sizeof(T) == 2 ? CVMI_F16NAME : "float", KS, S, CC, BN, WM, WN, TH);
   hipLaunchKernelGGL((conv_tile_kernel<T, KS, S, CC, BN, WM, WN, TH>), dim3((unsigned)blocks), dim3(256), lds, stream, a);
   CVMI_LAUNCH_CHECK();
   return 0;

@@ -4,6 +4,11 @@ ATTN_ROWS: the attention dispatch matrix.  One row = one shape and layout of cvm
 after the launch (attention.hip, cvmi_attention: the dispatcher with default settings).  Kernel names do not carry the operand type, so one
 expected name serves fp16 and bf16.
 
+CONV_ROWS: the convolution / GEMM dispatch matrix.  One row = one cvmi_conv2d descriptor (shape + epilogue options) and the kernel tag
+cvmi_last_kernel() must name (igemm.hip launch_typed / launch_cfg / launch_glds / launch_g256*, conv_tile.hip launch_tile_*).  Tags carry the
+operand type, and the bf16 build has no conv_tile path, so `expect` is a string with a {T} placeholder (the operand type as the tag spells it)
+or a dict per dtype of such strings.
+
 BF16_OPS: every entry point that common.hpp builds twice (CVMI_ENTRY) -> (test module, test function) that checks its bf16 build per op.
 
 Plain data: importing this module needs neither a GPU nor the library."""
@@ -101,10 +106,178 @@ SHARE_ROWS = [
     ("i2t", 1, 32, 8, 4096, 8, 16, "attn64_kernel<32, 32, 8>"),
 ]
 
+ALL3 = ("f16", "bf16", "f32")
+F16_F32 = ("f16", "f32")
+TNAME = {"f16": "_Float16", "bf16": "__bf16", "f32": "float"}          # CVMI_F16NAME / "float" as igemm.hip and conv_tile.hip print them
+
+# (BM, BN, WM, WN) of igemm_kernel as launch_typed passes them to launch_cfg
+T256x32, T128x32, T128x64, T64x64, T128x128, T64x128 = (256, 32, 4, 1), (128, 32, 4, 1), (128, 64, 2, 2), (64, 64, 2, 2), (128, 128, 2, 2), (64, 128, 2, 2)
+
+
+def ig(tile, bkb, plain, ks=1, to="{T}"):
+    """igemm_kernel<T, TO, BM, BN, WM, WN, BKB, PLAIN, KS>"""
+    return "igemm_kernel<{T}, %s, %d, %d, %d, %d, %d, %s, %d>" % ((to,) + tile + (bkb, "true" if plain else "false", ks))
+
+
+def glds(bn, to="{T}"):
+    return "gemm_glds_kernel<{T}, %s, 128, %d, 2, 2>" % (to, bn)
+
+
+def tile(ks, s, cc, bn, th=8):
+    """conv_tile_kernel<T, KS, S, CC, BN, WM, WN, TH>: the four tile forms are 32/8 (4 x 1 waves), 64/4, 64/8 and 128/8 (2 x 2 waves)"""
+    return "conv_tile_kernel<{T}, %d, %d, %d, %d, %d, %d, %d>" % (ks, s, cc, bn, 4 if bn == 32 else 2, 1 if bn == 32 else 2, th)
+
+
+G256, G256_F32 = "gemm256_kernel<{T}, true>", "gemm256_kernel<float, true>"
+G256_I2C, G256_I2C_F32 = "gemm256_kernel<{T}, true, true>", "gemm256_kernel<float, true, true>"
+G256P, G192, G192_F32, G192R = "gemm256p_kernel", "gemm256x192_kernel<{T}>", "gemm256x192_kernel<float>", "gemm256x192r_kernel"
+
+
+def _conv(rid, expect, B, Cin, H, W, Cout, k=1, stride=1, dtypes=F16_BF16, pad=None, out_hw=None, act="none", res="none", res_rep=0,
+          act_after_res=False, shuffle_cout=0, out_f32=False, y_pad=0, scalar_gather=False, up=None, note=""):
+    """One cvmi_conv2d launch on an NHWC [B, H, W, Cin] input (H, W: the logical size, after upsampling).  Cin: an int, or (c0, c1) for two
+    channel-concatenated sources of which source `up` (0 / 1 / None) is stored at half resolution.  B = "cu/2": half the device's CU count
+    (gemm256x192r_kernel needs whole rounds of tiles).  pad None = k // 2.  res: "none" | "full" (one value per output element) | "bcast"
+    (one [OH * OW, Cout] table for every image: res_mod) | "rep" (B / res_rep residual images, image b reads b / res_rep).  out_f32: f32
+    output and residual from 16-bit operands.  y_pad > 0: the output (and a full residual) sit at channel y_pad of a buffer y_pad channels
+    wider on both sides.  act: "none" | "relu" | "silu" | "gelu"."""
+    return dict(id=rid, expect=expect, dtypes=dtypes, B=B, Cin=Cin, up=up, H=H, W=W, Cout=Cout, k=k, stride=stride,
+                pad=k // 2 if pad is None else pad, out_hw=out_hw, act=act, res=res, res_rep=res_rep, act_after_res=act_after_res,
+                shuffle_cout=shuffle_cout, out_f32=out_f32, y_pad=y_pad, scalar_gather=scalar_gather, note=note)
+
+
+def conv_expect(row, dt):
+    """The tag row `row` must report in dtype dt."""
+    e = row["expect"]
+    return (e[dt] if isinstance(e, dict) else e).replace("{T}", TNAME[dt])
+
+
+CONV_ROWS = [
+    # ================= conv_tile_kernel (fp16 and f32 builds; bf16 has no such path and takes igemm_kernel) =================
+    # ---- 3x3 stride 1: CC 32 / 16 / 8, tile forms 32/8, 64/4, 64/8, 128/8
+    _conv("t31_c32_n32", dict(f16=tile(3, 1, 32, 32), f32=tile(3, 1, 32, 32), bf16=ig(T128x32, 64, False)), 2, 32, 9, 21, 32, 3, dtypes=ALL3, act="silu",
+          note="OW = 21: a second tile column with 5 of 16 pixels"),
+    _conv("t31_c32_n64_res", dict(f16=tile(3, 1, 32, 64, 4), f32=tile(3, 1, 16, 64), bf16=ig(T64x64, 64, False)), 2, 32, 17, 13, 64, 3, dtypes=ALL3,
+          act="silu", res="full", note="odd size; f32 cannot hold a 32-channel chunk next to 64 weight rows in LDS: CC = 16"),
+    _conv("t31_c32_4chunks", dict(f16=tile(3, 1, 32, 64, 4), f32=tile(3, 1, 16, 64)), 1, 128, 12, 20, 64, 3, dtypes=F16_F32, act="relu",
+          note="128 channels: the most conv_tile takes at stride 1; 4 (f32: 8) staged chunks"),
+    _conv("t31_c32_n64_th8", dict(f16=tile(3, 1, 32, 64), f32=tile(3, 1, 16, 64)), 65, 32, 16, 32, 64, 3, dtypes=F16_F32, act="silu",
+          note="260 tiles of 8 x 16 > 256: the 8-row form in fp16"),
+    _conv("t31_c16_n24", dict(f16=tile(3, 1, 16, 32), f32=tile(3, 1, 16, 32), bf16=ig(T128x32, 64, False)), 1, 16, 20, 20, 24, 3, dtypes=ALL3,
+          act="silu", y_pad=8),
+    _conv("t31_c16_n128", dict(f16=tile(3, 1, 16, 128), f32=ig(T64x128, 64, False)), 1, 64, 10, 18, 128, 3, dtypes=F16_F32, act="silu", res="full", y_pad=8,
+          note="fp16: 128 weight rows leave no room for CC = 32; f32: no chunk width fits -> igemm_kernel"),
+    _conv("t31_c8_n16", dict(f16=tile(3, 1, 8, 32), f32=tile(3, 1, 8, 32), bf16=ig(T128x32, 64, False)), 3, 8, 9, 7, 16, 3, dtypes=ALL3,
+          note="fp16 CC = 8: two taps per MFMA k-step, the tenth tap is a zero weight"),
+    _conv("t31_c8_n96", tile(3, 1, 8, 128), 1, 24, 12, 20, 96, 3, dtypes=F16_F32, act="relu", res="full", note="3 chunks of 8 channels; N = 96 of a 128 tile"),
+    # ---- 3x3 stride 2
+    _conv("t32_c32_n32", dict(f16=tile(3, 2, 32, 32), f32=tile(3, 2, 16, 32), bf16=ig(T128x32, 64, False)), 1, 32, 20, 24, 32, 3, 2, dtypes=ALL3, act="silu"),
+    _conv("t32_c16_n128", dict(f16=tile(3, 2, 16, 128), f32=ig(T64x128, 64, False), bf16=ig(T64x128, 64, False, 2)), 1, 64, 32, 32, 128, 3, 2, dtypes=ALL3,
+          act="silu", note="64 channels: the most conv_tile takes at stride 2; bf16: 18 K-tiles on a 64 x 128 tile -> 2 K groups"),
+    _conv("t32_c16_n40", dict(f16=tile(3, 2, 16, 64, 4), f32=ig(T64x64, 64, False)), 2, 16, 17, 33, 40, 3, 2, dtypes=F16_F32, act="relu", res="full", y_pad=8,
+          note="odd H and W at stride 2: the last row / column sees 2 of 3 taps; f32: no chunk width fits next to 64 weight rows"),
+    _conv("t32_c8_n48", dict(f16=tile(3, 2, 8, 64, 4), f32=tile(3, 2, 8, 64), bf16=ig(T64x64, 64, False)), 1, 24, 21, 19, 48, 3, 2, dtypes=ALL3, act="silu",
+          note="odd H and W"),
+    # ---- 2x2 stride 1 (pad 1: OH = H + 1)
+    _conv("t21_c32_n32", tile(2, 1, 32, 32), 1, 32, 12, 12, 32, 2, dtypes=F16_F32, act="silu"),
+    _conv("t21_c16_n128", tile(2, 1, 16, 128), 1, 48, 8, 15, 72, 2, dtypes=F16_F32, act="relu", note="N = 72: one vector over 64 -> the 128 tile"),
+    _conv("t21_c8_n56", dict(f16=tile(2, 1, 8, 64, 4), f32=tile(2, 1, 8, 64), bf16=ig(T64x64, 64, False)), 2, 8, 9, 16, 56, 2, dtypes=ALL3, pad=0,
+          note="pad 0: OW = 15; N = 56: one vector under 64"),
+    # ---- just outside conv_tile: igemm_kernel takes over
+    _conv("k1224_ragged_group", dict(f16=ig(T64x128, 64, False, 2), bf16=ig(T64x128, 64, False, 2), f32=ig(T64x128, 64, False)), 1, 136, 19, 21, 72, 3,
+          dtypes=ALL3, act="relu", res="full", note="3x3 s1 over 136 channels; K = 1224 -> 39 K-tiles over 2 groups (20 + 19)"),
+    _conv("s2_72ch", dict(f16=ig(T64x64, 64, False, 2), bf16=ig(T64x64, 64, False, 2), f32=ig(T64x64, 64, False)), 2, 72, 20, 20, 64, 3, 2, dtypes=ALL3,
+          act="silu", note="3x3 s2 over 72 channels; 21 K-tiles: 2 K groups on BN = 64"),
+    _conv("n136_small", ig(T64x128, 64, False), 1, 16, 12, 12, 136, 3, dtypes=ALL3, act="silu", note="N = 136 > 128, one vector over the tile"),
+    _conv("n136_big", ig(T128x128, 64, False), 2, 16, 128, 128, 136, 3, dtypes=ALL3, act="relu", note="the same at M = 32768: 512 tiles of 128 x 128"),
+    _conv("cin12_f32", ig(T128x32, 64, False), 1, 12, 9, 7, 16, 3, dtypes=("f32",), note="12 channels: vectors of 4 but no conv_tile chunk width"),
+    _conv("cin12_scalar", ig(T128x32, 64, False), 1, 12, 9, 7, 16, 3, scalar_gather=True, note="16-bit: per-element gather"),
+    _conv("stem_cin3", ig(T128x32, 64, False), 2, 3, 32, 48, 16, 3, 2, dtypes=ALL3, act="silu", scalar_gather=True, note="K = 27"),
+
+    # ================= igemm_kernel: tiles x (T, TO), BKB, PLAIN, KS =================
+    # ---- N <= 32
+    _conv("n32_m256", dict(f16=ig(T256x32, 128, True), bf16=ig(T256x32, 128, True), f32=ig(T256x32, 64, True)), 1, 16, 3, 43691, 32, dtypes=ALL3, act="silu",
+          note="M = 131073: one row in the last 256-row tile"),
+    _conv("n32_m256_f32out", ig(T256x32, 128, True, to="float"), 8, 16, 128, 130, 24, res="full", out_f32=True, y_pad=4),
+    _conv("n32_m129", dict(f16=ig(T128x32, 128, True), bf16=ig(T128x32, 128, True), f32=ig(T128x32, 64, True)), 1, 16, 3, 43, 32, dtypes=ALL3, act="silu",
+          res="full", note="M = 129"),
+    _conv("n32_m127_f32out", ig(T128x32, 64, True, to="float"), 1, 72, 1, 127, 28, act="gelu", res="bcast", out_f32=True, note="M = 127; N one f32 vector under 32"),
+    # ---- N <= 64
+    _conv("n64_m128", dict(f16=ig(T128x64, 128, True), bf16=ig(T128x64, 128, True), f32=ig(T128x64, 64, True)), 8, 64, 100, 90, 64, dtypes=ALL3, act="silu"),
+    _conv("n64_m128_f32out", ig(T128x64, 128, True, to="float"), 8, 64, 100, 90, 60, act="relu", res="full", out_f32=True, y_pad=4, note="N = 60: one f32 vector under 64"),
+    _conv("n62_logits", ig(T64x64, 64, True), 1, 128, 40, 40, 62, dtypes=ALL3, note="ragged Cout: element-wise channel tail"),
+    _conv("n48_k64", dict(f16=ig(T64x64, 128, True), bf16=ig(T64x64, 128, True), f32=ig(T64x64, 64, True)), 1, 64, 5, 13, 48, dtypes=ALL3, act="relu", res="full",
+          note="M = 65; K is exactly one 128-byte tile in 16 bits"),
+    _conv("n64_f32out", ig(T64x64, 64, True, to="float"), 1, 96, 7, 9, 64, res="full", out_f32=True, note="M = 63"),
+    # ---- 16-bit in, f32 out, N <= 192: 128 x 64 tiles
+    _conv("f32out_n96", ig(T128x64, 128, True, to="float"), 2, 64, 8, 8, 96, res="full", out_f32=True),
+    _conv("patch_embed", dict(f16=ig(T128x64, 64, False, to="float"), bf16=ig(T128x64, 64, False, to="float"), f32=ig(T64x128, 64, False)), 2, 48, 16, 16, 144, 2,
+          dtypes=ALL3, pad=1, out_hw=(16, 16), res="bcast", out_f32=True, note="Hiera patch embedding: 2x2 over space-to-depth, out_hw crops the 17th row / column"),
+    # ---- N > 64
+    _conv("n160_big", dict(f16=ig(T128x128, 128, True), bf16=ig(T128x128, 128, True), f32=glds(64)), 8, 64, 100, 90, 160, dtypes=ALL3, act="silu",
+          note="K = 64: too short for gemm_glds_kernel in 16 bits"),
+    _conv("n72_deep_k", ig(T128x128, 128, True), 16, 1024, 64, 64, 72, dtypes=ALL3, act="relu", note="N < 96 keeps a deep plain GEMM on igemm_kernel; 128-byte K-tiles"),
+    _conv("n200_f32out_big", ig(T128x128, 128, True, to="float"), 8, 64, 64, 64, 200, res="full", out_f32=True, y_pad=4),
+    _conv("n200_f32out_small", ig(T64x128, 64, True, to="float"), 2, 96, 12, 10, 200, act="gelu", res="full", out_f32=True),
+    _conv("n432_small", dict(f16=ig(T64x128, 64, True), bf16=ig(T64x128, 64, True), f32=ig(T64x128, 64, True)), 1, 144, 16, 16, 432, dtypes=ALL3, act="gelu",
+          note="Hiera-like linear: 4 column tiles, the last one 48 wide"),
+    # ---- split-K (16-bit, 64-row tiles)
+    _conv("ks4_3x3", dict(f16=ig(T64x64, 64, False, 4), bf16=ig(T64x64, 64, False, 4), f32=ig(T64x64, 64, False)), 2, 256, 20, 20, 64, 3, dtypes=ALL3, act="silu",
+          note="Detect cv2: 72 K-tiles"),
+    _conv("ks4_plain", dict(f16=ig(T64x64, 64, True, 4), bf16=ig(T64x64, 64, True, 4), f32=ig(T64x64, 128, True)), 1, 1096, 10, 10, 40, dtypes=ALL3,
+          note="35 K-tiles over 4 groups (9, 9, 9, 8)"),
+    _conv("ks2_plain_n64", ig(T64x64, 64, True, 2), 1, 384, 10, 10, 48, act="silu", res="full", y_pad=8),
+    _conv("ks2_plain_n128", dict(f16=ig(T64x128, 64, True, 2), bf16=ig(T64x128, 64, True, 2), f32=ig(T64x128, 64, True)), 3, 384, 20, 20, 128, dtypes=ALL3, act="silu"),
+    _conv("ks2_two_sources", ig(T64x128, 64, False, 2), 2, (256, 128), 20, 20, 128, 3, up=0, act="silu", note="upsampled + skip, deep K: the gather restarts per group"),
+    # ---- two sources
+    _conv("two_src_generic", ig(T64x64, 64, False), 2, (32, 16), 12, 10, 40, dtypes=ALL3, up=0, act="silu", y_pad=16),
+    _conv("rows2_up_first", ig(T64x128, 64, False), 3, (128, 64), 18, 22, 96, dtypes=ALL3, up=0, act="silu", note="two-row-pointer gather below 512 tiles"),
+    _conv("rows2_up_second", ig(T64x128, 64, False), 3, (64, 128), 18, 22, 96, dtypes=ALL3, up=1, act="silu"),
+    # ---- epilogue options on igemm_kernel
+    _conv("ig_bcast", ig(T64x128, 64, True), 3, 256, 8, 8, 256, dtypes=ALL3, res="bcast", note="the decoder's positional tables"),
+    _conv("ig_rep_mod", dict(f16=ig(T64x128, 128, True), bf16=ig(T64x128, 128, True), f32=ig(T64x128, 64, True)), 6, 64, 6, 5, 72, dtypes=ALL3, res="rep", res_rep=3, note="res_rep with res_mod = OH * OW"),
+    _conv("ig_shuffle_rep_aar", dict(f16=ig(T64x128, 128, True), bf16=ig(T64x128, 128, True), f32=ig(T64x128, 64, True)), 6, 64, 6, 5, 128, dtypes=ALL3, act="gelu", res="rep", res_rep=3, act_after_res=True, shuffle_cout=32, y_pad=8,
+          note="ConvTranspose 2x2 / s2 scatter + the skip feature shared by 3 prompts + GELU after it"),
+    _conv("ig_aar", dict(f16=ig(T64x64, 128, True), bf16=ig(T64x64, 128, True), f32=ig(T64x64, 64, True)), 2, 32, 9, 7, 40, dtypes=ALL3, act="relu", res="full", act_after_res=True),
+
+    # ================= gemm_glds_kernel: >= 512 tiles, K in whole 128-byte tiles (or >= 256) =================
+    _conv("glds64", glds(64), 16, 128, 64, 64, 96, dtypes=ALL3, act="silu"),
+    _conv("glds64_f32out", glds(64, to="float"), 16, 128, 64, 64, 100, act="relu", res="full", out_f32=True, y_pad=4, note="N = 100: one f32 vector over 96"),
+    _conv("glds128_n648", glds(128), 1, 128, 27, 403, 648, dtypes=ALL3, act="gelu", note="M = 10881 = 85 x 128 + 1; N = 5 x 128 + 8"),
+    _conv("glds128_f32out", glds(128, to="float"), 1, 128, 27, 403, 644, res="bcast", out_f32=True),
+    _conv("glds64_ragged_k", glds(64), 16, 264, 64, 64, 96, act="relu", res="full", y_pad=8, note="K = 264: K % 64 = 8"),
+    _conv("glds64_bcast", glds(64), 16, 128, 64, 64, 120, res="bcast", note="N = 120: one vector under 128"),
+    _conv("glds64_shuffle_rep_aar", glds(64), 8, 128, 64, 64, 256, act="gelu", res="rep", res_rep=4, act_after_res=True, shuffle_cout=64, y_pad=8,
+          note="the decoder's transposed conv at B = 2 images x 4 prompts"),
+    _conv("glds_rows2_up_first", glds(64), 4, (64, 64), 128, 128, 96, up=0, act="silu"),
+    _conv("glds_rows2_up_second", glds(64), 4, (64, 64), 128, 128, 96, up=1, act="silu", res="full"),
+    # ---- one condition short of the 256-row kernels
+    _conv("g256_255_tiles", glds(64), 255, 128, 16, 16, 256, act="silu", note="255 tiles of 256 x 256"),
+    _conv("g256_col_eff", glds(64), 128, 128, 16, 16, 408, res="full", note="N = 408: 79.7 % of two 256-column tiles"),
+    _conv("g192_k960", glds(64), 128, 960, 16, 16, 384, act="gelu", note="K = 960 < 1024"),
+    _conv("g256_k64", ig(T128x128, 128, True), 256, 64, 16, 16, 256, act="silu", note="K = 64 < 128"),
+
+    # ================= the 256-row DMA kernels (16-bit operands) =================
+    _conv("g256_res", G256, 256, 128, 16, 16, 256, act="silu", res="full", y_pad=8, note="a residual keeps it off the persistent form"),
+    _conv("g256_bcast_aar", G256, 256, 128, 16, 16, 256, act="relu", res="bcast", act_after_res=True),
+    _conv("g256_f32out", G256_F32, 256, 128, 16, 16, 256, res="full", out_f32=True, y_pad=4),
+    _conv("g256p", G256P, 256, 128, 16, 16, 256, act="gelu"),
+    _conv("g256p_ypad_ragged", G256P, 256, 192, 16, 16, 440, act="silu", y_pad=8, note="512 tiles over 256 workgroups; N = 440 of 512; 3 K-tiles"),
+    _conv("i2c", G256_I2C, 2, 64, 128, 128, 256, 3, act="silu", note="128 tiles, one K-tile per tap"),
+    _conv("i2c_s2_odd_res", G256_I2C, 2, 64, 255, 257, 256, 3, 2, act="relu", res="full", y_pad=8, note="stride 2 on odd sizes"),
+    _conv("i2c_f32out", G256_I2C_F32, 2, 64, 128, 128, 256, 3, res="full", out_f32=True),
+    _conv("i2c_127_tiles", ig(T64x128, 64, False), 2, 64, 127, 128, 256, 3, act="silu", note="127 tiles: one short; 508 tiles of 128 x 128 -> 64-row tiles"),
+    _conv("g192_16", G192, 128, 1024, 16, 16, 384, act="gelu", y_pad=8),
+    _conv("g192_16_res_bcast", G192, 128, 1024, 16, 16, 384, res="bcast"),
+    _conv("g192_f32_act", G192_F32, 128, 2304, 16, 16, 384, act="relu", res="full", out_f32=True, note="gemm256x192r's shape with an activation"),
+    _conv("g192_f32_bcast", G192_F32, 128, 1024, 16, 16, 384, res="bcast", out_f32=True),
+    _conv("g192r", G192R, "cu/2", 2304, 16, 16, 384, res="full", out_f32=True, y_pad=4, note="CU-count tiles of 256 x 192: whole rounds; skipped unless CUs % 8 == 0"),
+]
+
 # dual-built entry point -> (test module, test function) that checks its bf16 build op by op
 BF16_OPS = {
     "cvmi_attention": ("test_attention_matrix_gpu.py", "test_attention_matrix"),
-    "cvmi_conv2d": ("test_bf16_ops_gpu.py", "test_conv2d_bf16"),
+    "cvmi_conv2d": ("test_conv_matrix_gpu.py", "test_conv_matrix"),            # (tests/test_bf16_ops_gpu.py test_conv2d_bf16* remain beside it)
     "cvmi_layernorm": ("test_bf16_ops_gpu.py", "test_layernorm_bf16"),
     "cvmi_layernorm_dual": ("test_bf16_ops_gpu.py", "test_layernorm_dual_bf16_copy"),
     "cvmi_maxpool2x2": ("test_bf16_ops_gpu.py", "test_maxpool_and_space_to_depth_bf16"),

@@ -1,11 +1,12 @@
 """CPU guard on the per-op GPU coverage (tests/op_matrix.py): every dual-built entry point has a bf16 test, every attention kernel family the
-dispatcher can launch has a row in the dispatch matrix.  Adding an entry point or a kernel without its per-op test fails here, on any checkout."""
+dispatcher can launch has a row in the dispatch matrix, and so has every kernel family and template instance of cvmi_conv2d's dispatcher
+(CONV_ROWS).  Adding an entry point or a kernel without its per-op test fails here, on any checkout."""
 import ast
 import glob
 import os
 import re
 
-from op_matrix import ATTN_ROWS, BF16_OPS, SHARE_ROWS
+from op_matrix import ATTN_ROWS, BF16_OPS, CONV_ROWS, SHARE_ROWS, TNAME, conv_expect
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(os.path.dirname(HERE), "circuitvision_amd", "csrc")
@@ -64,7 +65,7 @@ def missing_bf16_tests(entries, table=BF16_OPS):
         funcs = _test_functions(module)
         if fn not in funcs:
             out.append((e, f"{module} has no function {fn}"))
-        elif module not in ("test_bf16_ops_gpu.py", "test_attention_matrix_gpu.py") and "BF16" not in ast.get_source_segment(open(os.path.join(HERE, module)).read(), funcs[fn]) \
+        elif module not in ("test_bf16_ops_gpu.py", "test_attention_matrix_gpu.py", "test_conv_matrix_gpu.py") and "BF16" not in ast.get_source_segment(open(os.path.join(HERE, module)).read(), funcs[fn]) \
                 and not any("BF16" in ast.unparse(d) for d in funcs[fn].decorator_list):
             out.append((e, f"{module}::{fn} does not run BF16"))
     return out
@@ -106,6 +107,128 @@ def test_matrix_rows_are_well_formed():
             assert r["gh"] % r["win"] == 0 and r["gw"] % r["win"] == 0 and r["Nk"] == r["win"] ** 2, r["id"]
         if r["dtypes"] != ("f32",):
             assert r["dqk"] % 8 == 0 and r["dv"] % 8 == 0 and r["o_pad"] % 8 == 0, r["id"]      # the 16-bit kernels' alignment contract
+
+
+CONV_SOURCES = ("igemm.hip", "conv_tile.hip")
+CONV_FAMILIES = {"conv_tile_kernel", "igemm_kernel", "gemm_glds_kernel", "gemm256_kernel", "gemm256p_kernel", "gemm256x192_kernel", "gemm256x192r_kernel"}
+
+
+def conv_sources(csrc=CSRC):
+    return {name: open(os.path.join(csrc, name)).read() for name in CONV_SOURCES}
+
+
+def conv_families(sources):
+    """Kernel families cvmi_conv2d's dispatcher tags before a launch: the identifier that opens each cvmi_note_kernel("...") format (a launch
+    that picks one of two formats with ?: tags the same family either way)."""
+    return {re.match(r"\s*(\w+)", s).group(1) for text in sources.values() for s in re.findall(r'cvmi_note_kernel\(\s*(?:\w+\s*\?\s*)?"([^"]*)"', text)}
+
+
+def conv_instances(sources):
+    """Template instances the dispatcher can pick, from its call sites: {("igemm_kernel" | "gemm_glds_kernel" | "conv_tile_kernel", (ints))} --
+    launch_cfg<T, TO, BM, BN, WM, WN>, launch_glds<T, TO, BM, BN, WM, WN> and launch_tile<T, KS, S, CC, BN, WM, WN, TH> (the last four: the tile form)."""
+    text = "\n".join(sources.values())
+    ints = lambda s: tuple(int(v) for v in s.split(","))
+    out = {("igemm_kernel", ints(m)) for m in re.findall(r"launch_cfg<T, TO, ([\d, ]+)>\(", text)}
+    out |= {("gemm_glds_kernel", ints(m)) for m in re.findall(r"launch_glds<T, TO, ([\d, ]+)>\(", text)}
+    out |= {("conv_tile_kernel", ints(m)) for m in re.findall(r"launch_tile<T, KS, S, CC, ([\d, ]+)>\(", text)}
+    return out
+
+
+def _tag_args(tag):
+    fam = re.match(r"(\w+)", tag).group(1)
+    return fam, [a.strip() for a in tag[len(fam):].strip("<>").split(",")] if "<" in tag else []
+
+
+def _pair(args):
+    """(T, TO) of a tag as "16,16" | "16,float" | "float,float"."""
+    return ",".join("float" if a == "float" else "16" for a in args[:2])
+
+
+def conv_gaps(sources, rows=CONV_ROWS):
+    """What the dispatch matrix leaves uncovered, as a list of strings (empty = complete)."""
+    tags = {conv_expect(r, dt) for r in rows for dt in r["dtypes"]}
+    parsed = [_tag_args(t) for t in tags]
+    gaps = []
+    fams, covered = conv_families(sources), {f for f, _ in parsed}
+    gaps += [f"kernel family {f} has no row" for f in sorted(fams - covered)]
+    gaps += [f"rows expect {f}, which the sources no longer tag" for f in sorted(covered - fams)]
+    for fam, tup in sorted(conv_instances(sources)):
+        want = [str(v) for v in tup]
+        if fam == "conv_tile_kernel":                                       # the tile form, in fp16 and (all but the fp16-only 4-row form) in f32
+            for T in ("_Float16",) + (("float",) if tup[3] != 4 else ()):
+                if not any(f == fam and a[0] == T and a[4:8] == want for f, a in parsed):
+                    gaps.append(f"conv_tile_kernel<{T}, .., {', '.join(want)}> has no row")
+        else:                                                               # (BM, BN, WM, WN) in each (T, TO) pair
+            for pair in ("16,16", "16,float", "float,float"):
+                if not any(f == fam and a[2:6] == want and _pair(a) == pair for f, a in parsed):
+                    gaps.append(f"{fam}<{pair}, {', '.join(want)}> has no row")
+    ig = [a for f, a in parsed if f == "igemm_kernel"]
+    gaps += [f"igemm_kernel BKB = {v} has no row" for v in ("64", "128") if not any(a[6] == v for a in ig)]
+    gaps += [f"igemm_kernel PLAIN = {v} has no row" for v in ("true", "false") if not any(a[7] == v for a in ig)]
+    gaps += [f"igemm_kernel KS = {v} has no row" for v in ("1", "2", "4") if not any(a[8] == v for a in ig)]
+    gaps += [f"igemm_kernel KS = {ks} on BN = {bn} has no row" for ks, bn in (("4", "64"), ("2", "64"), ("2", "128")) if not any(a[8] == ks and a[3] == bn for a in ig)]
+    ct = [a for f, a in parsed if f == "conv_tile_kernel"]
+    for ks_s in (("3", "1"), ("3", "2"), ("2", "1")):
+        for cc in ("32", "16", "8"):
+            if not any(a[0] == "_Float16" and tuple(a[1:3]) == ks_s and a[3] == cc for a in ct):
+                gaps.append(f"conv_tile_kernel<_Float16, {ks_s[0]}, {ks_s[1]}, {cc}, ..> has no row")
+    gaps += [f"conv_tile_kernel<float, .., CC = {cc}> has no row" for cc in ("32", "16", "8") if not any(a[0] == "float" and a[3] == cc for a in ct)]
+    for t in ("gemm256_kernel<{T}, true>", "gemm256_kernel<{T}, true, true>", "gemm256x192_kernel<{T}>"):
+        for T in ("_Float16", "__bf16", "float"):
+            if t.replace("{T}", T) not in tags:
+                gaps.append(f"{t.replace('{T}', T)} has no row")
+    return gaps
+
+
+def test_every_conv_kernel_family_and_instance_is_in_the_dispatch_matrix():
+    src = conv_sources()
+    assert conv_families(src) == CONV_FAMILIES, conv_families(src)                 # the parser still finds the seven tagged families
+    inst = conv_instances(src)
+    assert len([i for i in inst if i[0] == "igemm_kernel"]) == 6 and len([i for i in inst if i[0] == "gemm_glds_kernel"]) == 2 and \
+        len([i for i in inst if i[0] == "conv_tile_kernel"]) == 4, sorted(inst)      # ... and the call sites
+    assert conv_gaps(src) == [], conv_gaps(src)
+
+
+def test_a_new_conv_instance_or_a_removed_row_is_caught():
+    src = conv_sources()
+    probe = dict(src)
+    probe["igemm.hip"] += "\n  if (N <= 16) return launch_cfg<T, TO, 32, 32, 1, 1>(a, stream);\n"
+    assert conv_gaps(probe) == [f"igemm_kernel<{p}, 32, 32, 1, 1> has no row" for p in ("16,16", "16,float", "float,float")]
+    probe = dict(src)
+    probe["conv_tile.hip"] = probe["conv_tile.hip"].replace("cvmi_note_kernel(", "note_off(")
+    assert "rows expect conv_tile_kernel, which the sources no longer tag" in conv_gaps(probe)
+    assert conv_gaps(src, [r for r in CONV_ROWS if r["id"] != "n32_m256"]) == ["igemm_kernel<16,16, 256, 32, 4, 1> has no row", "igemm_kernel<float,float, 256, 32, 4, 1> has no row"]
+    assert conv_gaps(src, [r for r in CONV_ROWS if r["id"] != "t31_c32_n64_th8"]) == ["conv_tile_kernel<_Float16, .., 64, 2, 2, 8> has no row"]
+    assert conv_gaps(src, [r for r in CONV_ROWS if r["id"] != "g192r"]) == ["kernel family gemm256x192r_kernel has no row"]
+    assert "igemm_kernel KS = 4 has no row" in conv_gaps(src, [r for r in CONV_ROWS if not r["id"].startswith("ks4")])
+
+
+def test_conv_matrix_rows_are_well_formed():
+    ids = [r["id"] for r in CONV_ROWS]
+    assert len(ids) == len(set(ids)), "duplicate row ids"
+    for r in CONV_ROWS:
+        rid = r["id"]
+        assert r["dtypes"] and set(r["dtypes"]) <= set(TNAME), rid
+        assert not isinstance(r["expect"], dict) or set(r["expect"]) == set(r["dtypes"]), rid
+        cins = r["Cin"] if isinstance(r["Cin"], tuple) else (r["Cin"],)
+        for dt in r["dtypes"]:
+            tag = conv_expect(r, dt)
+            assert "{" not in tag and _tag_args(tag)[0] in CONV_FAMILIES, (rid, tag)
+            assert dt != "bf16" or not tag.startswith("conv_tile_kernel"), f"{rid}: the bf16 build has no conv_tile path"
+            assert r["scalar_gather"] or all(c % (4 if dt == "f32" else 8) == 0 for c in cins), f"{rid}: channels not in 16-byte vectors"
+            ovec = 4 if (dt == "f32" or r["out_f32"]) else 8
+            assert r["y_pad"] % ovec == 0, f"{rid}: y_pad breaks the output's 16-byte alignment"
+            assert not r["shuffle_cout"] or r["shuffle_cout"] % ovec == 0, rid
+        assert r["act"] in ("none", "relu", "silu", "gelu") and r["res"] in ("none", "full", "bcast", "rep"), rid
+        assert (r["up"] is None) if len(cins) == 1 else (r["up"] in (None, 0, 1)), rid
+        assert r["up"] is None or (r["H"] % 2 == 0 and r["W"] % 2 == 0), rid
+        if r["shuffle_cout"]:
+            assert r["k"] == 1 and r["stride"] == 1 and r["pad"] == 0 and r["Cout"] == 4 * r["shuffle_cout"] and r["res"] != "bcast", rid
+        assert (r["res"] == "rep") == (r["res_rep"] > 1), rid
+        if r["res"] == "rep":
+            assert isinstance(r["B"], int) and r["B"] % r["res_rep"] == 0, rid
+        assert r["B"] == "cu/2" or (isinstance(r["B"], int) and r["B"] > 0), rid
+        assert not r["out_f32"] or "f32" not in r["dtypes"] or isinstance(r["expect"], dict), rid
 
 
 def test_the_native_library_reads_no_tuning_switch():
