@@ -57,6 +57,27 @@ template <> struct Mma<float> {
   }
 };
 
+// Workgroup index -> tile index: the hardware deals workgroups round-robin over the 8 XCDs; XCD x gets a contiguous run of tiles
+__device__ __forceinline__ int xcd_remap(int wg, int nwg) {
+  const int q = nwg >> 3, r = nwg & 7, xcd = wg & 7, j = wg >> 3;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
+}
+
+// Accumulator clears.  clear_acc serves arrays of f32x4 (16x16x32 accumulators, residual batches); the f32x16 accumulators
+// acc[NI][NJ] of the 32x32 kernels keep the element-wise form as a macro: hipcc assigns their registers differently when the
+// zero arrives as a whole vector, and these kernels' device code is pinned
+#define CLEAR_ACC32(acc, NI, NJ) \
+  _Pragma("unroll") for (int i = 0; i < NI; ++i) \
+  _Pragma("unroll") for (int j = 0; j < NJ; ++j) \
+  _Pragma("unroll") for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f
+template <typename V>
+__device__ __forceinline__ void clear_acc(V& v) { v = V{}; }
+template <typename V, int N>
+__device__ __forceinline__ void clear_acc(V (&a)[N]) {
+#pragma unroll
+  for (int i = 0; i < N; ++i) clear_acc(a[i]);
+}
+
 // Returns the RAW 16 bytes at a clamped (always valid) address and sets `ok`; the caller zeroes !ok chunks when it
 // writes the tile to LDS, i.e. after the MFMAs of the current tile -- a select next to the load would make the
 // compiler wait for the load before the compute it is supposed to overlap.
@@ -118,6 +139,18 @@ __device__ __forceinline__ size_t res_row(const ConvKArgs& p, int m) {
   return (size_t)(m / p.res_mod / p.res_rep) * (size_t)p.res_mod + (size_t)r;
 }
 
+// four consecutive channels of one pixel -> their place in an epilogue's LDS tile, in the output type
+template <typename TO>
+__device__ __forceinline__ void tile_put4(char* d, const float (&v)[4]) {
+  if constexpr (sizeof(TO) == 2) {
+    f16x4 hv = {(f16)v[0], (f16)v[1], (f16)v[2], (f16)v[3]};
+    *reinterpret_cast<f16x4*>(d) = hv;
+  } else {
+    f32x4 fv = {v[0], v[1], v[2], v[3]};
+    *reinterpret_cast<f32x4*>(d) = fv;
+  }
+}
+
 // ---- shared epilogue: bias + act in registers -> LDS tile [BM][BN] (TO) -> coalesced 16-byte stores (+ residual,
 //      batch-broadcast residual, activation-after-residual, ConvTranspose scatter) -----------------------------------
 template <typename T, typename TO, int BM, int BN, int WM, int WN, int KS = 1>
@@ -168,14 +201,7 @@ __device__ __forceinline__ void gemm_epilogue(const ConvKArgs& p, f32x16 (&acc)[
           float v[4];
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] = actf(acc[i][j][4 * q + e] + bv[e]);
-          char* dst = Ct + ml * CROWB + nl * OES;
-          if constexpr (OES == 2) {
-            f16x4 hv = {(f16)v[0], (f16)v[1], (f16)v[2], (f16)v[3]};
-            *reinterpret_cast<f16x4*>(dst) = hv;
-          } else {
-            f32x4 fv = {v[0], v[1], v[2], v[3]};
-            *reinterpret_cast<f32x4*>(dst) = fv;
-          }
+          tile_put4<TO>(Ct + ml * CROWB + nl * OES, v);
         }
       }
     }
@@ -284,11 +310,7 @@ __global__ __launch_bounds__(WM * WN * 64 * KS, (KS > 1 ? 4 : WM * WN == 8 ? 4 :
   // XCD-aware tile order: workgroups are dealt round-robin over the 8 XCDs (private L2 each), so give every XCD a
   // CONTIGUOUS run of tiles -- the nb_n column tiles that share one pixel/row tile then hit the same L2 instead of
   // each XCD fetching that A tile again from the Infinity Cache (bijective for any grid size; speed only).
-  int wg = blockIdx.x;
-  {
-    const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = wg & 7, j = wg >> 3;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-  }
+  const int wg = xcd_remap(blockIdx.x, gridDim.x);
   const int bn = wg % p.nb_n, bm = wg / p.nb_n;
   const int m0 = bm * BM, n0 = bn * BN;
 
@@ -401,12 +423,7 @@ __global__ __launch_bounds__(WM * WN * 64 * KS, (KS > 1 ? 4 : WM * WN == 8 ? 4 :
   const int lr = lane & 31, lh = lane >> 5;
 
   f32x16 acc[TN][TM];
-#pragma unroll
-  for (int i = 0; i < TN; ++i)
-#pragma unroll
-    for (int j = 0; j < TM; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  CLEAR_ACC32(acc, TN, TM);
 
   auto compute = [&](int buf) {
     const char* Ab = As + (buf * BM + wm * WTM + lr) * ROWB + lh * 16;
@@ -516,11 +533,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_glds_kernel(const ConvKA
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
   const int tid = threadIdx.x;
-  int wg = blockIdx.x;
-  {
-    const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = wg & 7, j = wg >> 3;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-  }
+  const int wg = xcd_remap(blockIdx.x, gridDim.x);
   const int bn = wg % p.nb_n, bm = wg / p.nb_n;
   const int m0 = bm * BM, n0 = bn * BN;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
@@ -571,12 +584,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_glds_kernel(const ConvKA
   };
 
   f32x16 acc[TN][TM];
-#pragma unroll
-  for (int i = 0; i < TN; ++i)
-#pragma unroll
-    for (int j = 0; j < TM; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  CLEAR_ACC32(acc, TN, TM);
 
   // fragment addresses: row r of a 32-row group, swizzled slot per k-step
   int a_off[TM], w_off[TN], a_sw[TM], w_sw[TN];
@@ -629,25 +637,185 @@ int launch_glds(ConvKArgs& a, hipStream_t stream) {
   return 0;
 }
 
-// ---- 256 x 256 tile GEMM: 8 waves, direct-to-LDS staging that stays in flight across barriers -----------------------
-// One workgroup per CU (128 KiB of LDS: two 64-KiB stages of X[256][64] + W[256][64] f16).  Waves form a 2 (pixel
-// halves) x 4 (channel quarters) grid, wave tile 128 px x 64 ch = 4 x 2 MFMA tiles of 32 x 32.  A K-tile (64 deep)
-// is computed in 4 phases of 8 MFMAs; each phase reads only the fragments it newly needs:
-//     phase 1: W c0, X p0 p1 -> (c0;p0,p1)     phase 2: W c1 -> (c1;p0,p1)
-//     phase 3: X p2 p3       -> (c1;p2,p3)     phase 4: --   -> (c0;p2,p3)
-// The stage is DMA'd (global_load_lds, 16 B per lane, XOR-swizzled source slots as in gemm_glds_kernel) in four
-// 128-row "half-tiles" named after the phase that consumes them: XA (p0 p1 of both pixel halves), WA (c0 of the
-// four channel quarters), WB (c1), XB (p2 p3).  One half-tile (2 DMA instructions per lane) is issued per phase,
-// into a region whose last reader finished at least one full phase earlier:
-//     phase (t,1): XB(t+1)   (t,2): XA(t+2)   (t,3): WA(t+2)   (t,4): WB(t+2)
-// and ONE counted wait per K-tile, `s_waitcnt vmcnt(6)` in phase 4 (everything but the three half-tiles just issued
-// has landed, i.e. all of tile t+1), followed by that phase's barriers, orders the DMA before the reads of (t+1,1).
-// Every phase is  [ds_reads; DMA issue; lgkmcnt(0)] s_barrier [8 MFMAs] s_barrier ; the two pixel halves (one wave of
-// each per SIMD) run offset by one barrier, so one wave's LDS reads overlap the other's MFMAs.
+// ---- the 256-row pipeline: direct-to-LDS staging that stays in flight across barriers ---------------------------------
+// gemm256_kernel, gemm256p_kernel, gemm256x192_kernel and gemm256x192r_kernel are one pipeline design.  Its primitives are
+// defined here, once; each kernel below says only what it adds.  8 waves, one workgroup per CU, two LDS stages of
+// X[256][64] + W[BN][64] 16-bit values (rows of 128 bytes).  A stage is DMA'd (global_load_lds, 16 B per lane, XOR-swizzled
+// source slots as in gemm_glds_kernel) in named units, one or two of which are issued per phase into a region whose last
+// reader finished at least one full phase earlier; ONE counted `s_waitcnt vmcnt(n)` per K-tile, in its last phase, followed
+// by that phase's barriers, orders the DMA of tile t+1 before the reads of (t+1,1).  Every phase is
+//     [ds_reads; DMA issue; lgkmcnt(0)] s_barrier [MFMAs] s_barrier
+//      READ_FRAG DMA16      sync_in ............ mma*_group sync_out
+// and the waves form two groups (one wave of each per SIMD) that run offset by one barrier, so one group's LDS reads overlap
+// the other's MFMAs.
+// Why some primitives are macros: the device code of these kernels is pinned instruction for instruction (tools/check_asm_*.py,
+// the measured schedules), and hipcc's instruction order and register assignment change when READ_FRAG, DMA16, MMA16_GROUP, the
+// lane setup, the row maps or the K-loop become functions with arguments -- as macros they expand to the statements the kernels
+// held before.  The macros use the enclosing kernel's names (smem, STAGE, BM, BKB, nk, p, lane, src / dst / adj, ko, xbase, wbase).
+
 // Hazards (both wave groups, group 1 one barrier behind; barrier instances numbered globally):
-//   RAW  every wave waits vmcnt before its first barrier of (t,4); readers of (t+1,1) have passed the barrier after it.
+//   RAW  every wave waits vmcnt before its first barrier of the K-tile's last phase; readers of (t+1,1) have passed the barrier
+//        after it.
 //   WAR  reads are retired (lgkmcnt(0)) BEFORE the phase's first barrier, so a region read in phase p is free once
 //        every wave is past that barrier: any wave issuing phase p+1's DMA is.
+__device__ __forceinline__ void sync_in() {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_sched_barrier(0);
+  __builtin_amdgcn_s_setprio(1);
+}
+__device__ __forceinline__ void sync_out() {
+  __builtin_amdgcn_s_setprio(0);
+  __builtin_amdgcn_sched_barrier(0);
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_sched_barrier(0);
+}
+
+// one DMA instruction: 16 bytes per lane, global -> LDS (the wave's 64 lanes fill 8 consecutive 128-byte rows from dst on)
+#define DMA16(src, dst) \
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src), (__attribute__((address_space(3))) void*)(dst), 16, 0, 0)
+
+// the four 16-byte reads of one 32-row fragment block at `base` (= stage + the lane's X or W row + block * 32 rows); ko[s2] =
+// the lane's swizzled chunk offset of read s2
+#define READ_FRAG(f, base, ko) \
+  _Pragma("unroll") for (int s2 = 0; s2 < 4; ++s2) (f)[s2] = *reinterpret_cast<const u32x4*>((base) + (ko)[s2])
+
+// Fragment addresses of a lane: byte offset xbase / wbase of its X / W row in a stage, and per 16-byte read s2 the swizzled chunk
+// offset ko[s2] (the macros declare the three).
+// 32x32x16 layout (256 x 256 tile; waves 2 pixel halves wr x 4 channel quarters wc; lr = lane & 31, lh = lane >> 5): rows are
+// (32-aligned base + lr), so one swizzle value serves every fragment of the lane; read s2 is k-step s2
+#define FRAG_LANE32(lr, lh, wr, wc) \
+  const int sw = (lr >> 1) & 7; \
+  int ko[4]; \
+  _Pragma("unroll") for (int s2 = 0; s2 < 4; ++s2) ko[s2] = ((2 * s2 + lh) ^ sw) << 4; \
+  const int xbase = (wr * 128 + lr) * BKB, wbase = (BM + wc * 64 + lr) * BKB
+// 16x16x32 layout (256 x 192 tile; waves 4 pixel quarters wp x 2 channel halves wh).  Fragment (16 rows x 32 k): lane
+// (r16 = lane & 15, g16 = lane >> 4) reads chunk 4 ks + g16 of row r16; with the source swizzle slot = chunk ^ ((row >> 1) & 7) a
+// 16-lane ds_read_b128 group still covers the 16 slots of a 256-byte bank period once.  Read s2 = ks + 2 * (16-row half).
+// C / D: lane holds channels 4 g16 .. 4 g16 + 3 (rows, from the weight operand) of pixel r16
+#define FRAG_LANE16(r16, g16, wp, wh) \
+  const int sw = (r16 >> 1) & 7; \
+  int ko[4]; \
+  _Pragma("unroll") for (int s2 = 0; s2 < 4; ++s2) ko[s2] = (((4 * (s2 & 1) + g16) ^ sw) << 4) + (s2 >> 1) * 16 * BKB; \
+  const int xbase = (wp * 64 + r16) * BKB, wbase = (BM + wh * 96 + r16) * BKB
+
+// The MFMA groups of a phase.  The empty asm statements pin the MFMAs between the two barriers of their phase: hipcc
+// otherwise sinks the (pure) MFMA calls below the second barrier, in among the next phase's loads.
+// 32x32x16: channel block wf x pixel blocks xf[0], xf[1] -> a0, a1 (8 MFMAs)
+__device__ __forceinline__ void mma32_group(u32x4 (&wf)[4], const u32x4 (&xf)[2][4], f32x16& a0, f32x16& a1) {
+  asm volatile("" : "+v"(wf[0]), "+v"(wf[1]), "+v"(wf[2]), "+v"(wf[3]));
+#pragma unroll
+  for (int s2 = 0; s2 < 4; ++s2) {
+    Mma<f16>::run(wf[s2], xf[0][s2], a0);
+    Mma<f16>::run(wf[s2], xf[1][s2], a1);
+  }
+  asm volatile("" : "+v"(a0), "+v"(a1));
+}
+// 16x16x32: wf[ks + 2 hh] = channels 16 hh .. of the block, k-step ks; xf[j][ks + 2 ph] = pixels 32 j + 16 ph .., k-step ks;
+// a[16-channel half][16-pixel block] (16 MFMAs)
+#define MMA16_GROUP(wf, xf, a) \
+  asm volatile("" : "+v"(wf[0]), "+v"(wf[1]), "+v"(wf[2]), "+v"(wf[3])); \
+  _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) \
+  _Pragma("unroll") for (int hh = 0; hh < 2; ++hh) \
+  _Pragma("unroll") for (int pq = 0; pq < 4; ++pq) \
+    (a)[hh][pq] = CVMI_MFMA_16X16X32(__builtin_bit_cast(f16x8, wf[ks + 2 * hh]), \
+                                     __builtin_bit_cast(f16x8, xf[pq >> 1][ks + 2 * (pq & 1)]), (a)[hh][pq], 0, 0, 0); \
+  asm volatile("" : "+v"((a)[0][0]), "+v"((a)[0][1]), "+v"((a)[0][2]), "+v"((a)[0][3]), \
+                    "+v"((a)[1][0]), "+v"((a)[1][1]), "+v"((a)[1][2]), "+v"((a)[1][3]))
+
+// ---- 256 x 256 tile: row map, DMA issue, prologue and K-loop of gemm256_kernel and gemm256p_kernel ---------------------
+// Waves form a 2 (pixel halves wr = the staggered groups) x 4 (channel quarters wc) grid, wave tile 128 px x 64 ch = 4 x 2
+// MFMA tiles of 32 x 32.  A K-tile (64 deep) is computed in 4 phases of 8 MFMAs; each phase reads only the fragments it newly
+// needs:
+//     phase 1: W c0, X p0 p1 -> (c0;p0,p1)     phase 2: W c1 -> (c1;p0,p1)
+//     phase 3: X p2 p3       -> (c1;p2,p3)     phase 4: --   -> (c0;p2,p3)
+// The stage (64 KiB) is DMA'd in four 128-row "half-tiles" named after the phase that consumes them: XA (p0 p1 of both pixel
+// halves), WA (c0 of the four channel quarters), WB (c1), XB (p2 p3).  One half-tile (2 DMA instructions per lane) is issued
+// per phase:
+//     phase (t,1): XB(t+1)   (t,2): XA(t+2)   (t,3): WA(t+2)   (t,4): WB(t+2)
+// and the counted wait is `s_waitcnt vmcnt(6)` in phase 4 (everything but the three half-tiles just issued has landed, i.e.
+// all of tile t+1).
+
+// first stage row of piece q = 2 wv + i (i = 0, 1) of half-tile h (0 XA, 1 WA, 2 WB, 3 XB): 16 pieces of 8 rows, 2 per wave
+#define G256_ROW0(h, q) \
+  ((h == 0 || h == 3) ? (q >> 3) * 128 + (h == 3 ? 64 : 0) + (q & 7) * 8 \
+                      : BM + (q >> 2) * 64 + (h == 2 ? 32 : 0) + (q & 3) * 8)
+
+// half-tile h of K-tile kt into `stage`.  G256_ISSUE_SEL adds gemm256_kernel's IM2COL source select (the only difference between
+// the two kernels' K-loops): the X half-tiles move by a wave-uniform tap offset, a lane outside the image reads the zero page
+#define G256_SRC(h, i, kt) src[h][i] + (long long)(kt) * BKB + last_ * adj[h][i]
+#define G256_ISSUE_PLAIN(h, stage, kt) \
+  do { \
+    const long long last_ = (kt) == nk - 1 ? 1 : 0; \
+    DMA16(G256_SRC(h, 0, kt), smem + (stage) * STAGE + dst[h][0]); \
+    DMA16(G256_SRC(h, 1, kt), smem + (stage) * STAGE + dst[h][1]); \
+  } while (0)
+#define G256_ISSUE_SEL(h, stage, kt) \
+  do { \
+    const long long last_ = (kt) == nk - 1 ? 1 : 0; \
+    const char *s0_ = G256_SRC(h, 0, kt), *s1_ = G256_SRC(h, 1, kt); \
+    if (IM2COL && ((h) == 0 || (h) == 3)) {                 /* X half-tiles: tap offset (wave-uniform), zero page outside the image */ \
+      const int tap_ = (kt) >> p.im2col_shift, c64_ = (kt) & ((1 << p.im2col_shift) - 1); \
+      const int ky_ = (tap_ * 11) >> 5, kx_ = tap_ - 3 * ky_; \
+      const long long off_ = ((long long)(ky_ * p.W + kx_) * p.x0_ld + c64_ * 64) * 2; \
+      const char* z_ = reinterpret_cast<const char*>(cvmi_zero_page) + (lane & 7) * 16; \
+      s0_ = ((vmask[h][0] >> tap_) & 1) ? src[h][0] + off_ : z_; \
+      s1_ = ((vmask[h][1] >> tap_) & 1) ? src[h][1] + off_ : z_; \
+    } \
+    DMA16(s0_, smem + (stage) * STAGE + dst[h][0]); \
+    DMA16(s1_, smem + (stage) * STAGE + dst[h][1]); \
+  } while (0)
+// prologue: all of tile 0, and XA WA WB of tile 1.  The wait is the caller's: gemm256_kernel waits at once, gemm256p_kernel an
+// epilogue later
+#define G256_PROLOGUE(ISSUE) \
+  do { \
+    ISSUE(0, 0, 0); ISSUE(1, 0, 0); ISSUE(2, 0, 0); ISSUE(3, 0, 0); \
+    if (nk > 1) { ISSUE(0, 1, 1); ISSUE(1, 1, 1); ISSUE(2, 1, 1); } \
+  } while (0)
+// the K-loop.  On entry the prologue has landed and group 1 (wr == 1) is one barrier behind; on exit the groups are aligned
+// again: every wave has left the loop, both stages are dead
+#define G256_KLOOP(ISSUE) \
+  for (int kt = 0; kt < nk; ++kt) { \
+    const int b = kt & 1; \
+    const char* st = smem + b * STAGE; \
+    const bool more1 = kt + 1 < nk, more2 = kt + 2 < nk; /* wave-uniform */ \
+    /* ---- phase 1 */ \
+    READ_FRAG(wf[0], st + wbase + 0 * 32 * BKB, ko); \
+    READ_FRAG(xf[0], st + xbase + 0 * 32 * BKB, ko); \
+    READ_FRAG(xf[1], st + xbase + 1 * 32 * BKB, ko); \
+    if (more1) ISSUE(3, b ^ 1, kt + 1); \
+    sync_in(); \
+    mma32_group(wf[0], xf, acc[0][0], acc[0][1]); \
+    sync_out(); \
+    /* ---- phase 2 */ \
+    READ_FRAG(wf[1], st + wbase + 1 * 32 * BKB, ko); \
+    if (more2) ISSUE(0, b, kt + 2); \
+    sync_in(); \
+    mma32_group(wf[1], xf, acc[1][0], acc[1][1]); \
+    sync_out(); \
+    /* ---- phase 3 */ \
+    READ_FRAG(xf[0], st + xbase + 2 * 32 * BKB, ko); \
+    READ_FRAG(xf[1], st + xbase + 3 * 32 * BKB, ko); \
+    if (more2) ISSUE(1, b, kt + 2); \
+    sync_in(); \
+    mma32_group(wf[1], xf, acc[1][2], acc[1][3]); \
+    sync_out(); \
+    /* ---- phase 4 */ \
+    if (more2) { \
+      ISSUE(2, b, kt + 2); \
+      asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); \
+    } else if (more1) { \
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); \
+    } \
+    sync_in(); \
+    mma32_group(wf[0], xf, acc[0][2], acc[0][3]); \
+    sync_out(); \
+  } \
+  if (wr == 0) __builtin_amdgcn_s_barrier()
+
+// ---- 256 x 256 tile GEMM, one tile per workgroup ---------------------------------------------------------------------
+// The pipeline above (128 KiB of LDS: two 64-KiB stages) + a tile-wide LDS-transposing epilogue.
 // IM2COL (r04): the A operand is a 3 x 3 convolution's im2col matrix instead of a plain row-major one -- YOLO11-l's large stride-2 / stride-1
 // convs (256 - 512 channels; 250 - 375 TFLOP/s on the register-staged 128 x 128 kernel above).  K runs tap-major (k = tap * Cin + c, as the
 // weights are packed), Cin is a power-of-two multiple of 64, so a K-tile of 64 channels lies inside ONE tap: the lane's source row pointer
@@ -659,16 +827,11 @@ int launch_glds(ConvKArgs& a, hipStream_t stream) {
 template <typename TO, bool STAGGER, bool IM2COL = false>
 __global__ __launch_bounds__(512, 1) void gemm256_kernel(const ConvKArgs p) {
   static_assert(STAGGER, "only the staggered schedule is built");
-  using T = f16;
   constexpr int BM = 256, BN = 256, BKB = 128;
   constexpr int STAGE = (BM + BN) * BKB;                  // 64 KiB
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
-  int wg = blockIdx.x;
-  {
-    const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = wg & 7, j = wg >> 3;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-  }
+  const int wg = xcd_remap(blockIdx.x, gridDim.x);
   const int bn = wg % p.nb_n, bm = wg / p.nb_n;
   const int m0 = bm * BM, n0 = bn * BN;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
@@ -684,8 +847,7 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(const ConvKArgs p) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int q = wv * 2 + i;
-      const int row0 = (h == 0 || h == 3) ? (q >> 3) * 128 + (h == 3 ? 64 : 0) + (q & 7) * 8
-                                          : BM + (q >> 2) * 64 + (h == 2 ? 32 : 0) + (q & 3) * 8;
+      const int row0 = G256_ROW0(h, q);
       const int row = row0 + (lane >> 3);
       const int slot = (lane & 7) ^ ((row >> 1) & 7);
       adj[h][i] = 0;
@@ -716,125 +878,20 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(const ConvKArgs p) {
       }
       dst[h][i] = row0 * BKB;
     }
-#define G256_ISSUE(h, stage, kt)                                                                                         \
-  do {                                                                                                                   \
-    const long long last_ = (kt) == nk - 1 ? 1 : 0;                                                                      \
-    const char *s0_ = src[h][0] + (long long)(kt) * BKB + last_ * adj[h][0], *s1_ = src[h][1] + (long long)(kt) * BKB + last_ * adj[h][1]; \
-    if (IM2COL && ((h) == 0 || (h) == 3)) {                 /* X half-tiles: tap offset (wave-uniform), zero page outside the image */ \
-      const int tap_ = (kt) >> p.im2col_shift, c64_ = (kt) & ((1 << p.im2col_shift) - 1);                               \
-      const int ky_ = (tap_ * 11) >> 5, kx_ = tap_ - 3 * ky_;                                                            \
-      const long long off_ = ((long long)(ky_ * p.W + kx_) * p.x0_ld + c64_ * 64) * 2;                                   \
-      const char* z_ = reinterpret_cast<const char*>(cvmi_zero_page) + (lane & 7) * 16;                                  \
-      s0_ = ((vmask[h][0] >> tap_) & 1) ? src[h][0] + off_ : z_;                                                          \
-      s1_ = ((vmask[h][1] >> tap_) & 1) ? src[h][1] + off_ : z_;                                                          \
-    }                                                                                                                    \
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)s0_,                                 \
-                                     (__attribute__((address_space(3))) void*)(smem + (stage) * STAGE + dst[h][0]), 16, 0, 0); \
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)s1_,                                 \
-                                     (__attribute__((address_space(3))) void*)(smem + (stage) * STAGE + dst[h][1]), 16, 0, 0); \
-  } while (0)
 
   f32x16 acc[2][4];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  CLEAR_ACC32(acc, 2, 4);
 
-  // fragment addresses: rows are (32-aligned base + lr), so one swizzle value serves every fragment of the lane
-  const int sw = (lr >> 1) & 7;
-  int ko[4];
-#pragma unroll
-  for (int s2 = 0; s2 < 4; ++s2) ko[s2] = ((2 * s2 + lh) ^ sw) << 4;
-  const int xbase = (wr * 128 + lr) * BKB, wbase = (BM + wc * 64 + lr) * BKB;
+  FRAG_LANE32(lr, lh, wr, wc);
 
-  // prologue: all of tile 0, and XA WA WB of tile 1
-  G256_ISSUE(0, 0, 0); G256_ISSUE(1, 0, 0); G256_ISSUE(2, 0, 0); G256_ISSUE(3, 0, 0);
-  if (nk > 1) {
-    G256_ISSUE(0, 1, 1); G256_ISSUE(1, 1, 1); G256_ISSUE(2, 1, 1);
-    asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-  } else {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  }
+  G256_PROLOGUE(G256_ISSUE_SEL);
+  if (nk > 1) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+  else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   if (wr == 1) __builtin_amdgcn_s_barrier();
 
   u32x4 xf[2][4], wf[2][4];
-#define G256_READ_X(slot_, j)                                                                                            \
-  _Pragma("unroll") for (int s2 = 0; s2 < 4; ++s2)                                                                       \
-      xf[slot_][s2] = *reinterpret_cast<const u32x4*>(st + xbase + (j) * 32 * BKB + ko[s2])
-#define G256_READ_W(i)                                                                                                   \
-  _Pragma("unroll") for (int s2 = 0; s2 < 4; ++s2)                                                                       \
-      wf[i][s2] = *reinterpret_cast<const u32x4*>(st + wbase + (i) * 32 * BKB + ko[s2])
-#define G256_SYNC_IN()                                                                                                   \
-  do {                                                                                                                   \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                                   \
-    __builtin_amdgcn_sched_barrier(0);                                                                                   \
-    __builtin_amdgcn_s_barrier();                                                                                        \
-    __builtin_amdgcn_sched_barrier(0);                                                                                   \
-    __builtin_amdgcn_s_setprio(1);                                                                                       \
-  } while (0)
-#define G256_SYNC_OUT()                                                                                                  \
-  do {                                                                                                                   \
-    __builtin_amdgcn_s_setprio(0);                                                                                       \
-    __builtin_amdgcn_sched_barrier(0);                                                                                   \
-    __builtin_amdgcn_s_barrier();                                                                                        \
-    __builtin_amdgcn_sched_barrier(0);                                                                                   \
-  } while (0)
-  // the empty asm statements pin the MFMAs between the two barriers of their phase: hipcc otherwise sinks the (pure)
-  // MFMA calls below the second barrier, in among the next phase's loads
-#define G256_MMA(i, j0)                                                                                                  \
-  asm volatile("" : "+v"(wf[i][0]), "+v"(wf[i][1]), "+v"(wf[i][2]), "+v"(wf[i][3]));                                     \
-  _Pragma("unroll") for (int s2 = 0; s2 < 4; ++s2) {                                                                     \
-    Mma<T>::run(wf[i][s2], xf[0][s2], acc[i][j0]);                                                                       \
-    Mma<T>::run(wf[i][s2], xf[1][s2], acc[i][(j0) + 1]);                                                                 \
-  }                                                                                                                      \
-  asm volatile("" : "+v"(acc[i][j0]), "+v"(acc[i][(j0) + 1]))
-
-  for (int kt = 0; kt < nk; ++kt) {
-    const int b = kt & 1;
-    const char* st = smem + b * STAGE;
-    const bool more1 = kt + 1 < nk, more2 = kt + 2 < nk;     // wave-uniform
-    // ---- phase 1
-    G256_READ_W(0);
-    G256_READ_X(0, 0);
-    G256_READ_X(1, 1);
-    if (more1) G256_ISSUE(3, b ^ 1, kt + 1);
-    G256_SYNC_IN();
-    G256_MMA(0, 0);
-    G256_SYNC_OUT();
-    // ---- phase 2
-    G256_READ_W(1);
-    if (more2) G256_ISSUE(0, b, kt + 2);
-    G256_SYNC_IN();
-    G256_MMA(1, 0);
-    G256_SYNC_OUT();
-    // ---- phase 3
-    G256_READ_X(0, 2);
-    G256_READ_X(1, 3);
-    if (more2) G256_ISSUE(1, b, kt + 2);
-    G256_SYNC_IN();
-    G256_MMA(1, 2);
-    G256_SYNC_OUT();
-    // ---- phase 4
-    if (more2) {
-      G256_ISSUE(2, b, kt + 2);
-      asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    } else if (more1) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    G256_SYNC_IN();
-    G256_MMA(0, 2);
-    G256_SYNC_OUT();
-  }
-  if (wr == 0) __builtin_amdgcn_s_barrier();
-#undef G256_ISSUE
-#undef G256_READ_X
-#undef G256_READ_W
-#undef G256_SYNC_IN
-#undef G256_SYNC_OUT
-#undef G256_MMA
+  G256_KLOOP(G256_ISSUE_SEL);
 
   // ---- epilogue: bias + act -> LDS tile -> 16-byte stores (+ residual); f32 output goes in two 128-column passes
   constexpr int OES = sizeof(TO), OVEC = 16 / OES;
@@ -861,14 +918,7 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(const ConvKArgs p) {
               float v[4];
 #pragma unroll
               for (int e = 0; e < 4; ++e) v[e] = actf(acc[i][j][4 * q + e] + bv[e]);
-              char* d = Ct + ml * CROWB + nl * OES;
-              if constexpr (OES == 2) {
-                f16x4 hv = {(f16)v[0], (f16)v[1], (f16)v[2], (f16)v[3]};
-                *reinterpret_cast<f16x4*>(d) = hv;
-              } else {
-                f32x4 fv = {v[0], v[1], v[2], v[3]};
-                *reinterpret_cast<f32x4*>(d) = fv;
-              }
+              tile_put4<TO>(Ct + ml * CROWB + nl * OES, v);
             }
           }
         }
@@ -909,9 +959,8 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(const ConvKArgs p) {
 // epilogue must not touch the stage buffers: each wave transposes its 128 x 64 sub-tile through a private 4 KiB scratch
 // (32 pixels x 64 channels per step, XOR-swizzled 16-byte chunks) -- no workgroup barrier, and no ordinary global load while
 // the DMA is in flight (hipcc would drain the queue at its use): the wave's 64 bias values are parked in its scratch at the
-// start of the tile.  K-loop, hazards and counted waits are those of gemm256_kernel (staggered groups).
+// start of the tile.  Prologue issue and K-loop are G256_PROLOGUE / G256_KLOOP, as in gemm256_kernel (plain sources).
 __global__ __launch_bounds__(512, 1) void gemm256p_kernel(const ConvKArgs p, int ntiles) {
-  using T = f16;
   constexpr int BM = 256, BN = 256, BKB = 128;
   constexpr int STAGE = (BM + BN) * BKB;                  // 64 KiB
   constexpr int SCR_OFF = 2 * STAGE, SCR_WAVE = 2048, BIAS_OFF = SCR_OFF + 8 * SCR_WAVE;   // 32 px x 32 ch scratch + 64 bias floats per wave
@@ -936,8 +985,7 @@ __global__ __launch_bounds__(512, 1) void gemm256p_kernel(const ConvKArgs p, int
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int q = wv * 2 + i;
-      dst[h][i] = ((h == 0 || h == 3) ? (q >> 3) * 128 + (h == 3 ? 64 : 0) + (q & 7) * 8
-                                       : BM + (q >> 2) * 64 + (h == 2 ? 32 : 0) + (q & 3) * 8) * BKB;
+      dst[h][i] = G256_ROW0(h, q) * BKB;
     }
   auto setup = [&](int tile, int& m0, int& n0) {
     const int bn = tile % p.nb_n, bm = tile / p.nb_n;
@@ -948,7 +996,7 @@ __global__ __launch_bounds__(512, 1) void gemm256p_kernel(const ConvKArgs p, int
     for (int h = 0; h < 4; ++h)
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
-        const int row = dst[h][i] / BKB + (ln >> 3);
+        const int row = dst[h][i] / BKB + (ln >> 3);   // (= G256_ROW0(h, q): read back from dst, which keeps the row map out of the per-tile code)
         const int slot_ = (ln & 7) ^ ((row >> 1) & 7);
         adj[h][i] = 0;
         if (row < BM) {
@@ -963,65 +1011,14 @@ __global__ __launch_bounds__(512, 1) void gemm256p_kernel(const ConvKArgs p, int
         }
       }
   };
-#define G256_ISSUE(h, stage, kt)                                                                                         \
-  do {                                                                                                                   \
-    const long long last_ = (kt) == nk - 1 ? 1 : 0;                                                                      \
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src[h][0] + (long long)(kt) * BKB + last_ * adj[h][0]), \
-                                     (__attribute__((address_space(3))) void*)(smem + (stage) * STAGE + dst[h][0]), 16, 0, 0); \
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src[h][1] + (long long)(kt) * BKB + last_ * adj[h][1]), \
-                                     (__attribute__((address_space(3))) void*)(smem + (stage) * STAGE + dst[h][1]), 16, 0, 0); \
-  } while (0)
-#define G256_PROLOGUE()                                                                                                  \
-  do {                                                                                                                   \
-    G256_ISSUE(0, 0, 0); G256_ISSUE(1, 0, 0); G256_ISSUE(2, 0, 0); G256_ISSUE(3, 0, 0);                                  \
-    if (nk > 1) { G256_ISSUE(0, 1, 1); G256_ISSUE(1, 1, 1); G256_ISSUE(2, 1, 1); }                                       \
-  } while (0)
 
   f32x16 acc[2][4];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-  const int sw = (lr >> 1) & 7;
-  int ko[4];
-#pragma unroll
-  for (int s2 = 0; s2 < 4; ++s2) ko[s2] = ((2 * s2 + lh) ^ sw) << 4;
-  const int xbase = (wr * 128 + lr) * BKB, wbase = (BM + wc * 64 + lr) * BKB;
-
+  CLEAR_ACC32(acc, 2, 4);
+  FRAG_LANE32(lr, lh, wr, wc);
   u32x4 xf[2][4], wf[2][4];
-#define G256_READ_X(slot_, j)                                                                                            \
-  _Pragma("unroll") for (int s2 = 0; s2 < 4; ++s2)                                                                       \
-      xf[slot_][s2] = *reinterpret_cast<const u32x4*>(st + xbase + (j) * 32 * BKB + ko[s2])
-#define G256_READ_W(i)                                                                                                   \
-  _Pragma("unroll") for (int s2 = 0; s2 < 4; ++s2)                                                                       \
-      wf[i][s2] = *reinterpret_cast<const u32x4*>(st + wbase + (i) * 32 * BKB + ko[s2])
-#define G256_SYNC_IN()                                                                                                   \
-  do {                                                                                                                   \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                                   \
-    __builtin_amdgcn_sched_barrier(0);                                                                                   \
-    __builtin_amdgcn_s_barrier();                                                                                        \
-    __builtin_amdgcn_sched_barrier(0);                                                                                   \
-    __builtin_amdgcn_s_setprio(1);                                                                                       \
-  } while (0)
-#define G256_SYNC_OUT()                                                                                                  \
-  do {                                                                                                                   \
-    __builtin_amdgcn_s_setprio(0);                                                                                       \
-    __builtin_amdgcn_sched_barrier(0);                                                                                   \
-    __builtin_amdgcn_s_barrier();                                                                                        \
-    __builtin_amdgcn_sched_barrier(0);                                                                                   \
-  } while (0)
-#define G256_MMA(i, j0)                                                                                                  \
-  asm volatile("" : "+v"(wf[i][0]), "+v"(wf[i][1]), "+v"(wf[i][2]), "+v"(wf[i][3]));                                     \
-  _Pragma("unroll") for (int s2 = 0; s2 < 4; ++s2) {                                                                     \
-    Mma<T>::run(wf[i][s2], xf[0][s2], acc[i][j0]);                                                                       \
-    Mma<T>::run(wf[i][s2], xf[1][s2], acc[i][(j0) + 1]);                                                                 \
-  }                                                                                                                      \
-  asm volatile("" : "+v"(acc[i][j0]), "+v"(acc[i][(j0) + 1]))
 
   int m0 = 0, n0 = 0;
-  if (slot < tcnt) { setup(tbase + slot, m0, n0); G256_PROLOGUE(); }
+  if (slot < tcnt) { setup(tbase + slot, m0, n0); G256_PROLOGUE(G256_ISSUE_PLAIN); }
   for (int ti = slot; ti < tcnt; ti += wpx) {
     const int cm0 = m0, cn0 = n0;
     // ---- this wave's 64 bias values -> its scratch (drains the prologue DMA: it was issued an epilogue ago)
@@ -1035,42 +1032,10 @@ __global__ __launch_bounds__(512, 1) void gemm256p_kernel(const ConvKArgs p, int
     __builtin_amdgcn_s_barrier();
     if (wr == 1) __builtin_amdgcn_s_barrier();
 
-    for (int kt = 0; kt < nk; ++kt) {
-      const int b = kt & 1;
-      const char* st = smem + b * STAGE;
-      const bool more1 = kt + 1 < nk, more2 = kt + 2 < nk;
-      G256_READ_W(0);
-      G256_READ_X(0, 0);
-      G256_READ_X(1, 1);
-      if (more1) G256_ISSUE(3, b ^ 1, kt + 1);
-      G256_SYNC_IN();
-      G256_MMA(0, 0);
-      G256_SYNC_OUT();
-      G256_READ_W(1);
-      if (more2) G256_ISSUE(0, b, kt + 2);
-      G256_SYNC_IN();
-      G256_MMA(1, 0);
-      G256_SYNC_OUT();
-      G256_READ_X(0, 2);
-      G256_READ_X(1, 3);
-      if (more2) G256_ISSUE(1, b, kt + 2);
-      G256_SYNC_IN();
-      G256_MMA(1, 2);
-      G256_SYNC_OUT();
-      if (more2) {
-        G256_ISSUE(2, b, kt + 2);
-        asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-      } else if (more1) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
-      G256_SYNC_IN();
-      G256_MMA(0, 2);
-      G256_SYNC_OUT();
-    }
-    if (wr == 0) __builtin_amdgcn_s_barrier();            // groups aligned: every wave has left the K-loop, both stages are dead
+    G256_KLOOP(G256_ISSUE_PLAIN);
 
     // ---- next tile's prologue flies during this tile's epilogue
-    if (ti + wpx < tcnt) { setup(tbase + ti + wpx, m0, n0); G256_PROLOGUE(); }
+    if (ti + wpx < tcnt) { setup(tbase + ti + wpx, m0, n0); G256_PROLOGUE(G256_ISSUE_PLAIN); }
 
     // ---- wave-private epilogue: 32 pixels x 32 channels per step through the scratch (64-byte rows, swizzled 16-byte chunks)
     // (one base register per kind of access + immediate offsets: anything the compiler would spill here comes back through
@@ -1115,20 +1080,8 @@ __global__ __launch_bounds__(512, 1) void gemm256p_kernel(const ConvKArgs p, int
           }
         }
     });
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  CLEAR_ACC32(acc, 2, 4);
   }
-#undef G256_ISSUE
-#undef G256_PROLOGUE
-#undef G256_READ_X
-#undef G256_READ_W
-#undef G256_SYNC_IN
-#undef G256_SYNC_OUT
-#undef G256_MMA
 }
 
 int launch_g256p(ConvKArgs& a, hipStream_t stream) {
@@ -1148,45 +1101,74 @@ int launch_g256p(ConvKArgs& a, hipStream_t stream) {
   return 0;
 }
 
-// ---- 256 x 192 tile variant of gemm256_kernel (N = 576 = 3 x 192: Hiera-L stage-3 proj / fc2) -------------------------
-// 8 waves as 4 (pixel quarters) x 2 (channel halves; the two staggered groups), wave tile 64 px x 96 ch = 2 x 3 MFMA
+// ---- 256 x 192 tile: what gemm256x192_kernel and gemm256x192r_kernel share (N = 576 = 3 x 192: Hiera-L stage-3 proj / fc2) ---
+// 8 waves as 4 (pixel quarters wp) x 2 (channel halves wh; the two staggered groups), wave tile 64 px x 96 ch = 2 x 3 MFMA
 // tiles.  A K-tile is three phases of 8 MFMAs:  1: W c0, X p0 p1 -> (c0;p0,p1)   2: W c1 -> (c1;..)   3: W c2 -> (c2;..).
 // DMA units per K-tile (56 KiB): X0, X1 (128 pixel rows each, 2 instructions per lane), WC0, WC1, WC2 (the 32-row channel
-// block k of both halves, 1 instruction per lane), issued one phase after their region's last read:
-//     phase (t,1): WC2(t+1)      (t,2): X0(t+2), WC0(t+2)      (t,3): X1(t+2), WC1(t+2)
-// and one counted wait per K-tile, vmcnt(6) in phase 3 (all but the six instructions of phases 2 and 3, i.e. all of tile
-// t+1, has landed).  Hazard argument as for gemm256_kernel (reads retired before a phase's first barrier).
+// block k of both halves, 1 instruction per lane).  The two kernels share the row map, the units, FRAG_LANE16, READ_FRAG,
+// MMA16_GROUP, the syncs and the row statistics; each keeps its own loop, because the issue slots and the counted waits differ.
 // MFMA shape v_mfma_f32_16x16x32 (16 per phase; 32x32x16 has equal cycles per flop and equal LDS bytes -- every lane still reads 16 bytes
 // per fragment -- but the chip holds a higher clock on this shape under the power limit: MI355X_MICROARCH.md, DVFS give-back item 7).
-// Fragment (16 rows x 32 k): lane (r16 = lane & 15, g = lane >> 4) reads chunk 4 ks + g of row r16; with the source swizzle
-// slot = chunk ^ ((row >> 1) & 7) a 16-lane ds_read_b128 group still covers the 16 slots of a 256-byte bank period once.
-// C / D: lane holds channels 4 g .. 4 g + 3 (rows, from the weight operand) of pixel r16.
+
+// first stage row of DMA instruction u of wave wv: u = 0, 1 X0, 2, 3 X1 (pieces 2 wv, 2 wv + 1 of 16), 4..6 WC0..WC2 (piece wv of
+// 8: half wv >> 2, 8-row group wv & 3)
+#define G192_ROW0(row0, u, wv) \
+    int row0; \
+    if (u < 4) row0 = (u >> 1) * 128 + (wv * 2 + (u & 1)) * 8; \
+    else row0 = BM + (wv >> 2) * 96 + (u - 4) * 32 + (wv & 3) * 8
+// the DMA units into `stage`.  AT(u, a) = the lane's source address for instruction u: AT_KT, K-tile a of a row that is clamped
+// and adjusted as in gemm256_kernel (one-tile kernel); AT_OFF, a bytes along the row (persistent kernel: stream offsets)
+#define G192_ISSUE1(u, stage, s) DMA16(s, smem + (stage) * STAGE + dst[u])
+#define G192_X0(stage, AT, a) do { G192_ISSUE1(0, stage, AT(0, a)); G192_ISSUE1(1, stage, AT(1, a)); } while (0)
+#define G192_X1(stage, AT, a) do { G192_ISSUE1(2, stage, AT(2, a)); G192_ISSUE1(3, stage, AT(3, a)); } while (0)
+#define G192_WC(k, stage, AT, a) G192_ISSUE1(4 + (k), stage, AT(4 + (k), a))
+#define AT_KT(u, kt) src[u] + (long long)(kt) * BKB + ((kt) == nk - 1 ? (long long)adj[u] : 0ll)
+#define AT_OFF(u, off) src[u] + (off)
+
+// Direct f32 epilogue of the two kernels (no LDS transposition, no barriers): in the 16x16x32 C / D layout a lane holds 4
+// consecutive channels of a pixel and the four lanes g16 = 0..3 hold 16 consecutive ones, so residual loads and stores are 64-byte
+// row pieces as they stand.  The kernels differ in how a value is summed -- (acc + bias) + res in the one-tile kernel, (res + sum)
+// + bias in the persistent one, where the residual is already in the accumulator -- and each keeps that loop and its stores; what
+// they share is the row statistics for the next LayerNorm (p.stats): v = this lane's 24 finished values of pixel m, sm their sum,
+// slice = the wave's 96-channel slice of the row (of `slices`).  Per pixel and slice the slice MEAN and the sum of squared
+// deviations from it, two passes over the 24 values in registers -- no E[x^2] - E[x]^2 cancellation however far the row sits
+// from zero; the consumer combines the slices as Chan et al. do (tok_linear16.hip / tok_linear.hip, stats_parts).
+#define G192_ROW_STATS(v, sm, m, slice) \
+  sm += __shfl_xor(sm, 16); \
+  sm += __shfl_xor(sm, 32); \
+  const float mean = sm * (1.0f / 96.0f); \
+  float m2 = 0.f; \
+  _Pragma("unroll") for (int i = 0; i < 3; ++i) \
+  _Pragma("unroll") for (int hh = 0; hh < 2; ++hh) \
+  _Pragma("unroll") for (int e = 0; e < 4; ++e) { const float dv = v[i][hh][e] - mean; m2 = fmaf(dv, dv, m2); } \
+  m2 += __shfl_xor(m2, 16); \
+  m2 += __shfl_xor(m2, 32); \
+  if (g16 == 0) *reinterpret_cast<float2*>(p.stats + (m * slices + (slice)) * 2) = make_float2(mean, m2)
+
+// ---- 256 x 192 tile GEMM, one tile per workgroup ---------------------------------------------------------------------
+// Units are issued one phase after their region's last read:
+//     phase (t,1): WC2(t+1)      (t,2): X0(t+2), WC0(t+2)      (t,3): X1(t+2), WC1(t+2)
+// and one counted wait per K-tile, vmcnt(6) in phase 3 (all but the six instructions of phases 2 and 3, i.e. all of tile
+// t+1, has landed).  Hazard argument: see sync_in (reads retired before a phase's first barrier).
 template <typename TO>
 __global__ __launch_bounds__(512, 1) void gemm256x192_kernel(const ConvKArgs p) {
   constexpr int BM = 256, BN = 192, BKB = 128;
   constexpr int STAGE = (BM + BN) * BKB;                  // 56 KiB
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
-  int wg = blockIdx.x;
-  {
-    const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = wg & 7, j = wg >> 3;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-  }
+  const int wg = xcd_remap(blockIdx.x, gridDim.x);
   const int bn = wg % p.nb_n;
   const int bm = wg / p.nb_n;
   const int m0 = bm * BM, n0 = bn * BN;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   const int wp = wv & 3, wh = wv >> 2;                    // pixel quarter, channel half (= stagger group; wv and wv + 4 share a SIMD)
 
-  // DMA: unit 0 X0, 1 X1 (pieces 2 wv, 2 wv + 1 of 16), 2..4 WC0..WC2 (piece wv of 8: half wv >> 2, 8-row group wv & 3)
   const int nk = (p.K + 63) / 64, krem = p.K & 63;
   const char* src[7];
   int dst[7], adj[7];
 #pragma unroll
   for (int u = 0; u < 7; ++u) {
-    int row0;
-    if (u < 4) row0 = (u >> 1) * 128 + (wv * 2 + (u & 1)) * 8;                    // u = 0,1: X0; 2,3: X1
-    else row0 = BM + (wv >> 2) * 96 + (u - 4) * 32 + (wv & 3) * 8;               // u = 4,5,6: WC0..2
+    G192_ROW0(row0, u, wv);
     const int row = row0 + (lane >> 3);
     const int slot = (lane & 7) ^ ((row >> 1) & 7);
     adj[u] = 0;
@@ -1202,31 +1184,16 @@ __global__ __launch_bounds__(512, 1) void gemm256x192_kernel(const ConvKArgs p) 
     }
     dst[u] = row0 * BKB;
   }
-#define G192_ISSUE1(u, stage, kt)                                                                                        \
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src[u] + (long long)(kt) * BKB + ((kt) == nk - 1 ? (long long)adj[u] : 0ll)), \
-                                   (__attribute__((address_space(3))) void*)(smem + (stage) * STAGE + dst[u]), 16, 0, 0)
-#define G192_X0(stage, kt) do { G192_ISSUE1(0, stage, kt); G192_ISSUE1(1, stage, kt); } while (0)
-#define G192_X1(stage, kt) do { G192_ISSUE1(2, stage, kt); G192_ISSUE1(3, stage, kt); } while (0)
-#define G192_WC(k, stage, kt) G192_ISSUE1(4 + (k), stage, kt)
 
   f32x4 acc16[3][2][4];                                   // [channel block][16-channel half][16-pixel block]
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) acc16[i][j][q] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  clear_acc(acc16);
 
   const int r16 = lane & 15, g16 = lane >> 4;
-  const int sw = (r16 >> 1) & 7;
-  int ko[4];
-#pragma unroll
-  for (int s2 = 0; s2 < 4; ++s2) ko[s2] = (((4 * (s2 & 1) + g16) ^ sw) << 4) + (s2 >> 1) * 16 * BKB;      // s2 = ks + 2 * (16-row half)
-  const int xbase = (wp * 64 + r16) * BKB, wbase = (BM + wh * 96 + r16) * BKB;
+  FRAG_LANE16(r16, g16, wp, wh);
 
-  G192_X0(0, 0); G192_WC(0, 0, 0); G192_X1(0, 0); G192_WC(1, 0, 0); G192_WC(2, 0, 0);
+  G192_X0(0, AT_KT, 0); G192_WC(0, 0, AT_KT, 0); G192_X1(0, AT_KT, 0); G192_WC(1, 0, AT_KT, 0); G192_WC(2, 0, AT_KT, 0);
   if (nk > 1) {
-    G192_X0(1, 1); G192_WC(0, 1, 1); G192_X1(1, 1); G192_WC(1, 1, 1);
+    G192_X0(1, AT_KT, 1); G192_WC(0, 1, AT_KT, 1); G192_X1(1, AT_KT, 1); G192_WC(1, 1, AT_KT, 1);
     asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
   } else {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1235,85 +1202,39 @@ __global__ __launch_bounds__(512, 1) void gemm256x192_kernel(const ConvKArgs p) 
   if (wh == 1) __builtin_amdgcn_s_barrier();
 
   u32x4 xf[2][4], wf[4];
-#define G192_READ_X(j)                                                                                                   \
-  _Pragma("unroll") for (int s2 = 0; s2 < 4; ++s2)                                                                       \
-      xf[j][s2] = *reinterpret_cast<const u32x4*>(st + xbase + (j) * 32 * BKB + ko[s2])
-#define G192_READ_W(i)                                                                                                   \
-  _Pragma("unroll") for (int s2 = 0; s2 < 4; ++s2)                                                                       \
-      wf[s2] = *reinterpret_cast<const u32x4*>(st + wbase + (i) * 32 * BKB + ko[s2])
-#define G192_SYNC_IN()                                                                                                   \
-  do {                                                                                                                   \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                                   \
-    __builtin_amdgcn_sched_barrier(0);                                                                                   \
-    __builtin_amdgcn_s_barrier();                                                                                        \
-    __builtin_amdgcn_sched_barrier(0);                                                                                   \
-    __builtin_amdgcn_s_setprio(1);                                                                                       \
-  } while (0)
-#define G192_SYNC_OUT()                                                                                                  \
-  do {                                                                                                                   \
-    __builtin_amdgcn_s_setprio(0);                                                                                       \
-    __builtin_amdgcn_sched_barrier(0);                                                                                   \
-    __builtin_amdgcn_s_barrier();                                                                                        \
-    __builtin_amdgcn_sched_barrier(0);                                                                                   \
-  } while (0)
-  // wf[ks + 2 hh] = channels 16 hh .. of block i, k-step ks; xf[j][ks + 2 ph] = pixels 32 j + 16 ph .., k-step ks
-#define G192_MMA(i)                                                                                                      \
-  asm volatile("" : "+v"(wf[0]), "+v"(wf[1]), "+v"(wf[2]), "+v"(wf[3]));                                                 \
-  _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                                                                       \
-  _Pragma("unroll") for (int hh = 0; hh < 2; ++hh)                                                                       \
-  _Pragma("unroll") for (int pq = 0; pq < 4; ++pq)                                                                       \
-    acc16[i][hh][pq] = CVMI_MFMA_16X16X32(__builtin_bit_cast(f16x8, wf[ks + 2 * hh]),                                    \
-                                          __builtin_bit_cast(f16x8, xf[pq >> 1][ks + 2 * (pq & 1)]), acc16[i][hh][pq], 0, 0, 0); \
-  asm volatile("" : "+v"(acc16[i][0][0]), "+v"(acc16[i][0][1]), "+v"(acc16[i][0][2]), "+v"(acc16[i][0][3]),              \
-                    "+v"(acc16[i][1][0]), "+v"(acc16[i][1][1]), "+v"(acc16[i][1][2]), "+v"(acc16[i][1][3]));
-
   for (int kt = 0; kt < nk; ++kt) {
     const int b = kt & 1;
     const char* st = smem + b * STAGE;
     const bool more1 = kt + 1 < nk, more2 = kt + 2 < nk;
     // ---- phase 1
-    G192_READ_W(0);
-    G192_READ_X(0);
-    G192_READ_X(1);
-    if (more1) G192_WC(2, b ^ 1, kt + 1);
-    G192_SYNC_IN();
-    G192_MMA(0)
-    G192_SYNC_OUT();
+    READ_FRAG(wf, st + wbase + 0 * 32 * BKB, ko);
+    READ_FRAG(xf[0], st + xbase + 0 * 32 * BKB, ko);
+    READ_FRAG(xf[1], st + xbase + 1 * 32 * BKB, ko);
+    if (more1) G192_WC(2, b ^ 1, AT_KT, kt + 1);
+    sync_in();
+    MMA16_GROUP(wf, xf, acc16[0]);
+    sync_out();
     // ---- phase 2
-    G192_READ_W(1);
-    if (more2) { G192_X0(b, kt + 2); G192_WC(0, b, kt + 2); }
-    G192_SYNC_IN();
-    G192_MMA(1)
-    G192_SYNC_OUT();
+    READ_FRAG(wf, st + wbase + 1 * 32 * BKB, ko);
+    if (more2) { G192_X0(b, AT_KT, kt + 2); G192_WC(0, b, AT_KT, kt + 2); }
+    sync_in();
+    MMA16_GROUP(wf, xf, acc16[1]);
+    sync_out();
     // ---- phase 3
-    G192_READ_W(2);
+    READ_FRAG(wf, st + wbase + 2 * 32 * BKB, ko);
     if (more2) {
-      G192_X1(b, kt + 2); G192_WC(1, b, kt + 2);
+      G192_X1(b, AT_KT, kt + 2); G192_WC(1, b, AT_KT, kt + 2);
       asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
     } else if (more1) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
-    G192_SYNC_IN();
-    G192_MMA(2)
-    G192_SYNC_OUT();
+    sync_in();
+    MMA16_GROUP(wf, xf, acc16[2]);
+    sync_out();
   }
   if (wh == 0) __builtin_amdgcn_s_barrier();
-#undef G192_ISSUE1
-#undef G192_X0
-#undef G192_X1
-#undef G192_WC
-#undef G192_READ_X
-#undef G192_READ_W
-#undef G192_SYNC_IN
-#undef G192_SYNC_OUT
-#undef G192_MMA
 
-  // ---- f32 output + residual on a full tile (Hiera stage-3 fc2, the dominant launch): NO LDS transposition, no barriers.  In the
-  //      16x16x32 C / D layout a lane holds 4 consecutive channels of a pixel and the four lanes g = 0..3 hold 16 consecutive ones:
-  //      residual loads and stores are 64-byte row pieces as they stand.  Row statistics for the next LayerNorm (p.stats): per pixel and
-  //      96-channel slice (= this wave's channel half) the slice MEAN and the sum of squared deviations from it, two passes over the 24
-  //      values in registers -- no E[x^2] - E[x]^2 cancellation however far the row sits from zero; the consumer combines the
-  //      slices as Chan et al. do (tok_linear16.hip / tok_linear.hip, stats_parts).
+  // ---- f32 output + residual on a full tile (Hiera stage-3 fc2, the dominant launch): the direct epilogue, (acc + bias) + res
   if constexpr (sizeof(TO) == 4) {
     if (p.res && p.act == CVMI_ACT_NONE && !p.act_after_res && p.res_mod == 0 && m0 + BM <= p.M && n0 + BN <= p.N) {      // (uniform)
       const int slices = p.N / 96;
@@ -1343,19 +1264,7 @@ __global__ __launch_bounds__(512, 1) void gemm256x192_kernel(const ConvKArgs p) 
             sm += (v[i][hh][0] + v[i][hh][1]) + (v[i][hh][2] + v[i][hh][3]);
           }
         if (p.stats) {                                          // (uniform)
-          sm += __shfl_xor(sm, 16);
-          sm += __shfl_xor(sm, 32);
-          const float mean = sm * (1.0f / 96.0f);
-          float m2 = 0.f;
-#pragma unroll
-          for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int hh = 0; hh < 2; ++hh)
-#pragma unroll
-              for (int e = 0; e < 4; ++e) { const float dv = v[i][hh][e] - mean; m2 = fmaf(dv, dv, m2); }
-          m2 += __shfl_xor(m2, 16);
-          m2 += __shfl_xor(m2, 32);
-          if (g16 == 0) *reinterpret_cast<float2*>(p.stats + (m * slices + (n0 / 96 + wh)) * 2) = make_float2(mean, m2);
+          G192_ROW_STATS(v, sm, m, n0 / 96 + wh);
         }
       }
       return;
@@ -1402,14 +1311,7 @@ __global__ __launch_bounds__(512, 1) void gemm256x192_kernel(const ConvKArgs p) 
               float v[4];
 #pragma unroll
               for (int e = 0; e < 4; ++e) v[e] = actf(acc16[i][hh][pq][e] + bv[e]);
-              char* d = Ct + ml * CROWB + nl * OES;
-              if constexpr (OES == 2) {
-                f16x4 hv = {(f16)v[0], (f16)v[1], (f16)v[2], (f16)v[3]};
-                *reinterpret_cast<f16x4*>(d) = hv;
-              } else {
-                f32x4 fv = {v[0], v[1], v[2], v[3]};
-                *reinterpret_cast<f32x4*>(d) = fv;
-              }
+              tile_put4<TO>(Ct + ml * CROWB + nl * OES, v);
             }
           }
       });
@@ -1510,83 +1412,32 @@ __global__ __launch_bounds__(512, 1) void gemm256x192r_kernel(const ConvKArgs p)
   int dst[7];
 #pragma unroll
   for (int u = 0; u < 7; ++u) {
-    int row0;
-    if (u < 4) row0 = (u >> 1) * 128 + (wv * 2 + (u & 1)) * 8;
-    else row0 = BM + (wv >> 2) * 96 + (u - 4) * 32 + (wv & 3) * 8;
+    G192_ROW0(row0, u, wv);
     const int row = row0 + (lane >> 3);
     const int slot = (lane & 7) ^ ((row >> 1) & 7);
     if (row < BM) src[u] = p.x0 + ((size_t)row * p.x0_ld + slot * 8) * 2;
     else src[u] = p.w + ((size_t)(row - BM) * p.Kpad + slot * 8) * 2;
     dst[u] = row0 * BKB;
   }
-#define R192_ISSUE1(u, stage, off)                                                                                       \
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src[u] + (off)),                      \
-                                   (__attribute__((address_space(3))) void*)(smem + (stage) * STAGE + dst[u]), 16, 0, 0)
-#define R192_X0(stage, xo) do { R192_ISSUE1(0, stage, xo); R192_ISSUE1(1, stage, xo); } while (0)
-#define R192_X1(stage, xo) do { R192_ISSUE1(2, stage, xo); R192_ISSUE1(3, stage, xo); } while (0)
-#define R192_WC(k, stage, wo) R192_ISSUE1(4 + (k), stage, wo)
 
   f32x4 acc16[3][2][4];                                   // [32-channel block][16-channel half][16-pixel block]
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int hh = 0; hh < 2; ++hh)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) acc16[i][hh][q] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  clear_acc(acc16);
   f32x4 rv[6];                                            // the residual batch in flight
-#pragma unroll
-  for (int k = 0; k < 6; ++k) rv[k] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  clear_acc(rv);
 
-  const int sw = (r16 >> 1) & 7;
-  int ko[4];
-#pragma unroll
-  for (int s2 = 0; s2 < 4; ++s2) ko[s2] = (((4 * (s2 & 1) + g16) ^ sw) << 4) + (s2 >> 1) * 16 * BKB;
-  const int xbase = (wp * 64 + r16) * BKB, wbase = (BM + wh * 96 + r16) * BKB;
+  FRAG_LANE16(r16, g16, wp, wh);
 
   // stream offsets (bytes) of K-tiles g + 1 and g + 2 of the ntile x nk stream
   const long long xo0 = (long long)(tile0 / p.nb_n) * xrow, wo0 = (long long)(tile0 % p.nb_n) * wrow;
   long long xo1 = xo0 + BKB, wo1 = wo0 + BKB, xo2 = xo0 + 2 * BKB, wo2 = wo0 + 2 * BKB;
   int kt2 = 2, tl2 = tile0;                               // (g + 2) % nk and the tile K-tile g + 2 belongs to
-  R192_X0(0, xo0); R192_WC(0, 0, wo0); R192_X1(0, xo0); R192_WC(1, 0, wo0); R192_WC(2, 0, wo0);
-  R192_X0(1, xo1); R192_WC(0, 1, wo1); R192_X1(1, xo1); R192_WC(1, 1, wo1);
+  G192_X0(0, AT_OFF, xo0); G192_WC(0, 0, AT_OFF, wo0); G192_X1(0, AT_OFF, xo0); G192_WC(1, 0, AT_OFF, wo0); G192_WC(2, 0, AT_OFF, wo0);
+  G192_X0(1, AT_OFF, xo1); G192_WC(0, 1, AT_OFF, wo1); G192_X1(1, AT_OFF, xo1); G192_WC(1, 1, AT_OFF, wo1);
   asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   if (wh == 1) __builtin_amdgcn_s_barrier();
 
   u32x4 xf[2][4], wf[4];
-#define R192_READ_X(j)                                                                                                   \
-  _Pragma("unroll") for (int s2 = 0; s2 < 4; ++s2)                                                                       \
-      xf[j][s2] = *reinterpret_cast<const u32x4*>(st + xbase + (j) * 32 * BKB + ko[s2])
-#define R192_READ_W(i)                                                                                                   \
-  _Pragma("unroll") for (int s2 = 0; s2 < 4; ++s2)                                                                       \
-      wf[s2] = *reinterpret_cast<const u32x4*>(st + wbase + (i) * 32 * BKB + ko[s2])
-#define R192_SYNC_IN()                                                                                                   \
-  do {                                                                                                                   \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                                   \
-    __builtin_amdgcn_sched_barrier(0);                                                                                   \
-    __builtin_amdgcn_s_barrier();                                                                                        \
-    __builtin_amdgcn_sched_barrier(0);                                                                                   \
-    __builtin_amdgcn_s_setprio(1);                                                                                       \
-  } while (0)
-#define R192_SYNC_OUT()                                                                                                  \
-  do {                                                                                                                   \
-    __builtin_amdgcn_s_setprio(0);                                                                                       \
-    __builtin_amdgcn_sched_barrier(0);                                                                                   \
-    __builtin_amdgcn_s_barrier();                                                                                        \
-    __builtin_amdgcn_sched_barrier(0);                                                                                   \
-  } while (0)
-#define R192_MMA(i)                                                                                                      \
-  asm volatile("" : "+v"(wf[0]), "+v"(wf[1]), "+v"(wf[2]), "+v"(wf[3]));                                                 \
-  _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                                                                       \
-  _Pragma("unroll") for (int hh = 0; hh < 2; ++hh)                                                                       \
-  _Pragma("unroll") for (int pq = 0; pq < 4; ++pq)                                                                       \
-    acc16[i][hh][pq] = CVMI_MFMA_16X16X32(__builtin_bit_cast(f16x8, wf[ks + 2 * hh]),                                    \
-                                          __builtin_bit_cast(f16x8, xf[pq >> 1][ks + 2 * (pq & 1)]), acc16[i][hh][pq], 0, 0, 0); \
-  asm volatile("" : "+v"(acc16[i][0][0]), "+v"(acc16[i][0][1]), "+v"(acc16[i][0][2]), "+v"(acc16[i][0][3]),              \
-                    "+v"(acc16[i][1][0]), "+v"(acc16[i][1][1]), "+v"(acc16[i][1][2]), "+v"(acc16[i][1][3]));
-#define R192_RLOAD(k, off)                                                                                               \
-  asm volatile("global_load_dwordx4 %0, %1, off offset:" #off : "+v"(rv[k]) : "v"(rptr) : "memory")
-
   int g = 0;
 #pragma unroll 1
   for (int tl = 0; tl < ntile; ++tl) {
@@ -1620,35 +1471,40 @@ __global__ __launch_bounds__(512, 1) void gemm256x192r_kernel(const ConvKArgs p)
             for (int hh = 0; hh < 2; ++hh) acc16[i][hh][seg] += rv[2 * i + hh];
         }
         // ---- phase 1
-        R192_READ_W(0);
-        R192_READ_X(0);
-        R192_READ_X(1);
-        if (more1) R192_WC(2, b ^ 1, wo1);
-        R192_SYNC_IN();
-        R192_MMA(0)
-        R192_SYNC_OUT();
+        READ_FRAG(wf, st + wbase + 0 * 32 * BKB, ko);
+        READ_FRAG(xf[0], st + xbase + 0 * 32 * BKB, ko);
+        READ_FRAG(xf[1], st + xbase + 1 * 32 * BKB, ko);
+        if (more1) G192_WC(2, b ^ 1, AT_OFF, wo1);
+        sync_in();
+        MMA16_GROUP(wf, xf, acc16[0]);
+        sync_out();
         // ---- phase 2
-        R192_READ_W(1);
+        READ_FRAG(wf, st + wbase + 1 * 32 * BKB, ko);
         // (both X halves of stage b were read in phase 1: X1 goes out here, a phase earlier than in gemm256x192_kernel -- the A rows are the
         //  loads that come from HBM, and the loop waits on its DMA, not on the matrix pipe: r03, 181 us WITHOUT the MFMAs)
-        if (more2) { R192_X0(b, xo2); R192_X1(b, xo2); R192_WC(0, b, wo2); }
-        R192_SYNC_IN();
-        R192_MMA(1)
-        R192_SYNC_OUT();
+        if (more2) { G192_X0(b, AT_OFF, xo2); G192_X1(b, AT_OFF, xo2); G192_WC(0, b, AT_OFF, wo2); }
+        sync_in();
+        MMA16_GROUP(wf, xf, acc16[1]);
+        sync_out();
         // ---- phase 3
-        R192_READ_W(2);
-        if (more2) { R192_WC(1, b, wo2); }
+        READ_FRAG(wf, st + wbase + 2 * 32 * BKB, ko);
+        if (more2) { G192_WC(1, b, AT_OFF, wo2); }
         if (j == ji) {                                      // (uniform) six more loads in flight behind the DMA: one counted wait covers both
-          R192_RLOAD(0, 0); R192_RLOAD(1, 64); R192_RLOAD(2, 128); R192_RLOAD(3, 192); R192_RLOAD(4, 256); R192_RLOAD(5, 320);
+          asm volatile("global_load_dwordx4 %0, %1, off offset:0" : "+v"(rv[0]) : "v"(rptr) : "memory");
+          asm volatile("global_load_dwordx4 %0, %1, off offset:64" : "+v"(rv[1]) : "v"(rptr) : "memory");
+          asm volatile("global_load_dwordx4 %0, %1, off offset:128" : "+v"(rv[2]) : "v"(rptr) : "memory");
+          asm volatile("global_load_dwordx4 %0, %1, off offset:192" : "+v"(rv[3]) : "v"(rptr) : "memory");
+          asm volatile("global_load_dwordx4 %0, %1, off offset:256" : "+v"(rv[4]) : "v"(rptr) : "memory");
+          asm volatile("global_load_dwordx4 %0, %1, off offset:320" : "+v"(rv[5]) : "v"(rptr) : "memory");
           if (more2) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
           else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");          // (cannot happen for ji + 2 < nseg; kept exact anyway)
         } else {
           if (more2) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
           else if (more1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
-        R192_SYNC_IN();
-        R192_MMA(2)
-        R192_SYNC_OUT();
+        sync_in();
+        MMA16_GROUP(wf, xf, acc16[2]);
+        sync_out();
         xo1 = xo2; wo1 = wo2;
         if (++kt2 == nk) {
           kt2 = 0; tl2 += wgx;
@@ -1657,7 +1513,8 @@ __global__ __launch_bounds__(512, 1) void gemm256x192r_kernel(const ConvKArgs p)
         } else { xo2 += BKB; wo2 += BKB; }
       }
     }
-    // ---- between two tiles: + bias, row statistics, 24 stores per lane; no LDS, no barrier (the next tile's first K-tiles are landing)
+    // ---- between two tiles: the direct epilogue, (res + sum) + bias: + bias, row statistics, 24 stores per lane; no LDS, no barrier
+    //      (the next tile's first K-tiles are landing)
     {
       const int slices = p.N / 96;
 #pragma unroll
@@ -1677,35 +1534,13 @@ __global__ __launch_bounds__(512, 1) void gemm256x192r_kernel(const ConvKArgs p)
             acc16[i][hh][pq] = (f32x4){0.f, 0.f, 0.f, 0.f};
           }
         if (p.stats) {                                          // (uniform)
-          sm += __shfl_xor(sm, 16);
-          sm += __shfl_xor(sm, 32);
-          const float mean = sm * (1.0f / 96.0f);
-          float m2 = 0.f;
-#pragma unroll
-          for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int hh = 0; hh < 2; ++hh)
-#pragma unroll
-              for (int e = 0; e < 4; ++e) { const float dv = v[i][hh][e] - mean; m2 = fmaf(dv, dv, m2); }
-          m2 += __shfl_xor(m2, 16);
-          m2 += __shfl_xor(m2, 32);
-          if (g16 == 0) *reinterpret_cast<float2*>(p.stats + (m * slices + (bn * 2 + wh)) * 2) = make_float2(mean, m2);
+          G192_ROW_STATS(v, sm, m, bn * 2 + wh);
         }
       }
     }
   }
   if (wh == 0) __builtin_amdgcn_s_barrier();
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#undef R192_ISSUE1
-#undef R192_X0
-#undef R192_X1
-#undef R192_WC
-#undef R192_READ_X
-#undef R192_READ_W
-#undef R192_SYNC_IN
-#undef R192_SYNC_OUT
-#undef R192_MMA
-#undef R192_RLOAD
 }
 
 template <typename TO>
