@@ -6,6 +6,9 @@
 //   contours                   get_contours' findContours(RETR_EXTERNAL, CHAIN_APPROX_SIMPLE) (:405): union-find labelling of the
 //                              foreground (8-connected) and the background (4-connected, the frame outside the plane included), one
 //                              lane per external component tracing its border with icvFetchContour's rules, count pass + scan + write.
+//   node_connect               the contour x component-box loop of get_node_connections (:1380-1446): per (contour, box) the first contour
+//                              point that passes is_point_near_bbox (:811-846), and contourMoments' integer Green sums for the ground choice;
+//                              one workgroup per 1024-point chunk of a contour, so one long border does not serialise the launch.
 #include "common.hpp"
 
 namespace {
@@ -516,6 +519,123 @@ void fill_geom(PlaneGeom& g, int n0, int nb, const int* sizes, int stride, long 
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// 4. contours x component boxes (get_node_connections :1380-1446) and contourMoments' sums.  A contour is cut into chunks of NC_CHUNK
+// points, one workgroup each: wave w holds points [256 w, 256 w + 256) of the chunk, four per lane (point 64 j + lane in register j), so
+// the first set bit of the first non-empty ballot is the wave's first hit in contour order.
+constexpr int NC_CHUNK = 1024;                // points per workgroup
+constexpr int NC_BOX_TILE = 256;              // boxes in LDS at a time
+constexpr int NC_NONE = 0x7fffffff;           // `first` before any hit
+
+__global__ __launch_bounds__(256) void node_chunks_kernel(const int* __restrict__ info, int C, int* __restrict__ nchunks) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c < C) nchunks[c] = (max(info[8 * (size_t)c + 1], 0) + NC_CHUNK - 1) / NC_CHUNK;
+}
+
+// is_point_near_bbox (:811-846): inside the closed box, or within t of one of the four edge LINES (not of the rectangle)
+__device__ __forceinline__ bool near_box(int px, int py, int xmin, int ymin, int xmax, int ymax, int t) {
+  if (xmin <= px && px <= xmax && ymin <= py && py <= ymax) return true;
+  const long long x = px, y = py, tt = t;
+  return llabs(x - xmin) <= tt || llabs(x - xmax) <= tt || llabs(y - ymin) <= tt || llabs(y - ymax) <= tt;
+}
+
+__global__ __launch_bounds__(256) void node_connect_kernel(const int* __restrict__ info, const int* __restrict__ points, int C, int P, int N,
+                                                           const int* __restrict__ boxes, const int* __restrict__ box_start,
+                                                           const int* __restrict__ pair_start, const int* __restrict__ chunk_start,
+                                                           int* __restrict__ first, unsigned long long* __restrict__ moments) {
+  __shared__ int s_box[NC_BOX_TILE * 5];
+  __shared__ int s_min[NC_BOX_TILE];
+  __shared__ long long s_mom[4][3];
+  const int blk = blockIdx.x;
+  if (blk >= chunk_start[C]) return;
+  int lo = 0, hi = C - 1;                                 // the last contour whose first chunk is <= blk
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (chunk_start[mid] <= blk) lo = mid; else hi = mid - 1;
+  }
+  const int c = lo, k = blk - chunk_start[c];
+  const int* r = info + 8 * (size_t)c;
+  const int n = r[0], npts = r[1], off = r[2], rx = r[3], ry = r[4], rw = r[5], rh = r[6];
+  if (n < 0 || n >= N || off < 0 || npts <= 0 || (long long)off + npts > P) return;       // a record that does not describe `points`
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int* pts = points + 2 * (size_t)off;
+  int px[4], py[4];
+  bool ok[4];
+  long long a00 = 0, a10 = 0, a01 = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int i = k * NC_CHUNK + wave * 256 + j * 64 + lane;
+    ok[j] = i < npts;
+    px[j] = py[j] = 0;
+    if (ok[j]) {
+      const int ip = i ? i - 1 : npts - 1;                // the predecessor: the previous chunk's last point, or the contour's last
+      px[j] = pts[2 * (size_t)i];
+      py[j] = pts[2 * (size_t)i + 1];
+      const long long xp = pts[2 * (size_t)ip], yp = pts[2 * (size_t)ip + 1], x = px[j], y = py[j];
+      const long long dxy = xp * y - x * yp;
+      a00 += dxy;
+      a10 += dxy * (xp + x);
+      a01 += dxy * (yp + y);
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    a00 += __shfl_xor(a00, o);
+    a10 += __shfl_xor(a10, o);
+    a01 += __shfl_xor(a01, o);
+  }
+  if (lane == 0) { s_mom[wave][0] = a00; s_mom[wave][1] = a10; s_mom[wave][2] = a01; }
+  __syncthreads();
+  if (tid < 3)                                            // two's-complement wrap makes the unsigned add the signed sum
+    atomicAdd(moments + 3 * (size_t)c + tid, (unsigned long long)(s_mom[0][tid] + s_mom[1][tid] + s_mom[2][tid] + s_mom[3][tid]));
+
+  const int b0 = box_start[n];
+  const int nb = min(box_start[n + 1] - b0, pair_start[c + 1] - pair_start[c]);
+  int* out = first + pair_start[c];
+  for (int t0 = 0; t0 < nb; t0 += NC_BOX_TILE) {
+    const int tn = min(NC_BOX_TILE, nb - t0);
+    __syncthreads();                                      // the previous tile has been read
+    for (int q = tid; q < tn * 5; q += 256) s_box[q] = boxes[5 * (size_t)(b0 + t0) + q];
+    for (int q = tid; q < tn; q += 256) s_min[q] = NC_NONE;
+    __syncthreads();
+    for (int b = 0; b < tn; ++b) {
+      const int xmin = s_box[5 * b], ymin = s_box[5 * b + 1], xmax = s_box[5 * b + 2], ymax = s_box[5 * b + 3], t = s_box[5 * b + 4];
+      if (xmax < rx || xmin > rx + rw || ymax < ry || ymin > ry + rh) continue;         // broad phase (:1399-1401), no threshold
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const unsigned long long m = __ballot(ok[j] && near_box(px[j], py[j], xmin, ymin, xmax, ymax, t));
+        if (m) {                                          // wave-uniform
+          if (lane == 0) atomicMin(&s_min[b], wave * 256 + j * 64 + (__ffsll((long long)m) - 1));
+          break;
+        }
+      }
+    }
+    __syncthreads();
+    for (int q = tid; q < tn; q += 256)
+      if (s_min[q] != NC_NONE) atomicMin(out + t0 + q, k * NC_CHUNK + s_min[q]);
+  }
+}
+
+__global__ __launch_bounds__(256) void node_first_finish_kernel(int* __restrict__ first, int total) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x)
+    if (first[i] == NC_NONE) first[i] = -1;
+}
+
+struct ConnectSpace {
+  int *box_start, *pair_start, *nchunks, *chunk_start;
+};
+
+size_t carve_connect(void* base, int N, int C, ConnectSpace* w) {
+  size_t off = 0;
+  auto take = [&](size_t bytes) { void* p = base ? (char*)base + off : nullptr; off += align256(bytes); return p; };
+  ConnectSpace t;
+  t.box_start = (int*)take(4 * ((size_t)N + 1));
+  t.pair_start = (int*)take(4 * ((size_t)C + 1));
+  t.nchunks = (int*)take(4 * ((size_t)C + 1));
+  t.chunk_start = (int*)take(4 * ((size_t)C + 1));
+  if (w) *w = t;
+  return off;
+}
+
 }  // namespace
 
 extern "C" int cvmi_node_prepare(const uint8_t* src, int N, const int* sizes, const int* boxes, const int* box_start, uint8_t* emptied,
@@ -633,6 +753,39 @@ extern "C" int cvmi_external_contours(uint8_t* planes, const unsigned long long*
   hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, s, w.npts, w.pt_off, 0, counts + N, counts + N + 1);
   hipLaunchKernelGGL(trace_kernel<true>, dim3(N), b256, dyn, s, w.tab, N, w.fgm, w.roots, w.row_off, w.npts, w.pt_off, use_lds, cap_contours,
                      cap_points, counts, info, area2, points);
+  CVMI_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" size_t cvmi_node_connect_workspace(int N, int C) {
+  if (N <= 0 || C < 0) return 0;
+  return carve_connect(nullptr, N, C, nullptr);
+}
+
+extern "C" int cvmi_node_connect(const int* info, const int* points, int C, int P, const int* boxes, int N, const int* box_start,
+                                 const int* pair_start, void* workspace, size_t workspace_bytes, int* first, long long* moments,
+                                 cvmi_stream_t stream_) {
+  CVMI_CHECK(N > 0 && C >= 0 && P >= 0 && box_start && pair_start, "node_connect: bad arguments");
+  CVMI_CHECK(box_start[0] == 0 && pair_start[0] == 0, "node_connect: offsets must start at 0");
+  for (int n = 0; n < N; ++n) CVMI_CHECK(box_start[n + 1] >= box_start[n], "node_connect: box offsets of plane %d decrease", n);
+  for (int c = 0; c < C; ++c) CVMI_CHECK(pair_start[c + 1] >= pair_start[c], "node_connect: pair offsets of contour %d decrease", c);
+  if (C == 0) return 0;
+  const int pairs = pair_start[C];
+  CVMI_CHECK(info && points && moments && workspace && (box_start[N] == 0 || boxes) && (pairs == 0 || first), "node_connect: bad arguments");
+  ConnectSpace w;
+  CVMI_CHECK(carve_connect(workspace, N, C, &w) <= workspace_bytes, "node_connect: workspace of %zu bytes is short (cvmi_node_connect_workspace)",
+             workspace_bytes);
+  hipStream_t s = (hipStream_t)stream_;
+  CVMI_HIP(hipMemcpyAsync(w.box_start, box_start, 4 * ((size_t)N + 1), hipMemcpyHostToDevice, s));
+  CVMI_HIP(hipMemcpyAsync(w.pair_start, pair_start, 4 * ((size_t)C + 1), hipMemcpyHostToDevice, s));
+  CVMI_HIP(hipMemsetAsync(moments, 0, sizeof(long long) * 3 * (size_t)C, s));
+  if (pairs) CVMI_HIP(hipMemsetD32Async((hipDeviceptr_t)first, NC_NONE, (size_t)pairs, s));
+  hipLaunchKernelGGL(node_chunks_kernel, dim3(cdiv(C, 256)), dim3(256), 0, s, info, C, w.nchunks);
+  hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, s, w.nchunks, w.chunk_start, C, nullptr, nullptr);
+  const int grid = P / NC_CHUNK + C;                     // >= the sum over the contours of ceil(npts / NC_CHUNK); the rest exit at once
+  hipLaunchKernelGGL(node_connect_kernel, dim3(grid), dim3(256), 0, s, info, points, C, P, N, boxes, w.box_start, w.pair_start, w.chunk_start,
+                     first, (unsigned long long*)moments);
+  if (pairs) hipLaunchKernelGGL(node_first_finish_kernel, dim3(grid_for(pairs)), dim3(256), 0, s, first, pairs);
   CVMI_LAUNCH_CHECK();
   return 0;
 }

@@ -59,7 +59,11 @@ class CircuitPipeline:
         pipeline hands it RGB (analysis_pipeline.py:199-203) -- i.e. the reference's segmenter sees the channels reversed.
         seg_batch: images per segmenter launch (BASELINE configs[2] runs SAM 2.1-L at 16).
         nodes=True (learned prompts only): each result also carries get_node_connections' front end on its mask and boxes
-        (circuit_analyzer.py:1325-1365, wires.node_contours): "emptied_mask", "resized_bboxes", "enhanced", "contours"."""
+        (circuit_analyzer.py:1325-1365, wires.node_contours): "emptied_mask", "resized_bboxes", "enhanced", "contours".
+        nodes="connections" (learned prompts only): get_node_connections through to its node list (:1325-1583, wires.node_connections):
+        the keys of nodes=True plus "nodes" and "connection_points"."""
+        if not (isinstance(nodes, bool) or nodes == "connections"):
+            raise ValueError("nodes must be False, True or 'connections'")
         self.det, self.seg, self.tr = detector, segmenter, transforms
         self.stage2_iou, self.max_prompts, self.swap = stage2_iou, max_prompts, swap_channels
         self.crop_padding = int(crop_padding)
@@ -68,6 +72,7 @@ class CircuitPipeline:
         self.seg_batch = max(1, int(seg_batch))
         self.seg_slots = 2                         # segmenter plan instances (each with its own stream) the overlapped path alternates between
         self.nodes = bool(nodes)
+        self.node_connections = nodes == "connections"
         self.timings = defaultdict(float)          # wall seconds per phase, accumulated over calls (bench.py prints them per step)
 
     def _tick(self, name, t0):
@@ -181,16 +186,20 @@ class CircuitPipeline:
             self._add_nodes(res)
         return [(lo + i, r) for i, r in enumerate(res)]
 
-    # ---- run_node_analysis (analysis_pipeline.py:227) -> get_node_connections up to get_contours, on the masks left on the device
+    # ---- run_node_analysis (analysis_pipeline.py:227) -> get_node_connections up to get_contours (nodes=True) or to its node list
+    #      (nodes="connections"), on the masks left on the device
     def _add_nodes(self, res):
-        from .wires import node_contours
+        from .wires import node_connections, node_contours
         t = time.perf_counter()
         dev = self.seg.dev if hasattr(self.seg, "dev") else None
         with torch.cuda.device(dev if dev is not None else torch.cuda.current_device()):
-            nodes = node_contours([r["mask"] for r in res], [r["bboxes"] for r in res])
+            nodes = (node_connections if self.node_connections else node_contours)([r["mask"] for r in res], [r["bboxes"] for r in res])
         for r, n in zip(res, nodes):
             r.update(n)
-        self._tick("nodes (empty boxes + resize + enhance_lines + external contours + D2H of the points)", t)
+        if self.node_connections:
+            self._tick("nodes (empty boxes + resize + enhance_lines + external contours + D2H of the points + contour x box connections + node list)", t)
+        else:
+            self._tick("nodes (empty boxes + resize + enhance_lines + external contours + D2H of the points)", t)
 
     # ---- learned prompts, no crop: the segmenter does not depend on the detector's boxes (analysis_pipeline.py:168-225 passes the
     #      image, not the boxes, to segment_with_sam2), so the whole batch is ENQUEUED -- segmenter chunks on the segmenter's stream, the

@@ -433,6 +433,22 @@ int cvmi_external_contours(uint8_t* planes, const unsigned long long* sums, int 
                            size_t workspace_bytes, int cap_contours, int cap_points, int* counts, int* info, long long* area2,
                            int* points, cvmi_stream_t stream);
 
+/* The contour x component-box loop of get_node_connections (:1380-1446) and the contour moments of its ground choice, on the outputs of
+ * cvmi_external_contours while they are on the device.  info i32 [C, 8] / points i32 [P, 2]: as cvmi_external_contours wrote them (C, P =
+ * its totals).  boxes: DEVICE i32 [box_start[N], 5] {xmin, ymin, xmax, ymax, threshold}: resize_bboxes' ints (:461-477) of the boxes the loop
+ * visits (class not in non_components, :51), threshold = 20 / 8 / 6 by class (:1407-1415), chosen by the host.  box_start: HOST N + 1 ints,
+ * plane n owns boxes [box_start[n], box_start[n + 1]); pair_start: HOST C + 1 ints, contour c owns first[pair_start[c] .. pair_start[c + 1]),
+ * one slot per box of its plane.  workspace: DEVICE, at least cvmi_node_connect_workspace(N, C) bytes.  Outputs (DEVICE):
+ *   first i32 [pair_start[C]]: the index within the contour of the FIRST point, in contour order, that passes is_point_near_bbox (:811-846:
+ *   inside the closed box, or within threshold of one of its four edge LINES), -1 when there is none or when the broad phase skips the pair
+ *   (:1399-1401: the box against the contour's rectangle {x, y, x + w, y + h}, without threshold);
+ *   moments i64 [C, 3] {a00, a10, a01}: cv::contourMoments' sums over the closed polygon, dxy = x_prev y - x y_prev, a00 += dxy,
+ *   a10 += dxy (x_prev + x), a01 += dxy (y_prev + y), exact in int64 (equal to OpenCV's double accumulators while they stay below 2^53).
+ * One workgroup per 1024 points of a contour; the host arrays are read during the call. */
+size_t cvmi_node_connect_workspace(int N, int C);
+int cvmi_node_connect(const int* info, const int* points, int C, int P, const int* boxes, int N, const int* box_start, const int* pair_start,
+                      void* workspace, size_t workspace_bytes, int* first, long long* moments, cvmi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
