@@ -128,6 +128,9 @@ SIGNATURES = {
     "cvmi_external_contours": (_i, [_vp, _vp, _i, _vp, _i, _vp, C.c_size_t, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "cvmi_node_connect_workspace": (C.c_size_t, [_i, _i]),
     "cvmi_node_connect": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, C.c_size_t, _vp, _vp, _vp]),
+    "cvmi_segment_circuit": (_i, [_vp, C.c_size_t, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "cvmi_contour_hits_workspace": (C.c_size_t, [_i, _i]),
+    "cvmi_contour_hits": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, C.c_size_t, _vp, _vp]),
     "cvmi_upsample_refine": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, C.POINTER(_i), _i, _i, _vp]),
     "cvmi_sam2_transform": (_i, [_vp, _i, _i, _vp, _i, _i, _vp]),
     "cvmi_sam2_transform_batch": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _vp]),

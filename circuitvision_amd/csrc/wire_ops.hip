@@ -9,6 +9,10 @@
 //   node_connect               the contour x component-box loop of get_node_connections (:1380-1446): per (contour, box) the first contour
 //                              point that passes is_point_near_bbox (:811-846), and contourMoments' integer Green sums for the ground choice;
 //                              one workgroup per 1024-point chunk of a contour, so one long border does not serialise the launch.
+// Terminal reclassification (CircuitAnalyzer.reclassify_terminals_based_on_connectivity, circuit_analyzer.py:2217-2311), the step before it:
+//   segment_circuit            segment_circuit (:313-319: RGB2GRAY -> adaptiveThreshold(MEAN_C, BINARY_INV, 31, 21)) on windows of u8 RGB
+//                              images, the boxes emptied (:2244-2249) and each plane's exact sum, in one tiled pass
+//   contour_hits               node_connect without the broad phase and the moments: the contour x terminal-box table of :2272-2286
 #include "common.hpp"
 
 namespace {
@@ -539,6 +543,9 @@ __device__ __forceinline__ bool near_box(int px, int py, int xmin, int ymin, int
   return llabs(x - xmin) <= tt || llabs(x - xmax) <= tt || llabs(y - ymin) <= tt || llabs(y - ymax) <= tt;
 }
 
+// BROAD: the broad phase of get_node_connections; MOMENTS: contourMoments' sums.  <true, true> is cvmi_node_connect, <false, false> the
+// loop of reclassify_terminals_based_on_connectivity (:2279-2286), which tests every contour against every terminal.
+template <bool BROAD, bool MOMENTS>
 __global__ __launch_bounds__(256) void node_connect_kernel(const int* __restrict__ info, const int* __restrict__ points, int C, int P, int N,
                                                            const int* __restrict__ boxes, const int* __restrict__ box_start,
                                                            const int* __restrict__ pair_start, const int* __restrict__ chunk_start,
@@ -571,6 +578,7 @@ __global__ __launch_bounds__(256) void node_connect_kernel(const int* __restrict
       const int ip = i ? i - 1 : npts - 1;                // the predecessor: the previous chunk's last point, or the contour's last
       px[j] = pts[2 * (size_t)i];
       py[j] = pts[2 * (size_t)i + 1];
+      if (!MOMENTS) continue;
       const long long xp = pts[2 * (size_t)ip], yp = pts[2 * (size_t)ip + 1], x = px[j], y = py[j];
       const long long dxy = xp * y - x * yp;
       a00 += dxy;
@@ -578,15 +586,17 @@ __global__ __launch_bounds__(256) void node_connect_kernel(const int* __restrict
       a01 += dxy * (yp + y);
     }
   }
-  for (int o = 32; o > 0; o >>= 1) {
-    a00 += __shfl_xor(a00, o);
-    a10 += __shfl_xor(a10, o);
-    a01 += __shfl_xor(a01, o);
+  if (MOMENTS) {
+    for (int o = 32; o > 0; o >>= 1) {
+      a00 += __shfl_xor(a00, o);
+      a10 += __shfl_xor(a10, o);
+      a01 += __shfl_xor(a01, o);
+    }
+    if (lane == 0) { s_mom[wave][0] = a00; s_mom[wave][1] = a10; s_mom[wave][2] = a01; }
+    __syncthreads();
+    if (tid < 3)                                          // two's-complement wrap makes the unsigned add the signed sum
+      atomicAdd(moments + 3 * (size_t)c + tid, (unsigned long long)(s_mom[0][tid] + s_mom[1][tid] + s_mom[2][tid] + s_mom[3][tid]));
   }
-  if (lane == 0) { s_mom[wave][0] = a00; s_mom[wave][1] = a10; s_mom[wave][2] = a01; }
-  __syncthreads();
-  if (tid < 3)                                            // two's-complement wrap makes the unsigned add the signed sum
-    atomicAdd(moments + 3 * (size_t)c + tid, (unsigned long long)(s_mom[0][tid] + s_mom[1][tid] + s_mom[2][tid] + s_mom[3][tid]));
 
   const int b0 = box_start[n];
   const int nb = min(box_start[n + 1] - b0, pair_start[c + 1] - pair_start[c]);
@@ -599,7 +609,7 @@ __global__ __launch_bounds__(256) void node_connect_kernel(const int* __restrict
     __syncthreads();
     for (int b = 0; b < tn; ++b) {
       const int xmin = s_box[5 * b], ymin = s_box[5 * b + 1], xmax = s_box[5 * b + 2], ymax = s_box[5 * b + 3], t = s_box[5 * b + 4];
-      if (xmax < rx || xmin > rx + rw || ymax < ry || ymin > ry + rh) continue;         // broad phase (:1399-1401), no threshold
+      if (BROAD && (xmax < rx || xmin > rx + rw || ymax < ry || ymin > ry + rh)) continue;   // broad phase (:1399-1401), no threshold
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const unsigned long long m = __ballot(ok[j] && near_box(px[j], py[j], xmin, ymin, xmax, ymax, t));
@@ -634,6 +644,102 @@ size_t carve_connect(void* base, int N, int C, ConnectSpace* w) {
   t.chunk_start = (int*)take(4 * ((size_t)C + 1));
   if (w) *w = t;
   return off;
+}
+
+// ------------------------------------------------------------------------------------------------
+// 5. segment_circuit (:313-319) + the box emptying of reclassify_terminals_based_on_connectivity (:2244-2249), fused.  Plane n is an H x W
+// window of a u8 [., ., 3] image: byte src_off, row pitch in bytes; the 31 x 31 mean replicates the WINDOW's border (clamped window
+// coordinates), so nothing outside the window is read.  A 128 x 64 output tile: grey once per halo cell (halo 15) into LDS, 31-tap row sums
+// by a running sum (u16: 31 * 255 = 7905), then each thread walks 32 rows of one column with a running column sum (<= 961 * 255 = 245055).
+// cvRound(S / 961) = (2 S + 961) / 1922 in integers (961 is odd: no ties; tests/test_terminal_reclass_cpu.py checks all 245056 sums).
+constexpr int STW = 128, STH = 64, SHALO = 15, SKS = 2 * SHALO + 1;
+constexpr int SGW = STW + 2 * SHALO, SGH = STH + 2 * SHALO;      // grey cells: 158 x 94
+constexpr int SGP = 160;                                          // LDS row pitch of the grey cells
+constexpr int SSEG = 16;                                          // row-sum outputs per running sum
+constexpr int SCOL = 32;                                          // rows per thread in the column pass: 128 columns x 2 halves = 256 threads
+constexpr int SRECT_TILE = 256;                                   // rectangles in LDS at a time
+static_assert(STW * (STH / SCOL) == 256 && STW % SSEG == 0 && SGP >= SGW, "segment_circuit tile");
+
+struct SegGeom {
+  long long src_off[PLANE_MAX], dst_off[PLANE_MAX];
+  int pitch[PLANE_MAX], H[PLANE_MAX], W[PLANE_MAX], box0[PLANE_MAX], nbox[PLANE_MAX];
+};
+
+__global__ __launch_bounds__(256) void segment_circuit_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, const int* __restrict__ rects,
+                                                              unsigned long long* __restrict__ sums, const SegGeom g, int n0, int red) {
+  const int n = blockIdx.z;
+  const int H = g.H[n], W = g.W[n];
+  const int x0 = blockIdx.x * STW, y0 = blockIdx.y * STH;
+  if (x0 >= W || y0 >= H) return;
+  const uint8_t* sp = src + g.src_off[n];
+  uint8_t* dp = dst + g.dst_off[n];
+  const long long pitch = g.pitch[n];
+  __shared__ uint8_t gs[SGH][SGP];
+  __shared__ uint16_t rs[SGH][STW];
+  __shared__ int s_rect[SRECT_TILE * 4];
+  __shared__ unsigned long long part[4];
+  const int tid = threadIdx.x;
+  const int tw = min(STW, W - x0), th = min(STH, H - y0);       // the part of the tile inside the plane
+  const int gw = tw + 2 * SHALO, gh = th + 2 * SHALO;
+  // grey cell (r, c) = grey at (clamp(y0 - 15 + r), clamp(x0 - 15 + c)): RGB2Gray<uchar>, red on channel `red`, blue on 2 - red
+  for (int i = tid; i < gh * gw; i += 256) {
+    const int r = i / gw, c = i - r * gw;
+    const uint8_t* p = sp + clampi(y0 - SHALO + r, H) * pitch + 3 * clampi(x0 - SHALO + c, W);
+    gs[r][c] = (uint8_t)((p[red] * 9798 + p[1] * 19235 + p[2 - red] * 3735 + 16384) >> 15);
+  }
+  __syncthreads();
+  // rs[r][c] = gs[r][c .. c + 30]: one running sum per SSEG outputs (cells past gw are never-used outputs' inputs)
+  const int nseg = (tw + SSEG - 1) / SSEG;
+  for (int i = tid; i < gh * nseg; i += 256) {
+    const int r = i / nseg, c0 = (i - r * nseg) * SSEG;
+    int s = 0;
+#pragma unroll
+    for (int k = 0; k < SKS; ++k) s += gs[r][c0 + k];
+    rs[r][c0] = (uint16_t)s;
+#pragma unroll
+    for (int j = 1; j < SSEG; ++j) {
+      s += gs[r][c0 + j + SKS - 1] - gs[r][c0 + j - 1];
+      rs[r][c0 + j] = (uint16_t)s;
+    }
+  }
+  __syncthreads();
+  // the rectangles that empty: bit j of `kill` = pixel (x0 + c, y0 + rb + j) lies in one of them
+  const int c = tid & (STW - 1), rb = (tid >> 7) * SCOL;
+  const int b0 = g.box0[n], nb = g.nbox[n];
+  uint32_t kill = 0;
+  for (int t0 = 0; t0 < nb; t0 += SRECT_TILE) {
+    const int tn = min(SRECT_TILE, nb - t0);
+    if (t0) __syncthreads();                                     // the previous tile has been read
+    for (int q = tid; q < tn * 4; q += 256) s_rect[q] = rects[4 * (size_t)(b0 + t0) + q];
+    __syncthreads();
+    for (int b = 0; b < tn; ++b) {
+      const int rx0 = s_rect[4 * b], ry0 = s_rect[4 * b + 1], rx1 = s_rect[4 * b + 2], ry1 = s_rect[4 * b + 3];   // [x0, x1) x [y0, y1)
+      if (rx1 <= x0 || rx0 >= x0 + STW || ry1 <= y0 || ry0 >= y0 + STH) continue;                                  // block-uniform
+      if (x0 + c >= rx0 && x0 + c < rx1) {
+        const int lo = max(ry0 - (y0 + rb), 0), hi = min(ry1 - (y0 + rb), SCOL);
+        if (lo < hi) kill |= (hi - lo == 32 ? 0xffffffffu : ((1u << (hi - lo)) - 1u)) << lo;
+      }
+    }
+  }
+  unsigned cnt = 0;
+  if (c < tw && rb < th) {
+    int s = 0;
+#pragma unroll
+    for (int k = 0; k < SKS; ++k) s += rs[rb + k][c];
+    const int rows = min(SCOL, th - rb);
+    for (int j = 0; j < rows; ++j) {
+      if (j) s += rs[rb + j + SKS - 1][c] - rs[rb + j - 1][c];
+      const int mean = (2 * s + SKS * SKS) / (2 * SKS * SKS);
+      const bool on = (int)gs[rb + j + SHALO][c + SHALO] - mean <= -21 && !((kill >> j) & 1u);     // THRESH_BINARY_INV, delta 21
+      dp[(size_t)(y0 + rb + j) * W + x0 + c] = on ? (uint8_t)255 : (uint8_t)0;
+      cnt += on;
+    }
+  }
+  // exact integer plane sum: wave reduction, one 64-bit atomic per block
+  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+  if ((tid & 63) == 0) part[tid >> 6] = 255ull * cnt;
+  __syncthreads();
+  if (tid == 0) atomicAdd(sums + n0 + n, part[0] + part[1] + part[2] + part[3]);
 }
 
 }  // namespace
@@ -783,9 +889,79 @@ extern "C" int cvmi_node_connect(const int* info, const int* points, int C, int 
   hipLaunchKernelGGL(node_chunks_kernel, dim3(cdiv(C, 256)), dim3(256), 0, s, info, C, w.nchunks);
   hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, s, w.nchunks, w.chunk_start, C, nullptr, nullptr);
   const int grid = P / NC_CHUNK + C;                     // >= the sum over the contours of ceil(npts / NC_CHUNK); the rest exit at once
-  hipLaunchKernelGGL(node_connect_kernel, dim3(grid), dim3(256), 0, s, info, points, C, P, N, boxes, w.box_start, w.pair_start, w.chunk_start,
-                     first, (unsigned long long*)moments);
+  hipLaunchKernelGGL((node_connect_kernel<true, true>), dim3(grid), dim3(256), 0, s, info, points, C, P, N, boxes, w.box_start, w.pair_start,
+                     w.chunk_start, first, (unsigned long long*)moments);
   if (pairs) hipLaunchKernelGGL(node_first_finish_kernel, dim3(grid_for(pairs)), dim3(256), 0, s, first, pairs);
+  CVMI_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int cvmi_segment_circuit(const uint8_t* src, size_t src_bytes, int N, const long long* planes, int red_channel, const int* rects,
+                                    const int* box_start, uint8_t* dst, unsigned long long* sums, cvmi_stream_t stream_) {
+  CVMI_CHECK(src && planes && box_start && dst && sums && N > 0, "segment_circuit: bad arguments");
+  CVMI_CHECK(red_channel == 0 || red_channel == 2, "segment_circuit: red_channel is %d, not 0 or 2", red_channel);
+  CVMI_CHECK(box_start[0] == 0, "segment_circuit: box offsets must start at 0");
+  long long out = 0;
+  for (int n = 0; n < N; ++n) {
+    const long long *p = planes + 4 * (size_t)n, off = p[0], pitch = p[1], H = p[2], W = p[3];
+    CVMI_CHECK(H > 0 && W > 0 && H * W < (1ll << 31) && pitch >= 3 * W && pitch < (1ll << 31), "segment_circuit: plane %d is %lld x %lld with pitch %lld", n,
+               H, W, pitch);
+    CVMI_CHECK(off >= 0 && (unsigned long long)(off + (H - 1) * pitch + 3 * W) <= src_bytes, "segment_circuit: plane %d leaves the %zu source bytes", n,
+               src_bytes);
+    CVMI_CHECK(box_start[n + 1] >= box_start[n], "segment_circuit: box offsets of plane %d decrease", n);
+    out += H * W;
+  }
+  CVMI_CHECK(box_start[N] == 0 || rects, "segment_circuit: rectangles missing");
+  CVMI_CHECK(dst + out <= src || src + src_bytes <= dst, "segment_circuit: dst overlaps src");
+  hipStream_t s = (hipStream_t)stream_;
+  CVMI_HIP(hipMemsetAsync(sums, 0, sizeof(unsigned long long) * N, s));
+  long long doff = 0;
+  for (int n0 = 0; n0 < N; n0 += PLANE_MAX) {
+    const int nb = N - n0 < PLANE_MAX ? N - n0 : PLANE_MAX;
+    SegGeom g;
+    int mh = 1, mw = 1;
+    for (int n = 0; n < PLANE_MAX; ++n) {
+      const long long* p = planes + 4 * (size_t)(n0 + (n < nb ? n : 0));
+      g.src_off[n] = p[0]; g.pitch[n] = (int)p[1]; g.H[n] = n < nb ? (int)p[2] : 0; g.W[n] = n < nb ? (int)p[3] : 0;
+      g.dst_off[n] = doff;
+      g.box0[n] = n < nb ? box_start[n0 + n] : 0;
+      g.nbox[n] = n < nb ? box_start[n0 + n + 1] - box_start[n0 + n] : 0;
+      if (n < nb) {
+        doff += p[2] * p[3];
+        mh = std::max(mh, g.H[n]);
+        mw = std::max(mw, g.W[n]);
+      }
+    }
+    hipLaunchKernelGGL(segment_circuit_kernel, dim3(cdiv(mw, STW), cdiv(mh, STH), nb), dim3(256), 0, s, src, dst, rects, sums, g, n0, red_channel);
+    CVMI_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+extern "C" size_t cvmi_contour_hits_workspace(int N, int C) { return cvmi_node_connect_workspace(N, C); }
+
+extern "C" int cvmi_contour_hits(const int* info, const int* points, int C, int P, const int* boxes, int N, const int* box_start,
+                                 const int* pair_start, void* workspace, size_t workspace_bytes, int* first, cvmi_stream_t stream_) {
+  CVMI_CHECK(N > 0 && C >= 0 && P >= 0 && box_start && pair_start, "contour_hits: bad arguments");
+  CVMI_CHECK(box_start[0] == 0 && pair_start[0] == 0, "contour_hits: offsets must start at 0");
+  for (int n = 0; n < N; ++n) CVMI_CHECK(box_start[n + 1] >= box_start[n], "contour_hits: box offsets of plane %d decrease", n);
+  for (int c = 0; c < C; ++c) CVMI_CHECK(pair_start[c + 1] >= pair_start[c], "contour_hits: pair offsets of contour %d decrease", c);
+  if (C == 0 || pair_start[C] == 0) return 0;
+  const int pairs = pair_start[C];
+  CVMI_CHECK(info && points && workspace && boxes && first, "contour_hits: bad arguments");
+  ConnectSpace w;
+  CVMI_CHECK(carve_connect(workspace, N, C, &w) <= workspace_bytes, "contour_hits: workspace of %zu bytes is short (cvmi_contour_hits_workspace)",
+             workspace_bytes);
+  hipStream_t s = (hipStream_t)stream_;
+  CVMI_HIP(hipMemcpyAsync(w.box_start, box_start, 4 * ((size_t)N + 1), hipMemcpyHostToDevice, s));
+  CVMI_HIP(hipMemcpyAsync(w.pair_start, pair_start, 4 * ((size_t)C + 1), hipMemcpyHostToDevice, s));
+  CVMI_HIP(hipMemsetD32Async((hipDeviceptr_t)first, NC_NONE, (size_t)pairs, s));
+  hipLaunchKernelGGL(node_chunks_kernel, dim3(cdiv(C, 256)), dim3(256), 0, s, info, C, w.nchunks);
+  hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, s, w.nchunks, w.chunk_start, C, nullptr, nullptr);
+  const int grid = P / NC_CHUNK + C;
+  hipLaunchKernelGGL((node_connect_kernel<false, false>), dim3(grid), dim3(256), 0, s, info, points, C, P, N, boxes, w.box_start, w.pair_start,
+                     w.chunk_start, first, (unsigned long long*)nullptr);
+  hipLaunchKernelGGL(node_first_finish_kernel, dim3(grid_for(pairs)), dim3(256), 0, s, first, pairs);
   CVMI_LAUNCH_CHECK();
   return 0;
 }

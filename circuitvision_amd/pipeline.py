@@ -52,7 +52,7 @@ class CircuitPipeline:
     segmenter: `SAM2Model`-like (`infer_masks(x, boxes=None)`, `.image_size`); transforms: `SAM2Transforms`-like."""
 
     def __init__(self, detector, segmenter, transforms, stage2_iou=0.6, max_prompts=32, crop_fn=None, swap_channels=True, seg_batch=16, crop=False,
-                 crop_padding=80, nodes=False):
+                 crop_padding=80, nodes=False, reclassify=False):
         """crop=True: the reference's chain -- detector -> stage-2 NMS -> crop window from the boxes (crop.py) -> segmenter on the window
         (analysis_pipeline.py:177 -> :206); False: the segmenter sees the whole image.  crop_fn overrides the built-in crop.
         swap_channels: segment_with_sam2 applies cv2.COLOR_BGR2RGB to whatever it is given (circuit_analyzer.py:343), and the
@@ -61,7 +61,11 @@ class CircuitPipeline:
         nodes=True (learned prompts only): each result also carries get_node_connections' front end on its mask and boxes
         (circuit_analyzer.py:1325-1365, wires.node_contours): "emptied_mask", "resized_bboxes", "enhanced", "contours".
         nodes="connections" (learned prompts only): get_node_connections through to its node list (:1325-1583, wires.node_connections):
-        the keys of nodes=True plus "nodes" and "connection_points"."""
+        the keys of nodes=True plus "nodes" and "connection_points".
+        reclassify=True (any prompts mode): run_terminal_reclassification (analysis_pipeline.py:117-137, wires.reclassify_terminals) runs
+        after the segmenter and before node analysis, on the image the segmenter saw and its boxes, with the detector's names: a 'terminal'
+        box that touches two or more wire contours becomes 'voltage.dc'.  "bboxes" are the rewritten boxes (node analysis reads them) and
+        each result gains "terminal_connections": {box index: connected contours}."""
         if not (isinstance(nodes, bool) or nodes == "connections"):
             raise ValueError("nodes must be False, True or 'connections'")
         self.det, self.seg, self.tr = detector, segmenter, transforms
@@ -73,6 +77,7 @@ class CircuitPipeline:
         self.seg_slots = 2                         # segmenter plan instances (each with its own stream) the overlapped path alternates between
         self.nodes = bool(nodes)
         self.node_connections = nodes == "connections"
+        self.reclassify = bool(reclassify)
         self.timings = defaultdict(float)          # wall seconds per phase, accumulated over calls (bench.py prints them per step)
 
     def _tick(self, name, t0):
@@ -182,9 +187,29 @@ class CircuitPipeline:
         else:
             bboxes = self.detect(mine)
             res = self.segment(mine, bboxes, prompts)
+            if self.reclassify:
+                self._reclassify(res)
         if self.nodes:
             self._add_nodes(res)
         return [(lo + i, r) for i, r in enumerate(res)]
+
+    # ---- run_terminal_reclassification (analysis_pipeline.py:117-137).  The image it is handed is the one the segmenter was handed; its
+    #      BGR2RGB and the method's RGB2BGR cancel, so cvtColor(RGB2GRAY)'s R weight falls on channel 0 of that image.
+    def _reclassify(self, res, src=None, windows=None):
+        """res: result dicts of one chunk.  src / windows: the detector's u8 device block and the crop windows (the cropped chain), read in
+        place; otherwise every r["image"] is uploaded."""
+        from .wires import reclassify_terminals
+        t = time.perf_counter()
+        dev = self.seg.dev if hasattr(self.seg, "dev") else None
+        with torch.cuda.device(dev if dev is not None else torch.cuda.current_device()):
+            bbs = [r["bboxes"] for r in res]
+            if src is not None:
+                counts = reclassify_terminals(src, bbs, self.det.names, red_channel=0, windows=windows)
+            else:
+                counts = reclassify_terminals([r["image"] for r in res], bbs, self.det.names, red_channel=0)
+        for r, c in zip(res, counts):
+            r["terminal_connections"] = c
+        self._tick("reclassify (segment_circuit + empty boxes + external contours + contour x terminal hits + class rewrite)", t)
 
     # ---- run_node_analysis (analysis_pipeline.py:227) -> get_node_connections up to get_contours (nodes=True) or to its node list
     #      (nodes="connections"), on the masks left on the device
@@ -230,6 +255,8 @@ class CircuitPipeline:
                 out.append({"image": im, "bboxes": bboxes[k], "mask": u8s[b], "extent": exts[b], "iou": iou[b]})
                 k += 1
         self._tick("wait: segmenter (GPU time not hidden behind host work) + extents to the host", t)
+        if self.reclassify:
+            self._reclassify(out)
         return out
 
     # ---- learned prompts WITH the reference's crop: the segmenter's input depends on the detector's boxes (analysis_pipeline.py:177 -> :206).
@@ -258,9 +285,9 @@ class CircuitPipeline:
                 wins.append(win)
                 metas.append((adjust_bboxes(bb, win), info))
             t = self._tick("glue (dicts + round + uid + stage-2 NMS + crop window + box shift)" + (", overlapped with the GPU" if k else ", chunk 0: not hidden"), t)
-            pend.append((idxs, wins, metas, self._enqueue_learned(None, k % self.seg_slots, src=h.src, windows=wins, det_stream=self.det.stream)))
+            pend.append((idxs, wins, metas, h.src, self._enqueue_learned(None, k % self.seg_slots, src=h.src, windows=wins, det_stream=self.det.stream)))
             t = self._tick("enqueue: segmenter chunk (transform from the windows of the detector's u8 block + SAM 2.1 graph + post-process)", t)
-        for idxs, wins, metas, fin in pend:
+        for idxs, wins, metas, _src, fin in pend:
             u8s, exts, iou = fin()
             for b, i in enumerate(idxs):
                 im, wnd = images[i], wins[b]
@@ -268,6 +295,9 @@ class CircuitPipeline:
                 out[i] = {"image": view, "bboxes": metas[b][0], "mask": u8s[b], "extent": exts[b], "iou": iou[b], "window": wnd,
                           "crop_debug_info": metas[b][1]}
         self._tick("wait: segmenter (GPU time not hidden behind host work) + extents to the host", t)
+        if self.reclassify:                                                # the windows of the detector's u8 block, still in HBM
+            for idxs, wins, _metas, src, _fin in pend:
+                self._reclassify([out[i] for i in idxs], src=src, windows=wins)
         return out
 
     def _enqueue_learned(self, imgs, slot=0, src=None, windows=None, det_stream=None):

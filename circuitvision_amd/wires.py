@@ -10,6 +10,13 @@ reference runs per image on the host through OpenCV (run_node_analysis, src/anal
     contours x component boxes          :1374-1446   cvmi_node_connect     (first near point per (contour, box) + contourMoments' sums)
     valid nodes, ground, renumbering    :1451-1583   assemble_nodes, on the host
 
+The step before it, run_terminal_reclassification (src/analysis_pipeline.py:117-137), rewrites the box list node analysis reads:
+
+    segment_circuit + box emptying      :313-319, :2244-2249   cvmi_segment_circuit   (grey -> 31 x 31 mean -> threshold, fused, + plane sums)
+    get_contours(0.0001)                :2254                  cvmi_external_contours + the area filter on the host
+    terminal x contour loop             :2272-2286             cvmi_contour_hits      (cvmi_node_connect without broad phase and moments)
+    the >= 2 rule and the rewrite       :2288-2308             reclassify_terminals, on the host
+
 A batch stays in HBM until it comes back as contour points (and, for node_connections, the first-hit table and the moment sums).  `contour_img`, the drawing get_contours returns second (drawContours +
 putText), is NOT rendered: a zero uint8 [H, W, 3] canvas stands in for it, so that callers that take `.copy()` of it run unchanged.
 The same holds for the two drawings get_node_connections adds (:1584-1603).  generate_netlist_from_nodes and what follows stay on the host.
@@ -257,6 +264,191 @@ def assemble_nodes(contours, boxes, visited, first, sums):
         for i in sorted(valid):
             out.append({"id": len(out), "components": valid[i]["components"], "contour": valid[i]["contour"]})
     return out, points
+
+
+# ---- terminal reclassification (circuit_analyzer.py:2217-2311) ----------------------------------------------------------------
+RECLASS_NEAR = 10                                                     # pixel_threshold_for_reclass :2277
+RECLASS_AREA = 0.0001                                                 # get_contours' threshold at :2254
+
+
+def emptying_rects(bboxes, H, W):
+    """:2244-2249 as plain rectangles: numpy resolves mask[max(0, ymin):min(H, ymax), max(0, xmin):min(W, xmax)] -- without a ymin < ymax
+    guard a negative ymax / xmax counts from the end -- so slice.indices gives the rows and columns it writes.  -> [[x0, y0, x1, y1]],
+    half-open, non-empty."""
+    out = []
+    for b in bboxes:
+        if b.get("class") in PRESERVED:
+            continue
+        y0, y1, _ = slice(max(0, int(b["ymin"])), min(H, int(b["ymax"]))).indices(H)
+        x0, x1, _ = slice(max(0, int(b["xmin"])), min(W, int(b["xmax"]))).indices(W)
+        if y0 < y1 and x0 < x1:
+            out.append([x0, y0, x1, y1])
+    return out
+
+
+def segment_packed(src, planes, rects, red_channel=0):
+    """cvmi_segment_circuit.  src: a flat u8 device buffer; planes: [(byte offset, pitch in bytes, H, W)] windows of u8 [., ., 3] images in
+    it; rects: per plane [[x0, y0, x1, y1]] (emptying_rects).  -> (packed u8 masks, exact plane sums as int64 [N]), on the device."""
+    lib = _lib.load()
+    N = len(planes)
+    geom = np.ascontiguousarray(np.asarray(planes, dtype=np.int64).reshape(N, 4))
+    start = np.concatenate(([0], np.cumsum([len(r) for r in rects]))).astype(np.int32)
+    rows = [r for rr in rects for r in rr]
+    rdev = torch.tensor(rows, dtype=torch.int32).reshape(-1, 4).to(src.device) if rows else None
+    dst = torch.empty(int((geom[:, 2] * geom[:, 3]).sum()), dtype=torch.uint8, device=src.device)
+    sums = torch.empty(N, dtype=torch.int64, device=src.device)
+    _lib.check(lib.cvmi_segment_circuit(src.data_ptr(), src.numel(), N, geom.ctypes.data, int(red_channel), rdev.data_ptr() if rdev is not None else None,
+                                        start.ctypes.data, dst.data_ptr(), sums.data_ptr(), _stream()), "segment_circuit")
+    return dst, sums
+
+
+def hits_packed(info, points, boxes, box_start, pair_start):
+    """cvmi_contour_hits on the device outputs of contours_packed(keep_device=True): connect_packed without the broad phase and the
+    moments.  -> first i32 [pair_start[C]] on the device."""
+    lib = _lib.load()
+    dev = info.device
+    C, P = int(info.shape[0]), int(points.shape[0])
+    box_start = np.ascontiguousarray(box_start, dtype=np.int32)
+    pair_start = np.ascontiguousarray(pair_start, dtype=np.int32)
+    N = len(box_start) - 1
+    if len(pair_start) != C + 1:
+        raise ValueError(f"pair_start has {len(pair_start)} entries for {C} contours")
+    rows = np.asarray(boxes, dtype=np.int64).reshape(-1, 5)
+    if len(rows) != int(box_start[-1]):
+        raise ValueError(f"{len(rows)} boxes for box offsets that end at {int(box_start[-1])}")
+    if len(rows) and np.abs(rows).max() >= 2 ** 30:
+        raise ValueError("a box coordinate does not fit the kernel's int32 arithmetic")
+    bdev = torch.from_numpy(rows.astype(np.int32)).to(dev) if len(rows) else None
+    first = torch.empty(max(int(pair_start[-1]), 1), dtype=torch.int32, device=dev)
+    ws_bytes = int(lib.cvmi_contour_hits_workspace(N, C))
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    _lib.check(lib.cvmi_contour_hits(info.data_ptr(), points.data_ptr(), C, P, bdev.data_ptr() if bdev is not None else None, N,
+                                     box_start.ctypes.data, pair_start.ctypes.data, ws.data_ptr(), ws_bytes, first.data_ptr(), _stream()), "contour_hits")
+    return first[:int(pair_start[-1])]
+
+
+def _rgb_planes(images, windows):
+    """-> (flat u8 device buffer, [(byte offset, pitch, H, W)])."""
+    if windows is not None:                                           # rectangles of one u8 [B, H, W, 3] device block, read in place
+        if not torch.is_tensor(images) or images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3 or not images.is_cuda \
+                or not images.is_contiguous() or len(windows) != images.shape[0]:
+            raise ValueError("with windows, images is one contiguous uint8 [B, H, W, 3] device block and windows has B entries")
+        _, H, W, _ = images.shape
+        planes = []
+        for b, w in enumerate(windows):
+            x0, y0, x1, y1 = (0, 0, W, H) if w is None else (int(v) for v in w)
+            if not (0 <= x0 < x1 <= W and 0 <= y0 < y1 <= H):
+                raise ValueError(f"window {b} = {w} leaves the {H} x {W} image")
+            planes.append(((b * H + y0) * W * 3 + x0 * 3, W * 3, y1 - y0, x1 - x0))
+        return images.view(-1), planes
+    flat, planes, off = [], [], 0
+    for im in images:
+        if isinstance(im, np.ndarray):
+            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
+                raise ValueError(f"expected a uint8 [H, W, 3] image, got {im.dtype} {im.shape}")
+            im = torch.from_numpy(np.ascontiguousarray(im)).to(_dev())
+        elif not torch.is_tensor(im) or im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3 or not im.is_cuda:
+            raise ValueError("expected a uint8 [H, W, 3] numpy image or device tensor")
+        H, W = int(im.shape[0]), int(im.shape[1])
+        flat.append(im.contiguous().view(-1))
+        planes.append((off, W * 3, H, W))
+        off += H * W * 3
+    return (flat[0] if len(flat) == 1 else torch.cat(flat)), planes
+
+
+def _dc_id(names):
+    for num_id, name in (names.items() if hasattr(names, "items") else enumerate(names)):      # :2263-2267
+        if name == "voltage.dc":
+            return num_id
+    return None
+
+
+def reclassify_terminals(images, bboxes, names, red_channel=0, windows=None, events=None):
+    """reclassify_terminals_based_on_connectivity (circuit_analyzer.py:2229-2308) for a batch.  images: u8 [H_i, W_i, 3] device tensors
+    or numpy arrays, or -- with windows = [(x0, y0, x1, y1) | None] -- one u8 [B, H, W, 3] device block whose rectangles are the planes
+    (read in place).  red_channel: the channel of `images` that takes cvtColor(RGB2GRAY)'s R weight: 0 for the image
+    run_terminal_reclassification is handed (it swaps, and the method swaps back), 2 for the method's own argument.
+    names: the detector's {id: name} (self.yolo.model.names).  Only images with a 'terminal' box are processed: segment + empty
+    (cvmi_segment_circuit), contours, the hit table, then the host rule.  The box dicts are rewritten IN PLACE (:2297-2308).
+    -> per image {box index: number of connected contours} for its terminals.
+    A terminal's coordinates must be integral-valued (the pipeline's are): the kernel tests in integers.
+    events: optional list that receives (name, torch.cuda.Event) pairs around the sub-stages (tools/terminal_reclass_bench.py)."""
+    n_img = len(windows) if windows is not None else len(images)
+    if len(bboxes) != n_img:
+        raise ValueError(f"{len(bboxes)} box lists for {n_img} images")
+    out = [{} for _ in range(n_img)]
+    terms = [[k for k, b in enumerate(bb) if b.get("class") == "terminal"] for bb in bboxes]
+    for bb, tk in zip(bboxes, terms):
+        for k in tk:
+            for key in ("xmin", "ymin", "xmax", "ymax"):
+                if bb[k][key] != int(bb[k][key]):
+                    raise ValueError(f"terminal box {k} has {key} = {bb[k][key]!r}: the device test needs integral-valued coordinates")
+    sel = [i for i in range(n_img) if terms[i]]
+    if not sel:
+        return out
+
+    def mark(name):
+        if events is not None:
+            e = torch.cuda.Event(enable_timing=True)
+            e.record()
+            events.append((name, e))
+    if windows is not None:
+        src, planes = _rgb_planes(images, windows)
+        planes = [planes[i] for i in sel]
+    else:
+        src, planes = _rgb_planes([images[i] for i in sel], None)
+    shapes = [(h, w) for _, _, h, w in planes]
+    mark("start")
+    masks, sums = segment_packed(src, planes, [emptying_rects(bboxes[i], h, w) for i, (h, w) in zip(sel, shapes)], red_channel)
+    mark("segment")
+    pc, info_dev, points_dev = contours_packed(masks, shapes, sums, binarize=True, keep_device=True)
+    mark("contours")
+    rows = [[int(bboxes[i][k]["xmin"]), int(bboxes[i][k]["ymin"]), int(bboxes[i][k]["xmax"]), int(bboxes[i][k]["ymax"]), RECLASS_NEAR] for i in sel for k in terms[i]]
+    box_start = np.concatenate(([0], np.cumsum([len(terms[i]) for i in sel]))).astype(np.int32)
+    per_plane = np.asarray(pc.counts[:len(sel)], dtype=np.int64)
+    pair_start = np.concatenate(([0], np.cumsum(np.repeat(np.diff(box_start), per_plane)))).astype(np.int64)
+    if pair_start[-1] >= 2 ** 31:
+        raise ValueError(f"{int(pair_start[-1])} (contour, box) pairs exceed the int32 offsets")
+    first = hits_packed(info_dev, points_dev, rows, box_start, pair_start)
+    mark("hits")
+    first = first.cpu().numpy()
+    dc = _dc_id(names)
+    c0 = 0
+    for j, i in enumerate(sel):
+        h, w = shapes[j]
+        kept = []
+        contour_dicts(pc.plane(j), h, w, RECLASS_AREA, kept)          # get_contours' area filter :410
+        nb = len(terms[i])
+        hit = np.zeros(nb, dtype=np.int64)
+        for k in kept:
+            hit += first[pair_start[c0 + k]:pair_start[c0 + k] + nb] >= 0
+        c0 += int(pc.counts[j])
+        for t, k in enumerate(terms[i]):
+            out[i][k] = int(hit[t])
+            if hit[t] >= 2:                                           # :2293-2308
+                b = bboxes[i][k]
+                b["original_yolo_class_if_reclassified"] = b["class"]
+                b["class"] = "voltage.dc"
+                if dc is not None:
+                    b["_yolo_class_id_temp"] = dc
+                b["was_reclassified_from_terminal"] = True
+    return out
+
+
+def segment_circuit(img):
+    """CircuitAnalyzer.segment_circuit (circuit_analyzer.py:313-319) on a u8 [H, W, 3] numpy image (-> numpy) or device tensor (-> tensor):
+    cvtColor(RGB2GRAY), the R weight on channel 0, then adaptiveThreshold(255, MEAN_C, BINARY_INV, 31, 21).  -> u8 [H, W], 0 / 255."""
+    src, planes = _rgb_planes([img], None)
+    masks, _ = segment_packed(src, planes, [[]], 0)
+    m = masks.view(planes[0][2], planes[0][3])
+    return m.cpu().numpy() if isinstance(img, np.ndarray) else m
+
+
+def reclassify_terminals_based_on_connectivity(image_rgb_original, bboxes_list_to_modify, names):
+    """CircuitAnalyzer.reclassify_terminals_based_on_connectivity (circuit_analyzer.py:2217-2311): the method's cvtColor(RGB2BGR) in front of
+    segment_circuit puts the R weight on channel 2 of its argument.  `names` stands for self.yolo.model.names.  Rewrites the list's dicts in
+    place and returns None, as the reference does."""
+    reclassify_terminals([image_rgb_original], [bboxes_list_to_modify], names, red_channel=2)
 
 
 # ---- the reference's two methods ----------------------------------------------------------------------------------------------

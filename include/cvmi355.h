@@ -449,6 +449,33 @@ size_t cvmi_node_connect_workspace(int N, int C);
 int cvmi_node_connect(const int* info, const int* points, int C, int P, const int* boxes, int N, const int* box_start, const int* pair_start,
                       void* workspace, size_t workspace_bytes, int* first, long long* moments, cvmi_stream_t stream);
 
+/* ---- terminal reclassification (CircuitAnalyzer.reclassify_terminals_based_on_connectivity, circuit_analyzer.py:2217-2311), the step
+ * between the segmenter and node analysis (run_terminal_reclassification, analysis_pipeline.py:117-137). */
+
+/* segment_circuit (:313-319) and the box emptying (:2244-2249) on N windows of u8 [., ., 3] images in ONE buffer, in one launch per 32
+ * planes: cv2.cvtColor(RGB2GRAY) = (R 9798 + G 19235 + B 3735 + 16384) >> 15 with R read from channel red_channel (0 or 2) and B from
+ * 2 - red_channel; cv2.adaptiveThreshold(255, ADAPTIVE_THRESH_MEAN_C, THRESH_BINARY_INV, 31, 21): mean = the normalised 31 x 31 box filter,
+ * u8, rounded half to even (no ties: 961 is odd), border REPLICATED AT THE WINDOW's edge (no pixel outside the window is read);
+ * dst = 255 where grey - mean <= -21, else 0; then 0 inside every rectangle of the plane.
+ *   src: DEVICE, src_bytes long (every window is checked against it).  planes: HOST i64 [N, 4] {byte offset of the window's first pixel, row
+ *   pitch in BYTES (>= 3 W, any alignment), H, W}, H W < 2^31.  rects: DEVICE i32 [box_start[N], 4] {x0, y0, x1, y1}, half-open, in window
+ *   pixels (the host resolves the reference's numpy slices, negative stops included, and drops the empty ones); plane n owns rectangles
+ *   [box_start[n], box_start[n + 1]) (HOST, N + 1 ints).  The host arrays are read during the call.
+ *   dst: DEVICE u8, the N planes packed back to back (plane n at the sum of its predecessors' H W), must not overlap src.
+ *   sums: DEVICE u64 [N], zeroed by this call, each plane's exact pixel sum of dst (what cvmi_external_contours' inversion test reads). */
+int cvmi_segment_circuit(const uint8_t* src, size_t src_bytes, int N, const long long* planes, int red_channel, const int* rects,
+                         const int* box_start, uint8_t* dst, unsigned long long* sums, cvmi_stream_t stream);
+
+/* The contour x terminal-box loop of :2272-2286 on the outputs of cvmi_external_contours: cvmi_node_connect WITHOUT its broad phase (every
+ * contour is tested against every box of its plane, so a contour far from a box but within threshold of one of its edge lines counts) and
+ * without the moments.  Arguments and layout as cvmi_node_connect: boxes DEVICE i32 [box_start[N], 5] {xmin, ymin, xmax, ymax, threshold}
+ * (the reference's threshold here is 10), box_start / pair_start HOST, workspace DEVICE of at least cvmi_contour_hits_workspace(N, C)
+ * bytes.  Output first i32 [pair_start[C]] (DEVICE, written entirely by this call): the index of the first point of the contour that passes
+ * is_point_near_bbox, or -1.  Nothing is launched when there is no contour or no pair. */
+size_t cvmi_contour_hits_workspace(int N, int C);
+int cvmi_contour_hits(const int* info, const int* points, int C, int P, const int* boxes, int N, const int* box_start, const int* pair_start,
+                      void* workspace, size_t workspace_bytes, int* first, cvmi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
