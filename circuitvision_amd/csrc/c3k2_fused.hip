@@ -382,6 +382,7 @@ int launch_c3k2(C3Args& a, int B, hipStream_t stream) {
   a.ntiles = B * a.tiles_y * a.tiles_x;
   CVMI_CHECK(a.ntiles > 0, "c3k2: bad grid");
   const int grid = a.ntiles < ncu * wgs_per_cu ? a.ntiles : ncu * wgs_per_cu;
+  cvmi_note_kernel("c3k2_kernel<%d, %d, %d, %d>", C, HR, C2, C1);
   hipLaunchKernelGGL((c3k2_kernel<C, HR, C2, C1>), dim3((unsigned)grid), dim3(C == 16 ? 256 : 512), G::LDS, stream, a);
   CVMI_LAUNCH_CHECK();
   return 0;

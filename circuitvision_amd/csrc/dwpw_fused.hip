@@ -284,6 +284,7 @@ int launch_dwpw(DwPwArgs& a, int B, hipStream_t stream) {
   }
   const long long blocks = (long long)B * a.tiles_y * a.tiles_x;
   CVMI_CHECK(blocks > 0 && blocks < (1ll << 31), "dwpw: bad grid");
+  cvmi_note_kernel("dwpw_kernel<%d, %d, %d, %d>", CC, NCHUNK, N1P, N2P);
   hipLaunchKernelGGL((dwpw_kernel<CC, NCHUNK, N1P, N2P>), dim3((unsigned)blocks), dim3(256), lds, stream, a);
   CVMI_LAUNCH_CHECK();
   return 0;

@@ -173,6 +173,7 @@ extern "C" int cvmi_stem2(const void* x, int x_ld, const void* w0, const float* 
   const long long blocks = (long long)B * a.tiles_y * a.tiles_x;
   CVMI_CHECK(blocks > 0 && blocks < (1ll << 31), "stem2: bad grid");
   constexpr size_t lds = (size_t)2 * PPLANE + (size_t)4 * TPLANE + 64 * sizeof(float);
+  cvmi_note_kernel("stem2_kernel");
   hipLaunchKernelGGL(stem2_kernel, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream_, a);
   CVMI_LAUNCH_CHECK();
   return 0;

@@ -9,6 +9,9 @@ cvmi_last_kernel() must name (igemm.hip launch_typed / launch_cfg / launch_glds 
 operand type, and the bf16 build has no conv_tile path, so `expect` is a string with a {T} placeholder (the operand type as the tag spells it)
 or a dict per dtype of such strings.
 
+FUSED_ROWS: the fused YOLO11 kernels.  One row = one launch of cvmi_c3k2, cvmi_stem2 or cvmi_dwpw, the tag it must report (launch_c3k2 / launch_dwpw /
+cvmi_stem2 tag the instance as the template is written) and its options; operands, references and the tolerance live in tests/fused_ref.py.
+
 BF16_OPS: every entry point that common.hpp builds twice (CVMI_ENTRY) -> (test module, test function) that checks its bf16 build per op.
 
 Plain data: importing this module needs neither a GPU nor the library."""
@@ -296,4 +299,89 @@ BF16_OPS = {
     "cvmi_tok_linear_pool_stats": ("test_ops_gpu.py", "test_tok_linear_pool_vs_torch"),
     "cvmi_tok_linear16_launch": ("test_ops_gpu.py", "test_tok_linear16_row_blocks_shared_between_workgroups"),
     "cvmi_tok_linear16_splits": ("test_ops_gpu.py", "test_tok_linear16_row_blocks_shared_between_workgroups"),
+}
+
+
+# ---- the fused YOLO11 kernels: c3k2_fused.hip, stem_fused.hip, dwpw_fused.hip ----------------------------------------------------------------
+C3K2_INSTANCES = ((16, 8, 64, 32), (32, 16, 128, 64), (16, 8, 64, 0), (32, 16, 64, 0), (32, 16, 128, 0))      # c3k2_kernel<C, HR, C2, C1>
+C3K2_TILE = (8, 16)                                                                                         # output pixels of one workgroup tile
+
+
+def c3k2_tag(inst):
+    return "c3k2_kernel<%d, %d, %d, %d>" % inst
+
+
+def c3k2_max_wgs_per_cu(inst):
+    """Hardware ceiling of resident workgroups per CU (8 waves per SIMD): 8 for the 256-thread instances (c = 16), 4 for the 512-thread ones."""
+    return 8 if inst[0] == 16 else 4
+
+
+def dwpw_tag(cc, nchunk, n1p, n2p):
+    return "dwpw_kernel<%d, %d, %d, %d>" % (cc, nchunk, n1p, n2p)
+
+
+def _c3(suffix, inst, B, H, W, shortcut=1, x_off=0, x_extra=0, y_guard=0, note=""):
+    """One cvmi_c3k2 launch on an NHWC [B, H, W, C1 or 2 C] input.  B = "persist": chosen on the device so that EVERY workgroup of the persistent
+    grid runs at least two tiles and the tiles do not divide evenly (test_fused_matrix_gpu.persistent_batch; k = the ceiling above).  x_off /
+    x_extra: the input sits at channel x_off of a buffer x_extra channels wider; y_guard: zeroed channels on both sides of the output."""
+    return dict(kernel="c3k2", id="c3k2_%d_%d_%d_%d_%s" % (inst + (suffix,)), expect=c3k2_tag(inst), inst=inst, B=B, H=H, W=W, shortcut=shortcut,
+                x_off=x_off, x_extra=x_extra, y_guard=y_guard, k=c3k2_max_wgs_per_cu(inst) if B == "persist" else 0, note=note)
+
+
+def _st(rid, H2, W2, B=2, x_ld=16, y_guard=0, note=""):
+    """One cvmi_stem2 launch on the space-to-depth(2) grid [B, H2, W2, 16 of x_ld] of a [B, 3, 2 H2, 2 W2] image."""
+    return dict(kernel="stem2", id="stem2_" + rid, expect="stem2_kernel", B=B, H=H2, W=W2, x_off=0, x_extra=x_ld - 16, y_guard=y_guard, note=note)
+
+
+def _dw(rid, expect, C, N1, N2, H=9, W=17, B=2, x_off=0, x_extra=0, y_guard=0, note=""):
+    """One cvmi_dwpw launch: depthwise 3x3 over C channels, pointwise to N1, chained class conv to N2 (0 = none)."""
+    return dict(kernel="dwpw", id="dwpw_" + rid, expect=expect, C=C, N1=N1, N2=N2, B=B, H=H, W=W, x_off=x_off, x_extra=x_extra, y_guard=y_guard, note=note)
+
+
+FUSED_ROWS = []
+for _inst in C3K2_INSTANCES:
+    FUSED_ROWS += [
+        _c3("8x16", _inst, 3, 8, 16, note="one whole tile: every halo pixel is outside the image"),
+        _c3("1x1", _inst, 3, 1, 1, y_guard=8),
+        _c3("7x15", _inst, 3, 7, 15, note="one row and column short of a tile"),
+        _c3("9x17", _inst, 3, 9, 17, note="one pixel into a second tile row and column: both halos partly outside on every side"),
+        _c3("19x37", _inst, 2, 19, 37, x_off=8, x_extra=16, y_guard=8, note="3 x 3 tiles, one interior; last row 3 of 8, last column 5 of 16"),
+        _c3("9x17_noshort", _inst, 3, 9, 17, shortcut=0),
+        _c3("persist", _inst, "persist", 19, 37, note="the persistent tile loop: prefetch, pmask, patch landing over the output tile"),
+    ]
+FUSED_ROWS += [
+    _st("16x32", 16, 32, note="exactly one tile: halo column 32 is outside"),
+    _st("1x1", 1, 1, B=3),
+    _st("15x31", 15, 31, note="odd grid one short of a tile: OH = 8, OW = 16"),
+    _st("17x33", 17, 33, note="odd grid one past a tile: OH = 9, OW = 17"),
+    _st("21x27_ld24", 21, 27, x_ld=24),
+    _st("34x66_guard", 34, 66, y_guard=8, note="OH = 17, OW = 33: 3 x 3 tiles"),
+    # ---- dwpw: the eight instances by tag
+    _dw("c64_n64", dwpw_tag(64, 1, 64, 0), 64, 64, 0),
+    _dw("c128_n64", dwpw_tag(64, 2, 64, 0), 128, 64, 0),
+    _dw("c256_n64", dwpw_tag(64, 4, 64, 0), 256, 64, 0),
+    _dw("c64_n80", dwpw_tag(64, 1, 96, 0), 64, 80, 0),
+    _dw("c128_n80", dwpw_tag(64, 2, 96, 0), 128, 80, 0, y_guard=8),
+    _dw("c256_n96", dwpw_tag(64, 4, 96, 0), 256, 96, 0),
+    _dw("c64_n64_cls62", dwpw_tag(64, 1, 64, 64), 64, 64, 62, note="ragged channel tail: 62 of 64"),
+    _dw("c80_n80_cls62", dwpw_tag(80, 1, 96, 64), 80, 80, 62, y_guard=8),
+    # ---- widths, sizes, layout
+    _dw("n1_8", dwpw_tag(64, 1, 64, 0), 64, 8, 0, y_guard=8),
+    _dw("cls64", dwpw_tag(64, 1, 64, 64), 64, 64, 64),
+    _dw("cls8", dwpw_tag(80, 1, 96, 64), 80, 80, 8),
+    _dw("1x1", dwpw_tag(64, 2, 96, 0), 128, 80, 0, H=1, W=1, B=3),
+    _dw("8x16", dwpw_tag(64, 4, 64, 0), 256, 64, 0, H=8, W=16, note="one whole tile"),
+    _dw("19x37_xoff", dwpw_tag(64, 2, 64, 0), 128, 64, 0, H=19, W=37, x_off=8, x_extra=16, y_guard=8, note="3 x 3 tiles; input inside a wider buffer"),
+]
+del _inst
+
+# mutant of tests/fused_ref.py -> ids of the rows that must catch it (tests/test_fused_ref_cpu.py)
+FUSED_MUTANT_ROWS = {
+    "t_from_padded_b": [r["id"] for r in FUSED_ROWS if r["kernel"] == "c3k2" and r["id"].endswith(("_9x17", "_1x1"))],
+    "ab_bias_outside": [r["id"] for r in FUSED_ROWS if r["kernel"] == "c3k2" and r["inst"][3] and r["id"].endswith(("_9x17", "_1x1"))],
+    "no_shortcut": [r["id"] for r in FUSED_ROWS if r["kernel"] == "c3k2" and r["id"].endswith("_9x17")],
+    "always_shortcut": [r["id"] for r in FUSED_ROWS if r["kernel"] == "c3k2" and r["id"].endswith("_9x17_noshort")],
+    "rows_bleed": [r["id"] for r in FUSED_ROWS if r["B"] != "persist" and (r["kernel"] != "stem2" or r["H"] % 2 == 0)],
+    "stem_t_bias_outside": ["stem2_17x33"],
+    "dw_first_chunk_taps": ["dwpw_c128_n64", "dwpw_c128_n80"],
 }

@@ -1,12 +1,14 @@
 """CPU guard on the per-op GPU coverage (tests/op_matrix.py): every dual-built entry point has a bf16 test, every attention kernel family the
 dispatcher can launch has a row in the dispatch matrix, and so has every kernel family and template instance of cvmi_conv2d's dispatcher
-(CONV_ROWS).  Adding an entry point or a kernel without its per-op test fails here, on any checkout."""
+(CONV_ROWS) and every built instance of the three fused YOLO11 kernels (FUSED_ROWS).  Adding an entry point or a kernel without its per-op test
+fails here, on any checkout."""
 import ast
 import glob
 import os
 import re
 
-from op_matrix import ATTN_ROWS, BF16_OPS, CONV_ROWS, SHARE_ROWS, TNAME, conv_expect
+from op_matrix import (ATTN_ROWS, BF16_OPS, C3K2_INSTANCES, CONV_ROWS, FUSED_MUTANT_ROWS, FUSED_ROWS, SHARE_ROWS, TNAME, c3k2_max_wgs_per_cu, c3k2_tag,
+                       conv_expect)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(os.path.dirname(HERE), "circuitvision_amd", "csrc")
@@ -229,6 +231,92 @@ def test_conv_matrix_rows_are_well_formed():
             assert isinstance(r["B"], int) and r["B"] % r["res_rep"] == 0, rid
         assert r["B"] == "cu/2" or (isinstance(r["B"], int) and r["B"] > 0), rid
         assert not r["out_f32"] or "f32" not in r["dtypes"] or isinstance(r["expect"], dict), rid
+
+
+FUSED_SOURCES = ("c3k2_fused.hip", "stem_fused.hip", "dwpw_fused.hip")
+
+
+def fused_sources(csrc=CSRC):
+    return {name: open(os.path.join(csrc, name)).read() for name in FUSED_SOURCES}
+
+
+def fused_instances(sources):
+    """Tags of the instances the three fused entry points can launch, from their call sites: launch_c3k2<C, HR, C2, C1>(, launch_dwpw<CC, NCHUNK,
+    N1P, N2P>( and the hipLaunchKernelGGL(stem2_kernel, ..) launch -- spelled as the launchers' cvmi_note_kernel formats spell them."""
+    ints = lambda s: tuple(int(v) for v in s.split(","))
+    out = ["c3k2_kernel<%d, %d, %d, %d>" % ints(m) for m in re.findall(r"launch_c3k2<([\d, ]+)>\(", sources["c3k2_fused.hip"])]
+    out += ["dwpw_kernel<%d, %d, %d, %d>" % ints(m) for m in re.findall(r"launch_dwpw<([\d, ]+)>\(", sources["dwpw_fused.hip"])]
+    out += ["stem2_kernel"] * len(re.findall(r"hipLaunchKernelGGL\(\s*stem2_kernel\s*,", sources["stem_fused.hip"]))
+    return out
+
+
+def fused_gaps(sources, rows=FUSED_ROWS):
+    """What the fused matrix leaves uncovered, as a list of strings (empty = complete)."""
+    gaps = []
+    for name, fmt in (("c3k2_fused.hip", "c3k2_kernel<%d, %d, %d, %d>"), ("dwpw_fused.hip", "dwpw_kernel<%d, %d, %d, %d>"), ("stem_fused.hip", "stem2_kernel")):
+        if 'cvmi_note_kernel("%s"' % fmt not in sources[name]:
+            gaps.append(f"{name} no longer tags its launch as {fmt}")
+    inst, tags = set(fused_instances(sources)), {r["expect"] for r in rows}
+    gaps += [f"{t} has no row" for t in sorted(inst - tags)]
+    gaps += [f"rows expect {t}, which the sources no longer launch" for t in sorted(tags - inst)]
+    for t in sorted(t for t in inst & tags if t.startswith("c3k2_kernel")):             # what every c3k2 instance needs beside a row
+        mine = [r for r in rows if r["expect"] == t]
+        if not any(r["B"] == "persist" for r in mine):
+            gaps.append(f"{t} has no persistent row")
+        if not any(r["shortcut"] == 0 for r in mine):
+            gaps.append(f"{t} has no shortcut = 0 row")
+    return gaps
+
+
+def test_every_fused_kernel_instance_is_in_the_fused_matrix():
+    src = fused_sources()
+    inst = fused_instances(src)
+    assert len(inst) == len(set(inst)), inst
+    assert [sum(t.startswith(f) for t in inst) for f in ("c3k2_kernel", "dwpw_kernel", "stem2_kernel")] == [5, 8, 1], inst      # the parser still finds the call sites
+    assert {t for t in inst if t.startswith("c3k2")} == {c3k2_tag(i) for i in C3K2_INSTANCES}
+    assert fused_gaps(src) == [], fused_gaps(src)
+
+
+def test_a_new_fused_instance_or_a_removed_row_is_caught():
+    src = fused_sources()
+    probe = dict(src)
+    probe["c3k2_fused.hip"] += "\n  if (d->c == 64) return launch_c3k2<64, 32, 128, 0>(a, d->B, s);\n"
+    assert fused_gaps(probe) == ["c3k2_kernel<64, 32, 128, 0> has no row"]
+    probe = dict(src)
+    probe["dwpw_fused.hip"] += "\n  return launch_dwpw<80, 2, 96, 0>(a, d->B, s);\n"
+    assert fused_gaps(probe) == ["dwpw_kernel<80, 2, 96, 0> has no row"]
+    probe = dict(src)
+    probe["stem_fused.hip"] = probe["stem_fused.hip"].replace('cvmi_note_kernel("stem2_kernel")', "")
+    assert fused_gaps(probe) == ["stem_fused.hip no longer tags its launch as stem2_kernel"]
+    assert fused_gaps(src, [r for r in FUSED_ROWS if r["id"] != "dwpw_c64_n80"]) == ["dwpw_kernel<64, 1, 96, 0> has no row"]
+    assert fused_gaps(src, [r for r in FUSED_ROWS if r["kernel"] != "stem2"]) == ["stem2_kernel has no row"]
+    assert fused_gaps(src, [r for r in FUSED_ROWS if r["id"] != "c3k2_32_16_128_0_persist"]) == ["c3k2_kernel<32, 16, 128, 0> has no persistent row"]
+    assert fused_gaps(src, [r for r in FUSED_ROWS if r["id"] != "c3k2_16_8_64_0_9x17_noshort"]) == ["c3k2_kernel<16, 8, 64, 0> has no shortcut = 0 row"]
+    assert fused_gaps(src, [r for r in FUSED_ROWS if r.get("inst") != (32, 16, 64, 0)]) == ["c3k2_kernel<32, 16, 64, 0> has no row"]
+
+
+def test_fused_matrix_rows_are_well_formed():
+    ids = [r["id"] for r in FUSED_ROWS]
+    assert len(ids) == len(set(ids)), "duplicate row ids"
+    for r in FUSED_ROWS:
+        rid = r["id"]
+        assert r["kernel"] in ("c3k2", "stem2", "dwpw") and r["expect"].startswith(r["kernel"] + "_kernel"), rid
+        assert r["x_off"] % 8 == 0 and r["x_extra"] % 8 == 0 and r["y_guard"] % 8 == 0, f"{rid}: offsets and guards keep the 16-byte alignment"
+        assert 0 <= r["x_off"] <= r["x_extra"], rid
+        assert r["H"] > 0 and r["W"] > 0, rid
+        if r["B"] == "persist":
+            assert r["kernel"] == "c3k2" and r["k"] == c3k2_max_wgs_per_cu(r["inst"]) == (8 if r["inst"][0] == 16 else 4), f"{rid}: k must match the thread count"
+            assert -(-r["H"] // 8) * -(-r["W"] // 16) > 1, f"{rid}: more than one tile per image, so consecutive tiles of a workgroup change image AND origin"
+        else:
+            assert isinstance(r["B"], int) and r["B"] >= 2, f"{rid}: B >= 2 with different images"
+        if r["kernel"] == "c3k2":
+            c, h, c2, c1 = r["inst"]
+            assert r["inst"] in C3K2_INSTANCES and r["expect"] == c3k2_tag(r["inst"]) and r["shortcut"] in (0, 1), rid
+            assert (c1 > 0) == (c1 in (32, 64)), f"{rid}: fuse_cv1 rows carry c1"
+        if r["kernel"] == "dwpw":
+            assert r["N1"] % 8 == 0 and 0 <= r["N2"] <= 64, rid
+    for mut, rids in FUSED_MUTANT_ROWS.items():
+        assert rids and set(rids) <= set(ids), mut
 
 
 def test_the_native_library_reads_no_tuning_switch():
