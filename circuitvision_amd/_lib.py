@@ -135,6 +135,9 @@ SIGNATURES = {
     "cvmi_sam2_transform": (_i, [_vp, _i, _i, _vp, _i, _i, _vp]),
     "cvmi_sam2_transform_batch": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _vp]),
     "cvmi_sam2_transform_rects": (_i, [_vp, C.c_longlong, _i, _i, _vp, _i, _vp, _i, _i, _i, _vp]),
+    "cvmi_sam2_transform_rects_dev": (_i, [_vp, C.c_longlong, _i, _i, _vp, _i, _vp, _i, _i, _i, _vp]),
+    "cvmi_mask_postprocess_rects_dev": (_i, [_vp, _i, _i, _i, _vp, C.c_longlong, _f, _vp, _vp, _vp]),
+    "cvmi_stage2_crop": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _i, _i, C.c_double, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

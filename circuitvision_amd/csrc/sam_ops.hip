@@ -538,10 +538,10 @@ __global__ __launch_bounds__(256) void sam2_transform_kernel(const uint8_t* __re
 constexpr int RECT_MAX = 64;
 struct RectTable { int4 r[RECT_MAX]; };
 
+// image blockIdx.y of the launch = the rectangle rc = {x0, y0, w, h} of source image blockIdx.y (both forms of the window table below)
 template <typename T>
-__global__ __launch_bounds__(256) void sam2_transform_rects_kernel(const uint8_t* __restrict__ src, long long image_stride, int W, const RectTable win,
-                                                                  T* __restrict__ dst, int R, int swap_rb) {
-  const int4 rc = win.r[blockIdx.y];                      // blockIdx.y = image
+__device__ __forceinline__ void sam2_transform_window(const uint8_t* __restrict__ src, long long image_stride, int W, const int4 rc,
+                                                      T* __restrict__ dst, int R, int swap_rb) {
   const int H0 = rc.w, W0 = rc.z;                         // the window's height, width: the resize sees nothing outside it
   const float sy = (float)H0 / (float)R, sx = (float)W0 / (float)R;
   src += (size_t)blockIdx.y * image_stride + ((size_t)rc.y * W + rc.x) * 3;
@@ -571,15 +571,29 @@ __global__ __launch_bounds__(256) void sam2_transform_rects_kernel(const uint8_t
   }
 }
 
-// cvmi_mask_postprocess for planes that go back to DIFFERENT sizes (each image's own crop window): plane n is resized to sz.r[n] = {H, W} and
-// written at mask + sz.r[n].z (a byte offset the host laid out: planes packed back to back); extents pre-initialised by the kernel's first block.
-__global__ __launch_bounds__(256) void bilinear_sizes_kernel(const float* __restrict__ x, int h, int w, const RectTable sz, uint8_t* __restrict__ mask,
-                                                            long long mask_base, float thresh, int* __restrict__ ext) {
+template <typename T>
+__global__ __launch_bounds__(256) void sam2_transform_rects_kernel(const uint8_t* __restrict__ src, long long image_stride, int W, const RectTable win,
+                                                                  T* __restrict__ dst, int R, int swap_rb) {
+  sam2_transform_window<T>(src, image_stride, W, win.r[blockIdx.y], dst, R, swap_rb);
+}
+
+// The window table in DEVICE memory (cvmi_stage2_crop's output): nothing of the launch depends on a value the host has seen.  A window is
+// clipped to the H x W image here, whatever the table holds.
+template <typename T>
+__global__ __launch_bounds__(256) void sam2_transform_rects_dev_kernel(const uint8_t* __restrict__ src, long long image_stride, int H, int W,
+                                                                      const int4* __restrict__ win, T* __restrict__ dst, int R, int swap_rb) {
+  int4 rc = win[blockIdx.y];
+  rc.x = min(max(rc.x, 0), W - 1); rc.y = min(max(rc.y, 0), H - 1);
+  rc.z = min(max(rc.z, 1), W - rc.x); rc.w = min(max(rc.w, 1), H - rc.y);
+  sam2_transform_window<T>(src, image_stride, W, rc, dst, R, swap_rb);
+}
+
+// plane blockIdx.y (f32 [h, w]) -> H x W, thresholded, at mp; its extent into ext[4 * blockIdx.y ..]
+__device__ __forceinline__ void bilinear_plane(const float* __restrict__ x, int h, int w, int H, int W, uint8_t* __restrict__ mp, float thresh,
+                                               int* __restrict__ ext) {
   const int n = blockIdx.y;
-  const int H = sz.r[n].x, W = sz.r[n].y;
   const float sy = (float)h / (float)H, sx = (float)w / (float)W;
   const float* pl = x + (size_t)n * h * w;
-  uint8_t* mp = mask + mask_base + (((long long)(unsigned)sz.r[n].w << 32) | (unsigned)sz.r[n].z);
   const int total = H * W;
   int ex0 = W, ey0 = H, ex1 = -1, ey1 = -1;
   for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
@@ -601,9 +615,38 @@ __global__ __launch_bounds__(256) void bilinear_sizes_kernel(const float* __rest
     atomicMax(ext + n * 4 + 2, ex1); atomicMax(ext + n * 4 + 3, ey1);
   }
 }
+// cvmi_mask_postprocess for planes that go back to DIFFERENT sizes (each image's own crop window): plane n is resized to sz.r[n] = {H, W} and
+// written at mask + sz.r[n].z (a byte offset the host laid out: planes packed back to back); extents pre-initialised by the kernel's first block.
+__global__ __launch_bounds__(256) void bilinear_sizes_kernel(const float* __restrict__ x, int h, int w, const RectTable sz, uint8_t* __restrict__ mask,
+                                                            long long mask_base, float thresh, int* __restrict__ ext) {
+  const int n = blockIdx.y;
+  bilinear_plane(x, h, w, sz.r[n].x, sz.r[n].y, mask + mask_base + (((long long)(unsigned)sz.r[n].w << 32) | (unsigned)sz.r[n].z), thresh, ext);
+}
 __global__ void mask_extent_init_sizes_kernel(int* ext, int N, const RectTable sz) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < N) { ext[i * 4] = sz.r[i].y; ext[i * 4 + 1] = sz.r[i].x; ext[i * 4 + 2] = -1; ext[i * 4 + 3] = -1; }
+}
+// The sizes in DEVICE memory: plane n returns to the {w, h} of win[n] = {x0, y0, w, h} at mask + n * plane_stride (fixed stride: no offset
+// depends on a window); a plane is clipped to its stride.
+__device__ __forceinline__ void rect_plane_size(const int4 rc, long long plane_stride, int& H, int& W) {
+  W = rc.z < 1 ? 1 : rc.z;
+  H = rc.w < 1 ? 1 : rc.w;
+  if ((long long)W > plane_stride) W = (int)plane_stride;
+  if ((long long)H * W > plane_stride) H = (int)(plane_stride / W);
+}
+__global__ __launch_bounds__(256) void bilinear_rects_dev_kernel(const float* __restrict__ x, int h, int w, const int4* __restrict__ win,
+                                                                uint8_t* __restrict__ mask, long long plane_stride, float thresh, int* __restrict__ ext) {
+  int H, W;
+  rect_plane_size(win[blockIdx.y], plane_stride, H, W);
+  bilinear_plane(x, h, w, H, W, mask + (size_t)blockIdx.y * plane_stride, thresh, ext);
+}
+__global__ void mask_extent_init_rects_dev_kernel(int* ext, int N, const int4* __restrict__ win, long long plane_stride) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < N) {
+    int H, W;
+    rect_plane_size(win[i], plane_stride, H, W);
+    ext[i * 4] = W; ext[i * 4 + 1] = H; ext[i * 4 + 2] = -1; ext[i * 4 + 3] = -1;
+  }
 }
 
 inline int grid_for(long long total, int block = 256, int cap = 256 * 16) {
@@ -938,6 +981,43 @@ extern "C" int CVMI_ENTRY(cvmi_sam2_transform_rects)(const uint8_t* src, long lo
   }
   return 0;
 }
+
+#ifndef CVMI_OPERAND_BF16
+// One copy for all three output types: the kernel computes in f32 and only its last conversion depends on T, so the bf16 instance needs no
+// second build of this translation unit (unlike the entry points above, whose 16-bit type is the translation unit's operand type).
+extern "C" int cvmi_sam2_transform_rects_dev(const uint8_t* src, long long src_image_stride, int H, int W, const int* rects_dev, int B, void* dst, int R,
+                                             int dst_dtype, int swap_rb, cvmi_stream_t stream_) {
+  CVMI_CHECK(src && dst && rects_dev && B >= 1 && B <= 65535 && H > 0 && W > 0 && R > 0 && src_image_stride >= 0 && ((uintptr_t)rects_dev & 15) == 0,
+             "sam2_transform_rects_dev: bad arguments");
+  CVMI_CHECK(dst_dtype == CVMI_F16 || dst_dtype == CVMI_BF16 || dst_dtype == CVMI_F32, "sam2_transform_rects_dev: bad dtype");
+  const float sy = (float)H / (float)R, sx = (float)W / (float)R;             // the whole image bounds every window inside it
+  CVMI_CHECK(2.f * (sy > 1.f ? sy : 1.f) + 2.f <= AA_MAXTAPS && 2.f * (sx > 1.f ? sx : 1.f) + 2.f <= AA_MAXTAPS,
+             "sam2_transform_rects_dev: down-scale factor of the %d x %d image too large", W, H);
+  hipStream_t s = (hipStream_t)stream_;
+  const dim3 g(grid_for((long long)R * R), B), blk(256);
+  const int4* win = (const int4*)rects_dev;
+  const int sw = swap_rb ? 1 : 0;
+  if (dst_dtype == CVMI_F16) hipLaunchKernelGGL(sam2_transform_rects_dev_kernel<_Float16>, g, blk, 0, s, src, src_image_stride, H, W, win, (_Float16*)dst, R, sw);
+  else if (dst_dtype == CVMI_BF16) hipLaunchKernelGGL(sam2_transform_rects_dev_kernel<__bf16>, g, blk, 0, s, src, src_image_stride, H, W, win, (__bf16*)dst, R, sw);
+  else hipLaunchKernelGGL(sam2_transform_rects_dev_kernel<float>, g, blk, 0, s, src, src_image_stride, H, W, win, (float*)dst, R, sw);
+  CVMI_LAUNCH_CHECK();
+  return 0;
+}
+#endif
+
+#ifndef CVMI_OPERAND_BF16
+extern "C" int cvmi_mask_postprocess_rects_dev(const float* x, int N, int h, int w, const int* rects_dev, long long plane_stride, float thresh,
+                                               uint8_t* mask_u8, int* extent, cvmi_stream_t stream_) {
+  CVMI_CHECK(x && mask_u8 && extent && rects_dev && N > 0 && N <= 65535 && h > 0 && w > 0 && plane_stride > 0 && plane_stride < (1ll << 31) &&
+             ((uintptr_t)rects_dev & 15) == 0, "mask_postprocess_rects_dev: bad arguments");
+  hipStream_t s = (hipStream_t)stream_;
+  hipLaunchKernelGGL(mask_extent_init_rects_dev_kernel, dim3((N + 63) / 64), dim3(64), 0, s, extent, N, (const int4*)rects_dev, plane_stride);
+  hipLaunchKernelGGL(bilinear_rects_dev_kernel, dim3(grid_for(plane_stride, 256, 1024), N), dim3(256), 0, s, x, h, w, (const int4*)rects_dev, mask_u8,
+                     plane_stride, thresh, extent);
+  CVMI_LAUNCH_CHECK();
+  return 0;
+}
+#endif
 
 #ifndef CVMI_OPERAND_BF16
 extern "C" int cvmi_mask_postprocess_sizes(const float* x, int N, int h, int w, const int* sizes, float thresh, uint8_t* mask_u8, int* extent,

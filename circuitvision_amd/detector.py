@@ -200,12 +200,16 @@ class YOLO:
                 done.record(self.stream)
         return PendingDetections(done, det_h, idx_h, cnt_h, (H, W), (h0, w0), self.names, src)
 
-    def predict_chunks_async(self, images, chunk, conf=0.25, iou=0.7, max_det=300, imgsz=None):
+    def predict_chunks_async(self, images, chunk, conf=0.25, iou=0.7, max_det=300, imgsz=None, after_chunk=None):
         """A batch pipeline's form of `predict_async`: ONE pinned staging pass and ONE H2D copy for all equally sized `images`, then one
         letterbox launch + graph replay + D2H of the detections per `chunk` images -- so the host can take chunk 0's boxes (and start what
         depends on them: the crop window, the segmenter) while the GPU still runs the later chunks.  Returns one handle per chunk; handle.src
         is that chunk's u8 [b, h, w, 3] DEVICE image block (valid once `.result()` has returned: the segmenter's transform reads its crop
-        windows straight out of it, no second H2D)."""
+        windows straight out of it, no second H2D).
+        handle.det_dev / handle.cnt_dev are the plan's own DEVICE outputs of that chunk (f32 [b, max_det, 6] letterboxed, i32 [b]).  The next
+        chunk's replay overwrites them, so whoever reads them does so on the detector's stream right after the replay: `after_chunk(handle)`
+        is called there, inside the stream context and before the chunk's `done` event is recorded -- what it enqueues (e.g. glue.stage2_crop
+        into tensors of its own, and their D2H copies) is complete when `done` is; its return value is kept as handle.after."""
         imgsz = self.imgsz if imgsz is None else self._check_imgsz(imgsz)
         if not images:
             raise ValueError("predict needs at least one image")
@@ -246,18 +250,23 @@ class YOLO:
                     det_h.copy_(p.det, non_blocking=True)
                     idx_h.copy_(p.det_idx, non_blocking=True)
                     cnt_h.copy_(p.det_count, non_blocking=True)
-                    done = torch.cuda.Event()
-                    done.record(self.stream)
-                    out.append(PendingDetections(done, det_h, idx_h, cnt_h, (H, W), (h0, w0), self.names, src, src=src[c0:c0 + B]))
+                    h = PendingDetections(None, det_h, idx_h, cnt_h, (H, W), (h0, w0), self.names, src, src=src[c0:c0 + B], det_dev=p.det, cnt_dev=p.det_count)
+                    if after_chunk is not None:
+                        h.after = after_chunk(h)
+                    h.done = torch.cuda.Event()
+                    h.done.record(self.stream)
+                    out.append(h)
         return out
 
 
 class PendingDetections:
     """Detections in flight (YOLO.predict_async).  `.result()` -> [Results], one per image."""
 
-    def __init__(self, done, det, idx, cnt, lb_shape, orig_shape, names, keep, src=None):
+    def __init__(self, done, det, idx, cnt, lb_shape, orig_shape, names, keep, src=None, det_dev=None, cnt_dev=None):
         self.done, self.det, self.idx, self.cnt, self.lb_shape, self.orig_shape, self.names, self._keep = done, det, idx, cnt, lb_shape, orig_shape, names, keep
         self.src = src                       # (predict_chunks_async) the chunk's u8 device images, for whoever crops from them
+        self.det_dev, self.cnt_dev = det_dev, cnt_dev        # (predict_chunks_async) the plan's device outputs: valid on the detector's stream until its next replay
+        self.after = None                    # what predict_chunks_async's after_chunk returned
         self._out = None
 
     def result(self):

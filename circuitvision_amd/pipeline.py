@@ -52,7 +52,7 @@ class CircuitPipeline:
     segmenter: `SAM2Model`-like (`infer_masks(x, boxes=None)`, `.image_size`); transforms: `SAM2Transforms`-like."""
 
     def __init__(self, detector, segmenter, transforms, stage2_iou=0.6, max_prompts=32, crop_fn=None, swap_channels=True, seg_batch=16, crop=False,
-                 crop_padding=80, nodes=False, reclassify=False):
+                 crop_padding=80, nodes=False, reclassify=False, device_glue=False):
         """crop=True: the reference's chain -- detector -> stage-2 NMS -> crop window from the boxes (crop.py) -> segmenter on the window
         (analysis_pipeline.py:177 -> :206); False: the segmenter sees the whole image.  crop_fn overrides the built-in crop.
         swap_channels: segment_with_sam2 applies cv2.COLOR_BGR2RGB to whatever it is given (circuit_analyzer.py:343), and the
@@ -65,10 +65,18 @@ class CircuitPipeline:
         reclassify=True (any prompts mode): run_terminal_reclassification (analysis_pipeline.py:117-137, wires.reclassify_terminals) runs
         after the segmenter and before node analysis, on the image the segmenter saw and its boxes, with the detector's names: a 'terminal'
         box that touches two or more wire contours becomes 'voltage.dc'.  "bboxes" are the rewritten boxes (node analysis reads them) and
-        each result gains "terminal_connections": {box index: connected contours}."""
+        each result gains "terminal_connections": {box index: connected contours}.
+        device_glue=True (needs crop=True without a crop_fn, and this package's own detector / segmenter / transforms): what sits between the
+        two models in the cropped chain -- scale_boxes, rounding, stage-2 NMS, the crop window, the box shift -- runs as one kernel on the
+        detector's stream (glue.py) and the segmenter reads its windows from device memory: no host wait between the detector's first kernel
+        and the segmenter's last.  Same result dicts, key for key and bit for bit."""
         if not (isinstance(nodes, bool) or nodes == "connections"):
             raise ValueError("nodes must be False, True or 'connections'")
         self.det, self.seg, self.tr = detector, segmenter, transforms
+        self.device_glue = bool(device_glue)
+        if self.device_glue and not (crop and crop_fn is None and self._product_objects()):
+            raise ValueError("device_glue=True needs crop=True, no crop_fn, and this package's own YOLO / SAM2Model / SAM2Transforms")
+        self._glue_flags = None                    # (class names, their flag table on the device)
         self.stage2_iou, self.max_prompts, self.swap = stage2_iou, max_prompts, swap_channels
         self.crop_padding = int(crop_padding)
         self.builtin_crop = bool(crop) and crop_fn is None
@@ -181,7 +189,7 @@ class CircuitPipeline:
         if not mine:
             return []
         if prompts == "learned" and self.builtin_crop and self._product_objects():
-            res = self._run_cropped(mine)
+            res = self._run_cropped_dev(mine) if self.device_glue else self._run_cropped(mine)
         elif prompts == "learned" and self.crop_fn is None and self._product_objects():
             res = self._run_overlapped(mine)
         else:
@@ -299,6 +307,89 @@ class CircuitPipeline:
             for idxs, wins, _metas, src, _fin in pend:
                 self._reclassify([out[i] for i in idxs], src=src, windows=wins)
         return out
+
+    # ---- the same chain with the glue on the device (device_glue=True): per chunk the detector's stream carries letterbox + YOLO11 graph + NMS
+    #      + the glue kernel (on the plan's own outputs, before the next replay overwrites them) + the D2H copies, and the segmenter's stream
+    #      waits for THAT chunk's event -- not for the tail of the detector's stream -- then transforms from the windows in device memory.
+    #      Everything is enqueued before the host waits for anything; building the dicts and uid strings happens behind the segmenter.
+    def _run_cropped_dev(self, images):
+        from . import glue
+        t = time.perf_counter()
+        names = self.det.names
+        key = tuple(sorted(names.items()))
+        if self._glue_flags is None or self._glue_flags[0] != key:
+            self._glue_flags = (key, torch.from_numpy(glue.class_flags(names)).to(self.det.device))
+        flags = self._glue_flags[1]
+
+        def after(h):                                                      # on the detector's stream, right after the chunk's replay
+            g = glue.stage2_crop(h.det_dev, h.cnt_dev, h.lb_shape, h.orig_shape, flags, self.crop_padding, self.stage2_iou)
+            return g, g.to_pinned()
+        groups = {}
+        for i, im in enumerate(images):
+            groups.setdefault(im.shape[:2], []).append(i)
+        work = []
+        for idxs in groups.values():
+            hs = self.det.predict_chunks_async([images[i] for i in idxs], self.seg_batch, after_chunk=after)
+            work += [(idxs[k * self.seg_batch:(k + 1) * self.seg_batch], h) for k, h in enumerate(hs)]
+        t = self._tick("enqueue: detector chunks (stage u8 + ONE H2D + per chunk: letterbox + YOLO11 graph + NMS + glue kernel + D2H launches)", t)
+        pend = [(idxs, h, self._enqueue_learned_dev(h.src, h.after[0].window, h.done, k % self.seg_slots)) for k, (idxs, h) in enumerate(work)]
+        t = self._tick("enqueue: segmenter chunks (wait for the chunk's event + transform from the device windows + SAM 2.1 graph + post-process)", t)
+        out, rows = [None] * len(images), []
+        for idxs, h, _fin in pend:
+            h.done.synchronize()
+            rows.append(glue.to_host(h.det, h.cnt, h.after[1], h.names, h.orig_shape))
+        t = self._tick("glue readback (dicts + uid strings + crop_debug_info from the kernel's outputs), behind the segmenter", t)
+        for (idxs, h, fin), chunk in zip(pend, rows):
+            u8, exts, iou = fin()
+            for b, i in enumerate(idxs):
+                bbs, shifted, wnd, info = chunk[b]
+                im = images[i]
+                hh, ww = im.shape[:2] if wnd is None else (wnd[3] - wnd[1], wnd[2] - wnd[0])
+                view = im if wnd is None else im[wnd[1]:wnd[3], wnd[0]:wnd[2]]
+                out[i] = {"image": view, "bboxes": shifted, "mask": u8[b, :hh * ww].view(hh, ww), "extent": exts[b], "iou": iou[b], "window": wnd,
+                          "crop_debug_info": info}
+        self._tick("wait: segmenter (GPU time not hidden behind host work) + extents to the host", t)
+        if self.reclassify:
+            for (idxs, h, _fin), chunk in zip(pend, rows):
+                self._reclassify([out[i] for i in idxs], src=h.src, windows=[r[2] for r in chunk])
+        return out
+
+    def _enqueue_learned_dev(self, src, window, ready, slot=0):
+        """_enqueue_learned for a chunk whose windows are a DEVICE int32 [B, 4] {x0, y0, w, h} tensor (glue.stage2_crop): ordered behind the
+        event `ready` alone; masks go to a fixed-stride u8 [B, H0 * W0] block (plane b holds its window's h * w pixels at its start), so no
+        size or offset is needed on the host.  Returns a closure that waits: -> (the u8 block, extent tuples, iou [B,1])."""
+        from . import _lib
+        seg, tr = self.seg, self.tr
+        lib = _lib.load()
+        B, H0, W0 = src.shape[:3]
+        R = seg.image_size
+        with seg._lock, torch.cuda.device(seg.dev):
+            p = seg.plan(B, slot=slot)
+            sst = seg.slot_stream(slot)
+            iou = torch.empty_like(p.iou)
+            ext = torch.empty(B, 4, dtype=torch.int32, device=seg.dev)
+            ext_h = torch.empty(B, 4, dtype=torch.int32, pin_memory=True)
+            u8 = torch.empty(B, H0 * W0, dtype=torch.uint8, device=seg.dev)
+            sst.wait_stream(torch.cuda.current_stream())
+            sst.wait_event(ready)                                           # this chunk's detector pass + glue: not the tail of the detector's stream
+            for t_ in (iou, ext, u8, src, window):
+                t_.record_stream(sst)
+            with torch.cuda.stream(sst):
+                sp = sst.cuda_stream
+                _lib.check(lib.cvmi_sam2_transform_rects_dev(src.data_ptr(), H0 * W0 * 3, H0, W0, window.data_ptr(), B, p.x_in.t.data_ptr(), R, seg.dtype,
+                                                             1 if self.swap else 0, sp), "sam2_transform_rects_dev")
+                p.plan.run()
+                iou.copy_(p.iou, non_blocking=True)
+                _lib.check(lib.cvmi_mask_postprocess_rects_dev(p.high_res.data_ptr(), B, R, R, window.data_ptr(), H0 * W0, float(tr.mask_threshold),
+                                                               u8.data_ptr(), ext.data_ptr(), sp), "mask_postprocess_rects_dev")
+                ext_h.copy_(ext, non_blocking=True)
+                done = torch.cuda.Event()
+                done.record(sst)
+
+        def finish():
+            done.synchronize()
+            return u8, [None if x1 < 0 else (x0, y0, x1 + 1, y1 + 1) for x0, y0, x1, y1 in ext_h.tolist()], iou
+        return finish
 
     def _enqueue_learned(self, imgs, slot=0, src=None, windows=None, det_stream=None):
         """transform -> SAM 2.1 (learned prompts) -> resize / threshold / u8 / extent for one chunk, enqueued on the stream of segmenter plan

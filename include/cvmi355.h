@@ -372,6 +372,11 @@ int cvmi_mask_postprocess(const float* x, int N, int h, int w, int H, int W, flo
  * written at mask_u8 + sum over m < n of H_m * W_m (planes packed back to back); extent[n] as above in plane n's own coordinates. */
 int cvmi_mask_postprocess_sizes(const float* x, int N, int h, int w, const int* sizes, float thresh, uint8_t* mask_u8, int* extent,
                                 cvmi_stream_t stream);
+/* The same with the sizes on the DEVICE: plane n is resized to the {w, h} of rects_dev[n] = {x0, y0, w, h} (a window of cvmi_stage2_crop) and
+ * written at mask_u8 + n * plane_stride BYTES -- fixed stride, the caller allocates plane_stride = H0 * W0 of the uncropped image, so no
+ * offset depends on a window; a plane is clipped to its stride.  The grid is sized for plane_stride pixels.  extent[n] as above. */
+int cvmi_mask_postprocess_rects_dev(const float* x, int N, int h, int w, const int* rects_dev, long long plane_stride, float thresh,
+                                    uint8_t* mask_u8, int* extent, cvmi_stream_t stream);
 
 /* Extent of N binary u8 planes [N,H,W]: extent[n] = {min x, min y, max x, max y} over the non-zero pixels, or
  * {W, H, -1, -1} for an empty plane.  Replaces cv2.findContours(RETR_EXTERNAL) + cv2.boundingRect on the SAM 2 mask
@@ -402,6 +407,60 @@ int cvmi_sam2_transform_batch(const uint8_t* src, int B, int H, int W, void* dst
  * (B x 4 ints, read during the call; it travels in the kernel arguments).  The source may be the buffer the detector's letterbox read. */
 int cvmi_sam2_transform_rects(const uint8_t* src, long long src_image_stride, int H, int W, const int* rects, int B, void* dst, int R,
                               int dst_dtype, int swap_rb, cvmi_stream_t stream);
+/* cvmi_sam2_transform_rects with rects as a DEVICE array (B x {x0, y0, w, h}, e.g. cvmi_stage2_crop's `window`), read by the kernel: nothing
+ * of the call depends on a value the host has not seen.  The host checks the tap bound for the whole H x W image, which bounds every window
+ * inside it; the kernel clips a window to the image (cvmi_stage2_crop guarantees 0 <= x0, x0 + w <= W, w, h >= 1 -- and the same in y).
+ * Bit-identical to cvmi_sam2_transform_rects on the same windows. */
+int cvmi_sam2_transform_rects_dev(const uint8_t* src, long long src_image_stride, int H, int W, const int* rects_dev, int B, void* dst, int R,
+                                  int dst_dtype, int swap_rb, cvmi_stream_t stream);
+
+/* ---- the glue between the detector and the segmenter, on the device (analysis_pipeline.py:97-115 -> :177): ultralytics' scale_boxes + clip
+ * in f32 (subtract the pad, DIVIDE by the gain, clamp), results_to_bboxes' np.rint of the f64 copy, the stage-2 NMS of utils.py:346-361
+ * (stable descending confidence, a box survives iff its f64 IoU with every kept box is < stage2_iou; stage2_iou < 0: no pass, list order),
+ * CircuitAnalyzer.crop_image_and_adjust_bboxes' window decision (circuit_analyzer.py:937-1284, f64) and its box shift -- one launch, one
+ * workgroup per image.  det f32 [B, max_det, 6] {x1, y1, x2, y2, conf, cls} in letterboxed coordinates and count i32 [B] are the detector
+ * plan's own outputs; H0, W0 the original image; gain, pad_x, pad_y as detector.scale_boxes computes them; class_flags DEVICE u8 [n_flags]
+ * by class id: CVMI_GLUE_CLASS_* bits.  max_det <= CVMI_GLUE_MAX_DET.  Outputs (DEVICE, fixed stride; rows past a count are not written):
+ *   kept_idx i32 [B, max_det]: index into the detector's list, in kept order;  kept_count i32 [B];
+ *   boxes i32 [B, max_det, 4]: every detector box rounded, in original pixels (detector order);
+ *   adj_boxes i32 [B, max_det, 4]: the kept boxes in the window's coordinates, clipped to it (kept order);
+ *   window i32 [B, 4] {x0, y0, w, h}: the crop window, the whole image when no crop applies (0 <= x0, x0 + w <= W0, w >= 1; same in y);
+ *   info i32 [B, CVMI_GLUE_INFO_HEAD + max_det]: the words named below (what crop_debug_info reports), then one word per KEPT box:
+ *   CVMI_GLUE_BOX_EXPANDED = this text box grew the window, CVMI_GLUE_BOX_DROPPED = no positive area left inside the window. */
+#define CVMI_GLUE_MAX_DET 320
+#define CVMI_GLUE_INFO_HEAD 40
+#define CVMI_GLUE_CLASS_NOT_CLUSTERED 1   /* text, explanatory, circuit, vss, crossover (:982) */
+#define CVMI_GLUE_CLASS_JUNCTION 2
+#define CVMI_GLUE_CLASS_TEXT 4
+#define CVMI_GLUE_CLASS_NON_COMPONENT 8   /* circuit_analyzer.py:51 */
+#define CVMI_GLUE_BOX_EXPANDED 1
+#define CVMI_GLUE_BOX_DROPPED 2
+enum {
+  CVMI_GLUE_REASON = 0,         /* reason_for_no_crop: CVMI_GLUE_REASON_* */
+  CVMI_GLUE_DECISION = 1,       /* crop_decision_source: CVMI_GLUE_DECISION_* */
+  CVMI_GLUE_APPLIED = 2,
+  CVMI_GLUE_LINK = 3,           /* clustering_proximity_threshold, -1 = None */
+  CVMI_GLUE_CLUSTERS = 4,       /* num_clusters_found, -1 = None */
+  CVMI_GLUE_MAIN_SIZE = 5,      /* main cluster: elements, text associations, ordinal, first member (position in the kept list, -1 = none) */
+  CVMI_GLUE_MAIN_TEXT = 6,
+  CVMI_GLUE_MAIN_ID = 7,
+  CVMI_GLUE_MAIN_FIRST = 8,
+  CVMI_GLUE_TOTAL = 9,          /* boxes the crop saw, component-type boxes, text boxes */
+  CVMI_GLUE_COMPONENT_TYPE = 10,
+  CVMI_GLUE_TEXT_TYPE = 11,
+  CVMI_GLUE_PADDING = 12,
+  CVMI_GLUE_BASIS_SET = 13,     /* 1: words BASIS .. BASIS + 7 hold crop_basis_bbox_before_padding as four f64 (low word first) */
+  CVMI_GLUE_PADDED_SET = 14,    /* 1: words PADDED .. + 3 hold window_after_main_padding */
+  CVMI_GLUE_FINAL_SET = 15,     /* 1: words FINAL .. + 3 hold final_crop_window_abs {x0, y0, x1, y1} */
+  CVMI_GLUE_BASIS = 16,
+  CVMI_GLUE_PADDED = 24,
+  CVMI_GLUE_FINAL = 28          /* 32 .. 39: reserved, zero */
+};
+enum { CVMI_GLUE_REASON_NONE = 0, CVMI_GLUE_REASON_NO_ELEMENTS = 1, CVMI_GLUE_REASON_TOO_LARGE = 2, CVMI_GLUE_REASON_INVALID = 3 };
+enum { CVMI_GLUE_DECISION_UNKNOWN = 0, CVMI_GLUE_DECISION_NO_ELEMENTS = 1, CVMI_GLUE_DECISION_SCORED = 2, CVMI_GLUE_DECISION_FALLBACK = 3 };
+int cvmi_stage2_crop(const float* det, const int* count, int B, int max_det, int H0, int W0, float gain, int pad_x, int pad_y,
+                     double stage2_iou, int padding, const uint8_t* class_flags, int n_flags, int* kept_idx, int* kept_count, int* boxes,
+                     int* adj_boxes, int* window, int* info, cvmi_stream_t stream);
 
 /* ---- node analysis (CircuitAnalyzer.get_node_connections, circuit_analyzer.py:1286-1370): N u8 planes of different sizes, packed back to
  * back (plane n at sum over m < n of its predecessors' pixels), sizes in HOST arrays read during the call. */
