@@ -66,6 +66,21 @@ class AttnDesc(C.Structure):
     ]
 
 
+class LetterboxRow(C.Structure):
+    """cvmi_letterbox_row: one source of cvmi_letterbox_ragged (a numpy array of LETTERBOX_ROW has the same layout)."""
+    _fields_ = [("src_byte_offset", C.c_longlong), ("H", C.c_int), ("W", C.c_int), ("new_h", C.c_int), ("new_w", C.c_int), ("top", C.c_int), ("left", C.c_int)]
+
+
+class Sam2SrcRow(C.Structure):
+    """cvmi_sam2_src_row: one source window of cvmi_sam2_transform_srcs."""
+    _fields_ = [("src_byte_offset", C.c_longlong), ("H", C.c_int), ("W", C.c_int), ("x0", C.c_int), ("y0", C.c_int), ("w", C.c_int), ("h", C.c_int)]
+
+
+# the two table rows as numpy record types (host arrays handed to the C ABI by pointer)
+LETTERBOX_ROW = [(n, "<i8" if t is C.c_longlong else "<i4") for n, t in LetterboxRow._fields_]
+SAM2_SRC_ROW = [(n, "<i8" if t is C.c_longlong else "<i4") for n, t in Sam2SrcRow._fields_]
+
+
 # name -> (restype, argtypes); every symbol declared in include/cvmi355.h
 _vp, _i, _f = C.c_void_p, C.c_int, C.c_float
 SIGNATURES = {
@@ -95,6 +110,7 @@ SIGNATURES = {
     "cvmi_yolo_nms": (_i, [_vp, _i, _i, _i, _f, _f, _i, _f, _vp, _vp, _vp, _vp, _vp]),
     "cvmi_letterbox": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "cvmi_letterbox_batch": (_i, [_vp, _i, _i, _i, _vp, C.c_longlong, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "cvmi_letterbox_ragged": (_i, [_vp, C.c_longlong, _vp, _i, _vp, C.c_longlong, _i, _i, _i, _i, _vp]),
     "cvmi_nchw_to_nhwc": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "cvmi_nhwc_to_nchw_f32": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _vp]),
     "cvmi_layernorm": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, C.c_longlong, _i, _f, _i, _i, _i, _i, _i, _vp]),
@@ -136,6 +152,7 @@ SIGNATURES = {
     "cvmi_sam2_transform_batch": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _vp]),
     "cvmi_sam2_transform_rects": (_i, [_vp, C.c_longlong, _i, _i, _vp, _i, _vp, _i, _i, _i, _vp]),
     "cvmi_sam2_transform_rects_dev": (_i, [_vp, C.c_longlong, _i, _i, _vp, _i, _vp, _i, _i, _i, _vp]),
+    "cvmi_sam2_transform_srcs": (_i, [_vp, C.c_longlong, _vp, _i, _vp, _i, _i, _i, _vp]),
     "cvmi_mask_postprocess_rects_dev": (_i, [_vp, _i, _i, _i, _vp, C.c_longlong, _f, _vp, _vp, _vp]),
     "cvmi_stage2_crop": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _i, _i, C.c_double, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }

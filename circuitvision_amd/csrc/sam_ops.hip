@@ -588,6 +588,17 @@ __global__ __launch_bounds__(256) void sam2_transform_rects_dev_kernel(const uin
   sam2_transform_window<T>(src, image_stride, W, rc, dst, R, swap_rb);
 }
 
+// Sources of DIFFERENT sizes in one packed u8 buffer: image blockIdx.y is the window {x0, y0, w, h} of the row's H x W image at
+// src + src_byte_offset (any byte offset: the taps are read byte by byte).  The third way to find the window; the arithmetic is
+// sam2_transform_window's.
+struct SrcTable { cvmi_sam2_src_row r[RECT_MAX]; };
+template <typename T>
+__global__ __launch_bounds__(256) void sam2_transform_srcs_kernel(const uint8_t* __restrict__ src, const SrcTable tab, T* __restrict__ dst, int R,
+                                                                 int swap_rb) {
+  const cvmi_sam2_src_row g = tab.r[blockIdx.y];
+  sam2_transform_window<T>(src + g.src_byte_offset, 0, g.W, make_int4(g.x0, g.y0, g.w, g.h), dst, R, swap_rb);
+}
+
 // plane blockIdx.y (f32 [h, w]) -> H x W, thresholded, at mp; its extent into ext[4 * blockIdx.y ..]
 __device__ __forceinline__ void bilinear_plane(const float* __restrict__ x, int h, int w, int H, int W, uint8_t* __restrict__ mp, float thresh,
                                                int* __restrict__ ext) {
@@ -1001,6 +1012,40 @@ extern "C" int cvmi_sam2_transform_rects_dev(const uint8_t* src, long long src_i
   else if (dst_dtype == CVMI_BF16) hipLaunchKernelGGL(sam2_transform_rects_dev_kernel<__bf16>, g, blk, 0, s, src, src_image_stride, H, W, win, (__bf16*)dst, R, sw);
   else hipLaunchKernelGGL(sam2_transform_rects_dev_kernel<float>, g, blk, 0, s, src, src_image_stride, H, W, win, (float*)dst, R, sw);
   CVMI_LAUNCH_CHECK();
+  return 0;
+}
+#endif
+
+#ifndef CVMI_OPERAND_BF16
+// (one copy for all three output types, as above)
+extern "C" int cvmi_sam2_transform_srcs(const uint8_t* src, long long src_bytes, const cvmi_sam2_src_row* rows, int B, void* dst, int R, int dst_dtype,
+                                        int swap_rb, cvmi_stream_t stream_) {
+  CVMI_CHECK(src && dst && rows && B >= 1 && R > 0 && src_bytes > 0, "sam2_transform_srcs: bad arguments");
+  CVMI_CHECK(dst_dtype == CVMI_F16 || dst_dtype == CVMI_BF16 || dst_dtype == CVMI_F32, "sam2_transform_srcs: bad dtype");
+  for (int b = 0; b < B; ++b) {                                     // every row before the first launch
+    const cvmi_sam2_src_row& r = rows[b];
+    CVMI_CHECK(r.H > 0 && r.W > 0 && r.src_byte_offset >= 0 && r.src_byte_offset + (long long)r.H * r.W * 3 <= src_bytes,
+               "sam2_transform_srcs: row %d: %d x %d x 3 bytes at offset %lld leave the %lld-byte source buffer", b, r.H, r.W, r.src_byte_offset, src_bytes);
+    CVMI_CHECK(r.x0 >= 0 && r.y0 >= 0 && r.w > 0 && r.h > 0 && (long long)r.x0 + r.w <= r.W && (long long)r.y0 + r.h <= r.H,
+               "sam2_transform_srcs: window %d = (x %d, y %d, w %d, h %d) leaves the %d x %d image", b, r.x0, r.y0, r.w, r.h, r.W, r.H);
+    const float sy = (float)r.h / (float)R, sx = (float)r.w / (float)R;
+    CVMI_CHECK(2.f * (sy > 1.f ? sy : 1.f) + 2.f <= AA_MAXTAPS && 2.f * (sx > 1.f ? sx : 1.f) + 2.f <= AA_MAXTAPS,
+               "sam2_transform_srcs: down-scale factor of window %d too large", b);
+  }
+  hipStream_t s = (hipStream_t)stream_;
+  const int sw = swap_rb ? 1 : 0;
+  const size_t esz = dst_dtype == CVMI_F32 ? 4 : 2;
+  for (int b0 = 0; b0 < B; b0 += RECT_MAX) {
+    const int nb = B - b0 < RECT_MAX ? B - b0 : RECT_MAX;
+    SrcTable t;
+    for (int b = 0; b < RECT_MAX; ++b) t.r[b] = rows[b0 + (b < nb ? b : 0)];
+    const dim3 g(grid_for((long long)R * R), nb), blk(256);
+    char* d = (char*)dst + (size_t)b0 * R * R * 3 * esz;
+    if (dst_dtype == CVMI_F16) hipLaunchKernelGGL(sam2_transform_srcs_kernel<_Float16>, g, blk, 0, s, src, t, (_Float16*)d, R, sw);
+    else if (dst_dtype == CVMI_BF16) hipLaunchKernelGGL(sam2_transform_srcs_kernel<__bf16>, g, blk, 0, s, src, t, (__bf16*)d, R, sw);
+    else hipLaunchKernelGGL(sam2_transform_srcs_kernel<float>, g, blk, 0, s, src, t, (float*)d, R, sw);
+    CVMI_LAUNCH_CHECK();
+  }
   return 0;
 }
 #endif

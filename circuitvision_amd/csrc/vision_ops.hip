@@ -346,6 +346,106 @@ __global__ __launch_bounds__(256) void letterbox_kernel(const uint8_t* __restric
 }
 
 // ------------------------------------------------------------------------------------------------
+// Ragged letterbox: B sources of DIFFERENT sizes (rows of a table in the kernel arguments, each with its byte offset into one packed u8
+// buffer) onto one out_h x out_w canvas shape, grid = (tiles, images).  A workgroup owns 16 rows x 64 columns of the canvas:
+//  * the tile's 64 column and 16 row entries {s0, s1, a0, a1} are computed ONCE (80 lb_axis calls per 1024 pixels instead of 2048; the same
+//    function as letterbox_kernel, so the same bits) and shared through LDS; an entry outside the resized image has s0 = -1
+//  * a tile that lies wholly in the padding reads nothing: no table, no barrier, only the constant's stores
+//  * no integer division per pixel (one per workgroup, for the tile's origin)
+//  * S2D: a thread owns one 2 x 2 block = the 16 channels of one output pixel, zero channels 12..15 included, and writes them as 16-byte
+//    stores (4 for f32, 2 for f16); otherwise a thread owns 4 pixels of one column, 3 scalar stores each (not the detector's path)
+constexpr int LBR_MAX = 64, LBR_TW = 64, LBR_TH = 16;
+struct LbRaggedTable { cvmi_letterbox_row r[LBR_MAX]; };
+
+// one canvas pixel from its column / row entries: the arithmetic of letterbox_kernel
+__device__ __forceinline__ void lbr_pixel(const uint8_t* __restrict__ src, int W, bool ident, const int4 cx, const int4 cy, int (&v)[3]) {
+  v[0] = v[1] = v[2] = 114;
+  if (cx.x < 0 || cy.x < 0) return;
+  if (ident) {
+    const uint8_t* s = src + ((size_t)cy.x * W + cx.x) * 3;
+    v[0] = s[0]; v[1] = s[1]; v[2] = s[2];
+    return;
+  }
+  const uint8_t* r0p = src + (size_t)cy.x * W * 3;
+  const uint8_t* r1p = src + (size_t)cy.y * W * 3;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const int r0 = r0p[(size_t)cx.x * 3 + c] * cx.z + r0p[(size_t)cx.y * 3 + c] * cx.w;
+    const int r1 = r1p[(size_t)cx.x * 3 + c] * cx.z + r1p[(size_t)cx.y * 3 + c] * cx.w;
+    const int o = (((cy.z * (r0 >> 4)) >> 16) + ((cy.w * (r1 >> 4)) >> 16) + 2) >> 2;
+    v[c] = o < 0 ? 0 : (o > 255 ? 255 : o);
+  }
+}
+
+template <typename T, bool S2D>
+__global__ __launch_bounds__(256) void letterbox_ragged_kernel(const uint8_t* __restrict__ src_base, const LbRaggedTable tab, T* __restrict__ dst,
+                                                              int out_h, int out_w, int tiles_x, long long dst_image_stride) {
+  __shared__ int4 colent[LBR_TW];
+  __shared__ int4 rowent[LBR_TH];
+  const cvmi_letterbox_row g = tab.r[blockIdx.y];
+  const uint8_t* __restrict__ src = src_base + g.src_byte_offset;
+  dst += (size_t)blockIdx.y * dst_image_stride;
+  const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+  const int ox0 = tx * LBR_TW, oy0 = ty * LBR_TH;
+  const int tid = threadIdx.x;
+  // the same for every thread of the workgroup: the branch holds no barrier on one side only
+  const bool pad_only = ox0 >= g.left + g.new_w || ox0 + LBR_TW <= g.left || oy0 >= g.top + g.new_h || oy0 + LBR_TH <= g.top;
+  const bool ident = g.new_w == g.W && g.new_h == g.H;
+  if (!pad_only) {
+    if (tid < LBR_TW + LBR_TH) {
+      const bool col = tid < LBR_TW;
+      const int r = col ? ox0 + tid - g.left : oy0 + (tid - LBR_TW) - g.top;          // index inside the resized image
+      const int dn = col ? g.new_w : g.new_h, sn = col ? g.W : g.H;
+      int4 e = make_int4(-1, -1, 0, 0);
+      if (r >= 0 && r < dn) {
+        int s0 = r, s1 = r, a0 = 2048, a1 = 0;                       // the identity copy reads tap s0 alone
+        if (!ident) lb_axis(r, dn, sn, s0, s1, a0, a1);
+        e = make_int4(s0, s1, a0, a1);
+      }
+      if (col) colent[tid] = e; else rowent[tid - LBR_TW] = e;
+    }
+    __syncthreads();
+  }
+  const int4 none = make_int4(-1, -1, 0, 0);
+  if constexpr (S2D) {
+    constexpr int NV = 16 * (int)sizeof(T) / 16;                     // 16-byte stores per output pixel
+    const int bx = tid & 31, by = tid >> 5;                          // the thread's 2 x 2 block inside the tile
+    const int ox = ox0 + 2 * bx, oy = oy0 + 2 * by;
+    if (ox >= out_w || oy >= out_h) return;                          // (out_w, out_h even: a block is inside or outside as a whole)
+    float ch[16];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int dy = q >> 1, dx = q & 1;
+      int v[3];
+      lbr_pixel(src, g.W, ident, pad_only ? none : colent[2 * bx + dx], pad_only ? none : rowent[2 * by + dy], v);
+      ch[q * 3 + 0] = (float)v[2] / 255.0f;                          // reversed channel order (ultralytics im[..., ::-1])
+      ch[q * 3 + 1] = (float)v[1] / 255.0f;
+      ch[q * 3 + 2] = (float)v[0] / 255.0f;
+    }
+    ch[12] = ch[13] = ch[14] = ch[15] = 0.f;
+    u32x4* o = reinterpret_cast<u32x4*>(dst + ((size_t)(oy >> 1) * (out_w >> 1) + (ox >> 1)) * 16);
+#pragma unroll
+    for (int i = 0; i < NV; ++i) o[i] = pack16<T>(ch + i * Elem<T>::VEC);
+  } else {
+    const int lx = tid & 63, ox = ox0 + lx;
+    if (ox >= out_w) return;
+    const int4 cx = pad_only ? none : colent[lx];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int ly = (tid >> 6) + 4 * k, oy = oy0 + ly;
+      if (oy < out_h) {
+        int v[3];
+        lbr_pixel(src, g.W, ident, cx, pad_only ? none : rowent[ly], v);
+        T* o = dst + ((size_t)oy * out_w + ox) * 3;
+        o[0] = (T)((float)v[2] / 255.0f);
+        o[1] = (T)((float)v[1] / 255.0f);
+        o[2] = (T)((float)v[0] / 255.0f);
+      }
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 template <typename TS, typename TD>
 __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const TS* __restrict__ src, TD* __restrict__ dst, int dst_ld, int B, int C, int H, int W) {
   const long long total = (long long)B * C * H * W;
@@ -486,6 +586,43 @@ extern "C" int cvmi_letterbox_batch(const uint8_t* src, int B, int H, int W, voi
   else
     hipLaunchKernelGGL(letterbox_kernel<float>, dim3(grid_for(total), B), dim3(256), 0, stream, src, H, W, (float*)dst, out_h, out_w, new_h, new_w, top, left, s2d, dst_image_stride);
   CVMI_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int cvmi_letterbox_ragged(const uint8_t* src, long long src_bytes, const cvmi_letterbox_row* rows, int B, void* dst,
+                                     long long dst_image_stride, int out_h, int out_w, int dtype, int s2d, cvmi_stream_t stream_) {
+  CVMI_CHECK(!s2d || (out_h % 2 == 0 && out_w % 2 == 0), "letterbox_ragged: space-to-depth output needs even out_h, out_w");
+  CVMI_CHECK(src && dst && rows && src_bytes > 0, "letterbox_ragged: null pointer");
+  CVMI_CHECK(out_h > 0 && out_w > 0 && B >= 1 && (B == 1 || dst_image_stride >= (long long)out_h * out_w * (s2d ? 4 : 3)),
+             "letterbox_ragged: bad batch / image stride");
+  CVMI_CHECK(dtype == CVMI_F16 || dtype == CVMI_F32, "letterbox_ragged: bad dtype");
+  const long long esz = dtype == CVMI_F16 ? 2 : 4;
+  CVMI_CHECK(!s2d || (((uintptr_t)dst & 15) == 0 && (B == 1 || dst_image_stride * esz % 16 == 0)),
+             "letterbox_ragged: the space-to-depth output is written in 16-byte stores: dst and the image stride must be 16-byte aligned");
+  for (int b = 0; b < B; ++b) {                                     // every row before the first launch: a bad row leaves nothing half done
+    const cvmi_letterbox_row& r = rows[b];
+    CVMI_CHECK(r.H > 0 && r.W > 0 && r.new_h > 0 && r.new_w > 0 && r.top >= 0 && r.left >= 0 && (long long)r.top + r.new_h <= out_h &&
+                   (long long)r.left + r.new_w <= out_w,
+               "letterbox_ragged: row %d: bad geometry (source %d x %d -> %d x %d at top %d, left %d of the %d x %d canvas)", b, r.H, r.W, r.new_h,
+               r.new_w, r.top, r.left, out_h, out_w);
+    CVMI_CHECK(r.src_byte_offset >= 0 && r.src_byte_offset + (long long)r.H * r.W * 3 <= src_bytes,
+               "letterbox_ragged: row %d: %d x %d x 3 bytes at offset %lld leave the %lld-byte source buffer", b, r.H, r.W, r.src_byte_offset, src_bytes);
+  }
+  hipStream_t stream = (hipStream_t)stream_;
+  const int tiles_x = (out_w + LBR_TW - 1) / LBR_TW, tiles_y = (out_h + LBR_TH - 1) / LBR_TH;
+  CVMI_CHECK((long long)tiles_x * tiles_y < (1ll << 31), "letterbox_ragged: canvas too large");
+  for (int b0 = 0; b0 < B; b0 += LBR_MAX) {
+    const int nb = B - b0 < LBR_MAX ? B - b0 : LBR_MAX;
+    LbRaggedTable t;
+    for (int b = 0; b < LBR_MAX; ++b) t.r[b] = rows[b0 + (b < nb ? b : 0)];
+    const dim3 g(tiles_x * tiles_y, nb), blk(256);
+    char* d = (char*)dst + (size_t)b0 * dst_image_stride * esz;
+#define CVMI_LBR(T, S) hipLaunchKernelGGL((letterbox_ragged_kernel<T, S>), g, blk, 0, stream, src, t, (T*)d, out_h, out_w, tiles_x, dst_image_stride)
+    if (dtype == CVMI_F16) { if (s2d) CVMI_LBR(f16, true); else CVMI_LBR(f16, false); }
+    else { if (s2d) CVMI_LBR(float, true); else CVMI_LBR(float, false); }
+#undef CVMI_LBR
+    CVMI_LAUNCH_CHECK();
+  }
   return 0;
 }
 #endif

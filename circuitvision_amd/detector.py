@@ -35,6 +35,74 @@ def letterbox_geometry(h, w, new_shape=640, stride=32, auto=True):
     return nw, nh, top, bottom, left, right
 
 
+def pack_layout(shapes):
+    """Byte offsets of u8 [h, w, 3] images packed back to back in one flat buffer: -> ([offset per image], total bytes).  No alignment is
+    added: every kernel that reads the block takes any byte offset."""
+    offsets, off = [], 0
+    for h, w in shapes:
+        if h <= 0 or w <= 0:
+            raise ValueError(f"empty image {h} x {w}")
+        offsets.append(off)
+        off += int(h) * int(w) * 3
+    return offsets, off
+
+
+def letterbox_rows(shapes, offsets, imgsz):
+    """The table cvmi_letterbox_ragged reads (numpy records of `_lib.LETTERBOX_ROW`), one row per source: ultralytics'
+    LetterBox(imgsz, auto=False) -- what a list of differently sized images gets -- on an imgsz x imgsz canvas."""
+    rows = np.zeros(len(shapes), dtype=_lib.LETTERBOX_ROW)
+    for b, ((h, w), off) in enumerate(zip(shapes, offsets)):
+        nw, nh, top, _bottom, left, _right = letterbox_geometry(h, w, imgsz, auto=False)
+        rows[b] = (off, h, w, nh, nw, top, left)
+    return rows
+
+
+class PackedImages:
+    """u8 images of DIFFERENT sizes in one flat device buffer: `.data` u8 [bytes] (device), `.offsets` the byte offset of each image in
+    `.data`, `.shapes` their (h, w).  `packed[i:j]` is the same buffer with the offsets / shapes of images i .. j - 1 (no copy)."""
+
+    def __init__(self, data, offsets, shapes):
+        if not (torch.is_tensor(data) and data.dtype == torch.uint8 and data.dim() == 1 and data.is_contiguous()) or len(offsets) != len(shapes):
+            raise TypeError("PackedImages: data is a contiguous 1-D uint8 tensor, with one offset per shape")
+        for off, (h, w) in zip(offsets, shapes):
+            if off < 0 or h <= 0 or w <= 0 or off + h * w * 3 > data.numel():
+                raise ValueError(f"PackedImages: a {h} x {w} image at byte {off} leaves the {data.numel()}-byte buffer")
+        self.data, self.offsets, self.shapes = data, [int(o) for o in offsets], [(int(h), int(w)) for h, w in shapes]
+
+    def __len__(self):
+        return len(self.shapes)
+
+    def __getitem__(self, sl):
+        if not isinstance(sl, slice):
+            raise TypeError("PackedImages is sliced by image range; .image(b) is one image")
+        return PackedImages(self.data, self.offsets[sl], self.shapes[sl])
+
+    def image(self, b):
+        """u8 [h, w, 3] view of image b."""
+        (h, w), off = self.shapes[b], self.offsets[b]
+        return self.data[off:off + h * w * 3].view(h, w, 3)
+
+    @staticmethod
+    def stage(images, host):
+        """The one host pass over the pixels: every image into the flat (pinned) u8 tensor `host` -> (offsets, total bytes)."""
+        shapes = [im.shape[:2] for im in images]
+        offsets, total = pack_layout(shapes)
+        if host.numel() < total:
+            raise ValueError(f"staging buffer of {host.numel()} bytes for {total} bytes of images")
+        hv = host.numpy()
+        for im, off, (h, w) in zip(images, offsets, shapes):
+            hv[off:off + h * w * 3].reshape(h, w, 3)[...] = im
+        return offsets, total
+
+    @classmethod
+    def upload(cls, images, device="cuda"):
+        """One pinned flat staging buffer, one host pass, ONE H2D copy on the current stream (nothing waits)."""
+        _, total = pack_layout([im.shape[:2] for im in images])
+        host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+        offsets, _ = cls.stage(images, host)
+        return cls(host.to(device, non_blocking=True), offsets, [im.shape[:2] for im in images])
+
+
 class Boxes:
     def __init__(self, det):
         self.data = det                      # [n, 6] x1,y1,x2,y2,conf,cls (host tensor: one D2H copy per batch brought it over)
@@ -103,6 +171,7 @@ class YOLO:
         self.names = names
         self.stream = torch.cuda.Stream(device=device)
         self._plans, self._staging = {}, {}
+        self._flat_staging = [None, None]  # mixed sizes: ONE flat pinned buffer (grown when a batch needs more) and its last H2D's event
         self._lock = threading.Lock()      # one analyzer is shared by all Streamlit sessions (app.py:134)
 
     @classmethod
@@ -120,6 +189,7 @@ class YOLO:
         self.model = SimpleNamespace(names=self.names, nc=len(self.names), scale=weights.scale, stride=32)
         self.stream = torch.cuda.Stream(device=device)
         self._plans, self._staging = {}, {}
+        self._flat_staging = [None, None]
         self._lock = threading.Lock()
         return self
 
@@ -142,10 +212,13 @@ class YOLO:
         return self._plans[key]
 
     # ---- reference entry point -----------------------------------------------------------------
-    def predict(self, image, verbose=True, conf=0.25, iou=0.7, max_det=300, imgsz=None, **_):
-        """image: uint8 HxWx3 numpy array (or a list of same-shaped ones).  Returns [Results] (host tensors: the reference reads them
-        through `.cpu().numpy().tolist()`, circuit_analyzer.py:270-273)."""
-        out = self.predict_async(image, conf=conf, iou=iou, max_det=max_det, imgsz=imgsz).result()
+    def predict(self, image, verbose=True, conf=0.25, iou=0.7, max_det=300, imgsz=None, rect=None, **_):
+        """image: uint8 HxWx3 numpy array, or a list of them (any sizes).  Returns [Results] (host tensors: the reference reads them
+        through `.cpu().numpy().tolist()`, circuit_analyzer.py:270-273).
+        rect: None = ultralytics' rule (BasePredictor.pre_transform: LetterBox(auto = same_shapes and rect)): a list that shares one size is
+        letterboxed to the smallest stride-multiple rectangle, a mixed list to the full imgsz x imgsz square, every image with its own
+        geometry, as ONE batch.  False forces the square for equal sizes too: one plan whatever arrives."""
+        out = self.predict_async(image, conf=conf, iou=iou, max_det=max_det, imgsz=imgsz, rect=rect).result()
         if verbose:
             H, W = out[0].letterboxed_shape if out else (0, 0)
             print(f"cvmi355 YOLO11{self.model.scale}: {H}x{W} {', '.join(str(len(r)) + ' boxes' for r in out)}")
@@ -153,21 +226,75 @@ class YOLO:
 
     __call__ = predict
 
-    def predict_async(self, image, conf=0.25, iou=0.7, max_det=300, imgsz=None):
+    @staticmethod
+    def _check_images(images):
+        if not images:
+            raise ValueError("predict needs at least one image")
+        for im in images:
+            if not (isinstance(im, np.ndarray) and im.ndim == 3 and im.shape[2] == 3 and im.dtype == np.uint8):
+                raise TypeError("predict expects uint8 HxWx3 numpy images")
+            if im.shape[0] == 0 or im.shape[1] == 0:
+                raise ValueError("predict got an empty image")
+
+    @staticmethod
+    def _square(images, rect):
+        """ultralytics' auto = same_shapes and rect, negated: True = the full imgsz x imgsz canvas (the ragged letterbox)."""
+        same = all(im.shape[:2] == images[0].shape[:2] for im in images)
+        return not (same and (True if rect is None else bool(rect)))
+
+    def _predict_square(self, images, chunk, conf, iou, max_det, imgsz, after_chunk=None):
+        """Every image to the imgsz x imgsz canvas with its own geometry: ONE flat pinned staging buffer, one host pass, ONE H2D copy, then
+        per chunk ONE cvmi_letterbox_ragged launch + plan(B, imgsz, imgsz) replay + D2H of the detections.  -> one handle per chunk."""
+        lib = _lib.load()
+        n = len(images)
+        shapes = [tuple(int(v) for v in im.shape[:2]) for im in images]
+        out = []
+        with self._lock, torch.cuda.device(self.device):
+            offsets, total = pack_layout(shapes)
+            st = self._flat_staging
+            if st[1] is not None:
+                st[1].synchronize()                                     # the previous call's H2D copy has left the buffer
+            if st[0] is None or st[0].numel() < total:
+                st[0] = torch.empty(max(total, 1 << 20) * 5 // 4, dtype=torch.uint8, pin_memory=True)
+            PackedImages.stage(images, st[0])
+            rows = letterbox_rows(shapes, offsets, imgsz)
+            sp = self.stream.cuda_stream
+            with torch.cuda.stream(self.stream):
+                packed = PackedImages(st[0][:total].to(self.device, non_blocking=True), offsets, shapes)
+                st[1] = torch.cuda.Event()
+                st[1].record(self.stream)
+                for c0 in range(0, n, chunk):
+                    B = min(chunk, n - c0)
+                    p = self.plan(B, imgsz, imgsz, conf, iou, max_det)
+                    det_h = torch.empty(B, p.max_det, 6, dtype=torch.float32, pin_memory=True)
+                    idx_h = torch.empty(B, p.max_det, dtype=torch.int32, pin_memory=True)
+                    cnt_h = torch.empty(B, dtype=torch.int32, pin_memory=True)
+                    _lib.check(lib.cvmi_letterbox_ragged(packed.data.data_ptr(), total, rows[c0:c0 + B].ctypes.data, B, p.x_in.t.data_ptr(),
+                                                         p.x_in.t[0].numel(), imgsz, imgsz, self.dtype, 1, sp), "letterbox_ragged")
+                    p.plan.run()
+                    det_h.copy_(p.det, non_blocking=True)
+                    idx_h.copy_(p.det_idx, non_blocking=True)
+                    cnt_h.copy_(p.det_count, non_blocking=True)
+                    h = PendingDetections(None, det_h, idx_h, cnt_h, (imgsz, imgsz), None, self.names, packed, src=packed[c0:c0 + B], det_dev=p.det,
+                                          cnt_dev=p.det_count, orig_shapes=shapes[c0:c0 + B])
+                    if after_chunk is not None:
+                        h.after = after_chunk(h)
+                    h.done = torch.cuda.Event()
+                    h.done.record(self.stream)
+                    out.append(h)
+        return out
+
+    def predict_async(self, image, conf=0.25, iou=0.7, max_det=300, imgsz=None, rect=None):
         """Batch-shaped, stream-ordered form of `predict`: ONE pinned staging buffer and ONE H2D copy for the batch, ONE letterbox launch,
         the captured graph, ONE D2H copy of (detections, anchor indices, counts) -- all enqueued on the detector's stream -- and nothing
         waits.  Returns a handle; `.result()` waits for the copy and builds the `Results` on the host (scale_boxes + clip there: ultralytics'
         own CPU arithmetic on <= 300 boxes).  The caller may do other work -- or enqueue the segmenter -- in between."""
         imgsz = self.imgsz if imgsz is None else self._check_imgsz(imgsz)
         images = image if isinstance(image, (list, tuple)) else [image]
-        if not images:
-            raise ValueError("predict needs at least one image")
-        for im in images:
-            if not (isinstance(im, np.ndarray) and im.ndim == 3 and im.shape[2] == 3 and im.dtype == np.uint8):
-                raise TypeError("predict expects uint8 HxWx3 numpy images")
+        self._check_images(images)
+        if self._square(images, rect):                                  # mixed sizes (or rect=False): see predict
+            return self._predict_square(images, len(images), conf, iou, max_det, imgsz)[0]
         h0, w0 = images[0].shape[:2]
-        if any(im.shape[:2] != (h0, w0) for im in images):
-            raise ValueError("a batch must share one image size")
         nw, nh, top, bottom, left, right = letterbox_geometry(h0, w0, imgsz)
         H, W = nh + top + bottom, nw + left + right
         lib = _lib.load()
@@ -200,7 +327,7 @@ class YOLO:
                 done.record(self.stream)
         return PendingDetections(done, det_h, idx_h, cnt_h, (H, W), (h0, w0), self.names, src)
 
-    def predict_chunks_async(self, images, chunk, conf=0.25, iou=0.7, max_det=300, imgsz=None, after_chunk=None):
+    def predict_chunks_async(self, images, chunk, conf=0.25, iou=0.7, max_det=300, imgsz=None, after_chunk=None, rect=None):
         """A batch pipeline's form of `predict_async`: ONE pinned staging pass and ONE H2D copy for all equally sized `images`, then one
         letterbox launch + graph replay + D2H of the detections per `chunk` images -- so the host can take chunk 0's boxes (and start what
         depends on them: the crop window, the segmenter) while the GPU still runs the later chunks.  Returns one handle per chunk; handle.src
@@ -209,16 +336,14 @@ class YOLO:
         handle.det_dev / handle.cnt_dev are the plan's own DEVICE outputs of that chunk (f32 [b, max_det, 6] letterboxed, i32 [b]).  The next
         chunk's replay overwrites them, so whoever reads them does so on the detector's stream right after the replay: `after_chunk(handle)`
         is called there, inside the stream context and before the chunk's `done` event is recorded -- what it enqueues (e.g. glue.stage2_crop
-        into tensors of its own, and their D2H copies) is complete when `done` is; its return value is kept as handle.after."""
+        into tensors of its own, and their D2H copies) is complete when `done` is; its return value is kept as handle.after.
+        Images of different sizes (or rect=False, see predict): every chunk runs on the imgsz x imgsz canvas, handle.src is a `PackedImages`
+        slice and handle.orig_shapes the chunk's (h, w) list (handle.orig_shape is None)."""
         imgsz = self.imgsz if imgsz is None else self._check_imgsz(imgsz)
-        if not images:
-            raise ValueError("predict needs at least one image")
-        for im in images:
-            if not (isinstance(im, np.ndarray) and im.ndim == 3 and im.shape[2] == 3 and im.dtype == np.uint8):
-                raise TypeError("predict expects uint8 HxWx3 numpy images")
+        self._check_images(images)
+        if self._square(images, rect):
+            return self._predict_square(images, max(1, int(chunk)), conf, iou, max_det, imgsz, after_chunk)
         h0, w0 = images[0].shape[:2]
-        if any(im.shape[:2] != (h0, w0) for im in images):
-            raise ValueError("a batch must share one image size")
         nw, nh, top, bottom, left, right = letterbox_geometry(h0, w0, imgsz)
         H, W = nh + top + bottom, nw + left + right
         lib = _lib.load()
@@ -262,9 +387,10 @@ class YOLO:
 class PendingDetections:
     """Detections in flight (YOLO.predict_async).  `.result()` -> [Results], one per image."""
 
-    def __init__(self, done, det, idx, cnt, lb_shape, orig_shape, names, keep, src=None, det_dev=None, cnt_dev=None):
+    def __init__(self, done, det, idx, cnt, lb_shape, orig_shape, names, keep, src=None, det_dev=None, cnt_dev=None, orig_shapes=None):
         self.done, self.det, self.idx, self.cnt, self.lb_shape, self.orig_shape, self.names, self._keep = done, det, idx, cnt, lb_shape, orig_shape, names, keep
-        self.src = src                       # (predict_chunks_async) the chunk's u8 device images, for whoever crops from them
+        self.orig_shapes = orig_shapes       # a mixed batch: one (h, w) per image (orig_shape is None); every image has its own scale_boxes
+        self.src = src                       # (predict_chunks_async) the chunk's u8 device images (a [b,h,w,3] block, or a PackedImages slice), for whoever crops from them
         self.det_dev, self.cnt_dev = det_dev, cnt_dev        # (predict_chunks_async) the plan's device outputs: valid on the detector's stream until its next replay
         self.after = None                    # what predict_chunks_async's after_chunk returned
         self._out = None
@@ -275,9 +401,10 @@ class PendingDetections:
             self._keep = None
             out = []
             for b, n in enumerate(self.cnt.tolist()):
+                shape = self.orig_shape if self.orig_shapes is None else self.orig_shapes[b]
                 det = self.det[b, :n].clone()
-                det[:, :4] = scale_boxes(self.lb_shape, det[:, :4], self.orig_shape)
-                r = Results(det, self.names, self.orig_shape, self.idx[b, :n].clone())
+                det[:, :4] = scale_boxes(self.lb_shape, det[:, :4], shape)
+                r = Results(det, self.names, shape, self.idx[b, :n].clone())
                 r.letterboxed_shape = self.lb_shape
                 out.append(r)
             self._out = out

@@ -52,7 +52,7 @@ class CircuitPipeline:
     segmenter: `SAM2Model`-like (`infer_masks(x, boxes=None)`, `.image_size`); transforms: `SAM2Transforms`-like."""
 
     def __init__(self, detector, segmenter, transforms, stage2_iou=0.6, max_prompts=32, crop_fn=None, swap_channels=True, seg_batch=16, crop=False,
-                 crop_padding=80, nodes=False, reclassify=False, device_glue=False):
+                 crop_padding=80, nodes=False, reclassify=False, device_glue=False, mixed_batch=False):
         """crop=True: the reference's chain -- detector -> stage-2 NMS -> crop window from the boxes (crop.py) -> segmenter on the window
         (analysis_pipeline.py:177 -> :206); False: the segmenter sees the whole image.  crop_fn overrides the built-in crop.
         swap_channels: segment_with_sam2 applies cv2.COLOR_BGR2RGB to whatever it is given (circuit_analyzer.py:343), and the
@@ -69,13 +69,21 @@ class CircuitPipeline:
         device_glue=True (needs crop=True without a crop_fn, and this package's own detector / segmenter / transforms): what sits between the
         two models in the cropped chain -- scale_boxes, rounding, stage-2 NMS, the crop window, the box shift -- runs as one kernel on the
         detector's stream (glue.py) and the segmenter reads its windows from device memory: no host wait between the detector's first kernel
-        and the segmenter's last.  Same result dicts, key for key and bit for bit."""
+        and the segmenter's last.  Same result dicts, key for key and bit for bit.
+        mixed_batch=True: images of different sizes go to the detector as ONE batch (ultralytics' rule for a mixed list: every image
+        letterboxed to the full imgsz x imgsz square, `YOLO.predict`) -- one packed upload, one ragged letterbox launch and one square plan per
+        chunk size instead of a detector batch, a staging buffer and a plan per image size; the cropped chain's segmenter and `reclassify`
+        read their windows out of the packed block.  False (default): one detector batch per image size, each on its own rectangle.  Not
+        with device_glue=True: cvmi_stage2_crop takes one image size per launch."""
         if not (isinstance(nodes, bool) or nodes == "connections"):
             raise ValueError("nodes must be False, True or 'connections'")
         self.det, self.seg, self.tr = detector, segmenter, transforms
         self.device_glue = bool(device_glue)
         if self.device_glue and not (crop and crop_fn is None and self._product_objects()):
             raise ValueError("device_glue=True needs crop=True, no crop_fn, and this package's own YOLO / SAM2Model / SAM2Transforms")
+        self.mixed_batch = bool(mixed_batch)
+        if self.mixed_batch and self.device_glue:
+            raise ValueError("mixed_batch=True cannot be combined with device_glue=True: the device glue takes one image size per launch")
         self._glue_flags = None                    # (class names, their flag table on the device)
         self.stage2_iou, self.max_prompts, self.swap = stage2_iou, max_prompts, swap_channels
         self.crop_padding = int(crop_padding)
@@ -93,14 +101,20 @@ class CircuitPipeline:
         self.timings[name] += t1 - t0
         return t1
 
+    def _detector_groups(self, images):
+        """Image indices per detector batch: one batch per image size, or -- mixed_batch=True -- the whole list as one."""
+        if self.mixed_batch:
+            return [list(range(len(images)))]
+        groups = {}
+        for i, im in enumerate(images):
+            groups.setdefault(im.shape[:2], []).append(i)
+        return list(groups.values())
+
     # ---- stage A: analysis_pipeline.py:97-115
     def detect(self, images):
         """-> per image: the bboxes that survive the second-stage NMS (list of dicts, original pixel coordinates)."""
         out = [None] * len(images)
-        groups = {}
-        for i, im in enumerate(images):
-            groups.setdefault(im.shape[:2], []).append(i)
-        for idxs in groups.values():                                   # one detector batch per image size
+        for idxs in self._detector_groups(images):                     # one detector batch per image size (mixed_batch: one in all)
             t = time.perf_counter()
             res = self.det.predict([images[i] for i in idxs], verbose=False)
             t = self._tick("detect.predict (H2D + letterbox + YOLO11 + NMS + D2H)", t)
@@ -242,10 +256,7 @@ class CircuitPipeline:
         chunks = [images[c0:c0 + self.seg_batch] for c0 in range(0, len(images), self.seg_batch)]
         pend = [self._enqueue_learned(chunks[0], 0)]
         t = self._tick("enqueue: segmenter chunk 0 (stage u8 + H2D + transform + SAM 2.1 graph + post-process launches)", t)
-        groups = {}
-        for i, im in enumerate(images):
-            groups.setdefault(im.shape[:2], []).append(i)
-        handles = [(idxs, self.det.predict_async([images[i] for i in idxs])) for idxs in groups.values()]
+        handles = [(idxs, self.det.predict_async([images[i] for i in idxs])) for idxs in self._detector_groups(images)]
         t = self._tick("enqueue: detector (stage u8 + H2D + letterbox + YOLO11 graph + NMS + D2H launches)", t)
         pend += [self._enqueue_learned(ch, (k + 1) % self.seg_slots) for k, ch in enumerate(chunks[1:])]
         t = self._tick("enqueue: segmenter chunks 1.. (same, while the GPU runs chunk 0)", t)
@@ -274,11 +285,8 @@ class CircuitPipeline:
     #      and segmenter chunks < k.  Only chunk 0's detector pass + glue is not hidden.
     def _run_cropped(self, images):
         t = time.perf_counter()
-        groups = {}
-        for i, im in enumerate(images):
-            groups.setdefault(im.shape[:2], []).append(i)
         work = []                                                          # (image indices of the chunk, detector handle)
-        for idxs in groups.values():
+        for idxs in self._detector_groups(images):
             hs = self.det.predict_chunks_async([images[i] for i in idxs], self.seg_batch)
             work += [(idxs[k * self.seg_batch:(k + 1) * self.seg_batch], h) for k, h in enumerate(hs)]
         t = self._tick("enqueue: detector chunks (stage u8 + ONE H2D + per chunk: letterbox + YOLO11 graph + NMS + D2H launches)", t)
@@ -398,9 +406,10 @@ class CircuitPipeline:
         from . import _lib
         seg, tr = self.seg, self.tr
         lib = _lib.load()
-        if src is not None:                                             # windows of a u8 device block (the cropped chain)
-            B, R = src.shape[0], seg.image_size
-            sizes = [tuple(src.shape[1:3]) if w is None else (w[3] - w[1], w[2] - w[0]) for w in windows]
+        if src is not None:                                             # windows of a u8 device block / PackedImages (the cropped chain)
+            B, R = len(src), seg.image_size
+            whole = src.shapes if hasattr(src, "shapes") else [tuple(src.shape[1:3])] * B
+            sizes = [whole[b] if w is None else (w[3] - w[1], w[2] - w[0]) for b, w in enumerate(windows)]
         else:
             B, R = len(imgs), seg.image_size
             sizes = [tuple(im.shape[:2]) for im in imgs]
@@ -423,7 +432,7 @@ class CircuitPipeline:
             sst.wait_stream(torch.cuda.current_stream())
             if det_stream is not None:
                 sst.wait_stream(det_stream)                                 # (the u8 block's H2D copy: already complete -- result() waited -- but stated)
-            for t_ in (iou, ext, u8) + ((src,) if src is not None else ()):
+            for t_ in (iou, ext, u8) + ((getattr(src, "data", src),) if src is not None else ()):
                 t_.record_stream(sst)                                       # written / read on sst: the allocator must not hand them out before sst is past them
             with torch.cuda.stream(sst):
                 sp = sst.cuda_stream

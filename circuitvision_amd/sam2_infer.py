@@ -245,7 +245,7 @@ class SAM2Transforms:
 
     def forward_batch(self, img_list, swap_rb=False, out=None, out_dtype=F32):
         """sam2_infer.py:53-56.  -> f32 [B,3,R,R] (channels-last memory).  Equally sized images go through ONE pinned staging buffer,
-        ONE H2D copy and ONE launch; ragged sizes take one launch each.  swap_rb: read the channels reversed (the caller's BGR2RGB,
+        ONE H2D copy and ONE launch; so do ragged sizes, packed back to back (`detector.PackedImages`, cvmi_sam2_transform_srcs).  swap_rb: read the channels reversed (the caller's BGR2RGB,
         circuit_analyzer.py:343) instead of a host pass over every image.  out / out_dtype: write into an existing [B,R,R,3] device
         tensor of that CVMI dtype (the segmenter's input buffer) instead of a fresh f32 one."""
         require_gpu()
@@ -263,22 +263,44 @@ class SAM2Transforms:
                 hv[b] = im
             src = host.to("cuda", non_blocking=True)
             _lib.check(lib.cvmi_sam2_transform_batch(src.data_ptr(), B, h, w, res.data_ptr(), R, out_dtype, 1 if swap_rb else 0, sp), "sam2_transform")
-        else:
-            for b, im in enumerate(imgs):
-                src = torch.from_numpy(im).cuda()
-                _lib.check(lib.cvmi_sam2_transform_batch(src.data_ptr(), 1, im.shape[0], im.shape[1], res[b].data_ptr(), R, out_dtype, 1 if swap_rb else 0, sp),
-                           "sam2_transform")
+        elif B > 1:                                                     # ragged: one packed upload, one launch over whole-image windows
+            from .detector import PackedImages
+            self._transform_srcs(PackedImages.upload(imgs, res.device), [None] * B, res, out_dtype, swap_rb)
+        elif B == 1:
+            src = torch.from_numpy(imgs[0]).cuda()
+            _lib.check(lib.cvmi_sam2_transform_batch(src.data_ptr(), 1, imgs[0].shape[0], imgs[0].shape[1], res.data_ptr(), R, out_dtype, 1 if swap_rb else 0, sp),
+                       "sam2_transform")
         return res.permute(0, 3, 1, 2) if out is None else res
 
+    def _transform_srcs(self, packed, windows, res, out_dtype, swap_rb):
+        """cvmi_sam2_transform_srcs: window b (None = the whole image) of image b of a `PackedImages`, into res[b]."""
+        lib = _lib.load()
+        rows = np.zeros(len(packed), dtype=_lib.SAM2_SRC_ROW)
+        for b, ((h, w), off, wnd) in enumerate(zip(packed.shapes, packed.offsets, windows)):
+            x0, y0, x1, y1 = (0, 0, w, h) if wnd is None else wnd
+            rows[b] = (off, h, w, x0, y0, x1 - x0, y1 - y0)
+        _lib.check(lib.cvmi_sam2_transform_srcs(packed.data.data_ptr(), packed.data.numel(), rows.ctypes.data, len(packed), res.data_ptr(), self.resolution,
+                                                out_dtype, 1 if swap_rb else 0, torch.cuda.current_stream().cuda_stream), "sam2_transform_srcs")
+
     def forward_windows(self, src, windows, swap_rb=False, out=None, out_dtype=F32):
-        """`forward_batch` on a WINDOW of each image of a u8 [B, H, W, 3] DEVICE tensor (e.g. the block the detector's letterbox read:
-        `PendingDetections.src`): windows = [(x0, y0, x1, y1) | None] per image, None = the whole image.  What the reference does with a host
+        """`forward_batch` on a WINDOW of each image of a u8 [B, H, W, 3] DEVICE tensor, or of a `detector.PackedImages` (images of different
+        sizes in one buffer) -- e.g. the block the detector's letterbox read, `PendingDetections.src`: windows = [(x0, y0, x1, y1) | None] per image, None = the whole image.  What the reference does with a host
         crop + a new transform (circuit_analyzer.py:1254 `image[y0:y1, x0:x1]`, then :347) is here a source rectangle of the resize kernel: no
         cropped copy, no second H2D, bit-identical to transforming a contiguous copy of the window."""
         require_gpu()
         lib = _lib.load()
+        from .detector import PackedImages
+        if isinstance(src, PackedImages):                               # images of different sizes in one packed device buffer
+            if not src.data.is_cuda:
+                raise TypeError("forward_windows expects the PackedImages on the device")
+            if len(windows) != len(src):
+                raise ValueError("one window (or None) per image")
+            R = self.resolution
+            res = torch.empty(len(src), R, R, 3, dtype=torch.float32, device=src.data.device) if out is None else out
+            self._transform_srcs(src, windows, res, out_dtype, swap_rb)
+            return res.permute(0, 3, 1, 2) if out is None else res
         if not (torch.is_tensor(src) and src.is_cuda and src.dtype == torch.uint8 and src.dim() == 4 and src.shape[3] == 3 and src.is_contiguous()):
-            raise TypeError("forward_windows expects a contiguous uint8 [B,H,W,3] device tensor")
+            raise TypeError("forward_windows expects a contiguous uint8 [B,H,W,3] device tensor or a PackedImages")
         B, H, W = src.shape[:3]
         if len(windows) != B:
             raise ValueError("one window (or None) per image")

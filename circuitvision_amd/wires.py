@@ -329,6 +329,16 @@ def hits_packed(info, points, boxes, box_start, pair_start):
 
 def _rgb_planes(images, windows):
     """-> (flat u8 device buffer, [(byte offset, pitch, H, W)])."""
+    if windows is not None and hasattr(images, "offsets"):            # rectangles of the images of a detector.PackedImages, read in place
+        if not images.data.is_cuda or len(windows) != len(images):
+            raise ValueError("with windows, a PackedImages is on the device and windows has one entry per image")
+        planes = []
+        for b, (w, (H, W), off) in enumerate(zip(windows, images.shapes, images.offsets)):
+            x0, y0, x1, y1 = (0, 0, W, H) if w is None else (int(v) for v in w)
+            if not (0 <= x0 < x1 <= W and 0 <= y0 < y1 <= H):
+                raise ValueError(f"window {b} = {w} leaves the {H} x {W} image")
+            planes.append((off + y0 * W * 3 + x0 * 3, W * 3, y1 - y0, x1 - x0))
+        return images.data, planes
     if windows is not None:                                           # rectangles of one u8 [B, H, W, 3] device block, read in place
         if not torch.is_tensor(images) or images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3 or not images.is_cuda \
                 or not images.is_contiguous() or len(windows) != images.shape[0]:
@@ -365,8 +375,8 @@ def _dc_id(names):
 
 def reclassify_terminals(images, bboxes, names, red_channel=0, windows=None, events=None):
     """reclassify_terminals_based_on_connectivity (circuit_analyzer.py:2229-2308) for a batch.  images: u8 [H_i, W_i, 3] device tensors
-    or numpy arrays, or -- with windows = [(x0, y0, x1, y1) | None] -- one u8 [B, H, W, 3] device block whose rectangles are the planes
-    (read in place).  red_channel: the channel of `images` that takes cvtColor(RGB2GRAY)'s R weight: 0 for the image
+    or numpy arrays, or -- with windows = [(x0, y0, x1, y1) | None] -- one u8 [B, H, W, 3] device block, or a `detector.PackedImages`
+    (images of different sizes in one buffer), whose rectangles are the planes (read in place).  red_channel: the channel of `images` that takes cvtColor(RGB2GRAY)'s R weight: 0 for the image
     run_terminal_reclassification is handed (it swaps, and the method swaps back), 2 for the method's own argument.
     names: the detector's {id: name} (self.yolo.model.names).  Only images with a 'terminal' box are processed: segment + empty
     (cvmi_segment_circuit), contours, the hit table, then the host rule.  The box dicts are rewritten IN PLACE (:2297-2308).

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define CVMI_VERSION 123
+#define CVMI_VERSION 124
 
 typedef void* cvmi_stream_t; /* hipStream_t */
 
@@ -223,6 +223,20 @@ int cvmi_letterbox(const uint8_t* src, int H, int W, void* dst, int out_h, int o
  * hipMemcpyAsync), image b written at dst + b * dst_image_stride elements (the detector's batched `predict([img, ...])`). */
 int cvmi_letterbox_batch(const uint8_t* src, int B, int H, int W, void* dst, long long dst_image_stride, int out_h, int out_w,
                          int new_h, int new_w, int top, int left, int dtype, int s2d, cvmi_stream_t stream);
+/* The same for B sources of DIFFERENT sizes onto ONE out_h x out_w canvas shape (a mixed list handed to `predict`: ultralytics letterboxes
+ * such a list with auto = False, every image to the full imgsz x imgsz square, and runs it as one batch).  All sources live in one u8 device
+ * buffer of src_bytes bytes (one pinned staging buffer, one H2D copy); image b is the H x W x 3 image at src + rows[b].src_byte_offset -- ANY
+ * byte offset, the taps are read byte by byte -- resized to new_w x new_h at (left, top) of canvas b, written at dst + b * dst_image_stride
+ * elements.  rows is a HOST array, read during the call; it travels in the kernel arguments, 64 images per launch.  Every row is checked as
+ * cvmi_letterbox_batch checks its one geometry, and against src_bytes, BEFORE the first launch; cvmi_last_error names the failing row.
+ * s2d = 1 writes 16-byte stores: dst and dst_image_stride * sizeof(element) must be 16-byte aligned.
+ * Bit-identical to cvmi_letterbox on the same image and geometry (one coefficient function for both kernels). */
+typedef struct cvmi_letterbox_row {
+  long long src_byte_offset;
+  int H, W, new_h, new_w, top, left;
+} cvmi_letterbox_row;
+int cvmi_letterbox_ragged(const uint8_t* src, long long src_bytes, const cvmi_letterbox_row* rows, int B, void* dst,
+                          long long dst_image_stride, int out_h, int out_w, int dtype, int s2d, cvmi_stream_t stream);
 
 /* ---- dtype conversion / layout helpers -------------------------------------------------------- */
 /* NCHW (f32 or f16) -> NHWC dtype */
@@ -413,6 +427,18 @@ int cvmi_sam2_transform_rects(const uint8_t* src, long long src_image_stride, in
  * Bit-identical to cvmi_sam2_transform_rects on the same windows. */
 int cvmi_sam2_transform_rects_dev(const uint8_t* src, long long src_image_stride, int H, int W, const int* rects_dev, int B, void* dst, int R,
                                   int dst_dtype, int swap_rb, cvmi_stream_t stream);
+/* cvmi_sam2_transform_rects for sources of DIFFERENT sizes in one packed u8 device buffer of src_bytes bytes (the block the ragged letterbox
+ * read): image b is the window {x0, y0, w, h} of the H x W x 3 image at src + rows[b].src_byte_offset (any byte offset).  rows is a HOST
+ * array in the kernel arguments, 64 images per launch; every row -- the image inside the buffer, the window inside the image, the tap bound
+ * of the window -- is checked before the first launch.  dst_dtype F16, BF16 or F32.  Bit-identical to cvmi_sam2_transform_rects on each
+ * image alone. */
+typedef struct cvmi_sam2_src_row {
+  long long src_byte_offset;
+  int H, W;
+  int x0, y0, w, h;
+} cvmi_sam2_src_row;
+int cvmi_sam2_transform_srcs(const uint8_t* src, long long src_bytes, const cvmi_sam2_src_row* rows, int B, void* dst, int R, int dst_dtype,
+                             int swap_rb, cvmi_stream_t stream);
 
 /* ---- the glue between the detector and the segmenter, on the device (analysis_pipeline.py:97-115 -> :177): ultralytics' scale_boxes + clip
  * in f32 (subtract the pad, DIVIDE by the gain, clamp), results_to_bboxes' np.rint of the f64 copy, the stage-2 NMS of utils.py:346-361
