@@ -138,6 +138,9 @@ SIGNATURES = {
     "cvmi_mask_extent": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "cvmi_mask_postprocess": (_i, [_vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
     "cvmi_mask_postprocess_sizes": (_i, [_vp, _i, _i, _i, _vp, _f, _vp, _vp, _vp]),
+    "cvmi_mask_cc_workspace": (C.c_size_t, [_i, _i, _i]),
+    "cvmi_mask_components": (_i, [_vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
+    "cvmi_mask_fill_small": (_i, [_vp, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp]),
     "cvmi_node_prepare": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cvmi_enhance_lines": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
     "cvmi_contours_workspace": (C.c_size_t, [_i, _vp]),

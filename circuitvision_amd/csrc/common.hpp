@@ -91,6 +91,32 @@ __device__ __forceinline__ void lb_axis(int d, int dst, int src, int& s0, int& s
 
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
+// ---- lock-free min-root union-find on an int label array, in global memory or in LDS (wire_ops.hip: contours; mask_cc.hip: tiles and seams) ----
+// lab[i] <= i always and a slot only ever decreases, so every chain walk ends at a root whatever stale value it reads on the way.
+__device__ __forceinline__ int ld_relaxed(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+__device__ __forceinline__ int uf_find(const int* lab, int x) {
+  int y = ld_relaxed(lab + x);
+  while (y != x) {
+    x = y;
+    y = ld_relaxed(lab + x);
+  }
+  return x;
+}
+
+// link the two sets by their minimum roots (Playne & Hawick's lock-free union: a stale read only costs another round)
+__device__ __forceinline__ void uf_union(int* lab, int a, int b) {
+  for (;;) {
+    a = uf_find(lab, a);
+    b = uf_find(lab, b);
+    if (a == b) return;
+    if (a > b) { const int t = a; a = b; b = t; }
+    const int old = atomicMin(lab + b, a);
+    if (old == b) return;
+    b = old;
+  }
+}
+
 // ---- exact division of n < 65536 by d <= 65536 via one 64-bit multiply --------------------------
 struct FastDiv {
   unsigned long long mul;

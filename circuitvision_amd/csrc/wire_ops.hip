@@ -190,30 +190,6 @@ __global__ void contour_table_kernel(PlaneRec* tab, const PlaneGeom g, int n0, i
   }
 }
 
-__device__ __forceinline__ int ld_relaxed(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__device__ __forceinline__ int uf_find(const int* lab, int x) {
-  int y = ld_relaxed(lab + x);
-  while (y != x) {
-    x = y;
-    y = ld_relaxed(lab + x);
-  }
-  return x;
-}
-
-// link the two sets by their minimum roots (Playne & Hawick's lock-free union: a stale read only costs another round)
-__device__ __forceinline__ void uf_union(int* lab, int a, int b) {
-  for (;;) {
-    a = uf_find(lab, a);
-    b = uf_find(lab, b);
-    if (a == b) return;
-    if (a > b) { const int t = a; a = b; b = t; }
-    const int old = atomicMin(lab + b, a);
-    if (old == b) return;
-    b = old;
-  }
-}
-
 // foreground = non-zero, or != 255 when the plane's sum exceeds 127 * H * W (get_contours' inversion); binarize: the reference's
 // img[img == 255] = 1 on the caller's array when it did not invert (:401)
 __global__ __launch_bounds__(256) void label_init_kernel(uint8_t* __restrict__ planes, const unsigned long long* __restrict__ sums, const PlaneRec* tab,

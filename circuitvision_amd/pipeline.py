@@ -388,7 +388,11 @@ class CircuitPipeline:
                                                              1 if self.swap else 0, sp), "sam2_transform_rects_dev")
                 p.plan.run()
                 iou.copy_(p.iou, non_blocking=True)
-                _lib.check(lib.cvmi_mask_postprocess_rects_dev(p.high_res.data_ptr(), B, R, R, window.data_ptr(), H0 * W0, float(tr.mask_threshold),
+                hi = p.high_res
+                if tr.fills_small_regions:                                  # holes / sprinkles go while the logits are in HBM, before the resize
+                    hi = tr.fill_small_regions(hi)
+                    hi.record_stream(sst)
+                _lib.check(lib.cvmi_mask_postprocess_rects_dev(hi.data_ptr(), B, R, R, window.data_ptr(), H0 * W0, float(tr.mask_threshold),
                                                                u8.data_ptr(), ext.data_ptr(), sp), "mask_postprocess_rects_dev")
                 ext_h.copy_(ext, non_blocking=True)
                 done = torch.cuda.Event()
@@ -443,6 +447,9 @@ class CircuitPipeline:
                 p.plan.run()
                 iou.copy_(p.iou, non_blocking=True)
                 hi = p.high_res                                             # f32 [B,1,R,R]
+                if tr.fills_small_regions:                                  # holes / sprinkles go while the logits are in HBM, before the resize
+                    hi = tr.fill_small_regions(hi)
+                    hi.record_stream(sst)
                 if same:
                     _lib.check(lib.cvmi_mask_postprocess(hi.data_ptr(), B, R, R, sizes[0][0], sizes[0][1], float(tr.mask_threshold), u8.data_ptr(),
                                                          ext.data_ptr(), sp), "mask_postprocess")

@@ -218,16 +218,41 @@ def get_modified_sam2(model_cfg_path, checkpoint_path, device="cuda", use_high_r
     return model
 
 
+MASK_CC_TILE = 64                                # include/cvmi355.h CVMI_MASK_CC_TILE: the edge of the tiles the labelling runs in LDS
+
+
+def get_connected_components(mask):
+    """Upstream's `sam2.utils.misc.get_connected_components` (imported by sam2_infer.py:14): mask bool / u8 [N,1,H,W] on the device ->
+    (labels, counts), both int32 [N,1,H,W] and 0 on background pixels; 8-connected.  A label is 1 + the flat index of the raster-first
+    pixel of its component (upstream's labels are only distinct per component), counts the component's area.  Enqueued on the current
+    stream (cvmi_mask_components); H and W need not be even."""
+    require_gpu()
+    lib = _lib.load()
+    if not (torch.is_tensor(mask) and mask.is_cuda and mask.dim() == 4 and mask.shape[1] == 1 and mask.dtype in (torch.bool, torch.uint8)):
+        raise TypeError("get_connected_components expects a bool / uint8 [N,1,H,W] device tensor")
+    fg = mask != 0
+    x = fg.float().contiguous()
+    N, _, h, w = x.shape
+    ws_bytes = int(lib.cvmi_mask_cc_workspace(N, h, w))
+    if ws_bytes == 0:
+        raise ValueError(f"get_connected_components: {N} planes of {h} x {w}: sizes must be positive and the pixel count below 2^31")
+    with torch.cuda.device(x.device):
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+        labels, counts = torch.empty(N, 1, h, w, dtype=torch.int32, device=x.device), torch.empty(N, 1, h, w, dtype=torch.int32, device=x.device)
+        _lib.check(lib.cvmi_mask_components(x.data_ptr(), N, h, w, 0.5, labels.data_ptr(), counts.data_ptr(), ws.data_ptr(),
+                                            torch.cuda.current_stream().cuda_stream), "mask_components")
+    return labels * fg, counts * fg                          # the kernel labels both phases; upstream's contract is 0 on the background
+
+
 class SAM2Transforms:
     """sam2_infer.py:29-128.  `__call__` returns an f32 [3,R,R] device tensor (channels-last memory, so the model
     consumes it without a layout pass); `postprocess_masks` with the reference's settings (areas = 0) is the
-    bilinear resize to the original size (:127)."""
+    bilinear resize to the original size (:127); with max_hole_area / max_sprinkle_area > 0 every post-process first removes the small
+    holes and sprinkles of the logits (:100-124, `fill_small_regions`)."""
 
     def __init__(self, resolution, mask_threshold, max_hole_area=0.0, max_sprinkle_area=0.0):
         self.resolution, self.mask_threshold = resolution, mask_threshold
         self.max_hole_area, self.max_sprinkle_area = max_hole_area, max_sprinkle_area
-        if max_hole_area > 0 or max_sprinkle_area > 0:
-            raise NotImplementedError("hole / sprinkle filtering (connected components) is disabled in the reference (circuit_analyzer.py:245-250)")
         self.mean, self.std = [0.485, 0.456, 0.406], [0.229, 0.224, 0.225]
 
     # Every method below behaves like a torch op: kernels are enqueued on the caller's CURRENT stream and nothing synchronises the device
@@ -314,13 +339,41 @@ class SAM2Transforms:
                                                  torch.cuda.current_stream().cuda_stream), "sam2_transform_rects")
         return res.permute(0, 3, 1, 2) if out is None else res
 
+    @property
+    def fills_small_regions(self):
+        return self.max_hole_area > 0 or self.max_sprinkle_area > 0
+
+    def fill_small_regions(self, masks):
+        """sam2_infer.py:100-124 on f32 [B,C,h,w] device logits, out of place: background components (8-connected, `<= mask_threshold`) of at
+        most max_hole_area pixels become mask_threshold + 10, foreground components of at most max_sprinkle_area pixels mask_threshold - 10,
+        both judged on the input.  Four launches on the current stream (cvmi_mask_fill_small); with both areas <= 0 the argument itself
+        comes back and nothing is launched.  A failing launch raises (the reference swallows it and returns the unfiltered masks)."""
+        if not self.fills_small_regions:
+            return masks
+        require_gpu()
+        lib = _lib.load()
+        if not (torch.is_tensor(masks) and masks.is_cuda and masks.dtype == torch.float32 and masks.dim() >= 2):
+            raise TypeError("fill_small_regions expects an f32 [B,C,h,w] device tensor")
+        m = masks.contiguous()
+        h, w = m.shape[-2:]
+        N = m.numel() // max(1, h * w)
+        ws_bytes = int(lib.cvmi_mask_cc_workspace(N, h, w))
+        if ws_bytes == 0:
+            raise ValueError(f"fill_small_regions: {N} planes of {h} x {w}: sizes must be positive and the pixel count below 2^31")
+        with torch.cuda.device(m.device):
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=m.device)        # torch's stream-ordered allocator owns it
+            y = torch.empty_like(m)
+            _lib.check(lib.cvmi_mask_fill_small(m.data_ptr(), N, h, w, float(self.mask_threshold), float(self.max_hole_area), float(self.max_sprinkle_area),
+                                                y.data_ptr(), ws.data_ptr(), torch.cuda.current_stream().cuda_stream), "mask_fill_small")
+        return y
+
     def postprocess_to_masks_sized(self, masks, sizes):
         """postprocess_to_mask_async for planes that return to DIFFERENT sizes (every image its own crop window): masks f32 [N,1,h,w] on the
         device, sizes = [(H, W)] per plane -> ([u8 [H_n, W_n] views of ONE packed buffer], extent int32 [N,4]); one launch, nothing copied to
         the host."""
         require_gpu()
         lib = _lib.load()
-        m = masks.float().contiguous()
+        m = self.fill_small_regions(masks.float().contiguous())
         N, h, w = m.shape[0] * m.shape[1], m.shape[-2], m.shape[-1]
         if len(sizes) != N:
             raise ValueError("one (H, W) per mask plane")
@@ -372,6 +425,7 @@ class SAM2Transforms:
         m = masks.float().contiguous()
         if not m.is_cuda:
             m = m.cuda()
+        m = self.fill_small_regions(m)
         B, C, h, w = m.shape
         H, W = int(orig_hw[0]), int(orig_hw[1])
         out = torch.empty(B, C, H, W, dtype=torch.float32, device=m.device)
@@ -388,6 +442,7 @@ class SAM2Transforms:
         m = masks.float().contiguous()
         if not m.is_cuda:
             m = m.cuda()
+        m = self.fill_small_regions(m)
         B, C, h, w = m.shape
         H, W = int(orig_hw[0]), int(orig_hw[1])
         u8 = torch.empty(B, C, H, W, dtype=torch.uint8, device=m.device)

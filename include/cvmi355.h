@@ -392,6 +392,22 @@ int cvmi_mask_postprocess_sizes(const float* x, int N, int h, int w, const int* 
 int cvmi_mask_postprocess_rects_dev(const float* x, int N, int h, int w, const int* rects_dev, long long plane_stride, float thresh,
                                     uint8_t* mask_u8, int* extent, cvmi_stream_t stream);
 
+/* Hole and sprinkle removal of postprocess_masks (sam2_infer.py:88-128) and the labelling under it, on f32 planes x [N,h,w] with a
+ * threshold t.  Foreground is x > t, background x <= t; components are 8-connected in BOTH phases and never cross a plane; h and w need
+ * not be even.  The label of a pixel is 1 + (y * w + x) of the raster-first pixel of its component, its area the component's pixel count.
+ * workspace: DEVICE, at least cvmi_mask_cc_workspace(N, h, w) bytes (0: the sizes are not positive or N * h * w >= 2^31, which the two
+ * calls refuse before they launch anything).  CVMI_MASK_CC_TILE: the edge of the tiles that are labelled in LDS.
+ *   cvmi_mask_components: labels / areas i32 [N,h,w], for the pixels of both phases.
+ *   cvmi_mask_fill_small: y [N,h,w] (must not overlap x) = t + 10 where x is background, max_hole_area > 0 and area <= max_hole_area;
+ *   t - 10 where x is foreground, max_sprinkle_area > 0 and area <= max_sprinkle_area; x elsewhere.  Both tests are made on x, the two
+ *   constants are f32 sums, and the limits are floats compared with <= (2.5 fills areas 1 and 2). */
+#define CVMI_MASK_CC_TILE 64
+size_t cvmi_mask_cc_workspace(int N, int h, int w);
+int cvmi_mask_components(const float* x, int N, int h, int w, float thresh, int* labels, int* areas, void* workspace,
+                         cvmi_stream_t stream);
+int cvmi_mask_fill_small(const float* x, int N, int h, int w, float thresh, float max_hole_area, float max_sprinkle_area, float* y,
+                         void* workspace, cvmi_stream_t stream);
+
 /* Extent of N binary u8 planes [N,H,W]: extent[n] = {min x, min y, max x, max y} over the non-zero pixels, or
  * {W, H, -1, -1} for an empty plane.  Replaces cv2.findContours(RETR_EXTERNAL) + cv2.boundingRect on the SAM 2 mask
  * (circuit_analyzer.py:364-370): sam_extent_bbox = (min x, min y, max x + 1, max y + 1). */
