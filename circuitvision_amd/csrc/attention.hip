@@ -116,6 +116,73 @@ __device__ __forceinline__ long long tok_off_fast(const AttnArgs& p, int b, int 
   return pix * st;
 }
 
+// ---- pieces shared by the MFMA kernels (attn_f16 / attn64 and the head_dim 72 ones), each defined once ------------------------------
+// Macros where a __forceinline__ function -- AttnArgs by reference, by value or field by field -- made hipcc commute the operands of the
+// 64-bit address products or hoist the argument loads (same instructions, other registers / order); they read the kernel's variables
+// named in their comments.
+
+// Q fragments (B operand of S^T = K Q^T): declares QF[NS]; lane (q = lr, half lh) holds Q[q][16 s + 8 lh .. + 7], zero past p.dqk and
+// for rows that are not q_ok.  QOFF0 = element offset of this lane's query token (pooled: of the top-left token of its 2 x 2 block),
+// computed once by the kernel with its own arithmetic (tok_off or tok_off_fast).  p.q_pool: q = 2 x 2 max-pool of the window's projected
+// q tokens.  (attn_f16_kernel keeps its own loader: it calls tok_off per pooled token instead of stepping from one offset.)
+// Reads p, q_ok, lh; declares QF; its own loop variables are s, e, dy, dx.
+#define LOAD_Q_FRAGS(QF, NS, QOFF0)                                                                                                    \
+  u32x4 QF[NS];                                                                                                                        \
+  _Pragma("unroll") for (int s = 0; s < NS; ++s) {                                                                                     \
+    const int d0 = 16 * s + 8 * lh;                                                                                                    \
+    u32x4 v = {0u, 0u, 0u, 0u};                                                                                                        \
+    if (q_ok && d0 < p.dqk) {                                                                                                          \
+      if (!p.q_pool) {                                                                                                                 \
+        v = *reinterpret_cast<const u32x4*>(p.q + ((QOFF0) + d0) * 2);                                                                 \
+      } else {                                                                                                                         \
+        f16x8 m;                                                                                                                       \
+        _Pragma("unroll") for (int e = 0; e < 8; ++e) m[e] = (f16)(CVMI_LOWEST16);                                                     \
+        _Pragma("unroll") for (int dy = 0; dy < 2; ++dy)                                                                               \
+          _Pragma("unroll") for (int dx = 0; dx < 2; ++dx) {       /* pooled: the 2 x 2 block's tokens are grid neighbours */          \
+            const long long off = (QOFF0) + ((long long)dy * p.grid_w + dx) * p.q_st + d0;                                             \
+            const f16x8 x = __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>(p.q + off * 2));                                 \
+            _Pragma("unroll") for (int e = 0; e < 8; ++e) m[e] = x[e] > m[e] ? x[e] : m[e];                                            \
+          }                                                                                                                            \
+        v = __builtin_bit_cast(u32x4, m);                                                                                              \
+      }                                                                                                                                \
+    }                                                                                                                                  \
+    QF[s] = v;                                                                                                                         \
+  }
+
+// Row maximum of a 64-key score tile over this lane's 32 values: two chains of v_max3_f32 (see max3f).
+__device__ __forceinline__ float tile_max(const f32x16 (&sacc)[2]) {
+  float mxa = max3f(sacc[0][0], sacc[1][0], sacc[0][8]), mxb = max3f(sacc[1][8], sacc[0][1], sacc[1][1]);
+#pragma unroll
+  for (int r = 2; r < 8; ++r) { mxa = max3f(mxa, sacc[0][r], sacc[1][r]); mxb = max3f(mxb, sacc[0][r + 7], sacc[1][r + 7]); }
+  return max3f(mxa, mxb, max3f(sacc[0][15], sacc[1][15], mxa));
+}
+
+// Normalise by l_run and store O[q][d] of query qi of (b, h), for a live query (the kernel tests q_ok): the lane holds runs of 4
+// consecutive d of oacc[NT].  FAST: the window arithmetic of the output offset by the host's multipliers (tok_off_fast: attn_res256 /
+// attn_res64); otherwise tok_off's divisions (attn_f16, attn64, and attn_dma72, which never sees a window).
+// Reads p, b, h, qi, lh, l_run, oacc; writes global memory only.
+#define NORMALISE_STORE(NT, FAST)                                                                                                      \
+  {                                                                                                                                    \
+    const float inv = 1.f / l_run;                                                                                                     \
+    long long obase;                                                                                                                   \
+    if (p.win > 0) {                                                                                                                   \
+      const int ow = p.q_pool ? p.win / 2 : p.win, ogh = p.q_pool ? p.grid_h / 2 : p.grid_h, ogw = p.q_pool ? p.grid_w / 2 : p.grid_w; \
+      if constexpr (FAST) obase = tok_off_fast(p, b, qi, p.o_st, ow, ogh, ogw, p.div_ow);                                              \
+      else obase = tok_off(b, qi, p.o_sb, p.o_st, ow, ogh, ogw);                                                                       \
+    } else {                                                                                                                           \
+      obase = (long long)b * p.o_sb + (long long)qi * p.o_st;                                                                          \
+    }                                                                                                                                  \
+    obase += (long long)h * p.o_sh;                                                                                                    \
+    _Pragma("unroll") for (int t = 0; t < NT; ++t)                                                                                     \
+      _Pragma("unroll") for (int g = 0; g < 4; ++g) {                                                                                  \
+        const int d0 = t * 32 + 8 * g + 4 * lh;                                                                                        \
+        if (d0 < p.dv) {                                                                                                               \
+          f16x4 ov;                                                                                                                    \
+          _Pragma("unroll") for (int e = 0; e < 4; ++e) ov[e] = (f16)(oacc[t][4 * g + e] * inv);                                       \
+          *reinterpret_cast<f16x4*>(p.o + (obase + d0) * 2) = ov;                                                                      \
+        }                                                                                                                              \
+      }                                                                                                                                \
+  }
 // GS: threads of a loader group.  One group per wave (GS = 64) is the only form left; the shared 256-thread loader went to attn64_kernel.
 template <int DQKP, int DVP, int GS>
 __global__ __launch_bounds__(256) void attn_f16_kernel(const AttnArgs p) {
@@ -157,6 +224,7 @@ __global__ __launch_bounds__(256) void attn_f16_kernel(const AttnArgs p) {
           const long long off = tok_off(b / p.q_bdiv, qi, p.q_sb, p.q_st, p.win, p.grid_h, p.grid_w) + (long long)h * p.q_sh + d0;
           v = *reinterpret_cast<const u32x4*>(p.q + off * 2);
         } else {                               // q = 2x2 max-pool of the window's projected q tokens
+          // (not LOAD_Q_FRAGS: this kernel calls tok_off per pooled token instead of stepping from one hoisted offset)
           const int py = qi / qwin, px = qi - py * qwin;
           f16x8 m;
 #pragma unroll
@@ -316,29 +384,7 @@ __global__ __launch_bounds__(256) void attn_f16_kernel(const AttnArgs p) {
   }
 
   // ---- normalise and store O[q][d] (lane holds runs of 4 consecutive d) ---------------------------
-  if (q_ok) {
-    const float inv = 1.f / l_run;
-    long long obase;
-    if (p.win > 0) {
-      const int ow = p.q_pool ? p.win / 2 : p.win, ogh = p.q_pool ? p.grid_h / 2 : p.grid_h, ogw = p.q_pool ? p.grid_w / 2 : p.grid_w;
-      obase = tok_off(b, qi, p.o_sb, p.o_st, ow, ogh, ogw);
-    } else {
-      obase = (long long)b * p.o_sb + (long long)qi * p.o_st;
-    }
-    obase += (long long)h * p.o_sh;
-#pragma unroll
-    for (int t = 0; t < DT; ++t)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int d0 = t * 32 + 8 * g + 4 * lh;
-        if (d0 < p.dv) {
-          f16x4 ov;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) ov[e] = (f16)(oacc[t][4 * g + e] * inv);
-          *reinterpret_cast<f16x4*>(p.o + (obase + d0) * 2) = ov;
-        }
-      }
-  }
+  if (q_ok) NORMALISE_STORE(DT, false)
 }
 
 // ---- long-sequence variant: 64-key tiles, V kept row-major and transposed by the LDS read --------------------------
@@ -388,32 +434,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn64_kernel(const 
     if (p.q_pool) { const int py = qc / qwin, px = qc - py * qwin; t = (2 * py) * p.win + 2 * px; }
     qoff0 = tok_off(b / p.q_bdiv, t, p.q_sb, p.q_st, p.win, p.grid_h, p.grid_w) + (long long)h * p.q_sh;
   }
-  u32x4 qf[QS];
-#pragma unroll
-  for (int s = 0; s < QS; ++s) {
-    const int d0 = 16 * s + 8 * lh;
-    u32x4 v = {0u, 0u, 0u, 0u};
-    if (q_ok && d0 < p.dqk) {
-      if (!p.q_pool) {
-        v = *reinterpret_cast<const u32x4*>(p.q + (qoff0 + d0) * 2);
-      } else {
-        f16x8 m;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) m[e] = (f16)(CVMI_LOWEST16);
-#pragma unroll
-        for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-          for (int dx = 0; dx < 2; ++dx) {
-            const long long off = qoff0 + ((long long)dy * p.grid_w + dx) * p.q_st + d0;   // pooled: the 2 x 2 block's tokens are grid neighbours
-            const f16x8 x = __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>(p.q + off * 2));
-#pragma unroll
-            for (int e = 0; e < 8; ++e) m[e] = x[e] > m[e] ? x[e] : m[e];
-          }
-        v = __builtin_bit_cast(u32x4, m);
-      }
-    }
-    qf[s] = v;
-  }
+  LOAD_Q_FRAGS(qf, QS, qoff0)
 
   f32x16 oacc[DT];
 #pragma unroll
@@ -527,10 +548,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn64_kernel(const 
           if (key >= p.Nk) sacc[u][r] = -INFINITY;
         }
     }
-    float mxa = max3f(sacc[0][0], sacc[1][0], sacc[0][8]), mxb = max3f(sacc[1][8], sacc[0][1], sacc[1][1]);      // two chains of v_max3_f32
-#pragma unroll
-    for (int r = 2; r < 8; ++r) { mxa = max3f(mxa, sacc[0][r], sacc[1][r]); mxb = max3f(mxb, sacc[0][r + 7], sacc[1][r + 7]); }
-    const float mx = max3f(mxa, mxb, max3f(sacc[0][15], sacc[1][15], mxa));
+    const float mx = tile_max(sacc);
     const float m_new = max3f(m_run, mx, __shfl_xor(mx, 32));
     const float mc = m_new * c;
     const float alpha = __builtin_amdgcn_exp2f(fmaf(m_run, c, -mc));
@@ -566,29 +584,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn64_kernel(const 
     __syncthreads();
   }
 
-  if (q_ok) {
-    const float inv = 1.f / l_run;
-    long long obase;
-    if (p.win > 0) {
-      const int ow = p.q_pool ? p.win / 2 : p.win, ogh = p.q_pool ? p.grid_h / 2 : p.grid_h, ogw = p.q_pool ? p.grid_w / 2 : p.grid_w;
-      obase = tok_off(b, qi, p.o_sb, p.o_st, ow, ogh, ogw);
-    } else {
-      obase = (long long)b * p.o_sb + (long long)qi * p.o_st;
-    }
-    obase += (long long)h * p.o_sh;
-#pragma unroll
-    for (int t = 0; t < DT; ++t)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int d0 = t * 32 + 8 * g + 4 * lh;
-        if (d0 < p.dv) {
-          f16x4 ov;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) ov[e] = (f16)(oacc[t][4 * g + e] * inv);
-          *reinterpret_cast<f16x4*>(p.o + (obase + d0) * 2) = ov;
-        }
-      }
-  }
+  if (q_ok) NORMALISE_STORE(DT, false)
 }
 
 template <int DQKP, int DVP, int NW>
@@ -623,6 +619,213 @@ __device__ __forceinline__ int key_perm72(int i) {            // i = 4 a + b  ->
   return 16 * (a >> 2) + 4 * (i & 3) + (a & 3);
 }
 
+// ---- pieces of the head_dim 72 kernels (attn_res256 / attn_res64 / attn_dma72), each defined once -------------------------------------
+// tile_max, softmax_tiles and mfma_consts_init are functions.  The other pieces are file-scope macros: as __forceinline__ functions --
+// arrays by reference, the address forms as lambdas -- each of them made hipcc commute operands, reassociate an address sum or assign
+// other registers in at least one of the ten instances, and these kernels sit at their register limit.  Every macro's comment ends with
+// "Reads / writes": ALL the kernel variables it names, so that a rename in a kernel is checked against this list.
+constexpr int ROW72 = 144, QS72 = 5, DT72 = 3, CH72 = 9;    // LDS row bytes, k16 steps of QK^T, 32-row tiles of O^T, 16-byte chunks per row
+
+// Resident kernels: every wave DMAs its share of the K and V rows of item (b, h) to Ks / Vs (global_load_lds, 16 B per lane, per-lane
+// source = the key's token row).  Chunk L -> (key row L / 9, 16-byte chunk L % 9); NINS wave-instructions per matrix (36: 256 keys,
+// 9: 64 keys), dealt round-robin over the item's NW waves (this one: wv).  Nothing waits here: see dma_wait().
+// Reads p, b, h, wv, lane, Ks, Vs; writes LDS only.
+#define WINDOW_KV_DMA(NINS, NW)                                                                                                        \
+  {                                                                                                                                    \
+    long long korg, vorg;                                                                                                              \
+    if (p.win > 0) {                                                                                                                   \
+      const long long pix0 = tok_off_fast(p, b, 0, 1, p.win, p.grid_h, p.grid_w, p.div_win);                                           \
+      korg = pix0 * p.k_st; vorg = pix0 * p.v_st;                                                                                      \
+    } else {                                                                                                                           \
+      korg = (long long)b * p.k_sb; vorg = (long long)b * p.v_sb;                                                                      \
+    }                                                                                                                                  \
+    const char* kbase = p.k + (korg + (long long)h * p.k_sh) * 2;                                                                      \
+    const char* vbase = p.v + (vorg + (long long)h * p.v_sh) * 2;                                                                      \
+    _Pragma("unroll") for (int j = 0; j < (NINS + NW - 1) / NW; ++j) {                                                                 \
+      if (j * NW + wv >= NINS) break;           /* (wave-uniform) */                                                                   \
+      const int L = (j * NW + wv) * 64 + lane;                                                                                         \
+      const int row = L / CH72, ch = L - row * CH72;                                                                                   \
+      int pix = row;                                                                                                                   \
+      if (p.win > 0) { const int ty = (int)p.div_win.div((unsigned)row); pix = ty * p.grid_w + (row - ty * p.win); }                   \
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(kbase + ((long long)pix * p.k_st + ch * 8) * 2),\
+                                       (__attribute__((address_space(3))) void*)(Ks + (j * NW + wv) * 1024), 16, 0, 0);                \
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(vbase + ((long long)pix * p.v_st + ch * 8) * 2),\
+                                       (__attribute__((address_space(3))) void*)(Vs + (j * NW + wv) * 1024), 16, 0, 0);                \
+    }                                                                                                                                  \
+  }
+
+// Row sums and (QL) the running maximum on the matrix pipe: the constants that PV16_STEP and the QL form of SCORE_TILE72 read instead
+// of data, at smem + ONES (behind the kernel's K / V images and their over-read slack).
+// Row sums (16-bit form): the third 32-row tile of O^T = V^T P^T has rows d = 72..95 to spare, and the lanes whose transposing reads would
+// fetch V[key][72..75] (past the row: the next key's first elements, rows never stored) read a constant (1, 0, 0, 0) instead -- row d = 72
+// of the accumulator is then the sum over keys of the ROUNDED probabilities, rescaled with the rest of the tile when the running maximum
+// moves.  That takes 32 v_add_f32 per tile and wave off the vector issue port, which -- not the matrix pipe -- bounds the tile loop (ISA
+// counts in DESIGN.md).  The constants sit at the eight offsets (32 u + 16 s) * ROW72 + {0, 2 ROW72} the reads of one tile use, in TWO
+// copies, one per 32-lane half (= LDS lane group of a transposing read): the 28 ordinary lanes of a group and the V rows they read cover
+// 56 of the 64 banks exactly once, and the 8 banks left over are the ones the redirected lanes WOULD have used -- banks 36 / 52 / 4 / 20
+// (+ 1) in the half lh = 0 (copy at ONES + 144), banks 8 / 24 / 40 / 56 in lh = 1 (copy at ONES + 32; tile bases are multiples of 256
+// bytes).  A constant anywhere else costs every t = 2 read a conflict cycle (PMC r03: 0.15 of the LDS cycles with one copy at bank 0).
+// QL: the K constants (1, 0, .., 0) at ONES + 16, (32 u) * ROW72 apart: see QL_UPDATE72.
+template <int ONES, bool QL>
+__device__ __forceinline__ void mfma_consts_init(char* smem, int tid) {
+  if (tid < 16) {
+    const int t8 = tid & 7, off = ((t8 >> 2) * 32 + ((t8 >> 1) & 1) * 16 + (t8 & 1) * 2) * ROW72;
+    *reinterpret_cast<u32x2*>(smem + ONES + (tid < 8 ? 144 : 32) + off) = (u32x2){CVMI_ONE16X2 & 0xFFFFu, 0u};
+  } else if (QL && tid < 18) {
+    *reinterpret_cast<u32x4*>(smem + ONES + 16 + (tid - 16) * 32 * ROW72) = (u32x4){CVMI_ONE16X2 & 0xFFFFu, 0u, 0u, 0u};
+  }
+}
+
+// One 1-KiB piece of the e4m3 V^T operand image, assigned to DST: this lane's 16 bytes are V[key(jj)][d] for jj = 0..15 in the k order of
+// the P operand (the two k-steps of the 16-bit path), gathered by the same transposing reads PV16_STEP feeds its MFMAs with, from the 32
+// key rows ROW0 .. of the 16-bit image (vt = the lane's transposing-read base in it) and d tile T.  f32 clamp to +-448: the conversion
+// returns NaN, not the maximum, on overflow.
+// Reads vt; writes DST.
+#define V_IMAGE_PIECE(DST, ROW0, T)                                                                                                    \
+  {                                                                                                                                    \
+    unsigned w[4];                                                                                                                     \
+    _Pragma("unroll") for (int sgrp = 0; sgrp < 2; ++sgrp) {                                                                           \
+      const char* a0 = vt + ((ROW0) + sgrp * 16) * ROW72 + (T) * 64;                                                                   \
+      const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a0));                        \
+      const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a0 + 2 * ROW72));            \
+      const f16x4 l4 = __builtin_bit_cast(f16x4, lo), h4 = __builtin_bit_cast(f16x4, hi);                                              \
+      float f[8];                                                                                                                      \
+      _Pragma("unroll") for (int e = 0; e < 4; ++e) { f[e] = (float)l4[e]; f[4 + e] = (float)h4[e]; }                                  \
+      _Pragma("unroll") for (int e = 0; e < 8; ++e) f[e] = __builtin_amdgcn_fmed3f(f[e], -448.f, 448.f);                               \
+      w[2 * sgrp] = pack4_e4m3(f[0], f[1], f[2], f[3]);                                                                                \
+      w[2 * sgrp + 1] = pack4_e4m3(f[4], f[5], f[6], f[7]);                                                                            \
+    }                                                                                                                                  \
+    DST = (u32x4){w[0], w[1], w[2], w[3]};                                                                                             \
+  }
+
+// S^T tile of 64 keys x 32 queries: declares SACC[2] and runs the 5 k16 steps x 2 key halves against qf[].  KA = an expression in (s, u)
+// for the address of the lane's K fragment of step s, half u (row key_perm72(lr) of the half, bytes 32 s + 16 lh ..): each kernel states
+// its own form, which is also where the QL redirect of the fifth step to the K constants goes (QL_UPDATE72).  Row reads that run past
+// column 72 in the fifth step fetch the next row's finite data against zero Q columns.  The lane's maximum over the tile: tile_max().
+// Reads qf (and whatever KA names); declares SACC; KA is written in the macro's loop variables s (k16 step) and u (key half).
+#define SCORE_TILE72(SACC, KA)                                                                                                         \
+  f32x16 SACC[2];                                                                                                                      \
+  _Pragma("unroll") for (int u = 0; u < 2; ++u)                                                                                        \
+    _Pragma("unroll") for (int r = 0; r < 16; ++r) SACC[u][r] = 0.f;                                                                   \
+  _Pragma("unroll") for (int s = 0; s < QS72; ++s)                                                                                     \
+    _Pragma("unroll") for (int u = 0; u < 2; ++u) {                                                                                    \
+      const f16x8 kf = __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>(KA));                                                 \
+      SACC[u] = CVMI_MFMA_32X32X16(kf, __builtin_bit_cast(f16x8, qf[s]), SACC[u], 0, 0, 0);                                            \
+    }
+
+// Online softmax of one score tile (sacc, this lane's maximum mx, c = scale * log2 e) with deferred rescaling (DEFER_LOG2): updates m_run,
+// l_run and oacc and leaves P in pf or p8.  MODE says where the row sum comes from and what P becomes:
+enum { P16_SUM_MFMA,   // 16-bit pf; row sums from the matrix pipe (mfma_consts_init): l_run is not touched here
+       P16_SUM_VALU,   // 16-bit pf; row sums added on the VALU (attn_res64_kernel: a single tile, nothing to amortise the constants over)
+       P8_SUM_VALU };  // p8 = this lane's 32 e4m3 bytes of P^T (tile u -> bytes 16 u .. 16 u + 15) as e4m3 of p * 2^8 (p <= 1: the row maximum
+                       // is exactly 256, no overflow; the block scale 2^-8 is PV8_STEP's scale operand); row sums stay fp32 sums of the
+                       // unquantised p; threshold 0 instead of DEFER_LOG2: this P is scaled by 2^8 already
+// Reads sacc, mx, c; updates m_run, l_run, oacc; writes pf or p8 (BOTH must be declared: the discarded branch still names the other).
+#define SOFTMAX_UPDATE72(MODE)                                                                                                         \
+  {                                                                                                                                    \
+    const float m_top = fmaxf(m_run, xhalf_max(mx));                                                                                   \
+    const bool grow = (m_top - m_run) * c > (MODE == P8_SUM_VALU ? 0.f : DEFER_LOG2);      /* first tile: m_run = -inf -> true */      \
+    const float m_new = grow ? m_top : m_run;                                                                                          \
+    const float mc = m_new * c;                                                                                                        \
+    const float alpha = grow ? __builtin_amdgcn_exp2f(fmaf(m_run, c, -mc)) : 1.0f;                                                     \
+    float psum = 0.f;                                                                                                                  \
+    if constexpr (MODE == P8_SUM_VALU) {                                                                                               \
+      const float mc8 = mc - 8.f;                           /* p * 2^8 through the exponent */                                         \
+      _Pragma("unroll") for (int u = 0; u < 2; ++u) {                                                                                  \
+        unsigned w[4];                                                                                                                 \
+        _Pragma("unroll") for (int r = 0; r < 16; r += 4) {                                                                            \
+          float e[4];                                                                                                                  \
+          _Pragma("unroll") for (int i = 0; i < 4; ++i) { e[i] = __builtin_amdgcn_exp2f(fmaf(sacc[u][r + i], c, -mc8)); psum += e[i]; }\
+          w[r >> 2] = pack4_e4m3(e[0], e[1], e[2], e[3]);                                                                              \
+        }                                                                                                                              \
+        p8[u] = (u32x4){w[0], w[1], w[2], w[3]};                                                                                       \
+      }                                                                                                                                \
+      psum *= 0.00390625f;                                  /* back to the scale of l_run (exact: a power of two) */                   \
+    } else {                                                                                                                           \
+      psum = softmax_tiles<MODE == P16_SUM_VALU>(sacc, c, mc, pf);                                                                     \
+    }                                                                                                                                  \
+    if constexpr (MODE != P16_SUM_MFMA) {                                                                                              \
+      psum = xhalf_sum(psum);                                                                                                          \
+      l_run = l_run * alpha + psum;                                                                                                    \
+    }                                                                                                                                  \
+    m_run = m_new;                                                                                                                     \
+    if (__any(grow)) {                                      /* (a real branch: rare once the first tiles have set the reference) */    \
+      asm volatile("" ::: "memory");                                                                                                   \
+      _Pragma("unroll") for (int t = 0; t < DT72; ++t)                                                                                 \
+        _Pragma("unroll") for (int r = 0; r < 16; ++r) oacc[t][r] *= alpha;                                                            \
+    }                                                                                                                                  \
+  }
+
+// QL (q pre-multiplied by scale * log2 e where it was produced, cvmi_attn_desc.q_log2): the running maximum goes through the matrix pipe
+// too.  head_dim 72 leaves k = 72..79 of the fifth QK^T step unused: the lanes that hold those k (lh = 1) read K = (1, 0, .., 0) from a
+// constant (mfma_consts_init) instead of the next key's first bytes, and hold Q = (-m, 0, .., 0), m = the row's reference maximum ROUNDED
+// to the operand type -- the score tile comes out of the MFMA as s - m and exp2 applies to it as it stands: no v_fma_f32 per score either.
+// m moves only when a tile's maximum exceeds it by more than the deferred-rescale threshold (and on the first tile): then the tile is
+// corrected by the exact difference of the two rounded references, which is also what the accumulators are rescaled by.
+// FIRST: the first tile.  RESCALE: attn_res256_kernel passes kc > 0 (the
+// accumulators are still zero in its first tile: no exp2, no 48 multiplies); attn_dma72_kernel passes true (it always rescales).
+// Reads mx, lh; updates sacc, m_ref, qf[4], oacc; writes pf.
+#define QL_UPDATE72(FIRST, RESCALE)                                                                                                    \
+  {                                                                                                                                    \
+    const float top = xhalf_max(mx);                          /* the tile's maximum RELATIVE to m_ref (the MFMA subtracted it) */      \
+    const bool grow = (FIRST) || top > DEFER_LOG2;                                                                                     \
+    if (__any(grow)) {                                      /* (a real branch: the first tile, then rare) */                           \
+      const float m_new = grow ? (float)(f16)(m_ref + top) : m_ref;       /* representable in the operand type, so the Q slot holds it exactly */\
+      const float dlt = m_new - m_ref;                        /* exact in f32 (both are 16-bit values of similar magnitude or m_ref = 0) */\
+      m_ref = m_new;                                                                                                                   \
+      _Pragma("unroll") for (int u = 0; u < 2; ++u)                                                                                    \
+        _Pragma("unroll") for (int r = 0; r < 16; ++r) sacc[u][r] -= dlt;                                                              \
+      if (RESCALE) {                                          /* (uniform) */                                                          \
+        const float alpha = __builtin_amdgcn_exp2f(-dlt);                                                                              \
+        _Pragma("unroll") for (int t = 0; t < DT72; ++t)                                                                               \
+          _Pragma("unroll") for (int r = 0; r < 16; ++r) oacc[t][r] *= alpha;                                                          \
+      }                                                                                                                                \
+      if (lh) {                                               /* the lanes that hold k = 72..79 of the fifth step */                   \
+        f16x8 qv = __builtin_bit_cast(f16x8, qf[4]);                                                                                   \
+        qv[0] = (f16)(-m_new);                                                                                                         \
+        qf[4] = __builtin_bit_cast(u32x4, qv);                                                                                         \
+      }                                                                                                                                \
+    }                                                                                                                                  \
+    _Pragma("unroll") for (int u = 0; u < 2; ++u)                                                                                      \
+      _Pragma("unroll") for (int r = 0; r < 16; ++r) pf[u][r >> 3][r & 7] = (f16)__builtin_amdgcn_exp2f(sacc[u][r]);                   \
+  }
+
+// O^T += V^T P^T over one 64-key tile, 16-bit form (pf, oacc): 12 MFMAs, the V^T operand gathered by two transposing reads whose four key
+// rows are 4 apart, the second 2 rows below the first (key_perm72).  VA = an expression in (u, s, t) for the lane's address for (32-key
+// half u, k16 step s, d tile t): each kernel states its own form, which is also where the lanes of d = 72..75 (t = 2) are redirected to the
+// row-sum constants (mfma_consts_init).  Reads of t = 2 past column 72 otherwise fetch the next row's finite data into output rows that
+// are never stored.
+// Reads pf (and whatever VA names); updates oacc; VA is written in the macro's loop variables u, s, t.
+#define PV16_STEP(VA)                                                                                                                  \
+  _Pragma("unroll") for (int u = 0; u < 2; ++u)                                                                                        \
+    _Pragma("unroll") for (int s = 0; s < 2; ++s)                                                                                      \
+      _Pragma("unroll") for (int t = 0; t < DT72; ++t) {                                                                               \
+        const char* a0 = VA;                                                                                                           \
+        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a0));                      \
+        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a0 + 2 * ROW72));          \
+        const u32x2 l2 = __builtin_bit_cast(u32x2, lo), h2 = __builtin_bit_cast(u32x2, hi);                                            \
+        const u32x4 vv = {l2[0], l2[1], h2[0], h2[1]};                                                                                 \
+        oacc[t] = CVMI_MFMA_32X32X16(__builtin_bit_cast(f16x8, vv), pf[u][s], oacc[t], 0, 0, 0);                                       \
+      }
+
+// O^T += V^T P^T over one 64-key tile on the block-scaled v_mfma_scale_f32_32x32x64_f8f6f4 (2 x the bf16 rate per clock): one instruction
+// per 32-wide d tile instead of four (p8, oacc).  VA0 = the lane's 16 bytes in the first of the tile's six 1-KiB e4m3 V^T pieces (V_IMAGE_PIECE; piece
+// 2 t + u, lane-linear: conflict-free ds_read_b128 of whole operands); p8 from SOFTMAX_UPDATE72(P8_SUM_VALU).  Operand maps measured on gfx950
+// (tools/probe/fp8_probe.hip, fp8_scale_probe.hip): lane (r = l & 31, h = l >> 5) holds A[row r] / B[col r] bytes j = 0..31 which pair with
+// the SAME (h, j) of the other operand; scale byte 0 of lane (r, h) scales that row's bytes 16 h .. 16 h + 15 of both lane halves; C / D as
+// every 32 x 32 MFMA.
+// Reads p8 (and whatever VA0 names); updates oacc.
+#define PV8_STEP(VA0)                                                                                                                  \
+  {                                                                                                                                    \
+    const v8i32 pb = {(int)p8[0][0], (int)p8[0][1], (int)p8[0][2], (int)p8[0][3], (int)p8[1][0], (int)p8[1][1], (int)p8[1][2], (int)p8[1][3]};\
+    _Pragma("unroll") for (int t = 0; t < DT72; ++t) {                                                                                 \
+      const char* va = (VA0) + (2 * t) * 1024;                                                                                         \
+      const u32x4 a_lo = *reinterpret_cast<const u32x4*>(va), a_hi = *reinterpret_cast<const u32x4*>(va + 1024);                       \
+      const v8i32 av = {(int)a_lo[0], (int)a_lo[1], (int)a_lo[2], (int)a_lo[3], (int)a_hi[0], (int)a_hi[1], (int)a_hi[2], (int)a_hi[3]};\
+      oacc[t] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(av, pb, oacc[t], 0, 0, 0, 127, 0, 119);      /* e4m3 x e4m3, scales 2^0 / 2^-8 */\
+    }                                                                                                                                  \
+  }
+
 // ---- 256-key windows of head_dim 72 (Hiera stage 3, 16 x 16): K and V of the whole window resident in LDS --------------
 // A (window, head) has only four 64-key tiles; with tile-by-tile staging the Q / first-tile latency, eight barriers and the
 // staging bookkeeping cost more than the 88 MFMAs.  Here every wave DMAs its share of the window's K and V rows
@@ -632,21 +835,18 @@ __device__ __forceinline__ int key_perm72(int i) {            // i = 4 a + b  ->
 // next row's finite data against zero Q columns / unstored output rows.  4 waves = 128 queries per workgroup; 72 KiB of
 // LDS, two workgroups per CU.
 // AV8 = true (cvmi_attn_desc.av_fp8, BASELINE configs[4] "fp8 MFMA attention"): the O^T += V^T P^T contraction -- whose K axis is the KEY axis,
-// a whole multiple of 64 here -- runs on the block-scaled v_mfma_scale_f32_32x32x64_f8f6f4 (2 x the bf16 rate per clock): one instruction
-// per (64-key tile, 32-wide d tile) instead of four.  V is quantised ONCE per workgroup: after the window has landed, every thread builds
-// three 16-byte pieces of the e4m3 V^T operand image from the fp16 rows (the same transposing reads the 16-bit path feeds its MFMAs with,
-// f32 clamp to +-448 because the conversion returns NaN, not the maximum, on overflow), a barrier, and the pieces overwrite the 16-bit V
-// image in place, lane-linear (conflict-free ds_read_b128 of whole operands).  P is quantised from the fp32 softmax as e4m3 of p * 2^8
-// (p <= 1: the row maximum is exactly 256, no overflow) with the block scale 2^-8 in the MFMA's scale operand; row sums stay fp32 sums of
-// the unquantised p.  Operand maps measured on gfx950 (tools/probe/fp8_probe.hip, fp8_scale_probe.hip): lane (r = l & 31, h = l >> 5) holds
-// A[row r] / B[col r] bytes j = 0..31 which pair with the SAME (h, j) of the other operand; scale byte 0 of lane (r, h) scales that row's
-// bytes 16 h .. 16 h + 15 of both lane halves; C / D as every 32 x 32 MFMA.
+// a whole multiple of 64 here -- runs on the block-scaled fp8 MFMA (PV8_STEP, P from SOFTMAX_UPDATE72(P8_SUM_VALU)).  V is quantised ONCE per
+// workgroup: after the window has landed, every thread builds three 16-byte pieces of the e4m3 V^T operand image from the fp16 rows
+// (V_IMAGE_PIECE), a barrier, and the pieces overwrite the 16-bit V image in place.
+// QL = true: row maximum through the matrix pipe (QL_UPDATE72), here without the accumulator rescale in the first tile.
+// The tile loop is the shared pieces in sequence; its redirects to the constants are selected per read (attn_dma72_kernel precomputes
+// bases: the two forms compile differently and each kernel keeps its own).
 template <int NW, bool AV8 = false, bool QL = false>
 __global__ __launch_bounds__(NW * 64, (AV8 || NW != 8) ? 2 : 4) void attn_res256_kernel(const AttnArgs p) {
-  constexpr int ROW = 144, NK = 256, QS = 5, DT = 3, CH = 9;
+  constexpr int NK = 256;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* const Ks = smem;
-  char* const Vs = smem + NK * ROW;
+  char* const Vs = smem + NK * ROW72;
   const int tid = threadIdx.x, wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   const int lr = lane & 31, lh = lane >> 5;
   const int qgroups = (p.qtiles + NW - 1) / NW;
@@ -657,34 +857,11 @@ __global__ __launch_bounds__(NW * 64, (AV8 || NW != 8) ? 2 : 4) void attn_res256
   const int b = (int)p.div_heads.div((unsigned)item), h = item - b * p.heads;
   const int qwin = p.q_pool ? p.win / 2 : p.win;
 
-  // ---- DMA the window's K and V: chunk L -> (key row L / 9, 16-byte chunk L % 9); 36 wave-instructions per matrix
-  {
-    long long korg, vorg;
-    if (p.win > 0) {
-      const long long pix0 = tok_off_fast(p, b, 0, 1, p.win, p.grid_h, p.grid_w, p.div_win);
-      korg = pix0 * p.k_st; vorg = pix0 * p.v_st;
-    } else {
-      korg = (long long)b * p.k_sb; vorg = (long long)b * p.v_sb;
-    }
-    const char* kbase = p.k + (korg + (long long)h * p.k_sh) * 2;
-    const char* vbase = p.v + (vorg + (long long)h * p.v_sh) * 2;
-#pragma unroll
-    for (int j = 0; j < (36 + NW - 1) / NW; ++j) {
-      if (j * NW + wv >= 36) break;           // 36 wave-instructions per matrix (wave-uniform)
-      const int L = (j * NW + wv) * 64 + lane;
-      const int row = L / CH, ch = L - row * CH;
-      int pix = row;
-      if (p.win > 0) { const int ty = (int)p.div_win.div((unsigned)row); pix = ty * p.grid_w + (row - ty * p.win); }
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(kbase + ((long long)pix * p.k_st + ch * 8) * 2),
-                                       (__attribute__((address_space(3))) void*)(Ks + (j * NW + wv) * 1024), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(vbase + ((long long)pix * p.v_st + ch * 8) * 2),
-                                       (__attribute__((address_space(3))) void*)(Vs + (j * NW + wv) * 1024), 16, 0, 0);
-    }
-  }
+  WINDOW_KV_DMA(36, NW)                                     // 36 wave-instructions per matrix
   // ---- Q fragments while the DMA flies
   const int qi = qt * 32 + lr;
   const bool q_ok = live && qi < p.Nq;
-  // element offset of this lane's query token (pooled: of the top-left token of its 2 x 2 block), computed once
+  // LOAD_Q_FRAGS' qoff0 (not shared: each kernel's own arithmetic -- host multipliers here, tok_off's divisions in attn_dma72_kernel)
   long long qoff0;
   {
     const int qc = q_ok ? qi : 0;
@@ -692,53 +869,21 @@ __global__ __launch_bounds__(NW * 64, (AV8 || NW != 8) ? 2 : 4) void attn_res256
     if (p.q_pool) { const int py = (int)p.div_ow.div((unsigned)qc), px = qc - py * qwin; t = (2 * py) * p.win + 2 * px; }
     qoff0 = (p.win > 0 ? tok_off_fast(p, b, t, p.q_st, p.win, p.grid_h, p.grid_w, p.div_win) : (long long)b * p.q_sb + (long long)t * p.q_st) + (long long)h * p.q_sh;
   }
-  u32x4 qf[QS];
+  LOAD_Q_FRAGS(qf, QS72, qoff0)
+  f32x16 oacc[DT72];
 #pragma unroll
-  for (int s = 0; s < QS; ++s) {
-    const int d0 = 16 * s + 8 * lh;
-    u32x4 v = {0u, 0u, 0u, 0u};
-    if (q_ok && d0 < p.dqk) {
-      if (!p.q_pool) {
-        v = *reinterpret_cast<const u32x4*>(p.q + (qoff0 + d0) * 2);
-      } else {
-        f16x8 m;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) m[e] = (f16)(CVMI_LOWEST16);
-#pragma unroll
-        for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-          for (int dx = 0; dx < 2; ++dx) {
-            const long long off = qoff0 + ((long long)dy * p.grid_w + dx) * p.q_st + d0;   // pooled: the 2 x 2 block's tokens are grid neighbours
-            const f16x8 x = __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>(p.q + off * 2));
-#pragma unroll
-            for (int e = 0; e < 8; ++e) m[e] = x[e] > m[e] ? x[e] : m[e];
-          }
-        v = __builtin_bit_cast(u32x4, m);
-      }
-    }
-    qf[s] = v;
-  }
-  f32x16 oacc[DT];
-#pragma unroll
-  for (int t = 0; t < DT; ++t)
+  for (int t = 0; t < DT72; ++t)
 #pragma unroll
     for (int r = 0; r < 16; ++r) oacc[t][r] = 0.f;
   float m_run = -INFINITY, l_run = 0.f;
   const float c = p.scale * 1.44269504088896340736f;
   const int li = lane & 15;
-  const char* const vt = Vs + (lh + 4 * (li >> 2)) * ROW + (16 * (lr >> 4) + 4 * (li & 3)) * 2;      // key rows 4 apart: see key_perm72
-  const char* const kq = Ks + key_perm72(lr) * ROW + lh * 16;
-  // Row sums and (QL) the running maximum on the matrix pipe: as in attn_dma72_kernel, which documents both.  The constants live behind V.
-  constexpr int ONES = 2 * NK * ROW + 256;
+  const char* const vt = Vs + (lh + 4 * (li >> 2)) * ROW72 + (16 * (lr >> 4) + 4 * (li & 3)) * 2;      // key rows 4 apart: see key_perm72
+  const char* const kq = Ks + key_perm72(lr) * ROW72 + lh * 16;
+  // Row sums and (QL) the running maximum on the matrix pipe: mfma_consts_init, QL_UPDATE72.  The constants live behind V.
+  constexpr int ONES = 2 * NK * ROW72 + 256;
   const bool ones_lane = !AV8 && (lr >> 4) == 0 && (li & 3) == 2;
-  if constexpr (!AV8) {
-    if (tid < 16) {                                           // two copies: see ONES_V in attn_dma72_kernel
-      const int t8 = tid & 7, off = ((t8 >> 2) * 32 + ((t8 >> 1) & 1) * 16 + (t8 & 1) * 2) * ROW;
-      *reinterpret_cast<u32x2*>(smem + ONES + (tid < 8 ? 144 : 32) + off) = (u32x2){CVMI_ONE16X2 & 0xFFFFu, 0u};
-    } else if (QL && tid < 18) {
-      *reinterpret_cast<u32x4*>(smem + ONES + 16 + (tid - 16) * 32 * ROW) = (u32x4){CVMI_ONE16X2 & 0xFFFFu, 0u, 0u, 0u};
-    }
-  }
+  if constexpr (!AV8) mfma_consts_init<ONES, QL>(smem, tid);
   float m_ref = 0.f;                                          // QL: the reference maximum held (negated) in the Q operand
   dma_wait();                                               // every wave waits for its OWN LDS-DMA pieces ...
   __syncthreads();                                          // ... and the barrier publishes the window
@@ -751,22 +896,7 @@ __global__ __launch_bounds__(NW * 64, (AV8 || NW != 8) ? 2 : 4) void attn_res256
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
       const int pc = wv + 8 * i, kt = pc / 6, t = (pc - 6 * kt) >> 1, u = pc & 1;
-      unsigned w[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-      for (int sgrp = 0; sgrp < 2; ++sgrp) {
-        const char* a0 = vt + (kt * 64 + u * 32 + sgrp * 16) * ROW + t * 64;
-        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a0));
-        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a0 + 2 * ROW));
-        const f16x4 l4 = __builtin_bit_cast(f16x4, lo), h4 = __builtin_bit_cast(f16x4, hi);
-        float f[8];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { f[e] = (float)l4[e]; f[4 + e] = (float)h4[e]; }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) f[e] = __builtin_amdgcn_fmed3f(f[e], -448.f, 448.f);
-        w[2 * sgrp] = pack4_e4m3(f[0], f[1], f[2], f[3]);
-        w[2 * sgrp + 1] = pack4_e4m3(f[4], f[5], f[6], f[7]);
-      }
-      piece[i] = (u32x4){w[0], w[1], w[2], w[3]};
+      V_IMAGE_PIECE(piece[i], kt * 64 + u * 32, t)
     }
     __syncthreads();                                        // every transposing read of the 16-bit V image is done ...
 #pragma unroll
@@ -776,142 +906,25 @@ __global__ __launch_bounds__(NW * 64, (AV8 || NW != 8) ? 2 : 4) void attn_res256
 
 #pragma unroll 1
   for (int kc = 0; kc < NK / 64; ++kc) {
-    f32x16 sacc[2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) sacc[u][r] = 0.f;
-#pragma unroll
-    for (int s = 0; s < QS; ++s)
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const char* ka = (QL && s == 4 && lh) ? smem + ONES + 16 + u * 32 * ROW : kq + (kc * 64 + u * 32) * ROW + s * 32;      // QL: k = 72..79 read (1, 0, .., 0)
-        const f16x8 kf = __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>(ka));
-        sacc[u] = CVMI_MFMA_32X32X16(kf, __builtin_bit_cast(f16x8, qf[s]), sacc[u], 0, 0, 0);
-      }
-    float mxa = max3f(sacc[0][0], sacc[1][0], sacc[0][8]), mxb = max3f(sacc[1][8], sacc[0][1], sacc[1][1]);      // two chains of v_max3_f32
-#pragma unroll
-    for (int r = 2; r < 8; ++r) { mxa = max3f(mxa, sacc[0][r], sacc[1][r]); mxb = max3f(mxb, sacc[0][r + 7], sacc[1][r + 7]); }
-    const float mx = max3f(mxa, mxb, max3f(sacc[0][15], sacc[1][15], mxa));
+    SCORE_TILE72(sacc, (QL && s == 4 && lh) ? smem + ONES + 16 + u * 32 * ROW72 : kq + (kc * 64 + u * 32) * ROW72 + s * 32)      // QL: k = 72..79 read (1, 0, .., 0), selected per read
+    const float mx = tile_max(sacc);
     f16x8 pf[2][2];
     u32x4 p8[2];                                            // AV8: this lane's 32 e4m3 bytes of P^T (tile u -> bytes 16 u .. 16 u + 15)
     if constexpr (QL) {
       static_assert(!AV8, "QL is the 16-bit form");
-      const float top = xhalf_max(mx);                          // the tile's maximum RELATIVE to m_ref (the MFMA subtracted it)
-      const bool grow = kc == 0 || top > DEFER_LOG2;
-      if (__any(grow)) {                                      // (a real branch: the first tile, then rare)
-        const float m_new = grow ? (float)(f16)(m_ref + top) : m_ref;
-        const float dlt = m_new - m_ref;
-        m_ref = m_new;
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) sacc[u][r] -= dlt;
-        if (kc > 0) {                                           // (uniform; the accumulators are still zero in the first tile)
-          const float alpha = __builtin_amdgcn_exp2f(-dlt);
-#pragma unroll
-          for (int t = 0; t < DT; ++t)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) oacc[t][r] *= alpha;
-        }
-        if (lh) {
-          f16x8 qv = __builtin_bit_cast(f16x8, qf[4]);
-          qv[0] = (f16)(-m_new);
-          qf[4] = __builtin_bit_cast(u32x4, qv);
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) pf[u][r >> 3][r & 7] = (f16)__builtin_amdgcn_exp2f(sacc[u][r]);
+      QL_UPDATE72(kc == 0, kc > 0)
     } else {
-    const float m_top = fmaxf(m_run, xhalf_max(mx));
-    const bool grow = (m_top - m_run) * c > (AV8 ? 0.f : DEFER_LOG2);      // first tile: m_run = -inf -> true
-    const float m_new = grow ? m_top : m_run;
-    const float mc = m_new * c;
-    const float alpha = grow ? __builtin_amdgcn_exp2f(fmaf(m_run, c, -mc)) : 1.0f;
-    float psum = 0.f;
-    if constexpr (AV8) {
-      const float mc8 = mc - 8.f;                           // p * 2^8 through the exponent
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        unsigned w[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-        for (int r = 0; r < 16; r += 4) {
-          float e[4];
-#pragma unroll
-          for (int i = 0; i < 4; ++i) { e[i] = __builtin_amdgcn_exp2f(fmaf(sacc[u][r + i], c, -mc8)); psum += e[i]; }
-          w[r >> 2] = pack4_e4m3(e[0], e[1], e[2], e[3]);
-        }
-        p8[u] = (u32x4){w[0], w[1], w[2], w[3]};
-      }
-      psum *= 0.00390625f;                                  // back to the scale of l_run (exact: a power of two)
-    } else {
-      softmax_tiles<false>(sacc, c, mc, pf);
+      SOFTMAX_UPDATE72((AV8 ? P8_SUM_VALU : P16_SUM_MFMA))
     }
     if constexpr (AV8) {
-      psum = xhalf_sum(psum);
-      l_run = l_run * alpha + psum;
-    }
-    m_run = m_new;
-    if (__any(grow)) {                                      // (a real branch: rare once the first tiles have set the reference)
-      asm volatile("" ::: "memory");
-#pragma unroll
-      for (int t = 0; t < DT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) oacc[t][r] *= alpha;
-    }
-    }
-    if constexpr (AV8) {
-      const v8i32 pb = {(int)p8[0][0], (int)p8[0][1], (int)p8[0][2], (int)p8[0][3], (int)p8[1][0], (int)p8[1][1], (int)p8[1][2], (int)p8[1][3]};
-#pragma unroll
-      for (int t = 0; t < DT; ++t) {
-        const char* va = Vs + ((kc * 3 + t) * 2) * 1024 + lane * 16;
-        const u32x4 a_lo = *reinterpret_cast<const u32x4*>(va), a_hi = *reinterpret_cast<const u32x4*>(va + 1024);
-        const v8i32 av = {(int)a_lo[0], (int)a_lo[1], (int)a_lo[2], (int)a_lo[3], (int)a_hi[0], (int)a_hi[1], (int)a_hi[2], (int)a_hi[3]};
-        oacc[t] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(av, pb, oacc[t], 0, 0, 0, 127, 0, 119);      // e4m3 x e4m3, scales 2^0 / 2^-8
-      }
+      PV8_STEP(Vs + kc * 6 * 1024 + lane * 16)
     } else {
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-          for (int t = 0; t < DT; ++t) {
-            const char* a0 = (t == 2 && ones_lane) ? smem + ONES + (lh ? 32 : 144) + (u * 32 + s * 16) * ROW     // (the lanes of d = 72..75: the row-sum constants)
-                                                   : vt + (kc * 64 + u * 32 + s * 16) * ROW + t * 64;
-            const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a0));
-            const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a0 + 2 * ROW));
-            const u32x2 l2 = __builtin_bit_cast(u32x2, lo), h2 = __builtin_bit_cast(u32x2, hi);
-            const u32x4 vv = {l2[0], l2[1], h2[0], h2[1]};
-            oacc[t] = CVMI_MFMA_32X32X16(__builtin_bit_cast(f16x8, vv), pf[u][s], oacc[t], 0, 0, 0);
-          }
+      PV16_STEP((t == 2 && ones_lane) ? smem + ONES + (lh ? 32 : 144) + (u * 32 + s * 16) * ROW72     /* (the lanes of d = 72..75: the row-sum constants, selected per read) */
+                                      : vt + (kc * 64 + u * 32 + s * 16) * ROW72 + t * 64)
     }
   }
   if constexpr (!AV8) l_run = __shfl(oacc[2][4], lr);        // row d = 72 (tile 2, row 8): register 4 of the lanes of half 0, column = query
-  if (q_ok) {
-    const float inv = 1.f / l_run;
-    long long obase;
-    if (p.win > 0) {
-      const int ow = p.q_pool ? p.win / 2 : p.win, ogh = p.q_pool ? p.grid_h / 2 : p.grid_h, ogw = p.q_pool ? p.grid_w / 2 : p.grid_w;
-      obase = tok_off_fast(p, b, qi, p.o_st, ow, ogh, ogw, p.div_ow);
-    } else {
-      obase = (long long)b * p.o_sb + (long long)qi * p.o_st;
-    }
-    obase += (long long)h * p.o_sh;
-#pragma unroll
-    for (int t = 0; t < DT; ++t)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int d0 = t * 32 + 8 * g + 4 * lh;
-        if (d0 < p.dv) {
-          f16x4 ov;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) ov[e] = (f16)(oacc[t][4 * g + e] * inv);
-          *reinterpret_cast<f16x4*>(p.o + (obase + d0) * 2) = ov;
-        }
-      }
-  }
+  if (q_ok) NORMALISE_STORE(DT72, true)
 }
 
 // ---- 64-key windows of head_dim 72 (Hiera stages 1 and 4, and the q-pooled stage transitions that keep 64 keys):
@@ -919,14 +932,14 @@ __global__ __launch_bounds__(NW * 64, (AV8 || NW != 8) ? 2 : 4) void attn_res256
 template <int QT>
 __global__ __launch_bounds__(QT * 128, 4) void attn_res64_kernel(const AttnArgs p) {
   constexpr int NW = QT;                                    // waves per item
-  constexpr int ROW = 144, NK = 64, QS = 5, DT = 3, CH = 9;
-  constexpr int ITEM_B = 2 * NK * ROW + 64;                // K + V of one item (+ slack for the last rows' over-reads)
+  constexpr int NK = 64;
+  constexpr int ITEM_B = 2 * NK * ROW72 + 64;                // K + V of one item (+ slack for the last rows' over-reads)
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
   const int tid = threadIdx.x, wvg = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   const int sub = wvg / QT, wv = wvg - sub * QT;            // item within the workgroup, wave within the item
   char* const Ks = smem + sub * ITEM_B;
-  char* const Vs = Ks + NK * ROW;
+  char* const Vs = Ks + NK * ROW72;
   const int lr = lane & 31, lh = lane >> 5;
   const int nitems = p.B * p.heads;
   const int item_raw = xcd_order((int)blockIdx.x, (int)gridDim.x) * 2 + sub;
@@ -936,34 +949,11 @@ __global__ __launch_bounds__(QT * 128, 4) void attn_res64_kernel(const AttnArgs 
   const int b = (int)p.div_heads.div((unsigned)item), h = item - b * p.heads;      // (host-computed multipliers: as attn_res256_kernel, r04)
   const int qwin = p.q_pool ? p.win / 2 : p.win;
 
-  // ---- DMA the window's K and V: chunk L -> (key row L / 9, 16-byte chunk L % 9); 36 wave-instructions per matrix
-  {
-    long long korg, vorg;
-    if (p.win > 0) {
-      const long long pix0 = tok_off_fast(p, b, 0, 1, p.win, p.grid_h, p.grid_w, p.div_win);
-      korg = pix0 * p.k_st; vorg = pix0 * p.v_st;
-    } else {
-      korg = (long long)b * p.k_sb; vorg = (long long)b * p.v_sb;
-    }
-    const char* kbase = p.k + (korg + (long long)h * p.k_sh) * 2;
-    const char* vbase = p.v + (vorg + (long long)h * p.v_sh) * 2;
-#pragma unroll
-    for (int j = 0; j < (9 + NW - 1) / NW; ++j) {
-      if (j * NW + wv >= 9) break;                            // 9 wave-instructions per matrix (wave-uniform)
-      const int L = (j * NW + wv) * 64 + lane;
-      const int row = L / CH, ch = L - row * CH;
-      int pix = row;
-      if (p.win > 0) { const int ty = (int)p.div_win.div((unsigned)row); pix = ty * p.grid_w + (row - ty * p.win); }
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(kbase + ((long long)pix * p.k_st + ch * 8) * 2),
-                                       (__attribute__((address_space(3))) void*)(Ks + (j * NW + wv) * 1024), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(vbase + ((long long)pix * p.v_st + ch * 8) * 2),
-                                       (__attribute__((address_space(3))) void*)(Vs + (j * NW + wv) * 1024), 16, 0, 0);
-    }
-  }
+  WINDOW_KV_DMA(9, NW)                                      // 9 wave-instructions per matrix
   // ---- Q fragments while the DMA flies
   const int qi = qt * 32 + lr;
   const bool q_ok = live && qi < p.Nq;
-  // element offset of this lane's query token (pooled: of the top-left token of its 2 x 2 block), computed once
+  // LOAD_Q_FRAGS' qoff0 (not shared: each kernel's own arithmetic -- host multipliers here, tok_off's divisions in attn_dma72_kernel)
   long long qoff0;
   {
     const int qc = q_ok ? qi : 0;
@@ -971,118 +961,29 @@ __global__ __launch_bounds__(QT * 128, 4) void attn_res64_kernel(const AttnArgs 
     if (p.q_pool) { const int py = (int)p.div_ow.div((unsigned)qc), px = qc - py * qwin; t = (2 * py) * p.win + 2 * px; }
     qoff0 = (p.win > 0 ? tok_off_fast(p, b, t, p.q_st, p.win, p.grid_h, p.grid_w, p.div_win) : (long long)b * p.q_sb + (long long)t * p.q_st) + (long long)h * p.q_sh;
   }
-  u32x4 qf[QS];
+  LOAD_Q_FRAGS(qf, QS72, qoff0)
+  f32x16 oacc[DT72];
 #pragma unroll
-  for (int s = 0; s < QS; ++s) {
-    const int d0 = 16 * s + 8 * lh;
-    u32x4 v = {0u, 0u, 0u, 0u};
-    if (q_ok && d0 < p.dqk) {
-      if (!p.q_pool) {
-        v = *reinterpret_cast<const u32x4*>(p.q + (qoff0 + d0) * 2);
-      } else {
-        f16x8 m;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) m[e] = (f16)(CVMI_LOWEST16);
-#pragma unroll
-        for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-          for (int dx = 0; dx < 2; ++dx) {
-            const long long off = qoff0 + ((long long)dy * p.grid_w + dx) * p.q_st + d0;   // pooled: the 2 x 2 block's tokens are grid neighbours
-            const f16x8 x = __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>(p.q + off * 2));
-#pragma unroll
-            for (int e = 0; e < 8; ++e) m[e] = x[e] > m[e] ? x[e] : m[e];
-          }
-        v = __builtin_bit_cast(u32x4, m);
-      }
-    }
-    qf[s] = v;
-  }
-  f32x16 oacc[DT];
-#pragma unroll
-  for (int t = 0; t < DT; ++t)
+  for (int t = 0; t < DT72; ++t)
 #pragma unroll
     for (int r = 0; r < 16; ++r) oacc[t][r] = 0.f;
   float m_run = -INFINITY, l_run = 0.f;
   const float c = p.scale * 1.44269504088896340736f;
   const int li = lane & 15;
-  const char* const vt = Vs + (lh + 4 * (li >> 2)) * ROW + (16 * (lr >> 4) + 4 * (li & 3)) * 2;      // key rows 4 apart: see key_perm72
-  const char* const kq = Ks + key_perm72(lr) * ROW + lh * 16;
+  const char* const vt = Vs + (lh + 4 * (li >> 2)) * ROW72 + (16 * (lr >> 4) + 4 * (li & 3)) * 2;      // key rows 4 apart: see key_perm72
+  const char* const kq = Ks + key_perm72(lr) * ROW72 + lh * 16;
   dma_wait();                                               // every wave waits for its OWN LDS-DMA pieces ...
   __syncthreads();                                          // ... and the barrier publishes the window
 
-  {
-    constexpr int kc = 0;
-    f32x16 sacc[2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) sacc[u][r] = 0.f;
-#pragma unroll
-    for (int s = 0; s < QS; ++s)
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const f16x8 kf = __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>(kq + (kc * 64 + u * 32) * ROW + s * 32));
-        sacc[u] = CVMI_MFMA_32X32X16(kf, __builtin_bit_cast(f16x8, qf[s]), sacc[u], 0, 0, 0);
-      }
-    float mxa = max3f(sacc[0][0], sacc[1][0], sacc[0][8]), mxb = max3f(sacc[1][8], sacc[0][1], sacc[1][1]);      // two chains of v_max3_f32
-#pragma unroll
-    for (int r = 2; r < 8; ++r) { mxa = max3f(mxa, sacc[0][r], sacc[1][r]); mxb = max3f(mxb, sacc[0][r + 7], sacc[1][r + 7]); }
-    const float mx = max3f(mxa, mxb, max3f(sacc[0][15], sacc[1][15], mxa));
-    const float m_top = fmaxf(m_run, xhalf_max(mx));
-    const bool grow = (m_top - m_run) * c > DEFER_LOG2;      // first tile: m_run = -inf -> true
-    const float m_new = grow ? m_top : m_run;
-    const float mc = m_new * c;
-    const float alpha = grow ? __builtin_amdgcn_exp2f(fmaf(m_run, c, -mc)) : 1.0f;
-    float psum = 0.f;
+  {                                                         // the single key tile
+    SCORE_TILE72(sacc, kq + (u * 32) * ROW72 + s * 32)
+    const float mx = tile_max(sacc);
     f16x8 pf[2][2];
-    psum = softmax_tiles<true>(sacc, c, mc, pf);
-    psum = xhalf_sum(psum);
-    l_run = l_run * alpha + psum;
-    m_run = m_new;
-    if (__any(grow)) {                                      // (a real branch: rare once the first tiles have set the reference)
-      asm volatile("" ::: "memory");
-#pragma unroll
-      for (int t = 0; t < DT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) oacc[t][r] *= alpha;
-    }
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-      for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int t = 0; t < DT; ++t) {
-          const char* a0 = vt + (kc * 64 + u * 32 + s * 16) * ROW + t * 64;
-          const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a0));
-          const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a0 + 2 * ROW));
-          const u32x2 l2 = __builtin_bit_cast(u32x2, lo), h2 = __builtin_bit_cast(u32x2, hi);
-          const u32x4 vv = {l2[0], l2[1], h2[0], h2[1]};
-          oacc[t] = CVMI_MFMA_32X32X16(__builtin_bit_cast(f16x8, vv), pf[u][s], oacc[t], 0, 0, 0);
-        }
+    u32x4 p8[2];                                            // (unused: SOFTMAX_UPDATE72 names it in its discarded e4m3 branch)
+    SOFTMAX_UPDATE72(P16_SUM_VALU)
+    PV16_STEP(vt + (u * 32 + s * 16) * ROW72 + t * 64)
   }
-  if (q_ok) {
-    const float inv = 1.f / l_run;
-    long long obase;
-    if (p.win > 0) {
-      const int ow = p.q_pool ? p.win / 2 : p.win, ogh = p.q_pool ? p.grid_h / 2 : p.grid_h, ogw = p.q_pool ? p.grid_w / 2 : p.grid_w;
-      obase = tok_off_fast(p, b, qi, p.o_st, ow, ogh, ogw, p.div_ow);
-    } else {
-      obase = (long long)b * p.o_sb + (long long)qi * p.o_st;
-    }
-    obase += (long long)h * p.o_sh;
-#pragma unroll
-    for (int t = 0; t < DT; ++t)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int d0 = t * 32 + 8 * g + 4 * lh;
-        if (d0 < p.dv) {
-          f16x4 ov;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) ov[e] = (f16)(oacc[t][4 * g + e] * inv);
-          *reinterpret_cast<f16x4*>(p.o + (obase + d0) * 2) = ov;
-        }
-      }
-  }
+  if (q_ok) NORMALISE_STORE(DT72, true)
 }
 
 template <int QT>
@@ -1100,12 +1001,14 @@ int launch_res64(const AttnArgs& a, hipStream_t stream) {
 //      LDS buffers by DMA (no staging registers: 4 waves per SIMD); one barrier per tile publishes tile t + 1 while it
 //      drains, issued a full tile of MFMAs earlier.  Rows past Nk re-read the last key (finite; their scores are masked).
 // AV8: as in attn_res256_kernel -- the AV product on the block-scaled fp8 MFMA.  Per 64-key tile, waves 0..5 build one 1-KiB piece each of
-// the tile's e4m3 V^T operand image (d tile t = wave / 2, operand half u = wave & 1) from the 16-bit tile in front of the QK^T products; a
-// second barrier per tile (LDS writes only: the next tile's DMA stays in flight across it) publishes the image before the three MFMAs.
+// the tile's e4m3 V^T operand image (V_IMAGE_PIECE; d tile t = wave / 2, operand half u = wave & 1) from the 16-bit tile in front of the QK^T
+// products; a second barrier per tile (LDS writes only: the next tile's DMA stays in flight across it) publishes the image before PV8_STEP.
+// Windows and q_pool never reach this kernel (see the dispatcher), but its window / q_pool branches and tok_off's plain divisions stay:
+// removing them moves registers in a kernel that sits at 127 of 128.
 template <int NW, bool AV8 = false, bool QL = false>
 __global__ __launch_bounds__(NW * 64, NW == 4 ? 4 : 2) void attn_dma72_kernel(const AttnArgs p) {
-  constexpr int ROW = 144, TK = 64, QS = 5, DT = 3, CH = 9;
-  constexpr int TILE_B = TK * ROW;                          // 9216 B per matrix per buffer
+  constexpr int TK = 64;
+  constexpr int TILE_B = TK * ROW72;                          // 9216 B per matrix per buffer
   extern __shared__ __attribute__((aligned(16))) char smem[];
   // buffer u: K at u * 2 * TILE_B, V right behind it (a K row's over-read lands in V: finite)
   const int tid = threadIdx.x, wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
@@ -1141,7 +1044,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 4 : 2) void attn_dma72_kernel(co
 #pragma unroll
   for (int j = 0; j < (18 + NW - 1) / NW; ++j) {
     const int ins = j * NW + wv, isv = ins >= 9 ? 1 : 0, pc = ins - 9 * isv;
-    const int L = pc * 64 + lane, row = L / CH, ch = L - row * CH;
+    const int L = pc * 64 + lane, row = L / CH72, ch = L - row * CH72;
     loff[j] = (row * (isv ? p.v_st : p.k_st) + ch * 8) * 2;
   }
   const int ktile_b = TK * p.k_st * 2, vtile_b = TK * p.v_st * 2;                  // bytes per 64-key tile (host: Nk * stride * 2 < 2^31)
@@ -1159,7 +1062,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 4 : 2) void attn_dma72_kernel(co
   // ---- Q fragments while the DMA flies
   const int qi = qt * 32 + lr;
   const bool q_ok = live && qi < p.Nq;
-  // element offset of this lane's query token (pooled: of the top-left token of its 2 x 2 block), computed once
+  // LOAD_Q_FRAGS' qoff0 (not shared: tok_off and plain division here, host multipliers in the resident kernels)
   long long qoff0;
   {
     const int qc = q_ok ? qi : 0;
@@ -1167,67 +1070,21 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 4 : 2) void attn_dma72_kernel(co
     if (p.q_pool) { const int py = qc / qwin, px = qc - py * qwin; t = (2 * py) * p.win + 2 * px; }
     qoff0 = tok_off(b, t, p.q_sb, p.q_st, p.win, p.grid_h, p.grid_w) + (long long)h * p.q_sh;
   }
-  u32x4 qf[QS];
+  LOAD_Q_FRAGS(qf, QS72, qoff0)
+  f32x16 oacc[DT72];
 #pragma unroll
-  for (int s = 0; s < QS; ++s) {
-    const int d0 = 16 * s + 8 * lh;
-    u32x4 v = {0u, 0u, 0u, 0u};
-    if (q_ok && d0 < p.dqk) {
-      if (!p.q_pool) {
-        v = *reinterpret_cast<const u32x4*>(p.q + (qoff0 + d0) * 2);
-      } else {
-        f16x8 m;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) m[e] = (f16)(CVMI_LOWEST16);
-#pragma unroll
-        for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-          for (int dx = 0; dx < 2; ++dx) {
-            const long long off = qoff0 + ((long long)dy * p.grid_w + dx) * p.q_st + d0;   // pooled: the 2 x 2 block's tokens are grid neighbours
-            const f16x8 x = __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>(p.q + off * 2));
-#pragma unroll
-            for (int e = 0; e < 8; ++e) m[e] = x[e] > m[e] ? x[e] : m[e];
-          }
-        v = __builtin_bit_cast(u32x4, m);
-      }
-    }
-    qf[s] = v;
-  }
-  f32x16 oacc[DT];
-#pragma unroll
-  for (int t = 0; t < DT; ++t)
+  for (int t = 0; t < DT72; ++t)
 #pragma unroll
     for (int r = 0; r < 16; ++r) oacc[t][r] = 0.f;
   float m_run = -INFINITY, l_run = 0.f;
   const float c = p.scale * 1.44269504088896340736f;
   const int li = lane & 15;
-  const int vt_off = TILE_B + (lh + 4 * (li >> 2)) * ROW + (16 * (lr >> 4) + 4 * (li & 3)) * 2;      // key rows 4 apart: see key_perm72
-  const int kq_off = key_perm72(lr) * ROW + lh * 16;
-  // Row sums from the matrix pipe (16-bit form): the third 32-row tile of O^T = V^T P^T has rows d = 72..95 to spare, and the lanes whose
-  // transposing reads would fetch V[key][72..75] (past the row: the next key's first elements, rows never stored) read a constant (1, 0, 0, 0)
-  // instead -- row d = 72 of the accumulator is then the sum over keys of the ROUNDED probabilities, rescaled with the rest of the tile when
-  // the running maximum moves.  That takes 32 v_add_f32 per tile and wave off the vector issue port, which -- not the matrix pipe -- bounds
-  // this loop (ISA counts in DESIGN.md).  The constants sit at the eight offsets (32 u + 16 s) * ROW + {0, 2 ROW} the reads of one tile use.
-  // QL (q pre-multiplied by scale * log2 e where it was produced, cvmi_attn_desc.q_log2): the running maximum goes through the matrix pipe
-  // too.  head_dim 72 leaves k = 72..79 of the fifth QK^T step unused: the lanes that hold those k read K = (1, 0, .., 0) from a constant
-  // instead of the next key's first bytes, and hold Q = (-m, 0, .., 0), m = the row's reference maximum ROUNDED to the operand type -- the
-  // score tile comes out of the MFMA as s - m and exp2 applies to it as it stands: no v_fma_f32 per score either.  m moves only when a tile's
-  // maximum exceeds it by more than the deferred-rescale threshold (and on the first tile): then the tile is corrected by the exact
-  // difference of the two rounded references, which is also what the accumulators are rescaled by.
+  const int vt_off = TILE_B + (lh + 4 * (li >> 2)) * ROW72 + (16 * (lr >> 4) + 4 * (li & 3)) * 2;      // key rows 4 apart: see key_perm72
+  const int kq_off = key_perm72(lr) * ROW72 + lh * 16;
+  // Row sums and (QL) the running maximum on the matrix pipe: mfma_consts_init, QL_UPDATE72.
   constexpr int ONES = 4 * TILE_B + 256;                     // behind the buffers and their over-read slack
   const bool ones_lane = !AV8 && (lr >> 4) == 0 && (li & 3) == 2;
-  if constexpr (!AV8) {
-    // TWO copies of the V constants, one per 32-lane half (= LDS lane group of a transposing read): the 28 ordinary lanes of a group and
-    // the V rows they read cover 56 of the 64 banks exactly once, and the 8 banks left over are the ones the redirected lanes WOULD have
-    // used -- banks 36 / 52 / 4 / 20 (+ 1) in the half lh = 0, banks 8 / 24 / 40 / 56 in lh = 1 (tile bases are multiples of 256 bytes).  A
-    // constant anywhere else costs every t = 2 read a conflict cycle (PMC r03: 0.15 of the LDS cycles with one copy at bank 0).
-    if (tid < 16) {
-      const int t8 = tid & 7, off = ((t8 >> 2) * 32 + ((t8 >> 1) & 1) * 16 + (t8 & 1) * 2) * ROW;
-      *reinterpret_cast<u32x2*>(smem + ONES + (tid < 8 ? 144 : 32) + off) = (u32x2){CVMI_ONE16X2 & 0xFFFFu, 0u};
-    } else if (QL && tid < 18) {
-      *reinterpret_cast<u32x4*>(smem + ONES + 16 + (tid - 16) * 32 * ROW) = (u32x4){CVMI_ONE16X2 & 0xFFFFu, 0u, 0u, 0u};      // K constants: (32 u) * ROW apart
-    }
-  }
+  if constexpr (!AV8) mfma_consts_init<ONES, QL>(smem, tid);
   float m_ref = 0.f;                                          // QL: the reference maximum held (negated) in the Q operand
   dma_wait();
   __syncthreads();                                          // tile 0 landed
@@ -1239,165 +1096,35 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 4 : 2) void attn_dma72_kernel(co
     const char* const vt2 = ones_lane ? smem + ONES + (lh ? 32 : 144) - 128 : vt;      // base of the t = 2 reads (their + 128 lands on the constants)
     const char* const kq4 = (QL && lh) ? smem + ONES + 16 - 128 : kq;   // QL: base of the s = 4 reads of the lanes that hold k = 72..79
     if (kt + 1 < nkt) issue(kt + 1, (kt + 1) & 1);          // the other buffer was last read in iteration kt - 1 (barrier below)
-    constexpr int kc = 0;
     if constexpr (AV8) {
       static_assert(NW == 8, "six of eight waves build the e4m3 V image");
       if (wv < 6) {                                         // wave-uniform
         const int t = wv >> 1, u = wv & 1;
-        unsigned w[4];
-#pragma unroll
-        for (int sgrp = 0; sgrp < 2; ++sgrp) {
-          const char* a0 = vt + (u * 32 + sgrp * 16) * ROW + t * 64;
-          const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a0));
-          const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a0 + 2 * ROW));
-          const f16x4 l4 = __builtin_bit_cast(f16x4, lo), h4 = __builtin_bit_cast(f16x4, hi);
-          float f[8];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { f[e] = (float)l4[e]; f[4 + e] = (float)h4[e]; }
-#pragma unroll
-          for (int e = 0; e < 8; ++e) f[e] = __builtin_amdgcn_fmed3f(f[e], -448.f, 448.f);
-          w[2 * sgrp] = pack4_e4m3(f[0], f[1], f[2], f[3]);
-          w[2 * sgrp + 1] = pack4_e4m3(f[4], f[5], f[6], f[7]);
-        }
-        *reinterpret_cast<u32x4*>(smem + 4 * TILE_B + wv * 1024 + lane * 16) = (u32x4){w[0], w[1], w[2], w[3]};     // last read before the barrier that ended iteration kt - 1
+        V_IMAGE_PIECE(*reinterpret_cast<u32x4*>(smem + 4 * TILE_B + wv * 1024 + lane * 16), u * 32, t)     // last read before the barrier that ended iteration kt - 1
       }
     }
-    f32x16 sacc[2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) sacc[u][r] = 0.f;
-#pragma unroll
-    for (int s = 0; s < QS; ++s)
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const f16x8 kf = __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>((s == 4 ? kq4 : kq) + (kc * 64 + u * 32) * ROW + s * 32));
-        sacc[u] = CVMI_MFMA_32X32X16(kf, __builtin_bit_cast(f16x8, qf[s]), sacc[u], 0, 0, 0);
-      }
-    float mxa = max3f(sacc[0][0], sacc[1][0], sacc[0][8]), mxb = max3f(sacc[1][8], sacc[0][1], sacc[1][1]);      // two chains of v_max3_f32
-#pragma unroll
-    for (int r = 2; r < 8; ++r) { mxa = max3f(mxa, sacc[0][r], sacc[1][r]); mxb = max3f(mxb, sacc[0][r + 7], sacc[1][r + 7]); }
-    const float mx = max3f(mxa, mxb, max3f(sacc[0][15], sacc[1][15], mxa));
+    SCORE_TILE72(sacc, (s == 4 ? kq4 : kq) + (u * 32) * ROW72 + s * 32)      // QL: the constants through the precomputed base kq4
+    const float mx = tile_max(sacc);
     f16x8 pf[2][2];
     u32x4 p8[2];
     if constexpr (QL) {
       static_assert(!AV8, "QL is the 16-bit form");
-      const float top = xhalf_max(mx);                          // the tile's maximum RELATIVE to m_ref (the MFMA subtracted it)
-      const bool grow = kt == 0 || top > DEFER_LOG2;
-      if (__any(grow)) {                                      // (a real branch: the first tile, then rare)
-        const float m_new = grow ? (float)(f16)(m_ref + top) : m_ref;       // representable in the operand type, so the Q slot holds it exactly
-        const float dlt = m_new - m_ref;                        // exact in f32 (both are 16-bit values of similar magnitude or m_ref = 0)
-        const float alpha = __builtin_amdgcn_exp2f(-dlt);
-        m_ref = m_new;
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) sacc[u][r] -= dlt;
-#pragma unroll
-        for (int t = 0; t < DT; ++t)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) oacc[t][r] *= alpha;
-        if (lh) {                                               // the lanes that hold k = 72..79 of the fifth step
-          f16x8 qv = __builtin_bit_cast(f16x8, qf[4]);
-          qv[0] = (f16)(-m_new);
-          qf[4] = __builtin_bit_cast(u32x4, qv);
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) pf[u][r >> 3][r & 7] = (f16)__builtin_amdgcn_exp2f(sacc[u][r]);
+      QL_UPDATE72(kt == 0, true)
     } else {
-    const float m_top = fmaxf(m_run, xhalf_max(mx));
-    const bool grow = (m_top - m_run) * c > (AV8 ? 0.f : DEFER_LOG2);      // first tile: m_run = -inf -> true
-    const float m_new = grow ? m_top : m_run;
-    const float mc = m_new * c;
-    const float alpha = grow ? __builtin_amdgcn_exp2f(fmaf(m_run, c, -mc)) : 1.0f;
-    float psum = 0.f;
-    if constexpr (AV8) {
-      const float mc8 = mc - 8.f;                           // p * 2^8 through the exponent
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        unsigned w[4];
-#pragma unroll
-        for (int r = 0; r < 16; r += 4) {
-          float e[4];
-#pragma unroll
-          for (int i = 0; i < 4; ++i) { e[i] = __builtin_amdgcn_exp2f(fmaf(sacc[u][r + i], c, -mc8)); psum += e[i]; }
-          w[r >> 2] = pack4_e4m3(e[0], e[1], e[2], e[3]);
-        }
-        p8[u] = (u32x4){w[0], w[1], w[2], w[3]};
-      }
-      psum *= 0.00390625f;
-    } else {
-      softmax_tiles<false>(sacc, c, mc, pf);
-    }
-    if constexpr (AV8) {
-      psum = xhalf_sum(psum);
-      l_run = l_run * alpha + psum;
-    }
-    m_run = m_new;
-    if (__any(grow)) {                                      // (a real branch: rare once the first tiles have set the reference)
-      asm volatile("" ::: "memory");
-#pragma unroll
-      for (int t = 0; t < DT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) oacc[t][r] *= alpha;
-    }
+      SOFTMAX_UPDATE72((AV8 ? P8_SUM_VALU : P16_SUM_MFMA))
     }
     if constexpr (AV8) {
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's piece of the e4m3 image is written ...
       __builtin_amdgcn_s_barrier();                         // ... and published (no vmcnt wait: tile kt + 1's DMA keeps flying)
-      const v8i32 pb = {(int)p8[0][0], (int)p8[0][1], (int)p8[0][2], (int)p8[0][3], (int)p8[1][0], (int)p8[1][1], (int)p8[1][2], (int)p8[1][3]};
-#pragma unroll
-      for (int t = 0; t < DT; ++t) {
-        const char* va = smem + 4 * TILE_B + (2 * t) * 1024 + lane * 16;
-        const u32x4 a_lo = *reinterpret_cast<const u32x4*>(va), a_hi = *reinterpret_cast<const u32x4*>(va + 1024);
-        const v8i32 av = {(int)a_lo[0], (int)a_lo[1], (int)a_lo[2], (int)a_lo[3], (int)a_hi[0], (int)a_hi[1], (int)a_hi[2], (int)a_hi[3]};
-        oacc[t] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(av, pb, oacc[t], 0, 0, 0, 127, 0, 119);
-      }
+      PV8_STEP(smem + 4 * TILE_B + lane * 16)
     } else {
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-          for (int t = 0; t < DT; ++t) {
-            const char* a0 = (t == 2 ? vt2 : vt) + (kc * 64 + u * 32 + s * 16) * ROW + t * 64;
-            const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a0));
-            const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a0 + 2 * ROW));
-            const u32x2 l2 = __builtin_bit_cast(u32x2, lo), h2 = __builtin_bit_cast(u32x2, hi);
-            const u32x4 vv = {l2[0], l2[1], h2[0], h2[1]};
-            oacc[t] = CVMI_MFMA_32X32X16(__builtin_bit_cast(f16x8, vv), pf[u][s], oacc[t], 0, 0, 0);
-          }
+      PV16_STEP((t == 2 ? vt2 : vt) + (u * 32 + s * 16) * ROW72 + t * 64)     // (the row-sum constants through the precomputed base vt2)
     }
     dma_wait();                                             // this wave's pieces of tile kt + 1 (issued a whole tile of MFMAs ago)
     __syncthreads();                                        // tile kt fully read; tile kt + 1 landed in every wave
   }
   if constexpr (!AV8) l_run = __shfl(oacc[2][4], lr);        // row d = 72 (tile 2, row 8): register 4 of the lanes of half 0, column = query
-  if (q_ok) {
-    const float inv = 1.f / l_run;
-    long long obase;
-    if (p.win > 0) {
-      const int ow = p.q_pool ? p.win / 2 : p.win, ogh = p.q_pool ? p.grid_h / 2 : p.grid_h, ogw = p.q_pool ? p.grid_w / 2 : p.grid_w;
-      obase = tok_off(b, qi, p.o_sb, p.o_st, ow, ogh, ogw);
-    } else {
-      obase = (long long)b * p.o_sb + (long long)qi * p.o_st;
-    }
-    obase += (long long)h * p.o_sh;
-#pragma unroll
-    for (int t = 0; t < DT; ++t)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int d0 = t * 32 + 8 * g + 4 * lh;
-        if (d0 < p.dv) {
-          f16x4 ov;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) ov[e] = (f16)(oacc[t][4 * g + e] * inv);
-          *reinterpret_cast<f16x4*>(p.o + (obase + d0) * 2) = ov;
-        }
-      }
-  }
+  if (q_ok) NORMALISE_STORE(DT72, false)
 }
 
 template <int NW, bool AV8 = false, bool QL = false>
