@@ -689,7 +689,9 @@ int launch_ln(const void* x, int x_ld, const float* gamma, const float* beta, vo
   CVMI_CHECK(bestG * bestN >= chunks, "layernorm: C=%d too wide", C);
   const int rpw = 64 / bestG;
   const dim3 g((unsigned)((rows + 4 * rpw - 1) / (4 * rpw))), b(256);
-#define CVMI_LN(N, W) hipLaunchKernelGGL((layernorm_kernel<TI, TO, N, W>), g, b, 0, stream, (const TI*)x, x_ld, gamma, beta, (TO*)y, y_ld, rows, C, eps, act, bestG, pw, pwp, phw, phpwp, (f16*)y2, y2_ld)
+#define CVMI_LN(N, W)                                                                                                    \
+  cvmi_note_kernel("layernorm_kernel<%s, %s, %d, %d>", sizeof(TI) == 2 ? CVMI_F16NAME : "float", sizeof(TO) == 2 ? CVMI_F16NAME : "float", N, W); \
+  hipLaunchKernelGGL((layernorm_kernel<TI, TO, N, W>), g, b, 0, stream, (const TI*)x, x_ld, gamma, beta, (TO*)y, y_ld, rows, C, eps, act, bestG, pw, pwp, phw, phpwp, (f16*)y2, y2_ld)
 #define CVMI_LN_SW(W)                                                                                                    \
   switch (bestN) {                                                                                                       \
     case 1: CVMI_LN(1, W); break;                                                                                        \
@@ -924,6 +926,7 @@ extern "C" int cvmi_upsample_refine(const float* low, int N, int h, int w, float
   a.nk = nk; a.ic = ic; a.comb_w = off; a.comb_b = off + nk * ic; a.halo = halo;
   if (nk == 4 && ks[0] == 3 && ks[1] == 5 && ks[2] == 7 && ks[3] == 11 && ic == 4 && ((uintptr_t)high & 15) == 0) {   // the reference's head
     const dim3 gf((W + RF_TW - 1) / RF_TW, (H + RF_TH - 1) / RF_TH, N);
+    cvmi_note_kernel("upsample_refine_fast_kernel");
     hipLaunchKernelGGL(upsample_refine_fast_kernel, gf, dim3(256), 0, (hipStream_t)stream_, low, h, w, high, H, W, params, (float)h / (float)H,
                        (float)w / (float)W);
     CVMI_LAUNCH_CHECK();
@@ -932,6 +935,7 @@ extern "C" int cvmi_upsample_refine(const float* low, int N, int h, int w, float
   const int TS = RF_TILE + 2 * halo;
   const size_t lds = (size_t)TS * (TS + 1) * sizeof(float);
   const dim3 g((W + RF_TILE - 1) / RF_TILE, (H + RF_TILE - 1) / RF_TILE, N);
+  cvmi_note_kernel("upsample_refine_kernel<4>");
   hipLaunchKernelGGL(upsample_refine_kernel<4>, g, dim3(256), lds, (hipStream_t)stream_, low, h, w, high, H, W, params, a, (float)h / (float)H,
                      (float)w / (float)W);
   CVMI_LAUNCH_CHECK();

@@ -515,12 +515,14 @@ extern "C" int cvmi_sppf_pool(void* buf, int ld, int B, int H, int W, int C, int
   const size_t lds = (size_t)2 * H * W * vec * sizeof(float);
   if (lds <= 64 * 1024) {
     const unsigned blocks = (unsigned)(B * (C / vec));
+    cvmi_note_kernel("sppf_pool_lds_kernel<%s>", dtype == CVMI_F16 ? CVMI_F16NAME : "float");
     if (dtype == CVMI_F16) hipLaunchKernelGGL(sppf_pool_lds_kernel<f16>, dim3(blocks), dim3(256), lds, stream, (char*)buf, ld, H, W, C);
     else hipLaunchKernelGGL(sppf_pool_lds_kernel<float>, dim3(blocks), dim3(256), lds, stream, (char*)buf, ld, H, W, C);
-  } else if (dtype == CVMI_F16)
-    hipLaunchKernelGGL(sppf_pool_kernel<f16>, dim3(grid_for(total)), dim3(256), 0, stream, (char*)buf, ld, B, H, W, C);
-  else
-    hipLaunchKernelGGL(sppf_pool_kernel<float>, dim3(grid_for(total)), dim3(256), 0, stream, (char*)buf, ld, B, H, W, C);
+  } else {
+    cvmi_note_kernel("sppf_pool_kernel<%s>", dtype == CVMI_F16 ? CVMI_F16NAME : "float");
+    if (dtype == CVMI_F16) hipLaunchKernelGGL(sppf_pool_kernel<f16>, dim3(grid_for(total)), dim3(256), 0, stream, (char*)buf, ld, B, H, W, C);
+    else hipLaunchKernelGGL(sppf_pool_kernel<float>, dim3(grid_for(total)), dim3(256), 0, stream, (char*)buf, ld, B, H, W, C);
+  }
   CVMI_LAUNCH_CHECK();
   return 0;
 }

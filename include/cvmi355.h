@@ -42,7 +42,7 @@ enum { CVMI_ACT_NONE = 0, CVMI_ACT_SILU = 1, CVMI_ACT_RELU = 2, CVMI_ACT_GELU = 
 int cvmi_version(void);
 const char* cvmi_last_error(void);
 /* Diagnostic: the kernel (template instance) the calling thread's most recent cvmi_conv2d / cvmi_attention / cvmi_tok_linear* /
- * cvmi_hiera_mlp* call dispatched to, as rocprofv3 names it up to the spelling of the 16-bit type (e.g. "gemm256x192_kernel<float>").  Read-and-clear: "" when no such
+ * cvmi_hiera_mlp* / cvmi_c3k2 / cvmi_stem2 / cvmi_dwpw / cvmi_layernorm* / cvmi_sppf_pool / cvmi_upsample_refine call dispatched to, as rocprofv3 names it up to the spelling of the 16-bit type (e.g. "gemm256x192_kernel<float>").  Read-and-clear: "" when no such
  * call happened since the last read. */
 const char* cvmi_last_kernel(void);
 /* fills: [0] CU count, [1] wave size, [2] LDS bytes per CU-workgroup, [3] gfx arch number (950) */

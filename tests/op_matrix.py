@@ -12,6 +12,14 @@ or a dict per dtype of such strings.
 FUSED_ROWS: the fused YOLO11 kernels.  One row = one launch of cvmi_c3k2, cvmi_stem2 or cvmi_dwpw, the tag it must report (launch_c3k2 / launch_dwpw /
 cvmi_stem2 tag the instance as the template is written) and its options; operands, references and the tolerance live in tests/fused_ref.py.
 
+LN_ROWS / LN_DUAL_ROWS: cvmi_layernorm and cvmi_layernorm_dual.  One row = one launch, the template instance layernorm_kernel<TI, TO, NCH, WD>
+that launch_ln (sam_ops.hip) must tag, and the lanes per row G that ln_pick -- a mirror of launch_ln's selection loop -- derives from C.  The
+rows are generated from ln_pick: every reachable (G, NCH) of every form at the smallest C that selects it, plus the row counts, layouts and
+options at which a row-per-lane-group kernel goes wrong.
+
+HELPER_ROWS: the other helper kernels of sam_ops.hip and vision_ops.hip (SPPF pooling, the refinement head, depthwise 3x3, the grid-capped
+copies, bilinear resize / mask post-processing, the mask decoder tail).  Operands, references and tolerances live in tests/helper_ref.py.
+
 BF16_OPS: every entry point that common.hpp builds twice (CVMI_ENTRY) -> (test module, test function) that checks its bf16 build per op.
 
 Plain data: importing this module needs neither a GPU nor the library."""
@@ -281,8 +289,8 @@ CONV_ROWS = [
 BF16_OPS = {
     "cvmi_attention": ("test_attention_matrix_gpu.py", "test_attention_matrix"),
     "cvmi_conv2d": ("test_conv_matrix_gpu.py", "test_conv_matrix"),            # (tests/test_bf16_ops_gpu.py test_conv2d_bf16* remain beside it)
-    "cvmi_layernorm": ("test_bf16_ops_gpu.py", "test_layernorm_bf16"),
-    "cvmi_layernorm_dual": ("test_bf16_ops_gpu.py", "test_layernorm_dual_bf16_copy"),
+    "cvmi_layernorm": ("test_helper_matrix_gpu.py", "test_layernorm_matrix"),      # (tests/test_bf16_ops_gpu.py test_layernorm_bf16 remains beside it)
+    "cvmi_layernorm_dual": ("test_helper_matrix_gpu.py", "test_layernorm_dual_matrix"),
     "cvmi_maxpool2x2": ("test_bf16_ops_gpu.py", "test_maxpool_and_space_to_depth_bf16"),
     "cvmi_space_to_depth4": ("test_bf16_ops_gpu.py", "test_maxpool_and_space_to_depth_bf16"),
     "cvmi_cast": ("test_bf16_ops_gpu.py", "test_cast_bf16"),
@@ -384,4 +392,173 @@ FUSED_MUTANT_ROWS = {
     "rows_bleed": [r["id"] for r in FUSED_ROWS if r["B"] != "persist" and (r["kernel"] != "stem2" or r["H"] % 2 == 0)],
     "stem_t_bias_outside": ["stem2_17x33"],
     "dw_first_chunk_taps": ["dwpw_c128_n64", "dwpw_c128_n80"],
+}
+
+
+# ---- cvmi_layernorm / cvmi_layernorm_dual: sam_ops.hip launch_ln ---------------------------------------------------------------------------
+LN_G = (4, 8, 16, 32, 64)                    # lanes per row
+LN_NCAND = (1, 2, 3, 5, 8, 9)                # slots per lane: the instances of CVMI_LN_SW
+LN_MAX_CHUNKS = LN_G[-1] * LN_NCAND[-1]      # beyond: "layernorm: C=.. too wide"
+# form -> (input type, output type, channels per slot, WD).  "16": the 16-bit operand type of the row's dtype (fp16 or bf16).
+LN_FORMS = {
+    "f32_f32": ("float", "float", 4, 1),
+    "f32_16w": ("float", "16", 8, 2),        # C % 8 == 0 and y_ld % 8 == 0: two 16-byte loads, one 16-byte store per slot
+    "f32_16n": ("float", "16", 4, 1),        # C % 8 == 4 or y_ld % 8 == 4
+    "16_16": ("16", "16", 8, 1),
+    "16_f32": ("16", "float", 8, 1),
+}
+LN_PAD = (5, 7, 8, 8)                        # pad = (H, W, Hp, Wp): rows are pixels of [*, 5, 7] images written into a [*, 8, 8] grid
+
+
+def ln_pick(C, slot):
+    """launch_ln's choice for C channels in slots of `slot`: (G, NCH, waste) with waste = G * NCH - C / slot idle slots.  For every G the first
+    NCH that fits; among those the least waste, then the smaller NCH."""
+    assert C > 0 and C % slot == 0, (C, slot)
+    chunks = C // slot
+    best = None
+    for G in LN_G:
+        for n in LN_NCAND:
+            if G * n < chunks:
+                continue
+            waste = G * n - chunks
+            if best is None or waste < best[2] or (waste == best[2] and n < best[1]):
+                best = (G, n, waste)
+            break
+    if best is None:
+        raise ValueError(f"layernorm: C={C} too wide")
+    return best
+
+
+def ln_reachable(ncand=LN_NCAND):
+    """{(G, NCH): [chunk counts that select it]} over every width launch_ln accepts."""
+    global LN_NCAND
+    keep, out = LN_NCAND, {}
+    LN_NCAND = tuple(ncand)
+    try:
+        for chunks in range(1, LN_G[-1] * max(ncand) + 1):
+            G, n, _ = ln_pick(chunks, 1)
+            out.setdefault((G, n), []).append(chunks)
+    finally:
+        LN_NCAND = keep
+    return out
+
+
+def ln_tag(form, nch, dt):
+    ti, to, _, wd = LN_FORMS[form]
+    return "layernorm_kernel<%s, %s, %d, %d>" % (TNAME[dt] if ti == "16" else ti, TNAME[dt] if to == "16" else to, nch, wd)
+
+
+def _ln(form, C, rows, tag, act="none", inside=0, pad=None):
+    """One cvmi_layernorm launch over `rows` rows of C channels.  inside = 8: input and output sit at column 8 of buffers 8 columns wider on both
+    sides.  The narrow f32 -> 16-bit form with C % 8 == 0 gets 4 more output columns (y_ld % 8 == 4), or the dispatcher would take the wide form."""
+    slot = LN_FORMS[form][2]
+    G, nch, waste = ln_pick(C, slot)
+    y_more = 4 if form == "f32_16n" and C % 8 == 0 else 0
+    return dict(id="%s_g%d_n%d_c%d_%s" % (form, G, nch, C, tag), form=form, dtypes=("f32",) if form == "f32_f32" else F16_BF16, C=C, rows=rows, G=G,
+                NCH=nch, waste=waste, act=act, x_off=inside, x_ld=C + 2 * inside, y_off=inside, y_ld=C + 2 * inside + y_more, pad=pad)
+
+
+def _ln_rows():
+    out = []
+    reach = ln_reachable()
+    for form, (_, _, slot, _) in LN_FORMS.items():
+        for (G, n), chunks in sorted(reach.items()):                      # every reachable instance at its smallest C: two workgroups, the second partial
+            out.append(_ln(form, chunks[0] * slot, 4 * 64 // G + 3, "min"))
+        for G, n in ((8, 3), (64, 2)):                                    # Hiera's NCH = 3 and the one-row-per-wave G = 64 form
+            full, short = reach[(G, n)][-1] * slot, reach[(G, n)][-2] * slot  # every slot busy / one idle slot
+            wg = 4 * 64 // G
+            out += [_ln(form, full, 1, "rows1"), _ln(form, full, wg - 1, "wg_minus1"), _ln(form, full, wg + 1, "wg_plus1"),
+                    _ln(form, short, wg + 3, "waste"), _ln(form, full, wg + 3, "inside", inside=8),
+                    _ln(form, full, 3 * LN_PAD[0] * LN_PAD[1], "padgrid", pad=LN_PAD), _ln(form, full, wg + 3, "gelu", act="gelu")]
+    # the narrow f32 -> 16-bit form by both of its conditions, at a Hiera-like width
+    out += [_ln("f32_16n", 100, 67, "c_mod8_4"), _ln("f32_16n", 96, 67, "yld_mod8_4")]
+    return out
+
+
+LN_ROWS = _ln_rows()
+# cvmi_layernorm_dual: f32 in place + a 16-bit copy (y2_ld = C + 8), NCH in {1, 3, 9}
+LN_DUAL_ROWS = [dict(id="dual_c%d" % C, C=C, rows=67, dtypes=F16_BF16, G=ln_pick(C, 4)[0], NCH=ln_pick(C, 4)[1], expect="layernorm_kernel<float, float, %d, 1>" % ln_pick(C, 4)[1])
+                for C in (256, 96, 144)]
+
+# mutant of tests/helper_ref.py -> ids of the rows that must catch it (tests/test_helper_ref_cpu.py)
+LN_MUTANT_ROWS = {
+    "ln_stats_over_slots": [r["id"] for r in LN_ROWS if r["waste"] > 0 and r["id"].endswith("_waste")],
+    "ln_rows_shift_at_wg": [r["id"] for r in LN_ROWS if r["id"].endswith(("_wg_plus1", "_waste", "_gelu"))],
+    "ln_pad_row_uses_w": [r["id"] for r in LN_ROWS if r["pad"]],
+}
+
+
+# ---- the other helper kernels -----------------------------------------------------------------------------------------------------------------
+GRID_CAP_ITEMS = {"cast": 4096 * 256, "maxpool2x2": 4096 * 256, "space_to_depth4": 4096 * 256, "nchw_to_nhwc": 4096 * 256, "nhwc_to_nchw_f32": 4096 * 256,
+                  "sppf_pool": 4096 * 256, "bilinear": 1024 * 256, "hyper_masks": 64 * 256, "repeat_images": 64 * 256}   # work items of one grid pass
+SPPF_LDS_PIXELS = {"f16": 1024, "f32": 2048}                              # the largest H * W of sppf_pool_lds_kernel (two f32 planes in 64 KiB)
+
+
+def _sppf(rid, dt, B, H, W, C, ld_extra=0):
+    lds = H * W <= SPPF_LDS_PIXELS[dt]
+    return dict(op="sppf_pool", id="sppf_%s_%s" % (rid, dt), dtypes=(dt,), expect=("sppf_pool_lds_kernel<%s>" if lds else "sppf_pool_kernel<%s>") % TNAME[dt],
+                B=B, H=H, W=W, C=C, ld=4 * C + ld_extra)
+
+
+REFINE_KS = (3, 5, 7, 11)                                                 # the reference's head: upsample_refine_fast_kernel
+
+
+def _rf(rid, hw, HW, ks=REFINE_KS, y_shift=0, N=2):
+    """cvmi_upsample_refine: [N, h, w] -> bilinear to [N, H, W] -> refinement branches ks.  y_shift: the output starts that many floats into its buffer."""
+    fast = tuple(ks) == REFINE_KS and y_shift == 0
+    return dict(op="refine", id="refine_" + rid, dtypes=("f32",), expect="upsample_refine_fast_kernel" if fast else "upsample_refine_kernel<4>", N=N,
+                h=hw[0], w=hw[1], H=HW[0], W=HW[1], ks=tuple(ks), y_shift=y_shift)
+
+
+def _dw(rid, dt, H, W, res, act, B=3, C=24):
+    return dict(op="dwconv3x3", id="dw_%s_%s" % (rid, dt), dtypes=(dt,), expect="", B=B, H=H, W=W, C=C, res=res, act=act, x_off=8, x_extra=16, y_guard=8)
+
+
+def _loop2(op, rid, **kw):
+    return dict(op=op, id="%s_%s" % (op, rid), expect="", **kw)
+
+
+def _helper_rows():
+    rows = []
+    for dt, c in (("f16", 16), ("f32", 8)):                                # >= two 16-byte channel chunks everywhere
+        edge = (32, 32) if dt == "f16" else (32, 64)
+        rows += [_sppf("1x1", dt, 2, 1, 1, c), _sppf("3x5", dt, 2, 3, 5, c, ld_extra=8), _sppf("1x20", dt, 2, 1, 20, c), _sppf("20x1", dt, 3, 20, 1, c),
+                 _sppf("lds_limit", dt, 2, edge[0], edge[1], c), _sppf("past_lds_limit", dt, 2, edge[0] + 1, edge[1], c, ld_extra=8)]
+    rows.append(_sppf("second_pass", "f16", 16, 40, 40, 328))              # 16 * 1600 * 41 = 1049600 chunk-pixels > 2^20
+    for H, W in ((16, 64), (17, 65), (5, 7), (33, 62), (40, 96)):
+        rows += [_rf("fast_%dx%d_identity" % (H, W), (H, W), (H, W)), _rf("fast_%dx%d_nonint" % (H, W), ((H + 2) // 3 + 1, (W + 2) // 3 + 2), (H, W))]
+    rows += [_rf("fast_16x64_up4", (4, 16), (16, 64)), _rf("fast_40x96_up4", (10, 24), (40, 96)), _rf("fast_20x28_up4", (5, 7), (20, 28))]
+    rows += [_rf("generic_ks357", (9, 14), (21, 37), ks=(3, 5, 7)), _rf("generic_ks1", (9, 14), (21, 37), ks=(1,)), _rf("generic_ks15", (9, 14), (21, 37), ks=(15,)),
+             _rf("generic_ks357_identity", (17, 33), (17, 33), ks=(3, 5, 7)), _rf("generic_unaligned_out", (9, 14), (21, 37), y_shift=1),
+             _rf("generic_unaligned_out_up4", (10, 24), (40, 96), y_shift=1)]
+    for dt in ("f16", "f32"):
+        for H in (1, 3):
+            for W in (1, 2, 3, 4, 5, 9):
+                rows += [_dw("%dx%d_res_silu" % (H, W), dt, H, W, 1, "silu"), _dw("%dx%d_plain" % (H, W), dt, H, W, 0, "none")]
+    # ---- the second pass of every capped grid-stride loop, bit-exact
+    for a, b in (("f32", "f16"), ("f16", "f32"), ("f32", "f32"), ("f16", "f16"), ("f32", "bf16"), ("bf16", "f32"), ("bf16", "bf16")):
+        rows.append(_loop2("cast", "%s_%s" % (a, b), dtypes=(a,), dst=b, rows=1025, C=1024, x_ld=1032, y_ld=1032))
+    for dt in ALL3:
+        rows.append(_loop2("maxpool2x2", dt, dtypes=(dt,), B=2, H=2 * 258, W=2 * 256, C=32 if dt == "f32" else 64))     # 8 chunks per output pixel
+        rows.append(_loop2("space_to_depth4", dt, dtypes=(dt,), B=2, H=4 * 363, W=4 * 362))
+    for a, b in (("f32", "f16"), ("f32", "f32"), ("f16", "f16"), ("f16", "f32"), ("f32", "bf16"), ("bf16", "bf16"), ("bf16", "f32")):
+        rows.append(_loop2("nchw_to_nhwc", "%s_%s" % (a, b), dtypes=(a,), dst=b, B=2, C=3, H=420, W=417, ld=8))
+    for dt in F16_F32:
+        rows.append(_loop2("nhwc_to_nchw_f32", dt, dtypes=(dt,), B=2, C=5, H=330, W=319, ld=8))
+    rows.append(_loop2("repeat_images", "rep3", dtypes=("f32",), B=2, rep=3, chunks=64 * 256 + 37))
+    rows.append(dict(op="bilinear", id="bilinear_520x517", dtypes=("f32",), expect="", N=2, h=130, w=97, H=520, W=517))
+    rows.append(dict(op="mask_postprocess", id="mask_postprocess_520x517", dtypes=("f32",), expect="", N=2, h=130, w=97, H=520, W=517))
+    for C, seed in ((32, 1), (64, 0)):
+        rows.append(dict(op="hyper_masks", id="hyper_masks_c%d" % C, dtypes=ALL3, expect="", B=3, P=129 * 129, C=C, up_ld=C + 8, delta=0.05, thresh=0.98, seed=seed))
+    return rows
+
+
+HELPER_ROWS = _helper_rows()
+
+HELPER_MUTANT_ROWS = {
+    "sppf_clip_zero": [r["id"] for r in HELPER_ROWS if r["op"] == "sppf_pool" and "second_pass" not in r["id"]],
+    "sppf_two_stages": [r["id"] for r in HELPER_ROWS if r["op"] == "sppf_pool" and max(r["H"], r["W"]) >= 20 and "second_pass" not in r["id"]],
+    "refine_pad_before_upsample": [r["id"] for r in HELPER_ROWS if r["op"] == "refine" and (r["h"], r["w"]) != (r["H"], r["W"]) and max(r["ks"]) > 1],
+    "refine_taps_transposed": [r["id"] for r in HELPER_ROWS if r["op"] == "refine" and max(r["ks"]) > 1],
+    "dw_tail_reads_next_row": [r["id"] for r in HELPER_ROWS if r["op"] == "dwconv3x3" and r["H"] > 1],
 }

@@ -10,6 +10,7 @@ import torch.nn.functional as F
 from circuitvision_amd import _lib
 from circuitvision_amd._lib import ACT_GELU, ACT_NONE, ACT_RELU, ACT_SILU, BF16, F16, F32
 from circuitvision_amd.engine import TORCH_DTYPE, Buf, PackedConv, Plan, op_conv, op_layernorm, op_maxpool2
+from helper_ref import _check_ln, _ln_ref
 from helpers import TOL, from_view, quant, run, stream, to_buf
 
 pytestmark = pytest.mark.gpu
@@ -138,32 +139,6 @@ def test_conv2d_bf16_rejects_bad_arguments():
 
 
 # ---- cvmi_layernorm / cvmi_layernorm_dual ---------------------------------------------------------------------------
-def _ulp16(x, dtype):
-    """One unit in the last place of the 16-bit type at |x| (bf16: 8 significant bits, fp16: 11, normal range)."""
-    mant = 8 if dtype == BF16 else 11
-    e = torch.floor(torch.log2(x.abs().clamp(min=2.0 ** -126)))
-    return torch.pow(2.0, e - (mant - 1))
-
-
-def _ln_ref(x, gam, bet, eps, act):
-    xd = x.double()
-    xh = (xd - xd.mean(-1, keepdim=True)) / torch.sqrt(xd.var(-1, unbiased=False, keepdim=True) + eps)
-    y = xh * gam.double() + bet.double()
-    scale = (xh * gam.double()).abs() + bet.double().abs()         # magnitude of the fp32 terms the kernel adds
-    return (F.gelu(y) if act == ACT_GELU else y), scale
-
-
-def _check_ln(got, ref, scale, dout, what):
-    err = (got.double() - ref).abs()
-    if dout == F32:
-        bound = 1e-5 + 1e-5 * ref.abs()
-    else:                                                        # 2 ulp of the 16-bit result + the fp32 arithmetic that feeds the rounding
-        bound = 2 * _ulp16(ref, dout) + 1e-6 * scale
-    ratio = float((err / bound).max())
-    print(f"{what}: max|err| {float(err.max()):.3e}  err/bound {ratio:.3f}")
-    assert ratio <= 1.0, (what, ratio)
-
-
 @pytest.mark.parametrize("din,dout", [(F32, BF16), (BF16, BF16), (BF16, F32)])
 @pytest.mark.parametrize("C_,act", [(16, ACT_NONE), (64, ACT_GELU), (144, ACT_NONE), (256, ACT_NONE), (1152, ACT_NONE)])
 def test_layernorm_bf16(din, dout, C_, act):

@@ -1,14 +1,15 @@
 """CPU guard on the per-op GPU coverage (tests/op_matrix.py): every dual-built entry point has a bf16 test, every attention kernel family the
 dispatcher can launch has a row in the dispatch matrix, and so has every kernel family and template instance of cvmi_conv2d's dispatcher
-(CONV_ROWS) and every built instance of the three fused YOLO11 kernels (FUSED_ROWS).  Adding an entry point or a kernel without its per-op test
+(CONV_ROWS), every built instance of the three fused YOLO11 kernels (FUSED_ROWS), and every layernorm_kernel instance, SPPF kernel and
+refinement kernel of the helper dispatchers (LN_ROWS, HELPER_ROWS).  Adding an entry point or a kernel without its per-op test
 fails here, on any checkout."""
 import ast
 import glob
 import os
 import re
 
-from op_matrix import (ATTN_ROWS, BF16_OPS, C3K2_INSTANCES, CONV_ROWS, FUSED_MUTANT_ROWS, FUSED_ROWS, SHARE_ROWS, TNAME, c3k2_max_wgs_per_cu, c3k2_tag,
-                       conv_expect)
+from op_matrix import (ATTN_ROWS, BF16_OPS, C3K2_INSTANCES, CONV_ROWS, FUSED_MUTANT_ROWS, FUSED_ROWS, HELPER_ROWS, LN_DUAL_ROWS, LN_FORMS, LN_NCAND, LN_ROWS,
+                       SHARE_ROWS, SPPF_LDS_PIXELS, TNAME, c3k2_max_wgs_per_cu, c3k2_tag, conv_expect, ln_pick, ln_reachable, ln_tag)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(os.path.dirname(HERE), "circuitvision_amd", "csrc")
@@ -317,6 +318,105 @@ def test_fused_matrix_rows_are_well_formed():
             assert r["N1"] % 8 == 0 and 0 <= r["N2"] <= 64, rid
     for mut, rids in FUSED_MUTANT_ROWS.items():
         assert rids and set(rids) <= set(ids), mut
+
+
+# ---- the helper kernels: sam_ops.hip launch_ln / cvmi_upsample_refine, vision_ops.hip cvmi_sppf_pool ---------------------------------------------------
+HELPER_SOURCES = ("sam_ops.hip", "vision_ops.hip")
+LN_PAIRS = [(4, 1), (4, 3), (4, 5), (4, 9), (8, 1), (8, 3), (8, 5), (8, 9), (16, 1), (16, 3), (16, 5), (16, 9), (32, 1), (32, 3), (32, 5), (32, 8), (32, 9),
+            (64, 1), (64, 2), (64, 3), (64, 5), (64, 8), (64, 9)]
+HELPER_TAGS = {"sam_ops.hip": ("layernorm_kernel<%s, %s, %d, %d>", "upsample_refine_fast_kernel", "upsample_refine_kernel<4>"),
+               "vision_ops.hip": ("sppf_pool_lds_kernel<%s>", "sppf_pool_kernel<%s>")}
+
+
+def helper_sources(csrc=CSRC):
+    return {name: open(os.path.join(csrc, name)).read() for name in HELPER_SOURCES}
+
+
+def ln_switch(sources):
+    """(instances of CVMI_LN_SW: the NCH of every case and of the default, the candidate list of launch_ln's selection loop) from sam_ops.hip."""
+    text = sources["sam_ops.hip"]
+    body = re.search(r"#define CVMI_LN_SW\(W\)(.*?)\n  \}\n", text, re.S).group(1)
+    inst = [int(m) for m in re.findall(r"(?:case \d+|default):\s*CVMI_LN\((\d+), W\)", body)]
+    assert all(c == n for c, n in re.findall(r"case (\d+):\s*CVMI_LN\((\d+), W\)", body)), "a case launches another instance than it names"
+    ncand = [int(v) for v in re.search(r"const int ncand\[\d+\] = \{([\d, ]+)\}", text).group(1).split(",")]
+    return inst, ncand
+
+
+def helper_gaps(sources, ln_rows=LN_ROWS, rows=HELPER_ROWS):
+    """What the helper matrix leaves uncovered, as a list of strings (empty = complete)."""
+    gaps = []
+    for name, fmts in HELPER_TAGS.items():
+        gaps += [f"{name} no longer tags its launch as {fmt}" for fmt in fmts if 'cvmi_note_kernel("%s"' % fmt not in sources[name]]
+    inst, ncand = ln_switch(sources)
+    have = {(r["form"], r["G"], r["NCH"]) for r in ln_rows}
+    gaps += [f"layernorm_kernel<.., {n}, ..> has no row" for n in sorted(set(inst) - {h[2] for h in have})]
+    gaps += [f"launch_ln tries NCH = {n}, which CVMI_LN_SW does not build" for n in sorted(set(ncand) - set(inst))]
+    for form in LN_FORMS:
+        gaps += [f"layernorm {form} (G, NCH) = ({G}, {n}) has no row" for G, n in sorted(ln_reachable(ncand)) if (form, G, n) not in have]
+    tags = {r["expect"] for r in rows}
+    for fam in ("sppf_pool_lds_kernel", "sppf_pool_kernel"):
+        gaps += [f"{fam}<{TNAME[dt]}> has no row" for dt in ("f16", "f32") if f"{fam}<{TNAME[dt]}>" not in tags]
+    gaps += [f"{t} has no row" for t in ("upsample_refine_fast_kernel", "upsample_refine_kernel<4>") if t not in tags]
+    sppf = [r for r in rows if r["op"] == "sppf_pool"]
+    for dt, px in SPPF_LDS_PIXELS.items():
+        if not any(r["dtypes"] == (dt,) and r["H"] * r["W"] == px for r in sppf):
+            gaps.append(f"sppf_pool {dt}: no row at the LDS limit of {px} pixels")
+        if not any(r["dtypes"] == (dt,) and px < r["H"] * r["W"] <= px + r["W"] for r in sppf):
+            gaps.append(f"sppf_pool {dt}: no row one image row past the LDS limit of {px} pixels")
+    return gaps
+
+
+def test_ln_pick_mirrors_launch_ln():
+    inst, ncand = ln_switch(helper_sources())
+    assert tuple(ncand) == LN_NCAND and sorted(inst) == sorted(LN_NCAND), (inst, ncand)
+    assert sorted(ln_reachable()) == LN_PAIRS
+    # the widths the older per-op tests run, as the issue that introduced this matrix lists them
+    assert [ln_pick(c, 4)[:2] for c in (16, 64, 144, 256, 1152)] == [(4, 1), (16, 1), (4, 9), (64, 1), (32, 9)]
+    assert [ln_pick(c, 8)[:2] for c in (16, 64, 144, 256, 1152)] == [(4, 1), (8, 1), (4, 5), (32, 1), (16, 9)]
+    assert all(ln_pick(c, s)[1] == 3 for c in (96, 192, 384, 768) for s in (4, 8))        # Hiera-T / S / B+
+    for r in LN_ROWS:                                                      # every row carries what ln_pick says, and G is the smallest that fits NCH
+        slot = LN_FORMS[r["form"]][2]
+        assert (r["G"], r["NCH"], r["waste"]) == ln_pick(r["C"], slot), r["id"]
+        assert r["G"] == min(G for G in (4, 8, 16, 32, 64) if G * r["NCH"] * slot >= r["C"]), r["id"]
+        assert all(ln_tag(r["form"], r["NCH"], dt).startswith("layernorm_kernel<") for dt in r["dtypes"])
+    assert all(r["expect"] == ln_tag("f32_f32", r["NCH"], "f32") for r in LN_DUAL_ROWS)
+
+
+def test_every_helper_kernel_and_layernorm_instance_is_in_the_helper_matrix():
+    src = helper_sources()
+    assert helper_gaps(src) == [], helper_gaps(src)
+    for form in LN_FORMS:                                                  # ... each reachable pair at the smallest width that selects it
+        slot = LN_FORMS[form][2]
+        for (G, n), chunks in ln_reachable().items():
+            assert any(r["form"] == form and r["C"] == chunks[0] * slot and (r["G"], r["NCH"]) == (G, n) for r in LN_ROWS), (form, G, n)
+        for tag in ("rows1", "wg_minus1", "wg_plus1", "waste", "inside", "padgrid", "gelu"):
+            assert {r["NCH"] for r in LN_ROWS if r["form"] == form and r["id"].endswith("_" + tag)} == {3, 2}, (form, tag)
+    assert all(r["dtypes"] == (("f32",) if r["form"] == "f32_f32" else ("f16", "bf16")) for r in LN_ROWS)
+
+
+def test_a_new_layernorm_case_or_a_removed_helper_row_is_caught():
+    src = helper_sources()
+    probe = dict(src)
+    probe["sam_ops.hip"] = probe["sam_ops.hip"].replace("    case 5: CVMI_LN(5, W); break;", "    case 4: CVMI_LN(4, W); break;  \\\n    case 5: CVMI_LN(5, W); break;")
+    assert probe != src and helper_gaps(probe) == ["layernorm_kernel<.., 4, ..> has no row"]
+    probe["sam_ops.hip"] = probe["sam_ops.hip"].replace("ncand[6] = {1, 2, 3, 5, 8, 9}", "ncand[7] = {1, 2, 3, 4, 5, 8, 9}")
+    assert "layernorm f32_f32 (G, NCH) = (64, 4) has no row" in helper_gaps(probe) and "layernorm_kernel<.., 4, ..> has no row" in helper_gaps(probe)
+    for name, fmts in HELPER_TAGS.items():
+        for fmt in fmts:
+            probe = dict(src)
+            probe[name] = probe[name].replace('cvmi_note_kernel("%s"' % fmt, 'note_off("%s"' % fmt)
+            assert helper_gaps(probe) == [f"{name} no longer tags its launch as {fmt}"]
+    for form in LN_FORMS:                                                  # deleting any one (G, NCH) row names it
+        for G, n in LN_PAIRS:
+            rid = next(r["id"] for r in LN_ROWS if r["form"] == form and (r["G"], r["NCH"]) == (G, n) and r["id"].endswith("_min"))
+            left = [r for r in LN_ROWS if r["id"] != rid and not ((r["G"], r["NCH"]) == (G, n) and r["form"] == form)]
+            assert f"layernorm {form} (G, NCH) = ({G}, {n}) has no row" in helper_gaps(src, left)
+    drop = lambda rid: helper_gaps(src, rows=[r for r in HELPER_ROWS if r["id"] != rid])
+    assert drop("sppf_past_lds_limit_f16") == ["sppf_pool f16: no row one image row past the LDS limit of 1024 pixels"]
+    assert drop("sppf_past_lds_limit_f32") == ["sppf_pool_kernel<float> has no row", "sppf_pool f32: no row one image row past the LDS limit of 2048 pixels"]
+    assert drop("sppf_lds_limit_f32") == ["sppf_pool f32: no row at the LDS limit of 2048 pixels"]
+    assert helper_gaps(src, rows=[r for r in HELPER_ROWS if r["expect"] != "upsample_refine_kernel<4>"]) == ["upsample_refine_kernel<4> has no row"]
+    assert helper_gaps(src, rows=[r for r in HELPER_ROWS if r["expect"] != "upsample_refine_fast_kernel"]) == ["upsample_refine_fast_kernel has no row"]
 
 
 def test_the_native_library_reads_no_tuning_switch():
