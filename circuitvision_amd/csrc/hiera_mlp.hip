@@ -20,9 +20,8 @@
 // C = 144 (stage 1): 8 waves / workgroup, two waves per SIMD (the GELU VALU of one overlaps the MFMAs of the other).
 // C = 288 (stage 2): the Y^T accumulator (144 registers) + Xn (76) leave room for one wave per SIMD only: 4 waves.  Its chunk loop is
 // software-pipelined inside the wave and written as asm blocks (VAR 2, below): nobody else is there to fill the matrix pipe while GELU issues.
-#include "common.hpp"
+#include "tok_stream.hpp"
 #include <stdlib.h>
-#include <type_traits>
 
 namespace {
 
@@ -53,22 +52,21 @@ template <int I, int N, typename F> __device__ __forceinline__ void static_for(F
 // VAR 2: one wave per SIMD with the chunk loop software-pipelined inside the wave (see `pipelined chunk loop` in the kernel).  C = 288 runs VAR 2;
 // VAR 0 (the chunk-order loop) is kept as the bit-exact reference of the pipelined loop (CVMI_MLP_PIPE=0, a test hook).
 template <int C, int VAR = 0> struct MlpCfg {
+  static_assert((C == 144 && VAR == 1) || (C == 288 && (VAR == 0 || VAR == 2)), "the instances that are built");
   static constexpr int KS = C / 16;                 // k-steps of fc1
   static constexpr int KS1 = KS + 1;                // + the bias step
   static constexpr int NT = (C + 31) / 32;          // 32-channel output tiles of fc2
   static constexpr int NCH = 4 * C / 32;            // hidden chunks
   static constexpr int FR = KS1 + 2 * NT;           // 1 KiB fragments per chunk
   static constexpr int CHB = FR * 1024;             // bytes per chunk
-  static constexpr int NW = VAR >= 1 ? 4 : (C <= 144 ? 8 : 4);       // waves per workgroup
-  static constexpr int WPS = VAR == 2 ? (C <= 144 ? 2 : 1) : VAR == 1 ? 2 : (C <= 144 ? 2 : 1);      // waves per SIMD the register budget is set for
+  static constexpr int NW = 4;                      // waves per workgroup
+  static constexpr int WPS = VAR == 1 ? 2 : 1;      // waves per SIMD the register budget is set for
   static constexpr int SLOTS = 2;                   // weight ring depth
   static constexpr int CNT = (FR + NW - 1) / NW;    // LDS-DMA instructions every wave issues per chunk (the same count in every wave: counted waits)
   static constexpr int LDS = SLOTS * CHB + 1024;    // + a dump piece for the padding instructions of the waves with fewer real pieces
 };
 
-// DIAG (timing-only builds, -DCVMI_MLP_DIAGS; results are wrong by design): 1 no GELU, 2 no MFMAs, 3 no weight DMA inside the loop, 4 no LDS reads,
-// 5 = 1 + 3 + 4 (MFMAs and barriers only).  A template parameter so that the shipped instantiation's code is untouched.
-template <int C, int VAR = 0, int DIAG = 0>
+template <int C, int VAR = 0>
 __global__ __launch_bounds__((MlpCfg<C, VAR>::NW * 64), (MlpCfg<C, VAR>::WPS)) void hiera_mlp_kernel(float* __restrict__ x, int x_ld, const float* __restrict__ gamma,
                                                                                       const float* __restrict__ beta, float eps,
                                                                                       const char* __restrict__ wp, const float* __restrict__ b2,
@@ -180,7 +178,6 @@ __global__ __launch_bounds__((MlpCfg<C, VAR>::NW * 64), (MlpCfg<C, VAR>::WPS)) v
     //   * dependent MFMAs on one accumulator may follow each other directly.
     static_assert(SLOTS == 2, "two stages in LDS");
     constexpr int PF = 6;
-    constexpr bool NO_GELU = DIAG == 1 || DIAG == 5, NO_MFMA = DIAG == 2, NO_DMA = DIAG == 3 || DIAG == 5, NO_LDS = DIAG == 4 || DIAG == 5;
     f32x16 hA, hB;
     // The PF registers the weight fragments pass through belong to the loop from here to its end ("+v" everywhere: a block reads its fragment and
     // refills the same registers).
@@ -195,7 +192,6 @@ __global__ __launch_bounds__((MlpCfg<C, VAR>::NW * 64), (MlpCfg<C, VAR>::WPS)) v
     asm volatile("" : "+v"(c1v));
     auto gelu_step = [&](f32x16& h, auto kc) {                          // step k = 4 c + s of 16
       constexpr int k = decltype(kc)::value, c = k >> 2;
-      if constexpr (NO_GELU) return;
       GeluPk2Steps& g = gs[c];
       if constexpr ((k & 3) == 0) g.s0(h[4 * c], h[4 * c + 1], h[4 * c + 2], h[4 * c + 3]);
       else if constexpr ((k & 3) == 1) g.s1(c1v);
@@ -215,7 +211,7 @@ __global__ __launch_bounds__((MlpCfg<C, VAR>::NW * 64), (MlpCfg<C, VAR>::WPS)) v
         constexpr int f = decltype(fc)::value;
         u32x4(&ring)[PF] = ring_;                                       // (clang does not capture a variable that only asm operands name)
         const unsigned lbase = lbase_;
-        if constexpr (!NO_LDS) asm volatile("ds_read_b128 %0, %1 offset:%2" : "+v"(ring[f]) : "v"(lbase), "n"(stage_frag<N1, NT>(f) * 1024));
+        asm volatile("ds_read_b128 %0, %1 offset:%2" : "+v"(ring[f]) : "v"(lbase), "n"(stage_frag<N1, NT>(f) * 1024));
       });
       if constexpr (MODE != 0) asm volatile("" : "+v"(hin));          // (hin's last MFMA is >= 18 MFMAs back: no wait needed before GELU reads it)
       static_for<0, NF>([&](auto ic) {
@@ -226,8 +222,8 @@ __global__ __launch_bounds__((MlpCfg<C, VAR>::NW * 64), (MlpCfg<C, VAR>::WPS)) v
         u32x4(&pfw)[2] = pfv;
         u32x4(&xf)[KS1] = xn;
         f32x16(&ya)[NT] = yacc;
-        constexpr int young = NO_LDS ? 15 : ((NF - 1 - i) < (PF - 1) ? (NF - 1 - i) : (PF - 1));
-        constexpr bool refill = i + PF < NF && !NO_LDS;
+        constexpr int young = (NF - 1 - i) < (PF - 1) ? (NF - 1 - i) : (PF - 1);
+        constexpr bool refill = i + PF < NF;
         constexpr int off = refill ? stage_frag<N1, NT>(i + PF) * 1024 : 0;
         if constexpr (i == N1 && MODE != 0) asm volatile("s_nop 1" : "+v"(pfw[0]));            // VALU result -> MFMA operand
         if constexpr (i == N1 + NT && MODE != 0) asm volatile("s_nop 1" : "+v"(pfw[1]));
@@ -237,10 +233,7 @@ __global__ __launch_bounds__((MlpCfg<C, VAR>::NW * 64), (MlpCfg<C, VAR>::WPS)) v
                  : [acc] ACCC(ACC), [a] "+v"(ring[i % PF]) : [b] "v"(B), [lb] "v"(lbase), [n] "n"(young), [off] "n"(off));                             \
   else                                                                                                                                                 \
     asm volatile("s_waitcnt lgkmcnt(%[n])\n\t" CVMI_MFMA_ASM " %[acc], %[a], %[b], " TAIL : [acc] ACCC(ACC), [a] "+v"(ring[i % PF]) : [b] "v"(B), [n] "n"(young))
-        if constexpr (NO_MFMA) {
-          if constexpr (i == 0 && N1 > 0) asm volatile("" : "=v"(ho_));
-          if constexpr (refill) asm volatile("s_waitcnt lgkmcnt(%2)\n\tds_read_b128 %0, %1 offset:%3" : "+v"(ring[i % PF]) : "v"(lbase), "n"(young), "n"(off));
-        } else if constexpr (i < N1) {
+        if constexpr (i < N1) {
           if constexpr (i == 0) { CVMI_MLP_BLK("0", "=&v", ho_, xf[i]); }
           else { CVMI_MLP_BLK("%[acc]", "+v", ho_, xf[i]); }
         } else {
@@ -265,7 +258,7 @@ __global__ __launch_bounds__((MlpCfg<C, VAR>::NW * 64), (MlpCfg<C, VAR>::WPS)) v
       // three slots with the DMA instructions of stage j + 2 spread one by one between this iteration's MFMAs -- 587 us against 580.)
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
-      if (j + 1 < NCH && !NO_DMA) issue_stage(j + 1);
+      if (j + 1 < NCH) issue_stage(j + 1);
       iter(mode, j % SLOTS, hin, hout);
     };
     static_assert(NCH % 2 == 0, "pairs of iterations");
@@ -314,15 +307,7 @@ __global__ __launch_bounds__((MlpCfg<C, VAR>::NW * 64), (MlpCfg<C, VAR>::WPS)) v
     f16x8 pf[2];
 #pragma unroll
     for (int f = 0; f < FR; ++f) {
-      const int young = (FR - 1 - f) < (PF - 1) ? (FR - 1 - f) : (PF - 1);
-      switch (young) {                                         // (compile-time after unrolling)
-        case 0: asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(ring[f % PF])); break;
-        case 1: asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(ring[f % PF])); break;
-        case 2: asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(ring[f % PF])); break;
-        case 3: asm volatile("s_waitcnt lgkmcnt(3)" : "+v"(ring[f % PF])); break;
-        case 4: asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(ring[f % PF])); break;
-        default: asm volatile("s_waitcnt lgkmcnt(5)" : "+v"(ring[f % PF])); break;
-      }
+      ring_wait(ring[f % PF], (FR - 1 - f) < (PF - 1) ? (FR - 1 - f) : (PF - 1));
       const f16x8 a = __builtin_bit_cast(f16x8, ring[f % PF]);
       if (f < KS1) {
         hacc = CVMI_MFMA_32X32X16(a, __builtin_bit_cast(f16x8, xn[f]), hacc, 0, 0, 0);
@@ -344,11 +329,11 @@ __global__ __launch_bounds__((MlpCfg<C, VAR>::NW * 64), (MlpCfg<C, VAR>::WPS)) v
 
   // ---- epilogue: x += y + b2; lane (token lr, half lh) owns channels 32 t + 8 g + 4 lh .. + 3.
   // stats_out: the updated row's LayerNorm statistics (mean, 1 / sqrt(var + stats_eps)) for the launch that normalises it next (the next
-  // block's norm1): shifted sums over this lane's half of the row, the shift being the row's first updated value.
-  float st_shift = 0.f, st_s = 0.f, st_q = 0.f;
+  // block's norm1): shifted sums (tok_stream.hpp) over this lane's half of the row, the shift being the row's first updated value.
+  ShiftedSums st;
   if (stats_out) {
     const float o0 = row_ok ? xr[0] + (yacc[0][0] + b2[0]) : 0.f;       // (the value the lane of half 0 stores at channel 0)
-    st_shift = __shfl(o0, lr);
+    st.shift = __shfl(o0, lr);
   }
   if (row_ok) {
 #pragma unroll
@@ -362,30 +347,25 @@ __global__ __launch_bounds__((MlpCfg<C, VAR>::NW * 64), (MlpCfg<C, VAR>::WPS)) v
 #pragma unroll
           for (int e = 0; e < 4; ++e) o[e] += yacc[t][4 * g + e] + bb[e];
           *reinterpret_cast<f32x4*>(xr + c0) = o;
-          if (stats_out) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { const float dv = o[e] - st_shift; st_s += dv; st_q = fmaf(dv, dv, st_q); }
-          }
+          if (stats_out) st.add(o);
         }
       }
   }
   if (stats_out) {
-    const float ss = st_s + __shfl_xor(st_s, 32), qq = st_q + __shfl_xor(st_q, 32);
-    const float dm = ss / (float)C;
-    const float var = fmaxf(qq / (float)C - dm * dm, 0.f);
-    if (row_ok && lh == 0) *reinterpret_cast<float2*>(stats_out + 2 * row_raw) = make_float2(st_shift + dm, 1.0f / sqrtf(var + stats_eps));
+    const float2 mr = shifted_mean_rstd(st.shift, row_sum<2>(st.s), row_sum<2>(st.q), (float)C, stats_eps);
+    if (row_ok && lh == 0) *reinterpret_cast<float2*>(stats_out + 2 * row_raw) = mr;
   }
 }
 
-template <int C, int VAR = 0, int DIAG = 0>
+template <int C, int VAR = 0>
 int launch_mlp(float* x, int x_ld, const float* gamma, const float* beta, float eps, const void* wp, const float* b2, long long rows, hipStream_t s,
                float* stats_out, float stats_eps) {
   using Cfg = MlpCfg<C, VAR>;
-  static hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&hiera_mlp_kernel<C, VAR, DIAG>), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS);
+  static hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&hiera_mlp_kernel<C, VAR>), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS);
   CVMI_HIP(attr);
   const long long per = (long long)Cfg::NW * 32;
   cvmi_note_kernel("hiera_mlp_kernel<%d, %d>", C, VAR);
-  hipLaunchKernelGGL((hiera_mlp_kernel<C, VAR, DIAG>), dim3((unsigned)((rows + per - 1) / per)), dim3(Cfg::NW * 64), Cfg::LDS, s, x, x_ld, gamma, beta, eps,
+  hipLaunchKernelGGL((hiera_mlp_kernel<C, VAR>), dim3((unsigned)((rows + per - 1) / per)), dim3(Cfg::NW * 64), Cfg::LDS, s, x, x_ld, gamma, beta, eps,
                      (const char*)wp, b2, rows, stats_out, stats_eps);
   CVMI_LAUNCH_CHECK();
   return 0;
@@ -423,12 +403,6 @@ extern "C" int CVMI_ENTRY(cvmi_hiera_mlp_stats)(void* x, int x_ld, const float* 
   hipStream_t s = (hipStream_t)stream_;
   float* xf = (float*)x;
   if (C == 144) return launch_mlp<144, 1>(xf, x_ld, gamma, beta, eps, w_packed, b2, rows, s, ln_stats_out, ln_stats_eps);
-#ifdef CVMI_MLP_DIAGS
-  static const int diag = getenv("CVMI_MLP_DIAG") ? atoi(getenv("CVMI_MLP_DIAG")) : 0;
-#define CVMI_MLP_DIAG_GO(D) if (diag == D) return launch_mlp<288, 2, D>(xf, x_ld, gamma, beta, eps, w_packed, b2, rows, s, ln_stats_out, ln_stats_eps)
-  CVMI_MLP_DIAG_GO(1); CVMI_MLP_DIAG_GO(2); CVMI_MLP_DIAG_GO(3); CVMI_MLP_DIAG_GO(4); CVMI_MLP_DIAG_GO(5);
-#undef CVMI_MLP_DIAG_GO
-#endif
   // Test hook, not a tuning switch: CVMI_MLP_PIPE=0 runs C = 288 on the chunk-order loop (VAR 0), the bit-exact reference the pipelined
   // loop is tested against (tests/test_ops_gpu.py switches it between two launches, so it is read per call).
   const char* const pipe = getenv("CVMI_MLP_PIPE");

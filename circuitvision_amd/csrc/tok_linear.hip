@@ -13,71 +13,38 @@
 // lane = row, registers = 4 consecutive channels per group -> 8-byte fp16 / 16-byte f32 stores.
 // 8 waves per workgroup, 256 rows; the two waves of a SIMD run half a chunk interval apart (ping-pong schedule, below): one in its
 // MFMAs beside the other in its epilogue VALU, stores and weight prefetch.
-#include "common.hpp"
-#include <type_traits>
+#include "tok_stream.hpp"
 
 namespace {
 
-constexpr int TL_NW = 8;
-
 template <int K> struct TlCfg {
+  static_assert(K == 144 || K == 288, "the instances that are built (K = 576: tok_linear16.hip)");
   static constexpr int KS = K / 16, KS1 = KS + 1;
   static constexpr int CHB = KS1 * 1024;                       // bytes per 32-channel weight chunk
-  static constexpr int SLOTS = K <= 288 ? 4 : 3;                // ring depth
-  static constexpr int STG = 32 * 144;                          // per-wave transposition stage of the epilogue: 32 rows x (128 + 16) bytes
-  static constexpr int LDS = SLOTS * CHB + TL_NW * STG;
+  static constexpr int SLOTS = 4;                               // ring depth
+  static constexpr int LDS = SLOTS * CHB + TL_NW * TL_STG;     // + the per-wave stage of the staged store
 };
 
 // LN = 1: `in` is the f32 stream (ld in_ld), normalised with gamma / beta / eps.  LN = 0: `in` is fp16 [rows, in_ld].  LN = 2: f32 rows
 // converted as they are (the neck's lateral convs read the stage outputs of the f32 stream: no cast pass).
 // RES = true: out is f32 (ld out_ld), out[r, n] += y.  RES = false: out is fp16.
-
-// Optional extras of a launch.  pool_*: the POOL form's token grid.  stats_in: LN = 1 only -- per-row (mean, rstd) of the LayerNorm, written by the
-// launch that produced the rows (the prologue then reads every row ONCE instead of twice).  stats_out: RES only -- after the in-place update, the
-// (mean, rstd) over the N updated values of every row, for the LayerNorm (eps = stats_eps) of the NEXT launch.
-struct TlExtra {
-  int pool_w, pool_hw2;
-  const float* stats_in;
-  float* stats_out;
-  float stats_eps;
-  int stats_parts;          // 0: stats_in holds (mean, rstd) per row; P > 0: P raw (sum, sum of squares) partials per row (cvmi_conv_desc.row_stats)
-};
-
 template <int K, int LN, bool RES, bool GELU, bool TSTORE, bool POOL = false>
 __global__ __launch_bounds__(TL_NW * 64, 2) void tok_linear_kernel(const void* __restrict__ in, int in_ld, const float* __restrict__ gamma,
                                                                    const float* __restrict__ beta, float eps, const char* __restrict__ wp,
                                                                    void* __restrict__ out, int out_ld, long long rows, int N, const TlExtra ex) {
   using Cfg = TlCfg<K>;
-  const int pool_w = ex.pool_w, pool_hw2 = ex.pool_hw2;
   constexpr int KS = Cfg::KS, KS1 = Cfg::KS1, CHB = Cfg::CHB, SLOTS = Cfg::SLOTS;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   const int lr = lane & 31, lh = lane >> 5;
-  // rows % 256 == 0 (checked by the host): every row exists.  POOL: lane quad q = lr / 4 holds the four tokens (dy, dx) = ((lr / 2) & 1, lr & 1)
-  // of 2 x 2 block `prow` of the [B, H, W] token grid (pool_w = W, pool_hw2 = (H / 2)(W / 2)); out is the pooled [B, H/2, W/2, N] f32 map.
-  long long row = ((long long)blockIdx.x * TL_NW + wv) * 32 + lr;
-  long long prow = 0;
-  if constexpr (POOL) {
-    prow = row >> 2;
-    const long long b = prow / pool_hw2;
-    const int r = (int)(prow - b * pool_hw2), w2 = pool_w >> 1;
-    const int py = r / w2, px = r - py * w2;
-    row = b * 4 * pool_hw2 + (long long)(2 * py + ((lr >> 1) & 1)) * pool_w + 2 * px + (lr & 1);
-  }
+  // rows % 256 == 0 (checked by the host): every row exists.  POOL: the lane reads the token of its 2 x 2 block (tok_stream.hpp: pool_token);
+  // out is the pooled [B, H/2, W/2, N] f32 map, row prow.
+  const long long wrow0 = ((long long)blockIdx.x * TL_NW + wv) * 32;
+  long long row = wrow0 + lr, prow = 0;
+  if constexpr (POOL) row = pool_token(row, lr, ex, prow);
   const int nch = (N + 31) / 32;
 
-  // chunk j -> ring slot j % SLOTS; wave w moves fragments w, w + 8, ...
-  auto issue_chunk = [&](int j) {
-    const char* src = wp + (size_t)j * CHB + lane * 16;
-    char* dst = smem + (j % SLOTS) * CHB;
-#pragma unroll
-    for (int f = 0; f < (KS1 + TL_NW - 1) / TL_NW; ++f) {
-      const int fi = f * TL_NW + wv;
-      if (fi < KS1)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + (size_t)fi * 1024),
-                                         (__attribute__((address_space(3))) void*)(dst + fi * 1024), 16, 0, 0);
-    }
-  };
+  auto issue_chunk = [&](int j) { tok_issue_chunk<KS1>(wp + (size_t)j * CHB, smem + (j % SLOTS) * CHB, wv, lane); };   // chunk j -> ring slot j % SLOTS
 #pragma unroll
   for (int j = 0; j < SLOTS - 1; ++j)
     if (j < nch) issue_chunk(j);
@@ -96,50 +63,10 @@ __global__ __launch_bounds__(TL_NW * 64, 2) void tok_linear_kernel(const void* _
       xn[k] = __builtin_bit_cast(u32x4, h);
     }
   } else if constexpr (LN == 1) {
-    // Two passes over the row instead of K/2 live f32 registers per lane (K = 576 would need 288 of the 256 available at two
-    // waves per SIMD): pass 1 accumulates sum and sum of squares of (x - x0), x0 = the row's first element (a shift that keeps
-    // the single-pass variance formula well conditioned: what cancels is (mean - x0)^2, bounded by the row's own spread);
-    // pass 2 re-reads the row -- from L1 / L2, the workgroup's 256 rows were touched a few hundred cycles earlier -- and writes
-    // the fp16 fragments.
+    // The statistics first (forwarded, or a pass of their own over the row: tok_stream.hpp), then one pass that writes the fp16 fragments.
     const float* xr = reinterpret_cast<const float*>(in) + row * (long long)in_ld;
-    float mean, rstd;
-    if (ex.stats_in && ex.stats_parts == 0) {                // forwarded by the producer of these rows: pass 1 disappears
-      const float2 st = *reinterpret_cast<const float2*>(ex.stats_in + 2 * row);
-      mean = st.x; rstd = st.y;
-    } else if (ex.stats_in) {                                // per column slice (mean, sum of squared deviations) of a tiled GEMM's epilogue, combined
-      float ms = 0.f, m2 = 0.f;                              // as Chan et al. do (equal slice sizes K / P, fixed order): see tok_linear16.hip
-      for (int t = 0; t < ex.stats_parts; ++t) {
-        const float2 st = *reinterpret_cast<const float2*>(ex.stats_in + (row * ex.stats_parts + t) * 2);
-        ms += st.x; m2 += st.y;
-      }
-      const float inv_p = 1.0f / (float)ex.stats_parts;
-      mean = ms * inv_p;
-      float dev = 0.f;
-      for (int t = 0; t < ex.stats_parts; ++t) {
-        const float d = ex.stats_in[(row * ex.stats_parts + t) * 2] - mean;
-        dev = fmaf(d, d, dev);
-      }
-      rstd = 1.0f / sqrtf(fmaxf((m2 + ((float)K * inv_p) * dev) / (float)K, 0.f) + eps);
-    } else {
-      const float x0 = xr[0];
-      float s = 0.f, q = 0.f;
-#pragma unroll 6
-      for (int k = 0; k < KS; ++k) {
-        const f32x4 a = *reinterpret_cast<const f32x4*>(xr + 16 * k + 8 * lh), b = *reinterpret_cast<const f32x4*>(xr + 16 * k + 8 * lh + 4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float da = a[e] - x0, db = b[e] - x0;
-          s += da + db;
-          q = fmaf(da, da, fmaf(db, db, q));
-        }
-      }
-      s += __shfl_xor(s, 32);
-      q += __shfl_xor(q, 32);
-      const float dm = s / (float)K;                           // mean - x0
-      mean = x0 + dm;
-      const float var = fmaxf(q / (float)K - dm * dm, 0.f);
-      rstd = 1.0f / sqrtf(var + eps);
-    }
+    const float2 st = tok_ln_stats<K, 16, 2>(ex, row, xr, 8 * lh, eps);
+    const float mean = st.x, rstd = st.y;
 #pragma unroll
     for (int k = 0; k < KS; ++k) {
       if (k % 3 == 0) __builtin_amdgcn_sched_barrier(0);      // at most 3 steps' loads in flight: no hoisting of all K/16 of them
@@ -180,26 +107,19 @@ __global__ __launch_bounds__(TL_NW * 64, 2) void tok_linear_kernel(const void* _
       r4[g] = 32 * j + 8 * g + 4 * lh < N ? *reinterpret_cast<const f32x4*>(o + 8 * g) : z;
     }
   };
-  // The accumulator has the row on the lane: written out directly, every lane of a store touches a different cache line (8-byte / 16-byte
-  // pieces, 64 lines per instruction).  TSTORE: the chunk goes through a wave-private LDS stage and leaves as whole 64-byte (16-bit) /
-  // 128-byte (f32) row pieces -- 4 / 8 lanes per row, 16 / 8 rows per instruction.
-  float st_shift = 0.f, st_s = 0.f, st_q = 0.f;               // RES + stats_out: shifted sums over the row's updated values (this lane's half)
-  char* const stage = smem + SLOTS * CHB + wv * Cfg::STG;
-  const long long wrow0 = ((long long)blockIdx.x * TL_NW + wv) * 32;
+  // 16-bit outputs leave through the wave's LDS stage as whole row pieces (TSTORE: tok_stream.hpp, stage_store) or, where N or out_ld
+  // is no multiple of 8, straight from the accumulator layout as 8-byte pieces.
+  ShiftedSums st;                                              // RES + stats_out: over the row's updated values (this lane's half), shift = the first of them
+  char* const stage = smem + SLOTS * CHB + wv * TL_STG;
   auto epilogue = [&](const f32x16& acc, int j) {
     if constexpr (POOL) {
-      // 2 x 2 max over the lane quad (two DPP quad permutes per value: lanes ^ 1, lanes ^ 2), then the quad's first lane stores
+      // 2 x 2 max over the lane quad, then the quad's first lane stores
       float* o = reinterpret_cast<float*>(out) + prow * (long long)out_ld + 32 * j + 4 * lh;
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         f32x4 v;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          float a = acc[4 * g + e];
-          a = fmaxf(a, __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, a), 0xB1, 0xF, 0xF, true)));   // quad_perm [1,0,3,2]
-          a = fmaxf(a, __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, a), 0x4E, 0xF, 0xF, true)));   // quad_perm [2,3,0,1]
-          v[e] = a;
-        }
+        for (int e = 0; e < 4; ++e) v[e] = quad_max(acc[4 * g + e]);
         if ((lr & 3) == 0 && 32 * j + 8 * g + 4 * lh < N) *reinterpret_cast<f32x4*>(o + 8 * g) = v;
       }
     } else if constexpr (RES) {
@@ -210,62 +130,24 @@ __global__ __launch_bounds__(TL_NW * 64, 2) void tok_linear_kernel(const void* _
         f32x4 v = r4[g];
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] += acc[4 * g + e];
-        if (stats && j == 0 && g == 0) st_shift = __shfl(v[0], lr);      // the row's first updated value (held by the lane of half 0): the variance shift
+        if (stats && j == 0 && g == 0) st.shift = __shfl(v[0], lr);      // the row's first updated value (held by the lane of half 0)
         if (32 * j + 8 * g + 4 * lh < N) {
           *reinterpret_cast<f32x4*>(o + 8 * g) = v;
-          if (stats) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { const float dv = v[e] - st_shift; st_s += dv; st_q = fmaf(dv, dv, st_q); }
-          }
+          if (stats) st.add(v);
         }
-      }
-    } else if constexpr (TSTORE) {
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        f16x4 h4;
-        if constexpr (GELU) {
-          const f16x2 lo2 = gelu_fast_pk(acc[4 * g], acc[4 * g + 1]), hi2 = gelu_fast_pk(acc[4 * g + 2], acc[4 * g + 3]);
-          h4 = (f16x4){lo2[0], lo2[1], hi2[0], hi2[1]};
-        } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) h4[e] = (f16)acc[4 * g + e];
-        }
-        *reinterpret_cast<f16x4*>(stage + lr * 80 + (8 * g + 4 * lh) * 2) = h4;
-      }
-      const int sr = lane >> 2, pc = lane & 3;
-      const int c0 = 32 * j + pc * 8;
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const u32x4 v = *reinterpret_cast<const u32x4*>(stage + (16 * i + sr) * 80 + pc * 16);
-        if (c0 < N) *reinterpret_cast<u32x4*>(reinterpret_cast<f16*>(out) + (wrow0 + 16 * i + sr) * (long long)out_ld + c0) = v;
       }
     } else {
       f16* o = reinterpret_cast<f16*>(out) + row * (long long)out_ld + 32 * j + 4 * lh;
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
-        f16x4 h4;
-        if constexpr (GELU) {
-          const f16x2 lo2 = gelu_fast_pk(acc[4 * g], acc[4 * g + 1]), hi2 = gelu_fast_pk(acc[4 * g + 2], acc[4 * g + 3]);
-          h4 = (f16x4){lo2[0], lo2[1], hi2[0], hi2[1]};
-        } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) h4[e] = (f16)acc[4 * g + e];
-        }
-        if (32 * j + 8 * g + 4 * lh < N) *reinterpret_cast<f16x4*>(o + 8 * g) = h4;
+        const f16x4 h4 = tok_pack4<GELU>(acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]);
+        if constexpr (TSTORE) stage_put(stage, lr, 8 * g + 4 * lh, h4);
+        else if (32 * j + 8 * g + 4 * lh < N) *reinterpret_cast<f16x4*>(o + 8 * g) = h4;
       }
+      if constexpr (TSTORE) stage_store(stage, reinterpret_cast<f16*>(out), out_ld, wrow0, j, N, lane);
     }
   };
 
-  auto stats_tail = [&]() {                                    // after the last chunk's epilogue
-    if constexpr (RES) {
-      if (ex.stats_out) {
-        const float ss = st_s + __shfl_xor(st_s, 32), qq = st_q + __shfl_xor(st_q, 32);
-        const float dm = ss / (float)N;
-        const float var = fmaxf(qq / (float)N - dm * dm, 0.f);
-        if (lh == 0) *reinterpret_cast<float2*>(ex.stats_out + 2 * row) = make_float2(st_shift + dm, 1.0f / sqrtf(var + ex.stats_eps));
-      }
-    }
-  };
   constexpr int PF = 8;                         // ring depth
   // The K/16 + 1 MFMAs of chunk j.  A-fragment ring: PF ds_read_b128 stay in flight ahead of the MFMA that consumes them.  The reads and
   // their COUNTED waits are inline asm: left to hipcc the same source becomes read -> lgkmcnt(0) -> MFMA (every MFMA then waits a full LDS
@@ -283,71 +165,21 @@ __global__ __launch_bounds__(TL_NW * 64, 2) void tok_linear_kernel(const void* _
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll
     for (int f = 0; f < KS1; ++f) {
-      const int young = (KS1 - 1 - f) < (PF - 1) ? (KS1 - 1 - f) : (PF - 1);
-      switch (young) {                                         // (f is a compile-time constant after unrolling)
-        case 0: asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(ring[f % PF])); break;
-        case 1: asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(ring[f % PF])); break;
-        case 2: asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(ring[f % PF])); break;
-        case 3: asm volatile("s_waitcnt lgkmcnt(3)" : "+v"(ring[f % PF])); break;
-        case 4: asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(ring[f % PF])); break;
-        case 5: asm volatile("s_waitcnt lgkmcnt(5)" : "+v"(ring[f % PF])); break;
-        case 6: asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(ring[f % PF])); break;
-        default: asm volatile("s_waitcnt lgkmcnt(7)" : "+v"(ring[f % PF])); break;
-      }
+      ring_wait(ring[f % PF], (KS1 - 1 - f) < (PF - 1) ? (KS1 - 1 - f) : (PF - 1));
       const f16x8 a = __builtin_bit_cast(f16x8, ring[f % PF]);
       acc = CVMI_MFMA_32X32X16(a, __builtin_bit_cast(f16x8, xn[f]), acc, 0, 0, 0);
       if (f + PF < KS1) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(ring[f % PF]) : "v"(lbase), "i"((f + PF) * 1024));
     }
     return acc;
   };
-  // ---- ping-pong schedule ------------------------------------------------------------------------------------------------------
-  // The two waves of a SIMD (w and w + 4) share its matrix pipe and its VALU issue.  Under one barrier per chunk both run the same
-  // program in phase -- epilogue beside epilogue, MFMAs beside MFMAs -- and a timer-stamped build (r02) showed what that costs: per chunk
-  // 1325 cycles in the 37 MFMAs, 1254 in epilogue + prefetch issue, and 1827 + 655 waiting (the partner's MFMAs): 5061 cycles for 2 x 1184
-  // cycles of matrix work per SIMD.  Here every chunk interval has TWO barriers and the halves run half an interval apart:
-  //     waves 0-3:  b1 | MFMAs(j)                | b2 | prefetch, epilogue(j)     |
-  //     waves 4-7:  b1 | prefetch, epilogue(j-1) | b2 | MFMAs(j)                  |
-  // so a SIMD always holds one wave in its matrix phase beside one in its VALU / memory phase, and the accumulator of a chunk is
-  // consumed by the phase right after it (no copy).  Ring invariants: chunk c is written to slot c % SLOTS after b1 of interval
-  // c - SLOTS + 1 -- the last reads of chunk c - SLOTS (trailing half, second phase of interval c - SLOTS) ended before that barrier
-  // -- and every wave waits for its own pieces (vmcnt(0), explicit: hipcc puts no wait in front of a barrier for LDS-DMA writes) at
-  // the end of its NEXT matrix phase, at least one barrier before b1 of interval c.  That wait also covers the wave's epilogue stores
-  // and residual loads, all issued a full phase earlier.
-  auto bar = [] {
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-  };
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // chunks 0 .. SLOTS - 2
-  f32x16 acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-  if (wv < TL_NW / 2) {
-#pragma unroll 1
-    for (int j = 0; j < nch; ++j) {
-      bar();
-      if constexpr (RES) res_load(j);
-      acc = mfma_seq(j);
-      asm volatile("s_waitcnt vmcnt(0)" : "+v"(acc) :: "memory");
-      bar();
-      if (j + SLOTS - 1 < nch) issue_chunk(j + SLOTS - 1);
-      epilogue(acc, j);
+  tok_pingpong<RES, SLOTS - 1>(wv < TL_NW / 2, 0, nch, res_load, mfma_seq, issue_chunk, epilogue,
+                               [](f32x16& acc) { asm volatile("s_waitcnt vmcnt(0)" : "+v"(acc) :: "memory"); });
+  if constexpr (RES) {
+    if (ex.stats_out) {                                        // after the last chunk's epilogue
+      const float2 mr = shifted_mean_rstd(st.shift, row_sum<2>(st.s), row_sum<2>(st.q), (float)N, ex.stats_eps);
+      if (lh == 0) *reinterpret_cast<float2*>(ex.stats_out + 2 * row) = mr;
     }
-  } else {
-#pragma unroll 1
-    for (int j = 0; j < nch; ++j) {
-      bar();
-      if (j + SLOTS - 1 < nch) issue_chunk(j + SLOTS - 1);
-      if (j > 0) epilogue(acc, j - 1);
-      if constexpr (RES) res_load(j);
-      bar();
-      acc = mfma_seq(j);
-      asm volatile("s_waitcnt vmcnt(0)" : "+v"(acc) :: "memory");
-    }
-    epilogue(acc, nch - 1);
   }
-  stats_tail();
-
 }
 
 template <int K, int LN, bool RES, bool GELU, bool TSTORE, bool POOL = false>
@@ -376,18 +208,10 @@ int launch_tl(const void* in, int in_ld, const float* gamma, const float* beta, 
 template <int K>
 int dispatch_tl(int ln, bool res, int act, const void* in, int in_ld, const float* gamma, const float* beta, float eps, const void* wp, void* out,
                 int out_ld, long long rows, int N, hipStream_t s, const TlExtra& ex) {
-  const bool gelu = act == CVMI_ACT_GELU;
   if (ln == 2) return launch_tl<K, 2, false, false>(in, in_ld, gamma, beta, eps, wp, out, out_ld, rows, N, s, ex);
-  if (res) {
-    if (ln) return launch_tl<K, 1, true, false>(in, in_ld, gamma, beta, eps, wp, out, out_ld, rows, N, s, ex);
-    return launch_tl<K, 0, true, false>(in, in_ld, gamma, beta, eps, wp, out, out_ld, rows, N, s, ex);
-  }
-  if (ln) {
-    if (gelu) return launch_tl<K, 1, false, true>(in, in_ld, gamma, beta, eps, wp, out, out_ld, rows, N, s, ex);
-    return launch_tl<K, 1, false, false>(in, in_ld, gamma, beta, eps, wp, out, out_ld, rows, N, s, ex);
-  }
-  if (gelu) return launch_tl<K, 0, false, true>(in, in_ld, gamma, beta, eps, wp, out, out_ld, rows, N, s, ex);
-  return launch_tl<K, 0, false, false>(in, in_ld, gamma, beta, eps, wp, out, out_ld, rows, N, s, ex);
+  return tok_dispatch(ln != 0, res, act == CVMI_ACT_GELU, [&](auto LN, auto RES, auto GELU) {
+    return launch_tl<K, decltype(LN)::value, decltype(RES)::value, decltype(GELU)::value>(in, in_ld, gamma, beta, eps, wp, out, out_ld, rows, N, s, ex);
+  });
 }
 
 }  // namespace

@@ -30,22 +30,11 @@ def attention_families(csrc=CSRC):
 
 
 def stray_getenv(sources):
-    """(file, line) of every getenv in {file name: text} other than the two the library keeps: hiera_mlp.hip's per-call read of the
-    CVMI_MLP_PIPE test hook, and reads inside `#ifdef CVMI_MLP_DIAGS` (a timing-only build that never reaches the shipped library)."""
+    """(file, line) of every getenv in {file name: text} other than the one the library keeps: hiera_mlp.hip's per-call read of the
+    CVMI_MLP_PIPE test hook.  No preprocessor block is exempt."""
     hits = []
     for name, text in sorted(sources.items()):
-        diag_depth = 0                                  # > 0: inside #ifdef CVMI_MLP_DIAGS (counting the #if blocks nested in it)
         for no, line in enumerate(text.splitlines(), 1):
-            directive = line.strip()
-            if diag_depth:
-                if directive.startswith("#if"):
-                    diag_depth += 1
-                elif directive.startswith("#endif"):
-                    diag_depth -= 1
-                continue
-            if directive == "#ifdef CVMI_MLP_DIAGS":
-                diag_depth = 1
-                continue
             for m in re.finditer(r"getenv\s*\(([^)]*)\)", line):
                 if not (name == "hiera_mlp.hip" and m.group(1).strip() == '"CVMI_MLP_PIPE"'):
                     hits.append((name, no))
@@ -427,4 +416,4 @@ def test_the_native_library_reads_no_tuning_switch():
     assert stray_getenv(sources) == [], stray_getenv(sources)
     probe = {"x.hip": 'int a = atoi(getenv("CVMI_X"));\n#ifdef CVMI_MLP_DIAGS\n#if 1\n#endif\ngetenv("D");\n#endif\ngetenv ("Y");\n',
              "hiera_mlp.hip": 'getenv("CVMI_MLP_PIPE"); getenv("CVMI_MLP_VAR");\n'}
-    assert stray_getenv(probe) == [("hiera_mlp.hip", 1), ("x.hip", 1), ("x.hip", 7)]
+    assert stray_getenv(probe) == [("hiera_mlp.hip", 1), ("x.hip", 1), ("x.hip", 5), ("x.hip", 7)]

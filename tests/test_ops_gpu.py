@@ -665,12 +665,14 @@ def test_hiera_mlp_pipelined_loop_equals_chunk_order_loop(rows, dt, monkeypatch)
 @pytest.mark.parametrize("K,N,ln,res,act", [(144, 432, True, False, ACT_NONE), (288, 864, True, False, ACT_NONE), (576, 1728, True, False, ACT_NONE),
                                             (576, 2304, True, False, ACT_GELU), (576, 576, False, True, ACT_NONE), (144, 144, False, True, ACT_NONE),
                                             (288, 104, False, False, ACT_GELU), (576, 40, True, True, ACT_NONE), (144, 432, True, False, ACT_GELU), (288, 288, True, True, ACT_NONE),
-                                            (144, 32, "cast", False, ACT_NONE), (288, 64, "cast", False, ACT_NONE)])
+                                            (144, 32, "cast", False, ACT_NONE), (288, 64, "cast", False, ACT_NONE),
+                                            (144, 36, False, False, ACT_GELU), (288, 36, True, False, ACT_NONE)])
 @pytest.mark.parametrize("dt", [F16, BF16])
 def test_tok_linear_vs_torch(K, N, ln, res, act, dt):
     """Token-stationary linear layer (tok_linear.hip): optional fused LayerNorm of the f32 stream on the way in, 16-bit output with
     optional GELU or in-place f32 residual update, N not a multiple of 32 (masked last chunk), vs fp32 torch on weights rounded to the
-    operand type (fp16, or bf16: the -DCVMI_OPERAND_BF16 build of the same kernel)."""
+    operand type (fp16, or bf16: the -DCVMI_OPERAND_BF16 build of the same kernel).  N = 36 is no multiple of 8: the 16-bit output then
+    leaves straight from the accumulator layout (8-byte pieces, a masked last half-chunk) instead of through the LDS stage."""
     import torch.nn.functional as TF
     from circuitvision_amd.engine import TORCH_DTYPE, PackedTokLinear, Rows, op_tok_linear
     td = TORCH_DTYPE[dt]
@@ -795,6 +797,37 @@ def test_tok_linear_forwarded_layernorm_statistics(K, N2, dt):
     ya, yb = out_a.float().cpu(), out_b.float().cpu()
     torch.testing.assert_close(ya, yb, rtol=2e-3 * tol, atol=2e-3 * tol)     # same rows, same statistics up to summation order
     torch.testing.assert_close(ya, y_ref, rtol=6e-3 * tol, atol=6e-3 * tol)
+
+
+@pytest.mark.parametrize("K", [288, 144])
+@pytest.mark.parametrize("dt", [F16, BF16])
+def test_tok_linear_per_slice_layernorm_statistics(K, dt):
+    """Per column slice (mean, sum of squared deviations) pairs as LayerNorm statistics (ln_stats_in_parts = 3), combined as Chan et al., at the
+    K the 32x32x16 kernel serves (tok_linear.hip; K = 576 runs through test_gemm_row_statistics_feed_the_next_layernorm).  The pairs are the
+    float64 moments of the rows' three K / 3 column slices; the first 32 rows sit 500 away from zero (the combination must not lose the
+    variance to cancellation).  Output vs the same launch with the two-pass prologue."""
+    from circuitvision_amd.engine import TORCH_DTYPE, PackedTokLinear, Rows, op_tok_linear
+    td = TORCH_DTYPE[dt]
+    tol = 1.0 if dt == F16 else 8.0
+    rows, N, P = 256, 64, 3
+    g = torch.Generator().manual_seed(K + P)
+    w = quant(torch.randn(N, K, generator=g) / K ** 0.5, dt); b = torch.randn(N, generator=g) * 0.2
+    gam, bet = (torch.rand(K, generator=g) + 0.5).cuda(), (torch.randn(K, generator=g) * 0.2).cuda()
+    x = torch.randn(rows, K, generator=g) * 1.5 + 0.4
+    x[:32] += 500.0
+    sl = x.double().view(rows, P, K // P)
+    mu = sl.mean(2, keepdim=True)
+    parts = torch.stack((mu[..., 0], ((sl - mu) ** 2).sum(2)), 2).float().contiguous().cuda()
+    xd = x.cuda()
+    oa = torch.empty(rows, N, dtype=td, device="cuda"); ob = torch.empty_like(oa)
+    pt = PackedTokLinear(w, b, dtype=dt)
+    plan = Plan(stream())
+    op_tok_linear(plan, "sliced", pt, Rows(xd, rows, K), Rows(oa, rows, N), ln=(gam, bet, 1e-6), stats_in=parts, stats_parts=P)
+    op_tok_linear(plan, "two_pass", pt, Rows(xd, rows, K), Rows(ob, rows, N), ln=(gam, bet, 1e-6))
+    run(plan)
+    ya, yb = oa.float().cpu(), ob.float().cpu()
+    print(f"K={K} dt={dt}: max |sliced - two pass| = {(ya - yb).abs().max().item():.3e}, offset rows {(ya[:32] - yb[:32]).abs().max().item():.3e}")
+    torch.testing.assert_close(ya, yb, rtol=2e-3 * tol, atol=2e-3 * tol)
 
 
 @pytest.mark.parametrize("dt", [F16, BF16])

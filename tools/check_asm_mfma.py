@@ -22,7 +22,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "circuitvision_amd", "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-KERNEL = "hiera_mlp_kernelILi288ELi2ELi0"          # <288, VAR 2, DIAG 0>
+KERNEL = "hiera_mlp_kernelILi288ELi2EE"             # <288, VAR 2>
 MIN_VALU_TO_MFMA, MIN_MFMA_TO_VALU = 2, 12
 # (source, kernel name fragment, MFMAs expected at least, wait states an MFMA result needs before a non-MFMA read: 32x32x16 = 8 passes -> 12,
 #  16x16x32 = 4 passes -> 8 in what hipcc emits for the builtins)
