@@ -246,7 +246,7 @@ extern "C" int cvmi_tok_linear_stats_bf16(const void* in, int in_ld, int in_f32_
 // cvmi_tok_linear with LayerNorm statistics handed from the launch that WRITES the residual stream to the launch that normalises it:
 //   ln_stats_out (out_f32_residual = 1): float2 per row = (mean, 1 / sqrt(var + ln_stats_eps)) over the N updated values of the row
 //   ln_stats_in  (in_f32_layernorm = 1): the same pair per row; the prologue then reads every row once instead of twice.
-//                ln_stats_in_parts = P > 0: instead P raw (sum, sum of squares) pairs per row, as cvmi_conv_desc.row_stats writes them
+//                ln_stats_in_parts = P > 0: instead P per column slice (mean, sum of squared deviations) pairs per row, as cvmi_conv_desc.row_stats writes them
 // (x = x + proj(attn) followed by mlp.layers[0](norm2(x)) in sam2 hieradet MultiScaleBlock; behind /root/reference/src/sam2_infer.py:226).
 extern "C" int CVMI_ENTRY(cvmi_tok_linear_stats)(const void* in, int in_ld, int in_f32_layernorm, const float* gamma, const float* beta, float eps,
                                                  const void* w_packed, void* out, int out_ld, int out_f32_residual, long long rows, int K, int N, int act,

@@ -292,7 +292,8 @@ int cvmi_hiera_mlp_stats(void* x, int x_ld, const float* gamma, const float* bet
  *                      0: out is fp16 (act NONE or GELU)
  * w_packed: ceil(N/32) chunks of (K/16 + 1) MFMA fragments of 1 KiB, fragment (j, s), lane l (r = l & 31, h = l >> 5), element e:
  *   Wx[32 j + r][16 s + 8 h + e],  Wx = [ W | fp16(b) | fp16(b - fp16(b)) | 0 ... ]  (K + 16 columns, rows >= N zero).
- * cvmi_tok_linear_packed_bytes(K, N) = ceil(N/32) * (K/16 + 1) * 1024. */
+ * The chunk count is padded to even (the added chunk is zero): cvmi_tok_linear_packed_bytes(K, N) = 2 ceil(ceil(N/32) / 2) * (K/16 + 1) * 1024
+ * for this format; the 16x16x32 format below is not padded: ceil(N/32) * (K/16 + 1) * 1024. */
 int cvmi_tok_linear_supported(int K);
 size_t cvmi_tok_linear_packed_bytes(int K, int N);
 /* Packed-weight format the library expects for this K: 32 = the layout above (32x32x16 MFMA fragments, bias on an extra k-step);

@@ -20,6 +20,13 @@ options at which a row-per-lane-group kernel goes wrong.
 HELPER_ROWS: the other helper kernels of sam_ops.hip and vision_ops.hip (SPPF pooling, the refinement head, depthwise 3x3, the grid-capped
 copies, bilinear resize / mask post-processing, the mask decoder tail).  Operands, references and tolerances live in tests/helper_ref.py.
 
+TOK_ROWS / MLP_ROWS: the token-stationary path (tok_linear.hip, tok_linear16.hip, hiera_mlp.hip).  One row = one launch through engine.py's wrappers and
+the template instance its dispatcher must tag; tok_pick / tl16_splits / mlp_pick mirror tok_dispatch, launch_tl's staged-store rule, the POOL call
+sites, the K = 576 hand-over and its row-block sharing, and generate TOK_INSTANCES / MLP_INSTANCES.  Operands, references and tolerances live in
+tests/tok_ref.py.  tl16_splits is compared with the library's own answer (cvmi_tok_linear_stats_parts) on the GPU for every N % 32 == 0 of the table;
+its N % 32 != 0 branch is checked by reading only: the library exports the split count through that entry point alone, which always asks for the
+statistics-out form, where a ragged N never splits; the split count is not in the tag.
+
 BF16_OPS: every entry point that common.hpp builds twice (CVMI_ENTRY) -> (test module, test function) that checks its bf16 build per op.
 
 Plain data: importing this module needs neither a GPU nor the library."""
@@ -562,3 +569,214 @@ HELPER_MUTANT_ROWS = {
     "refine_taps_transposed": [r["id"] for r in HELPER_ROWS if r["op"] == "refine" and max(r["ks"]) > 1],
     "dw_tail_reads_next_row": [r["id"] for r in HELPER_ROWS if r["op"] == "dwconv3x3" and r["H"] > 1],
 }
+
+
+# ---- the token-stationary path: tok_linear.hip, tok_linear16.hip, hiera_mlp.hip, tok_stream.hpp ------------------------------------------------
+# TOK_ROWS: one row = one launch of cvmi_tok_linear_stats / cvmi_tok_linear_pool_stats and the instance its dispatcher must tag; MLP_ROWS: one
+# launch of cvmi_hiera_mlp_stats.  Tags carry no operand type: every row runs in fp16 and bf16.  Operands, references and the tolerance live in
+# tests/tok_ref.py.  tok_pick / tl16_splits / mlp_pick mirror the host code (tests/test_op_coverage_cpu.py holds the mirror to the sources' text).
+TOK_KS = (144, 288, 576)
+TOK_FORMAT = {144: 32, 288: 32, 576: 16}          # cvmi_tok_linear_format: the MFMA shape of the packed weights
+TOK_SLOTS = {32: 4, 16: 3}                         # weight ring depth (TlCfg / Tl16Cfg SLOTS); chunks are prefetched SLOTS - 1 ahead
+_BOOL = {False: "false", True: "true"}
+
+
+def tok_dispatch(ln, res, gelu):
+    """tok_stream.hpp tok_dispatch: (LN, RES, GELU) of the instance for a LayerNorm-input / residual-output / GELU request."""
+    if res:
+        return (1, True, False) if ln else (0, True, False)
+    if ln:
+        return (1, False, True) if gelu else (1, False, False)
+    return (0, False, True) if gelu else (0, False, False)
+
+
+def tok_pick(K, ln, res, gelu, N, out_ld, pool=False):
+    """The tag of the launch cvmi_tok_linear_stats (pool: cvmi_tok_linear_pool_stats) ends in.  ln: 0 = 16-bit input, 1 = f32 + LayerNorm,
+    2 = f32 converted as it is."""
+    assert K in TOK_KS and ln in (0, 1, 2) and not (gelu and res) and (ln != 2 or not (res or gelu)), (K, ln, res, gelu)
+    if TOK_FORMAT[K] == 16:
+        assert ln != 2, "plain f32 input is built for K = 144 and 288"
+        if pool:
+            return "tok_linear16_kernel<%d, %d, %s, %s, %s>" % (K, 1, "false", "false", "true")
+        assert res or (N % 8 == 0 and out_ld % 8 == 0), "16-bit output needs N and out_ld multiples of 8"
+        LN, RES, GELU = tok_dispatch(ln != 0, res, gelu)
+        return "tok_linear16_kernel<%d, %d, %s, %s, %s>" % (K, LN, _BOOL[RES], _BOOL[GELU], "false")
+    if pool:
+        return "tok_linear_kernel<%d, %d, %s, %s, %s, %s>" % (K, 1, "false", "false", "false", "true")
+    LN, RES, GELU = (2, False, False) if ln == 2 else tok_dispatch(ln != 0, res, gelu)
+    tstore = not RES and N % 8 == 0 and out_ld % 8 == 0                      # launch_tl
+    return "tok_linear_kernel<%d, %d, %s, %s, %s, %s>" % (K, LN, _BOOL[RES], _BOOL[GELU], _BOOL[tstore], "false")
+
+
+def tl16_splits(rows, N, stats_out):
+    """tok_linear16.hip tl16_splits: workgroups that share one 256-row block of a K = 576 launch."""
+    wg, nch = rows // 256, (N + 31) // 32
+    if wg >= 256 or wg % 8 != 0 or (stats_out and N % 32 != 0):
+        return 1
+    best = 1
+    for ns in range(2, 9):
+        if ns <= nch and nch % ns == 0 and wg * ns <= 256:
+            best = ns
+    return best
+
+
+def mlp_pick(C, pipe=None):
+    """hiera_mlp.hip: C = 144 runs VAR 1, C = 288 VAR 2, or VAR 0 when the CVMI_MLP_PIPE test hook is set without bit 1."""
+    assert C in (144, 288), C
+    if C == 144:
+        return "hiera_mlp_kernel<144, 1>"
+    return "hiera_mlp_kernel<288, %d>" % (0 if pipe is not None and not (int(pipe) & 2) else 2)
+
+
+def _tok_instances():
+    out = set()
+    for K in TOK_KS:
+        out.add(tok_pick(K, 1, False, False, 32, 32, pool=True))
+        for ln in (0, 1) + ((2,) if TOK_FORMAT[K] == 32 else ()):
+            for res, gelu in ((False, False), (False, True), (True, False)):
+                if ln == 2 and (res or gelu):
+                    continue
+                for N, out_ld in ((32, 32), (36, 40), (32, 36)):
+                    if TOK_FORMAT[K] == 32 or res or (N % 8 == 0 and out_ld % 8 == 0):
+                        out.add(tok_pick(K, ln, res, gelu, N, out_ld))
+    return sorted(out)
+
+
+TOK_INSTANCES = _tok_instances()                                            # 26 tok_linear_kernel + 7 tok_linear16_kernel
+MLP_INSTANCES = sorted({mlp_pick(144), mlp_pick(288), mlp_pick(288, "0")})
+TOK_PARTS = (2, 3, 6)                                                       # slice counts of the per-slice statistics rows, at every K
+TOK_SPLIT_TABLE = ((2048, 64, 2), (2048, 96, 3), (2048, 160, 5), (2048, 224, 7), (2048, 256, 8), (2048, 576, 6), (2048, 544, 1), (2048, 40, 2),
+                   (2304, 256, 1), (16384, 256, 4))                         # (rows, N, workgroups per row block) of the K = 576 split rows
+# chunk counts every (K, family) needs: below the prefetch distance, equal to it, equal to SLOTS, one past SLOTS (the first reused slot), more
+TOK_NCH = {32: (1, 2, 3, 4, 5, 9), 16: (1, 2, 3, 4, 7)}
+TOK_NCH_FAMILIES = ("tstore", "direct", "res_ln0", "res_ln1")                # (K = 576 has no direct-store form: its 16-bit rows are all staged)
+
+
+def _tok(tag, K, N, out_ld, ln=0, res=False, gelu=False, rows=256, grid=None, in_ld=None, stats_in=None, stats_out=False, row_off=0, fam="inst", chain=False):
+    """One launch.  ln / res / gelu / grid (pool: (B, H, W)) are the form.  in_ld > K: the input's padding columns hold NaN.  out_ld > N: guard
+    columns hold a sentinel.  stats_in: None, "pair" = forwarded (mean, rstd), or P = per-slice (mean, M2) pairs.  stats_out: the residual form
+    also writes the updated rows' statistics.  row_off: the input is a view that many rows into a larger tensor.  chain: the statistics written are
+    consumed by a second launch (tests/test_tok_matrix_gpu.py).  ns (K = 576): workgroups per row block, what tl16_splits must say."""
+    pool = grid is not None
+    if pool:
+        rows, ln = grid[0] * grid[1] * grid[2], 1
+    in_ld = K if in_ld is None else in_ld
+    form = "pool" if pool else "ln%d%s%s" % (ln, "_res" if res else "", "_gelu" if gelu else "")
+    rid = "k%d_%s_n%d_ld%d_%s" % (K, form, N, out_ld, tag)
+    return dict(id=rid, fam=fam, expect=tok_pick(K, ln, res, gelu, N, out_ld, pool), K=K, N=N, rows=rows, grid=grid, in_ld=in_ld, out_ld=out_ld, ln=ln, res=res,
+                gelu=gelu, pool=pool, stats_in=stats_in, stats_out=stats_out, row_off=row_off, chain=chain, dtypes=F16_BF16,
+                ns=tl16_splits(rows, N, res and stats_out) if TOK_FORMAT[K] == 16 else None)
+
+
+def tok_nch_family(r):
+    """The chunk-count family a row belongs to ("tstore" | "direct" | "res_ln0" | "res_ln1"), or None."""
+    if r["pool"] or r["ln"] == 2:
+        return None
+    if r["res"]:
+        return "res_ln%d" % r["ln"]
+    return "tstore" if r["N"] % 8 == 0 and r["out_ld"] % 8 == 0 else "direct"
+
+
+def _tok_rows():
+    out = []
+    forms16 = ((0, False), (0, True), (1, False), (1, True))
+    for K in TOK_KS:                                                        # ---- every instance, one workgroup
+        f32fmt = TOK_FORMAT[K] == 32
+        for ln, gelu in forms16 + (((2, False),) if f32fmt else ()):
+            out.append(_tok("inst", K, 40, 48, ln=ln, gelu=gelu))            # staged store: two chunks, the last a single 8-column piece
+            if f32fmt:
+                out += [_tok("inst", K, 36, 40, ln=ln, gelu=gelu), _tok("inst", K, 32, 36, ln=ln, gelu=gelu)]      # direct store: by N, by the stride alone
+        out += [_tok("inst", K, 44, 48, ln=ln, res=True) for ln in (0, 1)]
+        out.append(_tok("inst", K, 36, 40, grid=(1, 16, 16)))
+    for K in TOK_KS:                                                        # ---- chunk counts around the ring, ragged and whole last chunks
+        f32fmt = TOK_FORMAT[K] == 32
+        for N in (8, 32, 64, 96, 104, 128, 136, 160, 288) if f32fmt else (8, 32, 64, 96, 104, 128, 200, 224):
+            out.append(_tok("nch", K, N, N + 8, ln=1, gelu=True, fam="nch"))
+            if f32fmt:
+                out.append(_tok("nch", K, N, N + 4, ln=0, fam="nch"))
+            else:
+                out.append(_tok("nch", K, N, N + 8, ln=0, fam="nch"))
+            out += [_tok("nch", K, N, N + 4, ln=ln, res=True, fam="nch") for ln in (0, 1)]
+        if f32fmt:                                                          # N = 144: the residual form's half chunk (tok_linear.hip, res_load)
+            out += [_tok("nch", K, 144, 144, ln=ln, res=True, fam="nch") for ln in (0, 1)]
+    for K in TOK_KS:                                                        # ---- layout: three workgroups, padded NaN input, guards, an offset view
+        pad16, pad32 = K + 8, K + 4
+        out += [_tok("layout", K, 72, 80, ln=0, gelu=True, rows=768, in_ld=pad16, row_off=256, fam="layout"),
+                _tok("layout", K, 72, 80, ln=1, rows=768, in_ld=pad32, row_off=256, fam="layout"),
+                _tok("layout", K, 68, 76, ln=1, res=True, rows=768, in_ld=pad32, row_off=256, stats_out=True, fam="layout"),
+                _tok("layout", K, 68, 76, ln=0, res=True, rows=768, in_ld=pad16, row_off=256, stats_out=True, fam="layout")]
+        if TOK_FORMAT[K] == 32:
+            out += [_tok("layout", K, 72, 80, ln=2, rows=768, in_ld=pad32, row_off=256, fam="layout"),
+                    _tok("layout", K, 68, 76, ln=1, gelu=True, rows=768, in_ld=pad32, row_off=256, fam="layout")]
+    for K in TOK_KS:                                                        # ---- statistics out / in
+        out += [_tok("stats", K, 136, 144, ln=0, res=True, stats_out=True, fam="stats"), _tok("stats", K, K, K, ln=0, res=True, stats_out=True, fam="stats"),
+                _tok("stats", K, 136, 144, ln=1, res=True, stats_out=True, stats_in="pair", fam="stats"),
+                _tok("pair", K, 72, 80, ln=1, gelu=True, stats_in="pair", fam="stats"), _tok("pair", K, 72, 80, ln=1, stats_in="pair", fam="stats")]
+        out += [_tok("parts%d" % P, K, 72, 80, ln=1, stats_in=P, fam="stats") for P in TOK_PARTS]
+        out.append(_tok("parts6", K, 68, 72, ln=1, res=True, stats_in=6, fam="stats"))
+    K = 576                                                                 # ---- K = 576: row blocks shared between workgroups (gridDim.y > 1, j0 != 0)
+    for rows, N, ns in TOK_SPLIT_TABLE:
+        if rows == 2048:
+            out.append(_tok("split%d" % ns, K, N, N + 8, ln=1, gelu=True, rows=rows, fam="split"))
+        else:
+            out.append(_tok("split%d_rows%d" % (ns, rows), K, N, N + 8, ln=0, rows=rows, fam="split"))
+    out += [_tok("split3", K, 96, 100, ln=0, res=True, rows=2048, fam="split"), _tok("split2", K, 40, 44, ln=1, res=True, rows=2048, fam="split"),
+            _tok("split6_parts_out", K, 576, 576, ln=0, res=True, rows=2048, stats_out=True, chain=True, fam="split"),
+            _tok("split1_stats_out", K, 40, 44, ln=0, res=True, rows=2048, stats_out=True, fam="split"),
+            _tok("split3", K, 96, 100, grid=(2, 32, 32), fam="split")]
+    for K in TOK_KS:                                                        # ---- POOL grids: square, half width 3 with B > 1, wide, one pooled row
+        for grid, N, ld in (((1, 16, 16), 64, 64), ((2, 64, 6), 36, 40), ((2, 64, 6), 64, 68), ((3, 8, 32), 36, 40), ((1, 2, 128), 64, 72)):
+            out.append(_tok("grid%dx%dx%d" % grid, K, N, ld, grid=grid, fam="pool"))
+        out.append(_tok("grid2x64x6_pair", K, 36, 40, grid=(2, 64, 6), stats_in="pair", in_ld=K + 4, fam="pool"))
+    return out
+
+
+TOK_ROWS = _tok_rows()
+MLP_ROW_COUNTS = (1, 5, 31, 32, 33, 127, 128, 129, 391)                     # wave (32) and workgroup (128) boundaries; 391: the fourth workgroup's ragged tile
+
+
+def _mlp(C, pipe, rows, stats_out=True, x_ld=None):
+    x_ld = C + 4 if x_ld is None else x_ld
+    tag = mlp_pick(C, pipe)
+    return dict(id="mlp_c%d_v%s_rows%d_ld%d%s" % (C, tag[-2], rows, x_ld, "" if stats_out else "_nostats"), expect=tag, C=C, pipe=pipe, rows=rows, x_ld=x_ld,
+                stats_out=stats_out, dtypes=F16_BF16)
+
+
+MLP_ROWS = [_mlp(C, pipe, rows) for C, pipe in ((144, None), (288, None), (288, "0")) for rows in MLP_ROW_COUNTS] + \
+           [_mlp(C, pipe, rows, stats_out=False) for C, pipe in ((144, None), (288, None), (288, "0")) for rows in (129, 391)] + \
+           [_mlp(C, pipe, 391, x_ld=C) for C, pipe in ((144, None), (288, None), (288, "0"))]
+
+
+def _tok_ids(pred):
+    return [r["id"] for r in TOK_ROWS if pred(r)]
+
+
+def _nch(r):
+    return (r["N"] + 31) // 32
+
+
+# mutant of tests/tok_ref.py -> ids of the rows that must catch it, in every dtype of TOK_MUTANT_DTYPES[mutant] (default: both)
+# (tests/test_tok_ref_cpu.py).  The predicates say where each mistake can show at all.
+TOK_MUTANT_ROWS = {
+    "ring_stale_slot": _tok_ids(lambda r: r["fam"] == "nch" and _nch(r) > TOK_SLOTS[TOK_FORMAT[r["K"]]]),
+    "split_ring_origin": _tok_ids(lambda r: r["fam"] == "split" and (r["ns"] or 1) > 1),
+    "last_piece_dropped": _tok_ids(lambda r: r["fam"] in ("nch", "inst") and r["N"] % 32 != 0),
+    "guard_written": _tok_ids(lambda r: r["fam"] in ("nch", "inst", "layout") and r["N"] % 32 != 0 and r["out_ld"] > r["N"]),
+    "res_overwrite": _tok_ids(lambda r: r["res"]),
+    "ln_no_eps": _tok_ids(lambda r: r["ln"] == 1 and r["stats_in"] is None and r["fam"] in ("inst", "layout", "pool")),
+    "ln_var_n_minus_1": _tok_ids(lambda r: r["ln"] == 1 and r["res"] and r["stats_in"] is None and r["fam"] in ("inst", "nch") and r["K"] == 144),
+    "chan_no_between_term": _tok_ids(lambda r: isinstance(r["stats_in"], int)),
+    "chan_raw_moments": _tok_ids(lambda r: isinstance(r["stats_in"], int)),
+    "stats_over_ld": _tok_ids(lambda r: r["stats_out"] and r["out_ld"] > r["N"]),
+    "pool_dxdy_swapped": _tok_ids(lambda r: r["pool"]),
+    "pool_w_for_hw": _tok_ids(lambda r: r["pool"] and r["grid"][1] != r["grid"][2]),
+    "pool_mean": _tok_ids(lambda r: r["pool"]),
+    "bias_hi_only": _tok_ids(lambda r: r["res"] and r["ln"] == 0 and TOK_FORMAT[r["K"]] == 32 and r["fam"] in ("inst", "nch")),
+    "mlp_rows_past_end": [r["id"] for r in MLP_ROWS if r["rows"] % 128 != 0],
+}
+# ln_var_n_minus_1: a 0.35 % change of rstd (K = 144) is below the bf16 step of the B fragments it feeds (2^-8); the f32 residual form sees it in fp16
+TOK_MUTANT_DTYPES = {"ln_var_n_minus_1": ("f16",)}
+# Mutants the fp64 comparison cannot see on any row, kept in tok_ref.py so that the CPU test records the blind spot with its measurement:
+# mlp_hidden_not_rounded is MORE accurate than the contract by the rounding noise of 4 C hidden values, 0.09 (fp16) / 0.45 (bf16) of the MLP bound,
+# which is set by the GELU form's error.
+TOK_UNSEEN_MUTANTS = {"mlp_hidden_not_rounded": [r["id"] for r in MLP_ROWS if r["rows"] >= 127]}

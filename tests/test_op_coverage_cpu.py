@@ -1,15 +1,18 @@
 """CPU guard on the per-op GPU coverage (tests/op_matrix.py): every dual-built entry point has a bf16 test, every attention kernel family the
 dispatcher can launch has a row in the dispatch matrix, and so has every kernel family and template instance of cvmi_conv2d's dispatcher
 (CONV_ROWS), every built instance of the three fused YOLO11 kernels (FUSED_ROWS), and every layernorm_kernel instance, SPPF kernel and
-refinement kernel of the helper dispatchers (LN_ROWS, HELPER_ROWS).  Adding an entry point or a kernel without its per-op test
-fails here, on any checkout."""
+refinement kernel of the helper dispatchers (LN_ROWS, HELPER_ROWS), and every instance of the token-stationary kernels with the chunk counts,
+split counts, pool grids and statistics forms their rings and index arithmetic need (TOK_ROWS, MLP_ROWS).  Adding an entry point or a kernel
+without its per-op test fails here, on any checkout."""
 import ast
 import glob
 import os
 import re
 
 from op_matrix import (ATTN_ROWS, BF16_OPS, C3K2_INSTANCES, CONV_ROWS, FUSED_MUTANT_ROWS, FUSED_ROWS, HELPER_ROWS, LN_DUAL_ROWS, LN_FORMS, LN_NCAND, LN_ROWS,
-                       SHARE_ROWS, SPPF_LDS_PIXELS, TNAME, c3k2_max_wgs_per_cu, c3k2_tag, conv_expect, ln_pick, ln_reachable, ln_tag)
+                       MLP_INSTANCES, MLP_ROWS, SHARE_ROWS, SPPF_LDS_PIXELS, TNAME, TOK_FORMAT, TOK_INSTANCES, TOK_KS, TOK_MUTANT_ROWS, TOK_NCH, TOK_NCH_FAMILIES,
+                       TOK_PARTS, TOK_ROWS, TOK_SLOTS, TOK_SPLIT_TABLE, TOK_UNSEEN_MUTANTS, c3k2_max_wgs_per_cu, c3k2_tag, conv_expect, ln_pick, ln_reachable,
+                       ln_tag, mlp_pick, tl16_splits, tok_dispatch, tok_nch_family, tok_pick)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(os.path.dirname(HERE), "circuitvision_amd", "csrc")
@@ -417,3 +420,183 @@ def test_the_native_library_reads_no_tuning_switch():
     probe = {"x.hip": 'int a = atoi(getenv("CVMI_X"));\n#ifdef CVMI_MLP_DIAGS\n#if 1\n#endif\ngetenv("D");\n#endif\ngetenv ("Y");\n',
              "hiera_mlp.hip": 'getenv("CVMI_MLP_PIPE"); getenv("CVMI_MLP_VAR");\n'}
     assert stray_getenv(probe) == [("hiera_mlp.hip", 1), ("x.hip", 1), ("x.hip", 5), ("x.hip", 7)]
+
+
+# ---- the token-stationary path: tok_linear.hip, tok_linear16.hip, hiera_mlp.hip, tok_stream.hpp ------------------------------------------------
+TOK_SOURCES = ("tok_linear.hip", "tok_linear16.hip", "hiera_mlp.hip", "tok_stream.hpp")
+TOK_TAGS = {"tok_linear.hip": "tok_linear_kernel<%d, %d, %s, %s, %s, %s>", "tok_linear16.hip": "tok_linear16_kernel<%d, %d, %s, %s, %s>",
+            "hiera_mlp.hip": "hiera_mlp_kernel<%d, %d>"}
+TOK_TAG_ARGS = {"tok_linear.hip": "K, LN, CVMI_BOOLNAME(RES), CVMI_BOOLNAME(GELU), CVMI_BOOLNAME(TSTORE), CVMI_BOOLNAME(POOL)",
+                "tok_linear16.hip": "K, LN, CVMI_BOOLNAME(RES), CVMI_BOOLNAME(GELU), CVMI_BOOLNAME(POOL)", "hiera_mlp.hip": "C, VAR"}
+# launch_tl (tok_linear.hip): the staged store for 16-bit outputs whose N and stride are multiples of 8, the direct store otherwise
+TSTORE_RULE = """  if constexpr (!RES) {
+    if (N % 8 == 0 && out_ld % 8 == 0) return launch_tl1<K, LN, RES, GELU, true>(in, in_ld, gamma, beta, eps, wp, out, out_ld, rows, N, s, ex);
+  }
+  return launch_tl1<K, LN, RES, GELU, false>(in, in_ld, gamma, beta, eps, wp, out, out_ld, rows, N, s, ex);"""
+TL16_SPLITS_BODY = """  const long long wg = rows / 256;
+  const int nch = (N + 31) / 32;
+  if (wg >= 256 || wg % 8 != 0 || (stats_out && N % 32 != 0)) return 1;
+  int best = 1;
+  for (int ns = 2; ns <= 8 && ns <= nch; ++ns)
+    if (nch % ns == 0 && wg * ns <= 256) best = ns;"""
+_DECL = "decltype(LN)::value, decltype(RES)::value, decltype(GELU)::value"
+_B = {"true": True, "false": False}
+
+
+def tok_sources(csrc=CSRC):
+    return {name: open(os.path.join(csrc, name)).read() for name in TOK_SOURCES}
+
+
+def tok_dispatch_forms(sources):
+    """The (LN, RES, GELU) triples tok_dispatch (tok_stream.hpp) can hand to its launcher, from the launch(..) calls of its return statements."""
+    body = re.search(r"int tok_dispatch\(bool ln, bool res, bool gelu, Launch&& launch\) \{(.*?)\n\}", sources["tok_stream.hpp"], re.S).group(1)
+    return [(int(a[2]), b == "yes", c == "yes") for a, b, c in re.findall(r"launch\((ln[01]), (yes|no), (yes|no)\)", body)]
+
+
+def tok_instances(sources):
+    """Tags of every instance the three dispatchers can launch, from their call sites, spelled as their cvmi_note_kernel formats spell them."""
+    tl, t16, mlp = sources["tok_linear.hip"], sources["tok_linear16.hip"], sources["hiera_mlp.hip"]
+    forms = tok_dispatch_forms(sources)
+    nb = lambda v: "true" if v else "false"
+    out = []
+    for K in re.findall(r"dispatch_tl<(\d+)>\(", tl):                       # launch_tl<K, ..> through tok_dispatch, and the ln == 2 branch
+        mine = list(forms) if "launch_tl<K, %s>(" % _DECL in tl else []
+        mine += [(int(l), _B[r], _B[g]) for l, r, g in re.findall(r"launch_tl<K, (\d), (true|false), (true|false)>\(", tl)]
+        for LN, RES, GELU in mine:
+            for ts in ((False,) if RES else (True, False)) if TSTORE_RULE in tl else ():
+                out.append("tok_linear_kernel<%s, %d, %s, %s, %s, false>" % (K, LN, nb(RES), nb(GELU), nb(ts)))
+    for m in re.findall(r"launch_tl1<(\d+), (\d), (true|false), (true|false), (true|false)(?:, (true|false))?>\(", tl):
+        out.append("tok_linear_kernel<%s, %s, %s, %s, %s, %s>" % (m[:5] + (m[5] or "false",)))
+    for K, pool in re.findall(r"launch16<(\d+), %s, (true|false)>\(" % re.escape(_DECL), t16):
+        out += ["tok_linear16_kernel<%s, %d, %s, %s, %s>" % (K, LN, nb(RES), nb(GELU), pool) for LN, RES, GELU in forms]
+    out += ["tok_linear16_kernel<%s, %s, %s, %s, %s>" % m for m in re.findall(r"launch16<(\d+), (\d), (true|false), (true|false), (true|false)>\(", t16)]
+    out += ["hiera_mlp_kernel<%s, %s>" % m for m in re.findall(r"launch_mlp<(\d+), (\d)>\(", mlp)]
+    return out
+
+
+def tok_gaps(sources, rows=TOK_ROWS, mlp_rows=MLP_ROWS):
+    """What the token-path matrix leaves uncovered, as a list of strings (empty = complete)."""
+    gaps = []
+    for name, fmt in TOK_TAGS.items():
+        if 'cvmi_note_kernel("%s", %s)' % (fmt, TOK_TAG_ARGS[name]) not in sources[name]:
+            gaps.append(f"{name} no longer tags its launch as {fmt}")
+    inst, tags = set(tok_instances(sources)), {r["expect"] for r in rows} | {r["expect"] for r in mlp_rows}
+    gaps += [f"{t} has no row" for t in sorted(inst - tags)]
+    gaps += [f"rows expect {t}, which the sources no longer launch" for t in sorted(tags - inst)]
+    for K in TOK_KS:
+        fmt = TOK_FORMAT[K]
+        for fam in TOK_NCH_FAMILIES:
+            if fam == "direct" and fmt == 16:
+                continue
+            have = {(r["N"] + 31) // 32 for r in rows if r["K"] == K and r["rows"] == 256 and tok_nch_family(r) == fam}
+            gaps += [f"K = {K} {fam}: no one-workgroup row with {n} chunks (ring of {TOK_SLOTS[fmt]} slots)" for n in TOK_NCH[fmt] if n not in have]
+        if not any(r["K"] == K and r["pool"] and (r["grid"][2] // 2) & (r["grid"][2] // 2 - 1) for r in rows):
+            gaps.append(f"K = {K}: no POOL row whose half width is no power of two")
+        gaps += [f"K = {K}: no row that takes {P} per-slice statistics" for P in TOK_PARTS if not any(r["K"] == K and r["stats_in"] == P for r in rows)]
+    for ns in sorted({ns for _, _, ns in TOK_SPLIT_TABLE if ns > 1}):
+        if not any(r["ns"] == ns for r in rows):
+            gaps.append(f"K = 576: no row whose row blocks are shared by {ns} workgroups")
+    return gaps
+
+
+def test_tok_pick_mirrors_the_dispatchers():
+    src = tok_sources()
+    tl, t16, mlp = src["tok_linear.hip"], src["tok_linear16.hip"], src["hiera_mlp.hip"]
+    forms = tok_dispatch_forms(src)
+    assert len(forms) == 6 and len(set(forms)) == 5 + 1, forms             # the parser still finds tok_dispatch's launches: three returns, six calls
+    assert set(forms) == {tok_dispatch(ln, res, gelu) for ln in (0, 1) for res, gelu in ((False, False), (False, True), (True, False))}
+    body = re.search(r"int tok_dispatch\(.*?\n\}", src["tok_stream.hpp"], re.S).group(0)
+    assert "if (res) return ln ? launch(ln1, yes, no) : launch(ln0, yes, no);" in body and "if (ln) return gelu ? launch(ln1, no, yes) : launch(ln1, no, no);" in body \
+        and "return gelu ? launch(ln0, no, yes) : launch(ln0, no, no);" in body
+    assert TSTORE_RULE in tl and tl.count("launch_tl1<K, LN, RES, GELU,") == 2          # launch_tl's rule, as tok_pick states it
+    assert "if (ln == 2) return launch_tl<K, 2, false, false>(" in tl and "return tok_dispatch(ln != 0, res, act == CVMI_ACT_GELU," in tl
+    assert "if (K == 144) return dispatch_tl<144>(" in tl and "return dispatch_tl<288>(" in tl and "if (tl_format(K) == 16)" in tl
+    assert "static int tl_format(int K) { return K == 576 ? 16 : 32; }" in tl
+    assert "if (K == 144) return launch_tl1<144, 1, false, false, false, true>(" in tl and "return launch_tl1<288, 1, false, false, false, true>(" in tl
+    assert "if (pool_w > 0) return launch16<576, 1, false, false, true>(" in t16 and "return tok_dispatch(ln != 0, res, gelu," in t16
+    assert 'CVMI_CHECK(res || (N % 8 == 0 && out_ld % 8 == 0), "tok_linear (16x16x32 format)' in t16
+    assert TL16_SPLITS_BODY in t16 and "const int ns = tl16_splits(rows, N, RES && ex.stats_out != nullptr);" in t16
+    assert "int CVMI_ENTRY(cvmi_tok_linear16_splits)(long long rows, int N) { return tl16_splits(rows, N, true); }" in t16
+    assert "if (C == 144) return launch_mlp<144, 1>(" in mlp and "if (pipe && !(atoi(pipe) & 2)) return launch_mlp<288, 0>(" in mlp and "return launch_mlp<288, 2>(" in mlp
+    assert "static constexpr int SLOTS = 4;" in tl and "static constexpr int SLOTS = 3;" in t16 and "tok_pingpong<RES, SLOTS - 1>(" in tl and "tok_pingpong<RES, SLOTS - 1>(" in t16
+    assert TOK_SLOTS == {32: 4, 16: 3}
+    inst = tok_instances(src)
+    assert len(inst) == len(set(inst)), inst
+    assert [sum(t.startswith(f) for t in inst) for f in ("tok_linear_kernel<", "tok_linear16_kernel<", "hiera_mlp_kernel<")] == [26, 7, 3], inst   # the parser still finds the call sites
+    assert sorted(t for t in inst if t.startswith("tok_linear")) == TOK_INSTANCES and sorted(t for t in inst if t.startswith("hiera")) == MLP_INSTANCES
+    assert [mlp_pick(144), mlp_pick(288), mlp_pick(288, "0"), mlp_pick(288, "2"), mlp_pick(288, "1")] == \
+        ["hiera_mlp_kernel<144, 1>", "hiera_mlp_kernel<288, 2>", "hiera_mlp_kernel<288, 0>", "hiera_mlp_kernel<288, 2>", "hiera_mlp_kernel<288, 0>"]
+    assert [tl16_splits(rows, N, False) for rows, N, _ in TOK_SPLIT_TABLE] == [ns for _, _, ns in TOK_SPLIT_TABLE]
+    assert tl16_splits(2048, 40, True) == 1 and tl16_splits(2048, 576, True) == 6 and tl16_splits(65536, 576, True) == 1 and tl16_splits(32768, 576, True) == 2
+
+
+def test_every_token_path_instance_is_in_the_matrix():
+    assert tok_gaps(tok_sources()) == [], tok_gaps(tok_sources())
+
+
+def test_a_new_token_path_instance_or_a_removed_row_is_caught():
+    src = tok_sources()
+    probe = dict(src)
+    probe["tok_linear.hip"] += "\n  if (res && gelu) return launch_tl1<144, 1, true, true, false>(in, in_ld, gamma, beta, eps, wp, out, out_ld, rows, N, s, ex);\n"
+    assert tok_gaps(probe) == ["tok_linear_kernel<144, 1, true, true, false, false> has no row"]
+    probe = dict(src)
+    probe["hiera_mlp.hip"] += "\n  return launch_mlp<288, 1>(xf, x_ld, gamma, beta, eps, w_packed, b2, rows, s, ln_stats_out, ln_stats_eps);\n"
+    assert tok_gaps(probe) == ["hiera_mlp_kernel<288, 1> has no row"]
+    for name, fmt in TOK_TAGS.items():
+        probe = dict(src)
+        probe[name] = probe[name].replace('cvmi_note_kernel("%s"' % fmt, 'note_off("%s"' % fmt)
+        assert probe != src and tok_gaps(probe) == [f"{name} no longer tags its launch as {fmt}"]
+    probe = dict(src)
+    probe["tok_linear.hip"] = probe["tok_linear.hip"].replace("N % 8 == 0 && out_ld % 8 == 0) return launch_tl1", "N % 16 == 0 && out_ld % 8 == 0) return launch_tl1")
+    assert len(tok_gaps(probe)) == 24 and all("which the sources no longer launch" in g for g in tok_gaps(probe))       # the rule's text is part of the mirror
+    drop = lambda *rids: tok_gaps(src, [r for r in TOK_ROWS if r["id"] not in rids], [r for r in MLP_ROWS if r["id"] not in rids])
+    assert drop("k144_ln1_gelu_n40_ld48_inst") == []                      # (the chunk-count rows launch this instance too)
+    assert drop("k288_ln2_n36_ld40_inst", "k288_ln2_n32_ld36_inst") == ["tok_linear_kernel<288, 2, false, false, false, false> has no row"]
+    assert drop("k288_ln0_n136_ld140_nch", "k288_ln0_n160_ld164_nch") == ["K = 288 direct: no one-workgroup row with 5 chunks (ring of 4 slots)"]
+    assert drop("k576_ln1_res_n128_ld132_nch", "k576_ln1_res_n104_ld108_nch") == ["K = 576 res_ln1: no one-workgroup row with 4 chunks (ring of 3 slots)"]
+    assert drop("k576_ln1_gelu_n224_ld232_split7") == ["K = 576: no row whose row blocks are shared by 7 workgroups"]
+    assert drop(*[r["id"] for r in TOK_ROWS if r["K"] == 144 and r["grid"] == (2, 64, 6)]) == ["K = 144: no POOL row whose half width is no power of two"]
+    assert drop("k288_ln1_n72_ld80_parts3") == ["K = 288: no row that takes 3 per-slice statistics"]
+    assert drop(*[r["id"] for r in MLP_ROWS if r["expect"] == "hiera_mlp_kernel<288, 0>"]) == ["hiera_mlp_kernel<288, 0> has no row"]
+
+
+def test_token_path_rows_are_well_formed():
+    ids = [r["id"] for r in TOK_ROWS] + [r["id"] for r in MLP_ROWS]
+    assert len(ids) == len(set(ids)), "duplicate row ids"
+    for r in TOK_ROWS:
+        rid, K, N = r["id"], r["K"], r["N"]
+        assert r["dtypes"] == ("f16", "bf16") and r["fam"] in ("inst", "nch", "layout", "stats", "split", "pool"), rid
+        assert r["rows"] % 256 == 0 and (r["rows"] <= 2304 or rid == "k576_ln0_n256_ld264_split4_rows16384"), rid   # (2304: nine row blocks)
+        assert r["in_ld"] >= K and r["in_ld"] % (4 if r["ln"] else 8) == 0 and r["out_ld"] >= N and r["out_ld"] % 4 == 0 and N % 4 == 0, f"{rid}: the alignment contract"
+        assert TOK_FORMAT[K] == 32 or r["res"] or r["pool"] or (N % 8 == 0 and r["out_ld"] % 8 == 0), f"{rid}: K = 576 16-bit outputs in 16-byte pieces"
+        assert r["expect"] == tok_pick(K, r["ln"], r["res"], r["gelu"], N, r["out_ld"], r["pool"]) and r["expect"] in TOK_INSTANCES, rid
+        assert r["ns"] == (tl16_splits(r["rows"], N, r["res"] and r["stats_out"]) if TOK_FORMAT[K] == 16 else None), rid
+        assert r["stats_in"] in (None, "pair") + TOK_PARTS and (r["stats_in"] is None or r["ln"] == 1) and (not r["stats_out"] or r["res"]), rid
+        assert not isinstance(r["stats_in"], int) or K % r["stats_in"] == 0, rid
+        assert r["row_off"] % 256 == 0 and (not r["chain"] or (r["stats_out"] and r["ns"] > 1 and K == N == r["out_ld"])), rid
+        if r["pool"]:
+            B, H, W = r["grid"]
+            assert H % 2 == 0 and W % 2 == 0 and B * H * W == r["rows"] and r["ln"] == 1 and not (r["res"] or r["gelu"] or r["stats_out"] or r["row_off"]), rid
+        else:
+            assert r["grid"] is None, rid
+    for rows, N, ns in TOK_SPLIT_TABLE:                                      # every split the table claims has its row, and the chain row writes 6 parts
+        assert any(r["K"] == 576 and (r["rows"], r["N"], r["ns"]) == (rows, N, ns) for r in TOK_ROWS), (rows, N, ns)
+    assert [r["ns"] for r in TOK_ROWS if r["chain"]] == [6] and any(r["stats_out"] and r["ns"] == 1 and r["rows"] == 2048 and r["N"] == 40 for r in TOK_ROWS)
+    assert any(r["pool"] and r["ns"] == 3 for r in TOK_ROWS)
+    for K in TOK_KS:                                                        # layout: three workgroups, padded input behind an offset view, guards; statistics out at N = 136 and N = K
+        lay = [r for r in TOK_ROWS if r["K"] == K and r["fam"] == "layout"]
+        assert lay and all(r["rows"] == 768 and r["in_ld"] == K + (4 if r["ln"] else 8) and r["row_off"] > 0 and r["out_ld"] > r["N"] for r in lay), K
+        assert {(r["ln"], r["res"]) for r in lay} >= {(0, False), (1, False), (0, True), (1, True)} and any(r["stats_out"] for r in lay), K
+        assert {(r["N"], r["out_ld"]) for r in TOK_ROWS if r["K"] == K and r["stats_out"] and r["fam"] == "stats"} == {(136, 144), (K, K)}, K
+        assert any(r["K"] == K and r["stats_in"] == "pair" and not r["pool"] for r in TOK_ROWS) and any(r["K"] == K and r["stats_in"] == "pair" and r["pool"] for r in TOK_ROWS), K
+        assert {r["grid"] for r in TOK_ROWS if r["K"] == K and r["fam"] == "pool"} == {(1, 16, 16), (2, 64, 6), (3, 8, 32), (1, 2, 128)}, K
+        if TOK_FORMAT[K] == 32:
+            assert {r["ln"] for r in TOK_ROWS if r["K"] == K and r["N"] == 144 and r["res"] and r["fam"] == "nch"} == {0, 1}, f"K = {K}: the residual form's half chunk"
+    for r in MLP_ROWS:
+        assert r["expect"] == mlp_pick(r["C"], r["pipe"]) and r["expect"] in MLP_INSTANCES and r["x_ld"] >= r["C"] and r["x_ld"] % 4 == 0 and r["dtypes"] == ("f16", "bf16"), r["id"]
+    for tag in MLP_INSTANCES:
+        mine = [r for r in MLP_ROWS if r["expect"] == tag]
+        assert {r["rows"] for r in mine if r["stats_out"] and r["x_ld"] > r["C"]} == {1, 5, 31, 32, 33, 127, 128, 129, 391}, tag
+        assert any(not r["stats_out"] for r in mine) and any(r["x_ld"] == r["C"] for r in mine), tag
+    for mut, rids in list(TOK_MUTANT_ROWS.items()) + list(TOK_UNSEEN_MUTANTS.items()):
+        assert rids and set(rids) <= set(ids), mut
