@@ -49,6 +49,20 @@ LORA_TARGETS_REFERENCE = (
     + [f"sam_mask_decoder.transformer.layers.{l}.cross_attn_image_to_token.{p}" for l in (0, 1) for p in ("q_proj", "k_proj", "v_proj")])
 
 
+# upstream PromptEncoder.mask_downscaling (mask_in_chans = 16): Conv2d(1,4,2,2) LayerNorm2d GELU Conv2d(4,16,2,2) LayerNorm2d GELU Conv2d(16,256,1)
+MASK_DOWN = "sam_prompt_encoder.mask_downscaling"
+MASK_DOWN_PARAMS = 4684                          # include/cvmi355.h CVMI_MASK_PROMPT_PARAMS
+
+
+def mask_down_tensors():
+    """(state-dict key, shape, synthetic kind) of the stack's ten tensors, in the order cvmi_mask_prompt_embed's parameter vector packs them."""
+    return [(f"{MASK_DOWN}.0.weight", (4, 1, 2, 2), "w"), (f"{MASK_DOWN}.0.bias", (4,), "w"),
+            (f"{MASK_DOWN}.1.weight", (4,), "gamma"), (f"{MASK_DOWN}.1.bias", (4,), "w"),
+            (f"{MASK_DOWN}.3.weight", (16, 4, 2, 2), "w"), (f"{MASK_DOWN}.3.bias", (16,), "w"),
+            (f"{MASK_DOWN}.4.weight", (16,), "gamma"), (f"{MASK_DOWN}.4.bias", (16,), "w"),
+            (f"{MASK_DOWN}.6.weight", (256, 16, 1, 1), "w"), (f"{MASK_DOWN}.6.bias", (256,), "w")]
+
+
 # ---- parameter sources ---------------------------------------------------------------------------------
 class SamSyntheticParams:
     """Seeded synthetic weights in the fine-tuned checkpoint's own key format (PEFT names for LoRA
@@ -56,11 +70,13 @@ class SamSyntheticParams:
 
     def __init__(self, seed=0, lora_targets=LORA_TARGETS_REFERENCE, r=4, alpha=16, std=0.02):
         self.seed, self.targets, self.r, self.scaling, self.std, self.sd = seed, set(lora_targets), r, alpha / r, std, {}
+        self.mask_sd = {}              # sam_prompt_encoder.mask_downscaling.*: kept apart, `state_dict()` stays what the oracle loads strictly
 
     def _t(self, name, shape, kind="w"):
-        if name in self.sd:
-            assert tuple(self.sd[name].shape) == tuple(shape), (name, self.sd[name].shape, shape)
-            return self.sd[name]
+        sd = self.mask_sd if name.startswith(MASK_DOWN + ".") else self.sd
+        if name in sd:
+            assert tuple(sd[name].shape) == tuple(shape), (name, sd[name].shape, shape)
+            return sd[name]
         h = int.from_bytes(hashlib.sha256(f"{self.seed}:{name}".encode()).digest()[:8], "little") & 0x7FFFFFFFFFFFFFFF
         g = torch.Generator().manual_seed(h)
         if kind == "gamma":
@@ -71,7 +87,7 @@ class SamSyntheticParams:
             t = torch.empty(shape).normal_(0, 0.2, generator=g)
         else:
             t = torch.empty(shape).normal_(0, self.std, generator=g).clamp_(-2 * self.std, 2 * self.std)
-        self.sd[name] = t
+        sd[name] = t
         return t
 
     def weight(self, mod, shape):
@@ -94,6 +110,13 @@ class SamSyntheticParams:
 
     def state_dict(self):
         return dict(self.sd)
+
+    def mask_prompt_state_dict(self):
+        """The ten tensors of `sam_prompt_encoder.mask_downscaling` (mask prompts, `infer_masks(mask_input=...)`) under their upstream
+        names.  Not part of `state_dict()`: the oracle restates the prompt encoder without that stack."""
+        for name, shape, kind in mask_down_tensors():
+            self._t(name, shape, kind)
+        return dict(self.mask_sd)
 
 
 class SamBlankParams:
@@ -310,12 +333,23 @@ class Sam2Weights:
             no_mask = self.p.tensor(f"{PE}.no_mask_embed.weight", (1, 256), "unit")[0]
             no_mem = self.p.tensor("no_mem_embed", (1, 1, 256), "unit").reshape(256)
         except KeyError:
-            self.prompt_ok = False                  # a checkpoint stripped of the prompt encoder: learned-prompt path only
+            self.prompt_ok = self.mask_prompt_ok = False      # a checkpoint stripped of the prompt encoder: learned-prompt path only
             return
         self.prompt_ok = True
         self._pack("embed_box", _lin(torch.cat((wn[1], wn[0]), 1)), bn[1] + bn[0] + no_mask + no_mem)
         self.const["prompt_table"] = table.float().contiguous().to(self.device)
         self.const["gauss"] = G.float().contiguous().to(self.device)
+        # mask prompts (`infer_masks(mask_input=...)`): mask_downscaling packed for cvmi_mask_prompt_embed.  The last bias carries
+        # - no_mask_embed: the embed GEMM above keeps its bias, and a masked pair's dense prompt REPLACES no_mask_embed
+        try:
+            parts = [self.p.tensor(name, shape, kind).float().reshape(-1) for name, shape, kind in mask_down_tensors()]
+        except KeyError:
+            self.mask_prompt_ok = False             # a checkpoint stripped of mask_downscaling: boxes and clicks only
+            return
+        self.mask_prompt_ok = True
+        parts[-1] = parts[-1] - no_mask.float()
+        self.const["mask_down"] = torch.cat(parts).contiguous().to(self.device)
+        assert self.const["mask_down"].numel() == MASK_DOWN_PARAMS
 
     def _attn(self, key, mod, inner, q_pe=None, k_pe=None):
         """One Attention module.  q / k / v projections packed separately; constants (x + pe) W^T folded."""
@@ -426,9 +460,14 @@ class Sam2Plan:
     prompts = 0: the reference's learned-prompt wrapper forward (one mask per image, sam2_infer.py:220-275).
     prompts = P > 0: upstream prompting, P prompts of `points` labelled points per image (a box = 2 corners + 1
     padding point); the caller fills `coords` [B*P, points, 2] / `labels` [B*P, points] before each run and the decoder
-    runs on B*P (image, prompt) pairs, image-major (MaskDecoder repeat_image=True); outputs are [B*P, 1, ...]."""
+    runs on B*P (image, prompt) pairs, image-major (MaskDecoder repeat_image=True); outputs are [B*P, 1, ...].
+    mask_prompt (prompts > 0): every pair also carries a mask prompt, low-res logits the caller writes to `mask_in` [B*P, R/4, R/4]
+    before each run (upstream `mask_input`); the image stream then differs per pair from the start, so layer 0 runs unshared.
+    multimask (prompts > 0): upstream multimask_output=True -- mask tokens 1..3 and their IoU heads in token order, no stability
+    fallback; outputs are [B*P, 3, ...]."""
 
-    def __init__(self, wt, B, stream, dynamic_multimask_via_stability=True, prompts=0, points=3, high_res=True, attn="16"):
+    def __init__(self, wt, B, stream, dynamic_multimask_via_stability=True, prompts=0, points=3, high_res=True, attn="16", mask_prompt=False,
+                 multimask=False):
         """attn = "fp8" (16-bit plans only; BASELINE configs[4]): the AV contraction of Hiera's 256-key windows and global blocks runs on the
         block-scaled fp8 MFMA (cvmi_attn_desc.av_fp8); "16": operands in the plan's 16-bit type (default)."""
         self.wt, self.B, self.dt, self.dev = wt, B, wt.dtype, wt.device
@@ -439,6 +478,11 @@ class Sam2Plan:
         self.P, self.K, self.want_high_res = prompts, points, high_res
         if prompts and not wt.prompt_ok:
             raise _lib.CvmiError("this checkpoint carries no sam_prompt_encoder tensors: box / point prompts are unavailable")
+        if (mask_prompt or multimask) and not prompts:
+            raise ValueError("mask_prompt / multimask need prompts > 0 (the learned-prompt wrapper always runs single-mask without a mask input)")
+        if mask_prompt and not wt.mask_prompt_ok:
+            raise _lib.CvmiError("this checkpoint carries no sam_prompt_encoder.mask_downscaling tensors: mask prompts are unavailable")
+        self.mask_prompt, self.multimask = bool(mask_prompt), bool(multimask)
         self.plan = Plan(stream)
         self.pool = {}
         self.dynamic = dynamic_multimask_via_stability
@@ -637,8 +681,18 @@ class Sam2Plan:
             # embedding: in fp16 mode layer 0 reads the B shared copies (k / v and q projections on B images instead of B * P,
             # attention kernels index the shared batch entry, the first residual add broadcasts) and the repeat pass disappears.
             # f32 parity mode keeps the literal repeat_image formulation (upstream MaskDecoder.predict_masks) as the cross-check.
-            self.share_l0 = is16(dt) and os.environ.get("CVMI_SAM_SHARE_L0", "1") != "0"
-            if not self.share_l0:
+            # A mask prompt makes the image stream differ per pair from the start (nothing to share): one launch writes
+            # keys = emb + mask_downscaling(mask_in) - no_mask_embed where the repeat pass stands, and in 16-bit mode the operand copy too.
+            self.share_l0 = is16(dt) and os.environ.get("CVMI_SAM_SHARE_L0", "1") != "0" and not self.mask_prompt
+            if self.mask_prompt:
+                self.mask_in = torch.zeros(NB, f0, f0, dtype=torch.float32, device=self.dev)
+                kn0 = bufd(fs, fs, 256, tag="kn") if is16(dt) else None
+                op_call(self.plan, "mask_prompt_embed", "decoder", lib.cvmi_mask_prompt_embed,
+                        (self.mask_in.data_ptr(), emb.t.data_ptr(), wt.const["mask_down"].data_ptr(), keys.t.data_ptr(),
+                         kn0.t.data_ptr() if kn0 is not None else None, dt if kn0 is not None else F16, B, NP, fs),
+                        keep=(emb, keys, kn0), bytes_=NB * f0 * f0 * 4 + (B + NB) * P * 256 * 4 + (NB * P * 256 * 2 if kn0 is not None else 0),
+                        flops=2 * NB * P * (16 * 4 + 16 * 16 + 256 * 16))
+            elif not self.share_l0:
                 op_call(self.plan, "repeat_embed", "decoder", lib.cvmi_repeat_images, (emb.t.data_ptr(), keys.t.data_ptr(), P * 256 * 4, B, NP),
                         keep=(emb, keys), bytes_=(B + NB) * P * 256 * 4)
             T = 6 + self.K
@@ -699,7 +753,7 @@ class Sam2Plan:
                 op_cast(self.plan, f"{p}.t2i.castk", emb.view(), kn_l.view())
             else:
                 kn_l = kn
-                if l == 0 or not dual:
+                if not dual or (l == 0 and not self.mask_prompt):        # (16-bit mask prompts: mask_prompt_embed has written kn)
                     op_cast(self.plan, f"{p}.t2i.castk", keys.view(), kn.view())
             tq = bufd(1, T, 128, tag="t2i_q")
             G(f"{p}.t2i.q", f"{p}.t2i.q", qn.view(), tq.view(), **tpe(f"{p}.t2i.q_pe", 128))
@@ -769,19 +823,24 @@ class Sam2Plan:
         P0 = f0 * f0
         self.masks4 = torch.empty(NB, 4, f0, f0, dtype=torch.float32, device=self.dev)
         self.areas = torch.zeros(NB, 2, dtype=torch.int32, device=self.dev)
-        self.low_res = torch.empty(NB, 1, f0, f0, dtype=torch.float32, device=self.dev)
-        self.iou = torch.empty(NB, 1, dtype=torch.float32, device=self.dev)
+        NM = 3 if self.multimask else 1                  # masks returned per pair
+        self.low_res = torch.empty(NB, NM, f0, f0, dtype=torch.float32, device=self.dev)
+        self.iou = torch.empty(NB, NM, dtype=torch.float32, device=self.dev)
         self.sel = torch.zeros(NB, dtype=torch.int32, device=self.dev)
         op_call(self.plan, "hyper_masks", "tail", lib.cvmi_hyper_masks,
                 (hyper.t.data_ptr(), 32, u2.t.data_ptr(), 32, dt, 32, self.masks4.data_ptr(), self.areas.data_ptr(), NB, P0, 0.05),
                 keep=(hyper, u2), bytes_=NB * P0 * (32 * ESIZE[dt] + 16), flops=2 * NB * P0 * 128)
-        op_call(self.plan, "select_mask", "tail", lib.cvmi_select_mask,
-                (self.masks4.data_ptr(), self.areas.data_ptr(), iou4.t.data_ptr(), 4, 1 if self.dynamic else 0, 0.98, self.low_res.data_ptr(),
-                 self.iou.data_ptr(), self.sel.data_ptr(), NB, P0), bytes_=NB * P0 * 8)
+        if self.multimask:
+            op_call(self.plan, "multimask_out", "tail", lib.cvmi_multimask_out,
+                    (self.masks4.data_ptr(), iou4.t.data_ptr(), 4, self.low_res.data_ptr(), self.iou.data_ptr(), NB, P0), bytes_=NB * P0 * 24)
+        else:
+            op_call(self.plan, "select_mask", "tail", lib.cvmi_select_mask,
+                    (self.masks4.data_ptr(), self.areas.data_ptr(), iou4.t.data_ptr(), 4, 1 if self.dynamic else 0, 0.98, self.low_res.data_ptr(),
+                     self.iou.data_ptr(), self.sel.data_ptr(), NB, P0), bytes_=NB * P0 * 8)
         if not self.want_high_res:
             self.high_res = None
             return
-        self.high_res = torch.empty(NB, 1, R, R, dtype=torch.float32, device=self.dev)
+        self.high_res = torch.empty(NB, NM, R, R, dtype=torch.float32, device=self.dev)
         if wt.refine_params is not None and not NP:            # the refinement head belongs to the learned-prompt wrapper (sam2_infer.py:269-270)
             import ctypes as C
             ks = (C.c_int * len(wt.kernels))(*wt.kernels)
@@ -791,7 +850,7 @@ class Sam2Plan:
                     keep=(ks,), bytes_=NB * (P0 + R * R) * 4, flops=2 * NB * R * R * 4 * taps)
         else:
             op_call(self.plan, "upsample", "tail", lib.cvmi_bilinear_f32,
-                    (self.low_res.data_ptr(), NB, f0, f0, self.high_res.data_ptr(), R, R, None, 0.0), bytes_=NB * (P0 + R * R) * 4)
+                    (self.low_res.data_ptr(), NB * NM, f0, f0, self.high_res.data_ptr(), R, R, None, 0.0), bytes_=NB * NM * (P0 + R * R) * 4)
 
 class _ConstView:
     """Constant [rows, C] device tensor posing as a residual View (ptr, ld)."""

@@ -79,15 +79,20 @@ class SAM2Model:
             self._slot_streams[slot] = torch.cuda.Stream(device=self.dev)
         return self._slot_streams[slot]
 
-    def plan(self, B, prompts=0, high_res=True, points=3, slot=0):
+    def _packed_weights(self):
         if self.weights is None and self._pending is not None:
             self.load_params(self._pending)           # base checkpoint only (no fine-tuned state dict followed): pack it now
         if self.weights is None:
             raise RuntimeError("SAM2 weights not loaded (call load_state_dict first)")
-        key = (B, prompts, high_res, points if prompts else 0, slot)
+        return self.weights
+
+    def plan(self, B, prompts=0, high_res=True, points=3, slot=0, mask_prompt=False, multimask=False):
+        wt = self._packed_weights()
+        key = (B, prompts, high_res, points if prompts else 0, slot, bool(mask_prompt), bool(multimask))
         if key not in self._plans:
             with torch.cuda.device(self.dev):
-                self._plans[key] = Sam2Plan(self.weights, B, self.slot_stream(slot), self.dynamic, prompts=prompts, points=points, high_res=high_res, attn=self.attn)
+                self._plans[key] = Sam2Plan(wt, B, self.slot_stream(slot), self.dynamic, prompts=prompts, points=points, high_res=high_res, attn=self.attn,
+                                            mask_prompt=mask_prompt, multimask=multimask)
         return self._plans[key]
 
     def _stage_images(self, p, images):
@@ -139,7 +144,7 @@ class SAM2Model:
 
     forward = __call__
 
-    def infer_masks(self, images, boxes=None, return_high_res=True, points=None, point_labels=None):
+    def infer_masks(self, images, boxes=None, return_high_res=True, points=None, point_labels=None, mask_input=None, multimask_output=False):
         """Batched segmentation entry point (north_star).  images [B,3,R,R].
         No prompt: exactly `SAM2ImageWrapper.forward` (learned prompts) -> (high_res [B,1,R,R], low_res [B,1,R/4,R/4], iou [B,1]).
         boxes [B,P,4] (xyxy in the R x R input pixel space, e.g. detector boxes scaled by R / original size) and / or
@@ -147,9 +152,15 @@ class SAM2Model:
         upstream's filler for ragged click lists -- still a token the decoder sees): upstream
         SAM2ImagePredictor prompting on the same weights -- a box enters as two corner points labelled 2 / 3, clicks follow it,
         one padding point closes the list -- one mask per prompt (multimask_output=False with the stability fallback) ->
-        (high_res logits [B,P,R,R] or None, low_res logits [B,P,R/4,R/4] (unclamped), iou [B,P])."""
+        (high_res logits [B,P,R,R] or None, low_res logits [B,P,R/4,R/4] (unclamped), iou [B,P]).
+        mask_input [B,P,R/4,R/4] (float, host or device; needs boxes and / or points): upstream's mask prompt -- low-res logits, e.g. the
+        low_res of an earlier call, enter through `sam_prompt_encoder.mask_downscaling` as the dense prompt in the place of no_mask_embed.
+        multimask_output=True (needs a prompt): the three multimask candidates in token order with their predicted IoUs, no stability
+        fallback -> (high_res [B,P,3,R,R] or None, low_res [B,P,3,R/4,R/4], iou [B,P,3])."""
         if boxes is None and points is None:
-            return self(images)
+            if mask_input is not None:
+                raise ValueError("mask_input needs boxes and / or points (a mask-only prompt is not built)")
+            return self(images, multimask_output=multimask_output)
         self._check_images(images)
         B = images.shape[0]
         bx = pts = None
@@ -172,8 +183,16 @@ class SAM2Model:
         nb, nk = (2 if bx is not None else 0), (pts.shape[2] if pts is not None else 0)
         K = nb + nk + 1                                            # + the closing padding point
         R, f0 = self.image_size, self.image_size // 4
+        mk = None
+        if mask_input is not None:
+            mk = torch.as_tensor(mask_input)
+            if not mk.is_floating_point() or tuple(mk.shape) != (B, P, f0, f0):
+                raise ValueError(f"mask_input must be float [B={B}, P={P}, {f0}, {f0}] low-res logits, got {mk.dtype} {tuple(mk.shape)}")
+        NM = 3 if multimask_output else 1
         with self._lock, torch.cuda.device(self.dev):
-            p = self.plan(B, prompts=P, high_res=return_high_res, points=K)
+            if mk is not None and not self._packed_weights().mask_prompt_ok:
+                raise RuntimeError("this checkpoint carries no sam_prompt_encoder.mask_downscaling tensors: mask_input is unavailable")
+            p = self.plan(B, prompts=P, high_res=return_high_res, points=K, mask_prompt=mk is not None, multimask=bool(multimask_output))
             coords = torch.zeros(B * P, K, 2, dtype=torch.float32)
             labels = torch.full((B * P, K), -1, dtype=torch.int32)
             if bx is not None:
@@ -185,9 +204,12 @@ class SAM2Model:
             def prompts_in():                                          # on the model's stream, in front of the replay that reads them
                 p.coords.copy_(coords, non_blocking=False)
                 p.labels.copy_(labels, non_blocking=False)
-            lo, iou = torch.empty(B, P, f0, f0, dtype=torch.float32, device=self.dev), torch.empty(B, P, dtype=torch.float32, device=self.dev)
-            hi = torch.empty(B, P, R, R, dtype=torch.float32, device=self.dev) if return_high_res else None
-            outs = [(p.low_res.view(B, P, f0, f0), lo), (p.iou.view(B, P), iou)] + ([(p.high_res.view(B, P, R, R), hi)] if return_high_res else [])
+                if mk is not None:
+                    p.mask_in.copy_(mk.reshape(B * P, f0, f0), non_blocking=False)
+            shp = (B, P, NM) if multimask_output else (B, P)
+            lo, iou = torch.empty(*shp, f0, f0, dtype=torch.float32, device=self.dev), torch.empty(*shp, dtype=torch.float32, device=self.dev)
+            hi = torch.empty(*shp, R, R, dtype=torch.float32, device=self.dev) if return_high_res else None
+            outs = [(p.low_res.view(*shp, f0, f0), lo), (p.iou.view(*shp), iou)] + ([(p.high_res.view(*shp, R, R), hi)] if return_high_res else [])
             self._run(p, images, outs, before=prompts_in)
             return hi, lo, iou
 

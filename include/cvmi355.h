@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define CVMI_VERSION 124
+#define CVMI_VERSION 125
 
 typedef void* cvmi_stream_t; /* hipStream_t */
 
@@ -371,6 +371,29 @@ int cvmi_hyper_masks(const float* hyper, int hyper_ld, const void* up, int up_ld
 int cvmi_select_mask(const float* masks, const int* areas, const float* iou, int iou_ld, int dynamic,
                      float thresh, float* low_res, float* iou_out, int* sel, int B, int P,
                      cvmi_stream_t stream);
+
+/* The multimask tail (upstream MaskDecoder.forward with multimask_output=True): tokens 1..3 of masks f32 [n,4,P] and of iou f32 [n, iou_ld]
+ * (4 values used) as contiguous low_res3 f32 [n,3,P] and iou3 f32 [n,3], in token order; no stability fallback.  A plain copy: candidate k
+ * is bit-identical to what cvmi_select_mask writes when it selects token 1 + k. */
+int cvmi_multimask_out(const float* masks, const float* iou, int iou_ld, float* low_res3, float* iou3, int n, int P,
+                       cvmi_stream_t stream);
+
+/* Mask prompts (upstream PromptEncoder._embed_masks + SAM2ImagePredictor._predict with mask_input): the decoder's image stream of the
+ * B * rep (image, prompt) pairs, image-major (pair i belongs to image i / rep), in one launch --
+ *   keys[i] = emb[i / rep] + mask_downscaling(mask[i]) - no_mask_embed
+ * with mask_downscaling = Conv2d(1,4,k=2,s=2) -> LayerNorm2d(4) -> GELU -> Conv2d(4,16,k=2,s=2) -> LayerNorm2d(16) -> GELU -> Conv2d(16,256,k=1)
+ * (LayerNorm2d: per pixel over the channels, biased variance, eps 1e-6; GELU: the exact erf form), all in f32.
+ *   mask    f32 [B*rep, 4*fs, 4*fs] logits (the size of low_res)
+ *   emb     f32 [B, fs*fs, 256]: the embed GEMM's output, whose bias already holds no_mem_embed + no_mask_embed
+ *   params  f32 [CVMI_MASK_PROMPT_PARAMS], packed in this order: w1[4][2][2] b1[4] g1[4] be1[4]  w2[16][4][2][2] b2[16] g2[16] be2[16]
+ *           w3[256][16]  b3'[256] with b3' = b3 - no_mask_embed (g / be: the LayerNorm2d weight / bias)
+ *   keys    f32 [B*rep, fs*fs, 256]
+ *   keys_lp optional: the same values rounded once (nearest even) to lp_dtype = CVMI_F16 or CVMI_BF16, same shape; NULL: lp_dtype is ignored
+ * All pointers 16-byte aligned (keys_lp 8-byte); B, rep, fs > 0; B * rep * fs * fs < 2^31.  fs * fs need not be a multiple of anything.
+ * No atomics: the result does not depend on the launch.  Replaces cvmi_repeat_images and, in a 16-bit plan, the first cvmi_cast of keys. */
+#define CVMI_MASK_PROMPT_PARAMS 4684
+int cvmi_mask_prompt_embed(const float* mask, const float* emb, const float* params, float* keys, void* keys_lp, int lp_dtype,
+                           int B, int rep, int fs, cvmi_stream_t stream);
 
 /* F.interpolate(bilinear, align_corners=False) of f32 planes [N,h,w] -> [N,H,W] (sam2_infer.py:263-268,
  * postprocess_masks :127).  mask_u8 (optional): also writes (value > thresh) ? 255 : 0. */
