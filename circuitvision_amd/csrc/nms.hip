@@ -8,6 +8,7 @@
 //      (up to ~4 k candidates; the workspace otherwise) -- the greedy pass re-reads them once per kept box
 //   4. greedy pass: next unsuppressed candidate is kept, every later candidate with
 //      inter / (area_i + area_j - inter) > iou_thres is marked in an LDS bitmask; stops at max_det.
+//      Only the NMS_MAX_NMS best candidates take part (ultralytics' max_nms): whatever the sort ranks behind them is dropped.
 //      The pass only records the kept sorted positions; the detections are written afterwards, one thread each
 //      (a kept box costs one LDS round + one barrier, not a chain of dependent global loads).
 #include "common.hpp"
@@ -22,6 +23,7 @@ constexpr int NMS_LDS_A = 16384;                   // sort keys live in LDS up t
 __host__ __device__ inline size_t nms_keys_offset(size_t nb, size_t A) { return (nb * A * 28 + 256 + 15) & ~(size_t)15; }
 constexpr int NMS_MAX_A = 65536;                   // ... and in the workspace above it (checkpoints trained at imgsz 960 / 1024 / 1280)
 constexpr int NMS_MAX_DET = 4096;                  // LDS list of kept positions
+constexpr int NMS_MAX_NMS = 30000;                 // ultralytics' max_nms: candidates ranked beyond it never reach the greedy pass
 
 struct Cand { float x1, y1, x2, y2, area; };   // offset boxes (class * max_wh added)
 
@@ -85,16 +87,16 @@ __global__ __launch_bounds__(NMS_THREADS) void yolo_nms_kernel(const float* __re
     }
   }
   __syncthreads();
-  const int n = s_count;
+  const int nall = s_count;
   // From here on every step is a short data-parallel pass followed by a barrier.  With up to 2048 candidates the passes fit four
   // waves (one per SIMD): the other twelve retire now, and a barrier among four waves is several times cheaper than among sixteen
   // (36 sort passes + one barrier per kept box at 256 candidates: 52 -> 20 us per image).
-  const int nthr = n <= 2048 ? 256 : NMS_THREADS;
+  const int nthr = nall <= 2048 ? 256 : NMS_THREADS;
   if (tid >= nthr) return;
 
   // 2. bitonic sort, descending, over the smallest power of two >= n
   int Ps = 1;
-  while (Ps < n) Ps <<= 1;
+  while (Ps < nall) Ps <<= 1;
   for (int k = 2; k <= Ps; k <<= 1) {
     for (int j = k >> 1; j > 0; j >>= 1) {
       for (int t = tid; t < Ps / 2; t += nthr) {
@@ -107,6 +109,8 @@ __global__ __launch_bounds__(NMS_THREADS) void yolo_nms_kernel(const float* __re
       __syncthreads();
     }
   }
+
+  const int n = min(nall, NMS_MAX_NMS);            // (only a GK launch can hold more: geo_lds is false there, and Ps stays the sorted length)
 
   // 3. candidate geometry in sorted order: in LDS behind the Ps sorted keys when it fits, in the workspace otherwise
   const bool geo_lds = !GK && (size_t)Ps * 8 + (size_t)n * sizeof(Cand) <= (size_t)P * 8;
@@ -204,6 +208,7 @@ static int nms_launch(const float* pred, const float* best_score, const int* bes
                                    NMS_LDS_A * 8 + (NMS_LDS_A / 64) * 8 + 16 + NMS_MAX_DET * (int)sizeof(int));
   });
   CVMI_HIP(attr_err);
+  cvmi_note_kernel(gk ? "yolo_nms_kernel<true>" : "yolo_nms_kernel<false>");
   if (gk)
     hipLaunchKernelGGL(yolo_nms_kernel<true>, dim3(B), dim3(NMS_THREADS), lds, stream, pred, best_score, best_cls, nc, A, conf_thres, iou_thres,
                        max_det, max_wh, out_det, out_idx, out_count, (char*)workspace, P);

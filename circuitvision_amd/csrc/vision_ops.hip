@@ -558,6 +558,7 @@ extern "C" int cvmi_detect_decode(const void* const* box, const int* box_ld, con
   const unsigned blocks = (unsigned)((total + 63) / 64);
   const size_t lds = (size_t)64 * (ncp + 1) * sizeof(float);
   CVMI_CHECK(lds <= 64 * 1024, "detect_decode: nc too large for the LDS tile");
+  cvmi_note_kernel("detect_decode_kernel<%s>", dtype == CVMI_F16 ? CVMI_F16NAME : "float");
   if (dtype == CVMI_F16)
     hipLaunchKernelGGL(detect_decode_kernel<f16>, dim3(blocks), dim3(256), lds, stream, d, pred, best_score, best_cls, write_cls);
   else

@@ -198,8 +198,9 @@ int cvmi_detect_decode(const void* const* box, const int* box_ld, const void* co
 
 /* ---- ultralytics-semantics NMS on the decoded predictions -------------------------------------
  * pred f32 [B, 4+nc, A].  Candidates: max class score > conf_thres; sorted by score desc (ties:
- * lower anchor index first); per-class via +cls*max_wh; greedy suppress IoU > iou_thres; first
- * max_det kept.  out_det f32 [B, max_det, 6] (x1,y1,x2,y2,conf,cls), out_idx i32 [B, max_det]
+ * lower anchor index first); only the first NMS_MAX_NMS = 30000 of them go on (ultralytics' max_nms);
+ * per-class via +cls*max_wh; greedy suppress IoU > iou_thres; first max_det kept (max_det <= 4096).
+ * out_det f32 [B, max_det, 6] (x1,y1,x2,y2,conf,cls), out_idx i32 [B, max_det]
  * (anchor index), out_count i32 [B].  workspace: >= cvmi_yolo_nms_workspace(B, A) bytes.
  * Replaces ultralytics ops.non_max_suppression + torchvision.ops.nms (circuit_analyzer.py:268). */
 size_t cvmi_yolo_nms_workspace(int B, int A);

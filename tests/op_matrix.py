@@ -27,6 +27,10 @@ tests/tok_ref.py.  tl16_splits is compared with the library's own answer (cvmi_t
 its N % 32 != 0 branch is checked by reading only: the library exports the split count through that entry point alone, which always asks for the
 statistics-out form, where a ragged N never splits; the split count is not in the tag.
 
+NMS_ROWS / DECODE_ROWS: the detector's tail (nms.hip, vision_ops.hip cvmi_detect_decode).  One NMS row = one input with an exact candidate count, the
+instance nms_launch must tag and the decisions nms_pick -- a mirror of nms_launch and of yolo_nms_kernel's data-dependent branches -- derives from it; one
+decode row = one launch per dtype with its stated seams.  Generators, references, mutants and the decode bound live in tests/detect_ref.py.
+
 BF16_OPS: every entry point that common.hpp builds twice (CVMI_ENTRY) -> (test module, test function) that checks its bf16 build per op.
 
 Plain data: importing this module needs neither a GPU nor the library."""
@@ -780,3 +784,147 @@ TOK_MUTANT_DTYPES = {"ln_var_n_minus_1": ("f16",)}
 # mlp_hidden_not_rounded is MORE accurate than the contract by the rounding noise of 4 C hidden values, 0.09 (fp16) / 0.45 (bf16) of the MLP bound,
 # which is set by the GELU form's error.
 TOK_UNSEEN_MUTANTS = {"mlp_hidden_not_rounded": [r["id"] for r in MLP_ROWS if r["rows"] >= 127]}
+
+
+# ---- the detector's tail: vision_ops.hip cvmi_detect_decode, nms.hip cvmi_yolo_nms / cvmi_yolo_nms_best ---------------------------------------
+# NMS_ROWS: one row = one input of nms_launch with an EXACT candidate count n per image (tests/detect_ref.py places exactly n best-class scores
+# above conf_thres and some at exactly conf_thres), the instance it must tag and the decisions nms_pick -- a mirror of nms_launch and of the
+# kernel's own branches -- derives from (A, n).  DECODE_ROWS: one row = one launch of cvmi_detect_decode per dtype.  Generators, references,
+# mutants and the decode bound live in tests/detect_ref.py.
+NMS_LDS_A, NMS_MAX_A, NMS_MAX_DET, NMS_MAX_NMS = 16384, 65536, 4096, 30000
+NMS_NTHR_N = 2048                                  # up to this many candidates four waves run the passes, sixteen beyond
+NMS_CAND_BYTES, NMS_WS_RECORD = 20, 28             # sizeof(Cand); workspace bytes per anchor (Cand + best score + best class)
+NMS_KINDS = ("cluster", "isolated", "touch", "clsoff", "rounding", "maxnms")
+
+
+def nms_pick(A, n):
+    """(gk, P, Ps, nthr, geo_lds) of nms_launch / yolo_nms_kernel for A anchors of which n are candidates: keys in the workspace, key slots, sorted
+    length, threads that stay after the candidate pass, geometry in LDS behind the sorted keys."""
+    assert 0 < A <= NMS_MAX_A and 0 <= n <= A, (A, n)
+    P = 1024
+    while P < A:
+        P <<= 1
+    gk = A > NMS_LDS_A
+    nthr = 256 if n <= NMS_NTHR_N else 1024
+    Ps = 1
+    while Ps < n:
+        Ps <<= 1
+    geo_lds = (not gk) and Ps * 8 + min(n, NMS_MAX_NMS) * NMS_CAND_BYTES <= P * 8
+    return gk, P, Ps, nthr, geo_lds
+
+
+def nms_workspace(B, A):
+    """cvmi_yolo_nms_workspace: the records, 256 spare bytes, rounded up to 16, and the GK keys behind them."""
+    P = nms_pick(A, 0)[1]
+    return ((B * A * NMS_WS_RECORD + 256 + 15) & ~15) + (B * P * 8 if A > NMS_LDS_A else 0)
+
+
+def nms_tag(gk):
+    return "yolo_nms_kernel<%s>" % ("true" if gk else "false")
+
+
+def _nms(rid, A, n, B=2, nc=4, conf=0.25, iou=0.7, max_det=300, max_wh=7680.0, kind="cluster", entry="best", clusters=12, jitter=1.5, zero=0.0,
+         equal_scores=False, survivors=None, note=""):
+    """entry: "best" = cvmi_yolo_nms_best alone, "both" = cvmi_yolo_nms as well (identical outputs).  kind: the box layout (detect_ref.nms_inputs).
+    survivors: what the reference must find before max_det cuts the list ("==300", ">300", ..), asserted on the CPU."""
+    gk, P, Ps, nthr, geo = nms_pick(A, n)
+    return dict(id=rid, expect=nms_tag(gk), A=A, n=n, B=B, nc=nc, conf=conf, iou=iou, max_det=max_det, max_wh=max_wh, kind=kind, entry=entry,
+                clusters=clusters, jitter=jitter, zero=zero, equal_scores=equal_scores, survivors=survivors, gk=gk, P=P, Ps=Ps, nthr=nthr, geo_lds=geo, note=note)
+
+
+NMS_ROWS = [
+    # ---- the six reachable (gk, nthr, geo_lds)
+    _nms("lds_256_geo", 1024, 100, entry="both", note="A = 1024: the last A with P = 1024"),
+    _nms("lds_1024_geo", 8193, 3000, note="P = 16384 at its smallest A"),
+    _nms("lds_256_nogeo", 2100, 1500, entry="both"),
+    _nms("lds_1024_nogeo", 2049, 2049, note="n = A = 2049: the first n with sixteen waves; Ps = P = 4096"),
+    _nms("gk_256_odd", 16385, 500, B=3, entry="both", note="B * A odd: the workspace key offset is rounded up to 16 bytes"),
+    _nms("gk_1024_b1", 16386, 2500, B=1, nc=62),
+    # ---- n edges at the smallest A that holds them (and a few anchors at exactly conf_thres)
+    _nms("n0", 5, 0, entry="both"), _nms("n1_a1", 1, 1, B=3, entry="both", note="A = 1"), _nms("n1", 5, 1), _nms("n2", 5, 2, entry="both"), _nms("n3", 7, 3, clusters=1),
+    _nms("n255", 300, 255), _nms("n256_quarter_p1024", 300, 256, note="n = P / 4: the last n with the geometry in LDS"),
+    _nms("n257_quarter_p1024_plus1", 300, 257, entry="both", note="Ps = 512: keys and geometry no longer fit"),
+    _nms("n2047", 2100, 2047), _nms("n2048", 2100, 2048, note="the last n with four waves"), _nms("n2049_geo", 8193, 2049, note="sixteen waves, geometry in LDS"),
+    _nms("n4096_quarter_p16384", 8193, 4096), _nms("n4097_quarter_p16384_plus1", 8193, 4097),
+    _nms("full_1024", 1024, 1024, note="every anchor a candidate, every key slot used"), _nms("full_16384", 16384, 16384, nc=3, clusters=40, note="the last A with LDS keys, full"),
+    # ---- A edges
+    _nms("a1025", 1025, 200, note="P = 2048"), _nms("a65536_second_grid_pass", 65536, 50, B=17, nc=2, entry="both",
+                                                    note="B * A > 4096 * 256: best_class_kernel's second grid pass; A = NMS_MAX_A"),
+    # ---- max_det: the LDS list kept_pos and the loop bound
+    _nms("md1", 300, 100, max_det=1, entry="both"),
+    _nms("md300_exact", 400, 300, kind="isolated", survivors="==300"), _nms("md300_more", 500, 400, kind="isolated", survivors=">300", entry="both"),
+    _nms("md4096_more", 4300, 4200, kind="isolated", max_det=4096, survivors=">4096", note="NMS_MAX_DET"),
+    # ---- thresholds and degenerate geometry
+    _nms("conf0", 300, 120, conf=0.0, entry="both", note="non-candidates score exactly 0"),
+    _nms("iou0_touch", 330, 300, nc=1, iou=0.0, kind="touch", note="boxes that share an edge have inter = 0: kept at iou_thres = 0"),
+    _nms("iou_neg", 300, 200, iou=-1.0, note="every later box is suppressed, disjoint and other-class ones included (ovr = 0 > -1)"),
+    _nms("dups", 300, 200, jitter=0.0, entry="both", note="exact duplicates: IoU = 1"),
+    _nms("zero_area", 300, 200, jitter=0.0, zero=0.5, note="duplicated zero-area boxes: 0 / 0 is not above any threshold"),
+    _nms("ties", 600, 500, equal_scores=True, entry="both", note="one score for the whole candidate set: the order is the anchor index"),
+    _nms("clsoff", 300, 240, nc=62, kind="clsoff", entry="both", note="the same box under classes 61, 60, 0: the offset keeps them apart"),
+    _nms("rounding", 200, 96, B=1, nc=62, kind="rounding", note="48 pairs whose verdict hangs on fp32 rounding: 24 by the class offset, 24 by a contracted union"),
+    _nms("max_nms", 32768, 32768, B=1, nc=2, kind="maxnms", survivors="==40", note="40 clusters; the 100 weakest candidates are isolated and ranked beyond NMS_MAX_NMS"),
+]
+NMS_N_EDGES = (0, 1, 2, 3, 255, 256, 257, 2047, 2048, 2049)
+NMS_A_EDGES = (1, 1024, 1025, 16384, 16385)
+NMS_REFUSED = [dict(id="max_det_4097", A=300, B=1, nc=4, max_det=NMS_MAX_DET + 1, text="bad shape"),
+               dict(id="a_65537", A=NMS_MAX_A + 1, B=1, nc=1, max_det=300, text="exceeds 65536 anchors")]
+
+
+def _dec(rid, levels, B, nc, kind="rand", dtypes=F16_F32, box_extra=0, cls_extra=0, straddle=(), optional=False, chain=False, note=""):
+    """levels: ((h, w), ..) at strides 8, 16, 32.  box_extra / cls_extra: channels beyond 64 / beyond the padded class count, holding NaN.
+    straddle: the seams ("image", "level1", "level2") that must fall inside a 64-anchor workgroup.  optional: also runs write_cls = 0 and no
+    best-class outputs.  chain: cvmi_yolo_nms_best on the kernel's own best arrays."""
+    A = sum(h * w for h, w in levels)
+    return dict(id=rid, levels=tuple(levels), B=B, nc=nc, A=A, kind=kind, dtypes=dtypes, box_extra=box_extra, cls_extra=cls_extra, straddle=tuple(straddle),
+                optional=optional, chain=chain, note=note)
+
+
+def decode_tag(dt):
+    return "detect_decode_kernel<%s>" % TNAME[dt]
+
+
+def decode_seams(row):
+    """{"image": [..], "level1": [..], "level2": [..]}: flat (image, anchor) indices at which a new image / level starts."""
+    a0, out = 0, {"image": [b * row["A"] for b in range(1, row["B"])], "level1": [], "level2": []}
+    for l, (h, w) in enumerate(row["levels"]):
+        if l:
+            out["level%d" % l] = [b * row["A"] + a0 for b in range(row["B"])]
+        a0 += h * w
+    return out
+
+
+DECODE_NC_MAX = {"f16": 248, "f32": 252}          # 64 x (ncp + 1) floats in 64 KiB, ncp = nc rounded up to a 16-byte vector
+DECODE_ROWS = [
+    _dec("l3_seams", ((5, 7), (3, 4), (1, 1)), 3, 62, box_extra=16, cls_extra=16, straddle=("image", "level1", "level2"), optional=True,
+         note="A = 48: workgroup 0 holds both level seams and the image seam; a 1 x 1 level; B * A = 144"),
+    _dec("l1_64", ((8, 8),), 1, 8, note="B * A = 64: one full workgroup"),
+    _dec("l1_1", ((1, 1),), 1, 1, note="B * A = 1, nc = 1"),
+    _dec("l2_nonsquare", ((3, 9), (2, 5)), 2, 7, cls_extra=8, straddle=("image", "level1"), note="A = 37"),
+    _dec("l3_nc80", ((6, 10), (3, 5), (2, 3)), 2, 80, box_extra=8, straddle=("image", "level2")),
+    _dec("l3_ncmax_f16", ((3, 5), (2, 2), (1, 1)), 4, DECODE_NC_MAX["f16"], dtypes=("f16",), note="the widest class tile of the fp16 instance"),
+    _dec("l3_ncmax_f32", ((3, 5), (2, 2), (1, 1)), 4, DECODE_NC_MAX["f32"], dtypes=("f32",)),
+    _dec("cls_ties", ((4, 6), (2, 3)), 2, 62, kind="ties", straddle=("image", "level1"), note="equal logits in several channels: the first maximum wins"),
+    _dec("saturated", ((4, 6), (2, 3)), 2, 7, kind="saturated", note="+-1000 in DFL bins and class logits"),
+    _dec("chain", ((12, 20), (6, 10), (3, 5)), 2, 62, chain=True, straddle=("image", "level1", "level2"), note="decode -> cvmi_yolo_nms_best"),
+]
+DECODE_REFUSED = [dict(id="nc_249_f16", dt="f16", nc=DECODE_NC_MAX["f16"] + 1, text="nc too large"), dict(id="nc_253_f32", dt="f32", nc=DECODE_NC_MAX["f32"] + 1, text="nc too large"),
+                  dict(id="score_without_cls", dt="f16", nc=8, best="score", text="go together"), dict(id="cls_without_score", dt="f32", nc=8, best="cls", text="go together")]
+
+# mutant of tests/detect_ref.py -> ids of the rows whose expected output it must change (tests/test_detect_ref_cpu.py)
+DETECT_MUTANT_ROWS = {
+    "conf_ge": ["n0", "conf0", "lds_256_geo"],
+    "iou_ge": ["iou0_touch"],
+    "ties_desc_anchor": ["ties"],
+    "no_class_offset": ["clsoff"],
+    "area_unoffset": ["rounding"],
+    "iou_fma": ["rounding"],
+    "max_det_off_by_one": ["md1", "md300_more", "md4096_more"],
+    "no_max_nms": ["max_nms"],
+    "best_last_max": ["lds_256_geo", "cls_ties:decode"],
+    "dfl_no_max": ["saturated:decode"],
+    "anchor_no_half": ["l1_1:decode", "l3_seams:decode"],
+    "level_seam_off_by_one": ["l3_seams:decode", "l2_nonsquare:decode"],
+}
+# mutants no row can see (none today): kept as a name so that a blind spot is recorded, never dropped
+DETECT_UNSEEN_MUTANTS = {}

@@ -1,7 +1,8 @@
 """CPU guard on the per-op GPU coverage (tests/op_matrix.py): every dual-built entry point has a bf16 test, every attention kernel family the
 dispatcher can launch has a row in the dispatch matrix, and so has every kernel family and template instance of cvmi_conv2d's dispatcher
 (CONV_ROWS), every built instance of the three fused YOLO11 kernels (FUSED_ROWS), and every layernorm_kernel instance, SPPF kernel and
-refinement kernel of the helper dispatchers (LN_ROWS, HELPER_ROWS), and every instance of the token-stationary kernels with the chunk counts,
+refinement kernel of the helper dispatchers (LN_ROWS, HELPER_ROWS), every branch combination and edge of the detector's tail (NMS_ROWS,
+DECODE_ROWS), and every instance of the token-stationary kernels with the chunk counts,
 split counts, pool grids and statistics forms their rings and index arithmetic need (TOK_ROWS, MLP_ROWS).  Adding an entry point or a kernel
 without its per-op test fails here, on any checkout."""
 import ast
@@ -9,7 +10,9 @@ import glob
 import os
 import re
 
-from op_matrix import (ATTN_ROWS, BF16_OPS, C3K2_INSTANCES, CONV_ROWS, FUSED_MUTANT_ROWS, FUSED_ROWS, HELPER_ROWS, LN_DUAL_ROWS, LN_FORMS, LN_NCAND, LN_ROWS,
+from op_matrix import (ATTN_ROWS, BF16_OPS, C3K2_INSTANCES, CONV_ROWS, DECODE_NC_MAX, DECODE_REFUSED, DECODE_ROWS, FUSED_MUTANT_ROWS, NMS_A_EDGES, NMS_CAND_BYTES,
+                       NMS_KINDS, NMS_LDS_A, NMS_MAX_A, NMS_MAX_DET, NMS_MAX_NMS, NMS_N_EDGES, NMS_NTHR_N, NMS_REFUSED, NMS_ROWS, NMS_WS_RECORD, decode_tag, nms_pick,
+                       nms_tag, nms_workspace, FUSED_ROWS, HELPER_ROWS, LN_DUAL_ROWS, LN_FORMS, LN_NCAND, LN_ROWS,
                        MLP_INSTANCES, MLP_ROWS, SHARE_ROWS, SPPF_LDS_PIXELS, TNAME, TOK_FORMAT, TOK_INSTANCES, TOK_KS, TOK_MUTANT_ROWS, TOK_NCH, TOK_NCH_FAMILIES,
                        TOK_PARTS, TOK_ROWS, TOK_SLOTS, TOK_SPLIT_TABLE, TOK_UNSEEN_MUTANTS, c3k2_max_wgs_per_cu, c3k2_tag, conv_expect, ln_pick, ln_reachable,
                        ln_tag, mlp_pick, tl16_splits, tok_dispatch, tok_nch_family, tok_pick)
@@ -600,3 +603,134 @@ def test_token_path_rows_are_well_formed():
         assert any(not r["stats_out"] for r in mine) and any(r["x_ld"] == r["C"] for r in mine), tag
     for mut, rids in list(TOK_MUTANT_ROWS.items()) + list(TOK_UNSEEN_MUTANTS.items()):
         assert rids and set(rids) <= set(ids), mut
+
+
+# ---- the detector's tail: nms.hip nms_launch / yolo_nms_kernel, vision_ops.hip cvmi_detect_decode -----------------------------------------------------
+DETECT_SOURCES = ("nms.hip", "vision_ops.hip")
+# the text nms_pick / nms_workspace mirror: constant or expression -> what op_matrix holds for it
+NMS_TEXT = {
+    "constexpr int NMS_LDS_A = %d;" % NMS_LDS_A: "NMS_LDS_A",
+    "constexpr int NMS_MAX_A = %d;" % NMS_MAX_A: "NMS_MAX_A",
+    "constexpr int NMS_MAX_DET = %d;" % NMS_MAX_DET: "NMS_MAX_DET",
+    "constexpr int NMS_MAX_NMS = %d;" % NMS_MAX_NMS: "NMS_MAX_NMS",
+    "const int nthr = nall <= %d ? 256 : NMS_THREADS;" % NMS_NTHR_N: "the four-wave threshold",
+    "const int n = min(nall, NMS_MAX_NMS);": "the max_nms cap behind the sort",
+    "const bool geo_lds = !GK && (size_t)Ps * 8 + (size_t)n * sizeof(Cand) <= (size_t)P * 8;": "the geo_lds expression",
+    "struct Cand { float x1, y1, x2, y2, area; };": "sizeof(Cand) = %d" % NMS_CAND_BYTES,
+    "return (nb * A * %d + 256 + 15) & ~(size_t)15; }" % NMS_WS_RECORD: "the 28-byte workspace record and its 16-byte rounding",
+    "static_assert(sizeof(Cand) + sizeof(float) + sizeof(int) == %d," % NMS_WS_RECORD: "the 28-byte workspace record",
+    "const bool gk = A > NMS_LDS_A;": "the GK rule",
+    "int P = 1024;\n  while (P < A) P <<= 1;": "P",
+    "int Ps = 1;\n  while (Ps < nall) Ps <<= 1;": "Ps",
+    "max_det > 0 && max_det <= NMS_MAX_DET": "the max_det check",
+}
+DETECT_TAGS = {"nms.hip": 'cvmi_note_kernel(gk ? "yolo_nms_kernel<true>" : "yolo_nms_kernel<false>");',
+               "vision_ops.hip": 'cvmi_note_kernel("detect_decode_kernel<%s>", dtype == CVMI_F16 ? CVMI_F16NAME : "float");'}
+NMS_COMBOS = [(False, 256, True), (False, 1024, True), (False, 256, False), (False, 1024, False), (True, 256, False), (True, 1024, False)]
+
+
+def detect_sources(csrc=CSRC):
+    return {name: open(os.path.join(csrc, name)).read() for name in DETECT_SOURCES}
+
+
+def detect_gaps(sources, nms_rows=NMS_ROWS, decode_rows=DECODE_ROWS):
+    """What the detector-tail matrix leaves uncovered, as a list of strings (empty = complete)."""
+    gaps = [f"nms.hip no longer reads {text!r} ({what}): nms_pick mirrors something else" for text, what in NMS_TEXT.items() if text not in sources["nms.hip"]]
+    gaps += [f"{name} no longer tags its launch with {text}" for name, text in DETECT_TAGS.items() if text not in sources[name]]
+    have = {(r["gk"], r["nthr"], r["geo_lds"]) for r in nms_rows}
+    gaps += ["yolo_nms_kernel (gk, nthr, geo_lds) = (%s, %d, %s) has no row" % c for c in NMS_COMBOS if c not in have]
+    gaps += [f"yolo_nms_kernel: no row with n = {n}" for n in NMS_N_EDGES if not any(r["n"] == n for r in nms_rows)]
+    gaps += [f"yolo_nms_kernel: no row with A = {a}" for a in NMS_A_EDGES if not any(r["A"] == a for r in nms_rows)]
+    for P in (1024, 16384):
+        for n, what in ((P // 4, "P / 4"), (P // 4 + 1, "P / 4 + 1"), (P, "A = P")):
+            if not any(r["P"] == P and r["n"] == n and not r["gk"] and (n < P or r["A"] == P) for r in nms_rows):
+                gaps.append(f"yolo_nms_kernel: no row with n = {what} at P = {P}")
+    checks = (("a GK row with B * A odd", lambda r: r["gk"] and (r["B"] * r["A"]) % 2 == 1), ("a row with B = 1", lambda r: r["B"] == 1),
+              ("a cvmi_yolo_nms row with B * A > 4096 * 256", lambda r: r["entry"] == "both" and r["B"] * r["A"] > 4096 * 256),
+              ("max_det = 1", lambda r: r["max_det"] == 1), ("max_det = 300 with exactly 300 survivors", lambda r: r["max_det"] == 300 and r["survivors"] == "==300"),
+              ("max_det = 300 with more survivors", lambda r: r["max_det"] == 300 and r["survivors"] == ">300"),
+              ("max_det = NMS_MAX_DET with more survivors", lambda r: r["max_det"] == NMS_MAX_DET and r["survivors"] == ">%d" % NMS_MAX_DET),
+              ("conf_thres = 0", lambda r: r["conf"] == 0), ("iou_thres = 0 with touching boxes", lambda r: r["iou"] == 0 and r["kind"] == "touch"),
+              ("iou_thres < 0", lambda r: r["iou"] < 0 and not r["zero"]), ("exact duplicates", lambda r: r["jitter"] == 0 and not r["zero"] and r["kind"] == "cluster"),
+              ("duplicated zero-area boxes", lambda r: r["zero"] > 0 and r["jitter"] == 0), ("score ties across the candidate set", lambda r: r["equal_scores"]),
+              ("class 61 at max_wh = 7680", lambda r: r["kind"] == "clsoff" and r["nc"] == 62 and r["max_wh"] == 7680.0),
+              ("the rounding pairs", lambda r: r["kind"] == "rounding"), ("more candidates than NMS_MAX_NMS", lambda r: r["kind"] == "maxnms" and r["n"] > NMS_MAX_NMS + 100))
+    gaps += [f"yolo_nms_kernel: no row with {what}" for what, f in checks if not any(f(r) for r in nms_rows)]
+    for dt in ("f16", "f32"):
+        mine = [r for r in decode_rows if dt in r["dtypes"]]
+        if not mine:
+            gaps.append(f"{decode_tag(dt)} has no row")
+        gaps += [f"{decode_tag(dt)}: no row with nc = {nc}" for nc in (1, 7, 8, 62, 80, DECODE_NC_MAX[dt]) if not any(r["nc"] == nc for r in mine)]
+        gaps += [f"{decode_tag(dt)}: no row with {nl} level(s)" for nl in (1, 2, 3) if not any(len(r["levels"]) == nl for r in mine)]
+        for what, f in (("B * A = 1", lambda r: r["B"] * r["A"] == 1), ("B * A = 64", lambda r: r["B"] * r["A"] == 64), ("B * A % 64 != 0", lambda r: r["B"] * r["A"] % 64),
+                        ("box_ld > 64", lambda r: r["box_extra"] > 0), ("cls_ld past the padded classes", lambda r: r["cls_extra"] > 0),
+                        ("the optional outputs", lambda r: r["optional"]), ("best-class ties", lambda r: r["kind"] == "ties"), ("saturated logits", lambda r: r["kind"] == "saturated"),
+                        ("the decode -> NMS chain", lambda r: r["chain"]), ("every seam inside a workgroup", lambda r: set(r["straddle"]) == {"image", "level1", "level2"})):
+            if not any(f(r) for r in mine):
+                gaps.append(f"{decode_tag(dt)}: no row with {what}")
+    return gaps
+
+
+def test_nms_pick_mirrors_nms_launch_and_the_kernel():
+    src = detect_sources()
+    assert detect_gaps(src) == [], detect_gaps(src)
+    assert nms_pick(1, 0) == (False, 1024, 1, 256, True) and nms_pick(1024, 1024) == (False, 1024, 1024, 256, False)
+    assert nms_pick(1024, 256)[4] and not nms_pick(1024, 257)[4] and nms_pick(16384, 4096)[4] and not nms_pick(16384, 4097)[4]
+    assert nms_pick(2049, 2048)[3] == 256 and nms_pick(2049, 2049)[3] == 1024
+    assert nms_pick(16384, 100)[0] is False and nms_pick(16385, 100)[:2] == (True, 32768) and nms_pick(65536, 65536)[1:3] == (65536, 65536)
+    for P in (1024, 2048, 4096, 8192, 16384):                              # without GK the geometry fits behind the keys exactly up to n = P / 4
+        assert all(nms_pick(P, n)[4] == (n <= P // 4) for n in range(0, P + 1, 1 if P == 1024 else 61)) and nms_pick(P, P // 4 + 1)[4] is False
+    assert nms_workspace(3, 16385) % 16 == 0 and (3 * 16385 * NMS_WS_RECORD + 256) % 16 != 0 and nms_workspace(1, 1) == 288
+    assert NMS_CAND_BYTES + 8 == NMS_WS_RECORD
+    assert {(g, t, l) for g in (False, True) for t in (256, 1024) for l in (False, True) if not (g and l)} == set(NMS_COMBOS)
+
+
+def test_detect_rows_are_well_formed():
+    ids = [r["id"] for r in NMS_ROWS] + [r["id"] for r in DECODE_ROWS]
+    assert len(ids) == len(set(ids)), "duplicate row ids"
+    for r in NMS_ROWS:
+        assert (r["gk"], r["P"], r["Ps"], r["nthr"], r["geo_lds"]) == nms_pick(r["A"], r["n"]) and r["expect"] == nms_tag(r["A"] > NMS_LDS_A), r["id"]
+        assert 0 <= r["n"] <= r["A"] <= NMS_MAX_A and 0 < r["max_det"] <= NMS_MAX_DET and r["conf"] >= 0 and r["kind"] in NMS_KINDS and r["entry"] in ("best", "both"), r["id"]
+        assert r["B"] * (4 + r["nc"]) * r["A"] * 4 <= 32 << 20, f"{r['id']}: the input stays under 32 MiB"
+    assert sum(r["entry"] == "both" for r in NMS_ROWS) >= 10
+    assert any(c["max_det"] == NMS_MAX_DET + 1 for c in NMS_REFUSED)
+    for r in DECODE_ROWS:
+        assert set(r["dtypes"]) <= {"f16", "f32"} and r["kind"] in ("rand", "ties", "saturated") and 1 <= len(r["levels"]) <= 3, r["id"]
+        assert all(r["nc"] <= DECODE_NC_MAX[dt] and r["box_extra"] % 8 == 0 and r["cls_extra"] % 8 == 0 for dt in r["dtypes"]), r["id"]
+    for dt, vec in (("f16", 8), ("f32", 4)):                               # the LDS tile: 64 rows of ncp + 1 floats in 64 KiB
+        ncp = lambda nc: (nc + vec - 1) // vec * vec
+        assert 64 * (ncp(DECODE_NC_MAX[dt]) + 1) * 4 <= 65536 < 64 * (ncp(DECODE_NC_MAX[dt] + 1) + 1) * 4
+        assert any(c["dt"] == dt and c["nc"] == DECODE_NC_MAX[dt] + 1 for c in DECODE_REFUSED)
+    assert {c.get("best") for c in DECODE_REFUSED} >= {"score", "cls"}
+    vis = detect_sources()["vision_ops.hip"]
+    assert "const size_t lds = (size_t)64 * (ncp + 1) * sizeof(float);" in vis and 'CVMI_CHECK(lds <= 64 * 1024, "detect_decode: nc too large for the LDS tile");' in vis
+
+
+def test_a_removed_detect_row_or_a_moved_threshold_is_caught():
+    src = detect_sources()
+    drop = lambda *rids: detect_gaps(src, nms_rows=[r for r in NMS_ROWS if r["id"] not in rids])
+    assert drop("lds_1024_nogeo") == [] and "yolo_nms_kernel (gk, nthr, geo_lds) = (False, 1024, False) has no row" in drop("lds_1024_nogeo", "n4097_quarter_p16384_plus1", "full_16384", "md4096_more")
+    assert drop("lds_1024_geo", "n2049_geo", "n4096_quarter_p16384")[0] == "yolo_nms_kernel (gk, nthr, geo_lds) = (False, 1024, True) has no row"
+    assert drop("gk_1024_b1", "max_nms")[0] == "yolo_nms_kernel (gk, nthr, geo_lds) = (True, 1024, False) has no row"
+    assert drop("n2048") == ["yolo_nms_kernel: no row with n = 2048"]
+    assert drop("n257_quarter_p1024_plus1") == ["yolo_nms_kernel: no row with n = 257", "yolo_nms_kernel: no row with n = P / 4 + 1 at P = 1024"]
+    assert drop("n4096_quarter_p16384") == ["yolo_nms_kernel: no row with n = P / 4 at P = 16384"]
+    assert drop("full_16384") == ["yolo_nms_kernel: no row with A = 16384", "yolo_nms_kernel: no row with n = A = P at P = 16384"]
+    assert drop("gk_256_odd") == ["yolo_nms_kernel: no row with A = 16385", "yolo_nms_kernel: no row with a GK row with B * A odd"]
+    assert drop("md4096_more") == ["yolo_nms_kernel: no row with max_det = NMS_MAX_DET with more survivors"]
+    assert drop("max_nms") == ["yolo_nms_kernel: no row with more candidates than NMS_MAX_NMS"]
+    assert drop("rounding") == ["yolo_nms_kernel: no row with the rounding pairs"]
+    assert drop("a65536_second_grid_pass") == ["yolo_nms_kernel: no row with a cvmi_yolo_nms row with B * A > 4096 * 256"]
+    ddrop = lambda rid: detect_gaps(src, decode_rows=[r for r in DECODE_ROWS if r["id"] != rid])
+    assert ddrop("l3_ncmax_f32") == ["detect_decode_kernel<float>: no row with nc = 252"]
+    assert ddrop("l1_1") == [f"detect_decode_kernel<{t}>: no row with {w}" for t in ("_Float16", "float") for w in ("nc = 1", "B * A = 1")]
+    assert ddrop("saturated") == [f"detect_decode_kernel<{t}>: no row with saturated logits" for t in ("_Float16", "float")]
+    probe = dict(src)
+    probe["nms.hip"] = src["nms.hip"].replace("nall <= 2048 ? 256", "nall <= 4096 ? 256")
+    assert len(detect_gaps(probe)) == 1 and "the four-wave threshold" in detect_gaps(probe)[0]
+    probe["nms.hip"] = src["nms.hip"].replace("constexpr int NMS_MAX_NMS = 30000;", "constexpr int NMS_MAX_NMS = 32768;")
+    assert len(detect_gaps(probe)) == 1 and "NMS_MAX_NMS" in detect_gaps(probe)[0]
+    for name, text in DETECT_TAGS.items():
+        probe = dict(src)
+        probe[name] = src[name].replace(text, "")
+        assert detect_gaps(probe) == [f"{name} no longer tags its launch with {text}"]
