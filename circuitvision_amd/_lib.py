@@ -63,6 +63,8 @@ class AttnDesc(C.Structure):
         ("dqk", C.c_int), ("dv", C.c_int), ("scale", C.c_float), ("dtype", C.c_int),
         ("win", C.c_int), ("grid_h", C.c_int), ("grid_w", C.c_int), ("q_pool", C.c_int),
         ("q_bdiv", C.c_int), ("kv_bdiv", C.c_int), ("av_fp8", C.c_int), ("q_log2", C.c_int),
+        ("proj_x", C.c_void_p), ("proj_w", C.c_void_p), ("proj_gamma", C.c_void_p), ("proj_beta", C.c_void_p), ("proj_stats", C.c_void_p),
+        ("proj_ld", C.c_int), ("proj_K", C.c_int), ("proj_eps", C.c_float),
     ]
 
 

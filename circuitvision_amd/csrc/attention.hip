@@ -997,6 +997,9 @@ int launch_res64(const AttnArgs& a, hipStream_t stream) {
   return 0;
 }
 
+// ---- the same window attention fed by the qkv projection of the f32 stream in one launch (cvmi_attn_desc.proj_x)
+#include "qkv_attn.hpp"
+
 // ---- long sequences of head_dim 72 (Hiera global attention): the same inner loop, K / V streamed through two 64-key
 //      LDS buffers by DMA (no staging registers: 4 waves per SIMD); one barrier per tile publishes tile t + 1 while it
 //      drains, issued a full tile of MFMAs earlier.  Rows past Nk re-read the last key (finite; their scores are masked).
@@ -1397,7 +1400,7 @@ extern "C" int cvmi_attention_bf16(const cvmi_attn_desc* d, cvmi_stream_t stream
 #endif
 
 extern "C" int CVMI_ENTRY(cvmi_attention)(const cvmi_attn_desc* d, cvmi_stream_t stream_) {
-  CVMI_CHECK(d && d->q && d->k && d->v && d->o, "attention: null pointer");
+  CVMI_CHECK(d && d->o && (d->proj_x || (d->q && d->k && d->v)), "attention: null pointer");
 #ifndef CVMI_OPERAND_BF16
   if (d->dtype == CVMI_BF16) return cvmi_attention_bf16(d, stream_);
 #endif
@@ -1431,6 +1434,7 @@ extern "C" int CVMI_ENTRY(cvmi_attention)(const cvmi_attn_desc* d, cvmi_stream_t
     CVMI_CHECK(!d->q_pool, "attention: q_pool requires window mode");
   }
   hipStream_t stream = (hipStream_t)stream_;
+  if (d->proj_x) return qkv_attn_dispatch(d, a, stream);    // q / k / v are projected inside the launch (qkv_attn.hpp); q, k, v are not read
   if (d->dtype == CVMI_F32) {
     CVMI_CHECK(d->dqk <= 128 && d->dv <= 128, "attention(f32): head dims up to 128");
     const long long rows = (long long)d->B * d->heads * d->Nq;

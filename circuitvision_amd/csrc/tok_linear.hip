@@ -67,31 +67,13 @@ __global__ __launch_bounds__(TL_NW * 64, 2) void tok_linear_kernel(const void* _
     const float* xr = reinterpret_cast<const float*>(in) + row * (long long)in_ld;
     const float2 st = tok_ln_stats<K, 16, 2>(ex, row, xr, 8 * lh, eps);
     const float mean = st.x, rstd = st.y;
-#pragma unroll
-    for (int k = 0; k < KS; ++k) {
-      if (k % 3 == 0) __builtin_amdgcn_sched_barrier(0);      // at most 3 steps' loads in flight: no hoisting of all K/16 of them
-      const f32x4 a = *reinterpret_cast<const f32x4*>(xr + 16 * k + 8 * lh), b = *reinterpret_cast<const f32x4*>(xr + 16 * k + 8 * lh + 4);
-      const float* gp = gamma + 16 * k + 8 * lh;
-      const float* bp = beta + 16 * k + 8 * lh;
-      const f32x4 g0 = *reinterpret_cast<const f32x4*>(gp), g1 = *reinterpret_cast<const f32x4*>(gp + 4);
-      const f32x4 b0 = *reinterpret_cast<const f32x4*>(bp), b1 = *reinterpret_cast<const f32x4*>(bp + 4);
-      f16x8 h;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        h[e] = (f16)((a[e] - mean) * rstd * g0[e] + b0[e]);
-        h[4 + e] = (f16)((b[e] - mean) * rstd * g1[e] + b1[e]);
-      }
-      xn[k] = __builtin_bit_cast(u32x4, h);
-    }
+    tok_ln_fragments<KS>(xr, gamma, beta, mean, rstd, lh, xn);
   } else {
     const f16* xr = reinterpret_cast<const f16*>(in) + row * (long long)in_ld;
 #pragma unroll
     for (int k = 0; k < KS; ++k) xn[k] = *reinterpret_cast<const u32x4*>(xr + 16 * k + 8 * lh);
   }
-  {
-    const u32x4 one = {lh == 0 ? CVMI_ONE16X2 : 0u, 0u, 0u, 0u};   // bias step: constant-1 columns k = K, K + 1
-    xn[KS] = one;
-  }
+  xn[KS] = tok_bias_fragment(lh);                           // bias step: constant-1 columns k = K, K + 1
 
   // Epilogue of chunk j: lane (row lr, half lh), register group g -> channels 32 j + 8 g + 4 lh .. + 3.
   // RES: the four residual loads of chunk j - 1 are ordinary loads issued right after the barrier of interval j; their first use sits in
@@ -149,29 +131,8 @@ __global__ __launch_bounds__(TL_NW * 64, 2) void tok_linear_kernel(const void* _
   };
 
   constexpr int PF = 8;                         // ring depth
-  // The K/16 + 1 MFMAs of chunk j.  A-fragment ring: PF ds_read_b128 stay in flight ahead of the MFMA that consumes them.  The reads and
-  // their COUNTED waits are inline asm: left to hipcc the same source becomes read -> lgkmcnt(0) -> MFMA (every MFMA then waits a full LDS
-  // round trip, and the matrix pipe idles two thirds of the time).  LDS returns data in issue order, so before MFMA f at most
-  // min(PF - 1, KS1 - 1 - f) younger reads may still be outstanding; nothing else of the wave may touch LDS inside the sequence, and no
-  // run-time branch may sit between a read and its wait (hipcc may copy values that live across a block boundary, in-flight or not).
-  auto mfma_seq = [&](int j) -> f32x16 {
-    const char* const buf = smem + (j % SLOTS) * CHB + lane * 16;
-    u32x4 ring[PF];
-    const unsigned lbase = (unsigned)(size_t)((const __attribute__((address_space(3))) char*)buf);
-#pragma unroll
-    for (int f = 0; f < PF; ++f) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(ring[f]) : "v"(lbase), "i"(f * 1024));
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-    for (int f = 0; f < KS1; ++f) {
-      ring_wait(ring[f % PF], (KS1 - 1 - f) < (PF - 1) ? (KS1 - 1 - f) : (PF - 1));
-      const f16x8 a = __builtin_bit_cast(f16x8, ring[f % PF]);
-      acc = CVMI_MFMA_32X32X16(a, __builtin_bit_cast(f16x8, xn[f]), acc, 0, 0, 0);
-      if (f + PF < KS1) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(ring[f % PF]) : "v"(lbase), "i"((f + PF) * 1024));
-    }
-    return acc;
-  };
+  // The K/16 + 1 MFMAs of chunk j against its ring slot: the counted A-fragment ring of tok_stream.hpp (tok_mfma_chunk)
+  auto mfma_seq = [&](int j) -> f32x16 { return tok_mfma_chunk<KS1, PF>(smem + (j % SLOTS) * CHB + lane * 16, xn); };
   tok_pingpong<RES, SLOTS - 1>(wv < TL_NW / 2, 0, nch, res_load, mfma_seq, issue_chunk, epilogue,
                                [](f32x16& acc) { asm volatile("s_waitcnt vmcnt(0)" : "+v"(acc) :: "memory"); });
   if constexpr (RES) {

@@ -21,12 +21,12 @@ struct TlExtra {
   int stats_parts;          // 0: stats_in holds (mean, rstd) per row; P > 0: P per column slice (mean, sum of squared deviations) pairs per row
 };
 
-// ---- weight stream: the NP 1-KiB pieces of one chunk, L2 -> its ring slot; wave w moves pieces w, w + TL_NW, ...
-template <int NP> __device__ __forceinline__ void tok_issue_chunk(const char* chunk, char* slot, int wv, int lane) {
+// ---- weight stream: the NP 1-KiB pieces of one chunk, L2 -> its ring slot; wave w moves pieces w, w + NWV, ... (NWV = waves per workgroup)
+template <int NP, int NWV = TL_NW> __device__ __forceinline__ void tok_issue_chunk(const char* chunk, char* slot, int wv, int lane) {
   const char* src = chunk + lane * 16;
 #pragma unroll
-  for (int f = 0; f < (NP + TL_NW - 1) / TL_NW; ++f) {
-    const int fi = f * TL_NW + wv;
+  for (int f = 0; f < (NP + NWV - 1) / NWV; ++f) {
+    const int fi = f * NWV + wv;
     if (fi < NP)
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + (size_t)fi * 1024),
                                        (__attribute__((address_space(3))) void*)(slot + fi * 1024), 16, 0, 0);
@@ -102,6 +102,55 @@ __device__ __forceinline__ float2 tok_ln_stats(const TlExtra& ex, long long row,
     }
   }
   return shifted_mean_rstd(x0, row_sum<LPR>(s), row_sum<LPR>(q), (float)K, eps);
+}
+
+// ---- B fragments of the 32x32x16 format from the f32 stream (tok_linear.hip LN = 1, qkv_attn.hpp): one pass over the row that writes
+// lane (row, half lh)'s LayerNorm'd values in[row][16 s + 8 lh .. + 7] of every k-step s as 16-bit fragments.
+// GROUP: k-steps whose loads may be in flight together (tok_linear.hip: 3, its register budget; qkv_attn.hpp: the whole row in one round trip).
+template <int KS, int GROUP = 3> __device__ __forceinline__ void tok_ln_fragments(const float* xr, const float* gamma, const float* beta, float mean, float rstd,
+                                                                                  int lh, u32x4* xn) {
+#pragma unroll
+  for (int k = 0; k < KS; ++k) {
+    if (k % GROUP == 0) __builtin_amdgcn_sched_barrier(0);  // at most GROUP steps' loads in flight: no hoisting of all K/16 of them
+    const f32x4 a = *reinterpret_cast<const f32x4*>(xr + 16 * k + 8 * lh), b = *reinterpret_cast<const f32x4*>(xr + 16 * k + 8 * lh + 4);
+    const float* gp = gamma + 16 * k + 8 * lh;
+    const float* bp = beta + 16 * k + 8 * lh;
+    const f32x4 g0 = *reinterpret_cast<const f32x4*>(gp), g1 = *reinterpret_cast<const f32x4*>(gp + 4);
+    const f32x4 b0 = *reinterpret_cast<const f32x4*>(bp), b1 = *reinterpret_cast<const f32x4*>(bp + 4);
+    f16x8 h;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      h[e] = (f16)((a[e] - mean) * rstd * g0[e] + b0[e]);
+      h[4 + e] = (f16)((b[e] - mean) * rstd * g1[e] + b1[e]);
+    }
+    xn[k] = __builtin_bit_cast(u32x4, h);
+  }
+}
+// the bias k-step of that format: constant-1 columns k = K, K + 1 (the packed weights carry the bias there as a hi + lo pair)
+__device__ __forceinline__ u32x4 tok_bias_fragment(int lh) { return (u32x4){lh == 0 ? CVMI_ONE16X2 : 0u, 0u, 0u, 0u}; }
+
+// ---- the KS1 = K/16 + 1 MFMAs of one 32-channel chunk of the 32x32x16 format: buf = the lane's 16 bytes in the chunk's first 1-KiB piece.
+// A-fragment ring: PF ds_read_b128 stay in flight ahead of the MFMA that consumes them.  The reads and their COUNTED waits are inline asm:
+// left to hipcc the same source becomes read -> lgkmcnt(0) -> MFMA (every MFMA then waits a full LDS round trip, and the matrix pipe idles
+// two thirds of the time).  LDS returns data in issue order, so before MFMA f at most min(PF - 1, KS1 - 1 - f) younger reads may still be
+// outstanding; nothing else of the wave may touch LDS inside the sequence, and no run-time branch may sit between a read and its wait
+// (hipcc may copy values that live across a block boundary, in-flight or not).
+template <int KS1, int PF> __device__ __forceinline__ f32x16 tok_mfma_chunk(const char* buf, const u32x4* xn) {
+  u32x4 ring[PF];
+  const unsigned lbase = (unsigned)(size_t)((const __attribute__((address_space(3))) char*)buf);
+#pragma unroll
+  for (int f = 0; f < PF; ++f) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(ring[f]) : "v"(lbase), "i"(f * 1024));
+  f32x16 acc;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+  for (int f = 0; f < KS1; ++f) {
+    ring_wait(ring[f % PF], (KS1 - 1 - f) < (PF - 1) ? (KS1 - 1 - f) : (PF - 1));
+    const f16x8 a = __builtin_bit_cast(f16x8, ring[f % PF]);
+    acc = CVMI_MFMA_32X32X16(a, __builtin_bit_cast(f16x8, xn[f]), acc, 0, 0, 0);
+    if (f + PF < KS1) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(ring[f % PF]) : "v"(lbase), "i"((f + PF) * 1024));
+  }
+  return acc;
 }
 
 // ---- POOL form: rows are tokens of a [B, H, W] grid (pool_w = W, pool_hw2 = (H / 2)(W / 2)) and a lane quad holds the four tokens of one

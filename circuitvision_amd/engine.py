@@ -613,6 +613,47 @@ class PackedTokLinear:
         self.param_bytes = N * K * 2
 
 
+def qkv_attn_rows(heads, hd=72):
+    """Row order of the packed weight of the fused qkv + window-attention launch (csrc/qkv_attn.hpp): for every packed row the row of the
+    [3 * heads * hd, K] qkv matrix it holds, -1 = a zero row.  Head by head: three 32-row chunks of q_h in the order that turns the MFMA's
+    accumulator (lane half lh, register 4 g + e <-> chunk row 8 g + 4 lh + e) into the B fragments of the score product (q channel
+    32 c + 16 (g >> 1) + 8 lh + 4 (g & 1) + e), then k_h | v_h in natural order, padded to five chunks."""
+    C_ = heads * hd
+    rows = []
+    for h in range(heads):
+        for c in range(3):
+            for r in range(32):
+                g, lh, e = r >> 3, (r >> 2) & 1, r & 3
+                d = 32 * c + 16 * (g >> 1) + 8 * lh + 4 * (g & 1) + e
+                rows.append(h * hd + d if d < hd else -1)
+        rows += [C_ + h * hd + n if n < hd else 2 * C_ + h * hd + n - hd if n < 2 * hd else -1 for n in range(160)]
+    return rows
+
+
+def qkv_attn_supported(dim, dout, heads, ws, q_pool, dtype, nwin):
+    """The shapes the fused launch is built for (cvmi_attention with cvmi_attn_desc.proj_x refuses the rest): 8 x 8-window Hiera blocks of
+    input width 144 -- plain with 2 heads of 72, or the q-pooled 144 -> 288 transition with 4 -- in a 16-bit dtype, a whole number of
+    two-window workgroups."""
+    return is16(dtype) and dim == 144 and ws == 8 and nwin % 2 == 0 and (dout, heads) == ((288, 4) if q_pool else (144, 2))
+
+
+class PackedQkvAttn:
+    """The qkv projection of a Hiera block for the fused qkv + window-attention launch: the rows of W / b in qkv_attn_rows order (zero rows
+    where it says -1), in PackedTokLinear's format -- no format of its own."""
+
+    def __init__(self, w, b, heads, device="cuda", dtype=F16):
+        N, K = w.shape
+        assert N % (3 * heads) == 0
+        self.rows = qkv_attn_rows(heads, N // (3 * heads))
+        idx = torch.tensor(self.rows)
+        keep = (idx >= 0).float()
+        b = b if b is not None else torch.zeros(N)
+        pt = PackedTokLinear(w[idx.clamp(min=0)] * keep[:, None], b[idx.clamp(min=0)] * keep, device, dtype)
+        self.w, self.bias = pt.w, pt.bias                     # (.w / .bias: what distributed.packed_tensors broadcasts)
+        self.N, self.K, self.heads, self.dtype = N, K, heads, dtype
+        self.param_bytes = pt.param_bytes
+
+
 def tok_linear_stats_parts(rows, K, N):
     """Slices P of the LayerNorm statistics a residual-form op_tok_linear of this shape writes: 0 = [rows, 2] of (mean, rstd); P > 0 = [rows, P, 2]
     of per-slice (mean, sum of squared deviations), to be consumed with stats_parts = P (small launches share row blocks: cvmi355.h)."""

@@ -29,9 +29,9 @@ import torch.nn.functional as TF
 
 from . import _lib
 from ._lib import ACT_GELU, ACT_NONE, ACT_RELU, ACT_SIGMOID, BF16, F16, F32
-from .engine import (ESIZE, TORCH_DTYPE, is16, Buf, PackedConv, PackedHieraMlp, PackedTokLinear, Plan, Rows, hiera_mlp_supported, make_attn_desc, op_attention,
+from .engine import (ESIZE, TORCH_DTYPE, is16, Buf, PackedConv, PackedHieraMlp, PackedQkvAttn, PackedTokLinear, Plan, Rows, hiera_mlp_supported, make_attn_desc, op_attention,
                      op_call, op_cast, op_conv, op_hiera_mlp, op_layernorm, op_maxpool2, op_tok_linear, op_tok_linear_pool, require_gpu, row_stats_supported,
-                     tok_linear_stats_parts, tok_linear_supported)
+                     qkv_attn_supported, tok_linear_stats_parts, tok_linear_supported)
 
 LOG2E = 1.4426950408889634
 HIERA_L = dict(embed_dim=144, num_heads=2, stages=(2, 6, 36, 4), global_att_blocks=(23, 33, 43), window_spec=(8, 4, 16, 8))
@@ -213,6 +213,8 @@ class Sam2Weights:
         self.use_tok = os.environ.get("CVMI_SAM_TOKLIN", "1") != "0"
         # Hiera q rows carry scale * log2(e) (16-bit plans): see _linear(row_scale=) and cvmi_attn_desc.q_log2
         self.q_log2 = is16(dtype) and os.environ.get("CVMI_SAM_QLOG2", "1") != "0"
+        # 8 x 8-window blocks of input width 144 (stage 1 and the transition into stage 2): qkv + window attention in one launch (csrc/qkv_attn.hpp); "0" restores the two launches
+        self.qkv_attn = os.environ.get("CVMI_SAM_QKVATTN", "1") != "0"
         self.param_bytes = 0
         self.flops_per_image = 0
         self._trunk()
@@ -227,7 +229,7 @@ class Sam2Weights:
         self.param_bytes += pc.param_bytes
         return pc
 
-    def _linear(self, key, mod, cout, cin, tok=False, row_scale=None):
+    def _linear(self, key, mod, cout, cin, tok=False, row_scale=None, fuse_heads=0):
         w, b = self.p.weight(mod, (cout, cin)), self.p.bias(mod, cout)
         if row_scale is not None:
             # (rows, factor): the attention scale * log2(e) folded into the q rows of a qkv projection, in fp32 before the weights are rounded
@@ -240,6 +242,9 @@ class Sam2Weights:
             # short-K Hiera linears also in the token-stationary kernel's fragment order (tok_linear.hip); the plan picks it
             # whenever its row count is a multiple of 256
             self.tl[key] = PackedTokLinear(w, b, self.device, self.dtype)
+            if fuse_heads:
+                # ... and, rows permuted head by head, for the fused qkv + window-attention launch (engine.PackedQkvAttn)
+                self.tl[key + "_attn"] = PackedQkvAttn(w, b, fuse_heads, self.device, self.dtype)
         return self._pack(key, _lin(w), b)
 
     def _norm(self, key, mod, c):
@@ -278,7 +283,8 @@ class Sam2Weights:
             b = f"{T}.blocks.{i}"
             self._norm(f"b{i}.norm1", f"{b}.norm1", dim)
             self._linear(f"b{i}.qkv", f"{b}.attn.qkv", 3 * dim_out, dim, tok=True,
-                         row_scale=(dim_out, (dim_out // heads) ** -0.5 * LOG2E) if self.q_log2 else None)
+                         row_scale=(dim_out, (dim_out // heads) ** -0.5 * LOG2E) if self.q_log2 else None,
+                         fuse_heads=heads if self.qkv_attn and qkv_attn_supported(dim, dim_out, heads, window, i in q_pool_blocks, self.dtype, 2) else 0)
             self._linear(f"b{i}.proj", f"{b}.attn.proj", dim_out, dim_out, tok=True)
             self._norm(f"b{i}.norm2", f"{b}.norm2", dim_out)
             if self.fused_mlp and hiera_mlp_supported(dim_out, self.dtype):
@@ -568,8 +574,13 @@ class Sam2Plan:
                 op_maxpool2(self.plan, f"b{i}.pool", pj.view(), short.view())
         else:
             short = x
-        qkv = self.buf(Hp, Wp, 3 * dout, tag="qkv")
-        if tok_qkv:
+        # qkv + window attention as ONE launch where the kernel is built for the block (stage 1): the qkv tensor is neither written nor read back
+        fuse_qkv = (tok_qkv and ws > 0 and f"b{i}.qkv_attn" in wt.tl and not self.av_fp8 and (ln1_stats is None or parts == 0)
+                    and qkv_attn_supported(dim, dout, heads, ws, blk["q_pool"], self.dt, B * (Hp // ws) * (Wp // ws)))
+        qkv = None if fuse_qkv else self.buf(Hp, Wp, 3 * dout, tag="qkv")
+        if fuse_qkv:
+            pass
+        elif tok_qkv:
             op_tok_linear(self.plan, f"b{i}.qkv", wt.tl[f"b{i}.qkv"], x.view(), qkv.view(), ln=(gam, bet, 1e-6), stats_in=ln1_stats, stats_parts=parts)
         else:
             self.gemm(f"b{i}.qkv", f"b{i}.qkv", xn.view(), qkv.view())
@@ -577,9 +588,22 @@ class Sam2Plan:
         OHp, OWp = (Hp // 2, Wp // 2) if blk["q_pool"] else (Hp, Wp)
         ao = self.buf(OHp, OWp, dout, tag="ao")
         es = ESIZE[self.dt]
-        base = qkv.t.data_ptr()
+        base = qkv.t.data_ptr() if qkv is not None else 0
         C3 = 3 * dout
-        if ws > 0:
+        if fuse_qkv:
+            nwin, pq = B * (H // ws) * (W // ws), wt.tl[f"b{i}.qkv_attn"]
+            xv = x.view()
+            nq = (ws // 2) ** 2 if blk["q_pool"] else ws * ws
+            desc = make_attn_desc(q=None, k=None, v=None, o=ao.t.data_ptr(), q_sb=0, q_sh=hd, q_st=C3, k_sb=0, k_sh=hd, k_st=C3, v_sb=0, v_sh=hd, v_st=C3,
+                                  o_sb=0, o_sh=hd, o_st=dout, B=nwin, heads=heads, Nq=nq, Nk=ws * ws, dqk=hd, dv=hd, scale=hd ** -0.5, dtype=self.dt,
+                                  win=ws, grid_h=H, grid_w=W, q_pool=1 if blk["q_pool"] else 0, av_fp8=0, q_log2=1 if wt.q_log2 else 0,
+                                  proj_x=xv.ptr, proj_ld=xv.ld, proj_K=dim, proj_w=pq.w.data_ptr(), proj_gamma=gam.data_ptr(), proj_beta=bet.data_ptr(),
+                                  proj_eps=1e-6, proj_stats=ln1_stats.data_ptr() if ln1_stats is not None else None)
+            rows = B * H * W
+            op_attention(self.plan, f"b{i}.attn", desc, (x, ao, pq, gam, bet, ln1_stats), bytes_=rows * dim * 4 + ao.nbytes,
+                         flops=2 * rows * C3 * dim + 4 * nwin * heads * nq * ws * ws * hd)
+            self.plan.ops[-1] = (self.plan.ops[-1][0], "attn_window") + self.plan.ops[-1][2:]
+        elif ws > 0:
             nwin = B * (Hp // ws) * (Wp // ws)
             nq = (ws // 2) ** 2 if blk["q_pool"] else ws * ws
             desc = make_attn_desc(q=base, k=base + dout * es, v=base + 2 * dout * es, o=ao.t.data_ptr(),
@@ -595,8 +619,9 @@ class Sam2Plan:
                                   o_sb=N * dout, o_sh=hd, o_st=dout, B=B, heads=heads, Nq=N, Nk=N, dqk=hd, dv=hd,
                                   scale=hd ** -0.5, dtype=self.dt, win=0, grid_h=0, grid_w=0, q_pool=0, av_fp8=self.av_fp8, q_log2=1 if wt.q_log2 else 0)
             fl = 4 * B * heads * N * N * hd
-        op_attention(self.plan, f"b{i}.attn", desc, (qkv, ao), bytes_=qkv.nbytes + ao.nbytes, flops=fl)
-        self.plan.ops[-1] = (self.plan.ops[-1][0], "attn_global" if ws == 0 else "attn_window") + self.plan.ops[-1][2:]
+        if not fuse_qkv:
+            op_attention(self.plan, f"b{i}.attn", desc, (qkv, ao), bytes_=qkv.nbytes + ao.nbytes, flops=fl)
+            self.plan.ops[-1] = (self.plan.ops[-1][0], "attn_global" if ws == 0 else "attn_window") + self.plan.ops[-1][2:]
         # x = shortcut + proj(attn)   (in place on the f32 residual stream)
         tok_out = not padded and (B * OH * OW) % 256 == 0
         # norm2's statistics travel from the launch that writes x to the launch that normalises it (fc1 then reads x once, not twice)

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define CVMI_VERSION 125
+#define CVMI_VERSION 126
 
 typedef void* cvmi_stream_t; /* hipStream_t */
 
@@ -183,6 +183,19 @@ typedef struct cvmi_attn_desc {
   int q_log2;                /* 1: q was produced already multiplied by scale * log2(e) (e.g. folded into the rows of the projection that makes it):
                                 softmax(q k^T) is then exp2 of the products as they stand and `scale` is ignored.  Same result as 0 with the
                                 unscaled q; the long-sequence head_dim-72 kernel uses it to carry the running maximum through the matrix pipe. */
+  /* Optional projection source (126).  proj_x != NULL: q, k and v are not read; the launch computes them itself as the rows of
+     LayerNorm(proj_x[token]) W^T + b and attends inside the windows, so the qkv tensor is never written (Hiera stage 1:
+     `attn(window_partition(qkv(norm1(x))))`, behind sam2_infer.py:226).  Built for a 16-bit dtype, win = 8, head_dim 72, proj_K = 144, an even number
+     of windows, and 2 heads (plain) or 4 heads with q_pool (the 144 -> 288 transition); every other combination is refused.  The result is
+     bit for bit that of cvmi_tok_linear into a [tokens, 3 * heads * 72] buffer followed by cvmi_attention on it. */
+  const void* proj_x;        /* f32 [img][grid_h][grid_w] token rows of proj_K values, row stride proj_ld elements */
+  const void* proj_w;        /* the qkv weight [3 * heads * 72, proj_K] + bias in cvmi_tok_linear's packed format, rows permuted and zero-padded
+                                head by head (circuitvision_amd.engine.PackedQkvAttn states the order) */
+  const float* proj_gamma;   /* LayerNorm weight / bias [proj_K] */
+  const float* proj_beta;
+  const float* proj_stats;   /* optional: (mean, rstd) per token as cvmi_tok_linear_stats / cvmi_hiera_mlp_stats write them; NULL = computed here */
+  int proj_ld, proj_K;
+  float proj_eps;
 } cvmi_attn_desc;
 int cvmi_attention(const cvmi_attn_desc* d, cvmi_stream_t stream);
 
