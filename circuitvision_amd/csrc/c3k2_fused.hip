@@ -22,9 +22,6 @@ struct C3Args {
   int H, W, tiles_x, tiles_y, shortcut, ntiles;
 };
 
-__device__ __forceinline__ void mma16(const u32x4& a, const u32x4& b, f32x16& c) {
-  c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
 __device__ __forceinline__ float silu(float v) { return v * fast_rcp(1.0f + __expf(-v)); }
 
 constexpr int odd16(int bytes) { return bytes + ((bytes / 16) % 2 == 0 ? 16 : 32); }   // row stride: odd multiple of 16 B

@@ -272,6 +272,11 @@ template <bool FAST, typename Body> __device__ __forceinline__ void with_act(int
 template <typename T> struct FastMath { static constexpr bool value = true; };
 template <> struct FastMath<float> { static constexpr bool value = false; };
 
+// one 32x32x16 MFMA on two 16-byte fragments of the translation unit's 16-bit operand type
+__device__ __forceinline__ void mma16(const u32x4& a, const u32x4& b, f32x16& c) {
+  c = CVMI_MFMA_32X32X16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+}
+
 // 16-byte chunk <-> float[VEC]
 template <typename T> __device__ __forceinline__ void unpack16(const u32x4& v, float* out);
 template <> __device__ __forceinline__ void unpack16<f16>(const u32x4& v, float* out) {

@@ -7,7 +7,7 @@
 // "lane base + compile-time tap offset" -- no per-chunk address math, and the 3x3 halo is re-read from LDS
 // instead of from L2.  Weights of the current channel chunk ([BN][KS*KS*CC]) sit in LDS next to the patch.
 // Operand roles, accumulator layout and the transposing epilogue are those of igemm.hip.
-#include "common.hpp"
+#include "conv_epilogue.hpp"
 
 namespace {
 
@@ -20,20 +20,6 @@ struct TileArgs {
   int act;
   int tiles_x, tiles_y, nb_n;
   int bias_off;                                    // LDS byte offset of the parked bias row
-};
-
-template <typename T> struct MmaT;
-template <> struct MmaT<f16> {
-  __device__ static __forceinline__ void run(const u32x4& a, const u32x4& b, f32x16& c) {
-    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-  }
-};
-template <> struct MmaT<float> {
-  __device__ static __forceinline__ void run(const u32x4& a, const u32x4& b, f32x16& c) {
-    const f32x4 fa = __builtin_bit_cast(f32x4, a), fb = __builtin_bit_cast(f32x4, b);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) c = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[e], fb[e], c, 0, 0, 0);
-  }
 };
 
 template <typename T, int KS, int S, int CC, int BN, int WM, int WN, int TH>
@@ -160,7 +146,7 @@ __global__ __launch_bounds__(256, (TH == 16 ? 2 : 3)) void conv_tile_kernel(cons
 #pragma unroll
         for (int i = 0; i < TN; ++i)
 #pragma unroll
-          for (int j = 0; j < TM; ++j) MmaT<T>::run(wf[i], xf[j], acc[i][j]);
+          for (int j = 0; j < TM; ++j) Mma<T>::run(wf[i], xf[j], acc[i][j]);
       }
     } else {
 #pragma unroll
@@ -176,7 +162,7 @@ __global__ __launch_bounds__(256, (TH == 16 ? 2 : 3)) void conv_tile_kernel(cons
 #pragma unroll
           for (int i = 0; i < TN; ++i)
 #pragma unroll
-            for (int j = 0; j < TM; ++j) MmaT<T>::run(wf[i], xf[j], acc[i][j]);
+            for (int j = 0; j < TM; ++j) Mma<T>::run(wf[i], xf[j], acc[i][j]);
         }
       }
     }
@@ -184,6 +170,8 @@ __global__ __launch_bounds__(256, (TH == 16 ? 2 : 3)) void conv_tile_kernel(cons
   __syncthreads();
 
   // ---- epilogue: bias + act -> LDS [128][BN] -> 16-byte channel-contiguous stores (+ residual) ----------
+  //      (the contract and tile_put4 are conv_epilogue.hpp's; the store loop stays written out here: on store_out_chunk a few of
+  //       these kernels need 4 to 8 more registers and three of the never-launched CC = 32 ones spill more)
   char* const Ct = smem;
   constexpr bool FAST = FastMath<T>::value;
   with_act<FAST>(p.act, [&](auto actf) {
@@ -199,14 +187,7 @@ __global__ __launch_bounds__(256, (TH == 16 ? 2 : 3)) void conv_tile_kernel(cons
           float v[4];
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] = actf(acc[i][j][4 * q + e] + bv[e]);
-          char* dst = Ct + ml * CROWB + nl * ES;
-          if constexpr (ES == 2) {
-            f16x4 hv = {(f16)v[0], (f16)v[1], (f16)v[2], (f16)v[3]};
-            *reinterpret_cast<f16x4*>(dst) = hv;
-          } else {
-            f32x4 fv = {v[0], v[1], v[2], v[3]};
-            *reinterpret_cast<f32x4*>(dst) = fv;
-          }
+          tile_put4<T>(Ct + ml * CROWB + nl * ES, v);
         }
       }
     }

@@ -31,10 +31,6 @@ struct DwPwArgs {
 constexpr int TH = 8, TW = 16, BMT = TH * TW;
 constexpr int PH = TH + 2, PW = TW + 2;
 
-__device__ __forceinline__ void mma16(const u32x4& a, const u32x4& b, f32x16& c) {
-  c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-
 // CC channels per chunk (64 or 80), NCHUNK chunks (C = CC * NCHUNK), N1P / N2P = padded widths of the pointwise / chained conv
 template <int CC, int NCHUNK, int N1P, int N2P>
 __global__ __launch_bounds__(256, (NCHUNK > 1 ? 2 : 3)) void dwpw_kernel(const DwPwArgs p) {

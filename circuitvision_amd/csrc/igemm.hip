@@ -17,7 +17,7 @@
 //
 // Pipeline: register-staged double buffer (global loads for tile t+1 are issued before the MFMAs
 // of tile t and written to the other LDS buffer after them; one barrier per K-tile).
-#include "common.hpp"
+#include "conv_epilogue.hpp"
 
 namespace {
 
@@ -42,20 +42,6 @@ struct ConvKArgs {
 
 // 16 zero bytes for every lane of an LDS-DMA instruction whose 3 x 3 tap falls outside the image (gemm256_kernel, IM2COL)
 __device__ __attribute__((aligned(256))) unsigned char cvmi_zero_page[256];
-
-template <typename T> struct Mma;
-template <> struct Mma<f16> {
-  __device__ static __forceinline__ void run(const u32x4& a, const u32x4& b, f32x16& c) {
-    c = CVMI_MFMA_32X32X16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-  }
-};
-template <> struct Mma<float> {
-  __device__ static __forceinline__ void run(const u32x4& a, const u32x4& b, f32x16& c) {
-    const f32x4 fa = __builtin_bit_cast(f32x4, a), fb = __builtin_bit_cast(f32x4, b);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) c = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[e], fb[e], c, 0, 0, 0);
-  }
-};
 
 // Workgroup index -> tile index: the hardware deals workgroups round-robin over the 8 XCDs; XCD x gets a contiguous run of tiles
 __device__ __forceinline__ int xcd_remap(int wg, int nwg) {
@@ -130,27 +116,6 @@ __device__ __forceinline__ u32x4 gather_chunk(const ConvKArgs& p, int k, int b, 
   return v;
 }
 
-// residual row of output row m: plain, a constant broadcast over the batch (res_mod rows, m % res_mod), or one image's rows
-// shared by res_rep consecutive batch entries (res_mod rows per image: entry e reads image e / res_rep)
-__device__ __forceinline__ size_t res_row(const ConvKArgs& p, int m) {
-  if (p.res_mod <= 0) return (size_t)m;
-  const int r = m % p.res_mod;
-  if (p.res_rep <= 1) return (size_t)r;
-  return (size_t)(m / p.res_mod / p.res_rep) * (size_t)p.res_mod + (size_t)r;
-}
-
-// four consecutive channels of one pixel -> their place in an epilogue's LDS tile, in the output type
-template <typename TO>
-__device__ __forceinline__ void tile_put4(char* d, const float (&v)[4]) {
-  if constexpr (sizeof(TO) == 2) {
-    f16x4 hv = {(f16)v[0], (f16)v[1], (f16)v[2], (f16)v[3]};
-    *reinterpret_cast<f16x4*>(d) = hv;
-  } else {
-    f32x4 fv = {v[0], v[1], v[2], v[3]};
-    *reinterpret_cast<f32x4*>(d) = fv;
-  }
-}
-
 // ---- shared epilogue: bias + act in registers -> LDS tile [BM][BN] (TO) -> coalesced 16-byte stores (+ residual,
 //      batch-broadcast residual, activation-after-residual, ConvTranspose scatter) -----------------------------------
 template <typename T, typename TO, int BM, int BN, int WM, int WN, int KS = 1>
@@ -169,23 +134,12 @@ __device__ __forceinline__ void gemm_epilogue(const ConvKArgs& p, f32x16 (&acc)[
   const int lr = lane & 31, lh = lane >> 5;
   const int ohow = p.OH * p.OW;
   char* const Ct = smem;
-  // Residual prefetch (full-width tiles, no scatter): the tile's residual chunks are requested before the accumulators
-  // go through LDS, so their latency overlaps the transposition instead of being paid once per store-loop iteration
-  // (loads cannot be hoisted over the stores by the compiler: res and y may be the same buffer).
-  constexpr int NCH_ = BN / OVEC, NIT = (BM * NCH_) / NT;
-  const bool res_pf = p.res != nullptr && p.shuf_c == 0 && n0 + BN <= p.N && (BM * NCH_) % NT == 0 && NIT <= 16;
-  u32x4 rv[NIT > 0 && NIT <= 16 ? NIT : 1];
-  if (res_pf) {
-#pragma unroll
-    for (int it = 0; it < (NIT <= 16 ? NIT : 0); ++it) {
-      const int idx = tid + it * NT;
-      const int row = idx / NCH_, ch = idx - row * NCH_;
-      int m = m0 + row;
-      m = m < p.M ? m : p.M - 1;
-      const size_t rpix = res_row(p, m);
-      rv[it] = *reinterpret_cast<const u32x4*>(p.res + (rpix * p.res_ld + n0 + ch * OVEC) * OES);
-    }
-  }
+  // Residual prefetch (full-width tiles, no scatter; store loops of at most 16 whole iterations)
+  constexpr int NCH = BN / OVEC;                  // 16-byte chunks per output row
+  constexpr int NPF = (BM * NCH) % NT == 0 && (BM * NCH) / NT <= 16 ? (BM * NCH) / NT : 0;
+  const bool res_pf = p.res != nullptr && p.shuf_c == 0 && n0 + BN <= p.N && NPF > 0;
+  u32x4 rv[NPF > 0 ? NPF : 1];
+  if (res_pf) { RES_PREFETCH(TO, NT, NCH, NPF, rv, p.res, p.res_ld, p.res_mod, p.res_rep, p.M, tid, m0, n0); }
   if (KS == 1 || tid < WM * WN * 64)
   with_act<FAST>(p.act_after_res ? CVMI_ACT_NONE : p.act, [&](auto actf) {
 #pragma unroll
@@ -207,25 +161,16 @@ __device__ __forceinline__ void gemm_epilogue(const ConvKArgs& p, f32x16 (&acc)[
     }
   });
   __syncthreads();
-  constexpr int NCH = BN / OVEC;                  // 16-byte chunks per output row
+  float a[OVEC];
   if (res_pf) {
 #pragma unroll
-    for (int it = 0; it < (NIT <= 16 ? NIT : 0); ++it) {
+    for (int it = 0; it < NPF; ++it) {
       const int idx = tid + it * NT;
       const int row = idx / NCH, ch = idx - row * NCH;
       const int m = m0 + row;
-      if (m < p.M) {
-        float a[OVEC], r[OVEC];
-        unpack16<TO>(*reinterpret_cast<const u32x4*>(Ct + row * CROWB + ch * 16), a);
-        unpack16<TO>(rv[it], r);
-#pragma unroll
-        for (int e = 0; e < OVEC; ++e) a[e] += r[e];
-        if (p.act_after_res) {
-#pragma unroll
-          for (int e = 0; e < OVEC; ++e) a[e] = act_apply<FAST>(a[e], p.act);
-        }
-        *reinterpret_cast<u32x4*>(p.y + ((size_t)m * p.y_ld + n0 + ch * OVEC) * OES) = pack16<TO>(a);
-      }
+      if (m < p.M)
+        store_out_chunk<TO, FAST, false>(p.y + ((size_t)m * p.y_ld + n0 + ch * OVEC) * OES, *reinterpret_cast<const u32x4*>(Ct + row * CROWB + ch * 16), a,
+                                         n0 + ch * OVEC, p.N, ResHeld{rv[it]}, p.act_after_res, p.act);
     }
     return;
   }
@@ -233,8 +178,8 @@ __device__ __forceinline__ void gemm_epilogue(const ConvKArgs& p, f32x16 (&acc)[
     const int row = idx / NCH, ch = idx - row * NCH;
     const int m = m0 + row, n = n0 + ch * OVEC;
     if (m >= p.M || n >= p.N) continue;
-    u32x4 cv = *reinterpret_cast<const u32x4*>(Ct + row * CROWB + ch * 16);
-    size_t ypix = (size_t)m, rpix = res_row(p, m);
+    const u32x4 cv = *reinterpret_cast<const u32x4*>(Ct + row * CROWB + ch * 16);
+    size_t ypix = (size_t)m, rpix = res_row(m, p.res_mod, p.res_rep);
     int nn = n;
     if (p.shuf_c > 0) {                            // ConvTranspose 2x2/s2: scatter to the 2x grid
       const int q = n / p.shuf_c;
@@ -244,37 +189,7 @@ __device__ __forceinline__ void gemm_epilogue(const ConvKArgs& p, f32x16 (&acc)[
       ypix = ((size_t)b * (2 * p.OH) + 2 * oy + (q >> 1)) * (size_t)(2 * p.OW) + 2 * ox + (q & 1);
       rpix = p.res_rep > 1 ? ((size_t)(b / p.res_rep) * (2 * p.OH) + 2 * oy + (q >> 1)) * (size_t)(2 * p.OW) + 2 * ox + (q & 1) : ypix;
     }
-    char* yp = p.y + (ypix * p.y_ld + nn) * OES;
-    if (n + OVEC <= p.N) {
-      if (p.res || p.act_after_res) {
-        float a[OVEC];
-        unpack16<TO>(cv, a);
-        if (p.res) {
-          float r[OVEC];
-          unpack16<TO>(*reinterpret_cast<const u32x4*>(p.res + (rpix * p.res_ld + nn) * OES), r);
-#pragma unroll
-          for (int e = 0; e < OVEC; ++e) a[e] += r[e];
-        }
-        if (p.act_after_res) {
-#pragma unroll
-          for (int e = 0; e < OVEC; ++e) a[e] = act_apply<FAST>(a[e], p.act);
-        }
-        cv = pack16<TO>(a);
-      }
-      *reinterpret_cast<u32x4*>(yp) = cv;
-    } else {                                       // ragged channel tail: element-wise
-      float a[OVEC];
-      unpack16<TO>(cv, a);
-#pragma unroll
-      for (int e = 0; e < OVEC; ++e) {
-        if (n + e < p.N) {
-          float av = a[e];
-          if (p.res) av += (float)reinterpret_cast<const TO*>(p.res + (rpix * p.res_ld + nn) * OES)[e];
-          if (p.act_after_res) av = act_apply<FAST>(av, p.act);
-          reinterpret_cast<TO*>(yp)[e] = (TO)av;
-        }
-      }
-    }
+    store_out_chunk<TO, FAST, true>(p.y + (ypix * p.y_ld + nn) * OES, cv, a, n, p.N, ResLoad<TO>{p.res, p.res_ld, rpix, nn}, p.act_after_res, p.act);
   }
 }
 
@@ -929,24 +844,9 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(const ConvKArgs p) {
       const int row = idx / NCH, ch = idx - row * NCH;
       const int m = m0 + row, n = n0 + pass * CW + ch * OVEC;
       if (m >= p.M || n >= p.N) continue;
-      u32x4 cv = *reinterpret_cast<const u32x4*>(Ct + row * CROWB + ch * 16);
-      const size_t rpix = p.res_mod > 0 ? (size_t)(m % p.res_mod) : (size_t)m;
-      if (p.res || p.act_after_res) {
-        float a[OVEC];
-        unpack16<TO>(cv, a);
-        if (p.res) {
-          float r[OVEC];
-          unpack16<TO>(*reinterpret_cast<const u32x4*>(p.res + (rpix * p.res_ld + n) * OES), r);
-#pragma unroll
-          for (int e = 0; e < OVEC; ++e) a[e] += r[e];
-        }
-        if (p.act_after_res) {
-#pragma unroll
-          for (int e = 0; e < OVEC; ++e) a[e] = act_apply<true>(a[e], p.act);
-        }
-        cv = pack16<TO>(a);
-      }
-      *reinterpret_cast<u32x4*>(p.y + ((size_t)m * p.y_ld + n) * OES) = cv;
+      float a[OVEC];
+      store_out_chunk<TO, true, false>(p.y + ((size_t)m * p.y_ld + n) * OES, *reinterpret_cast<const u32x4*>(Ct + row * CROWB + ch * 16), a, n, p.N,
+                                       ResLoad<TO>{p.res, p.res_ld, res_row(m, p.res_mod, 0), n}, p.act_after_res, p.act);      // (res_rep > 1 never comes here: launch_typed)
     }
     if (pass + 1 < NPASS) __syncthreads();
   }
@@ -1284,16 +1184,7 @@ __global__ __launch_bounds__(512, 1) void gemm256x192_kernel(const ConvKArgs p) 
   for (int pass = 0; pass < NPASS; ++pass) {
     const bool full = n0 + pass * CW + CW <= p.N;
     u32x4 rv[NIT];
-    if (p.res && full) {
-#pragma unroll
-      for (int it = 0; it < NIT; ++it) {
-        const int idx = tid + it * 512, row = idx / NCH, ch = idx - row * NCH;
-        int m = m0 + row;
-        m = m < p.M ? m : p.M - 1;
-        const size_t rpix = p.res_mod > 0 ? (size_t)(m % p.res_mod) : (size_t)m;
-        rv[it] = *reinterpret_cast<const u32x4*>(p.res + (rpix * p.res_ld + n0 + pass * CW + ch * OVEC) * OES);
-      }
-    }
+    if (p.res && full) { RES_PREFETCH(TO, 512, NCH, NIT, rv, p.res, p.res_ld, p.res_mod, 0, p.M, tid, m0, n0 + pass * CW); }      // (res_rep > 1 never comes here: launch_typed)
     if (NPASS == 1 || wh == pass) {
       const int cbase = NPASS == 1 ? wh * 96 : 0;
       with_act<true>(p.act_after_res ? CVMI_ACT_NONE : p.act, [&](auto actf) {
@@ -1322,37 +1213,20 @@ __global__ __launch_bounds__(512, 1) void gemm256x192_kernel(const ConvKArgs p) 
       const int idx = tid + it * 512, row = idx / NCH, ch = idx - row * NCH;
       const int m = m0 + row, n = n0 + pass * CW + ch * OVEC;
       if (m >= p.M || n >= p.N) continue;
-      u32x4 cv = *reinterpret_cast<const u32x4*>(Ct + row * CROWB + ch * 16);
-      if (p.res || p.act_after_res) {
-        float a[OVEC];
-        unpack16<TO>(cv, a);
-        if (p.res) {
-          float r[OVEC];
-          if (full) {
-            unpack16<TO>(rv[it], r);
-          } else {
-            const size_t rpix = p.res_mod > 0 ? (size_t)(m % p.res_mod) : (size_t)m;
-            unpack16<TO>(*reinterpret_cast<const u32x4*>(p.res + (rpix * p.res_ld + n) * OES), r);
-          }
-#pragma unroll
-          for (int e = 0; e < OVEC; ++e) a[e] += r[e];
-        }
-        if (p.act_after_res) {
-#pragma unroll
-          for (int e = 0; e < OVEC; ++e) a[e] = act_apply<true>(a[e], p.act);
-        }
-        cv = pack16<TO>(a);
-        if constexpr (OES == 4) {
-          // row statistics for the NEXT LayerNorm over these rows: this thread's 4 values -> (sum, sum of squares), parked in the chunk slot it
-          // has just consumed (no other thread reads that slot), reduced per row below
-          if (p.stats) {                                      // (mean of the 4 values, their squared deviations from it)
-            const float m4 = 0.25f * ((a[0] + a[1]) + (a[2] + a[3]));
-            const float d0 = a[0] - m4, d1 = a[1] - m4, d2 = a[2] - m4, d3 = a[3] - m4;
-            *reinterpret_cast<float2*>(Ct + row * CROWB + ch * 16) = make_float2(m4, fmaf(d0, d0, fmaf(d1, d1, fmaf(d2, d2, d3 * d3))));
-          }
+      char* const yp = p.y + ((size_t)m * p.y_ld + n) * OES;
+      const u32x4 cv = *reinterpret_cast<const u32x4*>(Ct + row * CROWB + ch * 16);
+      float a[OVEC];
+      const bool fin = p.res && full ? store_out_chunk<TO, true, false>(yp, cv, a, n, p.N, ResHeld{rv[it]}, p.act_after_res, p.act)
+                                     : store_out_chunk<TO, true, false>(yp, cv, a, n, p.N, ResLoad<TO>{p.res, p.res_ld, res_row(m, p.res_mod, 0), n}, p.act_after_res, p.act);
+      if constexpr (OES == 4) {
+        // row statistics for the NEXT LayerNorm over these rows: this thread's 4 finished values -> (their mean, their squared deviations from it),
+        // parked in the chunk slot it has just consumed (no other thread reads that slot), reduced per row below
+        if (fin && p.stats) {
+          const float m4 = 0.25f * ((a[0] + a[1]) + (a[2] + a[3]));
+          const float d0 = a[0] - m4, d1 = a[1] - m4, d2 = a[2] - m4, d3 = a[3] - m4;
+          *reinterpret_cast<float2*>(Ct + row * CROWB + ch * 16) = make_float2(m4, fmaf(d0, d0, fmaf(d1, d1, fmaf(d2, d2, d3 * d3))));
         }
       }
-      *reinterpret_cast<u32x4*>(p.y + ((size_t)m * p.y_ld + n) * OES) = cv;
     }
     if constexpr (OES == 4) {
       if (p.stats) {                                        // (uniform; the host admits it only with a residual and whole 96-column slices)

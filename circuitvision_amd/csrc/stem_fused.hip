@@ -31,10 +31,6 @@ constexpr int TROW = (SW / 2 + 1) * 16;           // 17 slots per (parity, row)
 constexpr int TPLANE = SH * TROW;                 // one (chunk, parity) plane
 __device__ __forceinline__ int t_off(int ck, int sy, int sx) { return ((ck * 2 + (sx & 1)) * SH + sy) * TROW + (sx >> 1) * 16; }
 
-__device__ __forceinline__ void mma16(const u32x4& a, const u32x4& b, f32x16& c) {
-  c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-
 __global__ __launch_bounds__(256, 4) void stem2_kernel(const StemArgs p) {
   constexpr int PATCH_B = 2 * PPLANE;               // 19584
   constexpr int T_B = 4 * TPLANE;                   // 18496

@@ -156,16 +156,17 @@ G256P, G192, G192_F32, G192R = "gemm256p_kernel", "gemm256x192_kernel<{T}>", "ge
 
 
 def _conv(rid, expect, B, Cin, H, W, Cout, k=1, stride=1, dtypes=F16_BF16, pad=None, out_hw=None, act="none", res="none", res_rep=0,
-          act_after_res=False, shuffle_cout=0, out_f32=False, y_pad=0, scalar_gather=False, up=None, note=""):
+          act_after_res=False, shuffle_cout=0, out_f32=False, y_pad=0, scalar_gather=False, up=None, row_stats=False, note=""):
     """One cvmi_conv2d launch on an NHWC [B, H, W, Cin] input (H, W: the logical size, after upsampling).  Cin: an int, or (c0, c1) for two
     channel-concatenated sources of which source `up` (0 / 1 / None) is stored at half resolution.  B = "cu/2": half the device's CU count
     (gemm256x192r_kernel needs whole rounds of tiles).  pad None = k // 2.  res: "none" | "full" (one value per output element) | "bcast"
     (one [OH * OW, Cout] table for every image: res_mod) | "rep" (B / res_rep residual images, image b reads b / res_rep).  out_f32: f32
     output and residual from 16-bit operands.  y_pad > 0: the output (and a full residual) sit at channel y_pad of a buffer y_pad channels
-    wider on both sides.  act: "none" | "relu" | "silu" | "gelu"."""
+    wider on both sides.  act: "none" | "relu" | "silu" | "gelu".  row_stats: the launch also writes cvmi_conv_desc.row_stats, per row and
+    96-column slice (mean, sum of squared deviations) of the values stored (gemm256x192_kernel<float> / gemm256x192r_kernel only)."""
     return dict(id=rid, expect=expect, dtypes=dtypes, B=B, Cin=Cin, up=up, H=H, W=W, Cout=Cout, k=k, stride=stride,
                 pad=k // 2 if pad is None else pad, out_hw=out_hw, act=act, res=res, res_rep=res_rep, act_after_res=act_after_res,
-                shuffle_cout=shuffle_cout, out_f32=out_f32, y_pad=y_pad, scalar_gather=scalar_gather, note=note)
+                shuffle_cout=shuffle_cout, out_f32=out_f32, y_pad=y_pad, scalar_gather=scalar_gather, row_stats=row_stats, note=note)
 
 
 def conv_expect(row, dt):
@@ -205,6 +206,8 @@ CONV_ROWS = [
     _conv("t21_c16_n128", tile(2, 1, 16, 128), 1, 48, 8, 15, 72, 2, dtypes=F16_F32, act="relu", note="N = 72: one vector over 64 -> the 128 tile"),
     _conv("t21_c8_n56", dict(f16=tile(2, 1, 8, 64, 4), f32=tile(2, 1, 8, 64), bf16=ig(T64x64, 64, False)), 2, 8, 9, 16, 56, 2, dtypes=ALL3, pad=0,
           note="pad 0: OW = 15; N = 56: one vector under 64"),
+    _conv("t31_c16_n22_tail_res", tile(3, 1, 16, 32), 1, 16, 9, 7, 22, 3, dtypes=F16_F32, act="relu", res="full",
+          note="N = 22: the ragged channel tail of conv_tile's epilogue (6 of 8 fp16 / 2 of 4 f32 elements), with a residual"),
     # ---- just outside conv_tile: igemm_kernel takes over
     _conv("k1224_ragged_group", dict(f16=ig(T64x128, 64, False, 2), bf16=ig(T64x128, 64, False, 2), f32=ig(T64x128, 64, False)), 1, 136, 19, 21, 72, 3,
           dtypes=ALL3, act="relu", res="full", note="3x3 s1 over 136 channels; K = 1224 -> 39 K-tiles over 2 groups (20 + 19)"),
@@ -228,6 +231,8 @@ CONV_ROWS = [
     _conv("n64_m128", dict(f16=ig(T128x64, 128, True), bf16=ig(T128x64, 128, True), f32=ig(T128x64, 64, True)), 8, 64, 100, 90, 64, dtypes=ALL3, act="silu"),
     _conv("n64_m128_f32out", ig(T128x64, 128, True, to="float"), 8, 64, 100, 90, 60, act="relu", res="full", out_f32=True, y_pad=4, note="N = 60: one f32 vector under 64"),
     _conv("n62_logits", ig(T64x64, 64, True), 1, 128, 40, 40, 62, dtypes=ALL3, note="ragged Cout: element-wise channel tail"),
+    _conv("n62_tail_res_aar", ig(T64x64, 64, True), 1, 128, 40, 40, 62, dtypes=ALL3, act="relu", res="full", act_after_res=True,
+          note="the element-wise channel tail with a residual and the activation after it"),
     _conv("n48_k64", dict(f16=ig(T64x64, 128, True), bf16=ig(T64x64, 128, True), f32=ig(T64x64, 64, True)), 1, 64, 5, 13, 48, dtypes=ALL3, act="relu", res="full",
           note="M = 65; K is exactly one 128-byte tile in 16 bits"),
     _conv("n64_f32out", ig(T64x64, 64, True, to="float"), 1, 96, 7, 9, 64, res="full", out_f32=True, note="M = 63"),
@@ -260,6 +265,8 @@ CONV_ROWS = [
     _conv("ig_rep_mod", dict(f16=ig(T64x128, 128, True), bf16=ig(T64x128, 128, True), f32=ig(T64x128, 64, True)), 6, 64, 6, 5, 72, dtypes=ALL3, res="rep", res_rep=3, note="res_rep with res_mod = OH * OW"),
     _conv("ig_shuffle_rep_aar", dict(f16=ig(T64x128, 128, True), bf16=ig(T64x128, 128, True), f32=ig(T64x128, 64, True)), 6, 64, 6, 5, 128, dtypes=ALL3, act="gelu", res="rep", res_rep=3, act_after_res=True, shuffle_cout=32, y_pad=8,
           note="ConvTranspose 2x2 / s2 scatter + the skip feature shared by 3 prompts + GELU after it"),
+    _conv("ig_rep_aar_n136", dict(f16=ig(T64x128, 128, True), bf16=ig(T64x128, 128, True), f32=ig(T64x128, 64, True)), 6, 64, 6, 5, 136, dtypes=ALL3, act="relu", res="rep", res_rep=3,
+          act_after_res=True, note="column tile 0 is full: res_rep and the activation after it through the PREFETCHED residual; tile 1 is one 16-bit vector wide"),
     _conv("ig_aar", dict(f16=ig(T64x64, 128, True), bf16=ig(T64x64, 128, True), f32=ig(T64x64, 64, True)), 2, 32, 9, 7, 40, dtypes=ALL3, act="relu", res="full", act_after_res=True),
 
     # ================= gemm_glds_kernel: >= 512 tiles, K in whole 128-byte tiles (or >= 256) =================
@@ -287,12 +294,16 @@ CONV_ROWS = [
     _conv("g256p_ypad_ragged", G256P, 256, 192, 16, 16, 440, act="silu", y_pad=8, note="512 tiles over 256 workgroups; N = 440 of 512; 3 K-tiles"),
     _conv("i2c", G256_I2C, 2, 64, 128, 128, 256, 3, act="silu", note="128 tiles, one K-tile per tap"),
     _conv("i2c_s2_odd_res", G256_I2C, 2, 64, 255, 257, 256, 3, 2, act="relu", res="full", y_pad=8, note="stride 2 on odd sizes"),
+    _conv("i2c_ragged_m", G256_I2C, 2, 64, 127, 129, 256, 3, act="relu", res="full", note="M = 32766: the last of 128 row blocks is two rows short"),
     _conv("i2c_f32out", G256_I2C_F32, 2, 64, 128, 128, 256, 3, res="full", out_f32=True),
     _conv("i2c_127_tiles", ig(T64x128, 64, False), 2, 64, 127, 128, 256, 3, act="silu", note="127 tiles: one short; 508 tiles of 128 x 128 -> 64-row tiles"),
     _conv("g192_16", G192, 128, 1024, 16, 16, 384, act="gelu", y_pad=8),
     _conv("g192_16_res_bcast", G192, 128, 1024, 16, 16, 384, res="bcast"),
+    _conv("g192_16_aar", G192, 128, 1024, 16, 16, 384, act="relu", res="full", act_after_res=True),
     _conv("g192_f32_act", G192_F32, 128, 2304, 16, 16, 384, act="relu", res="full", out_f32=True, note="gemm256x192r's shape with an activation"),
     _conv("g192_f32_bcast", G192_F32, 128, 1024, 16, 16, 384, res="bcast", out_f32=True),
+    _conv("g192_f32_stats_ragged", G192_F32, 180, 1024, 16, 17, 384, res="full", out_f32=True, row_stats=True,
+          note="M = 48960 = 191 x 256 + 64: the last row block misses the direct epilogue and takes the LDS one, statistics included (the others: direct)"),
     _conv("g192r", G192R, "cu/2", 2304, 16, 16, 384, res="full", out_f32=True, y_pad=4, note="CU-count tiles of 256 x 192: whole rounds; skipped unless CUs % 8 == 0"),
 ]
 

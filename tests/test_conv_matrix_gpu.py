@@ -1,7 +1,8 @@
 """The convolution / GEMM dispatch matrix (tests/op_matrix.py CONV_ROWS): every kernel family and template instance cvmi_conv2d picks, pinned by the
 name cvmi_last_kernel() reports, in fp16, bf16 and f32, each with its epilogue options, against a plain reference of the same rounded operands.
 
-What every epilogue in igemm.hip and conv_tile.hip does (gemm_epilogue, the copies of it in gemm256_kernel / gemm256x192_kernel, conv_tile_kernel):
+What every epilogue in igemm.hip and conv_tile.hip does (csrc/conv_epilogue.hpp states this contract once; gemm_epilogue, gemm256_kernel and
+gemm256x192_kernel finish through its finish_chunk / store_out_chunk, conv_tile_kernel through its own store loop):
     t = TO(act(acc + bias))           acc in fp32; TO = the output type; with act_after_res the activation is skipped here
     y = TO(act2(float(t) + res))      only with a residual or act_after_res; act2 = the activation iff act_after_res
 so a 16-bit output with a residual is rounded TWICE (the tile passes through LDS in the output type before the residual is added); without one, or
@@ -19,7 +20,12 @@ Three operand structures per row and dtype, each on a fresh Plan:
   ones     x = 1, w = 1, bias 0, residual 0, no activation (a row's RELU stays: the identity here, and gemm256x192r_kernel's dispatch depends on it):
            the output is Cin x (taps inside the image), exact; a failure names the pixel.
 Each case also checks the kernel tag, finiteness, that a second run of the plan is bit-identical, and that a sentinel survives in every column of
-the output buffer outside the view (y_pad rows, ragged Cout) and in one spare image allocated behind the last one."""
+the output buffer outside the view (y_pad rows, ragged Cout) and in one spare image allocated behind the last one.
+A row with row_stats also checks, in every structure, the statistics the launch writes per row and 96-column slice -- (mean, sum of squared
+deviations from it) of the values AS STORED -- against their float64 moments.  With u = 2^-24, A = the slice's largest |value| and m2 its sum of
+squared deviations: the kernel forms 24 means of 4 and merges them pairwise in f32, fewer than 48 roundings on a path, so |mean - ref| <= 48 u A
+=: e; a deviation then carries e + u A <= 2 e, its square 2 |dev| 2 e <= 8 A e, and 96 of them with < 48 roundings of the sum:
+|m2 - ref| <= 96 * 8 A e + 48 u m2."""
 import ctypes as C
 import math
 import time
@@ -155,6 +161,9 @@ def _launch(row, dtype, odt, geo, srcs, w, b, r, act, lib):
         kw = dict(res=rb.view(y_pad, Nst))
         if row["res"] == "rep":
             kw.update(res_rep=row["res_rep"], res_mod=0 if sc else OH * OW)
+    stats = torch.full((B * OH * OW, N // 96, 2), SENTINEL, device="cuda") if row["row_stats"] else None
+    if stats is not None:
+        kw["row_stats"] = stats
     plan = Plan(stream())
     op_conv(plan, row["id"], PackedConv(w, b, dtype), [(xb.view(), 1 if row["up"] == i else 0) for i, xb in enumerate(bufs)], dst,
             stride=row["stride"], pad=row["pad"], act=act, out_hw=row["out_hw"], scalar_gather=row["scalar_gather"],
@@ -162,12 +171,25 @@ def _launch(row, dtype, odt, geo, srcs, w, b, r, act, lib):
     lib.cvmi_last_kernel()                                                 # clears the tag
     run(plan)
     tag = lib.cvmi_last_kernel().decode()
-    first = yb.t.clone()
+    first, stats1 = yb.t.clone(), (stats.clone() if stats is not None else None)
     run(plan)
-    same = torch.equal(yb.t, first)
+    same = torch.equal(yb.t, first) and (stats is None or torch.equal(stats, stats1))
     got = first[:B, :, :, y_pad:y_pad + Nst].cpu()
     outside = torch.cat((first[:B, :, :, :y_pad].flatten(), first[:B, :, :, y_pad + Nst:].flatten(), first[B].flatten()))
-    return tag, got, same, bool((outside == SENTINEL).all())
+    return tag, got, same, bool((outside == SENTINEL).all()), (stats1.cpu() if stats is not None else None)
+
+
+def _stats_failure(got, stats):
+    """The statistics of the rows as stored, or None when they hold (bound: the module's docstring)."""
+    u = 2.0 ** -24
+    sl = got.double().reshape(-1, got.shape[-1] // 96, 96)
+    mu = sl.mean(2)
+    m2 = ((sl - mu[..., None]) ** 2).sum(2)
+    A = sl.abs().amax(2)
+    e = 48 * u * A + 1e-30
+    r_mean, r_m2 = ((stats[..., 0].double() - mu).abs() / e).max(), ((stats[..., 1].double() - m2).abs() / (96 * 8 * A * e + 48 * u * m2 + 1e-30)).max()
+    print(f"  row_stats: mean err/bound {float(r_mean):.3f}  m2 err/bound {float(r_m2):.3f}")
+    return None if float(r_mean) <= 1.0 and float(r_m2) <= 1.0 else f"row_stats: mean err/bound {float(r_mean):.3f}, m2 err/bound {float(r_m2):.3f}"
 
 
 def _exact_model(row, s, b, r, act, to, geo):
@@ -212,7 +234,7 @@ def test_conv_matrix(row, dt):
         elif kind == "ones":
             act = "relu" if act == "relu" else "none"                       # RELU is the identity on the counts; it stays, since dispatch may depend on it
         srcs, w, b, r = _operands(kind, row, dtype, odt, geo, g)
-        tag, got, same, clean = _launch(row, dtype, odt, geo, srcs, w, b, r, ACT[act], lib)
+        tag, got, same, clean, stats = _launch(row, dtype, odt, geo, srcs, w, b, r, ACT[act], lib)
         X = _logical_input(row, srcs)
         note = ""
         if kind == "integer":
@@ -262,6 +284,8 @@ def test_conv_matrix(row, dt):
                 failures.append(f"random: err/bound {ratio_random:.3f} at [b, y, x, c] = {_where(i, got.shape)}: got {float(got.flatten()[i]):.6e} "
                                 f"ref {float(ref.flatten()[i]):.6e} bound {float(bound.flatten()[i]):.3e}")
         print(f"{row['id']} {dt} {kind}: {tag}{note}")
+        if stats is not None and _stats_failure(got, stats):
+            failures.append(f"{kind}: " + _stats_failure(got, stats))
         if tag != expect:
             failures.append(f"{kind}: kernel {tag!r}, expected {expect!r}")
         if not bool(torch.isfinite(got.float()).all()):

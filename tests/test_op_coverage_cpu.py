@@ -175,6 +175,8 @@ def conv_gaps(sources, rows=CONV_ROWS):
         for T in ("_Float16", "__bf16", "float"):
             if t.replace("{T}", T) not in tags:
                 gaps.append(f"{t.replace('{T}', T)} has no row")
+    if not any(r["row_stats"] and (r["B"] * r["H"] * r["W"]) % 256 and conv_expect(r, r["dtypes"][0]) == "gemm256x192_kernel<float>" for r in rows if r["B"] != "cu/2"):
+        gaps.append("row_stats through gemm256x192_kernel<float>'s LDS epilogue (a ragged last row block) has no row")
     return gaps
 
 
@@ -199,6 +201,7 @@ def test_a_new_conv_instance_or_a_removed_row_is_caught():
     assert conv_gaps(src, [r for r in CONV_ROWS if r["id"] != "t31_c32_n64_th8"]) == ["conv_tile_kernel<_Float16, .., 64, 2, 2, 8> has no row"]
     assert conv_gaps(src, [r for r in CONV_ROWS if r["id"] != "g192r"]) == ["kernel family gemm256x192r_kernel has no row"]
     assert "igemm_kernel KS = 4 has no row" in conv_gaps(src, [r for r in CONV_ROWS if not r["id"].startswith("ks4")])
+    assert conv_gaps(src, [r for r in CONV_ROWS if r["id"] != "g192_f32_stats_ragged"]) == ["row_stats through gemm256x192_kernel<float>'s LDS epilogue (a ragged last row block) has no row"]
 
 
 def test_conv_matrix_rows_are_well_formed():
@@ -227,6 +230,11 @@ def test_conv_matrix_rows_are_well_formed():
             assert isinstance(r["B"], int) and r["B"] % r["res_rep"] == 0, rid
         assert r["B"] == "cu/2" or (isinstance(r["B"], int) and r["B"] > 0), rid
         assert not r["out_f32"] or "f32" not in r["dtypes"] or isinstance(r["expect"], dict), rid
+        if r["row_stats"]:                                                  # what engine.op_conv / launch_typed admit statistics with
+            M = r["B"] * r["H"] * r["W"]
+            assert r["out_f32"] and r["res"] == "full" and r["k"] == 1 and r["Cout"] % 192 == 0 and not r["y_pad"] and not r["shuffle_cout"], rid
+            from circuitvision_amd.engine import row_stats_supported
+            assert row_stats_supported(M, r["Cout"], r["Cin"]), rid
 
 
 FUSED_SOURCES = ("c3k2_fused.hip", "stem_fused.hip", "dwpw_fused.hip")
