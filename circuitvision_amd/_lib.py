@@ -68,6 +68,11 @@ class AttnDesc(C.Structure):
     ]
 
 
+class MlpProj(C.Structure):
+    """cvmi_mlp_proj: the attention projection that cvmi_hiera_mlp_stats runs in the same launch."""
+    _fields_ = [("ao", C.c_void_p), ("w_packed", C.c_void_p), ("bp", C.c_void_p), ("ao_ld", C.c_int)]
+
+
 class LetterboxRow(C.Structure):
     """cvmi_letterbox_row: one source of cvmi_letterbox_ragged (a numpy array of LETTERBOX_ROW has the same layout)."""
     _fields_ = [("src_byte_offset", C.c_longlong), ("H", C.c_int), ("W", C.c_int), ("new_h", C.c_int), ("new_w", C.c_int), ("top", C.c_int), ("left", C.c_int)]
@@ -120,7 +125,8 @@ SIGNATURES = {
     "cvmi_hiera_mlp_supported": (_i, [_i]),
     "cvmi_hiera_mlp_packed_bytes": (C.c_size_t, [_i]),
     "cvmi_hiera_mlp": (_i, [_vp, _i, _vp, _vp, _f, _vp, _vp, C.c_longlong, _i, _i, _vp]),
-    "cvmi_hiera_mlp_stats": (_i, [_vp, _i, _vp, _vp, _f, _vp, _vp, C.c_longlong, _i, _i, _vp, _f, _vp]),
+    "cvmi_hiera_mlp_proj_packed_bytes": (C.c_size_t, [_i]),
+    "cvmi_hiera_mlp_stats": (_i, [_vp, _i, _vp, _vp, _f, _vp, _vp, C.c_longlong, _i, _i, _vp, _f, _vp, C.POINTER(MlpProj)]),
     "cvmi_tok_linear_supported": (_i, [_i]),
     "cvmi_tok_linear_packed_bytes": (C.c_size_t, [_i, _i]),
     "cvmi_tok_linear_format": (_i, [_i]),

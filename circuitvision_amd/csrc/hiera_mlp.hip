@@ -66,23 +66,28 @@ template <int C, int VAR = 0> struct MlpCfg {
   static constexpr int LDS = SLOTS * CHB + 1024;    // + a dump piece for the padding instructions of the waves with fewer real pieces
 };
 
-template <int C, int VAR = 0>
-__global__ __launch_bounds__((MlpCfg<C, VAR>::NW * 64), (MlpCfg<C, VAR>::WPS)) void hiera_mlp_kernel(float* __restrict__ x, int x_ld, const float* __restrict__ gamma,
-                                                                                      const float* __restrict__ beta, float eps,
-                                                                                      const char* __restrict__ wp, const float* __restrict__ b2,
-                                                                                      long long rows, float* __restrict__ stats_out, float stats_eps) {
+// A wave's place in the launch (32 tokens: token = lane & 31, row half = lane >> 5) and its share of the weight stream.  The pieces below --
+// the stream's issue, the LayerNorm front end, both chunk-loop forms and the epilogue -- are force-inlined into hiera_mlp_kernel and into
+// proj_mlp_kernel (proj_mlp.hpp), which differs in its front end only.
+template <int C, int VAR> struct MlpWave {
   using Cfg = MlpCfg<C, VAR>;
-  constexpr int KS = Cfg::KS, KS1 = Cfg::KS1, NT = Cfg::NT, NCH = Cfg::NCH, FR = Cfg::FR, CHB = Cfg::CHB, NW = Cfg::NW, CNT = Cfg::CNT, SLOTS = Cfg::SLOTS;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x, wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-  const int lr = lane & 31, lh = lane >> 5;
-  const long long row_raw = ((long long)blockIdx.x * NW + wv) * 32 + lr;
-  const bool row_ok = row_raw < rows;
-  float* const xr = x + (row_ok ? row_raw : rows - 1) * (long long)x_ld;
-
+  char* smem;
+  const char* wp;
+  int wv, lane, lr, lh;
+  long long row_raw, row_clamped;
+  bool row_ok;
+  __device__ __forceinline__ MlpWave(char* smem_, const char* wp_, long long rows) : smem(smem_), wp(wp_) {
+    const int tid = threadIdx.x;
+    wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    lr = lane & 31, lh = lane >> 5;
+    row_raw = ((long long)blockIdx.x * Cfg::NW + wv) * 32 + lr;
+    row_ok = row_raw < rows;
+    row_clamped = row_ok ? row_raw : rows - 1;
+  }
   // ---- weight stream: chunk j -> ring slot j % SLOTS; wave w moves fragments w, w + NW, ...  Every wave issues exactly CNT instructions per
   // chunk (a wave without a last real piece re-loads piece 0 into the dump area behind the ring), so that one immediate vmcnt count fits all.
-  auto issue_chunk = [&](int j) {
+  __device__ __forceinline__ void issue_chunk(int j) const {
+    constexpr int FR = Cfg::FR, CHB = Cfg::CHB, NW = Cfg::NW, CNT = Cfg::CNT, SLOTS = Cfg::SLOTS;
     const char* src = wp + (size_t)j * CHB + lane * 16;
     char* dst = smem + (j % SLOTS) * CHB;
 #pragma unroll
@@ -92,10 +97,11 @@ __global__ __launch_bounds__((MlpCfg<C, VAR>::NW * 64), (MlpCfg<C, VAR>::WPS)) v
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + (size_t)(real ? fi : 0) * 1024),
                                        (__attribute__((address_space(3))) void*)(real ? dst + fi * 1024 : smem + SLOTS * CHB), 16, 0, 0);
     }
-  };
+  }
   // Pipelined form (VAR 2): the unit of the stream is a STAGE = the FR consecutive fragments that one loop iteration consumes: fc2's fragments of
   // chunk s followed by fc1's of chunk s + 1 (contiguous in the packed stream).  Stage -1 is fc1's part of chunk 0 alone, stage NCH - 1 fc2's alone.
-  auto issue_piece = [&](int st, int f) {                            // this wave's f-th DMA instruction of stage st (every wave issues CNT per stage)
+  __device__ __forceinline__ void issue_piece(int st, int f) const {  // this wave's f-th DMA instruction of stage st (every wave issues CNT per stage)
+    constexpr int KS1 = Cfg::KS1, NT = Cfg::NT, NCH = Cfg::NCH, FR = Cfg::FR, CHB = Cfg::CHB, NW = Cfg::NW, SLOTS = Cfg::SLOTS;
     const int lo = st < 0 ? 2 * NT : 0, hi = st == NCH - 1 ? 2 * NT : FR;
     const char* src = wp + ((long long)st * FR + KS1) * 1024 + lane * 16;
     char* dst = smem + ((st + SLOTS) % SLOTS) * CHB;
@@ -103,64 +109,75 @@ __global__ __launch_bounds__((MlpCfg<C, VAR>::NW * 64), (MlpCfg<C, VAR>::WPS)) v
     const bool real = fi >= lo && fi < hi;
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + (long long)(real ? fi : lo) * 1024),
                                      (__attribute__((address_space(3))) void*)(real ? dst + fi * 1024 : smem + SLOTS * CHB), 16, 0, 0);
-  };
-  auto issue_stage = [&](int st) {
-#pragma unroll
-    for (int f = 0; f < CNT; ++f) issue_piece(st, f);
-  };
-  if constexpr (VAR == 2) {
-#pragma unroll
-    for (int st = -1; st < SLOTS - 1; ++st) issue_stage(st);
-  } else {
-#pragma unroll
-    for (int j = 0; j < SLOTS - 1; ++j) issue_chunk(j);
   }
-
-  // ---- LayerNorm of this lane's half row -> B fragments of fc1 (lane (token lr, half lh) holds channels 16 s + 8 lh .. + 7)
-  u32x4 xn[KS1];
-  {
-    float v[KS][8];
-    float s = 0.f;
+  __device__ __forceinline__ void issue_stage(int st) const {
 #pragma unroll
-    for (int k = 0; k < KS; ++k) {
-      const f32x4 a = *reinterpret_cast<const f32x4*>(xr + 16 * k + 8 * lh), b = *reinterpret_cast<const f32x4*>(xr + 16 * k + 8 * lh + 4);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { v[k][e] = a[e]; v[k][4 + e] = b[e]; s += a[e] + b[e]; }
-    }
-    s += __shfl_xor(s, 32);
-    const float mean = s / (float)C;
-    float q = 0.f;
-#pragma unroll
-    for (int k = 0; k < KS; ++k)
-#pragma unroll
-      for (int e = 0; e < 8; ++e) { const float d = v[k][e] - mean; q += d * d; }
-    q += __shfl_xor(q, 32);
-    const float rstd = 1.0f / sqrtf(q / (float)C + eps);
-#pragma unroll
-    for (int k = 0; k < KS; ++k) {
-      const float* gp = gamma + 16 * k + 8 * lh;
-      const float* bp = beta + 16 * k + 8 * lh;
-      const f32x4 g0 = *reinterpret_cast<const f32x4*>(gp), g1 = *reinterpret_cast<const f32x4*>(gp + 4);
-      const f32x4 b0 = *reinterpret_cast<const f32x4*>(bp), b1 = *reinterpret_cast<const f32x4*>(bp + 4);
-      f16x8 h;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        h[e] = (f16)((v[k][e] - mean) * rstd * g0[e] + b0[e]);
-        h[4 + e] = (f16)((v[k][4 + e] - mean) * rstd * g1[e] + b1[e]);
-      }
-      xn[k] = __builtin_bit_cast(u32x4, h);
-    }
-    // bias step: k = C and C + 1 are constant-1 columns (lanes of half 0 hold k = C .. C + 7)
-    const u32x4 one = {lh == 0 ? CVMI_ONE16X2 : 0u, 0u, 0u, 0u};
-    xn[KS] = one;
+    for (int f = 0; f < Cfg::CNT; ++f) issue_piece(st, f);
   }
-
-  f32x16 yacc[NT];
+  // what is in flight when the chunk loop starts: VAR 2: stages -1 .. SLOTS - 2;  otherwise chunks 0 .. SLOTS - 2
+  __device__ __forceinline__ void issue_first() const {
+    if constexpr (VAR == 2) {
 #pragma unroll
-  for (int t = 0; t < NT; ++t)
+      for (int st = -1; st < Cfg::SLOTS - 1; ++st) issue_stage(st);
+    } else {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) yacc[t][r] = 0.f;
+      for (int j = 0; j < Cfg::SLOTS - 1; ++j) issue_chunk(j);
+    }
+  }
+};
 
+// ---- LayerNorm of this lane's half row -> B fragments of fc1 (lane (token lr, half lh) holds channels 16 s + 8 lh .. + 7)
+template <int C, int VAR>
+__device__ __forceinline__ void mlp_ln_fragments(const float* xr, int lh, const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
+                                                 u32x4 (&xn)[MlpCfg<C, VAR>::KS1]) {
+  constexpr int KS = MlpCfg<C, VAR>::KS;
+  float v[KS][8];
+  float s = 0.f;
+#pragma unroll
+  for (int k = 0; k < KS; ++k) {
+    const f32x4 a = *reinterpret_cast<const f32x4*>(xr + 16 * k + 8 * lh), b = *reinterpret_cast<const f32x4*>(xr + 16 * k + 8 * lh + 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { v[k][e] = a[e]; v[k][4 + e] = b[e]; s += a[e] + b[e]; }
+  }
+  s += __shfl_xor(s, 32);
+  const float mean = s / (float)C;
+  float q = 0.f;
+#pragma unroll
+  for (int k = 0; k < KS; ++k)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { const float d = v[k][e] - mean; q += d * d; }
+  q += __shfl_xor(q, 32);
+  const float rstd = 1.0f / sqrtf(q / (float)C + eps);
+#pragma unroll
+  for (int k = 0; k < KS; ++k) {
+    const float* gp = gamma + 16 * k + 8 * lh;
+    const float* bp = beta + 16 * k + 8 * lh;
+    const f32x4 g0 = *reinterpret_cast<const f32x4*>(gp), g1 = *reinterpret_cast<const f32x4*>(gp + 4);
+    const f32x4 b0 = *reinterpret_cast<const f32x4*>(bp), b1 = *reinterpret_cast<const f32x4*>(bp + 4);
+    f16x8 h;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      h[e] = (f16)((v[k][e] - mean) * rstd * g0[e] + b0[e]);
+      h[4 + e] = (f16)((v[k][4 + e] - mean) * rstd * g1[e] + b1[e]);
+    }
+    xn[k] = __builtin_bit_cast(u32x4, h);
+  }
+  // bias step: k = C and C + 1 are constant-1 columns (lanes of half 0 hold k = C .. C + 7)
+  const u32x4 one = {lh == 0 ? CVMI_ONE16X2 : 0u, 0u, 0u, 0u};
+  xn[KS] = one;
+}
+
+// ---- the chunk loop: yacc += fc2(GELU(fc1(xn))) over the NCH hidden chunks.  Enters with MlpWave::issue_first()'s DMA instructions in flight
+// (ordinary loads issued before them may be outstanding as well: the counted wait below then waits for more than it needs) and
+// leaves with nothing outstanding.  yacc enters holding whatever fc2's product is to be added to.
+template <int C, int VAR>
+__device__ __forceinline__ void mlp_chunk_loop(const MlpWave<C, VAR>& w, u32x4 (&xn)[MlpCfg<C, VAR>::KS1], f32x16 (&yacc)[MlpCfg<C, VAR>::NT]) {
+  using Cfg = MlpCfg<C, VAR>;
+  constexpr int KS1 = Cfg::KS1, NT = Cfg::NT, NCH = Cfg::NCH, FR = Cfg::FR, CHB = Cfg::CHB, CNT = Cfg::CNT, SLOTS = Cfg::SLOTS;
+  char* const smem = w.smem;
+  const int lane = w.lane;
+  auto issue_stage = [&](int st) { w.issue_stage(st); };
+  auto issue_chunk = [&](int j) { w.issue_chunk(j); };
   if constexpr (VAR == 2) {
     // ---- pipelined chunk loop.  Iteration j of one wave:   fc1(j + 1) -> hout   ||   GELU(hin = fc1(j)) -> pfv   ||   fc2(j): yacc += W2 . pfv
     // Left in chunk order, the wave runs fc1's MFMAs, then ~200 issue slots of GELU with the matrix pipe idle, then fc2's MFMAs -- and with one wave per
@@ -326,13 +343,22 @@ __global__ __launch_bounds__((MlpCfg<C, VAR>::NW * 64), (MlpCfg<C, VAR>::WPS)) v
       }
     }
   }
+}
 
-  // ---- epilogue: x += y + b2; lane (token lr, half lh) owns channels 32 t + 8 g + 4 lh .. + 3.
-  // stats_out: the updated row's LayerNorm statistics (mean, 1 / sqrt(var + stats_eps)) for the launch that normalises it next (the next
-  // block's norm1): shifted sums (tok_stream.hpp) over this lane's half of the row, the shift being the row's first updated value.
+// ---- epilogue: x += y + b2; lane (token lr, half lh) owns channels 32 t + 8 g + 4 lh .. + 3.
+// PROJ (proj_mlp.hpp): yacc also holds the attention projection's product and bp its bias: x += yacc + (bp + b2), in that association.
+// stats_out: the updated row's LayerNorm statistics (mean, 1 / sqrt(var + stats_eps)) for the launch that normalises it next (the next
+// block's norm1): shifted sums (tok_stream.hpp) over this lane's half of the row, the shift being the row's first updated value.
+template <int C, int VAR, bool PROJ>
+__device__ __forceinline__ void mlp_epilogue(const MlpWave<C, VAR>& w, float* xr, f32x16 (&yacc)[MlpCfg<C, VAR>::NT], const float* __restrict__ b2,
+                                             const float* __restrict__ bp, float* __restrict__ stats_out, float stats_eps) {
+  constexpr int NT = MlpCfg<C, VAR>::NT;
+  const int lr = w.lr, lh = w.lh;
+  const bool row_ok = w.row_ok;
+  const long long row_raw = w.row_raw;
   ShiftedSums st;
   if (stats_out) {
-    const float o0 = row_ok ? xr[0] + (yacc[0][0] + b2[0]) : 0.f;       // (the value the lane of half 0 stores at channel 0)
+    const float o0 = row_ok ? xr[0] + (yacc[0][0] + (PROJ ? bp[0] + b2[0] : b2[0])) : 0.f;       // (the value the lane of half 0 stores at channel 0)
     st.shift = __shfl(o0, lr);
   }
   if (row_ok) {
@@ -342,7 +368,8 @@ __global__ __launch_bounds__((MlpCfg<C, VAR>::NW * 64), (MlpCfg<C, VAR>::WPS)) v
       for (int g = 0; g < 4; ++g) {
         const int c0 = 32 * t + 8 * g + 4 * lh;
         if (c0 < C) {
-          const f32x4 bb = *reinterpret_cast<const f32x4*>(b2 + c0);
+          f32x4 bb = *reinterpret_cast<const f32x4*>(b2 + c0);
+          if constexpr (PROJ) bb += *reinterpret_cast<const f32x4*>(bp + c0);
           f32x4 o = *reinterpret_cast<const f32x4*>(xr + c0);
 #pragma unroll
           for (int e = 0; e < 4; ++e) o[e] += yacc[t][4 * g + e] + bb[e];
@@ -355,6 +382,27 @@ __global__ __launch_bounds__((MlpCfg<C, VAR>::NW * 64), (MlpCfg<C, VAR>::WPS)) v
     const float2 mr = shifted_mean_rstd(st.shift, row_sum<2>(st.s), row_sum<2>(st.q), (float)C, stats_eps);
     if (row_ok && lh == 0) *reinterpret_cast<float2*>(stats_out + 2 * row_raw) = mr;
   }
+}
+
+template <int C, int VAR = 0>
+__global__ __launch_bounds__((MlpCfg<C, VAR>::NW * 64), (MlpCfg<C, VAR>::WPS)) void hiera_mlp_kernel(float* __restrict__ x, int x_ld, const float* __restrict__ gamma,
+                                                                                      const float* __restrict__ beta, float eps,
+                                                                                      const char* __restrict__ wp, const float* __restrict__ b2,
+                                                                                      long long rows, float* __restrict__ stats_out, float stats_eps) {
+  using Cfg = MlpCfg<C, VAR>;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const MlpWave<C, VAR> w(smem, wp, rows);
+  float* const xr = x + w.row_clamped * (long long)x_ld;
+  w.issue_first();
+  u32x4 xn[Cfg::KS1];
+  mlp_ln_fragments<C, VAR>(xr, w.lh, gamma, beta, eps, xn);
+  f32x16 yacc[Cfg::NT];
+#pragma unroll
+  for (int t = 0; t < Cfg::NT; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) yacc[t][r] = 0.f;
+  mlp_chunk_loop<C, VAR>(w, xn, yacc);
+  mlp_epilogue<C, VAR, false>(w, xr, yacc, b2, nullptr, stats_out, stats_eps);
 }
 
 template <int C, int VAR = 0>
@@ -373,6 +421,8 @@ int launch_mlp(float* x, int x_ld, const float* gamma, const float* beta, float 
 
 }  // namespace
 
+#include "proj_mlp.hpp"
+
 #ifndef CVMI_OPERAND_BF16
 // C = 576 (stage 3) is not built: its Y^T accumulator alone is 288 registers per lane and, with the 148 of the resident Xn fragments,
 // leaves no room to keep LDS reads in flight (hipcc spills 1.8 KB per lane); stage 3 / 4 stay on the tiled GEMM kernels.
@@ -383,25 +433,34 @@ extern "C" size_t cvmi_hiera_mlp_packed_bytes(int C) {
   const size_t fr = (size_t)(C / 16 + 1) + 2 * (size_t)((C + 31) / 32);
   return (size_t)(4 * C / 32) * fr * 1024;
 }
+// the proj form's stream (proj_mlp.hpp): ceil(C/32) * C/16 fragments of the attention projection, then the MLP chunks
+extern "C" size_t cvmi_hiera_mlp_proj_packed_bytes(int C) {
+  if (!cvmi_hiera_mlp_supported(C)) return 0;
+  return (size_t)((C + 31) / 32) * (size_t)(C / 16) * 1024 + cvmi_hiera_mlp_packed_bytes(C);
+}
 extern "C" int cvmi_hiera_mlp_stats_bf16(void* x, int x_ld, const float* gamma, const float* beta, float eps, const void* w_packed, const float* b2,
-                                         long long rows, int C, int dtype, float* ln_stats_out, float ln_stats_eps, cvmi_stream_t stream_);
+                                         long long rows, int C, int dtype, float* ln_stats_out, float ln_stats_eps, cvmi_stream_t stream_,
+                                         const cvmi_mlp_proj* proj);
 #endif
 
 // cvmi_hiera_mlp that also writes, per updated row, the LayerNorm statistics (mean, 1 / sqrt(var + ln_stats_eps)) the NEXT launch needs
 // (the next block's norm1, fused into cvmi_tok_linear_stats / cvmi_tok_linear_pool_stats): ln_stats_out = float[2 * rows] or NULL.
+// proj != NULL: the block's attention projection runs in the same launch (proj_mlp.hpp); w_packed is then not read.
 extern "C" int CVMI_ENTRY(cvmi_hiera_mlp_stats)(void* x, int x_ld, const float* gamma, const float* beta, float eps, const void* w_packed, const float* b2,
-                                                long long rows, int C, int dtype, float* ln_stats_out, float ln_stats_eps, cvmi_stream_t stream_) {
+                                                long long rows, int C, int dtype, float* ln_stats_out, float ln_stats_eps, cvmi_stream_t stream_,
+                                                const cvmi_mlp_proj* proj) {
 #ifndef CVMI_OPERAND_BF16
-  if (dtype == CVMI_BF16) return cvmi_hiera_mlp_stats_bf16(x, x_ld, gamma, beta, eps, w_packed, b2, rows, C, dtype, ln_stats_out, ln_stats_eps, stream_);
+  if (dtype == CVMI_BF16) return cvmi_hiera_mlp_stats_bf16(x, x_ld, gamma, beta, eps, w_packed, b2, rows, C, dtype, ln_stats_out, ln_stats_eps, stream_, proj);
 #endif
   CVMI_CHECK(dtype == CVMI_T16, "hiera_mlp: dtype must be CVMI_F16 or CVMI_BF16");
-  CVMI_CHECK(x && gamma && beta && w_packed && b2 && rows > 0, "hiera_mlp: bad arguments");
+  CVMI_CHECK(x && gamma && beta && (w_packed || proj) && b2 && rows > 0, "hiera_mlp: bad arguments");
   CVMI_CHECK(C == 144 || C == 288, "hiera_mlp: C=%d is not built (144, 288)", C);
   CVMI_CHECK(x_ld >= C && x_ld % 4 == 0 && (((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)w_packed | (uintptr_t)b2) & 15) == 0 &&
                  ((uintptr_t)ln_stats_out & 7) == 0,
              "hiera_mlp: pointers / ld must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream_;
   float* xf = (float*)x;
+  if (proj) return proj_mlp_dispatch(xf, x_ld, proj, gamma, beta, eps, b2, rows, C, s, ln_stats_out, ln_stats_eps);
   if (C == 144) return launch_mlp<144, 1>(xf, x_ld, gamma, beta, eps, w_packed, b2, rows, s, ln_stats_out, ln_stats_eps);
   // Test hook, not a tuning switch: CVMI_MLP_PIPE=0 runs C = 288 on the chunk-order loop (VAR 0), the bit-exact reference the pipelined
   // loop is tested against (tests/test_ops_gpu.py switches it between two launches, so it is read per call).
@@ -412,5 +471,5 @@ extern "C" int CVMI_ENTRY(cvmi_hiera_mlp_stats)(void* x, int x_ld, const float* 
 
 extern "C" int CVMI_ENTRY(cvmi_hiera_mlp)(void* x, int x_ld, const float* gamma, const float* beta, float eps, const void* w_packed, const float* b2,
                                           long long rows, int C, int dtype, cvmi_stream_t stream_) {
-  return CVMI_ENTRY(cvmi_hiera_mlp_stats)(x, x_ld, gamma, beta, eps, w_packed, b2, rows, C, dtype, nullptr, 0.f, stream_);
+  return CVMI_ENTRY(cvmi_hiera_mlp_stats)(x, x_ld, gamma, beta, eps, w_packed, b2, rows, C, dtype, nullptr, 0.f, stream_, nullptr);
 }

@@ -527,6 +527,21 @@ def hiera_mlp_supported(C_, dtype):
     return is16(dtype) and bool(_lib.load().cvmi_hiera_mlp_supported(C_))
 
 
+def _mlp_chunks(w1, b1, w2, td):
+    """fc1 / fc2 as the [chunks, elements] fragment stream of cvmi_hiera_mlp (float32, values not yet rounded to td except the bias pair)."""
+    Hd, C_ = w1.shape
+    assert Hd == 4 * C_ and tuple(w2.shape) == (C_, Hd) and C_ % 16 == 0
+    ks1, nt, nch = C_ // 16 + 1, (C_ + 31) // 32, Hd // 32
+    b_hi = b1.to(td).float()
+    b_lo = (b1 - b_hi).to(td).float()
+    w1x = torch.cat((w1, b_hi[:, None], b_lo[:, None], torch.zeros(Hd, 14)), 1)              # [4C, C + 16]
+    f1 = w1x.view(nch, 32, ks1, 2, 8).permute(0, 2, 3, 1, 4)                                   # (j, s, h, r, e)
+    w2p = torch.zeros(nt * 32, Hd)
+    w2p[:C_] = w2
+    f2 = w2p.view(nt, 32, nch, 2, 2, 2, 4).permute(2, 0, 3, 5, 1, 4, 6)                        # (j, t, s2, h, r, e_hi, e_lo)
+    return torch.cat((f1.reshape(nch, -1), f2.reshape(nch, -1)), 1).contiguous()
+
+
 class PackedHieraMlp:
     """fc1 / fc2 of one Hiera block in the MFMA-fragment order cvmi_hiera_mlp streams (include/cvmi355.h)."""
 
@@ -534,16 +549,7 @@ class PackedHieraMlp:
         # w1 [4C, C], b1 [4C], w2 [C, 4C], b2 [C]  (float32, LoRA already merged); dtype: F16 or BF16 operands
         td = TORCH_DTYPE[dtype]
         Hd, C_ = w1.shape
-        assert Hd == 4 * C_ and tuple(w2.shape) == (C_, Hd) and C_ % 16 == 0
-        ks1, nt, nch = C_ // 16 + 1, (C_ + 31) // 32, Hd // 32
-        b_hi = b1.to(td).float()
-        b_lo = (b1 - b_hi).to(td).float()
-        w1x = torch.cat((w1, b_hi[:, None], b_lo[:, None], torch.zeros(Hd, 14)), 1)              # [4C, C + 16]
-        f1 = w1x.view(nch, 32, ks1, 2, 8).permute(0, 2, 3, 1, 4)                                   # (j, s, h, r, e)
-        w2p = torch.zeros(nt * 32, Hd)
-        w2p[:C_] = w2
-        f2 = w2p.view(nt, 32, nch, 2, 2, 2, 4).permute(2, 0, 3, 5, 1, 4, 6)                        # (j, t, s2, h, r, e_hi, e_lo)
-        packed = torch.cat((f1.reshape(nch, -1), f2.reshape(nch, -1)), 1).contiguous()
+        packed = _mlp_chunks(w1, b1, w2, td)
         assert packed.numel() * 2 == _lib.load().cvmi_hiera_mlp_packed_bytes(C_)
         self.w = packed.to(td).to(device)
         self.bias = b2.float().contiguous().to(device)          # (.w / .bias: what distributed.packed_tensors broadcasts)
@@ -551,23 +557,78 @@ class PackedHieraMlp:
         self.param_bytes = 2 * Hd * C_ * 2
 
 
-def op_hiera_mlp(plan, label, pm, x, gamma, beta, eps=1e-6, stats_out=None, stats_eps=1e-6):
+def proj_mlp_k_order(C_):
+    """Column order of fc1's weight in the proj form of cvmi_hiera_mlp_stats (csrc/proj_mlp.hpp): packed column 16 s + k holds channel
+    16 s + pi(k), pi(k) = 8 ((k & 7) >> 2) + 4 (k >> 3) + (k & 3) -- the order in which the proj product's accumulator serves as fc1's operand."""
+    n = torch.arange(C_)
+    k = n % 16
+    return n - k + 8 * ((k & 7) >> 2) + 4 * (k >> 3) + (k & 3)
+
+
+class PackedProjMlp:
+    """attn.proj + fc1 / fc2 of one Hiera block as the stream of the proj form of cvmi_hiera_mlp_stats (include/cvmi355.h): the projection's
+    output tiles in natural k order, then PackedHieraMlp's chunks with fc1's columns in proj_mlp_k_order."""
+
+    def __init__(self, wp, bp, w1, b1, w2, b2, device="cuda", dtype=F16):
+        # wp [C, C], bp [C], then as PackedHieraMlp  (float32, LoRA already merged)
+        td = TORCH_DTYPE[dtype]
+        Hd, C_ = w1.shape
+        assert tuple(wp.shape) == (C_, C_) and bp.numel() == C_ and b2.numel() == C_
+        nt, ks = (C_ + 31) // 32, C_ // 16
+        wpp = torch.zeros(nt * 32, C_)
+        wpp[:C_] = wp
+        fp = wpp.view(nt, 32, ks, 2, 8).permute(0, 2, 3, 1, 4)                                     # (t, s, h, r, e)
+        packed = torch.cat((fp.reshape(-1), _mlp_chunks(w1[:, proj_mlp_k_order(C_)], b1, w2, td).reshape(-1)))
+        assert packed.numel() * 2 == _lib.load().cvmi_hiera_mlp_proj_packed_bytes(C_)
+        self.w = packed.to(td).to(device)
+        self.bias = torch.cat((bp.float(), b2.float())).contiguous().to(device)      # (.w / .bias: what distributed.packed_tensors broadcasts)
+        self.C, self.dtype = C_, dtype
+        self.param_bytes = (C_ * C_ + 2 * Hd * C_) * 2
+
+    def unpack(self):
+        """-> dict(wp, bp, w1, b1, w2, b2) as float32 CPU tensors at the operand type's rounding (b1 = its hi + lo pair): the packing inverted."""
+        C_ = self.C
+        nt, ks, ks1, nch = (C_ + 31) // 32, C_ // 16, C_ // 16 + 1, 4 * C_ // 32
+        w, bias = self.w.cpu().float().reshape(-1), self.bias.cpu()
+        npj = nt * ks * 512
+        wp = w[:npj].view(nt, ks, 2, 32, 8).permute(0, 3, 1, 2, 4).reshape(nt * 32, C_)
+        ch = w[npj:].view(nch, -1)
+        f1 = ch[:, :ks1 * 512].reshape(nch, ks1, 2, 32, 8).permute(0, 3, 1, 2, 4).reshape(4 * C_, C_ + 16)
+        w1 = torch.zeros(4 * C_, C_)
+        w1[:, proj_mlp_k_order(C_)] = f1[:, :C_]
+        f2 = ch[:, ks1 * 512:].reshape(nch, nt, 2, 2, 32, 2, 4).permute(1, 4, 0, 2, 5, 3, 6).reshape(nt * 32, 4 * C_)
+        assert not wp[C_:].any() and not f2[C_:].any() and not f1[:, C_ + 2:].any()
+        return dict(wp=wp[:C_].clone(), bp=bias[:C_].clone(), w1=w1, b1=f1[:, C_] + f1[:, C_ + 1], w2=f2[:C_].clone(), b2=bias[C_:].clone())
+
+
+def op_hiera_mlp(plan, label, pm, x, gamma, beta, eps=1e-6, stats_out=None, stats_eps=1e-6, proj=None):
     """x <- x + fc2(GELU(fc1(LayerNorm(x)))) in place; x: f32 View (full rows).  stats_out: f32 tensor [rows, 2] that receives each updated
-    row's (mean, rstd) for the NEXT LayerNorm over x (eps = stats_eps)."""
+    row's (mean, rstd) for the NEXT LayerNorm over x (eps = stats_eps).
+    proj = (PackedProjMlp, ao): the block's attention projection in the same launch -- x <- x1 + mlp(x1), x1 = x + ao Wp^T + bp; ao: a 16-bit
+    View of the same rows (pm is then not used and may be None)."""
     lib = _lib.load()
+    if proj is not None:
+        pm, ao = proj[0], _as_rows(proj[1])
     assert x.dtype == F32 and x.c == pm.C and x.c0 == 0
     rows = x.B * x.H * x.W
     assert stats_out is None or (stats_out.dtype == torch.float32 and stats_out.numel() == 2 * rows and stats_out.is_contiguous()), label
-    args = (x.ptr, x.ld, gamma.data_ptr(), beta.data_ptr(), float(eps), pm.w.data_ptr(), pm.bias.data_ptr(), rows, pm.C, pm.dtype,
+    desc, b2 = None, pm.bias.data_ptr()
+    if proj is not None:
+        assert ao.rows == rows and ao.C == pm.C and ao.dtype == pm.dtype, label
+        desc = _lib.MlpProj(ao=ao.ptr, w_packed=pm.w.data_ptr(), bp=pm.bias.data_ptr(), ao_ld=ao.ld)
+        b2 += 4 * pm.C                                          # PackedProjMlp.bias = bp | b2
+    args = (x.ptr, x.ld, gamma.data_ptr(), beta.data_ptr(), float(eps), None if proj is not None else pm.w.data_ptr(), b2, rows, pm.C, pm.dtype,
             stats_out.data_ptr() if stats_out is not None else None, float(stats_eps))
-    plan.keep.append((pm, x, gamma, beta, stats_out))
+    plan.keep.append((pm, x, gamma, beta, stats_out, proj, desc))
     sp0, fn = plan.sptr, lib.cvmi_hiera_mlp_stats
+    pdesc = C.byref(desc) if desc is not None else None
 
     def thunk(sp=None):
         sp = sp0 if sp is None else sp
-        _lib.check(fn(*args, sp), label)
+        _lib.check(fn(*args, sp, pdesc), label)
 
-    plan.add(label, "mlp_fused", thunk, rows * pm.C * 8, 2 * rows * 2 * 4 * pm.C * pm.C)
+    plan.add(label, "mlp_fused", thunk, rows * pm.C * (8 + (ESIZE[pm.dtype] if proj is not None else 0)),
+             2 * rows * 2 * 4 * pm.C * pm.C + (2 * rows * pm.C * pm.C if proj is not None else 0))
 
 
 # ---- token-stationary linear layer (tok_linear.hip) ------------------------------------------------------------------------

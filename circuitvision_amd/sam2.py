@@ -29,7 +29,7 @@ import torch.nn.functional as TF
 
 from . import _lib
 from ._lib import ACT_GELU, ACT_NONE, ACT_RELU, ACT_SIGMOID, BF16, F16, F32
-from .engine import (ESIZE, TORCH_DTYPE, is16, Buf, PackedConv, PackedHieraMlp, PackedQkvAttn, PackedTokLinear, Plan, Rows, hiera_mlp_supported, make_attn_desc, op_attention,
+from .engine import (ESIZE, TORCH_DTYPE, is16, Buf, PackedConv, PackedHieraMlp, PackedProjMlp, PackedQkvAttn, PackedTokLinear, Plan, Rows, hiera_mlp_supported, make_attn_desc, op_attention,
                      op_call, op_cast, op_conv, op_hiera_mlp, op_layernorm, op_maxpool2, op_tok_linear, op_tok_linear_pool, require_gpu, row_stats_supported,
                      qkv_attn_supported, tok_linear_stats_parts, tok_linear_supported)
 
@@ -293,6 +293,12 @@ class Sam2Weights:
                                                    self.p.weight(f"{b}.mlp.layers.1", (dim_out, 4 * dim_out)), self.p.bias(f"{b}.mlp.layers.1", dim_out),
                                                    self.device, self.dtype)
                 self.param_bytes += self.mlp[f"b{i}"].param_bytes
+                # ... and, behind the attention projection, for the launch that runs proj + MLP together (proj_mlp.hpp); the same parameters
+                # a second time, so param_bytes stays
+                self.mlp[f"b{i}.projmlp"] = PackedProjMlp(self.p.weight(f"{b}.attn.proj", (dim_out, dim_out)), self.p.bias(f"{b}.attn.proj", dim_out),
+                                                          self.p.weight(f"{b}.mlp.layers.0", (4 * dim_out, dim_out)), self.p.bias(f"{b}.mlp.layers.0", 4 * dim_out),
+                                                          self.p.weight(f"{b}.mlp.layers.1", (dim_out, 4 * dim_out)), self.p.bias(f"{b}.mlp.layers.1", dim_out),
+                                                          self.device, self.dtype)
             else:
                 self._linear(f"b{i}.fc1", f"{b}.mlp.layers.0", 4 * dim_out, dim_out, tok=True)
                 self._linear(f"b{i}.fc2", f"{b}.mlp.layers.1", dim_out, 4 * dim_out)
@@ -629,7 +635,11 @@ class Sam2Plan:
                and os.environ.get("CVMI_SAM_LNSTATS", "1") != "0")
         sparts = tok_linear_stats_parts(B * OH * OW, dout, dout) if fwd else 0     # (a launch with fewer row blocks than CUs writes its statistics in slices)
         stats = torch.empty(B * OH * OW, max(sparts, 1), 2, dtype=torch.float32, device=self.dev) if fwd else None
-        if tok_out and f"b{i}.proj" in wt.tl:
+        # stages 1 / 2: the projection is the prologue of the fused MLP launch (proj_mlp.hpp): x1 = shortcut + proj(attn) is neither written nor read back
+        fuse_proj = (f"b{i}.projmlp" in wt.mlp and not padded and ao.view().ld == dout and os.environ.get("CVMI_SAM_PROJMLP", "1") != "0")
+        if fuse_proj:
+            pass
+        elif tok_out and f"b{i}.proj" in wt.tl:
             op_tok_linear(self.plan, f"b{i}.proj", wt.tl[f"b{i}.proj"], ao.view(), short.view(), residual=True, stats_out=stats, stats_eps=1e-6)
         else:
             self.gemm(f"b{i}.proj", f"b{i}.proj", ao.view(), short.view(), res=short.view(), out_hw=(OH, OW) if padded else None)
@@ -639,7 +649,8 @@ class Sam2Plan:
             nxt = wt.blocks[i + 1] if i + 1 < len(wt.blocks) else None
             if nxt is not None and os.environ.get("CVMI_SAM_LNSTATS", "1") != "0" and f"b{i + 1}.qkv" in wt.tl and (B * OH * OW) % 256 == 0:
                 self._ln1_stats = torch.empty(B * OH * OW, 2, dtype=torch.float32, device=self.dev)      # the next block's norm1 reads x once
-            op_hiera_mlp(self.plan, f"b{i}.mlp", wt.mlp[f"b{i}"], x.view(), gam, bet, 1e-6, stats_out=self._ln1_stats, stats_eps=1e-6)
+            op_hiera_mlp(self.plan, f"b{i}.mlp", wt.mlp[f"b{i}"], x.view(), gam, bet, 1e-6, stats_out=self._ln1_stats, stats_eps=1e-6,
+                         proj=(wt.mlp[f"b{i}.projmlp"], ao.view()) if fuse_proj else None)
         else:
             hid = self.buf(OH, OW, 4 * dout, tag="hid")
             if tok_out and f"b{i}.fc1" in wt.tl:                   # norm2 fused into fc1 (+ GELU)

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define CVMI_VERSION 126
+#define CVMI_VERSION 127
 
 typedef void* cvmi_stream_t; /* hipStream_t */
 
@@ -293,8 +293,30 @@ int cvmi_hiera_mlp(void* x, int x_ld, const float* gamma, const float* beta, flo
                    const float* b2, long long rows, int C, int dtype /* CVMI_F16 | CVMI_BF16: type of w_packed */, cvmi_stream_t stream);
 /* same; additionally writes per updated row (mean, 1 / sqrt(var + ln_stats_eps)) to ln_stats_out (float[2 * rows], or NULL): the statistics of
  * the NEXT LayerNorm over these rows (the next block's norm1), consumed by cvmi_tok_linear_stats / cvmi_tok_linear_pool_stats */
+/* proj (127), optional: the block's attention projection in the same launch.  With x1 = x + ao . Wp^T + bp the launch stores
+ * x1 + fc2(GELU(fc1(LayerNorm(x1)))) + b2; x1 itself is never written (sam2 hieradet MultiScaleBlock: `x = shortcut + proj(attn)` then the
+ * MLP half).  NULL = the launch described above, bit for bit.  With proj set the w_packed ARGUMENT of the call is not read (it may be NULL):
+ * the launch streams proj->w_packed; b2 stays the fc2 bias.  Built for C in {144, 288} and a 16-bit dtype; refused before any launch:
+ * another C or dtype, a NULL or not 16-byte aligned ao / w_packed / bp, ao_ld < C or no multiple of 8.  Equal to cvmi_tok_linear(residual)
+ * followed by cvmi_hiera_mlp to within f32 rounding ahead of the same 16-bit roundings (the f32 sums associate as x + (ao . Wp^T + (bp + b2) + ..),
+ * fc1 sums its k in the permuted order below), not bit for bit; a repeated launch on the same input is bit-identical.
+ * w_packed of the proj form, cvmi_hiera_mlp_proj_packed_bytes(C) = ceil(C/32) * (C/16) * 1024 + cvmi_hiera_mlp_packed_bytes(C) bytes:
+ *   [ P(t, s) for t = 0 .. ceil(C/32) - 1, s = 0 .. C/16 - 1 ]  ++  the chunks of cvmi_hiera_mlp with F1's k permuted
+ *   P(t, s)[l][e]  = Wp[32 t + r][16 s + 8 h + e]   (attn.proj.weight; 0 for output rows >= C); the kernel moves ring-slot sized runs of whole
+ *                    tiles: floor((C/16 + 1 + 2 ceil(C/32)) / (C/16)) = 2 tiles per piece
+ *   F1(j, s)[l][e] = W1[32 j + r][16 s + pi(8 h + e)] for s < C/16,  pi(k) = 8 ((k & 7) >> 2) + 4 (k >> 3) + (k & 3)  (bits 2 and 3 of k
+ *                    swapped): the k order in which the accumulator of the proj product (lane = token, register 4 g + e of tile t <-> channel
+ *                    32 t + 8 g + 4 h + e), normalised in place, serves as fc1's B operand.  The bias step s = C/16 and F2 are unchanged. */
+typedef struct {
+  const void* ao;            /* attention output, 16-bit [rows][C], row stride ao_ld elements; read only */
+  const void* w_packed;      /* the stream above */
+  const float* bp;           /* attn.proj.bias, f32 [C] */
+  int ao_ld;
+} cvmi_mlp_proj;
+size_t cvmi_hiera_mlp_proj_packed_bytes(int C);
 int cvmi_hiera_mlp_stats(void* x, int x_ld, const float* gamma, const float* beta, float eps, const void* w_packed, const float* b2,
-                         long long rows, int C, int dtype, float* ln_stats_out, float ln_stats_eps, cvmi_stream_t stream);
+                         long long rows, int C, int dtype, float* ln_stats_out, float ln_stats_eps, cvmi_stream_t stream,
+                         const cvmi_mlp_proj* proj);
 
 /* Token-stationary linear layer for Hiera's short-K GEMMs (sam2 hieradet MultiScaleBlock: qkv(norm1(x)), x = shortcut + proj(attn),
  * mlp.layers[0](norm2(x)) + GELU; behind sam2_infer.py:226):
