@@ -999,6 +999,7 @@ int launch_res64(const AttnArgs& a, hipStream_t stream) {
 
 // ---- the same window attention fed by the qkv projection of the f32 stream in one launch (cvmi_attn_desc.proj_x)
 #include "qkv_attn.hpp"
+#include "qkv_attn16.hpp"                                  // ... and stage 2: K = 288, 4 x 4 windows, the window attention on the matrix pipe
 
 // ---- long sequences of head_dim 72 (Hiera global attention): the same inner loop, K / V streamed through two 64-key
 //      LDS buffers by DMA (no staging registers: 4 waves per SIMD); one barrier per tile publishes tile t + 1 while it
@@ -1434,7 +1435,8 @@ extern "C" int CVMI_ENTRY(cvmi_attention)(const cvmi_attn_desc* d, cvmi_stream_t
     CVMI_CHECK(!d->q_pool, "attention: q_pool requires window mode");
   }
   hipStream_t stream = (hipStream_t)stream_;
-  if (d->proj_x) return qkv_attn_dispatch(d, a, stream);    // q / k / v are projected inside the launch (qkv_attn.hpp); q, k, v are not read
+  // q / k / v are projected inside the launch; q, k, v are not read.  4 x 4 windows of input width 288: qkv_attn16.hpp; everything else: qkv_attn.hpp
+  if (d->proj_x) return (d->win == 4 && d->proj_K == 288) ? qkv_attn16_dispatch(d, a, stream) : qkv_attn_dispatch(d, a, stream);
   if (d->dtype == CVMI_F32) {
     CVMI_CHECK(d->dqk <= 128 && d->dv <= 128, "attention(f32): head dims up to 128");
     const long long rows = (long long)d->B * d->heads * d->Nq;

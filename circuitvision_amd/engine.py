@@ -698,9 +698,16 @@ def qkv_attn_supported(dim, dout, heads, ws, q_pool, dtype, nwin):
     return is16(dtype) and dim == 144 and ws == 8 and nwin % 2 == 0 and (dout, heads) == ((288, 4) if q_pool else (144, 2))
 
 
+def qkv_attn16_supported(dim, dout, heads, ws, q_pool, dtype, nwin):
+    """The shapes the fused launch of csrc/qkv_attn16.hpp is built for: 4 x 4-window Hiera blocks of input width 288 -- plain with 4 heads of
+    72, or the q-pooled 288 -> 576 transition with 8 -- in a 16-bit dtype, a whole number of eight-window (128-token) workgroups.  Its packed
+    weight is PackedQkvAttn's: the q chunks feed the same score fragments, so qkv_attn_rows is its row order too."""
+    return is16(dtype) and dim == 288 and ws == 4 and nwin % 8 == 0 and (dout, heads) == ((576, 8) if q_pool else (288, 4))
+
+
 class PackedQkvAttn:
-    """The qkv projection of a Hiera block for the fused qkv + window-attention launch: the rows of W / b in qkv_attn_rows order (zero rows
-    where it says -1), in PackedTokLinear's format -- no format of its own."""
+    """The qkv projection of a Hiera block for the fused qkv + window-attention launches (8 x 8 windows: csrc/qkv_attn.hpp; 4 x 4: csrc/qkv_attn16.hpp):
+    the rows of W / b in qkv_attn_rows order (zero rows where it says -1), in PackedTokLinear's format -- no format of its own."""
 
     def __init__(self, w, b, heads, device="cuda", dtype=F16):
         N, K = w.shape

@@ -31,7 +31,7 @@ from . import _lib
 from ._lib import ACT_GELU, ACT_NONE, ACT_RELU, ACT_SIGMOID, BF16, F16, F32
 from .engine import (ESIZE, TORCH_DTYPE, is16, Buf, PackedConv, PackedHieraMlp, PackedProjMlp, PackedQkvAttn, PackedTokLinear, Plan, Rows, hiera_mlp_supported, make_attn_desc, op_attention,
                      op_call, op_cast, op_conv, op_hiera_mlp, op_layernorm, op_maxpool2, op_tok_linear, op_tok_linear_pool, require_gpu, row_stats_supported,
-                     qkv_attn_supported, tok_linear_stats_parts, tok_linear_supported)
+                     qkv_attn16_supported, qkv_attn_supported, tok_linear_stats_parts, tok_linear_supported)
 
 LOG2E = 1.4426950408889634
 HIERA_L = dict(embed_dim=144, num_heads=2, stages=(2, 6, 36, 4), global_att_blocks=(23, 33, 43), window_spec=(8, 4, 16, 8))
@@ -215,6 +215,8 @@ class Sam2Weights:
         self.q_log2 = is16(dtype) and os.environ.get("CVMI_SAM_QLOG2", "1") != "0"
         # 8 x 8-window blocks of input width 144 (stage 1 and the transition into stage 2): qkv + window attention in one launch (csrc/qkv_attn.hpp); "0" restores the two launches
         self.qkv_attn = os.environ.get("CVMI_SAM_QKVATTN", "1") != "0"
+        # ... and the 4 x 4-window blocks of input width 288 (stage 2 and the transition into stage 3; csrc/qkv_attn16.hpp); "0" restores their two launches alone
+        self.qkv_attn16 = self.qkv_attn and os.environ.get("CVMI_SAM_QKVATTN16", "1") != "0"
         self.param_bytes = 0
         self.flops_per_image = 0
         self._trunk()
@@ -284,7 +286,8 @@ class Sam2Weights:
             self._norm(f"b{i}.norm1", f"{b}.norm1", dim)
             self._linear(f"b{i}.qkv", f"{b}.attn.qkv", 3 * dim_out, dim, tok=True,
                          row_scale=(dim_out, (dim_out // heads) ** -0.5 * LOG2E) if self.q_log2 else None,
-                         fuse_heads=heads if self.qkv_attn and qkv_attn_supported(dim, dim_out, heads, window, i in q_pool_blocks, self.dtype, 2) else 0)
+                         fuse_heads=heads if (self.qkv_attn and qkv_attn_supported(dim, dim_out, heads, window, i in q_pool_blocks, self.dtype, 2))
+                         or (self.qkv_attn16 and qkv_attn16_supported(dim, dim_out, heads, window, i in q_pool_blocks, self.dtype, 8)) else 0)
             self._linear(f"b{i}.proj", f"{b}.attn.proj", dim_out, dim_out, tok=True)
             self._norm(f"b{i}.norm2", f"{b}.norm2", dim_out)
             if self.fused_mlp and hiera_mlp_supported(dim_out, self.dtype):
@@ -580,9 +583,10 @@ class Sam2Plan:
                 op_maxpool2(self.plan, f"b{i}.pool", pj.view(), short.view())
         else:
             short = x
-        # qkv + window attention as ONE launch where the kernel is built for the block (stage 1): the qkv tensor is neither written nor read back
+        # qkv + window attention as ONE launch where a kernel is built for the block (stages 1 and 2): the qkv tensor is neither written nor read back
         fuse_qkv = (tok_qkv and ws > 0 and f"b{i}.qkv_attn" in wt.tl and not self.av_fp8 and (ln1_stats is None or parts == 0)
-                    and qkv_attn_supported(dim, dout, heads, ws, blk["q_pool"], self.dt, B * (Hp // ws) * (Wp // ws)))
+                    and (qkv_attn_supported(dim, dout, heads, ws, blk["q_pool"], self.dt, B * (Hp // ws) * (Wp // ws))
+                         or qkv_attn16_supported(dim, dout, heads, ws, blk["q_pool"], self.dt, B * (Hp // ws) * (Wp // ws))))
         qkv = None if fuse_qkv else self.buf(Hp, Wp, 3 * dout, tag="qkv")
         if fuse_qkv:
             pass

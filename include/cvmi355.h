@@ -187,7 +187,10 @@ typedef struct cvmi_attn_desc {
      LayerNorm(proj_x[token]) W^T + b and attends inside the windows, so the qkv tensor is never written (Hiera stage 1:
      `attn(window_partition(qkv(norm1(x))))`, behind sam2_infer.py:226).  Built for a 16-bit dtype, win = 8, head_dim 72, proj_K = 144, an even number
      of windows, and 2 heads (plain) or 4 heads with q_pool (the 144 -> 288 transition); every other combination is refused.  The result is
-     bit for bit that of cvmi_tok_linear into a [tokens, 3 * heads * 72] buffer followed by cvmi_attention on it. */
+     bit for bit that of cvmi_tok_linear into a [tokens, 3 * heads * 72] buffer followed by cvmi_attention on it.
+     Also built (Hiera stage 2): win = 4, head_dim 72, proj_K = 288, a multiple of 8 windows, 4 heads (plain) or 8 heads with q_pool (the
+     288 -> 576 transition), no av_fp8.  Its q, k, v are bit for bit cvmi_tok_linear's; the window attention runs on the matrix pipe with a
+     16-bit P, so the result is that of the two launches within the 16-bit window kernels' error bound, not bit for bit. */
   const void* proj_x;        /* f32 [img][grid_h][grid_w] token rows of proj_K values, row stride proj_ld elements */
   const void* proj_w;        /* the qkv weight [3 * heads * 72, proj_K] + bias in cvmi_tok_linear's packed format, rows permuted and zero-padded
                                 head by head (circuitvision_amd.engine.PackedQkvAttn states the order) */
