@@ -402,7 +402,7 @@ def op_sppf_pool(plan, label, buf, c):
     plan.add(label, "pool", thunk, 4 * n * ESIZE[buf.dtype], 0)
 
 
-def op_attention(plan, label, desc, keep, bytes_=0, flops=0):
+def op_attention(plan, label, desc, keep, bytes_=0, flops=0, kind="attention"):
     lib = _lib.load()
     plan.keep.append((desc, keep))
     sp0 = plan.sptr
@@ -412,7 +412,7 @@ def op_attention(plan, label, desc, keep, bytes_=0, flops=0):
         sp = sp0 if sp is None else sp
         _lib.check(fn(C.byref(desc), sp), label)
 
-    plan.add(label, "attention", thunk, bytes_, flops)
+    plan.add(label, kind, thunk, bytes_, flops)
 
 
 def make_attn_desc(**kw):

@@ -20,7 +20,6 @@ mode GEMM / attention operands are fp16.  F32 mode runs everything on exact-f32 
 """
 import hashlib
 import math
-import os
 import threading
 
 import numpy as np
@@ -29,9 +28,9 @@ import torch.nn.functional as TF
 
 from . import _lib
 from ._lib import ACT_GELU, ACT_NONE, ACT_RELU, ACT_SIGMOID, BF16, F16, F32
-from .engine import (ESIZE, TORCH_DTYPE, is16, Buf, PackedConv, PackedHieraMlp, PackedProjMlp, PackedQkvAttn, PackedTokLinear, Plan, Rows, hiera_mlp_supported, make_attn_desc, op_attention,
-                     op_call, op_cast, op_conv, op_hiera_mlp, op_layernorm, op_maxpool2, op_tok_linear, op_tok_linear_pool, require_gpu, row_stats_supported,
-                     qkv_attn16_supported, qkv_attn_supported, tok_linear_stats_parts, tok_linear_supported)
+from .engine import (ESIZE, TORCH_DTYPE, is16, Buf, PackedConv, PackedHieraMlp, PackedProjMlp, PackedQkvAttn, PackedTokLinear, Plan, Rows, make_attn_desc, op_attention,
+                     op_call, op_cast, op_conv, op_hiera_mlp, op_layernorm, op_maxpool2, op_tok_linear, op_tok_linear_pool, require_gpu, tok_linear_supported)
+from .hiera_route import WEIGHT_SWITCHES, block_packings, hiera_blocks, route_block, sam_switches
 
 LOG2E = 1.4426950408889634
 HIERA_L = dict(embed_dim=144, num_heads=2, stages=(2, 6, 36, 4), global_att_blocks=(23, 33, 43), window_spec=(8, 4, 16, 8))
@@ -209,14 +208,10 @@ class Sam2Weights:
         self.p, self.hiera, self.image_size, self.dtype, self.device = params, hiera, image_size, dtype, device
         self.use_refinement, self.kernels = use_refinement, tuple(refinement_kernels)
         self.pc, self.ln, self.const, self.mlp, self.tl = {}, {}, {}, {}, {}
-        self.fused_mlp = os.environ.get("CVMI_SAM_FUSED_MLP", "1") != "0"      # (the switches are for A/B measurements)
-        self.use_tok = os.environ.get("CVMI_SAM_TOKLIN", "1") != "0"
+        self.sw = sw = sam_switches()                      # (A/B switches, hiera_route.SWITCH_TABLE; the weight-level ones decide what is packed)
+        self.fused_mlp, self.use_tok, self.qkv_attn, self.qkv_attn16 = sw.fused_mlp, sw.toklin, sw.qkvattn, sw.qkvattn and sw.qkvattn16
         # Hiera q rows carry scale * log2(e) (16-bit plans): see _linear(row_scale=) and cvmi_attn_desc.q_log2
-        self.q_log2 = is16(dtype) and os.environ.get("CVMI_SAM_QLOG2", "1") != "0"
-        # 8 x 8-window blocks of input width 144 (stage 1 and the transition into stage 2): qkv + window attention in one launch (csrc/qkv_attn.hpp); "0" restores the two launches
-        self.qkv_attn = os.environ.get("CVMI_SAM_QKVATTN", "1") != "0"
-        # ... and the 4 x 4-window blocks of input width 288 (stage 2 and the transition into stage 3; csrc/qkv_attn16.hpp); "0" restores their two launches alone
-        self.qkv_attn16 = self.qkv_attn and os.environ.get("CVMI_SAM_QKVATTN16", "1") != "0"
+        self.q_log2 = is16(dtype) and sw.qlog2
         self.param_bytes = 0
         self.flops_per_image = 0
         self._trunk()
@@ -231,7 +226,7 @@ class Sam2Weights:
         self.param_bytes += pc.param_bytes
         return pc
 
-    def _linear(self, key, mod, cout, cin, tok=False, row_scale=None, fuse_heads=0):
+    def _linear(self, key, mod, cout, cin, row_scale=None, heads=0):
         w, b = self.p.weight(mod, (cout, cin)), self.p.bias(mod, cout)
         if row_scale is not None:
             # (rows, factor): the attention scale * log2(e) folded into the q rows of a qkv projection, in fp32 before the weights are rounded
@@ -240,13 +235,13 @@ class Sam2Weights:
             w, b = w.clone(), b.clone()
             w[:n] *= f
             b[:n] *= f
-        if tok and self.use_tok and is16(self.dtype) and tok_linear_supported(cin, self.dtype, 256):
+        if key in self.packed_keys:
             # short-K Hiera linears also in the token-stationary kernel's fragment order (tok_linear.hip); the plan picks it
             # whenever its row count is a multiple of 256
             self.tl[key] = PackedTokLinear(w, b, self.device, self.dtype)
-            if fuse_heads:
-                # ... and, rows permuted head by head, for the fused qkv + window-attention launch (engine.PackedQkvAttn)
-                self.tl[key + "_attn"] = PackedQkvAttn(w, b, fuse_heads, self.device, self.dtype)
+        if key + "_attn" in self.packed_keys:
+            # ... and, rows permuted head by head, for the fused qkv + window-attention launch (engine.PackedQkvAttn)
+            self.tl[key + "_attn"] = PackedQkvAttn(w, b, heads, self.device, self.dtype)
         return self._pack(key, _lin(w), b)
 
     def _norm(self, key, mod, c):
@@ -272,25 +267,16 @@ class Sam2Weights:
         win = self.p.tensor(f"{T}.pos_embed_window", (1, E, ws[0], ws[0]))
         pos = pos + win.tile([1, 1, g // ws[0], g // ws[0]])
         self.const["pos_embed"] = pos.permute(0, 2, 3, 1).reshape(g * g, E).contiguous().float().to(self.device)   # f32 residual stream
-        stage_ends = [sum(stages[:i]) - 1 for i in range(1, len(stages) + 1)]
-        q_pool_blocks = [x + 1 for x in stage_ends[:-1]][:3]
-        self.blocks, self.stage_ends = [], stage_ends
-        cur, dim, heads = 1, E, h["num_heads"]
-        for i in range(sum(stages)):
-            dim_out, window = dim, ws[cur - 1]
-            if i in h["global_att_blocks"]:
-                window = 0
-            if i - 1 in stage_ends:
-                dim_out, heads, cur = dim * 2, heads * 2, cur + 1
+        self.blocks, self.stage_ends = hiera_blocks(h)
+        self.packed_keys = block_packings(self.blocks, self.dtype, self.sw)      # keys of the packed forms beside the tiled GEMM's; Sam2Plan routes by them
+        for i, (dim, dim_out, heads, _, _) in enumerate(self.blocks):
             b = f"{T}.blocks.{i}"
             self._norm(f"b{i}.norm1", f"{b}.norm1", dim)
-            self._linear(f"b{i}.qkv", f"{b}.attn.qkv", 3 * dim_out, dim, tok=True,
-                         row_scale=(dim_out, (dim_out // heads) ** -0.5 * LOG2E) if self.q_log2 else None,
-                         fuse_heads=heads if (self.qkv_attn and qkv_attn_supported(dim, dim_out, heads, window, i in q_pool_blocks, self.dtype, 2))
-                         or (self.qkv_attn16 and qkv_attn16_supported(dim, dim_out, heads, window, i in q_pool_blocks, self.dtype, 8)) else 0)
-            self._linear(f"b{i}.proj", f"{b}.attn.proj", dim_out, dim_out, tok=True)
+            self._linear(f"b{i}.qkv", f"{b}.attn.qkv", 3 * dim_out, dim, heads=heads,
+                         row_scale=(dim_out, (dim_out // heads) ** -0.5 * LOG2E) if self.q_log2 else None)
+            self._linear(f"b{i}.proj", f"{b}.attn.proj", dim_out, dim_out)
             self._norm(f"b{i}.norm2", f"{b}.norm2", dim_out)
-            if self.fused_mlp and hiera_mlp_supported(dim_out, self.dtype):
+            if f"b{i}" in self.packed_keys:
                 # stages 1 / 2: norm2 + fc1 + GELU + fc2 + residual as ONE launch (hiera_mlp.hip); weights in fragment order
                 self.mlp[f"b{i}"] = PackedHieraMlp(self.p.weight(f"{b}.mlp.layers.0", (4 * dim_out, dim_out)), self.p.bias(f"{b}.mlp.layers.0", 4 * dim_out),
                                                    self.p.weight(f"{b}.mlp.layers.1", (dim_out, 4 * dim_out)), self.p.bias(f"{b}.mlp.layers.1", dim_out),
@@ -303,14 +289,10 @@ class Sam2Weights:
                                                           self.p.weight(f"{b}.mlp.layers.1", (dim_out, 4 * dim_out)), self.p.bias(f"{b}.mlp.layers.1", dim_out),
                                                           self.device, self.dtype)
             else:
-                self._linear(f"b{i}.fc1", f"{b}.mlp.layers.0", 4 * dim_out, dim_out, tok=True)
+                self._linear(f"b{i}.fc1", f"{b}.mlp.layers.0", 4 * dim_out, dim_out)
                 self._linear(f"b{i}.fc2", f"{b}.mlp.layers.1", dim_out, 4 * dim_out)
             if dim != dim_out:
-                self._linear(f"b{i}.dimproj", f"{b}.proj", dim_out, dim, tok=True)
-            self.blocks.append(dict(dim=dim, dim_out=dim_out, heads=heads, window=window, q_pool=i in q_pool_blocks))
-            if window > 0 and i in q_pool_blocks and window % 2:
-                raise ValueError("q-pool block with odd window")
-            dim = dim_out
+                self._linear(f"b{i}.dimproj", f"{b}.proj", dim_out, dim)
         self.stage_dims = [E * 2 ** s for s in range(len(stages))]
 
     def _neck_and_prompts(self, embedding_r):
@@ -489,7 +471,7 @@ class Sam2Plan:
         if attn not in ("16", "fp8") or (attn == "fp8" and not is16(wt.dtype)):
             raise ValueError("attn must be '16' or 'fp8' (fp8 needs an fp16 / bf16 plan)")
         self.av_fp8 = 1 if attn == "fp8" else 0
-        self._ln1_stats, self._ln1_parts = None, 0                    # LayerNorm statistics handed from a block's MLP to the next block's norm1
+        self.sw = sam_switches()._replace(**{f: getattr(wt.sw, f) for f in WEIGHT_SWITCHES})      # plan-level switches as set now, weight-level as packed
         self.P, self.K, self.want_high_res = prompts, points, high_res
         if prompts and not wt.prompt_ok:
             raise _lib.CvmiError("this checkpoint carries no sam_prompt_encoder tensors: box / point prompts are unavailable")
@@ -539,142 +521,98 @@ class Sam2Plan:
                 res=_ConstView(pos, E), res_mod=g * g, kind="stem")
         H = W = g
         stage_out = []
-        for i, blk in enumerate(wt.blocks):
-            x, H, W = self._block(i, blk, x, H, W)
+        state, stats = None, None                 # LayerNorm statistics a block leaves for the next block's norm1: the route's (rows, parts) and the tensor
+        for i in range(len(wt.blocks)):
+            route = route_block(wt.blocks, wt.packed_keys, i, B, H, W, self.dt, self.av_fp8, self.sw, state)
+            x, stats = self._block(i, route, x, H, W, stats)
+            H, W, state = route.OH, route.OW, route.stats_next
             if i in wt.stage_ends:
                 stage_out.append(x)
         self.stage_out = stage_out
         self._neck_decoder(stage_out)
 
     # ---- one Hiera block ---------------------------------------------------------------------------------
-    def _block(self, i, blk, x, H, W):
-        wt, B = self.wt, self.B
-        dim, dout, heads, ws = blk["dim"], blk["dim_out"], blk["heads"], blk["window"]
-        hd = dout // heads
+    def _block(self, i, r, x, H, W, stats_in):
+        """Emits block i's launches as r (hiera_route.BlockRoute) routes them.  stats_in: the statistics tensor the previous block left behind.
+        -> (x, the statistics tensor left for the next block's norm1)"""
+        wt, B, tl = self.wt, self.B, self.wt.tl
+        dim, dout, heads, _, q_pool = wt.blocks[i]
         gam, bet = wt.ln[f"b{i}.norm1"]
-        # Hiera pads the NORMALISED tokens up to a window multiple (zeros), attends inside the padded windows and crops
-        # after the un-partition: the padded grid is a zero-initialised buffer whose valid region the LayerNorm writes
-        Hp, Wp = (H, W) if ws == 0 else (-(-H // ws) * ws, -(-W // ws) * ws)
-        padded = (Hp, Wp) != (H, W)
-        if blk["q_pool"] and (ws == 0 or ws % 2 or Hp % 2 or Wp % 2):
-            raise NotImplementedError("q-pool block needs an even window")
-        tok_rows = not padded and (B * H * W) % 256 == 0          # token-stationary linears (tok_linear.hip) take 256-row workgroups
-        tok_qkv = tok_rows and f"b{i}.qkv" in wt.tl                # ... and fuse norm1 into the qkv projection
-        if dim != dout and os.environ.get("CVMI_SAM_QKVTOK_TRANS", "1") == "0":
-            tok_qkv = False                                        # (A/B: the transition blocks' qkv through the tiled GEMM + a norm1 launch)
-        tok_pool = tok_rows and dim != dout and f"b{i}.dimproj" in wt.tl and os.environ.get("CVMI_SAM_POOLFUSE", "1") != "0"     # norm1 + dimproj + 2 x 2 max-pool in one launch
-        if padded:
-            xn = self.buf(Hp, Wp, dim, tag="xn_padded", zero=True)
-            op_layernorm(self.plan, f"b{i}.norm1", x.view(), gam, bet, xn.view(), 1e-6, pad=(H, W, Hp, Wp))
-        elif not tok_qkv or (dim != dout and not tok_pool):
+        ln1 = (gam, bet, 1e-6)
+        if r.stats_in is None:
+            stats_in = None                                        # (none written for exactly these rows)
+        parts = r.stats_in or 0
+        if r.norm1 == "padded":
+            # the padded grid is a zero-initialised buffer whose valid region the LayerNorm writes
+            xn = self.buf(r.Hp, r.Wp, dim, tag="xn_padded", zero=True)
+            op_layernorm(self.plan, f"b{i}.norm1", x.view(), gam, bet, xn.view(), 1e-6, pad=(H, W, r.Hp, r.Wp))
+        elif r.norm1:
             xn = self.buf(H, W, dim, tag="xn")
             op_layernorm(self.plan, f"b{i}.norm1", x.view(), gam, bet, xn.view(), 1e-6)
-        parts = self._ln1_parts
-        ln1_stats = self._ln1_stats if (self._ln1_stats is not None and self._ln1_stats.numel() == 2 * B * H * W * max(parts, 1)) else None
-        self._ln1_stats, self._ln1_parts = None, 0                 # (written by the previous block's MLP for exactly these rows)
-        if dim != dout:
-            short = self.buf(H // 2, W // 2, dout, F32)
-            if tok_pool:
-                op_tok_linear_pool(self.plan, f"b{i}.dimproj_pool", wt.tl[f"b{i}.dimproj"], x.view(), short.view(), (gam, bet, 1e-6),
-                                   stats_in=ln1_stats if parts == 0 else None)
-            else:
-                pj = self.buf(H, W, dout, F32, tag="dimproj")
-                self.gemm(f"b{i}.dimproj", f"b{i}.dimproj", xn.view(), pj.view(), out_hw=(H, W) if padded else None)
-                op_maxpool2(self.plan, f"b{i}.pool", pj.view(), short.view())
-        else:
-            short = x
-        # qkv + window attention as ONE launch where a kernel is built for the block (stages 1 and 2): the qkv tensor is neither written nor read back
-        fuse_qkv = (tok_qkv and ws > 0 and f"b{i}.qkv_attn" in wt.tl and not self.av_fp8 and (ln1_stats is None or parts == 0)
-                    and (qkv_attn_supported(dim, dout, heads, ws, blk["q_pool"], self.dt, B * (Hp // ws) * (Wp // ws))
-                         or qkv_attn16_supported(dim, dout, heads, ws, blk["q_pool"], self.dt, B * (Hp // ws) * (Wp // ws))))
-        qkv = None if fuse_qkv else self.buf(Hp, Wp, 3 * dout, tag="qkv")
-        if fuse_qkv:
-            pass
-        elif tok_qkv:
-            op_tok_linear(self.plan, f"b{i}.qkv", wt.tl[f"b{i}.qkv"], x.view(), qkv.view(), ln=(gam, bet, 1e-6), stats_in=ln1_stats, stats_parts=parts)
-        else:
+        short = x if r.dimproj is None else self.buf(H // 2, W // 2, dout, F32)
+        if r.dimproj == "tok_pool":
+            op_tok_linear_pool(self.plan, f"b{i}.dimproj_pool", tl[f"b{i}.dimproj"], x.view(), short.view(), ln1, stats_in=stats_in if parts == 0 else None)
+        elif r.dimproj:
+            pj = self.buf(H, W, dout, F32, tag="dimproj")
+            self.gemm(f"b{i}.dimproj", f"b{i}.dimproj", xn.view(), pj.view(), out_hw=(H, W) if r.padded else None)
+            op_maxpool2(self.plan, f"b{i}.pool", pj.view(), short.view())
+        qkv = None if r.qkv == "fused" else self.buf(r.Hp, r.Wp, 3 * dout, tag="qkv")
+        if r.qkv == "tok":
+            op_tok_linear(self.plan, f"b{i}.qkv", tl[f"b{i}.qkv"], x.view(), qkv.view(), ln=ln1, stats_in=stats_in, stats_parts=parts)
+        elif r.qkv == "gemm":
             self.gemm(f"b{i}.qkv", f"b{i}.qkv", xn.view(), qkv.view())
-        OH, OW = (H // 2, W // 2) if blk["q_pool"] else (H, W)
-        OHp, OWp = (Hp // 2, Wp // 2) if blk["q_pool"] else (Hp, Wp)
-        ao = self.buf(OHp, OWp, dout, tag="ao")
-        es = ESIZE[self.dt]
-        base = qkv.t.data_ptr() if qkv is not None else 0
-        C3 = 3 * dout
-        if fuse_qkv:
-            nwin, pq = B * (H // ws) * (W // ws), wt.tl[f"b{i}.qkv_attn"]
-            xv = x.view()
-            nq = (ws // 2) ** 2 if blk["q_pool"] else ws * ws
-            desc = make_attn_desc(q=None, k=None, v=None, o=ao.t.data_ptr(), q_sb=0, q_sh=hd, q_st=C3, k_sb=0, k_sh=hd, k_st=C3, v_sb=0, v_sh=hd, v_st=C3,
-                                  o_sb=0, o_sh=hd, o_st=dout, B=nwin, heads=heads, Nq=nq, Nk=ws * ws, dqk=hd, dv=hd, scale=hd ** -0.5, dtype=self.dt,
-                                  win=ws, grid_h=H, grid_w=W, q_pool=1 if blk["q_pool"] else 0, av_fp8=0, q_log2=1 if wt.q_log2 else 0,
-                                  proj_x=xv.ptr, proj_ld=xv.ld, proj_K=dim, proj_w=pq.w.data_ptr(), proj_gamma=gam.data_ptr(), proj_beta=bet.data_ptr(),
-                                  proj_eps=1e-6, proj_stats=ln1_stats.data_ptr() if ln1_stats is not None else None)
-            rows = B * H * W
-            op_attention(self.plan, f"b{i}.attn", desc, (x, ao, pq, gam, bet, ln1_stats), bytes_=rows * dim * 4 + ao.nbytes,
-                         flops=2 * rows * C3 * dim + 4 * nwin * heads * nq * ws * ws * hd)
-            self.plan.ops[-1] = (self.plan.ops[-1][0], "attn_window") + self.plan.ops[-1][2:]
-        elif ws > 0:
-            nwin = B * (Hp // ws) * (Wp // ws)
-            nq = (ws // 2) ** 2 if blk["q_pool"] else ws * ws
-            desc = make_attn_desc(q=base, k=base + dout * es, v=base + 2 * dout * es, o=ao.t.data_ptr(),
-                                  q_sb=0, q_sh=hd, q_st=C3, k_sb=0, k_sh=hd, k_st=C3, v_sb=0, v_sh=hd, v_st=C3,
-                                  o_sb=0, o_sh=hd, o_st=dout, B=nwin, heads=heads, Nq=nq, Nk=ws * ws, dqk=hd, dv=hd,
-                                  scale=hd ** -0.5, dtype=self.dt, win=ws, grid_h=Hp, grid_w=Wp, q_pool=1 if blk["q_pool"] else 0, av_fp8=self.av_fp8,
-                                  q_log2=1 if wt.q_log2 else 0)
-            fl = 4 * nwin * heads * nq * ws * ws * hd
+        OH, OW = r.OH, r.OW
+        ao = self.buf(*((r.Hp // 2, r.Wp // 2) if q_pool else (r.Hp, r.Wp)), dout, tag="ao")
+        fl = 4 * r.nwin * heads * r.nq * r.nk * (dout // heads)
+        if r.qkv == "fused":
+            # the qkv tensor is neither written nor read back: the attention launch projects x itself
+            pq, xv, rows = tl[f"b{i}.qkv_attn"], x.view(), B * H * W
+            desc = self._attn_desc(i, r, ao, None, proj_x=xv.ptr, proj_ld=xv.ld, proj_K=dim, proj_w=pq.w.data_ptr(), proj_gamma=gam.data_ptr(),
+                                   proj_beta=bet.data_ptr(), proj_eps=1e-6, proj_stats=stats_in.data_ptr() if stats_in is not None else None)
+            op_attention(self.plan, f"b{i}.attn", desc, (x, ao, pq, gam, bet, stats_in), bytes_=rows * dim * 4 + ao.nbytes,
+                         flops=2 * rows * 3 * dout * dim + fl, kind="attn_window")
         else:
-            N = H * W
-            desc = make_attn_desc(q=base, k=base + dout * es, v=base + 2 * dout * es, o=ao.t.data_ptr(),
-                                  q_sb=N * C3, q_sh=hd, q_st=C3, k_sb=N * C3, k_sh=hd, k_st=C3, v_sb=N * C3, v_sh=hd, v_st=C3,
-                                  o_sb=N * dout, o_sh=hd, o_st=dout, B=B, heads=heads, Nq=N, Nk=N, dqk=hd, dv=hd,
-                                  scale=hd ** -0.5, dtype=self.dt, win=0, grid_h=0, grid_w=0, q_pool=0, av_fp8=self.av_fp8, q_log2=1 if wt.q_log2 else 0)
-            fl = 4 * B * heads * N * N * hd
-        if not fuse_qkv:
-            op_attention(self.plan, f"b{i}.attn", desc, (qkv, ao), bytes_=qkv.nbytes + ao.nbytes, flops=fl)
-            self.plan.ops[-1] = (self.plan.ops[-1][0], "attn_global" if ws == 0 else "attn_window") + self.plan.ops[-1][2:]
-        # x = shortcut + proj(attn)   (in place on the f32 residual stream)
-        tok_out = not padded and (B * OH * OW) % 256 == 0
-        # norm2's statistics travel from the launch that writes x to the launch that normalises it (fc1 then reads x once, not twice)
-        fwd = (tok_out and f"b{i}.proj" in wt.tl and f"b{i}" not in wt.mlp and f"b{i}.fc1" in wt.tl
-               and os.environ.get("CVMI_SAM_LNSTATS", "1") != "0")
-        sparts = tok_linear_stats_parts(B * OH * OW, dout, dout) if fwd else 0     # (a launch with fewer row blocks than CUs writes its statistics in slices)
-        stats = torch.empty(B * OH * OW, max(sparts, 1), 2, dtype=torch.float32, device=self.dev) if fwd else None
-        # stages 1 / 2: the projection is the prologue of the fused MLP launch (proj_mlp.hpp): x1 = shortcut + proj(attn) is neither written nor read back
-        fuse_proj = (f"b{i}.projmlp" in wt.mlp and not padded and ao.view().ld == dout and os.environ.get("CVMI_SAM_PROJMLP", "1") != "0")
-        if fuse_proj:
-            pass
-        elif tok_out and f"b{i}.proj" in wt.tl:
-            op_tok_linear(self.plan, f"b{i}.proj", wt.tl[f"b{i}.proj"], ao.view(), short.view(), residual=True, stats_out=stats, stats_eps=1e-6)
-        else:
-            self.gemm(f"b{i}.proj", f"b{i}.proj", ao.view(), short.view(), res=short.view(), out_hw=(OH, OW) if padded else None)
-        x = short
+            op_attention(self.plan, f"b{i}.attn", self._attn_desc(i, r, ao, qkv), (qkv, ao), bytes_=qkv.nbytes + ao.nbytes, flops=fl,
+                         kind="attn_global" if r.attn == "global" else "attn_window")
+        # x = shortcut + proj(attn)   (in place on the f32 residual stream); "fused": the prologue of the MLP launch below (proj_mlp.hpp), x1 is
+        # neither written nor read back
+        stats_fc1 = None if r.stats_fc1 is None else torch.empty(B * OH * OW, max(r.stats_fc1, 1), 2, dtype=torch.float32, device=self.dev)
+        if r.proj == "tok":
+            op_tok_linear(self.plan, f"b{i}.proj", tl[f"b{i}.proj"], ao.view(), short.view(), residual=True, stats_out=stats_fc1, stats_eps=1e-6)
+        elif r.proj == "gemm":
+            self.gemm(f"b{i}.proj", f"b{i}.proj", ao.view(), short.view(), res=short.view(), out_hw=(OH, OW) if r.padded else None)
+        x = short               # (after a stage's last block the next one writes its own shortcut buffer, so x stays intact as the stage output)
         gam, bet = wt.ln[f"b{i}.norm2"]
-        if f"b{i}" in wt.mlp:
-            nxt = wt.blocks[i + 1] if i + 1 < len(wt.blocks) else None
-            if nxt is not None and os.environ.get("CVMI_SAM_LNSTATS", "1") != "0" and f"b{i + 1}.qkv" in wt.tl and (B * OH * OW) % 256 == 0:
-                self._ln1_stats = torch.empty(B * OH * OW, 2, dtype=torch.float32, device=self.dev)      # the next block's norm1 reads x once
-            op_hiera_mlp(self.plan, f"b{i}.mlp", wt.mlp[f"b{i}"], x.view(), gam, bet, 1e-6, stats_out=self._ln1_stats, stats_eps=1e-6,
-                         proj=(wt.mlp[f"b{i}.projmlp"], ao.view()) if fuse_proj else None)
+        stats_out = None
+        if r.mlp == "fused":
+            if r.stats_mlp:
+                stats_out = torch.empty(B * OH * OW, 2, dtype=torch.float32, device=self.dev)      # the next block's norm1 reads x once
+            op_hiera_mlp(self.plan, f"b{i}.mlp", wt.mlp[f"b{i}"], x.view(), gam, bet, 1e-6, stats_out=stats_out, stats_eps=1e-6,
+                         proj=(wt.mlp[f"b{i}.projmlp"], ao.view()) if r.proj == "fused" else None)
+            return x, stats_out
+        hid = self.buf(OH, OW, 4 * dout, tag="hid")
+        if r.mlp == "tok_fc1":                                     # norm2 fused into fc1 (+ GELU)
+            op_tok_linear(self.plan, f"b{i}.fc1", tl[f"b{i}.fc1"], x.view(), hid.view(), ln=(gam, bet, 1e-6), act=ACT_GELU, stats_in=stats_fc1,
+                          stats_parts=r.stats_fc1 or 0)
         else:
-            hid = self.buf(OH, OW, 4 * dout, tag="hid")
-            if tok_out and f"b{i}.fc1" in wt.tl:                   # norm2 fused into fc1 (+ GELU)
-                op_tok_linear(self.plan, f"b{i}.fc1", wt.tl[f"b{i}.fc1"], x.view(), hid.view(), ln=(gam, bet, 1e-6), act=ACT_GELU, stats_in=stats, stats_parts=sparts)
-            else:
-                xn2 = self.buf(OH, OW, dout, tag="xn")
-                op_layernorm(self.plan, f"b{i}.norm2", x.view(), gam, bet, xn2.view(), 1e-6)
-                self.gemm(f"b{i}.fc1", f"b{i}.fc1", xn2.view(), hid.view(), act=ACT_GELU)
-            # a tiled GEMM hands the next block's norm1 raw per-slice sums (the 256 x 192 kernel: stage-3 fc2 shape); tok_linear adds them up
-            rs = None
-            nxt_qkv = f"b{i + 1}.qkv" in wt.tl and i + 1 < len(wt.blocks) and wt.blocks[i + 1]["dim"] == dout
-            if (nxt_qkv and tok_out and self.dt != F32 and row_stats_supported(B * OH * OW, dout, 4 * dout)
-                    and os.environ.get("CVMI_SAM_LNSTATS", "1") != "0" and os.environ.get("CVMI_SAM_LNSTATS_FC2", "1") != "0"):
-                rs = torch.empty(B * OH * OW, dout // 96, 2, dtype=torch.float32, device=self.dev)
-                self._ln1_stats, self._ln1_parts = rs, dout // 96
-            self.gemm(f"b{i}.fc2", f"b{i}.fc2", hid.view(), x.view(), res=x.view(), row_stats=rs)
-        if i in self.wt.stage_ends and i != len(self.wt.blocks) - 1:
-            # the next block writes its own shortcut buffer (dim change) -> x stays intact as the stage output
-            pass
-        return x, OH, OW
+            xn2 = self.buf(OH, OW, dout, tag="xn")
+            op_layernorm(self.plan, f"b{i}.norm2", x.view(), gam, bet, xn2.view(), 1e-6)
+            self.gemm(f"b{i}.fc1", f"b{i}.fc1", xn2.view(), hid.view(), act=ACT_GELU)
+        if r.stats_fc2 is not None:
+            stats_out = torch.empty(B * OH * OW, r.stats_fc2, 2, dtype=torch.float32, device=self.dev)
+        self.gemm(f"b{i}.fc2", f"b{i}.fc2", hid.view(), x.view(), res=x.view(), row_stats=stats_out)
+        return x, stats_out
+
+    def _attn_desc(self, i, r, ao, qkv, **proj):
+        """Descriptor of block i's attention over the qkv buffer, or (qkv None, proj = the proj_* fields) projecting inside the launch."""
+        _, dout, heads, ws, q_pool = self.wt.blocks[i]
+        hd, C3, step = dout // heads, 3 * dout, dout * ESIZE[self.dt]
+        q, k, v = (None,) * 3 if qkv is None else (qkv.t.data_ptr() + j * step for j in range(3))
+        sb = 0 if ws else r.nk                                     # windows are found through (win, grid); a global block strides image by image
+        return make_attn_desc(q=q, k=k, v=v, o=ao.t.data_ptr(), q_sb=sb * C3, q_sh=hd, q_st=C3, k_sb=sb * C3, k_sh=hd, k_st=C3, v_sb=sb * C3, v_sh=hd, v_st=C3,
+                              o_sb=sb * dout, o_sh=hd, o_st=dout, B=r.nwin, heads=heads, Nq=r.nq, Nk=r.nk, dqk=hd, dv=hd, scale=hd ** -0.5, dtype=self.dt,
+                              win=ws, grid_h=r.Hp if ws else 0, grid_w=r.Wp if ws else 0, q_pool=1 if q_pool else 0, av_fp8=self.av_fp8,
+                              q_log2=1 if r.q_log2 else 0, **proj)
 
     # ---- neck + mask decoder + tail -------------------------------------------------------------------------
     def _neck_decoder(self, st):
@@ -690,9 +628,8 @@ class Sam2Plan:
             return o
         feat_s0 = self.buf(f0, f0, 32)
         feat_s1 = self.buf(f1, f1, 64)
-        fused = os.environ.get("CVMI_SAM_NECKCAST", "1") != "0"
         for key, src, dstb, tag in (("feat_s0", st[0], feat_s0, "s0"), ("feat_s1", st[1], feat_s1, "s1")):
-            if fused and key in wt.tl and src.dtype == F32 and (B * src.H * src.W) % 256 == 0:
+            if self.sw.neckcast and key in wt.tl and src.dtype == F32 and (B * src.H * src.W) % 256 == 0:
                 op_tok_linear(self.plan, key, wt.tl[key], src.view(), dstb.view(), ln="cast", kind="neck")     # reads the f32 stage output itself
             else:
                 self.gemm(key, key, cast(src, tag).view(), dstb.view(), kind="neck")
@@ -723,7 +660,7 @@ class Sam2Plan:
             # f32 parity mode keeps the literal repeat_image formulation (upstream MaskDecoder.predict_masks) as the cross-check.
             # A mask prompt makes the image stream differ per pair from the start (nothing to share): one launch writes
             # keys = emb + mask_downscaling(mask_in) - no_mask_embed where the repeat pass stands, and in 16-bit mode the operand copy too.
-            self.share_l0 = is16(dt) and os.environ.get("CVMI_SAM_SHARE_L0", "1") != "0" and not self.mask_prompt
+            self.share_l0 = is16(dt) and self.sw.share_l0 and not self.mask_prompt
             if self.mask_prompt:
                 self.mask_in = torch.zeros(NB, f0, f0, dtype=torch.float32, device=self.dev)
                 kn0 = bufd(fs, fs, 256, tag="kn") if is16(dt) else None
@@ -762,8 +699,7 @@ class Sam2Plan:
                                   q_sb=Nq * qb.C, q_sh=hd, q_st=qb.C, k_sb=Nk * kb.C, k_sh=hd, k_st=kb.C, v_sb=Nk * vb.C, v_sh=hd, v_st=vb.C,
                                   o_sb=Nq * ob.C, o_sh=hd, o_st=ob.C, B=NB, heads=8, Nq=Nq, Nk=Nk, dqk=hd, dv=hd, scale=hd ** -0.5, dtype=dt,
                                   win=0, grid_h=0, grid_w=0, q_pool=0, q_bdiv=q_bdiv, kv_bdiv=kv_bdiv)
-            op_attention(self.plan, label, desc, (qb, kb, vb, ob), flops=4 * NB * 8 * Nq * Nk * hd)
-            self.plan.ops[-1] = (self.plan.ops[-1][0], "decoder") + self.plan.ops[-1][2:]
+            op_attention(self.plan, label, desc, (qb, kb, vb, ob), flops=4 * NB * 8 * Nq * Nk * hd, kind="decoder")
 
         dual = is16(dt)                          # norm4 writes the 16-bit operand copy of the image stream itself (no cast pass)
         qn = bufd(1, T, 256, tag="qn")           # compute-dtype copies of the f32 streams
