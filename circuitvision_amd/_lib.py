@@ -27,7 +27,7 @@ class ConvDesc(C.Structure):
         ("N", C.c_int), ("Kpad", C.c_int), ("act", C.c_int), ("dtype", C.c_int),
         ("out_f32", C.c_int), ("scalar_gather", C.c_int),
         ("res_mod", C.c_int), ("act_after_res", C.c_int), ("shuffle_cout", C.c_int), ("res_rep", C.c_int),
-        ("row_stats", C.c_void_p),
+        ("row_stats", C.c_void_p), ("res_map", C.c_void_p),
     ]
 
 
@@ -65,6 +65,7 @@ class AttnDesc(C.Structure):
         ("q_bdiv", C.c_int), ("kv_bdiv", C.c_int), ("av_fp8", C.c_int), ("q_log2", C.c_int),
         ("proj_x", C.c_void_p), ("proj_w", C.c_void_p), ("proj_gamma", C.c_void_p), ("proj_beta", C.c_void_p), ("proj_stats", C.c_void_p),
         ("proj_ld", C.c_int), ("proj_K", C.c_int), ("proj_eps", C.c_float),
+        ("q_bmap", C.c_void_p), ("kv_bmap", C.c_void_p),
     ]
 
 
@@ -140,10 +141,12 @@ SIGNATURES = {
     "cvmi_cast": (_i, [_vp, _i, _i, _vp, _i, _i, C.c_longlong, _i, _vp]),
     "cvmi_prompt_tokens": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _i, _i, _i, _i, _vp]),
     "cvmi_repeat_images": (_i, [_vp, _vp, C.c_longlong, _i, _i, _vp]),
+    "cvmi_gather_images": (_i, [_vp, _vp, _vp, _i, C.c_longlong, _vp, _i, _vp]),
     "cvmi_hyper_masks": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _i, _i, _f, _vp]),
     "cvmi_select_mask": (_i, [_vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _i, _i, _vp]),
     "cvmi_multimask_out": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _vp]),
     "cvmi_mask_prompt_embed": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "cvmi_mask_prompt_embed_pairs": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp]),
     "cvmi_bilinear_f32": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, _f, _vp]),
     "cvmi_mask_extent": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "cvmi_mask_postprocess": (_i, [_vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp]),

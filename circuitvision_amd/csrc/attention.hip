@@ -23,6 +23,7 @@ struct AttnArgs {
   float scale;
   int win, grid_h, grid_w, q_pool;
   int q_bdiv, kv_bdiv;   // batch sharing (no window): q rows of batch entry b come from entry b / q_bdiv, k / v rows from b / kv_bdiv
+  const int* q_bmap; const int* kv_bmap;      // ... or from the entry a device table names (cvmi_attn_desc.q_bmap / kv_bmap; null: the divisor)
   int qtiles;      // ceil(Nq / 32)
   int items;       // B * heads * qtiles
   int q_log2;      // cvmi_attn_desc.q_log2: q already carries scale * log2(e) (the dispatcher then passes scale = 1 / log2(e): every kernel's c = scale * log2(e) is 1 to one ulp; attn_dma72_kernel<.., QL = true> uses exactly 1)
@@ -221,7 +222,7 @@ __global__ __launch_bounds__(256) void attn_f16_kernel(const AttnArgs p) {
       u32x4 v = {0u, 0u, 0u, 0u};
       if (q_ok && d0 < p.dqk) {
         if (!p.q_pool) {
-          const long long off = tok_off(b / p.q_bdiv, qi, p.q_sb, p.q_st, p.win, p.grid_h, p.grid_w) + (long long)h * p.q_sh + d0;
+          const long long off = tok_off(p.q_bmap ? p.q_bmap[b] : b / p.q_bdiv, qi, p.q_sb, p.q_st, p.win, p.grid_h, p.grid_w) + (long long)h * p.q_sh + d0;
           v = *reinterpret_cast<const u32x4*>(p.q + off * 2);
         } else {                               // q = 2x2 max-pool of the window's projected q tokens
           // (not LOAD_Q_FRAGS: this kernel calls tok_off per pooled token instead of stepping from one hoisted offset)
@@ -268,7 +269,8 @@ __global__ __launch_bounds__(256) void attn_f16_kernel(const AttnArgs p) {
       const long long pix0 = tok_off(b, 0, 1, 1, p.win, p.grid_h, p.grid_w);      // window origin, in pixels
       korg = pix0 * p.k_st; vorg = pix0 * p.v_st;
     } else {
-      korg = (long long)(b / p.kv_bdiv) * p.k_sb; vorg = (long long)(b / p.kv_bdiv) * p.v_sb;
+      const int bkv = p.kv_bmap ? p.kv_bmap[b] : b / p.kv_bdiv;
+      korg = (long long)bkv * p.k_sb; vorg = (long long)bkv * p.v_sb;
     }
     kbase = p.k + (korg + (long long)h * p.k_sh) * 2;
     vbase = p.v + (vorg + (long long)h * p.v_sh) * 2;
@@ -432,7 +434,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn64_kernel(const 
     const int qc = q_ok ? qi : 0;
     int t = qc;
     if (p.q_pool) { const int py = qc / qwin, px = qc - py * qwin; t = (2 * py) * p.win + 2 * px; }
-    qoff0 = tok_off(b / p.q_bdiv, t, p.q_sb, p.q_st, p.win, p.grid_h, p.grid_w) + (long long)h * p.q_sh;
+    qoff0 = tok_off(p.q_bmap ? p.q_bmap[b] : b / p.q_bdiv, t, p.q_sb, p.q_st, p.win, p.grid_h, p.grid_w) + (long long)h * p.q_sh;
   }
   LOAD_Q_FRAGS(qf, QS, qoff0)
 
@@ -452,7 +454,8 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn64_kernel(const 
       const long long pix0 = tok_off(b, 0, 1, 1, p.win, p.grid_h, p.grid_w);
       korg = pix0 * p.k_st; vorg = pix0 * p.v_st;
     } else {
-      korg = (long long)(b / p.kv_bdiv) * p.k_sb; vorg = (long long)(b / p.kv_bdiv) * p.v_sb;
+      const int bkv = p.kv_bmap ? p.kv_bmap[b] : b / p.kv_bdiv;
+      korg = (long long)bkv * p.k_sb; vorg = (long long)bkv * p.v_sb;
     }
     kbase = p.k + (korg + (long long)h * p.k_sh) * 2;
     vbase = p.v + (vorg + (long long)h * p.v_sh) * 2;
@@ -1414,9 +1417,12 @@ extern "C" int CVMI_ENTRY(cvmi_attention)(const cvmi_attn_desc* d, cvmi_stream_t
   a.B = d->B; a.heads = d->heads; a.Nq = d->Nq; a.Nk = d->Nk; a.dqk = d->dqk; a.dv = d->dv; a.scale = d->q_log2 ? 0.6931471805599453f : d->scale; a.q_log2 = d->q_log2;
   a.win = d->win; a.grid_h = d->grid_h; a.grid_w = d->grid_w; a.q_pool = d->q_pool;
   a.q_bdiv = d->q_bdiv > 1 ? d->q_bdiv : 1; a.kv_bdiv = d->kv_bdiv > 1 ? d->kv_bdiv : 1;
-  const bool shared = a.q_bdiv > 1 || a.kv_bdiv > 1;
+  a.q_bmap = d->q_bmap; a.kv_bmap = d->kv_bmap;
+  CVMI_CHECK(!(d->q_bmap && a.q_bdiv > 1) && !(d->kv_bmap && a.kv_bdiv > 1), "attention: q_bmap / kv_bmap exclude a divisor (q_bdiv / kv_bdiv > 1) on the same operand");
+  CVMI_CHECK((((uintptr_t)d->q_bmap | (uintptr_t)d->kv_bmap) & 3) == 0, "attention: misaligned q_bmap / kv_bmap");
+  const bool shared = a.q_bdiv > 1 || a.kv_bdiv > 1 || d->q_bmap || d->kv_bmap;
   CVMI_CHECK(!shared || (d->win == 0 && d->dtype == CVMI_T16 && d->dqk <= 64 && d->dv <= 64 && d->B % a.q_bdiv == 0 && d->B % a.kv_bdiv == 0),
-             "attention: batch sharing (q_bdiv / kv_bdiv) needs fp16, no window, head dims <= 64 and B a multiple of the divisor");
+             "attention: batch sharing (q_bdiv / kv_bdiv, q_bmap / kv_bmap) needs fp16, no window, head dims <= 64 and B a multiple of the divisor");
   a.qtiles = (d->Nq + 31) / 32;
   a.div_win.init(d->win > 0 ? (unsigned)d->win : 1u);
   a.wpr = d->win > 0 ? d->grid_w / d->win : 1;

@@ -35,10 +35,12 @@ __device__ __forceinline__ void tile_put4(char* d, const float (&v)[4]) {
 }
 
 // residual row of output row m: plain, a constant broadcast over the batch (res_mod rows, m % res_mod), or one image's rows
-// shared by res_rep consecutive batch entries (res_mod rows per image: entry e reads image e / res_rep)
-__device__ __forceinline__ size_t res_row(int m, int res_mod, int res_rep) {
+// shared by res_rep consecutive batch entries (res_mod rows per image: entry e reads image e / res_rep) or by the entries a table names
+// (res_map, uniform over the launch: entry e reads image res_map[e]; the host has excluded res_rep > 1 beside it)
+__device__ __forceinline__ size_t res_row(int m, int res_mod, int res_rep, const int* res_map = nullptr) {
   if (res_mod <= 0) return (size_t)m;
   const int r = m % res_mod;
+  if (res_map) return (size_t)res_map[m / res_mod] * (size_t)res_mod + (size_t)r;
   if (res_rep <= 1) return (size_t)r;
   return (size_t)(m / res_mod / res_rep) * (size_t)res_mod + (size_t)r;
 }
@@ -62,13 +64,13 @@ struct ResHeld {
 // overlaps it instead of being paid per store-loop iteration (the compiler cannot hoist the loads over the stores: res and y may
 // alias).  A macro on purpose: hipcc unrolls the loop of a callee before it inlines it and then computes all NIT rows ahead of the
 // caller's branch (gemm256x192_kernel<float>: 56 spilled registers); pasted in, the loop unrolls with the kernel's own.
-#define RES_PREFETCH(TO, NT, NCH, NIT, rv, res, res_ld, res_mod, res_rep, M, tid, m0, n0) \
+#define RES_PREFETCH(TO, NT, NCH, NIT, rv, res, res_ld, res_mod, res_rep, res_map, M, tid, m0, n0) \
   _Pragma("unroll") for (int it_ = 0; it_ < (NIT); ++it_) { \
     const int idx_ = (tid) + it_ * (NT); \
     const int row_ = idx_ / (NCH), ch_ = idx_ - row_ * (NCH); \
     int m_ = (m0) + row_; \
     m_ = m_ < (M) ? m_ : (M) - 1; \
-    const size_t rpix_ = res_row(m_, res_mod, res_rep); \
+    const size_t rpix_ = res_row(m_, res_mod, res_rep, res_map); \
     rv[it_] = *reinterpret_cast<const u32x4*>((res) + (rpix_ * (res_ld) + (n0) + ch_ * (16 / (int)sizeof(TO))) * (int)sizeof(TO)); \
   }
 

@@ -30,6 +30,7 @@ struct ConvKArgs {
   int M, N, K, Kpad;
   int act, scalar_gather;
   int res_mod, act_after_res, shuf_c, res_rep;
+  const int* res_map;                    // cvmi_conv_desc.res_map: batch entry e reads residual image res_map[e] (null: off)
   int plain;
   int rows2;                             // 1x1 / s1 / p0 over two concatenated sources with channel counts that are K-tile multiples
   int nb_n;
@@ -139,7 +140,7 @@ __device__ __forceinline__ void gemm_epilogue(const ConvKArgs& p, f32x16 (&acc)[
   constexpr int NPF = (BM * NCH) % NT == 0 && (BM * NCH) / NT <= 16 ? (BM * NCH) / NT : 0;
   const bool res_pf = p.res != nullptr && p.shuf_c == 0 && n0 + BN <= p.N && NPF > 0;
   u32x4 rv[NPF > 0 ? NPF : 1];
-  if (res_pf) { RES_PREFETCH(TO, NT, NCH, NPF, rv, p.res, p.res_ld, p.res_mod, p.res_rep, p.M, tid, m0, n0); }
+  if (res_pf) { RES_PREFETCH(TO, NT, NCH, NPF, rv, p.res, p.res_ld, p.res_mod, p.res_rep, p.res_map, p.M, tid, m0, n0); }
   if (KS == 1 || tid < WM * WN * 64)
   with_act<FAST>(p.act_after_res ? CVMI_ACT_NONE : p.act, [&](auto actf) {
 #pragma unroll
@@ -179,7 +180,7 @@ __device__ __forceinline__ void gemm_epilogue(const ConvKArgs& p, f32x16 (&acc)[
     const int m = m0 + row, n = n0 + ch * OVEC;
     if (m >= p.M || n >= p.N) continue;
     const u32x4 cv = *reinterpret_cast<const u32x4*>(Ct + row * CROWB + ch * 16);
-    size_t ypix = (size_t)m, rpix = res_row(m, p.res_mod, p.res_rep);
+    size_t ypix = (size_t)m, rpix = res_row(m, p.res_mod, p.res_rep, p.res_map);
     int nn = n;
     if (p.shuf_c > 0) {                            // ConvTranspose 2x2/s2: scatter to the 2x grid
       const int q = n / p.shuf_c;
@@ -187,7 +188,12 @@ __device__ __forceinline__ void gemm_epilogue(const ConvKArgs& p, f32x16 (&acc)[
       const int b = m / ohow, r = m - b * ohow;
       const int oy = r / p.OW, ox = r - oy * p.OW;
       ypix = ((size_t)b * (2 * p.OH) + 2 * oy + (q >> 1)) * (size_t)(2 * p.OW) + 2 * ox + (q & 1);
-      rpix = p.res_rep > 1 ? ((size_t)(b / p.res_rep) * (2 * p.OH) + 2 * oy + (q >> 1)) * (size_t)(2 * p.OW) + 2 * ox + (q & 1) : ypix;
+      if (p.res_map || p.res_rep > 1) {              // the residual of the image this batch entry shares: the table's, or b / res_rep
+        const int rb = p.res_map ? p.res_map[b] : b / p.res_rep;
+        rpix = ((size_t)rb * (2 * p.OH) + 2 * oy + (q >> 1)) * (size_t)(2 * p.OW) + 2 * ox + (q & 1);
+      } else {
+        rpix = ypix;
+      }
     }
     store_out_chunk<TO, FAST, true>(p.y + (ypix * p.y_ld + nn) * OES, cv, a, n, p.N, ResLoad<TO>{p.res, p.res_ld, rpix, nn}, p.act_after_res, p.act);
   }
@@ -1184,7 +1190,7 @@ __global__ __launch_bounds__(512, 1) void gemm256x192_kernel(const ConvKArgs p) 
   for (int pass = 0; pass < NPASS; ++pass) {
     const bool full = n0 + pass * CW + CW <= p.N;
     u32x4 rv[NIT];
-    if (p.res && full) { RES_PREFETCH(TO, 512, NCH, NIT, rv, p.res, p.res_ld, p.res_mod, 0, p.M, tid, m0, n0 + pass * CW); }      // (res_rep > 1 never comes here: launch_typed)
+    if (p.res && full) { RES_PREFETCH(TO, 512, NCH, NIT, rv, p.res, p.res_ld, p.res_mod, 0, nullptr, p.M, tid, m0, n0 + pass * CW); }      // (res_rep > 1 / res_map never come here: launch_typed)
     if (NPASS == 1 || wh == pass) {
       const int cbase = NPASS == 1 ? wh * 96 : 0;
       with_act<true>(p.act_after_res ? CVMI_ACT_NONE : p.act, [&](auto actf) {
@@ -1554,7 +1560,7 @@ bool im2col_256_ok(const ConvKArgs& a) {
   constexpr int i2c_tiles = 128;
   const int tpt = a.ctot / 64;
   if (a.plain || !(!a.rows2 && a.x1 == nullptr && a.up0 == 0 && !a.scalar_gather && a.KW == 3 && a.K == 9 * a.ctot &&
-        a.ctot % 64 == 0 && tpt >= 1 && (tpt & (tpt - 1)) == 0 && a.Kpad == a.K && a.N % 8 == 0 && a.shuf_c == 0 && a.res_rep <= 1 && !a.stats && a.res_mod == 0))
+        a.ctot % 64 == 0 && tpt >= 1 && (tpt & (tpt - 1)) == 0 && a.Kpad == a.K && a.N % 8 == 0 && a.shuf_c == 0 && a.res_rep <= 1 && !a.res_map && !a.stats && a.res_mod == 0))
     return false;
   const long long tiles = (long long)cdiv(a.M, 256) * cdiv(a.N, 256);
   // (N = 128 fills half of every tile's columns: still a gain over conv_tile_kernel for the 64-channel model.1, 957 -> 633 us, a loss against the
@@ -1579,7 +1585,7 @@ int launch_typed(ConvKArgs& a, hipStream_t stream) {
     // (N = 576 -> 75 % of 3 column tiles: ties / loses against the 128-row kernels below)
     constexpr int g256_mink = 128;
     constexpr int g256_minn = 256;      // (r04: 384 -> 256, YOLO11-l model.2.cv2 654 -> 424 us; Hiera unaffected)
-    if (a.plain && a.K % 8 == 0 && a.K >= g256_mink && a.Kpad % 64 == 0 && N % 8 == 0 && N >= g256_minn && a.shuf_c == 0 && a.res_rep <= 1) {
+    if (a.plain && a.K % 8 == 0 && a.K >= g256_mink && a.Kpad % 64 == 0 && N % 8 == 0 && N >= g256_minn && a.shuf_c == 0 && a.res_rep <= 1 && !a.res_map) {
       const long long tiles = (long long)cdiv(M, 256) * cdiv(N, 256);
       const double col_eff = (double)N / (cdiv(N, 256) * 256), wave_eff = (double)tiles / (double)(cdiv(tiles, 256) * 256);
       if (!a.stats && tiles >= 256 && col_eff >= 0.8 && wave_eff >= 0.8) {
@@ -1673,7 +1679,7 @@ extern "C" int CVMI_ENTRY(cvmi_conv2d)(const cvmi_conv_desc* d, cvmi_stream_t st
   a.H = d->H; a.W = d->W; a.OH = d->OH; a.OW = d->OW; a.KW = d->KW; a.stride = d->stride; a.pad = d->pad;
   a.M = (int)M; a.N = d->N; a.K = (int)K; a.Kpad = d->Kpad;
   a.act = d->act; a.scalar_gather = d->scalar_gather; a.nb_n = 1;
-  a.res_mod = d->res_mod; a.act_after_res = d->act_after_res; a.shuf_c = d->shuffle_cout; a.res_rep = d->res_rep;
+  a.res_mod = d->res_mod; a.act_after_res = d->act_after_res; a.shuf_c = d->shuffle_cout; a.res_rep = d->res_rep; a.res_map = d->res_map;
   a.stats = d->row_stats;
   a.im2col_shift = 0;
   CVMI_CHECK(!d->row_stats || (d->out_f32 && d->res && !d->act_after_res && d->N % 192 == 0 && ((uintptr_t)d->row_stats & 7) == 0),
@@ -1685,6 +1691,8 @@ extern "C" int CVMI_ENTRY(cvmi_conv2d)(const cvmi_conv_desc* d, cvmi_stream_t st
   CVMI_CHECK(d->res_mod >= 0 && d->shuffle_cout >= 0, "conv2d: negative res_mod / shuffle_cout");
   CVMI_CHECK(d->res_rep <= 1 || (d->res && d->B % d->res_rep == 0 && (d->shuffle_cout > 0 || d->res_mod == d->OH * d->OW)),
              "conv2d: res_rep needs a residual, B %% res_rep == 0 and either shuffle_cout or res_mod == OH * OW");
+  CVMI_CHECK(!d->res_map || (d->res && d->res_rep <= 1 && ((uintptr_t)d->res_map & 3) == 0 && (d->shuffle_cout > 0 || d->res_mod == d->OH * d->OW)),
+             "conv2d: res_map needs a residual, res_rep <= 1 and either shuffle_cout or res_mod == OH * OW");
   if (d->shuffle_cout > 0) {
     CVMI_CHECK(d->N == 4 * d->shuffle_cout && d->shuffle_cout % ovec == 0 && d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0 &&
                d->res_mod == 0, "conv2d: shuffle_cout needs a 1x1 conv with N == 4*shuffle_cout (multiple of %d)", ovec);

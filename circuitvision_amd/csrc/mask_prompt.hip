@@ -10,6 +10,8 @@
 //                              pixels, lane i computes the 16 hidden values of pixel i in registers, then the wave walks its pixels with the
 //                              hidden vector of pixel j read across lanes (v_readlane), every lane producing ITS four output channels from the
 //                              64 weights of the 1 x 1 convolution it keeps in registers -- one 16-byte store per lane and pixel row.
+//                              cvmi_mask_prompt_embed_pairs runs the same kernel for pairs whose images a device table names (prompt lists:
+//                              pair i belongs to image pair_image[i] instead of i / rep).
 //   multimask_out_kernel       the multimask tail: tokens 1..3 of masks4 / iou4 as contiguous [n, 3, P] / [n, 3] (sibling of select_mask_kernel).
 #include <algorithm>
 
@@ -43,7 +45,8 @@ template <typename TL> using Lp4 = TL __attribute__((ext_vector_type(4)));      
 
 template <typename TL>
 __global__ __launch_bounds__(NT) void mask_prompt_embed_kernel(const float* __restrict__ mask, const float* __restrict__ emb, const float* __restrict__ params,
-                                                               float* __restrict__ keys, TL* __restrict__ keys_lp, int rep, int fs, int total) {
+                                                               float* __restrict__ keys, TL* __restrict__ keys_lp, int rep, int fs, int total,
+                                                               const int* __restrict__ pair_image) {
   __shared__ __attribute__((aligned(16))) float prm[N_PARAMS];
   for (int i = threadIdx.x; i < N_PARAMS / 4; i += NT) ((f32x4*)prm)[i] = ((const f32x4*)params)[i];
   __syncthreads();
@@ -69,7 +72,7 @@ __global__ __launch_bounds__(NT) void mask_prompt_embed_kernel(const float* __re
     const int cnt = min(64, total - q0);                                 // wave-uniform; the lanes past it recompute the last pixel and store nothing
     const int q = q0 + (lane < cnt ? lane : cnt - 1);
     const int pair = q / P, p = q - pair * P, y = p / fs, x = p - y * fs;
-    const int erow = (pair / rep) * P + p;                               // row of emb [B * P, 256] this pixel adds (image-major pairs)
+    const int erow = (pair_image ? pair_image[pair] : pair / rep) * P + p;      // row of emb [B * P, 256] this pixel adds (image-major pairs, or the table's image)
     // ---- the 4 x 4 patch -> 4 channels on 2 x 2 -> 16 channels, all in registers
     const float* mp = mask + ((size_t)pair * mw + 4 * y) * mw + 4 * x;
     f32x4 pt[4];
@@ -151,8 +154,9 @@ __global__ __launch_bounds__(NT) void multimask_out_kernel(const float* __restri
 
 }  // namespace
 
-extern "C" int cvmi_mask_prompt_embed(const float* mask, const float* emb, const float* params, float* keys, void* keys_lp, int lp_dtype, int B, int rep,
-                                      int fs, cvmi_stream_t stream_) {
+// pair_image == nullptr: B * rep image-major pairs; else B pairs (rep = 1) whose images the device table names
+static int mask_prompt_embed_launch(const float* mask, const float* emb, const float* params, float* keys, void* keys_lp, int lp_dtype, int B, int rep,
+                                    int fs, const int* pair_image, cvmi_stream_t stream_) {
   CVMI_CHECK(mask && emb && params && keys && B > 0 && rep > 0 && fs > 0, "mask_prompt_embed: bad arguments");
   CVMI_CHECK(!keys_lp || lp_dtype == CVMI_F16 || lp_dtype == CVMI_BF16, "mask_prompt_embed: the 16-bit copy must be CVMI_F16 or CVMI_BF16");
   CVMI_CHECK((((uintptr_t)mask | (uintptr_t)emb | (uintptr_t)params | (uintptr_t)keys) & 15) == 0 && ((uintptr_t)keys_lp & 7) == 0,
@@ -163,13 +167,24 @@ extern "C" int cvmi_mask_prompt_embed(const float* mask, const float* emb, const
   hipStream_t s = (hipStream_t)stream_;
   if (keys_lp && lp_dtype == CVMI_BF16) {
     cvmi_note_kernel("mask_prompt_embed_kernel<__bf16>");
-    hipLaunchKernelGGL(mask_prompt_embed_kernel<__bf16>, dim3(grid), dim3(NT), 0, s, mask, emb, params, keys, (__bf16*)keys_lp, rep, fs, (int)total);
+    hipLaunchKernelGGL(mask_prompt_embed_kernel<__bf16>, dim3(grid), dim3(NT), 0, s, mask, emb, params, keys, (__bf16*)keys_lp, rep, fs, (int)total, pair_image);
   } else {
     cvmi_note_kernel("mask_prompt_embed_kernel<_Float16>");
-    hipLaunchKernelGGL(mask_prompt_embed_kernel<_Float16>, dim3(grid), dim3(NT), 0, s, mask, emb, params, keys, (_Float16*)keys_lp, rep, fs, (int)total);
+    hipLaunchKernelGGL(mask_prompt_embed_kernel<_Float16>, dim3(grid), dim3(NT), 0, s, mask, emb, params, keys, (_Float16*)keys_lp, rep, fs, (int)total, pair_image);
   }
   CVMI_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int cvmi_mask_prompt_embed(const float* mask, const float* emb, const float* params, float* keys, void* keys_lp, int lp_dtype, int B, int rep,
+                                      int fs, cvmi_stream_t stream_) {
+  return mask_prompt_embed_launch(mask, emb, params, keys, keys_lp, lp_dtype, B, rep, fs, nullptr, stream_);
+}
+
+extern "C" int cvmi_mask_prompt_embed_pairs(const float* mask, const float* emb, const float* params, float* keys, void* keys_lp, int lp_dtype, int n_pairs,
+                                            const int* pair_image, int fs, cvmi_stream_t stream_) {
+  CVMI_CHECK(pair_image && ((uintptr_t)pair_image & 3) == 0, "mask_prompt_embed_pairs: the pair table must be a 4-byte aligned device pointer");
+  return mask_prompt_embed_launch(mask, emb, params, keys, keys_lp, lp_dtype, n_pairs, 1, fs, pair_image, stream_);
 }
 
 extern "C" int cvmi_multimask_out(const float* masks, const float* iou, int iou_ld, float* low_res3, float* iou3, int n, int P, cvmi_stream_t stream_) {

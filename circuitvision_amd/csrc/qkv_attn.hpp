@@ -158,7 +158,7 @@ static int qkv_attn_dispatch(const cvmi_attn_desc* d, const AttnArgs& a, hipStre
   CVMI_CHECK(d->proj_K == 144, "attention(qkv fused): K=%d is not built (144)", d->proj_K);
   CVMI_CHECK(d->heads == (d->q_pool ? 4 : 2), "attention(qkv fused): heads=%d is not built (plain: 2 heads of 72, q_pool: 4)", d->heads);
   CVMI_CHECK(d->B % 2 == 0, "attention(qkv fused): B=%d windows are no whole number of 128-token workgroups", d->B);
-  CVMI_CHECK(a.q_bdiv == 1 && a.kv_bdiv == 1, "attention(qkv fused): no batch sharing");
+  CVMI_CHECK(a.q_bdiv == 1 && a.kv_bdiv == 1 && !a.q_bmap && !a.kv_bmap, "attention(qkv fused): no batch sharing");
   CVMI_CHECK(d->proj_w && d->proj_gamma && d->proj_beta, "attention(qkv fused): needs the packed weight and gamma / beta");
   CVMI_CHECK(d->proj_ld >= d->proj_K && d->proj_ld % 4 == 0 &&
                  (((uintptr_t)d->proj_x | (uintptr_t)d->proj_w | (uintptr_t)d->proj_gamma | (uintptr_t)d->proj_beta) & 15) == 0 && ((uintptr_t)d->proj_stats & 7) == 0,

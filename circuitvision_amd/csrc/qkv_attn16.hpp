@@ -174,7 +174,7 @@ static int qkv_attn16_dispatch(const cvmi_attn_desc* d, const AttnArgs& a, hipSt
   CVMI_CHECK(!d->av_fp8, "attention(qkv fused, 4 x 4): no fp8 AV product (av_fp8)");
   CVMI_CHECK(d->heads == (d->q_pool ? 8 : 4), "attention(qkv fused, 4 x 4): heads=%d is not built (plain: 4 heads of 72, q_pool: 8)", d->heads);
   CVMI_CHECK(d->B % (2 * QW_NW) == 0, "attention(qkv fused, 4 x 4): B=%d windows are no whole number of 128-token workgroups", d->B);
-  CVMI_CHECK(a.q_bdiv == 1 && a.kv_bdiv == 1, "attention(qkv fused, 4 x 4): no batch sharing");
+  CVMI_CHECK(a.q_bdiv == 1 && a.kv_bdiv == 1 && !a.q_bmap && !a.kv_bmap, "attention(qkv fused, 4 x 4): no batch sharing");
   CVMI_CHECK(d->proj_w && d->proj_gamma && d->proj_beta, "attention(qkv fused, 4 x 4): needs the packed weight and gamma / beta");
   CVMI_CHECK(d->proj_ld >= d->proj_K && d->proj_ld % 4 == 0 &&
                  (((uintptr_t)d->proj_x | (uintptr_t)d->proj_w | (uintptr_t)d->proj_gamma | (uintptr_t)d->proj_beta) & 15) == 0 && ((uintptr_t)d->proj_stats & 7) == 0,

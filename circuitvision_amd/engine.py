@@ -246,8 +246,9 @@ def row_stats_supported(M, N, K):
 
 
 def op_conv(plan, label, pc, srcs, dst, stride=1, pad=None, act=_lib.ACT_NONE, res=None, out_hw=None,
-            scalar_gather=False, kind="conv", res_mod=0, act_after_res=False, shuffle_cout=0, res_rep=0, row_stats=None):
-    """srcs: [(View, up)] (1 or 2 channel-concatenated sources).  dst / res: View."""
+            scalar_gather=False, kind="conv", res_mod=0, act_after_res=False, shuffle_cout=0, res_rep=0, row_stats=None, res_map=None):
+    """srcs: [(View, up)] (1 or 2 channel-concatenated sources).  dst / res: View.  res_map: device int32 [batch] tensor, batch entry e reads
+    residual image res_map[e] (cvmi_conv_desc.res_map); its values are the caller's to keep inside the residual."""
     lib = _lib.load()
     (v0, up0) = srcs[0]
     v1, up1 = (srcs[1] if len(srcs) > 1 else (None, 0))
@@ -269,6 +270,9 @@ def op_conv(plan, label, pc, srcs, dst, stride=1, pad=None, act=_lib.ACT_NONE, r
     if res_rep > 1:
         assert res is not None and res.B * res_rep == v0.B, (label, "res_rep needs a per-image residual")
         assert shuffle_cout or res_mod == dst.H * dst.W, (label, "res_rep: ConvTranspose scatter or res_mod = rows per image")
+    if res_map is not None:
+        assert res is not None and res_rep <= 1 and res_map.dtype == torch.int32 and res_map.is_cuda and res_map.numel() == v0.B, (label, "res_map: one int32 per batch entry")
+        assert shuffle_cout or res_mod == dst.H * dst.W, (label, "res_map: ConvTranspose scatter or res_mod = rows per image")
     out_f32 = 1 if (dst.dtype == F32 and is16(pc.dtype)) else 0
     d = ConvDesc(
         x0=v0.ptr, x1=(v1.ptr if v1 is not None else None), w=pc.w.data_ptr(), bias=pc.bias.data_ptr(),
@@ -278,10 +282,10 @@ def op_conv(plan, label, pc, srcs, dst, stride=1, pad=None, act=_lib.ACT_NONE, r
         B=v0.B, H=H, W=W, OH=OH, OW=OW, KH=pc.KH, KW=pc.KW, stride=stride, pad=pad,
         N=pc.N, Kpad=pc.Kpad, act=act, dtype=pc.dtype, out_f32=out_f32, scalar_gather=1 if scalar_gather else 0,
         res_mod=res_mod, act_after_res=1 if act_after_res else 0, shuffle_cout=shuffle_cout, res_rep=res_rep,
-        row_stats=(row_stats.data_ptr() if row_stats is not None else None))
+        row_stats=(row_stats.data_ptr() if row_stats is not None else None), res_map=(res_map.data_ptr() if res_map is not None else None))
     if row_stats is not None:       # f32 [rows, N / 96, 2]: (mean, sum of squared deviations) per 96-column slice of every written row (Hiera stage-3 fc2 shape only)
         assert row_stats.dtype == torch.float32 and row_stats.is_contiguous() and row_stats.numel() == v0.B * OH * OW * (pc.N // 96) * 2, label
-    plan.keep.append((d, pc, srcs, dst, res, row_stats))
+    plan.keep.append((d, pc, srcs, dst, res, row_stats, res_map))
     sp0 = plan.sptr
     fn = lib.cvmi_conv2d
 

@@ -58,6 +58,9 @@ class CircuitPipeline:
         swap_channels: segment_with_sam2 applies cv2.COLOR_BGR2RGB to whatever it is given (circuit_analyzer.py:343), and the
         pipeline hands it RGB (analysis_pipeline.py:199-203) -- i.e. the reference's segmenter sees the channels reversed.
         seg_batch: images per segmenter launch (BASELINE configs[2] runs SAM 2.1-L at 16).
+        max_prompts (prompts="boxes"): boxes per image handed to the segmenter; longer lists are cut, shorter ones filled with their first box (the
+        tensor form `boxes[B,P,4]`).  None: every image's whole stage-2 box list as its own prompt list (`infer_masks` with lists: the decoder runs
+        on the boxes there are, an image without boxes returns no mask).
         nodes=True (learned prompts only): each result also carries get_node_connections' front end on its mask and boxes
         (circuit_analyzer.py:1325-1365, wires.node_contours): "emptied_mask", "resized_bboxes", "enhanced", "contours".
         nodes="connections" (learned prompts only): get_node_connections through to its node list (:1325-1583, wires.node_connections):
@@ -167,6 +170,8 @@ class CircuitPipeline:
                 out.append({"image": im, "bboxes": boxes_adj[b], "mask": u8[0, 0], "extent": ext[0], "iou": iou[b]})
             self._tick("segment.postprocess (resize + threshold + u8 + extent + D2H of extents)", t)
             return out
+        if self.max_prompts is None:
+            return self._segment_chunk_lists(crops, boxes_adj, x, t)
         P = self.max_prompts
         bx = torch.zeros(len(crops), P, 4)
         counts = []
@@ -190,6 +195,35 @@ class CircuitPipeline:
             else:
                 masks, ext = torch.zeros(0, *im.shape[:2], dtype=torch.uint8, device=lo.device), []
             out.append({"image": im, "bboxes": boxes_adj[b][:P], "masks": masks, "extents": ext, "iou": iou[b, :k]})
+        self._tick("segment.postprocess (resize + threshold + u8 + extent + D2H of extents)", t)
+        return out
+
+    def _segment_chunk_lists(self, crops, boxes_adj, x, t):
+        """max_prompts=None: every image's whole stage-2 box list goes to `infer_masks` as its own prompt list -- nothing cut, nothing repeated,
+        no whole-image box for an image without boxes -- and the packed low-res planes are post-processed in one launch, each to the size of
+        its image (`postprocess_to_masks_sized`)."""
+        lists = []
+        for im, bb in zip(crops, boxes_adj):
+            t_ = torch.tensor([[d["xmin"], d["ymin"], d["xmax"], d["ymax"]] for d in bb], dtype=torch.float32).reshape(-1, 4)
+            lists.append(self.tr.transform_boxes(t_, normalize=True, orig_hw=im.shape[:2]).reshape(-1, 4))
+        counts = [int(l.shape[0]) for l in lists]
+        if sum(counts) == 0:                                             # no box in the whole chunk: nothing to launch
+            dev = x.device
+            return [{"image": im, "bboxes": bb, "masks": torch.zeros(0, *im.shape[:2], dtype=torch.uint8, device=dev), "extents": [],
+                     "iou": torch.zeros(0, device=dev)} for im, bb in zip(crops, boxes_adj)]
+        _, lo, iou = self.seg.infer_masks(x, lists, return_high_res=False)
+        t = self._tick("segment.infer_masks (SAM 2.1 forward)", t)
+        base = getattr(lo[0], "_base", None)                             # the lists are `torch.split` views of one packed [N, h, w] block
+        packed = base if base is not None and tuple(base.shape) == (sum(counts),) + tuple(lo[0].shape[1:]) else torch.cat(lo)
+        sizes = [im.shape[:2] for im, k in zip(crops, counts) for _ in range(k)]
+        planes, ext = self.tr.postprocess_to_masks_sized(packed.unsqueeze(1), sizes)
+        boxes = self.tr.extents_to_boxes(ext)
+        out, n0 = [], 0
+        for b, (im, k) in enumerate(zip(crops, counts)):
+            H, W = im.shape[:2]
+            masks = planes[n0].as_strided((k, H, W), (H * W, W, 1)) if k else torch.zeros(0, H, W, dtype=torch.uint8, device=packed.device)
+            out.append({"image": im, "bboxes": boxes_adj[b], "masks": masks, "extents": boxes[n0:n0 + k], "iou": iou[b]})
+            n0 += k
         self._tick("segment.postprocess (resize + threshold + u8 + extent + D2H of extents)", t)
         return out
 

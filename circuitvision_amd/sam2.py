@@ -461,10 +461,15 @@ class Sam2Plan:
     mask_prompt (prompts > 0): every pair also carries a mask prompt, low-res logits the caller writes to `mask_in` [B*P, R/4, R/4]
     before each run (upstream `mask_input`); the image stream then differs per pair from the start, so layer 0 runs unshared.
     multimask (prompts > 0): upstream multimask_output=True -- mask tokens 1..3 and their IoU heads in token order, no stability
-    fallback; outputs are [B*P, 3, ...]."""
+    fallback; outputs are [B*P, 3, ...].
+    pairs = cap > 0 (in the place of prompts): the decoder runs on `cap` (image, prompt) pairs whose images the caller names in `pair_image`
+    (device int32 [cap], written beside `coords` / `labels` / `mask_in` before each run; every value must lie in [0, B) -- the kernels read
+    the table as it is): any number of prompts per image, in any order.  Everything that finds a pair's image as b / P in a prompts = P plan
+    reads the table instead (the gather in the place of the repeat pass, layer 0's shared tensors, the up1 / up2 residuals); the table is
+    data, so one captured plan serves every distribution of `cap` pairs over the B images."""
 
     def __init__(self, wt, B, stream, dynamic_multimask_via_stability=True, prompts=0, points=3, high_res=True, attn="16", mask_prompt=False,
-                 multimask=False):
+                 multimask=False, pairs=0):
         """attn = "fp8" (16-bit plans only; BASELINE configs[4]): the AV contraction of Hiera's 256-key windows and global blocks runs on the
         block-scaled fp8 MFMA (cvmi_attn_desc.av_fp8); "16": operands in the plan's 16-bit type (default)."""
         self.wt, self.B, self.dt, self.dev = wt, B, wt.dtype, wt.device
@@ -473,9 +478,14 @@ class Sam2Plan:
         self.av_fp8 = 1 if attn == "fp8" else 0
         self.sw = sam_switches()._replace(**{f: getattr(wt.sw, f) for f in WEIGHT_SWITCHES})      # plan-level switches as set now, weight-level as packed
         self.P, self.K, self.want_high_res = prompts, points, high_res
-        if prompts and not wt.prompt_ok:
+        if pairs and prompts:
+            raise ValueError("pairs (a pair-to-image table) and prompts (P per image) are alternatives")
+        if pairs < 0 or pairs > 65535:
+            raise ValueError("pairs must be in 1 .. 65535")
+        self.pairs = int(pairs)
+        if (prompts or pairs) and not wt.prompt_ok:
             raise _lib.CvmiError("this checkpoint carries no sam_prompt_encoder tensors: box / point prompts are unavailable")
-        if (mask_prompt or multimask) and not prompts:
+        if (mask_prompt or multimask) and not (prompts or pairs):
             raise ValueError("mask_prompt / multimask need prompts > 0 (the learned-prompt wrapper always runs single-mask without a mask input)")
         if mask_prompt and not wt.mask_prompt_ok:
             raise _lib.CvmiError("this checkpoint carries no sam_prompt_encoder.mask_downscaling tensors: mask prompts are unavailable")
@@ -635,11 +645,14 @@ class Sam2Plan:
                 self.gemm(key, key, cast(src, tag).view(), dstb.view(), kind="neck")
         s2, s3 = cast(st[2], "s2"), cast(st[3], "s3")
         lib = _lib.load()
-        NP = self.P                                   # prompts per image (0: learned prompts)
-        NB = B * NP if NP else B                      # decoder batch: (image, prompt) pairs, image-major
+        NP = self.P                                   # prompts per image (0: learned prompts, or pairs)
+        NB = self.pairs or (B * NP if NP else B)      # decoder batch: (image, prompt) pairs -- image-major, or as the pair table names them
+        prompted = bool(NP or self.pairs)
+        # pairs: the image of pair n is pair_image[n]; the launches that derive it as n / NP in a prompts = P plan take the table instead
+        self.pair_image = pim = torch.zeros(NB, dtype=torch.int32, device=self.dev) if self.pairs else None
         P = fs * fs
         bufd = lambda *a, **k: self.buf(*a, batch=NB, **k)
-        if not NP:
+        if not prompted:
             # src = FPN level 2 + learned dense prompt   (f32: it is the decoder's residual stream "keys")
             keys = self.buf(fs, fs, 256, F32)
             dense = wt.const["dense"]
@@ -664,11 +677,19 @@ class Sam2Plan:
             if self.mask_prompt:
                 self.mask_in = torch.zeros(NB, f0, f0, dtype=torch.float32, device=self.dev)
                 kn0 = bufd(fs, fs, 256, tag="kn") if is16(dt) else None
-                op_call(self.plan, "mask_prompt_embed", "decoder", lib.cvmi_mask_prompt_embed,
-                        (self.mask_in.data_ptr(), emb.t.data_ptr(), wt.const["mask_down"].data_ptr(), keys.t.data_ptr(),
-                         kn0.t.data_ptr() if kn0 is not None else None, dt if kn0 is not None else F16, B, NP, fs),
-                        keep=(emb, keys, kn0), bytes_=NB * f0 * f0 * 4 + (B + NB) * P * 256 * 4 + (NB * P * 256 * 2 if kn0 is not None else 0),
+                head = (self.mask_in.data_ptr(), emb.t.data_ptr(), wt.const["mask_down"].data_ptr(), keys.t.data_ptr(),
+                        kn0.t.data_ptr() if kn0 is not None else None, dt if kn0 is not None else F16)
+                fn, tail = (lib.cvmi_mask_prompt_embed_pairs, (NB, pim.data_ptr(), fs)) if self.pairs else (lib.cvmi_mask_prompt_embed, (B, NP, fs))
+                op_call(self.plan, "mask_prompt_embed", "decoder", fn, head + tail,
+                        keep=(emb, keys, kn0, pim), bytes_=NB * f0 * f0 * 4 + (B + NB) * P * 256 * 4 + (NB * P * 256 * 2 if kn0 is not None else 0),
                         flops=2 * NB * P * (16 * 4 + 16 * 16 + 256 * 16))
+            elif self.pairs and not self.share_l0:
+                # the gather stands where the repeat pass stands; in a 16-bit plan it writes layer 0's operand copy too (no l0.t2i.castk)
+                kn0 = bufd(fs, fs, 256, tag="kn") if is16(dt) else None
+                op_call(self.plan, "gather_embed", "decoder", lib.cvmi_gather_images,
+                        (emb.t.data_ptr(), keys.t.data_ptr(), kn0.t.data_ptr() if kn0 is not None else None, dt if kn0 is not None else F16,
+                         P * 256 * 4, pim.data_ptr(), NB),
+                        keep=(emb, keys, kn0, pim), bytes_=2 * NB * P * 256 * 4 + (NB * P * 256 * 2 if kn0 is not None else 0))
             elif not self.share_l0:
                 op_call(self.plan, "repeat_embed", "decoder", lib.cvmi_repeat_images, (emb.t.data_ptr(), keys.t.data_ptr(), P * 256 * 4, B, NP),
                         keep=(emb, keys), bytes_=(B + NB) * P * 256 * 4)
@@ -693,13 +714,14 @@ class Sam2Plan:
             gam, bet = wt.ln[key]
             op_layernorm(self.plan, label, src.view(), gam, bet, dst.view(), 1e-5, dst2=dst2.view() if dst2 is not None else None)
 
-        def attention(label, qb, q_off, kb, k_off, vb, v_off, ob, Nq, Nk, hd, q_bdiv=0, kv_bdiv=0):
+        def attention(label, qb, q_off, kb, k_off, vb, v_off, ob, Nq, Nk, hd, q_bdiv=0, kv_bdiv=0, q_bmap=None, kv_bmap=None):
             es = ESIZE[dt]
             desc = make_attn_desc(q=qb.t.data_ptr() + q_off * es, k=kb.t.data_ptr() + k_off * es, v=vb.t.data_ptr() + v_off * es, o=ob.t.data_ptr(),
                                   q_sb=Nq * qb.C, q_sh=hd, q_st=qb.C, k_sb=Nk * kb.C, k_sh=hd, k_st=kb.C, v_sb=Nk * vb.C, v_sh=hd, v_st=vb.C,
                                   o_sb=Nq * ob.C, o_sh=hd, o_st=ob.C, B=NB, heads=8, Nq=Nq, Nk=Nk, dqk=hd, dv=hd, scale=hd ** -0.5, dtype=dt,
-                                  win=0, grid_h=0, grid_w=0, q_pool=0, q_bdiv=q_bdiv, kv_bdiv=kv_bdiv)
-            op_attention(self.plan, label, desc, (qb, kb, vb, ob), flops=4 * NB * 8 * Nq * Nk * hd, kind="decoder")
+                                  win=0, grid_h=0, grid_w=0, q_pool=0, q_bdiv=q_bdiv, kv_bdiv=kv_bdiv,
+                                  q_bmap=q_bmap.data_ptr() if q_bmap is not None else None, kv_bmap=kv_bmap.data_ptr() if kv_bmap is not None else None)
+            op_attention(self.plan, label, desc, (qb, kb, vb, ob, q_bmap, kv_bmap), flops=4 * NB * 8 * Nq * Nk * hd, kind="decoder")
 
         dual = is16(dt)                          # norm4 writes the 16-bit operand copy of the image stream itself (no cast pass)
         qn = bufd(1, T, 256, tag="qn")           # compute-dtype copies of the f32 streams
@@ -723,20 +745,20 @@ class Sam2Plan:
             ln(f"{p}.norm1", f"{p}.norm1", q, q)
             # --- tokens attend to the image
             op_cast(self.plan, f"{p}.t2i.castq", q.view(), qn.view())
-            share = l == 0 and NP and getattr(self, "share_l0", False)      # layer 0 of the box path: image-side tensors per IMAGE
+            share = l == 0 and prompted and getattr(self, "share_l0", False)      # layer 0 of the box path: image-side tensors per IMAGE
             if share:
                 kn_l = self.buf(fs, fs, 256, tag="kn_shared")
                 op_cast(self.plan, f"{p}.t2i.castk", emb.view(), kn_l.view())
             else:
                 kn_l = kn
-                if not dual or (l == 0 and not self.mask_prompt):        # (16-bit mask prompts: mask_prompt_embed has written kn)
+                if not dual or (l == 0 and not self.mask_prompt and not self.pairs):      # (16-bit mask prompts / pairs: mask_prompt_embed / gather_embed has written kn)
                     op_cast(self.plan, f"{p}.t2i.castk", keys.view(), kn.view())
             tq = bufd(1, T, 128, tag="t2i_q")
             G(f"{p}.t2i.q", f"{p}.t2i.q", qn.view(), tq.view(), **tpe(f"{p}.t2i.q_pe", 128))
             kv = self.buf(fs, fs, 256, tag="t2i_kv_shared") if share else bufd(fs, fs, 256, tag="t2i_kv")
             G(f"{p}.t2i.kv", f"{p}.t2i.kv", kn_l.view(), kv.view(), res=_ConstView(wt.const[f"{p}.t2i.kv_pe"], 256), res_mod=P)
             ao2 = bufd(1, T, 128, tag="t2i_ao")
-            attention(f"{p}.t2i.attn", tq, 0, kv, 0, kv, 128, ao2, T, P, 16, kv_bdiv=NP if share else 0)
+            attention(f"{p}.t2i.attn", tq, 0, kv, 0, kv, 128, ao2, T, P, 16, kv_bdiv=NP if share else 0, kv_bmap=pim if share else None)
             G(f"{p}.t2i.out", f"{p}.t2i.out", ao2.view(), q.view(), res=q.view())
             ln(f"{p}.norm2", f"{p}.norm2", q, q)
             # --- MLP on the tokens
@@ -752,9 +774,9 @@ class Sam2Plan:
             ikv = bufd(1, T, 256, tag="i2t_kv")
             G(f"{p}.i2t.kv", f"{p}.i2t.kv", qn.view(), ikv.view(), **tpe(f"{p}.i2t.kv_pe", 256))
             ao3 = bufd(fs, fs, 128, tag="i2t_ao")
-            attention(f"{p}.i2t.attn", iq, 0, ikv, 0, ikv, 128, ao3, P, T, 16, q_bdiv=NP if share else 0)
-            if share:      # first write of the per-prompt image stream: keys[b] = emb[b / P] + out-projection
-                G(f"{p}.i2t.out", f"{p}.i2t.out", ao3.view(), keys.view(), res=emb.view(), res_mod=P, res_rep=NP)
+            attention(f"{p}.i2t.attn", iq, 0, ikv, 0, ikv, 128, ao3, P, T, 16, q_bdiv=NP if share else 0, q_bmap=pim if share else None)
+            if share:      # first write of the per-prompt image stream: keys[b] = emb[b / P] (pairs: emb[pair_image[b]]) + out-projection
+                G(f"{p}.i2t.out", f"{p}.i2t.out", ao3.view(), keys.view(), res=emb.view(), res_mod=P, res_rep=NP, res_map=pim)
             else:
                 G(f"{p}.i2t.out", f"{p}.i2t.out", ao3.view(), keys.view(), res=keys.view())
             ln(f"{p}.norm4", f"{p}.norm4", keys, keys, dst2=kn if dual else None)      # + the fp16 copy the next k / v projection reads
@@ -773,11 +795,11 @@ class Sam2Plan:
         self.tokens_out, self.keys_out = q, keys
         # --- upscaling: act1(ln1(dc1(src) + s1)) ; act2(dc2(.) + s0)
         u1 = bufd(f1, f1, 64)
-        G("up1", "up1", kn.view(), u1.view(), res=feat_s1.view(), shuffle_cout=64, res_rep=NP)
+        G("up1", "up1", kn.view(), u1.view(), res=feat_s1.view(), shuffle_cout=64, res_rep=NP, res_map=pim)
         gam, bet = wt.ln["up_ln"]
         op_layernorm(self.plan, "up_ln", u1.view(), gam, bet, u1.view(), 1e-6, act=ACT_GELU)
         u2 = bufd(f0, f0, 32)
-        G("up2", "up2", u1.view(), u2.view(), res=feat_s0.view(), shuffle_cout=32, act=ACT_GELU, act_after_res=True, res_rep=NP)
+        G("up2", "up2", u1.view(), u2.view(), res=feat_s0.view(), shuffle_cout=32, act=ACT_GELU, act_after_res=True, res_rep=NP, res_map=pim)
         self.up = u2
         # --- hypernetwork MLPs on the 4 mask tokens, IoU head on the iou token (rows strided by T*256)
         op_cast(self.plan, "heads.cast", q.view(), qn.view())
@@ -817,7 +839,7 @@ class Sam2Plan:
             self.high_res = None
             return
         self.high_res = torch.empty(NB, NM, R, R, dtype=torch.float32, device=self.dev)
-        if wt.refine_params is not None and not NP:            # the refinement head belongs to the learned-prompt wrapper (sam2_infer.py:269-270)
+        if wt.refine_params is not None and not prompted:            # the refinement head belongs to the learned-prompt wrapper (sam2_infer.py:269-270)
             import ctypes as C
             ks = (C.c_int * len(wt.kernels))(*wt.kernels)
             taps = sum(k * k for k in wt.kernels)

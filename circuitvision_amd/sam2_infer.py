@@ -30,6 +30,81 @@ def _hiera_from_yaml(path):
     return hiera, int(m.get("image_size", 1024))
 
 
+def _is_list(a):
+    return isinstance(a, (list, tuple))
+
+
+def pack_prompt_lists(B, R, boxes=None, points=None, point_labels=None, mask_input=None, pair_bucket=32):
+    """The host half of `infer_masks` with one prompt list per image (no GPU needed): boxes = B tensors [P_b, 4], points / point_labels = B
+    tensors [P_b, K, 2] / [P_b, K] (one K for all), mask_input = B float tensors [P_b, R/4, R/4]; P_b may be 0.  -> a dict of host tensors
+    for a `Sam2Plan(pairs=cap)`:
+      sizes [P_0 .. P_{B-1}], N = their sum, cap = N rounded up to a multiple of pair_bucket, K = tokens per prompt (box corners, clicks, the
+      closing padding point), coords f32 [cap, K, 2], labels i32 [cap, K], pair_image i32 [cap] (pair n belongs to image pair_image[n];
+      pairs are image-major), mask f32 [cap, R/4, R/4] or None.
+    Slots N .. cap - 1 are padding: image 0, the box [0, 0, R, R] (without boxes: not-a-point tokens only) and a zero mask.
+    Raises ValueError for a list of the wrong length, entries that are not tensors or have the wrong shape, counts that differ between the
+    arguments, and N == 0."""
+    f0 = R // 4
+    if pair_bucket < 1:
+        raise ValueError("pair_bucket must be >= 1")
+    if boxes is None and points is None:
+        raise ValueError("prompt lists need boxes and / or points")
+    if points is not None and point_labels is None:
+        raise ValueError("points need point_labels")
+    given = dict(boxes=boxes, points=points, point_labels=point_labels if points is not None else None, mask_input=mask_input)
+    for name, a in given.items():
+        if a is None:
+            continue
+        if not _is_list(a):
+            raise ValueError(f"{name}: with one prompt list per image every prompt argument is a list of B = {B} tensors")
+        if len(a) != B:
+            raise ValueError(f"{name}: {len(a)} entries for B = {B} images")
+        if not all(torch.is_tensor(t) for t in a):
+            raise ValueError(f"{name}: every entry must be a tensor (an image without prompts: an empty one, e.g. torch.zeros(0, 4))")
+    sizes = [int(t.shape[0]) if t.dim() > 0 else -1 for t in (boxes if boxes is not None else points)]
+    nk = 0
+    if boxes is not None:
+        for b, t in enumerate(boxes):
+            if t.dim() != 2 or t.shape[1] != 4:
+                raise ValueError(f"boxes[{b}] must be [P_b, 4] xyxy, got {tuple(t.shape)}")
+    if points is not None:
+        ks = {int(t.shape[1]) for t in points if t.dim() == 3}
+        if len(ks) != 1 or 0 in ks:
+            raise ValueError("points: one click count K > 0 for every prompt of every image ([P_b, K, 2]; label -1 pads a shorter list)")
+        nk = ks.pop()
+        for b, (t, l) in enumerate(zip(points, point_labels)):
+            if t.dim() != 3 or t.shape[2] != 2 or tuple(l.shape) != tuple(t.shape[:2]):
+                raise ValueError(f"points[{b}] must be [P_b, K, 2] with point_labels[{b}] [P_b, K], got {tuple(t.shape)} / {tuple(l.shape)}")
+            if t.shape[0] != sizes[b]:
+                raise ValueError(f"image {b}: {sizes[b]} boxes but {t.shape[0]} point prompts")
+            if l.numel() and (int(l.min()) < -1 or int(l.max()) > 1):
+                raise ValueError("point_labels must be -1 (padding token), 0 (background) or 1 (foreground)")
+    if mask_input is not None:
+        for b, t in enumerate(mask_input):
+            if not t.is_floating_point() or tuple(t.shape) != (sizes[b], f0, f0):
+                raise ValueError(f"mask_input[{b}] must be float [P_b={sizes[b]}, {f0}, {f0}] low-res logits, got {t.dtype} {tuple(t.shape)}")
+    N = sum(sizes)
+    if N == 0:
+        raise ValueError("no prompt in any image (N = 0): nothing to segment")
+    cap = -(-N // pair_bucket) * pair_bucket
+    nb = 2 if boxes is not None else 0
+    K = nb + nk + 1                                            # + the closing padding point
+    coords = torch.zeros(cap, K, 2, dtype=torch.float32)
+    labels = torch.full((cap, K), -1, dtype=torch.int32)
+    pair_image = torch.zeros(cap, dtype=torch.int32)
+    pair_image[:N] = torch.repeat_interleave(torch.arange(B, dtype=torch.int32), torch.tensor(sizes))
+    if boxes is not None:
+        coords[:N, :2] = torch.cat([t.detach().float().cpu().reshape(-1, 2, 2) for t in boxes])
+        coords[N:, 1] = float(R)                               # padding: the whole-image box [0, 0, R, R]
+        labels[:, 0], labels[:, 1] = 2, 3
+    if points is not None:
+        coords[:N, nb:nb + nk] = torch.cat([t.detach().float().cpu() for t in points])
+        labels[:N, nb:nb + nk] = torch.cat([l.detach().cpu().to(torch.int32) for l in point_labels])
+    if int(pair_image.min()) < 0 or int(pair_image.max()) >= B:            # the kernels read the table unchecked (include/cvmi355.h)
+        raise ValueError("pair_image outside [0, B)")
+    return dict(sizes=sizes, N=N, cap=cap, K=K, coords=coords, labels=labels, pair_image=pair_image, has_mask=mask_input is not None)
+
+
 class SAM2Model:
     """What `get_modified_sam2(...)` returns: `.load_state_dict`, `.eval`, `.sam2_model.image_size`,
     `__call__(x) -> (high_res, low_res, iou)` (sam2_infer.py:220-275), plus `infer_masks`."""
@@ -53,6 +128,7 @@ class SAM2Model:
         self._plans = {}                                                    # that two independent batches run side by side: CircuitPipeline)
         self._lock = threading.Lock()                                       # one analyzer is shared across sessions (app.py:134)
         self.training = False
+        self.pair_bucket = 32                                               # prompt lists: the pair count is rounded up to a multiple (bounds the plans / graphs)
 
     # -- nn.Module-like surface the reference touches
     def load_params(self, params):
@@ -86,13 +162,14 @@ class SAM2Model:
             raise RuntimeError("SAM2 weights not loaded (call load_state_dict first)")
         return self.weights
 
-    def plan(self, B, prompts=0, high_res=True, points=3, slot=0, mask_prompt=False, multimask=False):
+    def plan(self, B, prompts=0, high_res=True, points=3, slot=0, mask_prompt=False, multimask=False, pairs=0):
+        """pairs = cap: the plan of `cap` (image, prompt) pairs with a pair-to-image table (prompt lists); keyed on cap, not on the pair count."""
         wt = self._packed_weights()
-        key = (B, prompts, high_res, points if prompts else 0, slot, bool(mask_prompt), bool(multimask))
+        key = (B, prompts, high_res, points if (prompts or pairs) else 0, slot, bool(mask_prompt), bool(multimask), pairs)
         if key not in self._plans:
             with torch.cuda.device(self.dev):
                 self._plans[key] = Sam2Plan(wt, B, self.slot_stream(slot), self.dynamic, prompts=prompts, points=points, high_res=high_res, attn=self.attn,
-                                            mask_prompt=mask_prompt, multimask=multimask)
+                                            mask_prompt=mask_prompt, multimask=multimask, pairs=pairs)
         return self._plans[key]
 
     def _stage_images(self, p, images):
@@ -156,7 +233,14 @@ class SAM2Model:
         mask_input [B,P,R/4,R/4] (float, host or device; needs boxes and / or points): upstream's mask prompt -- low-res logits, e.g. the
         low_res of an earlier call, enter through `sam_prompt_encoder.mask_downscaling` as the dense prompt in the place of no_mask_embed.
         multimask_output=True (needs a prompt): the three multimask candidates in token order with their predicted IoUs, no stability
-        fallback -> (high_res [B,P,3,R,R] or None, low_res [B,P,3,R/4,R/4], iou [B,P,3])."""
+        fallback -> (high_res [B,P,3,R,R] or None, low_res [B,P,3,R/4,R/4], iou [B,P,3]).
+        Prompt lists: boxes a list of B tensors [P_b,4], points / point_labels lists of [P_b,K,2] / [P_b,K], mask_input a list of
+        [P_b,R/4,R/4] -- every image its own number of prompts, 0 included; all lists given agree on B and on every P_b.  The decoder runs on
+        the N = sum P_b pairs (rounded up to a multiple of `pair_bucket`), nothing is padded per image.  Lists in, lists out: high_res,
+        low_res and iou are each a list of B tensors ([P_b,R,R], [P_b,R/4,R/4], [P_b]; a candidate axis of 3 after P_b with
+        multimask_output=True), `torch.split` views of one packed [N,...] allocation."""
+        if _is_list(boxes) or _is_list(points) or _is_list(point_labels) or _is_list(mask_input):
+            return self._infer_masks_lists(images, boxes, return_high_res, points, point_labels, mask_input, multimask_output)
         if boxes is None and points is None:
             if mask_input is not None:
                 raise ValueError("mask_input needs boxes and / or points (a mask-only prompt is not built)")
@@ -212,6 +296,32 @@ class SAM2Model:
             outs = [(p.low_res.view(*shp, f0, f0), lo), (p.iou.view(*shp), iou)] + ([(p.high_res.view(*shp, R, R), hi)] if return_high_res else [])
             self._run(p, images, outs, before=prompts_in)
             return hi, lo, iou
+
+    def _infer_masks_lists(self, images, boxes, return_high_res, points, point_labels, mask_input, multimask_output):
+        """`infer_masks` with one prompt list per image: pack on the host (`pack_prompt_lists`), replay the `pairs=cap` plan, split."""
+        self._check_images(images)
+        B, R, f0 = images.shape[0], self.image_size, self.image_size // 4
+        pk = pack_prompt_lists(B, R, boxes, points, point_labels, mask_input, self.pair_bucket)
+        N, cap, sizes = pk["N"], pk["cap"], pk["sizes"]
+        NM = 3 if multimask_output else 1
+        with self._lock, torch.cuda.device(self.dev):
+            if pk["has_mask"] and not self._packed_weights().mask_prompt_ok:
+                raise RuntimeError("this checkpoint carries no sam_prompt_encoder.mask_downscaling tensors: mask_input is unavailable")
+            p = self.plan(B, high_res=return_high_res, points=pk["K"], mask_prompt=pk["has_mask"], multimask=bool(multimask_output), pairs=cap)
+
+            def prompts_in():                                          # on the model's stream, in front of the replay that reads them
+                p.coords.copy_(pk["coords"], non_blocking=False)
+                p.labels.copy_(pk["labels"], non_blocking=False)
+                p.pair_image.copy_(pk["pair_image"], non_blocking=False)
+                if pk["has_mask"]:
+                    p.mask_in[:N].copy_(torch.cat([t.detach().to(self.dev, torch.float32) for t in mask_input]), non_blocking=False)
+                    p.mask_in[N:].zero_()
+            shp = (N, NM) if multimask_output else (N,)
+            lo, iou = torch.empty(*shp, f0, f0, dtype=torch.float32, device=self.dev), torch.empty(*shp, dtype=torch.float32, device=self.dev)
+            hi = torch.empty(*shp, R, R, dtype=torch.float32, device=self.dev) if return_high_res else None
+            outs = [(p.low_res[:N].view(*shp, f0, f0), lo), (p.iou[:N].view(*shp), iou)] + ([(p.high_res[:N].view(*shp, R, R), hi)] if return_high_res else [])
+            self._run(p, images, outs, before=prompts_in)
+            return (list(torch.split(hi, sizes)) if hi is not None else None), list(torch.split(lo, sizes)), list(torch.split(iou, sizes))
 
 
 def get_modified_sam2(model_cfg_path, checkpoint_path, device="cuda", use_high_res_features=True, use_peft=True, lora_rank=12,

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define CVMI_VERSION 127
+#define CVMI_VERSION 128
 
 typedef void* cvmi_stream_t; /* hipStream_t */
 
@@ -100,6 +100,10 @@ typedef struct cvmi_conv_desc {
                                        written to each row's 96-column slices -- the statistics of the NEXT LayerNorm over these rows, free of
                                        the E[x^2] - E[x]^2 cancellation (cvmi_tok_linear_stats with ln_stats_in_parts = N / 96 combines the
                                        slices); NULL = off */
+  const int* res_map;               /* optional DEVICE table of B ints (128; needs a residual, res_rep <= 1, and shuffle_cout > 0 or res_mod == OH * OW): batch
+                                       entry e reads residual image res_map[e] -- res_rep's sharing with the image of every entry stated instead of
+                                       derived as e / res_rep ((image, prompt) pairs with a different number of prompts per image).  The CALLER
+                                       guarantees 0 <= res_map[e] < number of residual images: the kernels do not check it.  NULL = off */
 } cvmi_conv_desc;
 int cvmi_conv2d(const cvmi_conv_desc* d, cvmi_stream_t stream);
 
@@ -199,6 +203,12 @@ typedef struct cvmi_attn_desc {
   const float* proj_stats;   /* optional: (mean, rstd) per token as cvmi_tok_linear_stats / cvmi_hiera_mlp_stats write them; NULL = computed here */
   int proj_ld, proj_K;
   float proj_eps;
+  /* Batch sharing by table (128): DEVICE arrays of B ints; q rows of batch entry b are read from entry q_bmap[b], k / v rows from entry
+     kv_bmap[b] -- what q_bdiv / kv_bdiv derive as b / divisor, stated per entry.  Each excludes its divisor being > 1 and carries the
+     divisors' restrictions (16-bit dtype, no window, head dims <= 64, no proj_x).  The CALLER guarantees that every value indexes an
+     existing batch entry of the shared tensor: the kernels do not check it.  NULL = off */
+  const int* q_bmap;
+  const int* kv_bmap;
 } cvmi_attn_desc;
 int cvmi_attention(const cvmi_attn_desc* d, cvmi_stream_t stream);
 
@@ -399,6 +409,15 @@ int cvmi_prompt_tokens(const float* coords, const int* labels, const float* gaus
  * (upstream MaskDecoder repeat_image=True).  bytes_per_image must be a multiple of 16. */
 int cvmi_repeat_images(const void* src, void* dst, long long bytes_per_image, int B, int rep, cvmi_stream_t stream);
 
+/* dst[n] = src[pair_image[n]] for n < n_pairs: per-image tensors gathered to (image, prompt) pairs whose images a DEVICE table names -- cvmi_repeat_images
+ * for pairs with a different number of prompts per image, in any order.  bytes_per_image must be a multiple of 16, src / dst 16-byte aligned,
+ * n_pairs <= 65535.  dst_lp (optional, 8-byte aligned; src is then f32): the same values rounded once (nearest even) to lp_dtype = CVMI_F16 or
+ * CVMI_BF16, same shape -- in a 16-bit plan the first cvmi_cast of the gathered tensor; NULL: lp_dtype is ignored.
+ * The CALLER guarantees 0 <= pair_image[n] < number of images in src: the kernel reads the table as it is (the host side of
+ * circuitvision_amd checks every value before it uploads the table). */
+int cvmi_gather_images(const void* src, void* dst, void* dst_lp, int lp_dtype, long long bytes_per_image, const int* pair_image, int n_pairs,
+                       cvmi_stream_t stream);
+
 /* Mask decoder tail: masks[b,i,p] = sum_c hyper[b,i,c] * up[b,p,c] for the 4 mask tokens (c = 32),
  * plus the stability counters of token 0 (area over +delta / -delta) for
  * dynamic_multimask_via_stability.  hyper f32 [B,4,hyper_ld], up dtype [B,P,up_ld], masks f32 [B,4,P],
@@ -433,6 +452,12 @@ int cvmi_multimask_out(const float* masks, const float* iou, int iou_ld, float* 
 #define CVMI_MASK_PROMPT_PARAMS 4684
 int cvmi_mask_prompt_embed(const float* mask, const float* emb, const float* params, float* keys, void* keys_lp, int lp_dtype,
                            int B, int rep, int fs, cvmi_stream_t stream);
+
+/* cvmi_mask_prompt_embed for n_pairs pairs whose images a DEVICE table names (same kernel, the image index read instead of derived):
+ *   keys[i] = emb[pair_image[i]] + mask_downscaling(mask[i]) - no_mask_embed,   mask f32 [n_pairs, 4*fs, 4*fs], keys f32 [n_pairs, fs*fs, 256].
+ * The CALLER guarantees 0 <= pair_image[i] < number of images in emb.  Everything else as above. */
+int cvmi_mask_prompt_embed_pairs(const float* mask, const float* emb, const float* params, float* keys, void* keys_lp, int lp_dtype, int n_pairs,
+                                 const int* pair_image, int fs, cvmi_stream_t stream);
 
 /* F.interpolate(bilinear, align_corners=False) of f32 planes [N,h,w] -> [N,H,W] (sam2_infer.py:263-268,
  * postprocess_masks :127).  mask_u8 (optional): also writes (value > thresh) ? 255 : 0. */
