@@ -973,17 +973,20 @@ extern "C" int CVMI_ENTRY(cvmi_sam2_transform_rects)(const uint8_t* src, long lo
 #endif
   CVMI_CHECK(src && dst && rects && B >= 1 && H > 0 && W > 0 && R > 0 && src_image_stride >= 0, "sam2_transform_rects: bad arguments");
   CVMI_CHECK(dst_dtype == CVMI_T16 || dst_dtype == CVMI_F32, "sam2_transform_rects: bad dtype");
+  for (int b = 0; b < B; ++b) {                                     // every window before the first launch: a bad one leaves nothing half done
+    const int* r = rects + 4 * (size_t)b;
+    CVMI_CHECK(r[0] >= 0 && r[1] >= 0 && r[2] > 0 && r[3] > 0 && (long long)r[0] + r[2] <= W && (long long)r[1] + r[3] <= H,
+               "sam2_transform_rects: window %d = (x %d, y %d, w %d, h %d) leaves the %d x %d image", b, r[0], r[1], r[2], r[3], W, H);
+    const float sy = (float)r[3] / (float)R, sx = (float)r[2] / (float)R;
+    CVMI_CHECK(2.f * (sy > 1.f ? sy : 1.f) + 2.f <= AA_MAXTAPS && 2.f * (sx > 1.f ? sx : 1.f) + 2.f <= AA_MAXTAPS,
+               "sam2_transform_rects: down-scale factor of window %d too large", b);
+  }
   hipStream_t s = (hipStream_t)stream_;
   for (int b0 = 0; b0 < B; b0 += RECT_MAX) {
     const int nb = B - b0 < RECT_MAX ? B - b0 : RECT_MAX;
     RectTable t;
     for (int b = 0; b < nb; ++b) {
       const int* r = rects + 4 * (size_t)(b0 + b);
-      CVMI_CHECK(r[0] >= 0 && r[1] >= 0 && r[2] > 0 && r[3] > 0 && (long long)r[0] + r[2] <= W && (long long)r[1] + r[3] <= H,
-                 "sam2_transform_rects: window %d = (x %d, y %d, w %d, h %d) leaves the %d x %d image", b0 + b, r[0], r[1], r[2], r[3], W, H);
-      const float sy = (float)r[3] / (float)R, sx = (float)r[2] / (float)R;
-      CVMI_CHECK(2.f * (sy > 1.f ? sy : 1.f) + 2.f <= AA_MAXTAPS && 2.f * (sx > 1.f ? sx : 1.f) + 2.f <= AA_MAXTAPS,
-                 "sam2_transform_rects: down-scale factor of window %d too large", b0 + b);
       t.r[b] = make_int4(r[0], r[1], r[2], r[3]);
     }
     for (int b = nb; b < RECT_MAX; ++b) t.r[b] = make_int4(0, 0, 1, 1);
@@ -1072,6 +1075,10 @@ extern "C" int cvmi_mask_postprocess_rects_dev(const float* x, int N, int h, int
 extern "C" int cvmi_mask_postprocess_sizes(const float* x, int N, int h, int w, const int* sizes, float thresh, uint8_t* mask_u8, int* extent,
                                            cvmi_stream_t stream_) {
   CVMI_CHECK(x && mask_u8 && extent && sizes && N > 0 && h > 0 && w > 0, "mask_postprocess_sizes: bad arguments");
+  for (int n = 0; n < N; ++n) {                                     // every size before the first launch
+    const int H = sizes[2 * (size_t)n], W = sizes[2 * (size_t)n + 1];
+    CVMI_CHECK(H > 0 && W > 0 && (long long)H * W < (1ll << 31), "mask_postprocess_sizes: plane %d has size %d x %d", n, H, W);
+  }
   hipStream_t s = (hipStream_t)stream_;
   long long off = 0;
   for (int n0 = 0; n0 < N; n0 += RECT_MAX) {
@@ -1080,7 +1087,6 @@ extern "C" int cvmi_mask_postprocess_sizes(const float* x, int N, int h, int w, 
     long long maxhw = 1, rel = 0;
     for (int n = 0; n < nb; ++n) {
       const int H = sizes[2 * (size_t)(n0 + n)], W = sizes[2 * (size_t)(n0 + n) + 1];
-      CVMI_CHECK(H > 0 && W > 0 && (long long)H * W < (1ll << 31), "mask_postprocess_sizes: plane %d has size %d x %d", n0 + n, H, W);
       t.r[n] = make_int4(H, W, (int)(unsigned)(rel & 0xffffffffll), (int)(unsigned)(rel >> 32));
       rel += (long long)H * W;
       if ((long long)H * W > maxhw) maxhw = (long long)H * W;

@@ -31,6 +31,11 @@ NMS_ROWS / DECODE_ROWS: the detector's tail (nms.hip, vision_ops.hip cvmi_detect
 instance nms_launch must tag and the decisions nms_pick -- a mirror of nms_launch and of yolo_nms_kernel's data-dependent branches -- derives from it; one
 decode row = one launch per dtype with its stated seams.  Generators, references, mutants and the decode bound live in tests/detect_ref.py.
 
+RESAMPLE_ROWS: the resampling kernels of sam_ops.hip (the five forms of cvmi_sam2_transform*, the four forms of the bilinear mask return and
+cvmi_mask_extent).  One row = the sources, windows or sizes of one call and the entry forms, output types and swap_rb values it runs through; the
+constants the rows were built from (AA_MAXTAPS, RECT_MAX, the grid caps) mirror the source text.  Operands, references, mutants and bounds live in
+tests/resample_ref.py.
+
 BF16_OPS: every entry point that common.hpp builds twice (CVMI_ENTRY) -> (test module, test function) that checks its bf16 build per op.
 
 Plain data: importing this module needs neither a GPU nor the library."""
@@ -939,3 +944,136 @@ DETECT_MUTANT_ROWS = {
 }
 # mutants no row can see (none today): kept as a name so that a blind spot is recorded, never dropped
 DETECT_UNSEEN_MUTANTS = {}
+
+
+# ---- the resampling kernels: the five forms of cvmi_sam2_transform* and the bilinear mask return (sam_ops.hip) ------------------------------------
+# One transform row = a list of source images (H, W), a list of items (image, x0, y0, w, h) -- output b of the launch is that window of that
+# image -- and the entry forms, output types and swap_rb values it runs through.  One mask-return row = one source shape and what it returns to.
+# Operands, references, mutants and the bounds live in tests/resample_ref.py.  The constants below mirror sam_ops.hip
+# (tests/test_op_coverage_cpu.py holds them to the source text).
+AA_MAXTAPS = 24                                    # taps per axis aa_axis keeps; the host guards refuse 2 * max(scale, 1) + 2 > AA_MAXTAPS
+RECT_MAX = 64                                      # windows / rows / sizes per launch of the table-by-value entry points
+AA_CAP_SCALE = (AA_MAXTAPS - 2) / 2                # 11: the largest legal down-scale
+RESAMPLE_GRID_CAP = {"transform": 4096 * 256, "bilinear": 1024 * 256, "mask_extent": 32 * 256}      # work items of one grid pass
+TRANSFORM_FORMS = ("single", "batch", "rects", "rects_dev", "srcs")
+TRANSFORM_ENTRY = {"single": "cvmi_sam2_transform", "batch": "cvmi_sam2_transform_batch", "rects": "cvmi_sam2_transform_rects",
+                   "rects_dev": "cvmi_sam2_transform_rects_dev", "srcs": "cvmi_sam2_transform_srcs"}
+MASK_FORMS = ("bilinear_f32", "mask_postprocess", "mask_postprocess_sizes", "mask_postprocess_rects_dev", "mask_extent")
+MASK_ENTRY = {f: "cvmi_" + f for f in MASK_FORMS}
+MASK_THRESHOLDS = (0.0, 0.3, -1.5)
+ALL_FORMS4 = ("batch", "rects", "rects_dev", "srcs")
+WIN_FORMS = ("rects", "rects_dev", "srcs")
+
+
+def _tf(rid, images, items=None, forms=ALL_FORMS4, dtypes=ALL3, swaps=(0, 1), R=16, stride0=False, fill="noise", refuse=None, tags=(), note=""):
+    """items None: the whole of every image.  stride0: every item reads image 0 (`rects` / `rects_dev` with src_image_stride = 0).  fill "window":
+    mid-grey noise inside each image's window and 0 / 255 outside it.  refuse: {form: text of the error}; the other forms of the row run."""
+    images = [tuple(i) for i in images]
+    if items is None:
+        items = [(i, 0, 0, W, H) for i, (H, W) in enumerate(images)]
+    return dict(op="transform", id="tf_" + rid, R=R, images=images, items=[tuple(i) for i in items], forms=tuple(forms), dtypes=tuple(dtypes), swaps=tuple(swaps),
+                stride0=stride0, fill=fill, refuse=dict(refuse or {}), tags=tuple(tags), note=note)
+
+
+def _mk(rid, hw, HW, N=2, forms=MASK_FORMS[:4], kind="blob", seed=0):
+    return dict(op="mask", id="mask_" + rid, N=N, h=hw[0], w=hw[1], H=HW[0], W=HW[1], thresholds=MASK_THRESHOLDS, forms=tuple(forms), kind=kind, seed=seed)
+
+
+TF_WIN_IMAGE = (40, 56)                            # H, W of the windowed rows' images
+TF_WINDOWS = ((0, 0, 56, 40), (7, 5, 33, 21), (13, 17, 1, 1), (3, 9, 37, 1), (11, 2, 1, 29), (32, 20, 24, 20))   # whole, interior, 1 x 1, two strips, bottom-right
+TF_CLIP_WINDOWS = ((-5, 3, 20, 10), (4, -7, 12, 20), (60, 5, 10, 10), (10, 10, 0, -3), (40, 8, 30, 12), (9, 31, 14, 25))   # x0 < 0, y0 < 0, x0 >= W, w <= 0, x0 + w > W, y0 + h > H
+
+
+def _w65(b):
+    x0, y0 = b % 5, b % 3
+    return (b, x0, y0, 40 - x0 - b % 7, 24 - y0 - b % 4)
+
+
+def _resample_rows():
+    rows = [
+        _tf("identity_16x16", [(16, 16)], forms=TRANSFORM_FORMS),
+        _tf("up_1x1", [(1, 1)], forms=TRANSFORM_FORMS),
+        _tf("up_2x3", [(2, 3)]),
+        _tf("up_down_1x40", [(1, 40)], note="one axis up, one down"),
+        _tf("down_24x40", [(24, 40)], forms=TRANSFORM_FORMS),
+        _tf("down_37x53", [(37, 53)]),
+        # ---- the cap: 2 * scale + 2 == AA_MAXTAPS at 176 source pixels
+        _tf("cap_176x176", [(176, 176)], forms=TRANSFORM_FORMS, tags=("cap", "deep")),
+        _tf("deep_175x131", [(175, 131)], swaps=(0,), tags=("deep",)),
+        _tf("cap_176x5", [(176, 5)], swaps=(1,), tags=("cap", "deep"), note="the guard is per axis: 11 down, 3.2 up"),
+        _tf("cap_window_176_in_200x300", [(200, 300)], [(0, 61, 13, 176, 176)], forms=("rects", "srcs"), fill="window", tags=("cap", "deep", "window"),
+            note="rects_dev refuses this image: its guard is on the whole image"),
+        # ---- refused: the output keeps its sentinel
+        _tf("refuse_177x16", [(177, 16)], forms=TRANSFORM_FORMS, dtypes=("f32", "bf16"), swaps=(0,), tags=("refused",),
+            refuse={"single": "sam2_transform: down-scale factor too large", "batch": "sam2_transform: down-scale factor too large",
+                    "rects": "sam2_transform_rects: down-scale factor of window 0 too large",
+                    "rects_dev": "sam2_transform_rects_dev: down-scale factor of the 16 x 177 image too large",
+                    "srcs": "sam2_transform_srcs: down-scale factor of window 0 too large"}),
+        _tf("refuse_16x177", [(16, 177)], forms=TRANSFORM_FORMS, dtypes=("f32", "f16"), swaps=(0,), tags=("refused",),
+            refuse={"single": "sam2_transform: down-scale factor too large", "batch": "sam2_transform: down-scale factor too large",
+                    "rects": "sam2_transform_rects: down-scale factor of window 0 too large",
+                    "rects_dev": "sam2_transform_rects_dev: down-scale factor of the 177 x 16 image too large",
+                    "srcs": "sam2_transform_srcs: down-scale factor of window 0 too large"}),
+        _tf("refuse_window_177_high", [(180, 24)], [(0, 2, 1, 16, 177)], forms=("rects", "srcs"), dtypes=("f32", "f16"), swaps=(0,), tags=("refused",),
+            refuse={"rects": "sam2_transform_rects: down-scale factor of window 0 too large", "srcs": "sam2_transform_srcs: down-scale factor of window 0 too large"}),
+        _tf("small_window_in_177_high", [(177, 24)], [(0, 3, 4, 8, 8)], forms=WIN_FORMS, dtypes=("f32", "bf16"), swaps=(0,), fill="window", tags=("refused", "window"),
+            refuse={"rects_dev": "sam2_transform_rects_dev: down-scale factor of the 24 x 177 image too large"},
+            note="the documented whole-image guard of rects_dev; rects and srcs judge the window and run"),
+        # ---- the second grid pass: R * R > 4096 * 256
+        _tf("second_pass_8x8", [(8, 8)], R=1025, dtypes=("f32", "bf16"), swaps=(0,), tags=("second_pass",)),
+        _tf("second_pass_40x24", [(40, 24)], R=1025, forms=("batch", "rects_dev"), dtypes=("f32", "f16"), swaps=(1,), tags=("second_pass",)),
+        _tf("batch3", [(24, 40)] * 3),
+        # ---- windows
+        _tf("windows", [TF_WIN_IMAGE] * len(TF_WINDOWS), [(i,) + w for i, w in enumerate(TF_WINDOWS)], forms=WIN_FORMS, fill="window", tags=("window",)),
+        _tf("windows_one_image", [TF_WIN_IMAGE], [(0,) + w for w in TF_WINDOWS], forms=WIN_FORMS, stride0=True, tags=("window",)),
+        _tf("windows_65", [(24, 40)] * 65, [_w65(b) for b in range(65)], forms=("rects", "srcs"), swaps=(0,), fill="window", tags=("window", "second_table")),
+        _tf("srcs_three_sizes", [(24, 40), (37, 53), (9, 11)], [(0, 3, 2, 30, 20), (1, 0, 0, 53, 37), (2, 4, 1, 5, 7), (1, 20, 9, 33, 28)], forms=("srcs",),
+            fill="window", tags=("window",), note="item 3 reuses image 1: its outside pattern is image 1's window"),
+        _tf("clip_rects_dev", [TF_WIN_IMAGE] * len(TF_CLIP_WINDOWS), [(i,) + w for i, w in enumerate(TF_CLIP_WINDOWS)], forms=("rects_dev",), tags=("clip",)),
+        _tf("refuse_window_64_of_65", [(24, 40)] * 65, [_w65(b) if b < 64 else (64, 30, 2, 11, 10) for b in range(65)], forms=("rects", "srcs"), dtypes=("f32", "f16"),
+            swaps=(0,), tags=("refused", "nothing_written"),
+            refuse={"rects": "sam2_transform_rects: window 64 = (x 30, y 2, w 11, h 10) leaves the 40 x 24 image",
+                    "srcs": "sam2_transform_srcs: window 64 = (x 30, y 2, w 11, h 10) leaves the 40 x 24 image"}),
+        # ---- the mask return
+        _mk("identity_9x7", (9, 7), (9, 7)),
+        _mk("down_64_to_5x3", (64, 64), (5, 3)),
+        _mk("down_64_to_1x1", (64, 64), (1, 1)),
+        _mk("up_1x1_to_7x5", (1, 1), (7, 5)),
+        _mk("up_2x2_to_7x5", (2, 2), (7, 5)),
+        _mk("out_1x33", (12, 10), (1, 33)),
+        _mk("out_33x1", (12, 10), (33, 1)),
+        _mk("empty_and_full", (6, 5), (13, 11), kind="flat"),
+        dict(op="mask_sizes", id="mask_sizes_65", N=65, h=12, w=10, sizes=[(1 + 3 * (n // 8), 1 + 4 * (n % 8)) for n in range(65)], thresholds=MASK_THRESHOLDS,
+             forms=("mask_postprocess_sizes",), refuse=None, kind="edge", seed=0),
+        dict(op="mask_sizes", id="mask_sizes_refuse_64_of_65", N=65, h=12, w=10, sizes=[(1 + 3 * (n // 8), 1 + 4 * (n % 8)) if n < 64 else (0, 5) for n in range(65)],
+             thresholds=(0.0,), forms=("mask_postprocess_sizes",), refuse="mask_postprocess_sizes: plane 64 has size 0 x 5", seed=0),
+        dict(op="mask_rects_dev", id="mask_rects_dev_clip", N=5, h=12, w=10, windows=[(3, 4, 40, 30), (0, 0, 1500, 3), (5, 5, 0, -2), (7, 7, 33, 30), (0, 0, 1000, 1)],
+             plane_stride=1000, thresholds=MASK_THRESHOLDS, forms=("mask_postprocess_rects_dev",), kind="edge", seed=0),
+        dict(op="mask_rects_dev", id="mask_rects_dev_513x512", N=1, h=64, w=64, windows=[(0, 0, 512, 513)], plane_stride=513 * 512, thresholds=MASK_THRESHOLDS,
+             forms=("mask_postprocess_rects_dev",), seed=3),              # seed: moved until no value lies within the bound of a threshold
+        dict(op="extent", id="extent_91x91", H=91, W=91, planes=[((0, 0), (90, 0), (0, 90), (90, 90)), ((58, 37),), ()], forms=("mask_extent",)),
+    ]
+    return rows
+
+
+RESAMPLE_ROWS = _resample_rows()
+
+
+def _tf_ids(pred):
+    return [r["id"] for r in RESAMPLE_ROWS if r["op"] == "transform" and not (r["refuse"] and not set(r["forms"]) - set(r["refuse"])) and pred(r)]
+
+
+# mutant of tests/resample_ref.py -> ids of the rows that must catch it (tests/test_resample_ref_cpu.py)
+RESAMPLE_MUTANT_ROWS = {
+    "aa_taps_capped_16": _tf_ids(lambda r: "deep" in r["tags"]),
+    "aa_no_antialias": _tf_ids(lambda r: any(max(w, h) > r["R"] for _, _, _, w, h in r["items"])),
+    "aa_center_no_half": _tf_ids(lambda r: any((w, h) != (1, 1) for _, _, _, w, h in r["items"])),
+    "aa_window_reads_image": ["tf_cap_window_176_in_200x300", "tf_small_window_in_177_high", "tf_windows", "tf_windows_one_image", "tf_windows_65", "tf_srcs_three_sizes"],
+    "aa_swap_moves_mean_std": _tf_ids(lambda r: 1 in r["swaps"]),
+    "aa_second_window_table_restarts": ["tf_windows_65"],
+    "bil_align_corners": ["mask_down_64_to_5x3", "mask_up_2x2_to_7x5", "mask_out_1x33", "mask_out_33x1", "mask_sizes_65", "mask_rects_dev_clip", "mask_rects_dev_513x512"],
+    "bil_no_low_clamp": ["mask_up_2x2_to_7x5", "mask_out_1x33", "mask_out_33x1", "mask_sizes_65", "mask_rects_dev_clip"],   # the mask-only forms see it where a blob sits on the border
+    "bil_extent_exclusive_max": ["mask_identity_9x7", "mask_down_64_to_5x3", "mask_up_2x2_to_7x5", "mask_empty_and_full", "mask_sizes_65", "mask_rects_dev_clip",
+                                 "mask_rects_dev_513x512", "extent_91x91"],
+    "clip_moves_window": ["tf_clip_rects_dev"],
+}

@@ -3,7 +3,8 @@ dispatcher can launch has a row in the dispatch matrix, and so has every kernel 
 (CONV_ROWS), every built instance of the three fused YOLO11 kernels (FUSED_ROWS), and every layernorm_kernel instance, SPPF kernel and
 refinement kernel of the helper dispatchers (LN_ROWS, HELPER_ROWS), every branch combination and edge of the detector's tail (NMS_ROWS,
 DECODE_ROWS), and every instance of the token-stationary kernels with the chunk counts,
-split counts, pool grids and statistics forms their rings and index arithmetic need (TOK_ROWS, MLP_ROWS).  Adding an entry point or a kernel
+split counts, pool grids and statistics forms their rings and index arithmetic need (TOK_ROWS, MLP_ROWS), and every entry point and output-type
+instance of the resampling kernels with the constants their rows were built from (RESAMPLE_ROWS).  Adding an entry point or a kernel
 without its per-op test fails here, on any checkout."""
 import ast
 import glob
@@ -16,6 +17,7 @@ from op_matrix import (ATTN_ROWS, BF16_OPS, C3K2_INSTANCES, CONV_ROWS, DECODE_NC
                        MLP_INSTANCES, MLP_ROWS, SHARE_ROWS, SPPF_LDS_PIXELS, TNAME, TOK_FORMAT, TOK_INSTANCES, TOK_KS, TOK_MUTANT_ROWS, TOK_NCH, TOK_NCH_FAMILIES,
                        TOK_PARTS, TOK_ROWS, TOK_SLOTS, TOK_SPLIT_TABLE, TOK_UNSEEN_MUTANTS, c3k2_max_wgs_per_cu, c3k2_tag, conv_expect, ln_pick, ln_reachable,
                        ln_tag, mlp_pick, tl16_splits, tok_dispatch, tok_nch_family, tok_pick)
+from op_matrix import AA_MAXTAPS, MASK_ENTRY, RECT_MAX, RESAMPLE_GRID_CAP, RESAMPLE_ROWS, TRANSFORM_ENTRY
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(os.path.dirname(HERE), "circuitvision_amd", "csrc")
@@ -742,3 +744,136 @@ def test_a_removed_detect_row_or_a_moved_threshold_is_caught():
         probe = dict(src)
         probe[name] = src[name].replace(text, "")
         assert detect_gaps(probe) == [f"{name} no longer tags its launch with {text}"]
+
+
+# ---- the resampling kernels: sam_ops.hip cvmi_sam2_transform* and the bilinear mask return ------------------------------------------------------
+RESAMPLE_ENTRY_RE = r"cvmi_sam2_transform\w*|cvmi_mask_postprocess\w*|cvmi_bilinear_f32|cvmi_mask_extent"
+RESAMPLE_TYPES = {"f16": ("f16", "bf16"), "float": ("f32",), "_Float16": ("f16",), "__bf16": ("bf16",)}     # f16: the dual build's operand type
+RESAMPLE_CAP_KIND = {"cvmi_bilinear_f32": "bilinear", "cvmi_mask_postprocess": "bilinear", "cvmi_mask_postprocess_sizes": "bilinear",
+                     "cvmi_mask_postprocess_rects_dev": "bilinear", "cvmi_mask_extent": "mask_extent"}       # every other entry: "transform"
+
+
+def resample_entries(text):
+    """{entry: (dual built, body)} of every extern "C" definition in sam_ops.hip whose name matches RESAMPLE_ENTRY_RE (prototypes are skipped)."""
+    out = {}
+    for m in re.finditer(r'extern "C" int (CVMI_ENTRY\()?(cvmi_\w+)\)?\(([^{;]*)\)\s*(\{|;)', text):
+        if m.group(4) == "{" and re.fullmatch(RESAMPLE_ENTRY_RE, m.group(2)):
+            out[m.group(2)] = (bool(m.group(1)), text[m.end():text.index("\n}\n", m.end())])
+    return out
+
+
+def resample_constants(text):
+    """(AA_MAXTAPS, RECT_MAX, {entry: work items of one pass of each capped grid it launches}) as sam_ops.hip states them."""
+    taps = int(re.search(r"constexpr int AA_MAXTAPS = (\d+);", text).group(1))
+    rect = int(re.search(r"constexpr int RECT_MAX = (\d+);", text).group(1))
+    block, a, b = (int(v) for v in re.search(r"inline int grid_for\(long long total, int block = (\d+), int cap = (\d+) \* (\d+)\)", text).groups())
+    caps = {}
+    for name, (_, body) in resample_entries(text).items():
+        found = set()
+        for args in re.findall(r"grid_for\(((?:[^()]|\([^()]*\))*)\)", body):
+            parts = [p.strip() for p in re.split(r",(?![^()]*\))", args)]
+            found.add((int(parts[2]) if len(parts) > 2 else a * b) * (int(parts[1]) if len(parts) > 1 else block))
+        caps[name] = found
+    return taps, rect, caps
+
+
+def _refuses(row, form):
+    """Is the row's call through `form` one the entry point must refuse (transform rows: per form; mask-return rows: the whole row)?"""
+    ref = row.get("refuse")
+    return form in ref if isinstance(ref, dict) else bool(ref)
+
+
+def resample_gaps(text, rows=RESAMPLE_ROWS):
+    """What the resampling matrix leaves uncovered or mirrors wrongly, as a list of strings (empty = complete)."""
+    gaps = []
+    taps, rect, caps = resample_constants(text)
+    if taps != AA_MAXTAPS:
+        gaps.append(f"AA_MAXTAPS is {taps} in sam_ops.hip, op_matrix mirrors {AA_MAXTAPS}")
+    if rect != RECT_MAX:
+        gaps.append(f"RECT_MAX is {rect} in sam_ops.hip, op_matrix mirrors {RECT_MAX}")
+    entries = resample_entries(text)
+    form_of = {e: f for f, e in list(TRANSFORM_ENTRY.items()) + list(MASK_ENTRY.items())}
+    gaps += [f"op_matrix names {e}, which sam_ops.hip no longer defines" for e in sorted(set(form_of) - set(entries))]
+
+    def launched(name, seen=()):
+        """Output-type instances an entry launches, through the entry it forwards to if it has no launch of its own."""
+        dual, body = entries[name]
+        inst = [(k, t, dual) for k, t in re.findall(r"hipLaunchKernelGGL\(\(?(sam2_transform\w*_kernel)<([\w ]+)>", body)]
+        fwd = re.search(r"return (cvmi_\w+)\(", body)
+        return inst or (launched(fwd.group(1), seen + (name,)) if fwd and fwd.group(1) in entries and fwd.group(1) not in seen else [])
+
+    for name in sorted(entries):
+        kind = RESAMPLE_CAP_KIND.get(name, "transform")
+        want = {RESAMPLE_GRID_CAP[kind]}
+        if caps[name] and caps[name] != want:
+            gaps.append(f"{name} caps a grid at {sorted(caps[name])} work items, op_matrix.RESAMPLE_GRID_CAP[{kind!r}] mirrors {sorted(want)}")
+        form = form_of.get(name)
+        mine = [r for r in rows if form in r["forms"] and not _refuses(r, form)] if form else []
+        if not mine:
+            gaps.append(f"{name} has no rows in op_matrix.RESAMPLE_ROWS")
+            continue
+        if form in TRANSFORM_ENTRY:
+            inst = launched(name)
+            if not inst:
+                gaps.append(f"{name}: no sam2_transform kernel launch found")
+            for kernel, t, dual in inst:
+                for dt in (RESAMPLE_TYPES[t] if dual or t != "f16" else ("f16",)):
+                    if not any(dt in r["dtypes"] for r in mine):
+                        gaps.append(f"{name}: {kernel}<{t}> ({dt}) has no row that launches it")
+            if not any(form in r["forms"] and _refuses(r, form) for r in rows):
+                gaps.append(f"{name} has no refused row")
+    return gaps
+
+
+def _sam_ops():
+    return open(os.path.join(CSRC, "sam_ops.hip")).read()
+
+
+def test_resample_rows_mirror_sam_ops_and_cover_every_entry_and_type_instance():
+    text = _sam_ops()
+    entries = resample_entries(text)
+    assert set(entries) == set(TRANSFORM_ENTRY.values()) | set(MASK_ENTRY.values()), sorted(entries)       # the parser still finds the nine entry points
+    assert {e for e, (dual, _) in entries.items() if dual} == {"cvmi_sam2_transform_batch", "cvmi_sam2_transform_rects"}
+    taps, rect, caps = resample_constants(text)
+    assert (taps, rect) == (AA_MAXTAPS, RECT_MAX) == (24, 64)
+    assert caps["cvmi_sam2_transform_batch"] == {RESAMPLE_GRID_CAP["transform"]} == {4096 * 256} and caps["cvmi_sam2_transform"] == set()
+    assert caps["cvmi_mask_postprocess_rects_dev"] == {RESAMPLE_GRID_CAP["bilinear"]} == {1024 * 256} and caps["cvmi_mask_extent"] == {RESAMPLE_GRID_CAP["mask_extent"]} == {32 * 256}
+    assert resample_gaps(text) == [], resample_gaps(text)
+    # the dual-built entries launch <f16> and <float>, the single-copy ones all three: every one of them is a (form, type) some row runs
+    for form in ("single", "batch", "rects", "rects_dev", "srcs"):
+        have = {dt for r in RESAMPLE_ROWS if form in r["forms"] and not _refuses(r, form) for dt in r["dtypes"]}
+        assert have == {"f16", "bf16", "f32"}, (form, have)
+
+
+def test_a_new_resampling_entry_a_removed_row_or_a_moved_constant_is_caught():
+    text = _sam_ops()
+    probe = text + '\nextern "C" int cvmi_sam2_transform_foo(const uint8_t* src, void* dst, cvmi_stream_t stream_) {\n  return 0;\n}\n'
+    assert resample_gaps(probe) == ["cvmi_sam2_transform_foo has no rows in op_matrix.RESAMPLE_ROWS"]
+    probe = text + '\nextern "C" int cvmi_mask_postprocess_foo(const float* x) {\n  return 0;\n}\n'
+    assert resample_gaps(probe) == ["cvmi_mask_postprocess_foo has no rows in op_matrix.RESAMPLE_ROWS"]
+    assert resample_gaps(text + '\nextern "C" int cvmi_sam2_transform_foo(const uint8_t* src);\n') == []              # a prototype is no entry point
+    drop = lambda pred: resample_gaps(text, [r for r in RESAMPLE_ROWS if not pred(r)])
+    assert drop(lambda r: "mask_extent" in r["forms"]) == ["cvmi_mask_extent has no rows in op_matrix.RESAMPLE_ROWS"]
+    strip = lambda form: resample_gaps(text, [dict(r, forms=tuple(f for f in r["forms"] if f != form)) for r in RESAMPLE_ROWS])
+    assert strip("mask_postprocess_rects_dev") == ["cvmi_mask_postprocess_rects_dev has no rows in op_matrix.RESAMPLE_ROWS"]
+    assert strip("single") == ["cvmi_sam2_transform has no rows in op_matrix.RESAMPLE_ROWS"]
+    assert strip("rects_dev") == ["cvmi_sam2_transform_rects_dev has no rows in op_matrix.RESAMPLE_ROWS"]
+    unrefused = [dict(r, refuse={f: t for f, t in r["refuse"].items() if f != "srcs"}) if isinstance(r.get("refuse"), dict) else r for r in RESAMPLE_ROWS]
+    assert resample_gaps(text, unrefused) == ["cvmi_sam2_transform_srcs has no refused row"]
+    def no_bf16(form):                                                         # the form's rows lose bf16; their other forms keep it
+        rows = []
+        for r in RESAMPLE_ROWS:
+            if form in r["forms"]:
+                rows += [dict(r, forms=tuple(f for f in r["forms"] if f != form)), dict(r, forms=(form,), dtypes=tuple(d for d in r["dtypes"] if d != "bf16"))]
+            else:
+                rows.append(r)
+        return resample_gaps(text, rows)
+
+    assert no_bf16("srcs") == ["cvmi_sam2_transform_srcs: sam2_transform_srcs_kernel<__bf16> (bf16) has no row that launches it"]
+    assert no_bf16("rects") == ["cvmi_sam2_transform_rects: sam2_transform_rects_kernel<f16> (bf16) has no row that launches it"]
+    assert resample_gaps(text.replace("constexpr int AA_MAXTAPS = 24;", "constexpr int AA_MAXTAPS = 32;")) == ["AA_MAXTAPS is 32 in sam_ops.hip, op_matrix mirrors 24"]
+    assert resample_gaps(text.replace("constexpr int RECT_MAX = 64;", "constexpr int RECT_MAX = 128;")) == ["RECT_MAX is 128 in sam_ops.hip, op_matrix mirrors 64"]
+    moved = text.replace("int cap = 256 * 16)", "int cap = 256 * 32)")
+    assert moved != text and any("cvmi_sam2_transform_srcs caps a grid at [2097152] work items" in g for g in resample_gaps(moved))
+    moved = text.replace("grid_for((long long)H * W, 256, 32)", "grid_for((long long)H * W, 256, 64)")
+    assert moved != text and resample_gaps(moved) == ["cvmi_mask_extent caps a grid at [16384] work items, op_matrix.RESAMPLE_GRID_CAP['mask_extent'] mirrors [8192]"]
