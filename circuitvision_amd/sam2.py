@@ -18,9 +18,12 @@ into constant post-projection residuals; Hiera's bicubic position embedding prec
 Numerics: the residual stream, LayerNorm statistics, softmax and all accumulators are fp32; in F16
 mode GEMM / attention operands are fp16.  F32 mode runs everything on exact-f32 MFMA (parity mode).
 """
+import ctypes
 import hashlib
 import math
 import threading
+from collections import namedtuple
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -30,6 +33,7 @@ from . import _lib
 from ._lib import ACT_GELU, ACT_NONE, ACT_RELU, ACT_SIGMOID, BF16, F16, F32
 from .engine import (ESIZE, TORCH_DTYPE, is16, Buf, PackedConv, PackedHieraMlp, PackedProjMlp, PackedQkvAttn, PackedTokLinear, Plan, Rows, make_attn_desc, op_attention,
                      op_call, op_cast, op_conv, op_hiera_mlp, op_layernorm, op_maxpool2, op_tok_linear, op_tok_linear_pool, require_gpu, tok_linear_supported)
+from .decoder_route import route_decoder
 from .hiera_route import WEIGHT_SWITCHES, block_packings, hiera_blocks, route_block, sam_switches
 
 LOG2E = 1.4426950408889634
@@ -451,6 +455,12 @@ class Sam2Weights:
         self.refine_params = torch.cat([t.float() for t in parts]).to(self.device)
 
 
+# The image of decoder batch entry n, for a launch that reads a per-image tensor: n // rep (a prompts = P plan: rep = P), else table[n] (a pairs plan's
+# `pair_image`), else n itself (0 and None).  The fields are the kernels' `*_bdiv` / `res_rep` and `*_bmap` / `res_map` arguments.
+_PairMap = namedtuple("_PairMap", "rep table")
+_PER_PAIR = _PairMap(0, None)
+
+
 class Sam2Plan:
     """Launch plan for B images: x [B, R, R, 3] (NHWC, normalised) -> high_res, low_res, iou.
 
@@ -477,19 +487,17 @@ class Sam2Plan:
             raise ValueError("attn must be '16' or 'fp8' (fp8 needs an fp16 / bf16 plan)")
         self.av_fp8 = 1 if attn == "fp8" else 0
         self.sw = sam_switches()._replace(**{f: getattr(wt.sw, f) for f in WEIGHT_SWITCHES})      # plan-level switches as set now, weight-level as packed
-        self.P, self.K, self.want_high_res = prompts, points, high_res
-        if pairs and prompts:
-            raise ValueError("pairs (a pair-to-image table) and prompts (P per image) are alternatives")
-        if pairs < 0 or pairs > 65535:
-            raise ValueError("pairs must be in 1 .. 65535")
+        self.P, self.K = prompts, points
+        # everything after the trunk is routed here (the route checks the prompt arguments), before anything is allocated; _neck_decoder emits it
+        self.droute = route_decoder(wt.dtype, B, wt.image_size, self.sw, prompts=prompts, pairs=pairs, points=points, mask_prompt=mask_prompt,
+                                    multimask=multimask, high_res=high_res, refine=wt.refine_params is not None,
+                                    neck_tok=("feat_s0" in wt.tl, "feat_s1" in wt.tl), stage_dims=wt.stage_dims, n_tok=wt.n_tok)
         self.pairs = int(pairs)
-        if (prompts or pairs) and not wt.prompt_ok:
+        if self.droute.prompted and not wt.prompt_ok:
             raise _lib.CvmiError("this checkpoint carries no sam_prompt_encoder tensors: box / point prompts are unavailable")
-        if (mask_prompt or multimask) and not (prompts or pairs):
-            raise ValueError("mask_prompt / multimask need prompts > 0 (the learned-prompt wrapper always runs single-mask without a mask input)")
         if mask_prompt and not wt.mask_prompt_ok:
             raise _lib.CvmiError("this checkpoint carries no sam_prompt_encoder.mask_downscaling tensors: mask prompts are unavailable")
-        self.mask_prompt, self.multimask = bool(mask_prompt), bool(multimask)
+        self.mask_prompt, self.multimask, self.share_l0 = bool(mask_prompt), bool(multimask), self.droute.stream == "shared"
         self.plan = Plan(stream)
         self.pool = {}
         self.dynamic = dynamic_multimask_via_stability
@@ -624,231 +632,210 @@ class Sam2Plan:
                               win=ws, grid_h=r.Hp if ws else 0, grid_w=r.Wp if ws else 0, q_pool=1 if q_pool else 0, av_fp8=self.av_fp8,
                               q_log2=1 if r.q_log2 else 0, **proj)
 
-    # ---- neck + mask decoder + tail -------------------------------------------------------------------------
+    # ---- neck + mask decoder + tail: emits what self.droute (decoder_route.DecoderRoute) says ----------------------------------
     def _neck_decoder(self, st):
-        wt, B, dt = self.wt, self.B, self.dt
-        R = wt.image_size
-        f0, f1, fs = R // 4, R // 8, R // 16
-        # GEMM operands in compute dtype (stage outputs are f32 residual streams)
-        def cast(buf, tag):
-            if dt == F32:
-                return buf
-            o = self.buf(buf.H, buf.W, buf.C, dt)
-            op_cast(self.plan, f"cast.{tag}", buf.view(), o.view())
-            return o
-        feat_s0 = self.buf(f0, f0, 32)
-        feat_s1 = self.buf(f1, f1, 64)
-        for key, src, dstb, tag in (("feat_s0", st[0], feat_s0, "s0"), ("feat_s1", st[1], feat_s1, "s1")):
-            if self.sw.neckcast and key in wt.tl and src.dtype == F32 and (B * src.H * src.W) % 256 == 0:
-                op_tok_linear(self.plan, key, wt.tl[key], src.view(), dstb.view(), ln="cast", kind="neck")     # reads the f32 stage output itself
-            else:
-                self.gemm(key, key, cast(src, tag).view(), dstb.view(), kind="neck")
-        s2, s3 = cast(st[2], "s2"), cast(st[3], "s3")
-        lib = _lib.load()
-        NP = self.P                                   # prompts per image (0: learned prompts, or pairs)
-        NB = self.pairs or (B * NP if NP else B)      # decoder batch: (image, prompt) pairs -- image-major, or as the pair table names them
-        prompted = bool(NP or self.pairs)
-        # pairs: the image of pair n is pair_image[n]; the launches that derive it as n / NP in a prompts = P plan take the table instead
-        self.pair_image = pim = torch.zeros(NB, dtype=torch.int32, device=self.dev) if self.pairs else None
-        P = fs * fs
-        bufd = lambda *a, **k: self.buf(*a, batch=NB, **k)
-        if not prompted:
-            # src = FPN level 2 + learned dense prompt   (f32: it is the decoder's residual stream "keys")
-            keys = self.buf(fs, fs, 256, F32)
-            dense = wt.const["dense"]
-            self.gemm("embed", "embed", [(s2.view(), 0), (s3.view(), 1)], keys.view(), res=_ConstView(dense, 256), res_mod=fs * fs, kind="neck")
-            T = wt.n_tok
-            # token stream (f32).  Layer 0 reads the constant tokens (qn0) and REPLACES the stream, so it needs no init.
-            qn0 = Buf(B, 1, T, 256, dt, self.dev)
-            qn0.t.copy_(wt.const["tokens"].to(TORCH_DTYPE[dt]).view(1, 1, T, 256).expand(B, 1, T, 256))
-            tpe = lambda name, C_: dict(res=_ConstView(wt.const[name], C_), res_mod=T)
-        else:
-            # src = FPN level 2 + no_mem_embed + no_mask_embed (both in the GEMM bias), repeated for the prompts of each image
-            emb = self.buf(fs, fs, 256, F32)
-            self.gemm("embed", "embed_box", [(s2.view(), 0), (s3.view(), 1)], emb.view(), kind="neck")
-            keys = bufd(fs, fs, 256, F32)
-            # Until layer 0's image -> token attention writes into it, the image stream of every prompt of an image IS that image's
-            # embedding: in fp16 mode layer 0 reads the B shared copies (k / v and q projections on B images instead of B * P,
-            # attention kernels index the shared batch entry, the first residual add broadcasts) and the repeat pass disappears.
-            # f32 parity mode keeps the literal repeat_image formulation (upstream MaskDecoder.predict_masks) as the cross-check.
-            # A mask prompt makes the image stream differ per pair from the start (nothing to share): one launch writes
-            # keys = emb + mask_downscaling(mask_in) - no_mask_embed where the repeat pass stands, and in 16-bit mode the operand copy too.
-            self.share_l0 = is16(dt) and self.sw.share_l0 and not self.mask_prompt
-            if self.mask_prompt:
-                self.mask_in = torch.zeros(NB, f0, f0, dtype=torch.float32, device=self.dev)
-                kn0 = bufd(fs, fs, 256, tag="kn") if is16(dt) else None
-                head = (self.mask_in.data_ptr(), emb.t.data_ptr(), wt.const["mask_down"].data_ptr(), keys.t.data_ptr(),
-                        kn0.t.data_ptr() if kn0 is not None else None, dt if kn0 is not None else F16)
-                fn, tail = (lib.cvmi_mask_prompt_embed_pairs, (NB, pim.data_ptr(), fs)) if self.pairs else (lib.cvmi_mask_prompt_embed, (B, NP, fs))
-                op_call(self.plan, "mask_prompt_embed", "decoder", fn, head + tail,
-                        keep=(emb, keys, kn0, pim), bytes_=NB * f0 * f0 * 4 + (B + NB) * P * 256 * 4 + (NB * P * 256 * 2 if kn0 is not None else 0),
-                        flops=2 * NB * P * (16 * 4 + 16 * 16 + 256 * 16))
-            elif self.pairs and not self.share_l0:
-                # the gather stands where the repeat pass stands; in a 16-bit plan it writes layer 0's operand copy too (no l0.t2i.castk)
-                kn0 = bufd(fs, fs, 256, tag="kn") if is16(dt) else None
-                op_call(self.plan, "gather_embed", "decoder", lib.cvmi_gather_images,
-                        (emb.t.data_ptr(), keys.t.data_ptr(), kn0.t.data_ptr() if kn0 is not None else None, dt if kn0 is not None else F16,
-                         P * 256 * 4, pim.data_ptr(), NB),
-                        keep=(emb, keys, kn0, pim), bytes_=2 * NB * P * 256 * 4 + (NB * P * 256 * 2 if kn0 is not None else 0))
-            elif not self.share_l0:
-                op_call(self.plan, "repeat_embed", "decoder", lib.cvmi_repeat_images, (emb.t.data_ptr(), keys.t.data_ptr(), P * 256 * 4, B, NP),
-                        keep=(emb, keys), bytes_=(B + NB) * P * 256 * 4)
-            T = 6 + self.K
-            self.coords = torch.zeros(NB, self.K, 2, dtype=torch.float32, device=self.dev)
-            self.labels = torch.full((NB, self.K), -1, dtype=torch.int32, device=self.dev)
-            tok0 = Buf(NB, 1, T, 256, F32, self.dev)
-            qn0 = Buf(NB, 1, T, 256, dt, self.dev)
-            op_call(self.plan, "prompt_tokens", "decoder", lib.cvmi_prompt_tokens,
-                    (self.coords.data_ptr(), self.labels.data_ptr(), wt.const["gauss"].data_ptr(), wt.const["out_tokens"].data_ptr(),
-                     wt.const["prompt_table"].data_ptr(), float(R), tok0.t.data_ptr(), qn0.t.data_ptr(), dt, NB, self.K, 6),
-                    keep=(tok0, qn0), bytes_=NB * T * 256 * 6)
-            npe = wt.pc["token_pe"].N
-            pe_all = Buf(NB, 1, T, npe, dt, self.dev)
-            self.gemm("token_pe", "token_pe", qn0.view(), pe_all.view(), kind="decoder")
-            tpe = lambda name, C_: dict(res=pe_all.view(wt.pe_off[name][0], C_))
-            self.tokens0 = tok0
-        self.feat_s0, self.feat_s1, self.keys0 = feat_s0, feat_s1, keys
-        q = Buf(NB, 1, T, 256, F32, self.dev, zero=True)
-
-        def ln(label, key, src, dst, dst2=None):
-            gam, bet = wt.ln[key]
-            op_layernorm(self.plan, label, src.view(), gam, bet, dst.view(), 1e-5, dst2=dst2.view() if dst2 is not None else None)
-
-        def attention(label, qb, q_off, kb, k_off, vb, v_off, ob, Nq, Nk, hd, q_bdiv=0, kv_bdiv=0, q_bmap=None, kv_bmap=None):
-            es = ESIZE[dt]
-            desc = make_attn_desc(q=qb.t.data_ptr() + q_off * es, k=kb.t.data_ptr() + k_off * es, v=vb.t.data_ptr() + v_off * es, o=ob.t.data_ptr(),
-                                  q_sb=Nq * qb.C, q_sh=hd, q_st=qb.C, k_sb=Nk * kb.C, k_sh=hd, k_st=kb.C, v_sb=Nk * vb.C, v_sh=hd, v_st=vb.C,
-                                  o_sb=Nq * ob.C, o_sh=hd, o_st=ob.C, B=NB, heads=8, Nq=Nq, Nk=Nk, dqk=hd, dv=hd, scale=hd ** -0.5, dtype=dt,
-                                  win=0, grid_h=0, grid_w=0, q_pool=0, q_bdiv=q_bdiv, kv_bdiv=kv_bdiv,
-                                  q_bmap=q_bmap.data_ptr() if q_bmap is not None else None, kv_bmap=kv_bmap.data_ptr() if kv_bmap is not None else None)
-            op_attention(self.plan, label, desc, (qb, kb, vb, ob, q_bmap, kv_bmap), flops=4 * NB * 8 * Nq * Nk * hd, kind="decoder")
-
-        dual = is16(dt)                          # norm4 writes the 16-bit operand copy of the image stream itself (no cast pass)
-        qn = bufd(1, T, 256, tag="qn")           # compute-dtype copies of the f32 streams
-        kn = bufd(fs, fs, 256, tag="kn")
-        G = lambda *a, **k: self.gemm(*a, kind="decoder", **k)
+        r = self.droute
+        self.feat_s0, self.feat_s1, s2, s3 = self._neck(st, r)
+        # pairs: the image of pair n is pair_image[n]; the launches that derive it as n / P in a prompts = P plan take the table instead
+        self.pair_image = torch.zeros(r.NB, dtype=torch.int32, device=self.dev) if self.pairs else None
+        pm = _PairMap(self.P, self.pair_image)
+        emb, keys, kn = self._image_stream(r, pm, s2, s3)
+        qn0, pe = self._tokens(r)
+        # the two f32 residual streams -- tokens q (layer 0 REPLACES it, so it needs no init) and image `keys` -- with their operand-dtype copies
+        s = SimpleNamespace(q=Buf(r.NB, 1, r.T, 256, F32, self.dev, zero=True), qn=self._bufd(1, r.T, 256, tag="qn"), emb=emb, keys=keys, kn=kn)
         for l in (0, 1):
-            p = f"l{l}"
-            # --- self attention on the tokens
-            qkv = bufd(1, T, 768, tag="sa_qkv")
-            if l == 0:
-                G(f"{p}.sa.qkv", f"{p}.sa.qkv", qn0.view(), qkv.view())
+            self._two_way_layer(l, r, s, qn0, pe, pm)
+        self._t2i("final", r.castk[2], s, pe, pm)
+        self._ln("norm_final", s.q, s.q)
+        self.keys0, self.keys_out, self.tokens_out = keys, keys, s.q
+        self._upscale_and_heads(r, s, pm)
+        self._tail(r)
+
+    def _bufd(self, *a, **k):                  # a buffer with the decoder's batch (pairs), where `buf` has the images'
+        return self.buf(*a, batch=self.droute.NB, **k)
+
+    def _G(self, name, src, dst, **kw):
+        self.gemm(name, name, src, dst, kind="decoder", **kw)
+
+    def _ln(self, name, src, dst, dst2=None, eps=1e-5, act=ACT_NONE):
+        gam, bet = self.wt.ln[name]
+        op_layernorm(self.plan, name, src.view(), gam, bet, dst.view(), eps, act=act, dst2=dst2.view() if dst2 is not None else None)
+
+    def _attention(self, label, qb, q_off, kb, k_off, vb, v_off, ob, Nq, Nk, hd, q_map=_PER_PAIR, kv_map=_PER_PAIR):
+        """q_map / kv_map: the _PairMap through which batch entry n finds its q / its k and v, where those are per IMAGE."""
+        dt, NB, es, (q_bdiv, q_bmap), (kv_bdiv, kv_bmap) = self.dt, self.droute.NB, ESIZE[self.dt], q_map, kv_map
+        desc = make_attn_desc(q=qb.t.data_ptr() + q_off * es, k=kb.t.data_ptr() + k_off * es, v=vb.t.data_ptr() + v_off * es, o=ob.t.data_ptr(),
+                              q_sb=Nq * qb.C, q_sh=hd, q_st=qb.C, k_sb=Nk * kb.C, k_sh=hd, k_st=kb.C, v_sb=Nk * vb.C, v_sh=hd, v_st=vb.C,
+                              o_sb=Nq * ob.C, o_sh=hd, o_st=ob.C, B=NB, heads=8, Nq=Nq, Nk=Nk, dqk=hd, dv=hd, scale=hd ** -0.5, dtype=dt,
+                              win=0, grid_h=0, grid_w=0, q_pool=0, q_bdiv=q_bdiv, kv_bdiv=kv_bdiv,
+                              q_bmap=q_bmap.data_ptr() if q_bmap is not None else None, kv_bmap=kv_bmap.data_ptr() if kv_bmap is not None else None)
+        op_attention(self.plan, label, desc, (qb, kb, vb, ob, q_bmap, kv_bmap), flops=4 * NB * 8 * Nq * Nk * hd, kind="decoder")
+
+    def _neck(self, st, r):
+        """FPN levels 0 / 1 from the first two stage outputs, and the last two as GEMM operands -> (feat_s0, feat_s1, s2, s3)."""
+        def cast(j):                       # GEMM operands in compute dtype (stage outputs are f32 residual streams)
+            if j not in r.casts:
+                return st[j]
+            o = self.buf(st[j].H, st[j].W, st[j].C, self.dt)
+            op_cast(self.plan, f"cast.s{j}", st[j].view(), o.view())
+            return o
+        feats = (self.buf(r.f0, r.f0, 32), self.buf(r.f1, r.f1, 64))
+        for j, (key, dst) in enumerate(zip(("feat_s0", "feat_s1"), feats)):
+            if r.neck[j] == "tok":
+                op_tok_linear(self.plan, key, self.wt.tl[key], st[j].view(), dst.view(), ln="cast", kind="neck")     # reads the f32 stage output itself
             else:
-                op_cast(self.plan, f"{p}.sa.cast", q.view(), qn.view())
-                G(f"{p}.sa.qkv", f"{p}.sa.qkv", qn.view(), qkv.view(), **tpe(f"{p}.sa.qkv_pe", 768))
-            ao = bufd(1, T, 256, tag="sa_ao")
-            attention(f"{p}.sa.attn", qkv, 0, qkv, 256, qkv, 512, ao, T, T, 32)
-            if l == 0:
-                G(f"{p}.sa.out", f"{p}.sa.out", ao.view(), q.view())                         # layer 0: queries REPLACED (skip_first_layer_pe)
-            else:
-                G(f"{p}.sa.out", f"{p}.sa.out", ao.view(), q.view(), res=q.view())
-            ln(f"{p}.norm1", f"{p}.norm1", q, q)
-            # --- tokens attend to the image
-            op_cast(self.plan, f"{p}.t2i.castq", q.view(), qn.view())
-            share = l == 0 and prompted and getattr(self, "share_l0", False)      # layer 0 of the box path: image-side tensors per IMAGE
-            if share:
-                kn_l = self.buf(fs, fs, 256, tag="kn_shared")
-                op_cast(self.plan, f"{p}.t2i.castk", emb.view(), kn_l.view())
-            else:
-                kn_l = kn
-                if not dual or (l == 0 and not self.mask_prompt and not self.pairs):      # (16-bit mask prompts / pairs: mask_prompt_embed / gather_embed has written kn)
-                    op_cast(self.plan, f"{p}.t2i.castk", keys.view(), kn.view())
-            tq = bufd(1, T, 128, tag="t2i_q")
-            G(f"{p}.t2i.q", f"{p}.t2i.q", qn.view(), tq.view(), **tpe(f"{p}.t2i.q_pe", 128))
-            kv = self.buf(fs, fs, 256, tag="t2i_kv_shared") if share else bufd(fs, fs, 256, tag="t2i_kv")
-            G(f"{p}.t2i.kv", f"{p}.t2i.kv", kn_l.view(), kv.view(), res=_ConstView(wt.const[f"{p}.t2i.kv_pe"], 256), res_mod=P)
-            ao2 = bufd(1, T, 128, tag="t2i_ao")
-            attention(f"{p}.t2i.attn", tq, 0, kv, 0, kv, 128, ao2, T, P, 16, kv_bdiv=NP if share else 0, kv_bmap=pim if share else None)
-            G(f"{p}.t2i.out", f"{p}.t2i.out", ao2.view(), q.view(), res=q.view())
-            ln(f"{p}.norm2", f"{p}.norm2", q, q)
-            # --- MLP on the tokens
-            op_cast(self.plan, f"{p}.mlp.cast", q.view(), qn.view())
-            hid = bufd(1, T, 2048, tag="mlp_hid")
-            G(f"{p}.mlp1", f"{p}.mlp1", qn.view(), hid.view(), act=ACT_RELU)
-            G(f"{p}.mlp2", f"{p}.mlp2", hid.view(), q.view(), res=q.view())
-            ln(f"{p}.norm3", f"{p}.norm3", q, q)
-            # --- image attends to the tokens
-            op_cast(self.plan, f"{p}.i2t.castq", q.view(), qn.view())
-            iq = self.buf(fs, fs, 128, tag="i2t_q_shared") if share else bufd(fs, fs, 128, tag="i2t_q")
-            G(f"{p}.i2t.q", f"{p}.i2t.q", kn_l.view(), iq.view(), res=_ConstView(wt.const[f"{p}.i2t.q_pe"], 128), res_mod=P)
-            ikv = bufd(1, T, 256, tag="i2t_kv")
-            G(f"{p}.i2t.kv", f"{p}.i2t.kv", qn.view(), ikv.view(), **tpe(f"{p}.i2t.kv_pe", 256))
-            ao3 = bufd(fs, fs, 128, tag="i2t_ao")
-            attention(f"{p}.i2t.attn", iq, 0, ikv, 0, ikv, 128, ao3, P, T, 16, q_bdiv=NP if share else 0, q_bmap=pim if share else None)
-            if share:      # first write of the per-prompt image stream: keys[b] = emb[b / P] (pairs: emb[pair_image[b]]) + out-projection
-                G(f"{p}.i2t.out", f"{p}.i2t.out", ao3.view(), keys.view(), res=emb.view(), res_mod=P, res_rep=NP, res_map=pim)
-            else:
-                G(f"{p}.i2t.out", f"{p}.i2t.out", ao3.view(), keys.view(), res=keys.view())
-            ln(f"{p}.norm4", f"{p}.norm4", keys, keys, dst2=kn if dual else None)      # + the fp16 copy the next k / v projection reads
-        # --- final token -> image attention
-        op_cast(self.plan, "final.castq", q.view(), qn.view())
-        if not dual:
-            op_cast(self.plan, "final.castk", keys.view(), kn.view())
-        tq = bufd(1, T, 128, tag="t2i_q")
-        G("final.q", "final.q", qn.view(), tq.view(), **tpe("final.q_pe", 128))
-        kv = bufd(fs, fs, 256, tag="t2i_kv")
-        G("final.kv", "final.kv", kn.view(), kv.view(), res=_ConstView(wt.const["final.kv_pe"], 256), res_mod=P)
-        ao2 = bufd(1, T, 128, tag="t2i_ao")
-        attention("final.attn", tq, 0, kv, 0, kv, 128, ao2, T, P, 16)
-        G("final.out", "final.out", ao2.view(), q.view(), res=q.view())
-        ln("norm_final", "norm_final", q, q)
-        self.tokens_out, self.keys_out = q, keys
-        # --- upscaling: act1(ln1(dc1(src) + s1)) ; act2(dc2(.) + s0)
-        u1 = bufd(f1, f1, 64)
-        G("up1", "up1", kn.view(), u1.view(), res=feat_s1.view(), shuffle_cout=64, res_rep=NP, res_map=pim)
-        gam, bet = wt.ln["up_ln"]
-        op_layernorm(self.plan, "up_ln", u1.view(), gam, bet, u1.view(), 1e-6, act=ACT_GELU)
-        u2 = bufd(f0, f0, 32)
-        G("up2", "up2", u1.view(), u2.view(), res=feat_s0.view(), shuffle_cout=32, act=ACT_GELU, act_after_res=True, res_rep=NP, res_map=pim)
-        self.up = u2
+                self.gemm(key, key, cast(j).view(), dst.view(), kind="neck")
+        return feats + (cast(2), cast(3))
+
+    def _image_stream(self, r, pm, s2, s3):
+        """FPN level 2 (`embed`) and the launch r.stream names -> (emb: a prompted plan's per-image embedding, keys: the decoder's per-pair f32 image
+        stream, kn: its copy in the operand dtype -- allocated here, once; r.castk says which launches write it)."""
+        wt, dt, B, NB, lib, fs, f0, P = self.wt, self.dt, self.B, r.NB, _lib.load(), r.fs, r.f0, r.fs * r.fs
+        emb = self.buf(fs, fs, 256, F32) if r.prompted else None
+        keys, kn = self._bufd(fs, fs, 256, F32), self._bufd(fs, fs, 256, tag="kn")
+        srcs = [(s2.view(), 0), (s3.view(), 1)]
+        if r.stream == "dense":            # FPN level 2 + learned dense prompt, straight into the stream
+            self.gemm("embed", "embed", srcs, keys.view(), res=_ConstView(wt.const["dense"], 256), res_mod=P, kind="neck")
+            return emb, keys, kn
+        # FPN level 2 + no_mem_embed + no_mask_embed (both in the GEMM bias), per image
+        self.gemm("embed", "embed_box", srcs, emb.view(), kind="neck")
+        # the launch that makes the per-pair stream of it ("shared": none, see DecoderRoute.stream); in a 16-bit plan it writes the operand copy too
+        kn16, copy16 = ((kn.t.data_ptr(), dt), NB * P * 256 * 2) if is16(dt) else ((None, F16), 0)
+        if r.stream == "mask_prompt":      # keys = emb + mask_downscaling(mask_in) - no_mask_embed
+            self.mask_in = torch.zeros(NB, f0, f0, dtype=torch.float32, device=self.dev)
+            head = (self.mask_in.data_ptr(), emb.t.data_ptr(), wt.const["mask_down"].data_ptr(), keys.t.data_ptr()) + kn16
+            fn, tail = (lib.cvmi_mask_prompt_embed_pairs, (NB, pm.table.data_ptr(), fs)) if self.pairs else (lib.cvmi_mask_prompt_embed, (B, pm.rep, fs))
+            op_call(self.plan, "mask_prompt_embed", "decoder", fn, head + tail, keep=(emb, keys, kn, pm.table),
+                    bytes_=NB * f0 * f0 * 4 + (B + NB) * P * 256 * 4 + copy16, flops=2 * NB * P * (16 * 4 + 16 * 16 + 256 * 16))
+        elif r.stream == "gather":
+            op_call(self.plan, "gather_embed", "decoder", lib.cvmi_gather_images,
+                    (emb.t.data_ptr(), keys.t.data_ptr()) + kn16 + (P * 256 * 4, pm.table.data_ptr(), NB),
+                    keep=(emb, keys, kn, pm.table), bytes_=2 * NB * P * 256 * 4 + copy16)
+        elif r.stream == "repeat":
+            op_call(self.plan, "repeat_embed", "decoder", lib.cvmi_repeat_images, (emb.t.data_ptr(), keys.t.data_ptr(), P * 256 * 4, B, pm.rep),
+                    keep=(emb, keys), bytes_=(B + NB) * P * 256 * 4)
+        return emb, keys, kn
+
+    def _tokens(self, r):
+        """-> (the tokens layer 0 reads, in the operand dtype; pe(name, C): the residual arguments that add (token PE) @ W^T of constant `name`, C
+        wide, to a GEMM on the tokens: a constant of the checkpoint's own tokens, or a column group of the prompt tokens' `token_pe` GEMM)."""
+        wt, dt, NB, T = self.wt, self.dt, r.NB, r.T
+        qn0 = Buf(NB, 1, T, 256, dt, self.dev)
+        if r.tokens == "const":
+            qn0.t.copy_(wt.const["tokens"].to(TORCH_DTYPE[dt]).view(1, 1, T, 256).expand(NB, 1, T, 256))
+            return qn0, lambda name, C_: dict(res=_ConstView(wt.const[name], C_), res_mod=T)
+        self.coords = torch.zeros(NB, self.K, 2, dtype=torch.float32, device=self.dev)
+        self.labels = torch.full((NB, self.K), -1, dtype=torch.int32, device=self.dev)
+        self.tokens0 = tok0 = Buf(NB, 1, T, 256, F32, self.dev)
+        op_call(self.plan, "prompt_tokens", "decoder", _lib.load().cvmi_prompt_tokens,
+                (self.coords.data_ptr(), self.labels.data_ptr(), wt.const["gauss"].data_ptr(), wt.const["out_tokens"].data_ptr(),
+                 wt.const["prompt_table"].data_ptr(), float(wt.image_size), tok0.t.data_ptr(), qn0.t.data_ptr(), dt, NB, self.K, 6),
+                keep=(tok0, qn0), bytes_=NB * T * 256 * 6)
+        pe_all = Buf(NB, 1, T, wt.pc["token_pe"].N, dt, self.dev)
+        self._G("token_pe", qn0.view(), pe_all.view())
+        return qn0, lambda name, C_: dict(res=pe_all.view(wt.pe_off[name][0], C_))
+
+    def _t2i(self, p, castk, s, pe, pm):
+        """Tokens attend to the image (layer 0, layer 1, `final`) -> the image stream's operand copy it read.  castk (the route's) "emb": layer 0 of a
+        shared plan, the image-side tensors are per IMAGE, made from the embedding."""
+        T, fs, shared = self.droute.T, self.droute.fs, castk == "emb"
+        op_cast(self.plan, f"{p}.castq", s.q.view(), s.qn.view())
+        kn = self.buf(fs, fs, 256, tag="kn_shared") if shared else s.kn
+        if castk:
+            op_cast(self.plan, f"{p}.castk", (s.emb if shared else s.keys).view(), kn.view())
+        tq = self._bufd(1, T, 128, tag="t2i_q")
+        self._G(f"{p}.q", s.qn.view(), tq.view(), **pe(f"{p}.q_pe", 128))
+        kv = self.buf(fs, fs, 256, tag="t2i_kv_shared") if shared else self._bufd(fs, fs, 256, tag="t2i_kv")
+        self._G(f"{p}.kv", kn.view(), kv.view(), res=_ConstView(self.wt.const[f"{p}.kv_pe"], 256), res_mod=fs * fs)
+        ao = self._bufd(1, T, 128, tag="t2i_ao")
+        self._attention(f"{p}.attn", tq, 0, kv, 0, kv, 128, ao, T, fs * fs, 16, kv_map=pm if shared else _PER_PAIR)
+        self._G(f"{p}.out", ao.view(), s.q.view(), res=s.q.view())
+        return kn
+
+    def _two_way_layer(self, l, r, s, qn0, pe, pm):
+        T, fs, p, q, qn, keys, shared = r.T, r.fs, f"l{l}", s.q, s.qn, s.keys, r.castk[l] == "emb"      # shared: layer 0's image-side tensors are per IMAGE
+        # --- self attention on the tokens
+        qkv = self._bufd(1, T, 768, tag="sa_qkv")
+        if l:              # (layer 0 reads the initial tokens as they are, without a positional residual)
+            op_cast(self.plan, f"{p}.sa.cast", q.view(), qn.view())
+        self._G(f"{p}.sa.qkv", (qn if l else qn0).view(), qkv.view(), **(pe(f"{p}.sa.qkv_pe", 768) if l else {}))
+        ao = self._bufd(1, T, 256, tag="sa_ao")
+        self._attention(f"{p}.sa.attn", qkv, 0, qkv, 256, qkv, 512, ao, T, T, 32)
+        self._G(f"{p}.sa.out", ao.view(), q.view(), res=q.view() if l else None)         # layer 0: queries REPLACED (skip_first_layer_pe)
+        self._ln(f"{p}.norm1", q, q)
+        # --- tokens attend to the image
+        kn = self._t2i(f"{p}.t2i", r.castk[l], s, pe, pm)
+        self._ln(f"{p}.norm2", q, q)
+        # --- MLP on the tokens
+        op_cast(self.plan, f"{p}.mlp.cast", q.view(), qn.view())
+        hid = self._bufd(1, T, 2048, tag="mlp_hid")
+        self._G(f"{p}.mlp1", qn.view(), hid.view(), act=ACT_RELU)
+        self._G(f"{p}.mlp2", hid.view(), q.view(), res=q.view())
+        self._ln(f"{p}.norm3", q, q)
+        # --- image attends to the tokens
+        op_cast(self.plan, f"{p}.i2t.castq", q.view(), qn.view())
+        iq = self.buf(fs, fs, 128, tag="i2t_q_shared") if shared else self._bufd(fs, fs, 128, tag="i2t_q")
+        self._G(f"{p}.i2t.q", kn.view(), iq.view(), res=_ConstView(self.wt.const[f"{p}.i2t.q_pe"], 128), res_mod=fs * fs)
+        ikv = self._bufd(1, T, 256, tag="i2t_kv")
+        self._G(f"{p}.i2t.kv", qn.view(), ikv.view(), **pe(f"{p}.i2t.kv_pe", 256))
+        ao3 = self._bufd(fs, fs, 128, tag="i2t_ao")
+        self._attention(f"{p}.i2t.attn", iq, 0, ikv, 0, ikv, 128, ao3, fs * fs, T, 16, q_map=pm if shared else _PER_PAIR)
+        # shared: the first write of the per-pair image stream, keys[n] = emb[image of pair n] + out-projection
+        res = dict(res=s.emb.view(), res_mod=fs * fs, res_rep=pm.rep, res_map=pm.table) if shared else dict(res=keys.view())
+        self._G(f"{p}.i2t.out", ao3.view(), keys.view(), **res)
+        self._ln(f"{p}.norm4", keys, keys, dst2=s.kn if is16(self.dt) else None)      # + the 16-bit copy the next k / v projection reads (no cast pass)
+
+    def _mlp3(self, name, src, dst, act=ACT_NONE):             # a three-layer head `name`.0 - .2 on one row per pair
+        h1, h2 = self._bufd(1, 1, 256, tag="h1"), self._bufd(1, 1, 256, tag="h2")
+        self._G(f"{name}.0", src, h1.view(), act=ACT_RELU)
+        self._G(f"{name}.1", h1.view(), h2.view(), act=ACT_RELU)
+        self._G(f"{name}.2", h2.view(), dst, act=act)
+
+    def _upscale_and_heads(self, r, s, pm):
+        dt, NB, T = self.dt, r.NB, r.T
+        # --- upscaling: act1(ln1(dc1(src) + s1)) ; act2(dc2(.) + s0), s1 / s0 of the pair's image
+        u1 = self._bufd(r.f1, r.f1, 64)
+        self._G("up1", s.kn.view(), u1.view(), res=self.feat_s1.view(), shuffle_cout=64, res_rep=pm.rep, res_map=pm.table)
+        self._ln("up_ln", u1, u1, eps=1e-6, act=ACT_GELU)
+        self.up = u2 = self._bufd(r.f0, r.f0, 32)
+        self._G("up2", u1.view(), u2.view(), res=self.feat_s0.view(), shuffle_cout=32, act=ACT_GELU, act_after_res=True, res_rep=pm.rep, res_map=pm.table)
         # --- hypernetwork MLPs on the 4 mask tokens, IoU head on the iou token (rows strided by T*256)
-        op_cast(self.plan, "heads.cast", q.view(), qn.view())
-        hyper = Buf(NB, 1, 4, 32, F32, self.dev)
+        op_cast(self.plan, "heads.cast", s.q.view(), s.qn.view())
+        token = lambda i: _RowsView(s.qn.t, NB, 256, ld=T * 256, offset=i * 256, dtype=dt)
+        self.hyper, self.iou4 = Buf(NB, 1, 4, 32, F32, self.dev), Buf(NB, 1, 1, 4, F32, self.dev)
         for i in range(4):
-            src = _RowsView(qn.t, NB, 256, ld=T * 256, offset=(2 + i) * 256, dtype=dt)
-            h1 = bufd(1, 1, 256, tag="h1"); h2 = bufd(1, 1, 256, tag="h2")
-            G(f"hyper{i}.0", f"hyper{i}.0", src, h1.view(), act=ACT_RELU)
-            G(f"hyper{i}.1", f"hyper{i}.1", h1.view(), h2.view(), act=ACT_RELU)
-            G(f"hyper{i}.2", f"hyper{i}.2", h2.view(), _RowsView(hyper.t, NB, 32, ld=128, offset=i * 32, dtype=F32))
-        iou4 = Buf(NB, 1, 1, 4, F32, self.dev)
-        src = _RowsView(qn.t, NB, 256, ld=T * 256, offset=256, dtype=dt)
-        h1 = bufd(1, 1, 256, tag="h1"); h2 = bufd(1, 1, 256, tag="h2")
-        G("iou.0", "iou.0", src, h1.view(), act=ACT_RELU)
-        G("iou.1", "iou.1", h1.view(), h2.view(), act=ACT_RELU)
-        G("iou.2", "iou.2", h2.view(), iou4.view(), act=ACT_SIGMOID)
-        self.hyper, self.iou4 = hyper, iou4
-        # --- masks, dynamic multimask selection, upsample + refinement
-        P0 = f0 * f0
+            self._mlp3(f"hyper{i}", token(2 + i), _RowsView(self.hyper.t, NB, 32, ld=128, offset=i * 32, dtype=F32))
+        self._mlp3("iou", token(1), self.iou4.view(), act=ACT_SIGMOID)
+
+    def _tail(self, r):                        # masks, dynamic multimask selection, upsample + refinement
+        wt, dt, NB, R, f0, lib = self.wt, self.dt, r.NB, self.wt.image_size, r.f0, _lib.load()
+        P0, NM = f0 * f0, 3 if r.masks == "multimask_out" else 1                  # NM: masks returned per pair
         self.masks4 = torch.empty(NB, 4, f0, f0, dtype=torch.float32, device=self.dev)
         self.areas = torch.zeros(NB, 2, dtype=torch.int32, device=self.dev)
-        NM = 3 if self.multimask else 1                  # masks returned per pair
         self.low_res = torch.empty(NB, NM, f0, f0, dtype=torch.float32, device=self.dev)
         self.iou = torch.empty(NB, NM, dtype=torch.float32, device=self.dev)
         self.sel = torch.zeros(NB, dtype=torch.int32, device=self.dev)
         op_call(self.plan, "hyper_masks", "tail", lib.cvmi_hyper_masks,
-                (hyper.t.data_ptr(), 32, u2.t.data_ptr(), 32, dt, 32, self.masks4.data_ptr(), self.areas.data_ptr(), NB, P0, 0.05),
-                keep=(hyper, u2), bytes_=NB * P0 * (32 * ESIZE[dt] + 16), flops=2 * NB * P0 * 128)
-        if self.multimask:
+                (self.hyper.t.data_ptr(), 32, self.up.t.data_ptr(), 32, dt, 32, self.masks4.data_ptr(), self.areas.data_ptr(), NB, P0, 0.05),
+                keep=(self.hyper, self.up), bytes_=NB * P0 * (32 * ESIZE[dt] + 16), flops=2 * NB * P0 * 128)
+        if r.masks == "multimask_out":
             op_call(self.plan, "multimask_out", "tail", lib.cvmi_multimask_out,
-                    (self.masks4.data_ptr(), iou4.t.data_ptr(), 4, self.low_res.data_ptr(), self.iou.data_ptr(), NB, P0), bytes_=NB * P0 * 24)
+                    (self.masks4.data_ptr(), self.iou4.t.data_ptr(), 4, self.low_res.data_ptr(), self.iou.data_ptr(), NB, P0), bytes_=NB * P0 * 24)
         else:
             op_call(self.plan, "select_mask", "tail", lib.cvmi_select_mask,
-                    (self.masks4.data_ptr(), self.areas.data_ptr(), iou4.t.data_ptr(), 4, 1 if self.dynamic else 0, 0.98, self.low_res.data_ptr(),
+                    (self.masks4.data_ptr(), self.areas.data_ptr(), self.iou4.t.data_ptr(), 4, 1 if self.dynamic else 0, 0.98, self.low_res.data_ptr(),
                      self.iou.data_ptr(), self.sel.data_ptr(), NB, P0), bytes_=NB * P0 * 8)
-        if not self.want_high_res:
-            self.high_res = None
-            return
-        self.high_res = torch.empty(NB, NM, R, R, dtype=torch.float32, device=self.dev)
-        if wt.refine_params is not None and not prompted:            # the refinement head belongs to the learned-prompt wrapper (sam2_infer.py:269-270)
-            import ctypes as C
-            ks = (C.c_int * len(wt.kernels))(*wt.kernels)
+        self.high_res = torch.empty(NB, NM, R, R, dtype=torch.float32, device=self.dev) if r.upsample else None
+        if r.upsample == "upsample_refine":            # the refinement head belongs to the learned-prompt wrapper (sam2_infer.py:269-270)
+            ks = (ctypes.c_int * len(wt.kernels))(*wt.kernels)
             taps = sum(k * k for k in wt.kernels)
             op_call(self.plan, "upsample_refine", "tail", lib.cvmi_upsample_refine,
                     (self.low_res.data_ptr(), NB, f0, f0, self.high_res.data_ptr(), R, R, wt.refine_params.data_ptr(), ks, len(wt.kernels), 4),
                     keep=(ks,), bytes_=NB * (P0 + R * R) * 4, flops=2 * NB * R * R * 4 * taps)
-        else:
+        elif r.upsample:
             op_call(self.plan, "upsample", "tail", lib.cvmi_bilinear_f32,
                     (self.low_res.data_ptr(), NB * NM, f0, f0, self.high_res.data_ptr(), R, R, None, 0.0), bytes_=NB * NM * (P0 + R * R) * 4)
+
 
 class _ConstView:
     """Constant [rows, C] device tensor posing as a residual View (ptr, ld)."""

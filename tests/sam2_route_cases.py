@@ -3,7 +3,9 @@ against the plan itself), and the fixture's form: per configuration the trunk's 
 kernels as their family (cvmi_last_kernel's name up to `_kernel`), equal consecutive blocks collapsed to [count, [[suffix, kind, family], ...]].
 
 `python tests/sam2_route_cases.py OUT.json` (on a GPU) records the fixture from the plans as they are built: run it BEFORE a change that is meant to
-leave the launches alone, or after one that changes routing on purpose (and say so in that pull request)."""
+leave the launches alone, or after one that changes routing on purpose (and say so in that pull request).
+
+HEAD_CASES below do the same for everything outside the blocks (tests/test_decoder_route_cpu.py / _gpu.py against tests/decoder_route_fixture.json)."""
 import json
 import os
 import re
@@ -122,13 +124,84 @@ def build_plan(case, params_cache=None):
                 os.environ[k] = v
 
 
+# ---- everything after the trunk: neck, mask decoder, tail (circuitvision_amd/decoder_route.py) ------------------------------------------------
+# tests/decoder_route_fixture.json, per configuration {"act_bytes": the plan's, "launches": [[label, kind, bytes, flops, kernel family], ...]} of
+# every launch whose label is not a block's (the two stem launches in front of the trunk included), in launch order.
+# `python tests/sam2_route_cases.py --head OUT.json` (on a GPU) records it, under the same rule as the trunk's fixture.
+def _head(id, dtype, hiera="MINI", refinement=True, env=None, **plan):
+    return dict(id=id, hiera=hiera, size=256, dtype=dtype, B=2, refinement=refinement, env=env or {}, plan=plan)
+
+
+_NO_SHARE, _NO_NECKCAST = {"CVMI_SAM_SHARE_L0": "0"}, {"CVMI_SAM_NECKCAST": "0"}
+HEAD_CASES = [
+    _head("learned_f16", "f16"), _head("learned_bf16", "bf16"), _head("learned_f32", "f32"),
+    _head("learned_f16_norefine", "f16", refinement=False),
+    _head("learned_f16_lowres", "f16", high_res=False),
+    _head("prompts2_f16", "f16", prompts=2), _head("prompts2_f32", "f32", prompts=2),
+    _head("prompts2_f16_SHARE_L0=0", "f16", prompts=2, env=_NO_SHARE),
+    _head("prompts2_mask_f16", "f16", prompts=2, mask_prompt=True), _head("prompts2_mask_f32", "f32", prompts=2, mask_prompt=True),
+    _head("prompts2_multimask_f16", "f16", prompts=2, multimask=True),
+    _head("pairs3_f16", "f16", pairs=3), _head("pairs3_f32", "f32", pairs=3),
+    _head("pairs3_f16_SHARE_L0=0", "f16", pairs=3, env=_NO_SHARE),
+    _head("pairs3_mask_f16", "f16", pairs=3, mask_prompt=True),
+    _head("mini144_learned_f16", "f16", hiera="MINI144"),                # MINI's 16 / 32-wide stage outputs have no token-stationary neck; 144 / 288 do
+    _head("mini144_learned_f16_NECKCAST=0", "f16", hiera="MINI144", env=_NO_NECKCAST),
+]
+STEM = [["s2d4", "stem"], ["patch_embed", "stem"]]                       # what the fixture holds in front of the route's launches
+
+
+def head_params(hiera):
+    """The synthetic checkpoint the prompt tests build their mini models from (MINI144: test_proj_mlp_gpu's)."""
+    if hiera == "MINI":
+        from test_mask_prompt_gpu import _params
+        return _params()
+    from circuitvision_amd.sam2 import SamSyntheticParams
+    return SamSyntheticParams(seed=5, lora_targets=lora_targets_of(hiera), std=0.05)
+
+
+def _with_env(env, fn):
+    old = {k: os.environ.get(k) for k in env}
+    os.environ.update(env)
+    try:
+        return fn()
+    finally:
+        for k, v in old.items():
+            if v is None:
+                del os.environ[k]
+            else:
+                os.environ[k] = v
+
+
+def build_head_plan(case, cache=None):
+    """Sam2Plan of a HEAD_CASE under its switches (GPU).  cache: {(hiera, dtype, refinement): Sam2Weights} shared between cases (the two
+    switches the cases set are plan-level)."""
+    import torch
+    from circuitvision_amd.sam2 import Sam2Plan, Sam2Weights
+    cache = {} if cache is None else cache
+    key = (case["hiera"], case["dtype"], case["refinement"])
+    if key not in cache:
+        cache[key] = Sam2Weights(head_params(case["hiera"]), hiera_of(case["hiera"]), case["size"], dtype_of(case["dtype"]), use_refinement=case["refinement"])
+    return _with_env(case["env"], lambda: Sam2Plan(cache[key], case["B"], torch.cuda.Stream(), **case["plan"]))
+
+
+def head_launches(sp):
+    """[[label, kind, bytes, flops, kernel family]] of a plan's launches outside the Hiera blocks (one timed eager pass)."""
+    return [[t[0], t[1], t[3], t[4], t[5].split("_kernel")[0]] for t in sp.plan.timed_eager(with_kernels=True) if not BLOCK_LABEL.fullmatch(t[0])]
+
+
 if __name__ == "__main__":
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     cache, fixture = {}, {}
-    for case in CASES:
-        sp = build_plan(case, cache)
-        fixture[case["id"]] = collapse(trunk_blocks([(t[0], t[1], t[5]) for t in sp.plan.timed_eager(with_kernels=True)]))
-        del sp
-    with open(sys.argv[1], "w") as f:
+    if sys.argv[1] == "--head":
+        for case in HEAD_CASES:
+            sp = build_head_plan(case, cache)
+            fixture[case["id"]] = dict(act_bytes=sp.act_bytes, launches=head_launches(sp))
+            del sp
+    else:
+        for case in CASES:
+            sp = build_plan(case, cache)
+            fixture[case["id"]] = collapse(trunk_blocks([(t[0], t[1], t[5]) for t in sp.plan.timed_eager(with_kernels=True)]))
+            del sp
+    with open(sys.argv[-1], "w") as f:
         json.dump(fixture, f, separators=(",", ":"))
         f.write("\n")
