@@ -441,7 +441,7 @@ inline int grid_for(long long total, int block = 256, int cap = 1024) {
   return (int)(g < 1 ? 1 : (g > cap ? cap : g));
 }
 
-constexpr size_t kLdsMax = 160 * 1024;              // LDS of one gfx950 workgroup
+constexpr size_t kLdsMax = 160 * 1024;              // LDS of one gfx950 workgroup; a dynamic request of all of it is accepted (row lds_160k_exact)
 
 struct Workspace {
   PlaneRec* tab;
@@ -830,6 +830,8 @@ extern "C" int cvmi_external_contours(uint8_t* planes, const unsigned long long*
     CVMI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&trace_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
     CVMI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&trace_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
   }
+  // which of the two plane forms the trace reads, and the dynamic LDS it asks for (cvmi_last_kernel)
+  cvmi_note_kernel(use_lds ? "trace_kernel<lds, %d>" : "trace_kernel<global, %d>", (int)dyn);
   hipLaunchKernelGGL(trace_kernel<false>, dim3(N), b256, dyn, s, w.tab, N, w.fgm, w.roots, w.row_off, w.npts, w.pt_off, use_lds, cap_contours,
                      cap_points, counts, info, area2, points);
   hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, s, w.npts, w.pt_off, 0, counts + N, counts + N + 1);

@@ -36,6 +36,11 @@ cvmi_mask_extent).  One row = the sources, windows or sizes of one call and the 
 constants the rows were built from (AA_MAXTAPS, RECT_MAX, the grid caps) mirror the source text.  Operands, references, mutants and bounds live in
 tests/resample_ref.py.
 
+CONTOUR_ROWS / PREPARE_ROWS: the contour stage of wire_ops.hip (cvmi_external_contours' ten kernels, cvmi_node_prepare).  One contour row = one batch
+of plane specs and the trace tag (path and dynamic LDS bytes) the call must report; contour_tag mirrors the per-batch choice, and the constants
+the shapes were sized from (PLANE_MAX, the launch shapes, the two LDS thresholds) mirror the source text.  Plane builders, the geometric oracle
+and the float64 resize live in tests/contour_ref.py.
+
 BF16_OPS: every entry point that common.hpp builds twice (CVMI_ENTRY) -> (test module, test function) that checks its bf16 build per op.
 
 Plain data: importing this module needs neither a GPU nor the library."""
@@ -1077,3 +1082,94 @@ RESAMPLE_MUTANT_ROWS = {
                                  "mask_rects_dev_513x512", "extent_91x91"],
     "clip_moves_window": ["tf_clip_rects_dev"],
 }
+
+
+# ---- the contour stage of wire_ops.hip: cvmi_external_contours and cvmi_node_prepare --------------------------------------------------------
+# One CONTOUR row = one batch of planes (specs that tests/contour_ref.build_plane turns into arrays), whether the planes' sums are passed, and
+# the tag cvmi_external_contours must leave in cvmi_last_kernel(): the trace path and its dynamic LDS bytes.  The constants mirror wire_ops.hip;
+# tests/test_op_coverage_cpu.py compares them with the source text.
+PLANE_MAX = 32                                     # planes per contour_table_kernel / node_empty_kernel launch
+TRACE_LANES = 256                                  # contours traced per round of a plane's workgroup
+ROOT_ROWS_PER_BLOCK = 4                            # one wave per row in root_count_kernel / root_assign_kernel
+BALLOT_LANES = 64                                  # columns per ballot chunk of root_assign_kernel
+CONTOUR_GRID_CAP = 1024 * 256                      # pixels one grid pass of the three label kernels (and of node_prepare's two) covers
+TRACE_LDS_OPTIN = 64 * 1024                        # above: hipFuncSetAttribute(MaxDynamicSharedMemorySize)
+TRACE_LDS_MAX = 160 * 1024                         # kLdsMax: above, the trace reads bytes from global memory
+
+
+def plane_shape(spec):
+    """(H, W) of a plane spec."""
+    fixed = {"rings": (120, 160), "leak": (9, 11), "comb": (23, 61), "serpentine": (21, 37), "inv127": (15, 17), "inv127_plus1": (15, 17)}
+    return fixed[spec[0]] if spec[0] in fixed else (spec[1], spec[2])
+
+
+def trace_lds_bytes(shapes):
+    """The bit planes of a batch in LDS: 4 bytes per 32 columns per row of the largest plane."""
+    return 4 * max(h * ((w + 31) // 32) for h, w in shapes)
+
+
+def contour_tag(shapes, lds_max=TRACE_LDS_MAX):
+    """Mirror of cvmi_external_contours' choice, made once per batch from the largest plane."""
+    lds = trace_lds_bytes(shapes)
+    return "trace_kernel<lds, %d>" % lds if lds <= lds_max else "trace_kernel<global, 0>"
+
+
+WORD_EDGE_W = (1, 31, 32, 33, 63, 64, 65, 129)
+WORD_EDGE_H = (1, 4, 5, 9)
+WORD_EDGE_PLANES = tuple(p for h in WORD_EDGE_H for w in WORD_EDGE_W for p in (("rand", h, w, 0.5, 1000 * h + w), ("full", h, w), ("lastrc", h, w)))
+
+
+def _ct(rid, planes, expect, sums=True, note=""):
+    return dict(id=rid, planes=tuple(planes), sums=sums, expect=expect, note=note)
+
+
+def _lds_row(rid, tall, expect, note):
+    return _ct(rid, WORD_EDGE_PLANES + (tall,), expect, sums=False, note=note)
+
+
+CONTOUR_ROWS = [
+    _ct("word_edges", WORD_EDGE_PLANES, "trace_kernel<lds, 180>", sums=False, note="the tail word, the frame rule, 64-wide ballot chunks, 4 rows per block"),
+    _ct("lattice_9x129", [("lattice", 9, 129)], "trace_kernel<lds, 180>", sums=False, note="325 contours = the root capacity; the lane loop wraps; 65 roots per row"),
+    _ct("nesting", [("rings",), ("leak",), ("comb", 23, 61), ("serpentine", 21, 37)], "trace_kernel<lds, 2400>", note="holes, the 4-connected background, revisited pixels"),
+    _ct("inversion", [("inv127",), ("inv127_plus1",), ("values", 13, 19, 1, tuple(range(1, 101))), ("values", 13, 19, 2, tuple(range(150, 255))),
+                      ("values", 16, 33, 3, (0, 0, 0, 7, 200, 255)), ("values", 16, 33, 4, (0, 7, 200, 255, 255, 255, 255))],
+        "trace_kernel<lds, 128>", note="sum == 127 * H * W does not invert, + 1 does; both foreground rules; binarize"),
+    _ct("inversion_no_sums", [("inv127_plus1",), ("values", 16, 33, 4, (0, 7, 200, 255, 255, 255, 255))], "trace_kernel<lds, 128>", sums=False,
+        note="without sums nothing inverts"),
+    _ct("empty_zero", [("zero", 7, 9), ("zero", 1, 1), ("zero", 40, 50)], "trace_kernel<lds, 320>", note="no contour: scan_kernel reads n = 0 from the device"),
+    _ct("empty_full_inverts", [("full", 7, 9), ("full", 1, 1), ("full", 40, 50)], "trace_kernel<lds, 320>", note="all 255 inverts to nothing"),
+    _ct("plane_max_plus_1", [("rand", 1 + (5 * n) % 8, 1 + (3 * n) % 8, 0.5, 50 + n) for n in range(PLANE_MAX)] + [("rand", 40, 50, 0.4, 99)], "trace_kernel<lds, 320>",
+        note="the second contour_table_kernel launch with p0, r0, q0 carried"),
+    _ct("grid_stride_513x512", [("rand", 513, 512, 0.35, 7)], "trace_kernel<lds, 32832>", sums=False, note="past the grid_for cap of the label kernels"),
+    _lds_row("lds_64k_no_optin", ("stripes", 16384, 1, 0), "trace_kernel<lds, 65536>", "the largest request without the opt-in"),
+    _lds_row("lds_64k_plus_optin", ("stripes", 16385, 1, 0), "trace_kernel<lds, 65540>", "the smallest request with the opt-in"),
+    _lds_row("lds_160k_exact", ("stripes", 40960, 1, 0), "trace_kernel<lds, 163840>", "exactly kLdsMax"),
+    _lds_row("global_160k_plus", ("stripes", 40961, 1, 0), "trace_kernel<global, 0>", "one row past kLdsMax: bytes from global memory"),
+    _lds_row("global_40961x2", ("stripes", 40961, 2, 1), "trace_kernel<global, 0>", "the global path with a ragged last column"),
+]
+CONTOUR_CAPACITY_ROW = _ct("capacity_lattice_rings", [("lattice", 9, 129), ("rings",)], "trace_kernel<lds, 2400>", sums=False, note="the capacity cases")
+CONTOUR_CAPACITY_CASES = ("exact", "contours_minus_1", "points_minus_1", "count_only")
+
+
+# One PREPARE row = the planes (H, W, seed) of one prepare_packed(new_height = PREPARE_HEIGHT) call and the boxes of each plane: "kinds" = the
+# box kinds of tests/test_wires_gpu.py (negative, past the edge, empty, preserved, a fractional one), "none" = no box.
+PREPARE_HEIGHT = 12
+PREPARE_REFUSED = ((40, 1),)                       # int(12 * (1 / 40)) = 0 columns: prepare_packed refuses what cv2.resize would reject
+
+
+def _pp(rid, planes, boxes, note=""):
+    return dict(id=rid, planes=tuple(planes), boxes=tuple(boxes), note=note)
+
+
+PREPARE_ROWS = [
+    _pp("identity_12x18", [(12, 18, 1)], ["kinds"], "NH == H and NW == W: the copy branch"),
+    _pp("down_2x_24x36", [(24, 36, 2)], ["kinds"], "an exact 2x downscale"),
+    _pp("up_from_5x7", [(5, 7, 3)], ["kinds"], "an upscale"),
+    _pp("ratio_37x53", [(37, 53, 4)], ["kinds"], "a non-integer ratio"),
+    _pp("tiny_1x1_1x40", [(1, 1, 5), (1, 40, 6)], ["kinds", "kinds"], "one-pixel axes"),
+    _pp("thin_2x300", [(2, 300, 7)], ["kinds"], "a thin plane"),
+    _pp("grid_stride_513x512", [(513, 512, 8)], ["kinds"], "past the grid cap of node_empty_kernel"),
+    _pp("plane_max_plus_1", [(3 + n % 5, 4 + n % 7, 20 + n) for n in range(PLANE_MAX + 1)], ["none"] * (PLANE_MAX - 1) + ["kinds", "kinds"],
+        "boxes only on the last plane of the first launch and the only plane of the second: box0 of the second launch"),
+    _pp("mixed_no_box", [(12, 18, 9), (9, 14, 10), (24, 36, 11)], ["kinds", "none", "kinds"], "a plane with no box between two that have them"),
+]

@@ -4,7 +4,8 @@ dispatcher can launch has a row in the dispatch matrix, and so has every kernel 
 refinement kernel of the helper dispatchers (LN_ROWS, HELPER_ROWS), every branch combination and edge of the detector's tail (NMS_ROWS,
 DECODE_ROWS), and every instance of the token-stationary kernels with the chunk counts,
 split counts, pool grids and statistics forms their rings and index arithmetic need (TOK_ROWS, MLP_ROWS), and every entry point and output-type
-instance of the resampling kernels with the constants their rows were built from (RESAMPLE_ROWS).  Adding an entry point or a kernel
+instance of the resampling kernels with the constants their rows were built from (RESAMPLE_ROWS), and every trace path, LDS threshold and
+launch-table edge of the contour stage (CONTOUR_ROWS, PREPARE_ROWS).  Adding an entry point or a kernel
 without its per-op test fails here, on any checkout."""
 import ast
 import glob
@@ -18,6 +19,8 @@ from op_matrix import (ATTN_ROWS, BF16_OPS, C3K2_INSTANCES, CONV_ROWS, DECODE_NC
                        TOK_PARTS, TOK_ROWS, TOK_SLOTS, TOK_SPLIT_TABLE, TOK_UNSEEN_MUTANTS, c3k2_max_wgs_per_cu, c3k2_tag, conv_expect, ln_pick, ln_reachable,
                        ln_tag, mlp_pick, tl16_splits, tok_dispatch, tok_nch_family, tok_pick)
 from op_matrix import AA_MAXTAPS, MASK_ENTRY, RECT_MAX, RESAMPLE_GRID_CAP, RESAMPLE_ROWS, TRANSFORM_ENTRY
+from op_matrix import (BALLOT_LANES, CONTOUR_CAPACITY_ROW, CONTOUR_GRID_CAP, CONTOUR_ROWS, PLANE_MAX, PREPARE_ROWS, ROOT_ROWS_PER_BLOCK, TRACE_LANES, TRACE_LDS_MAX,
+                       TRACE_LDS_OPTIN, contour_tag, plane_shape, trace_lds_bytes)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(os.path.dirname(HERE), "circuitvision_amd", "csrc")
@@ -877,3 +880,122 @@ def test_a_new_resampling_entry_a_removed_row_or_a_moved_constant_is_caught():
     assert moved != text and any("cvmi_sam2_transform_srcs caps a grid at [2097152] work items" in g for g in resample_gaps(moved))
     moved = text.replace("grid_for((long long)H * W, 256, 32)", "grid_for((long long)H * W, 256, 64)")
     assert moved != text and resample_gaps(moved) == ["cvmi_mask_extent caps a grid at [16384] work items, op_matrix.RESAMPLE_GRID_CAP['mask_extent'] mirrors [8192]"]
+
+
+# ---- the contour stage of wire_ops.hip: cvmi_external_contours, cvmi_node_prepare ----------------------------------------------------------------
+CONTOUR_RULE_TEXT = ("maxwords = std::max(maxwords, g.H[n] * ((g.W[n] + 31) / 32));", "const size_t lds = (size_t)maxwords * 4;", "const int use_lds = lds <= kLdsMax;",
+                     "const size_t dyn = use_lds ? lds : 0;")
+CONTOUR_SHAPE_TEXT = {                             # launch shapes the rows were sized for -> how often wire_ops.hip states them
+    "template <bool WRITE>\n__global__ __launch_bounds__(%d) void trace_kernel(" % TRACE_LANES: 1,
+    "for (int k = threadIdx.x; k < cnt; k += blockDim.x) {": 1,
+    "const int y = blockIdx.x * %d + (threadIdx.x >> 6), lane = threadIdx.x & 63;" % ROOT_ROWS_PER_BLOCK: 2,
+    "b256(256), grow(cdiv(mh, %d), N);" % ROOT_ROWS_PER_BLOCK: 1,
+    "for (int x0 = 0; x0 < t.W; x0 += %d) {" % BALLOT_LANES: 1,
+    "inline int grid_for(long long total, int block = 256, int cap = %d) {" % (CONTOUR_GRID_CAP // 256): 1,
+}
+
+
+def _product(expr):
+    out = 1
+    for f in expr.split("*"):
+        out *= int(f)
+    return out
+
+
+def contour_constants(text):
+    """(PLANE_MAX, kLdsMax, the opt-in threshold, (the lds tag format, the global tag format)) as wire_ops.hip states them."""
+    plane_max = int(re.search(r"constexpr int PLANE_MAX = (\d+);", text).group(1))
+    lds_max = _product(re.search(r"constexpr size_t kLdsMax = ([\d *]+);", text).group(1))
+    optin = _product(re.search(r"if \(dyn > ([\d *]+)\) \{\s*CVMI_HIP\(hipFuncSetAttribute\(", text).group(1))
+    tags = re.search(r'cvmi_note_kernel\(use_lds \? "([^"]*)" : "([^"]*)", \(int\)dyn\);', text)
+    return plane_max, lds_max, optin, tags.groups() if tags else ()
+
+
+def contour_gaps(text, rows=CONTOUR_ROWS, prepare_rows=PREPARE_ROWS):
+    """What the contour matrix leaves uncovered, as a list of strings (empty = complete)."""
+    plane_max, lds_max, optin, tags = contour_constants(text)
+    gaps = []
+    for name, got, mirror in (("PLANE_MAX", plane_max, PLANE_MAX), ("kLdsMax", lds_max, TRACE_LDS_MAX), ("the LDS opt-in threshold", optin, TRACE_LDS_OPTIN)):
+        if got != mirror:
+            gaps.append(f"{name} is {got} in wire_ops.hip, op_matrix mirrors {mirror}")
+    gaps += [f"wire_ops.hip no longer states `{t}`" for t in CONTOUR_RULE_TEXT if t not in text]
+    gaps += [f"wire_ops.hip states `{t.strip()}` {text.count(t)} times, not {n}" for t, n in CONTOUR_SHAPE_TEXT.items() if text.count(t) != n]
+    if tags != ("trace_kernel<lds, %d>", "trace_kernel<global, %d>"):
+        gaps.append(f"cvmi_external_contours tags its trace as {tags}, not as trace_kernel<lds, %d> / trace_kernel<global, %d>")
+    shapes = {r["id"]: [plane_shape(s) for s in r["planes"]] for r in rows}
+    need = {r["id"]: trace_lds_bytes(shapes[r["id"]]) for r in rows}
+    for r in rows:                                                          # the source's rule, with the source's constant, on the row's shapes
+        if contour_tag(shapes[r["id"]], lds_max) != r["expect"]:
+            gaps.append(f"row {r['id']} expects {r['expect']}, the rule of wire_ops.hip gives {contour_tag(shapes[r['id']], lds_max)}")
+    for name, T in (("the LDS opt-in threshold", optin), ("kLdsMax", lds_max)):
+        if not any(b == T for b in need.values()):
+            gaps.append(f"{name}: no row whose largest plane needs exactly {T} bytes")
+        if not any(T < b <= T + 8 for b in need.values()):
+            gaps.append(f"{name}: no row whose largest plane needs one or two words more than {T} bytes")
+        if not any(b < T for b in need.values()):
+            gaps.append(f"{name}: no row below {T} bytes")
+    fams = {re.match(r"trace_kernel<(\w+),", r["expect"]).group(1) for r in rows}
+    gaps += [f"the tag {t} is expected by no row" for t in tags if re.match(r"trace_kernel<(\w+),", t).group(1) not in fams]
+    for r in rows:                                                          # one large plane moves every plane of the call: the path rows carry small planes too
+        if need[r["id"]] > min(optin, lds_max) - 8 and not any(h * w <= 9 * 129 for h, w in shapes[r["id"]]):
+            gaps.append(f"row {r['id']} reaches a threshold without a small plane in the same call")
+    if not any(len(s) > plane_max for s in shapes.values()):
+        gaps.append(f"no contour row with more than PLANE_MAX = {plane_max} planes")
+    if not any(len(r["planes"]) > plane_max and [b for b in r["boxes"][plane_max - 1:] if b != "none"] and set(r["boxes"][:plane_max - 1]) == {"none"} for r in prepare_rows):
+        gaps.append(f"no prepare row with boxes only on plane {plane_max - 1} and after it")
+    if not any(h * w > CONTOUR_GRID_CAP for s in shapes.values() for h, w in s):
+        gaps.append(f"no contour row with a plane of more than {CONTOUR_GRID_CAP} pixels")
+    if not any(h * w > CONTOUR_GRID_CAP for r in prepare_rows for h, w, _ in r["planes"]):
+        gaps.append(f"no prepare row with a plane of more than {CONTOUR_GRID_CAP} pixels")
+    if not any(s[0] == "lattice" and ((s[1] + 1) // 2) * ((s[2] + 1) // 2) > TRACE_LANES and (s[2] + 1) // 2 > BALLOT_LANES and s[1] > ROOT_ROWS_PER_BLOCK
+               for r in rows for s in r["planes"]):
+        gaps.append("no lattice plane with more contours than trace lanes, more roots in a row than ballot lanes and more rows than one root block")
+    return gaps
+
+
+def _wire_ops():
+    return open(os.path.join(CSRC, "wire_ops.hip")).read()
+
+
+def test_contour_rows_mirror_wire_ops_and_cover_every_trace_path_and_threshold():
+    text = _wire_ops()
+    assert contour_constants(text) == (32, 160 * 1024, 64 * 1024, ("trace_kernel<lds, %d>", "trace_kernel<global, %d>"))      # the parser still finds them
+    assert (PLANE_MAX, TRACE_LDS_MAX, TRACE_LDS_OPTIN, CONTOUR_GRID_CAP) == (32, 163840, 65536, 1024 * 256)
+    assert contour_gaps(text) == [], contour_gaps(text)
+    ids = [r["id"] for r in CONTOUR_ROWS] + [CONTOUR_CAPACITY_ROW["id"]]
+    assert len(ids) == len(set(ids)), "duplicate row ids"
+    for r in CONTOUR_ROWS + [CONTOUR_CAPACITY_ROW]:
+        assert r["expect"] == contour_tag([plane_shape(s) for s in r["planes"]]), r["id"]
+    by = {r["id"]: r for r in CONTOUR_ROWS}
+    assert [by[i]["expect"] for i in ("lds_64k_no_optin", "lds_64k_plus_optin", "lds_160k_exact", "global_160k_plus", "global_40961x2")] == \
+        ["trace_kernel<lds, 65536>", "trace_kernel<lds, 65540>", "trace_kernel<lds, 163840>", "trace_kernel<global, 0>", "trace_kernel<global, 0>"]
+    # probes, as the sibling guards do: a moved constant, a moved rule, a removed row
+    moved = text.replace("constexpr size_t kLdsMax = 160 * 1024;", "constexpr size_t kLdsMax = 192 * 1024;")
+    g = contour_gaps(moved)
+    assert moved != text and "kLdsMax is 196608 in wire_ops.hip, op_matrix mirrors 163840" in g and "kLdsMax: no row whose largest plane needs exactly 196608 bytes" in g \
+        and "row global_160k_plus expects trace_kernel<global, 0>, the rule of wire_ops.hip gives trace_kernel<lds, 163844>" in g \
+        and "the tag trace_kernel<global, %d> is expected by no row" not in g, g
+    moved = text.replace("if (dyn > 64 * 1024) {", "if (dyn > 96 * 1024) {")
+    assert moved != text and contour_gaps(moved) == ["the LDS opt-in threshold is 98304 in wire_ops.hip, op_matrix mirrors 65536",
+                                                     "the LDS opt-in threshold: no row whose largest plane needs exactly 98304 bytes",
+                                                     "the LDS opt-in threshold: no row whose largest plane needs one or two words more than 98304 bytes"]
+    moved = text.replace("constexpr int PLANE_MAX = 32;", "constexpr int PLANE_MAX = 128;")
+    assert contour_gaps(moved) == ["PLANE_MAX is 128 in wire_ops.hip, op_matrix mirrors 32", "no contour row with more than PLANE_MAX = 128 planes",
+                                   "no prepare row with boxes only on plane 127 and after it"]
+    moved = text.replace("const int use_lds = lds <= kLdsMax;", "const int use_lds = lds < kLdsMax;")
+    assert contour_gaps(moved) == ["wire_ops.hip no longer states `const int use_lds = lds <= kLdsMax;`"]
+    moved = text.replace('cvmi_note_kernel(use_lds ? "trace_kernel<lds, %d>"', 'note_off(use_lds ? "trace_kernel<lds, %d>"')
+    assert any("tags its trace as ()" in m for m in contour_gaps(moved))
+    drop = lambda *rids: contour_gaps(text, [r for r in CONTOUR_ROWS if r["id"] not in rids])
+    assert drop("lds_160k_exact") == ["kLdsMax: no row whose largest plane needs exactly 163840 bytes"]
+    assert drop("global_160k_plus") == []                                  # (global_40961x2 is one word past kLdsMax too)
+    assert drop("global_160k_plus", "global_40961x2") == ["kLdsMax: no row whose largest plane needs one or two words more than 163840 bytes",
+                                                          "the tag trace_kernel<global, %d> is expected by no row"]
+    assert drop("lds_64k_no_optin") == ["the LDS opt-in threshold: no row whose largest plane needs exactly 65536 bytes"]
+    assert drop("lds_64k_plus_optin") == ["the LDS opt-in threshold: no row whose largest plane needs one or two words more than 65536 bytes"]
+    assert drop("plane_max_plus_1", "word_edges", *[i for i in by if i.startswith(("lds_", "global_"))])[-1] == "no contour row with more than PLANE_MAX = 32 planes"
+    assert drop("grid_stride_513x512") == ["no contour row with a plane of more than 262144 pixels"]
+    assert drop("lattice_9x129")[-1].startswith("no lattice plane with more contours than trace lanes")
+    assert contour_gaps(text, prepare_rows=[r for r in PREPARE_ROWS if r["id"] != "plane_max_plus_1"]) == ["no prepare row with boxes only on plane 31 and after it"]
+    alone = [dict(r, planes=r["planes"][-1:]) if r["id"] == "lds_160k_exact" else r for r in CONTOUR_ROWS]
+    assert contour_gaps(text, alone) == ["row lds_160k_exact reaches a threshold without a small plane in the same call"]

@@ -10,7 +10,8 @@ OpenCV is not installed, so nothing here is pinned against cv2 itself.  Items ma
   [UP] the bit-exact 8-bit GaussianBlur (getGaussianKernelBitExact in ufixedpoint16, row then column pass, (s + 32768) >> 16)
   [UP] the point order of a traced border (icvFetchContour) and the list order of the contours (reverse raster order of the start
        pixels: cvFindContours inserts each new contour at the head of its list)
-Everything else is exact integer arithmetic with independent checks in scipy (tests/test_wires_cpu.py).
+Everything else is exact integer arithmetic with independent checks in scipy (tests/test_wires_cpu.py).  The traced borders are judged by
+geometry alone, without following a border, in tests/contour_ref.py (tests/test_contour_ref_cpu.py).
 """
 import math
 
