@@ -180,7 +180,8 @@ def test_row_stats_predicate_mirrors_the_gemm_dispatch():
 
 
 def test_counted_lds_rings_hold_no_scalar_memory_instruction():
-    """the hand-counted `s_waitcnt lgkmcnt(N > 0)` rings of tok_linear16.hip / hiera_mlp.hip / tok_linear.hip are only valid while
+    """the hand-counted `s_waitcnt lgkmcnt(N > 0)` rings of tok_linear16.hip / hiera_mlp.hip / tok_linear.hip / attention.hip (the
+    fused qkv + window attention kernels run the token path's tok_mfma_chunk) are only valid while
     hipcc emits no scalar-memory instruction (same counter, out-of-order return) between a ring `ds_read_b128` and the MFMA that consumes it.
     tools/check_ring_asm.py disassembles the device code of both operand builds and fails on any; the checker itself is exercised on a
     synthetic stream first."""
@@ -194,12 +195,12 @@ def test_counted_lds_rings_hold_no_scalar_memory_instruction():
     assert (k, s) == (1, 1) and [b[2] for b in bad] == ["s_load_dwordx2 s[0:1], s[4:5], 0x0"]      # inside the window: flagged; after the drain: not
     if not os.path.exists(m.HIPCC):
         pytest.skip("hipcc not available")
-    assert m.main(["tok_linear16.hip", "hiera_mlp.hip", "tok_linear.hip"]) == 0
+    assert m.main(["tok_linear16.hip", "hiera_mlp.hip", "tok_linear.hip", "attention.hip"]) == 0
 
 
 def test_attention_kernels_stay_inside_their_occupancy_register_budget():
     """The global / windowed head_dim-72 attention kernels are designed for four waves per SIMD (two 8-wave workgroups per CU): <= 128 registers,
-    nothing spilled.  `__launch_bounds__` does not enforce that -- attn_dma72_kernel drifted to 139 registers in r03 and ran one workgroup per
+    nothing spilled; the four fused qkv + window attention instances for two 4-wave workgroups per CU: <= 256 registers, nothing spilled.  `__launch_bounds__` does not enforce that -- attn_dma72_kernel drifted to 139 registers in r03 and ran one workgroup per
     CU, correct and 13 % slower.  tools/check_occupancy.py reads the kernel descriptors of the device assembly; the extraction is exercised on
     a synthetic descriptor first."""
     import importlib.util

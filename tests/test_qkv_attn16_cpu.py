@@ -25,7 +25,9 @@ def header_instances(text):
 
 def test_every_instance_the_header_launches_has_a_row_and_every_row_an_instance():
     text = open(HEADER).read()
-    assert 'cvmi_note_kernel("qkv_attn16_kernel<%d, %d, %s>", K, HEADS, CVMI_BOOLNAME(QPOOL));' in text
+    # the tag: the shared launcher (qa_launch of qkv_attn.hpp) formats its caller's format string with (K, heads, q-pooled)
+    assert 'cvmi_note_kernel(tag, K, heads, CVMI_BOOLNAME(qpool));' in open(os.path.join(os.path.dirname(HEADER), "qkv_attn.hpp")).read()
+    assert re.findall(r'return qa_launch<&(\w+)<K, HEADS, QPOOL>, [^(]*\("([^"]*)", K, HEADS, QPOOL, a, ps, stream\);', text) == [("qkv_attn16_kernel", "qkv_attn16_kernel<%d, %d, %s>")]
     inst = header_instances(text)
     assert inst and len(inst) == len(set(inst)), inst       # the parser still finds the call sites
     tags = {r["expect"] for r in QKV_ATTN16_ROWS}

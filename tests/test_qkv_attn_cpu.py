@@ -24,7 +24,9 @@ def header_instances(text):
 
 def test_every_instance_the_header_launches_has_a_row():
     text = open(HEADER).read()
-    assert 'cvmi_note_kernel("qkv_attn64_kernel<%d, %d, %s>", K, HEADS, CVMI_BOOLNAME(QPOOL));' in text
+    # the tag: the shared launcher (qa_launch) formats its caller's format string with (K, heads, q-pooled)
+    assert 'cvmi_note_kernel(tag, K, heads, CVMI_BOOLNAME(qpool));' in text
+    assert re.findall(r'return qa_launch<&(\w+)<K, HEADS, QPOOL>, [^(]*\("([^"]*)", K, HEADS, QPOOL, a, ps, stream\);', text) == [("qkv_attn64_kernel", "qkv_attn64_kernel<%d, %d, %s>")]
     inst = header_instances(text)
     assert inst and len(inst) == len(set(inst)), inst       # the parser still finds the call sites
     tags = {r["expect"] for r in QKV_ATTN_ROWS}

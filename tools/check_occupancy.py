@@ -26,6 +26,10 @@ BUDGETS = {
         "attn_res256_kernelILi8ELb0ELb0EE": 128,  # 16 x 16 windows: two 8-wave workgroups per CU (2 x 79 KiB of LDS)
         "attn_res256_kernelILi8ELb0ELb1EE": 128,  # the same on log2-prescaled q (Hiera stage 3)
         "attn_res64_kernelILi2EE": 128,           # 8 x 8 windows: launch bounds ask for 4 waves per SIMD
+        "qkv_attn64_kernelILi144ELi2ELb0EE": 256,  # fused qkv + 8 x 8 windows: two 4-wave workgroups per CU = 2 waves per SIMD
+        "qkv_attn64_kernelILi144ELi4ELb1EE": 256,  # the same, q-pooled
+        "qkv_attn16_kernelILi288ELi4ELb0EE": 256,  # fused qkv + 4 x 4 windows: two 4-wave workgroups per CU
+        "qkv_attn16_kernelILi288ELi8ELb1EE": 256,  # the same, q-pooled (at the budget: 256)
     }),
 }
 

@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
-"""Build check for the hand-counted LDS rings: tok_linear.hip, tok_linear16.hip and hiera_mlp.hip keep several inline-asm
-`ds_read_b128` in flight and release each MFMA with a COUNTED `s_waitcnt lgkmcnt(N)`.  That is only valid while nothing else of the wave
+"""Build check for the hand-counted LDS rings: tok_linear.hip, tok_linear16.hip, hiera_mlp.hip and the fused qkv + window
+attention kernels of attention.hip (qkv_attn.hpp: the same tok_mfma_chunk) keep several inline-asm `ds_read_b128` in flight and release each MFMA with a COUNTED `s_waitcnt lgkmcnt(N)`.  That is only valid while nothing else of the wave
 counts on lgkmcnt inside the window: scalar memory loads (s_load / s_buffer_load / s_memtime / s_memrealtime) share the counter and return
 out of order, so a compiler that re-materialised a kernel argument inside the window would let a partial wait release before the LDS
 operand has arrived -- silently.  This script compiles the device code to assembly and fails on any such instruction between the first
 ring read of a sequence and the `lgkmcnt(0)` wait that ends it.
 
-usage: check_ring_asm.py [file.hip ...]      (default: the three ring kernels; exit code 1 on a violation)"""
+usage: check_ring_asm.py [file.hip ...]      (default: the four ring sources; exit code 1 on a violation)"""
 import os
 import re
 import subprocess
@@ -16,6 +16,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "circuitvision_amd", "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+FLAGS = {"attention.hip": ("-fno-honor-nans",)}                 # what the Makefile's rule of a source adds to CXXFLAGS
 SMEM = re.compile(r"^\s*(s_load_|s_buffer_load_|s_memtime|s_memrealtime|s_scratch_load)")
 
 
@@ -67,7 +68,7 @@ def main(files):
     rc = 0
     for f in files:
         for tag, extra in (("fp16", ()), ("bf16", ("-DCVMI_OPERAND_BF16",))):
-            k, s, bad = check(device_asm(os.path.join(CSRC, f), extra))
+            k, s, bad = check(device_asm(os.path.join(CSRC, f), FLAGS.get(f, ()) + extra))
             print(f"{f} [{tag}]: {k} functions, {s} ring sequences, {len(bad)} scalar-memory instructions inside a ring window")
             for func, ln, t in bad[:10]:
                 print(f"  {func} line {ln}: {t}")
@@ -76,4 +77,4 @@ def main(files):
 
 
 if __name__ == "__main__":
-    sys.exit(main(sys.argv[1:] or ["tok_linear16.hip", "hiera_mlp.hip", "tok_linear.hip"]))
+    sys.exit(main(sys.argv[1:] or ["tok_linear16.hip", "hiera_mlp.hip", "tok_linear.hip", "attention.hip"]))
