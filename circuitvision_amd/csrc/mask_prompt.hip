@@ -13,6 +13,10 @@
 //                              cvmi_mask_prompt_embed_pairs runs the same kernel for pairs whose images a device table names (prompt lists:
 //                              pair i belongs to image pair_image[i] instead of i / rep).
 //   multimask_out_kernel       the multimask tail: tokens 1..3 of masks4 / iou4 as contiguous [n, 3, P] / [n, 3] (sibling of select_mask_kernel).
+//   best_candidate_kernel      mask feedback between two decoder passes (upstream's recipe for ambiguous prompts): per pair the logits of the
+//                              candidate with the highest predicted IoU, copied to the next pass's mask_in.  Every workgroup of a pair reads the
+//                              pair's NM IoUs itself (12 bytes, no second launch, no atomics) and then moves 16 bytes per lane and step of the
+//                              ONE selected plane: n * P * 4 bytes in, as many out.
 #include <algorithm>
 
 #include "common.hpp"
@@ -152,6 +156,30 @@ __global__ __launch_bounds__(NT) void multimask_out_kernel(const float* __restri
   }
 }
 
+// torch.argmax over NM values: the lowest index among equal maxima; a NaN counts as greater than every number (the first NaN wins)
+template <int NM> __device__ __forceinline__ int argmax_first(const float* __restrict__ v) {
+  int sel = 0;
+  float best = v[0];
+#pragma unroll
+  for (int k = 1; k < NM; ++k) {
+    const float x = v[k];
+    if (best == best && (x != x || x > best)) { best = x; sel = k; }
+  }
+  return sel;
+}
+
+template <int NM>
+__global__ __launch_bounds__(NT) void best_candidate_kernel(const float* __restrict__ low_res, const float* __restrict__ iou, float* __restrict__ mask_out,
+                                                            int* __restrict__ sel_out, int P4) {
+  // grid.y = pair; P4 = P / 4 16-byte groups per plane
+  const int b = blockIdx.y;
+  const int sel = argmax_first<NM>(iou + (size_t)b * NM);
+  if (sel_out && blockIdx.x == 0 && threadIdx.x == 0) sel_out[b] = sel;
+  const f32x4* src = (const f32x4*)low_res + ((size_t)b * NM + sel) * P4;
+  f32x4* dst = (f32x4*)mask_out + (size_t)b * P4;
+  for (int i = blockIdx.x * NT + threadIdx.x; i < P4; i += gridDim.x * NT) dst[i] = src[i];
+}
+
 }  // namespace
 
 // pair_image == nullptr: B * rep image-major pairs; else B pairs (rep = 1) whose images the device table names
@@ -195,6 +223,27 @@ extern "C" int cvmi_multimask_out(const float* masks, const float* iou, int iou_
   cvmi_note_kernel(vec ? "multimask_out_kernel<true>" : "multimask_out_kernel<false>");
   if (vec) hipLaunchKernelGGL(multimask_out_kernel<true>, g, b, 0, (hipStream_t)stream_, masks, iou, iou_ld, low_res3, iou3, (long long)P);
   else hipLaunchKernelGGL(multimask_out_kernel<false>, g, b, 0, (hipStream_t)stream_, masks, iou, iou_ld, low_res3, iou3, (long long)P);
+  CVMI_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int cvmi_best_candidate(const float* low_res, const float* iou, int NM, float* mask_out, int* sel_out, int n, int P, cvmi_stream_t stream_) {
+  CVMI_CHECK(NM == 1 || NM == 3, "best_candidate: NM = %d candidates: 1 or 3", NM);
+  CVMI_CHECK(n >= 0 && n <= 65535 && P > 0 && P % 4 == 0, "best_candidate: n = %d pairs of P = %d logits: n in 0 .. 65535, P a positive multiple of 4", n, P);
+  if (n == 0) return 0;
+  CVMI_CHECK(low_res && iou && mask_out, "best_candidate: bad arguments");
+  CVMI_CHECK((((uintptr_t)low_res | (uintptr_t)iou | (uintptr_t)mask_out) & 15) == 0 && ((uintptr_t)sel_out & 3) == 0,
+             "best_candidate: pointers must be 16-byte aligned (sel_out 4-byte)");
+  const int P4 = P / 4;
+  const dim3 g(std::min((P4 + NT - 1) / NT, 64), n), b(NT);
+  hipStream_t s = (hipStream_t)stream_;
+  if (NM == 3) {
+    cvmi_note_kernel("best_candidate_kernel<3>");
+    hipLaunchKernelGGL(best_candidate_kernel<3>, g, b, 0, s, low_res, iou, mask_out, sel_out, P4);
+  } else {
+    cvmi_note_kernel("best_candidate_kernel<1>");
+    hipLaunchKernelGGL(best_candidate_kernel<1>, g, b, 0, s, low_res, iou, mask_out, sel_out, P4);
+  }
   CVMI_LAUNCH_CHECK();
   return 0;
 }

@@ -39,15 +39,24 @@ class DecoderRoute(NamedTuple):
         """[(label, kind)] in launch order.  A second statement of the order in which `Sam2Plan._neck_decoder` emits, kept for the tests: the
         fixture test derives sequences from it without a GPU, and tests/test_decoder_route_gpu.py holds the emitter to it -- change the two
         together."""
+        return self.neck_launches() + self.decoder_launches()
+
+    def neck_launches(self):
+        """The launches up to and including `embed` -- behind the trunk they end an encode plan (`Sam2Plan(stage="encode")`, which adds the other
+        form of the embed GEMM); what `embed` writes is the seam: the predictor's image embedding."""
+        cast = lambda *names: [(n, "cast") for n in names]
+        out = []
+        for j in (0, 1):
+            out += cast(*([f"cast.s{j}"] if j in self.casts else [])) + [(f"feat_s{j}", "neck")]
+        return out + cast(*(f"cast.s{j}" for j in (2, 3) if j in self.casts)) + [("embed", "neck")]
+
+    def decoder_launches(self):
+        """Everything behind `embed`: all of a decode plan (`Sam2Plan(stage="decode")`)."""
         d = lambda *names: [(n, "decoder") for n in names]
         cast = lambda *names: [(n, "cast") for n in names]
         ln = lambda *names: [(n, "layernorm") for n in names]
         t2i = lambda p, castk: cast(f"{p}.castq", *([f"{p}.castk"] if castk else [])) + d(f"{p}.q", f"{p}.kv", f"{p}.attn", f"{p}.out")
-        out = []
-        for j in (0, 1):
-            out += cast(*([f"cast.s{j}"] if j in self.casts else [])) + [(f"feat_s{j}", "neck")]
-        out += cast(*(f"cast.s{j}" for j in (2, 3) if j in self.casts)) + [("embed", "neck")]
-        out += d(*([STREAM_LAUNCH[self.stream]] if self.stream in STREAM_LAUNCH else []), *(["prompt_tokens", "token_pe"] if self.tokens == "prompt" else []))
+        out = d(*([STREAM_LAUNCH[self.stream]] if self.stream in STREAM_LAUNCH else []), *(["prompt_tokens", "token_pe"] if self.tokens == "prompt" else []))
         for l in (0, 1):
             p = f"l{l}"
             out += cast(*([f"{p}.sa.cast"] if l else [])) + d(f"{p}.sa.qkv", f"{p}.sa.attn", f"{p}.sa.out") + ln(f"{p}.norm1")

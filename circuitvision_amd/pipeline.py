@@ -15,7 +15,8 @@ What it restates, batched and on the device, is the chain the reference runs per
 
 `prompts="learned"` is the reference's own segmentation (one mask per image from the wrapper's learned prompts);
 `prompts="boxes"` feeds the detector's boxes to `infer_masks(images, boxes)` (upstream box prompting, BASELINE configs[4]):
-one mask per detected component.
+one mask per detected component; `prompts="both"` returns the two from one `encode_images` per chunk (`Sam2Embeddings`: the trunk runs once, the
+learned-prompt decode and the box decode read its embeddings).
 
 Images are independent through both models, so a batch shards contiguously over ranks with no collective on the data path
 (`shard_range`); every rank returns the results of its own images, `gather_results` collects them on one rank when a single
@@ -61,9 +62,9 @@ class CircuitPipeline:
         max_prompts (prompts="boxes"): boxes per image handed to the segmenter; longer lists are cut, shorter ones filled with their first box (the
         tensor form `boxes[B,P,4]`).  None: every image's whole stage-2 box list as its own prompt list (`infer_masks` with lists: the decoder runs
         on the boxes there are, an image without boxes returns no mask).
-        nodes=True (learned prompts only): each result also carries get_node_connections' front end on its mask and boxes
+        nodes=True (prompts="learned" or "both"): each result also carries get_node_connections' front end on its mask and boxes
         (circuit_analyzer.py:1325-1365, wires.node_contours): "emptied_mask", "resized_bboxes", "enhanced", "contours".
-        nodes="connections" (learned prompts only): get_node_connections through to its node list (:1325-1583, wires.node_connections):
+        nodes="connections" (prompts="learned" or "both"): get_node_connections through to its node list (:1325-1583, wires.node_connections):
         the keys of nodes=True plus "nodes" and "connection_points".
         reclassify=True (any prompts mode): run_terminal_reclassification (analysis_pipeline.py:117-137, wires.reclassify_terminals) runs
         after the segmenter and before node analysis, on the image the segmenter saw and its boxes, with the detector's names: a 'terminal'
@@ -128,8 +129,10 @@ class CircuitPipeline:
 
     # ---- stage B: analysis_pipeline.py:168-225
     def segment(self, images, bboxes, prompts="learned"):
-        if prompts not in ("learned", "boxes"):
-            raise ValueError("prompts must be 'learned' or 'boxes'")
+        """prompts="both": per chunk ONE `encode_images` and two decodes of its embeddings -- the learned-prompt mask ("mask", "extent", "iou", as
+        "learned" returns them) and the per-box masks ("masks", "extents", "box_iou": what "boxes" returns as "masks", "extents", "iou")."""
+        if prompts not in ("learned", "boxes", "both"):
+            raise ValueError("prompts must be 'learned', 'boxes' or 'both'")
         crops, boxes_adj, infos = [], [], []
         for im, bb in zip(images, bboxes):
             info = None
@@ -154,22 +157,34 @@ class CircuitPipeline:
         return isinstance(self.det, YOLO) and isinstance(self.seg, SAM2Model) and isinstance(self.tr, SAM2Transforms)
 
     def _segment_chunk(self, crops, boxes_adj, prompts):
-        R = self.seg.image_size
         t = time.perf_counter()
         if self._product_objects():
             x = self.tr.forward_batch(crops, swap_rb=self.swap)           # the BGR2RGB of circuit_analyzer.py:343 as a channel index on the device
         else:
             x = self.tr.forward_batch([np.ascontiguousarray(im[..., ::-1]) if self.swap else im for im in crops])
         t = self._tick("segment.transform (channel swap + H2D + resize / normalise)", t)
-        out = []
-        if prompts == "learned":
-            hi, lo, iou = self.seg.infer_masks(x)
-            t = self._tick("segment.infer_masks (SAM 2.1 forward)", t)
-            for b, im in enumerate(crops):
-                u8, ext = self.tr.postprocess_to_mask(hi[b:b + 1], im.shape[:2])
-                out.append({"image": im, "bboxes": boxes_adj[b], "mask": u8[0, 0], "extent": ext[0], "iou": iou[b]})
-            self._tick("segment.postprocess (resize + threshold + u8 + extent + D2H of extents)", t)
+        if prompts == "both":                                            # the trunk once; both decodes read its embeddings
+            x = self.seg.encode_images(x)
+            t = self._tick("segment.encode_images (SAM 2.1 trunk + neck)", t)
+            out = self._segment_chunk_learned(crops, boxes_adj, x, t)
+            for r, rb in zip(out, self._segment_chunk_boxes(crops, boxes_adj, x, time.perf_counter())):
+                r.update(masks=rb["masks"], extents=rb["extents"], box_iou=rb["iou"])
             return out
+        return (self._segment_chunk_learned if prompts == "learned" else self._segment_chunk_boxes)(crops, boxes_adj, x, t)
+
+    def _segment_chunk_learned(self, crops, boxes_adj, x, t):
+        """x: the transformed images, or their embeddings."""
+        out = []
+        hi, lo, iou = self.seg.infer_masks(x)
+        t = self._tick("segment.infer_masks (SAM 2.1 forward)", t)
+        for b, im in enumerate(crops):
+            u8, ext = self.tr.postprocess_to_mask(hi[b:b + 1], im.shape[:2])
+            out.append({"image": im, "bboxes": boxes_adj[b], "mask": u8[0, 0], "extent": ext[0], "iou": iou[b]})
+        self._tick("segment.postprocess (resize + threshold + u8 + extent + D2H of extents)", t)
+        return out
+
+    def _segment_chunk_boxes(self, crops, boxes_adj, x, t):
+        R, out = self.seg.image_size, []
         if self.max_prompts is None:
             return self._segment_chunk_lists(crops, boxes_adj, x, t)
         P = self.max_prompts
@@ -230,8 +245,8 @@ class CircuitPipeline:
     def run_batch(self, images, prompts="learned", rank=0, world=1):
         """The share [lo, hi) of `images` that belongs to `rank`: detection, stage-2 NMS, (crop), segmentation.
         Returns [(global image index, result dict)]."""
-        if self.nodes and prompts != "learned":
-            raise ValueError("nodes=True needs prompts='learned': node analysis reads the one mask per image of the learned prompts")
+        if self.nodes and prompts not in ("learned", "both"):
+            raise ValueError("nodes=True needs prompts='learned' or 'both': node analysis reads the one mask per image of the learned prompts")
         lo, hi = shard_range(len(images), rank, world)
         mine = list(images[lo:hi])
         if not mine:

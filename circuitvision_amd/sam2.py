@@ -476,16 +476,29 @@ class Sam2Plan:
     (device int32 [cap], written beside `coords` / `labels` / `mask_in` before each run; every value must lie in [0, B) -- the kernels read
     the table as it is): any number of prompts per image, in any order.  Everything that finds a pair's image as b / P in a prompts = P plan
     reads the table instead (the gather in the place of the repeat pass, layer 0's shared tensors, the up1 / up2 residuals); the table is
-    data, so one captured plan serves every distribution of `cap` pairs over the B images."""
+    data, so one captured plan serves every distribution of `cap` pairs over the B images.
+    stage: "full" (default) is all of the above in one plan.  The other two cut it at the seam between `embed` and the first decoder launch -- the
+    predictor's set_image / predict split:
+      "encode"  stem, Hiera blocks, neck and BOTH forms of the embed GEMM (no prompt arguments): `feat_s0`, `feat_s1`, `emb` (the prompted form; None
+                for a checkpoint without a prompt encoder) and `keys0` (the learned-prompt form) are its outputs
+      "decode"  no `x_in`, no trunk, no neck: `feat_s0`, `feat_s1` and `emb` (prompted routes) or `keys0` (the `dense` stream) are INPUT buffers of
+                the shapes and types the full plan has there, written by the caller before each run; the launches are the route's
+                `decoder_launches()`, emitted by the same functions.  The decoder updates `keys0` in place: it is re-staged before EVERY run,
+                the one `capture()` makes included."""
 
     def __init__(self, wt, B, stream, dynamic_multimask_via_stability=True, prompts=0, points=3, high_res=True, attn="16", mask_prompt=False,
-                 multimask=False, pairs=0):
+                 multimask=False, pairs=0, stage="full"):
         """attn = "fp8" (16-bit plans only; BASELINE configs[4]): the AV contraction of Hiera's 256-key windows and global blocks runs on the
         block-scaled fp8 MFMA (cvmi_attn_desc.av_fp8); "16": operands in the plan's 16-bit type (default)."""
         self.wt, self.B, self.dt, self.dev = wt, B, wt.dtype, wt.device
         if attn not in ("16", "fp8") or (attn == "fp8" and not is16(wt.dtype)):
             raise ValueError("attn must be '16' or 'fp8' (fp8 needs an fp16 / bf16 plan)")
         self.av_fp8 = 1 if attn == "fp8" else 0
+        if stage not in ("full", "encode", "decode"):
+            raise ValueError("stage must be 'full', 'encode' or 'decode'")
+        if stage == "encode" and (prompts or pairs or mask_prompt or multimask):
+            raise ValueError("an encode plan takes no prompt arguments (it writes both forms of the embedding)")
+        self.stage = stage
         self.sw = sam_switches()._replace(**{f: getattr(wt.sw, f) for f in WEIGHT_SWITCHES})      # plan-level switches as set now, weight-level as packed
         self.P, self.K = prompts, points
         # everything after the trunk is routed here (the route checks the prompt arguments), before anything is allocated; _neck_decoder emits it
@@ -525,6 +538,8 @@ class Sam2Plan:
     def _build(self):
         wt, B = self.wt, self.B
         R = wt.image_size
+        if self.stage == "decode":
+            return self._decode_inputs(self.droute)
         g = R // 4
         self.x_in = Buf(B, R, R, 3, self.dt, self.dev, zero=True)
         E = wt.hiera["embed_dim"]
@@ -548,6 +563,12 @@ class Sam2Plan:
                 stage_out.append(x)
         self.stage_out = stage_out
         self._neck_decoder(stage_out)
+
+    def _decode_inputs(self, r):
+        """A decode plan's side of the seam: the buffers the full plan's neck and embed GEMM write, here inputs the caller fills."""
+        self.feat_s0, self.feat_s1 = self.buf(r.f0, r.f0, 32, zero=True), self.buf(r.f1, r.f1, 64, zero=True)
+        emb = self.buf(r.fs, r.fs, 256, F32, zero=True) if r.prompted else None
+        self._decoder(r, emb, None if r.prompted else self._bufd(r.fs, r.fs, 256, F32, zero=True))
 
     # ---- one Hiera block ---------------------------------------------------------------------------------
     def _block(self, i, r, x, H, W, stats_in):
@@ -634,12 +655,22 @@ class Sam2Plan:
 
     # ---- neck + mask decoder + tail: emits what self.droute (decoder_route.DecoderRoute) says ----------------------------------
     def _neck_decoder(self, st):
+        """Up to `embed` (route.neck_launches()), then -- unless this is an encode plan -- everything behind it (route.decoder_launches())."""
         r = self.droute
         self.feat_s0, self.feat_s1, s2, s3 = self._neck(st, r)
+        emb, keys = self._embed(r, s2, s3, "embed", "box" if r.prompted else "dense")
+        if self.stage == "encode":                     # the route is the learned-prompt one; the prompted form follows it
+            self.emb, self.keys0 = (self._embed(r, s2, s3, "embed_box", "box")[0] if self.wt.prompt_ok else None), keys
+            return
+        self._decoder(r, emb, keys)
+
+    def _decoder(self, r, emb, keys):
+        """emb: a prompted plan's per-image embedding, keys: the `dense` stream as the embed GEMM wrote it (the other is None)."""
+        self.emb = emb
         # pairs: the image of pair n is pair_image[n]; the launches that derive it as n / P in a prompts = P plan take the table instead
         self.pair_image = torch.zeros(r.NB, dtype=torch.int32, device=self.dev) if self.pairs else None
         pm = _PairMap(self.P, self.pair_image)
-        emb, keys, kn = self._image_stream(r, pm, s2, s3)
+        keys, kn = self._image_stream(r, pm, emb, keys)
         qn0, pe = self._tokens(r)
         # the two f32 residual streams -- tokens q (layer 0 REPLACES it, so it needs no init) and image `keys` -- with their operand-dtype copies
         s = SimpleNamespace(q=Buf(r.NB, 1, r.T, 256, F32, self.dev, zero=True), qn=self._bufd(1, r.T, 256, tag="qn"), emb=emb, keys=keys, kn=kn)
@@ -687,19 +718,27 @@ class Sam2Plan:
                 self.gemm(key, key, cast(j).view(), dst.view(), kind="neck")
         return feats + (cast(2), cast(3))
 
-    def _image_stream(self, r, pm, s2, s3):
-        """FPN level 2 (`embed`) and the launch r.stream names -> (emb: a prompted plan's per-image embedding, keys: the decoder's per-pair f32 image
-        stream, kn: its copy in the operand dtype -- allocated here, once; r.castk says which launches write it)."""
-        wt, dt, B, NB, lib, fs, f0, P = self.wt, self.dt, self.B, r.NB, _lib.load(), r.fs, r.f0, r.fs * r.fs
-        emb = self.buf(fs, fs, 256, F32) if r.prompted else None
-        keys, kn = self._bufd(fs, fs, 256, F32), self._bufd(fs, fs, 256, tag="kn")
+    def _embed(self, r, s2, s3, label, form):
+        """FPN level 2, the seam between an encode and a decode plan -> (emb, keys), one of them None.  form "dense": + the learned dense prompt,
+        straight into the decoder's image stream `keys`; "box": + no_mem_embed + no_mask_embed (both in the GEMM bias), per image, `emb`."""
         srcs = [(s2.view(), 0), (s3.view(), 1)]
-        if r.stream == "dense":            # FPN level 2 + learned dense prompt, straight into the stream
-            self.gemm("embed", "embed", srcs, keys.view(), res=_ConstView(wt.const["dense"], 256), res_mod=P, kind="neck")
-            return emb, keys, kn
-        # FPN level 2 + no_mem_embed + no_mask_embed (both in the GEMM bias), per image
-        self.gemm("embed", "embed_box", srcs, emb.view(), kind="neck")
-        # the launch that makes the per-pair stream of it ("shared": none, see DecoderRoute.stream); in a 16-bit plan it writes the operand copy too
+        if form == "dense":
+            keys = self._bufd(r.fs, r.fs, 256, F32)
+            self.gemm(label, "embed", srcs, keys.view(), res=_ConstView(self.wt.const["dense"], 256), res_mod=r.fs * r.fs, kind="neck")
+            return None, keys
+        emb = self.buf(r.fs, r.fs, 256, F32)
+        self.gemm(label, "embed_box", srcs, emb.view(), kind="neck")
+        return emb, None
+
+    def _image_stream(self, r, pm, emb, keys):
+        """The launch r.stream names behind `embed` -> (keys: the decoder's per-pair f32 image stream, kn: its copy in the operand dtype --
+        allocated here, once; r.castk says which launches write it)."""
+        wt, dt, B, NB, lib, fs, f0, P = self.wt, self.dt, self.B, r.NB, _lib.load(), r.fs, r.f0, r.fs * r.fs
+        kn = self._bufd(fs, fs, 256, tag="kn")
+        if r.stream == "dense":            # the embed GEMM wrote the stream itself
+            return keys, kn
+        keys = self._bufd(fs, fs, 256, F32)
+        # the launch that makes the per-pair stream of emb ("shared": none, see DecoderRoute.stream); in a 16-bit plan it writes the operand copy too
         kn16, copy16 = ((kn.t.data_ptr(), dt), NB * P * 256 * 2) if is16(dt) else ((None, F16), 0)
         if r.stream == "mask_prompt":      # keys = emb + mask_downscaling(mask_in) - no_mask_embed
             self.mask_in = torch.zeros(NB, f0, f0, dtype=torch.float32, device=self.dev)
@@ -714,7 +753,7 @@ class Sam2Plan:
         elif r.stream == "repeat":
             op_call(self.plan, "repeat_embed", "decoder", lib.cvmi_repeat_images, (emb.t.data_ptr(), keys.t.data_ptr(), P * 256 * 4, B, pm.rep),
                     keep=(emb, keys), bytes_=(B + NB) * P * 256 * 4)
-        return emb, keys, kn
+        return keys, kn
 
     def _tokens(self, r):
         """-> (the tokens layer 0 reads, in the operand dtype; pe(name, C): the residual arguments that add (token PE) @ W^T of constant `name`, C

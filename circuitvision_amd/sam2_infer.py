@@ -2,6 +2,7 @@
 (`from .sam2_infer import SAM2Transforms, get_modified_sam2, device`, circuit_analyzer.py:17-21),
 backed by the cvmi355 HIP kernels.  See SURVEY.md 8(b) for the exact surface the callers rely on.
 """
+import itertools
 import os
 import threading
 from types import SimpleNamespace
@@ -105,6 +106,81 @@ def pack_prompt_lists(B, R, boxes=None, points=None, point_labels=None, mask_inp
     return dict(sizes=sizes, N=N, cap=cap, K=K, coords=coords, labels=labels, pair_image=pair_image, has_mask=mask_input is not None)
 
 
+_WEIGHTS_IDS = itertools.count(1)                # identity of one packing of weights (`SAM2Model.load_params`), unique in the process
+
+
+class Sam2Embeddings:
+    """What `SAM2Model.encode_images` returns and `infer_masks` takes in the place of images (upstream's set_image / predict split): the tensors
+    at the seam between the encoder and the mask decoder, owned by the caller --
+      feat_s0 [B, R/4, R/4, 32], feat_s1 [B, R/8, R/8, 64] in the model's dtype (FPN levels 0 / 1 behind conv_s0 / conv_s1),
+      emb   f32 [B, R/16, R/16, 256]: the image embedding box / click / mask prompts decode from (None: a checkpoint without a prompt encoder),
+      dense f32 [B, R/16, R/16, 256]: the same plus the learned dense prompt, the learned-prompt decode's image stream
+    -- with image_size, dtype (the CVMI dtype of the model) and weights_id, the identity of the packed weights that made them.  A plain container
+    that works on tensors of any device: `len()`, `nbytes`, `e[i]` / `e[a:b]` / `e[[i, j]]` (a new Sam2Embeddings; an int keeps the batch
+    axis) and `Sam2Embeddings.cat` build batches out of cached images."""
+    TENSORS = ("feat_s0", "feat_s1", "emb", "dense")
+
+    def __init__(self, feat_s0, feat_s1, emb, dense, image_size, dtype, weights_id):
+        self.feat_s0, self.feat_s1, self.emb, self.dense = feat_s0, feat_s1, emb, dense
+        self.image_size, self.dtype, self.weights_id = int(image_size), dtype, weights_id
+        f0, fs = self.image_size // 4, self.image_size // 16
+        B = feat_s0.shape[0]
+        want = dict(feat_s0=(B, f0, f0, 32), feat_s1=(B, f0 // 2, f0 // 2, 64), emb=(B, fs, fs, 256), dense=(B, fs, fs, 256))
+        for name, t in self.tensors():
+            if tuple(t.shape) != want[name]:
+                raise ValueError(f"Sam2Embeddings.{name}: shape {tuple(t.shape)}, expected {want[name]}")
+
+    def tensors(self):
+        return [(n, getattr(self, n)) for n in self.TENSORS if getattr(self, n) is not None]
+
+    def signature(self):
+        """What two embeddings must share to be batched together or decoded by a model."""
+        return (self.weights_id, self.dtype, self.image_size, self.emb is not None)
+
+    def __len__(self):
+        return int(self.feat_s0.shape[0])
+
+    @property
+    def device(self):
+        return self.feat_s0.device
+
+    @property
+    def nbytes(self):
+        return sum(t.numel() * t.element_size() for _, t in self.tensors())
+
+    def _like(self, fn):
+        return Sam2Embeddings(*(fn(getattr(self, n)) if getattr(self, n) is not None else None for n in self.TENSORS),
+                              self.image_size, self.dtype, self.weights_id)
+
+    def __getitem__(self, idx):
+        if isinstance(idx, bool) or not isinstance(idx, (int, slice, list, tuple)):
+            raise TypeError("Sam2Embeddings index: an int, a slice or a list of ints")
+        B = len(self)
+        if isinstance(idx, int):
+            if not -B <= idx < B:
+                raise IndexError(f"image {idx} of {B}")
+            idx = slice(idx % B, idx % B + 1)
+        if isinstance(idx, slice):
+            return self._like(lambda t: t[idx])
+        rows = [int(i) for i in idx]
+        if any(not -B <= i < B for i in rows):
+            raise IndexError(f"images {rows} of {B}")
+        return self._like(lambda t: t[torch.tensor(rows, dtype=torch.long, device=t.device)])
+
+    @staticmethod
+    def cat(parts):
+        parts = list(parts)
+        if not parts:
+            raise ValueError("Sam2Embeddings.cat of an empty list")
+        if any(not isinstance(e, Sam2Embeddings) for e in parts):
+            raise TypeError("Sam2Embeddings.cat takes Sam2Embeddings")
+        if any(e.signature() != parts[0].signature() for e in parts[1:]):
+            raise ValueError("Sam2Embeddings.cat: embeddings of different weights, dtypes or image sizes do not mix")
+        first = parts[0]
+        return Sam2Embeddings(*(torch.cat([getattr(e, n) for e in parts]) if getattr(first, n) is not None else None for n in first.TENSORS),
+                              first.image_size, first.dtype, first.weights_id)
+
+
 class SAM2Model:
     """What `get_modified_sam2(...)` returns: `.load_state_dict`, `.eval`, `.sam2_model.image_size`,
     `__call__(x) -> (high_res, low_res, iou)` (sam2_infer.py:220-275), plus `infer_masks`."""
@@ -122,7 +198,7 @@ class SAM2Model:
         self.lora = (lora_rank, lora_alpha)
         self.dynamic = dynamic_multimask_via_stability
         self.sam2_model = SimpleNamespace(image_size=image_size)          # circuit_analyzer.py:237-240 reads .sam2_model.image_size
-        self.weights, self.params, self._pending = None, None, None
+        self.weights, self.params, self._pending, self.weights_id = None, None, None, 0
         self.stream = torch.cuda.Stream(device=dev)
         self._slot_streams = {0: self.stream}                               # plan slot -> stream (slot 1: a second plan instance on its own stream, so
         self._plans = {}                                                    # that two independent batches run side by side: CircuitPipeline)
@@ -135,6 +211,7 @@ class SAM2Model:
         self.params, self._pending = params, None
         with torch.cuda.device(self.dev):
             self.weights = Sam2Weights(params, self.hiera, self.image_size, self.dtype, self.dev, **self.cfg)
+        self.weights_id = next(_WEIGHTS_IDS)                  # embeddings of an earlier packing are refused (`Sam2Embeddings.weights_id`)
         self._plans.clear()
         return self
 
@@ -162,14 +239,15 @@ class SAM2Model:
             raise RuntimeError("SAM2 weights not loaded (call load_state_dict first)")
         return self.weights
 
-    def plan(self, B, prompts=0, high_res=True, points=3, slot=0, mask_prompt=False, multimask=False, pairs=0):
-        """pairs = cap: the plan of `cap` (image, prompt) pairs with a pair-to-image table (prompt lists); keyed on cap, not on the pair count."""
+    def plan(self, B, prompts=0, high_res=True, points=3, slot=0, mask_prompt=False, multimask=False, pairs=0, stage="full"):
+        """pairs = cap: the plan of `cap` (image, prompt) pairs with a pair-to-image table (prompt lists); keyed on cap, not on the pair count.
+        stage: "full", or one side of the encode / decode split (`Sam2Plan`); the key of a full plan carries no stage."""
         wt = self._packed_weights()
-        key = (B, prompts, high_res, points if (prompts or pairs) else 0, slot, bool(mask_prompt), bool(multimask), pairs)
+        key = (B, prompts, high_res, points if (prompts or pairs) else 0, slot, bool(mask_prompt), bool(multimask), pairs) + ((stage,) if stage != "full" else ())
         if key not in self._plans:
             with torch.cuda.device(self.dev):
                 self._plans[key] = Sam2Plan(wt, B, self.slot_stream(slot), self.dynamic, prompts=prompts, points=points, high_res=high_res, attn=self.attn,
-                                            mask_prompt=mask_prompt, multimask=multimask, pairs=pairs)
+                                            mask_prompt=mask_prompt, multimask=multimask, pairs=pairs, stage=stage)
         return self._plans[key]
 
     def _stage_images(self, p, images):
@@ -189,19 +267,65 @@ class SAM2Model:
             _lib.check(lib.cvmi_nchw_to_nhwc(x.data_ptr(), src_dt, p.x_in.t.data_ptr(), self.dtype, 3, B, 3, self.image_size, self.image_size, sp), "nchw_to_nhwc")
         return x                                              # keep alive until the stream has consumed it
 
-    def _run(self, p, images, outs, before=None):
+    @staticmethod
+    def _stage_embeddings(p, e):
+        """D2D copies of embeddings into a decode plan's input buffers, on the model's stream like `_stage_images`."""
+        p.feat_s0.t.copy_(e.feat_s0, non_blocking=True)
+        p.feat_s1.t.copy_(e.feat_s1, non_blocking=True)
+        if p.droute.prompted:
+            p.emb.t.copy_(e.emb, non_blocking=True)
+        else:
+            p.keys0.t.copy_(e.dense, non_blocking=True)      # the decoder updates its image stream in place: staged before every run
+
+    def _seam(self, p):
+        """The seam tensors of an encode plan as (un-owned) embeddings."""
+        return Sam2Embeddings(p.feat_s0.t, p.feat_s1.t, p.emb.t if p.emb is not None else None, p.keys0.t, self.image_size, self.dtype, self.weights_id)
+
+    def _run(self, p, src, outs, before=None, refine=(), pairs=0):
         """Stage -> replay the plan -> copy `outs` = [(plan tensor, fresh tensor)] -- all on the model's stream, which first waits for the
         caller's current stream and is synchronised before returning (the reference's call is synchronous).  The output copies are
         part of the stream's order, so the next caller's replay (another session thread, app.py:134) cannot overwrite the plan's
-        buffers under them."""
+        buffers under them.
+        src: images for a full plan, or `Sam2Embeddings` for a decode plan (copied into its inputs first, then `before`).
+        refine: the decode plans of the mask-feedback passes that follow p (itself a decode plan then; with images the encode plan runs in
+        front, once): each gets the embeddings and p's prompts, and `mask_in` from its predecessor's low_res / iou through
+        cvmi_best_candidate over the `pairs` real pairs, launched on the stream between the two replays."""
+        lib, sp = _lib.load(), self.stream.cuda_stream
         self.stream.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(self.stream):
+            keep, e = src, src if isinstance(src, Sam2Embeddings) else None
+            if e is not None or refine:
+                for q in (p,) + tuple(refine):
+                    if q.plan.graph is None:                  # capture's warm pass runs on the buffers as they are: in front of the staging
+                        q.plan.capture()
+            if e is None and refine:
+                enc = self.plan(src.shape[0], stage="encode")
+                keep = self._stage_images(enc, src)
+                enc.plan.run()
+                e = self._seam(enc)
+            if e is not None:
+                self._stage_embeddings(p, e)
             if before is not None:
                 before()
-            keep = self._stage_images(p, images)
+            if e is None:
+                keep = self._stage_images(p, src)
             p.plan.run()
-            for src, dst in outs:
-                dst.copy_(src, non_blocking=True)
+            prev, fed = p, {id(p)}
+            for q in refine:
+                if id(q) not in fed:                          # inputs no replay writes: once per plan
+                    fed.add(id(q))
+                    self._stage_embeddings(q, e)
+                    q.coords.copy_(p.coords, non_blocking=True)
+                    q.labels.copy_(p.labels, non_blocking=True)
+                    if q.pair_image is not None:
+                        q.pair_image.copy_(p.pair_image, non_blocking=True)
+                NM, f0 = prev.low_res.shape[1], prev.low_res.shape[2]
+                _lib.check(lib.cvmi_best_candidate(prev.low_res.data_ptr(), prev.iou.data_ptr(), NM, q.mask_in.data_ptr(), None, pairs, f0 * f0, sp), "best_candidate")
+                q.mask_in[pairs:].zero_()                     # the padding rows of a pairs = cap plan
+                q.plan.run()
+                prev = q
+            for a, b in outs:
+                b.copy_(a, non_blocking=True)
         self.stream.synchronize()
         del keep
 
@@ -209,20 +333,46 @@ class SAM2Model:
         if not (torch.is_tensor(images) and images.dim() == 4 and images.shape[1] == 3 and images.shape[2] == images.shape[3] == self.image_size):
             raise ValueError(f"expected a [B,3,{self.image_size},{self.image_size}] tensor")
 
-    def __call__(self, images, points=None, point_labels=None, masks_prompt=None, multimask_output=False):
+    def _check_src(self, src):
+        """images [B,3,R,R] or the `Sam2Embeddings` of this model's weights -> B."""
+        if not isinstance(src, Sam2Embeddings):
+            self._check_images(src)
+            return src.shape[0]
+        self._packed_weights()
+        if src.signature()[:3] != (self.weights_id, self.dtype, self.image_size):
+            raise ValueError("these embeddings were made by other weights, another dtype or another image size (encode_images of THIS model)")
+        if len(src) == 0 or any(not t.is_cuda for _, t in src.tensors()):
+            raise ValueError("embeddings to decode must be a non-empty batch on the device")
+        return len(src)
+
+    def encode_images(self, images):
+        """upstream `SAM2ImagePredictor.set_image`: images [B,3,R,R] (as `infer_masks` takes them) -> `Sam2Embeddings`, which `infer_masks`
+        accepts in the place of images, any number of times, with any prompts: only the mask decoder runs then (bit for bit what the one-shot
+        call computes).  The tensors are the caller's; the model keeps nothing of them."""
         self._check_images(images)
+        with self._lock, torch.cuda.device(self.dev):
+            p = self.plan(images.shape[0], stage="encode")
+            seam = self._seam(p)
+            out = seam._like(torch.empty_like)                                        # the caller's tensors, as in __call__
+            self._run(p, images, [(a, getattr(out, n)) for n, a in seam.tensors()])
+            return out
+
+    def __call__(self, images, points=None, point_labels=None, masks_prompt=None, multimask_output=False):
+        B = self._check_src(images)
         if multimask_output:
             raise NotImplementedError("the wrapper always runs multimask_output=False (sam2_infer.py:257)")
         with self._lock, torch.cuda.device(self.dev):
-            p = self.plan(images.shape[0])
+            p = self.plan(B, stage="decode" if isinstance(images, Sam2Embeddings) else "full")
             out = [torch.empty_like(t) for t in (p.high_res, p.low_res, p.iou)]       # the caller's tensors (its allocator pool, not the model stream's)
             self._run(p, images, list(zip((p.high_res, p.low_res, p.iou), out)))
             return tuple(out)
 
     forward = __call__
 
-    def infer_masks(self, images, boxes=None, return_high_res=True, points=None, point_labels=None, mask_input=None, multimask_output=False):
-        """Batched segmentation entry point (north_star).  images [B,3,R,R].
+    def infer_masks(self, images, boxes=None, return_high_res=True, points=None, point_labels=None, mask_input=None, multimask_output=False,
+                    refine_steps=0):
+        """Batched segmentation entry point (north_star).  images [B,3,R,R], or the `Sam2Embeddings` `encode_images` made of them (the trunk
+        and the neck are then not run again: every prompt form below decodes from them, with the same checks and the same results).
         No prompt: exactly `SAM2ImageWrapper.forward` (learned prompts) -> (high_res [B,1,R,R], low_res [B,1,R/4,R/4], iou [B,1]).
         boxes [B,P,4] (xyxy in the R x R input pixel space, e.g. detector boxes scaled by R / original size) and / or
         points [B,P,K,2] (x, y) with point_labels [B,P,K] (1 foreground click, 0 background click, -1 "not a point" padding token,
@@ -238,15 +388,20 @@ class SAM2Model:
         [P_b,R/4,R/4] -- every image its own number of prompts, 0 included; all lists given agree on B and on every P_b.  The decoder runs on
         the N = sum P_b pairs (rounded up to a multiple of `pair_bucket`), nothing is padded per image.  Lists in, lists out: high_res,
         low_res and iou are each a list of B tensors ([P_b,R,R], [P_b,R/4,R/4], [P_b]; a candidate axis of 3 after P_b with
-        multimask_output=True), `torch.split` views of one packed [N,...] allocation."""
+        multimask_output=True), `torch.split` views of one packed [N,...] allocation.
+        refine_steps = k > 0 (needs a prompt and a checkpoint with mask_downscaling): upstream's recipe for ambiguous prompts on the device.
+        The call as given is pass 1; k single-mask passes on the same prompts follow, each with the previous pass's best candidate (the
+        highest predicted IoU, cvmi_best_candidate) as its mask prompt.  The trunk runs once, nothing goes through the host, and the
+        last pass's (high_res or None, low_res, iou) come back in the single-mask shapes, whatever multimask_output was."""
+        if not isinstance(refine_steps, int) or isinstance(refine_steps, bool) or refine_steps < 0:
+            raise ValueError("refine_steps must be an int >= 0")
         if _is_list(boxes) or _is_list(points) or _is_list(point_labels) or _is_list(mask_input):
-            return self._infer_masks_lists(images, boxes, return_high_res, points, point_labels, mask_input, multimask_output)
+            return self._infer_masks_lists(images, boxes, return_high_res, points, point_labels, mask_input, multimask_output, refine_steps)
         if boxes is None and points is None:
-            if mask_input is not None:
-                raise ValueError("mask_input needs boxes and / or points (a mask-only prompt is not built)")
+            if mask_input is not None or refine_steps:
+                raise ValueError("mask_input / refine_steps need boxes and / or points (a mask-only prompt is not built)")
             return self(images, multimask_output=multimask_output)
-        self._check_images(images)
-        B = images.shape[0]
+        B = self._check_src(images)
         bx = pts = None
         if boxes is not None:
             bx = torch.as_tensor(boxes, dtype=torch.float32)
@@ -266,62 +421,64 @@ class SAM2Model:
         P = (bx if bx is not None else pts).shape[1]
         nb, nk = (2 if bx is not None else 0), (pts.shape[2] if pts is not None else 0)
         K = nb + nk + 1                                            # + the closing padding point
-        R, f0 = self.image_size, self.image_size // 4
+        f0 = self.image_size // 4
         mk = None
         if mask_input is not None:
             mk = torch.as_tensor(mask_input)
             if not mk.is_floating_point() or tuple(mk.shape) != (B, P, f0, f0):
                 raise ValueError(f"mask_input must be float [B={B}, P={P}, {f0}, {f0}] low-res logits, got {mk.dtype} {tuple(mk.shape)}")
-        NM = 3 if multimask_output else 1
-        with self._lock, torch.cuda.device(self.dev):
-            if mk is not None and not self._packed_weights().mask_prompt_ok:
-                raise RuntimeError("this checkpoint carries no sam_prompt_encoder.mask_downscaling tensors: mask_input is unavailable")
-            p = self.plan(B, prompts=P, high_res=return_high_res, points=K, mask_prompt=mk is not None, multimask=bool(multimask_output))
-            coords = torch.zeros(B * P, K, 2, dtype=torch.float32)
-            labels = torch.full((B * P, K), -1, dtype=torch.int32)
-            if bx is not None:
-                coords[:, :2] = bx.reshape(B * P, 2, 2)
-                labels[:, 0], labels[:, 1] = 2, 3
-            if pts is not None:
-                coords[:, nb:nb + nk] = pts.reshape(B * P, nk, 2)
-                labels[:, nb:nb + nk] = lab.reshape(B * P, nk)
-            def prompts_in():                                          # on the model's stream, in front of the replay that reads them
-                p.coords.copy_(coords, non_blocking=False)
-                p.labels.copy_(labels, non_blocking=False)
-                if mk is not None:
-                    p.mask_in.copy_(mk.reshape(B * P, f0, f0), non_blocking=False)
-            shp = (B, P, NM) if multimask_output else (B, P)
-            lo, iou = torch.empty(*shp, f0, f0, dtype=torch.float32, device=self.dev), torch.empty(*shp, dtype=torch.float32, device=self.dev)
-            hi = torch.empty(*shp, R, R, dtype=torch.float32, device=self.dev) if return_high_res else None
-            outs = [(p.low_res.view(*shp, f0, f0), lo), (p.iou.view(*shp), iou)] + ([(p.high_res.view(*shp, R, R), hi)] if return_high_res else [])
-            self._run(p, images, outs, before=prompts_in)
-            return hi, lo, iou
+        coords = torch.zeros(B * P, K, 2, dtype=torch.float32)
+        labels = torch.full((B * P, K), -1, dtype=torch.int32)
+        if bx is not None:
+            coords[:, :2] = bx.reshape(B * P, 2, 2)
+            labels[:, 0], labels[:, 1] = 2, 3
+        if pts is not None:
+            coords[:, nb:nb + nk] = pts.reshape(B * P, nk, 2)
+            labels[:, nb:nb + nk] = lab.reshape(B * P, nk)
+        pk = dict(kw=dict(prompts=P), N=B * P, K=K, coords=coords, labels=labels, pair_image=None, mask=mk.reshape(B * P, f0, f0) if mk is not None else None)
+        hi, lo, iou = self._prompt_passes(images, B, pk, return_high_res, multimask_output, refine_steps)
+        return tuple(t.view(B, P, *t.shape[1:]) if t is not None else None for t in (hi, lo, iou))
 
-    def _infer_masks_lists(self, images, boxes, return_high_res, points, point_labels, mask_input, multimask_output):
-        """`infer_masks` with one prompt list per image: pack on the host (`pack_prompt_lists`), replay the `pairs=cap` plan, split."""
-        self._check_images(images)
-        B, R, f0 = images.shape[0], self.image_size, self.image_size // 4
-        pk = pack_prompt_lists(B, R, boxes, points, point_labels, mask_input, self.pair_bucket)
-        N, cap, sizes = pk["N"], pk["cap"], pk["sizes"]
-        NM = 3 if multimask_output else 1
+    def _prompt_passes(self, src, B, pk, return_high_res, multimask_output, refine_steps):
+        """The prompted decode of N (image, prompt) pairs packed on the host -- pk: kw = the plan's prompts=P or pairs=cap, N, K, coords, labels,
+        pair_image (pairs plans), mask ([N, R/4, R/4], or a list of tensors that concatenate to it, or None) -- and the refine_steps mask-feedback
+        passes behind it -> (high_res or None, low_res, iou) with N in front."""
+        R, f0, N = self.image_size, self.image_size // 4, pk["N"]
+        masked, multimask = pk["mask"] is not None, bool(multimask_output)
         with self._lock, torch.cuda.device(self.dev):
-            if pk["has_mask"] and not self._packed_weights().mask_prompt_ok:
+            if (masked or refine_steps) and not self._packed_weights().mask_prompt_ok:
                 raise RuntimeError("this checkpoint carries no sam_prompt_encoder.mask_downscaling tensors: mask_input is unavailable")
-            p = self.plan(B, high_res=return_high_res, points=pk["K"], mask_prompt=pk["has_mask"], multimask=bool(multimask_output), pairs=cap)
+            stage = "decode" if refine_steps or isinstance(src, Sam2Embeddings) else "full"       # one-shot use: one graph and no copies
+            plan = lambda high_res, mask_prompt, multi: self.plan(B, high_res=high_res, points=pk["K"], mask_prompt=mask_prompt, multimask=multi, stage=stage,
+                                                                  **pk["kw"])
+            p = plan(return_high_res and not refine_steps, masked, multimask)
+            refine = [plan(return_high_res and i == refine_steps - 1, True, False) for i in range(refine_steps)]
+            last = refine[-1] if refine else p
 
             def prompts_in():                                          # on the model's stream, in front of the replay that reads them
                 p.coords.copy_(pk["coords"], non_blocking=False)
                 p.labels.copy_(pk["labels"], non_blocking=False)
-                p.pair_image.copy_(pk["pair_image"], non_blocking=False)
-                if pk["has_mask"]:
-                    p.mask_in[:N].copy_(torch.cat([t.detach().to(self.dev, torch.float32) for t in mask_input]), non_blocking=False)
+                if pk["pair_image"] is not None:
+                    p.pair_image.copy_(pk["pair_image"], non_blocking=False)
+                if masked:
+                    mask = pk["mask"]
+                    p.mask_in[:N].copy_(torch.cat([t.detach().to(self.dev, torch.float32) for t in mask]) if _is_list(mask) else mask, non_blocking=False)
                     p.mask_in[N:].zero_()
-            shp = (N, NM) if multimask_output else (N,)
+            shp = (N, 3) if multimask and not refine else (N,)
             lo, iou = torch.empty(*shp, f0, f0, dtype=torch.float32, device=self.dev), torch.empty(*shp, dtype=torch.float32, device=self.dev)
             hi = torch.empty(*shp, R, R, dtype=torch.float32, device=self.dev) if return_high_res else None
-            outs = [(p.low_res[:N].view(*shp, f0, f0), lo), (p.iou[:N].view(*shp), iou)] + ([(p.high_res[:N].view(*shp, R, R), hi)] if return_high_res else [])
-            self._run(p, images, outs, before=prompts_in)
-            return (list(torch.split(hi, sizes)) if hi is not None else None), list(torch.split(lo, sizes)), list(torch.split(iou, sizes))
+            outs = [(last.low_res[:N].view(*shp, f0, f0), lo), (last.iou[:N].view(*shp), iou)] + ([(last.high_res[:N].view(*shp, R, R), hi)] if return_high_res else [])
+            self._run(p, src, outs, before=prompts_in, refine=refine, pairs=N)
+            return hi, lo, iou
+
+    def _infer_masks_lists(self, images, boxes, return_high_res, points, point_labels, mask_input, multimask_output, refine_steps=0):
+        """`infer_masks` with one prompt list per image: pack on the host (`pack_prompt_lists`), replay the `pairs=cap` plan, split."""
+        B = self._check_src(images)
+        pk = pack_prompt_lists(B, self.image_size, boxes, points, point_labels, mask_input, self.pair_bucket)
+        sizes = pk["sizes"]
+        pk.update(kw=dict(pairs=pk["cap"]), mask=mask_input if pk["has_mask"] else None)
+        hi, lo, iou = self._prompt_passes(images, B, pk, return_high_res, multimask_output, refine_steps)
+        return (list(torch.split(hi, sizes)) if hi is not None else None), list(torch.split(lo, sizes)), list(torch.split(iou, sizes))
 
 
 def get_modified_sam2(model_cfg_path, checkpoint_path, device="cuda", use_high_res_features=True, use_peft=True, lora_rank=12,

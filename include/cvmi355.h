@@ -436,6 +436,15 @@ int cvmi_select_mask(const float* masks, const int* areas, const float* iou, int
 int cvmi_multimask_out(const float* masks, const float* iou, int iou_ld, float* low_res3, float* iou3, int n, int P,
                        cvmi_stream_t stream);
 
+/* Mask feedback between two decoder passes (upstream's recipe for ambiguous prompts: multimask_output=True, then the best candidate's logits as
+ * mask_input of a single-mask pass on the same prompts): mask_out[i] = low_res[i, argmax(iou[i, :])] for the n pairs, in one launch.
+ *   low_res  f32 [n, NM, P] and iou f32 [n, NM], NM = 1 or 3 (what a single-mask / multimask plan leaves in low_res / iou)
+ *   mask_out f32 [n, P] (the next plan's mask_in);  sel_out i32 [n] the selected candidate, or NULL
+ * The selection is torch.argmax's: the lowest index among equal maxima, and a NaN counts as greater than every number (the first NaN wins).
+ * NM = 1 always selects candidate 0: the call is a copy.  Only the selected plane is read: n * P * 4 bytes in, as many out, 16 bytes per access.
+ * P must be a multiple of 4, low_res / iou / mask_out 16-byte aligned (sel_out 4-byte), n <= 65535; n == 0 returns 0 without a launch. */
+int cvmi_best_candidate(const float* low_res, const float* iou, int NM, float* mask_out, int* sel_out, int n, int P, cvmi_stream_t stream);
+
 /* Mask prompts (upstream PromptEncoder._embed_masks + SAM2ImagePredictor._predict with mask_input): the decoder's image stream of the
  * B * rep (image, prompt) pairs, image-major (pair i belongs to image i / rep), in one launch --
  *   keys[i] = emb[i / rep] + mask_downscaling(mask[i]) - no_mask_embed
