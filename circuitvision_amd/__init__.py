@@ -7,11 +7,14 @@ there is no CPU or PyTorch-eager fallback (a missing library or GPU raises).
 """
 from ._lib import CvmiError, F16, F32  # noqa: F401
 
-__all__ = ["CvmiError", "F16", "F32", "YOLO"]
+__all__ = ["CvmiError", "F16", "F32", "YOLO", "Sam2AutomaticMaskGenerator"]
 
 
 def __getattr__(name):
     if name == "YOLO":
         from .detector import YOLO
         return YOLO
+    if name == "Sam2AutomaticMaskGenerator":
+        from .amg import Sam2AutomaticMaskGenerator
+        return Sam2AutomaticMaskGenerator
     raise AttributeError(name)

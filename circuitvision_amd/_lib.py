@@ -87,6 +87,8 @@ class Sam2SrcRow(C.Structure):
 # the two table rows as numpy record types (host arrays handed to the C ABI by pointer)
 LETTERBOX_ROW = [(n, "<i8" if t is C.c_longlong else "<i4") for n, t in LetterboxRow._fields_]
 SAM2_SRC_ROW = [(n, "<i8" if t is C.c_longlong else "<i4") for n, t in Sam2SrcRow._fields_]
+# cvmi_amg_record: one kept candidate of cvmi_amg_select (a device array read back as this numpy record type)
+AMG_RECORD = [("score", "<f4"), ("stability", "<f4")] + [(n, "<i4") for n in ("area", "x0", "y0", "x1", "y1", "point", "token", "reserved")]
 
 
 # name -> (restype, argtypes); every symbol declared in include/cvmi355.h
@@ -152,6 +154,8 @@ SIGNATURES = {
     "cvmi_mask_extent": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "cvmi_mask_postprocess": (_i, [_vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
     "cvmi_mask_postprocess_sizes": (_i, [_vp, _i, _i, _i, _vp, _f, _vp, _vp, _vp]),
+    "cvmi_amg_score": (_i, [_vp, _i, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp]),
+    "cvmi_amg_select": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "cvmi_mask_cc_workspace": (C.c_size_t, [_i, _i, _i]),
     "cvmi_mask_components": (_i, [_vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
     "cvmi_mask_fill_small": (_i, [_vp, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp]),

@@ -277,19 +277,7 @@ __global__ __launch_bounds__(256) void select_mask_kernel(const float* __restric
 }
 
 // ---- bilinear, align_corners = False (PyTorch semantics) ----------------------------------------------------
-__device__ __forceinline__ void bil_axis(int d, float scale, int in, int& i0, int& i1, float& l1) {
-  float s = ((float)d + 0.5f) * scale - 0.5f;
-  if (s < 0.f) s = 0.f;
-  i0 = (int)s;
-  if (i0 > in - 1) i0 = in - 1;
-  i1 = i0 + (i0 < in - 1 ? 1 : 0);
-  l1 = s - (float)i0;
-}
-
-__device__ __forceinline__ float bil_sample(const float* __restrict__ pl, int w, int y0, int y1, float ly, int x0, int x1, float lx) {
-  const float hy = 1.f - ly, hx = 1.f - lx;
-  return hy * (hx * pl[(size_t)y0 * w + x0] + lx * pl[(size_t)y0 * w + x1]) + ly * (hx * pl[(size_t)y1 * w + x0] + lx * pl[(size_t)y1 * w + x1]);
-}
+#include "bilinear.hpp"
 
 // y (f32 map), mask (u8 {0,255} of v > thresh) and ext (per-plane extent of the mask, pre-initialised to {W, H, -1, -1}) are each
 // optional: the reference's post-processing (circuit_analyzer.py:354-370) only needs the u8 mask and its bounding rectangle, so the

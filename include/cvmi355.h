@@ -489,6 +489,47 @@ int cvmi_mask_postprocess_sizes(const float* x, int N, int h, int w, const int* 
 int cvmi_mask_postprocess_rects_dev(const float* x, int N, int h, int w, const int* rects_dev, long long plane_stride, float thresh,
                                     uint8_t* mask_u8, int* extent, cvmi_stream_t stream);
 
+/* ---- automatic mask generation (upstream SAM2AutomaticMaskGenerator at its defaults: one crop, multimask, no mask-to-mask pass): what
+ * follows the decoder for the candidate planes of a chunk of grid points, without the f32 map at the image's size.
+ *
+ * cvmi_amg_score: M planes low f32 [M,h,w] are resized to H x W exactly as cvmi_bilinear_f32 resizes them -- the same taps, weights and
+ * scale factors (float)h / (float)H, (float)w / (float)W, the same f32 value v per pixel (csrc/bilinear.hpp) -- and only counted:
+ *   stats i32 [M,8] = {n_hi, n_lo, area, x0, y0, x1, y1, 0}: n_hi = #(v > hi), n_lo = #(v > lo), area = #(v > mid), and the inclusive
+ *   {min x, min y, max x, max y} of v > mid, {0, 0, 0, 0} for an empty mask (upstream's batched_mask_to_box).
+ * The caller passes the levels as f32 (upstream: mid = mask_threshold, lo / hi = mid -+ stability_score_offset, computed in double and rounded
+ * once); lo <= mid <= hi is not required.  stats is defined by this call alone (three launches: initialise, score, close the empty boxes) and
+ * needs no preparation; all reductions are integer sums and extrema, so the result does not depend on the launch.
+ * mask_u8 (optional) u8 [M,H,W]: the same kernel also writes (v > mid) ? 255 : 0; stats is identical with and without it, so the area and
+ * box agree with the written mask by construction.
+ * A workgroup stages the source rows and columns of a band of output rows in LDS; the call refuses (before any launch) an M above 65535,
+ * a plane of 2^31 pixels or more, and a resize whose single output row needs more than 12288 staged floats (w > 6144 of a down-scale beyond
+ * 6x in x). */
+int cvmi_amg_score(const float* low, int M, int h, int w, int H, int W, float lo, float mid, float hi, int* stats, uint8_t* mask_u8,
+                   cvmi_stream_t stream);
+
+/* cvmi_amg_select: ONE image's filter and ordered append of a chunk's candidates, in one launch.
+ *   stats i32 [n,8] (cvmi_amg_score), iou f32 [n] (the decoder's predicted IoUs) and low f32 [n,P] for the chunk's n candidate planes in
+ *   candidate order (point-major: plane i belongs to point point_base + i / ncand, candidate token i % ncand; ncand = 3 multimask, else 1);
+ *   only the first n_valid <= n take part (the rest are the pairs a short last chunk was padded with: never selected, whatever they score).
+ * Keep rule: iou > iou_thresh and stability >= stab_thresh with stability = (float)n_hi / (float)n_lo in f32 (0 / 0 = NaN fails, as in torch).
+ * Every kept candidate is appended, in candidate order (a prefix sum over the keep flags, not a slot grab), at the image's running count:
+ *   counter i32 [2] (DEVICE) = {candidates kept so far, 0}: the caller zeroes both once per image; every call adds its kept count to counter[0]
+ *   (counter[1] is the call's own ticket and is 0 again afterwards).  The count goes on past cap; nothing is written at or past slot cap.
+ *   records [cap]: cvmi_amg_record of slot s;  pool f32 [cap,P]: its low plane;
+ *   nms_block f32 [5,cap]: column s = (cx, cy, w, h, score) of the inclusive box as floats -- the layout cvmi_yolo_nms reads with nc = 1,
+ *   A = cap; cx - w / 2 gives the integer corner back exactly.  The caller fills row 4 (score) with -inf once per image, so that the
+ *   unused columns never pass its conf_thres; this call does not touch them.
+ * P a multiple of 4; low and pool 16-byte aligned.  n_valid == 0 returns 0 without a launch. */
+typedef struct cvmi_amg_record {
+  float score, stability;      /* predicted IoU, stability score */
+  int area, x0, y0, x1, y1;    /* stats[2..6] */
+  int point, token;            /* grid point index, candidate token */
+  int reserved;                /* 0 */
+} cvmi_amg_record;
+int cvmi_amg_select(const int* stats, const float* iou, const float* low, int n, int n_valid, int ncand, int point_base, float iou_thresh,
+                    float stab_thresh, int P, int cap, int* counter, cvmi_amg_record* records, float* pool, float* nms_block,
+                    cvmi_stream_t stream);
+
 /* Hole and sprinkle removal of postprocess_masks (sam2_infer.py:88-128) and the labelling under it, on f32 planes x [N,h,w] with a
  * threshold t.  Foreground is x > t, background x <= t; components are 8-connected in BOTH phases and never cross a plane; h and w need
  * not be even.  The label of a pixel is 1 + (y * w + x) of the raster-first pixel of its component, its area the component's pixel count.
