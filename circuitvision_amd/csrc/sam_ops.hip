@@ -1,6 +1,5 @@
-// SAM 2.1 path helpers (everything that is not a GEMM or an attention): LayerNorm, 2x2 max-pool, casts,
-// the mask-decoder tail (hypernetwork product + stability selection), bilinear resizes, the fused
-// upsample + multi-kernel refinement head, and the antialiased input transform.
+// SAM 2.1 path helpers (everything that is not a GEMM, an attention or a resampling kernel -- resample.hip): LayerNorm, 2x2 max-pool, casts,
+// prompt tokens, the mask-decoder tail (hypernetwork product + stability selection) and the fused upsample + multi-kernel refinement head.
 #include "common.hpp"
 
 namespace {
@@ -196,35 +195,6 @@ __global__ __launch_bounds__(256) void s2d4_kernel(const T* __restrict__ x, T* _
   }
 }
 
-// ---- extent of a binary mask: min / max x, y over the non-zero pixels of each plane ----------------------------------
-// (circuit_analyzer.py:364-370: cv2.findContours(EXTERNAL) + boundingRect over all contour points == the bounding
-// rectangle of the non-zero pixels)
-__global__ __launch_bounds__(256) void mask_extent_kernel(const uint8_t* __restrict__ m, int H, int W, int* __restrict__ ext) {
-  const int n = blockIdx.y;
-  const uint8_t* pl = m + (size_t)n * H * W;
-  int x0 = W, y0 = H, x1 = -1, y1 = -1;
-  const long long total = (long long)H * W;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-    if (pl[i]) {
-      const int y = (int)(i / W), x = (int)(i - (long long)y * W);
-      x0 = x < x0 ? x : x0; x1 = x > x1 ? x : x1; y0 = y < y0 ? y : y0; y1 = y > y1 ? y : y1;
-    }
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    x0 = min(x0, __shfl_xor(x0, off)); y0 = min(y0, __shfl_xor(y0, off));
-    x1 = max(x1, __shfl_xor(x1, off)); y1 = max(y1, __shfl_xor(y1, off));
-  }
-  if ((threadIdx.x & 63) == 0 && x1 >= 0) {
-    atomicMin(ext + n * 4 + 0, x0); atomicMin(ext + n * 4 + 1, y0);
-    atomicMax(ext + n * 4 + 2, x1); atomicMax(ext + n * 4 + 3, y1);
-  }
-}
-__global__ void mask_extent_init_kernel(int* ext, int N, int H, int W) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < N) { ext[i * 4] = W; ext[i * 4 + 1] = H; ext[i * 4 + 2] = -1; ext[i * 4 + 3] = -1; }
-}
-
 // ---- mask decoder tail ------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void zero_i32_kernel(int* __restrict__ p, int n) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) p[i] = 0;
@@ -276,41 +246,7 @@ __global__ __launch_bounds__(256) void select_mask_kernel(const float* __restric
   for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < P; p += gridDim.x * blockDim.x) low[(size_t)b * P + p] = src[p];
 }
 
-// ---- bilinear, align_corners = False (PyTorch semantics) ----------------------------------------------------
 #include "bilinear.hpp"
-
-// y (f32 map), mask (u8 {0,255} of v > thresh) and ext (per-plane extent of the mask, pre-initialised to {W, H, -1, -1}) are each
-// optional: the reference's post-processing (circuit_analyzer.py:354-370) only needs the u8 mask and its bounding rectangle, so the
-// f32 [N,H,W] map need not be written at all.
-__global__ __launch_bounds__(256) void bilinear_kernel(const float* __restrict__ x, int h, int w, float* __restrict__ y, int H, int W,
-                                                      uint8_t* __restrict__ mask, float thresh, float sy, float sx, int* __restrict__ ext) {
-  const int n = blockIdx.y;
-  const float* pl = x + (size_t)n * h * w;
-  const int total = H * W;
-  int ex0 = W, ey0 = H, ex1 = -1, ey1 = -1;
-  for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
-    const int oy = idx / W, ox = idx - oy * W;
-    int y0, y1, x0, x1; float ly, lx;
-    bil_axis(oy, sy, h, y0, y1, ly);
-    bil_axis(ox, sx, w, x0, x1, lx);
-    const float v = bil_sample(pl, w, y0, y1, ly, x0, x1, lx);
-    if (y) y[(size_t)n * total + idx] = v;
-    const bool on = v > thresh;
-    if (mask) mask[(size_t)n * total + idx] = on ? 255 : 0;
-    if (on) { ex0 = min(ex0, ox); ex1 = max(ex1, ox); ey0 = min(ey0, oy); ey1 = max(ey1, oy); }
-  }
-  if (ext) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      ex0 = min(ex0, __shfl_xor(ex0, off)); ey0 = min(ey0, __shfl_xor(ey0, off));
-      ex1 = max(ex1, __shfl_xor(ex1, off)); ey1 = max(ey1, __shfl_xor(ey1, off));
-    }
-    if ((threadIdx.x & 63) == 0 && ex1 >= 0) {
-      atomicMin(ext + n * 4 + 0, ex0); atomicMin(ext + n * 4 + 1, ey0);
-      atomicMax(ext + n * 4 + 2, ex1); atomicMax(ext + n * 4 + 3, ey1);
-    }
-  }
-}
 
 // ---- fused upsample + MultiKernelRefinement -------------------------------------------------------------------
 // 16x16 output tile per workgroup; the bilinear-upsampled tile (+ halo of max(ks)/2, zero outside the
@@ -467,185 +403,6 @@ __global__ __launch_bounds__(256) void upsample_refine_fast_kernel(const float* 
   if (ox + 4 <= W && (W & 3) == 0) *reinterpret_cast<f32x4*>(op) = f32x4{out[0], out[1], out[2], out[3]};
   else
     for (int q = 0; q < 4; ++q) if (ox + q < W) op[q] = out[q];
-}
-
-// ---- SAM2Transforms.__call__: /255, antialiased bilinear (torch _upsample_bilinear2d_aa), normalise -----------
-constexpr int AA_MAXTAPS = 24;
-__device__ __forceinline__ void aa_axis(int i, float scale, int in, int& xmin, int& xsize, float* wt) {
-  const float support = scale >= 1.f ? scale : 1.f;
-  const float invscale = scale >= 1.f ? 1.f / scale : 1.f;
-  const float center = scale * ((float)i + 0.5f);
-  xmin = max((int)(center - support + 0.5f), 0);
-  xsize = min((int)(center + support + 0.5f), in) - xmin;
-  if (xsize > AA_MAXTAPS) xsize = AA_MAXTAPS;
-  float total = 0.f;
-  for (int j = 0; j < xsize; ++j) {
-    float t = ((float)(j + xmin) - center + 0.5f) * invscale;
-    t = fabsf(t);
-    const float wv = t < 1.f ? 1.f - t : 0.f;
-    wt[j] = wv;
-    total += wv;
-  }
-  const float ws = total != 0.f ? 1.f / total : 0.f;
-  for (int j = 0; j < xsize; ++j) wt[j] *= ws;
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void sam2_transform_kernel(const uint8_t* __restrict__ src, int H, int W, T* __restrict__ dst, int R, float sy, float sx,
-                                                            int swap_rb) {
-  src += (size_t)blockIdx.y * H * W * 3;                  // blockIdx.y = image of a batch of equally sized sources
-  dst += (size_t)blockIdx.y * R * R * 3;
-  const int c0 = swap_rb ? 2 : 0, c2 = swap_rb ? 0 : 2;   // swap_rb: output channel c reads source channel 2 - c (the caller's cv2.COLOR_BGR2RGB)
-  const int total = R * R;
-  for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
-    const int oy = idx / R, ox = idx - oy * R;
-    int ymin, ysize, xmin, xsize;
-    float wy[AA_MAXTAPS], wx[AA_MAXTAPS];
-    aa_axis(oy, sy, H, ymin, ysize, wy);
-    aa_axis(ox, sx, W, xmin, xsize, wx);
-    float acc[3] = {0.f, 0.f, 0.f};
-    for (int j = 0; j < ysize; ++j) {
-      float row[3] = {0.f, 0.f, 0.f};
-      const uint8_t* sp = src + ((size_t)(ymin + j) * W + xmin) * 3;
-      for (int i = 0; i < xsize; ++i) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) row[c] += wx[i] * ((float)sp[i * 3 + (c == 0 ? c0 : c == 2 ? c2 : 1)] / 255.0f);
-      }
-#pragma unroll
-      for (int c = 0; c < 3; ++c) acc[c] += wy[j] * row[c];
-    }
-    const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
-#pragma unroll
-    for (int c = 0; c < 3; ++c) dst[(size_t)idx * 3 + c] = (T)((acc[c] - mean[c]) / stdv[c]);
-  }
-}
-
-// The same on a WINDOW of each source image (the crop between the two stages, circuit_analyzer.py:937-1284 as called at
-// analysis_pipeline.py:177, without a cropped copy): image b of the launch is the rectangle win[b] = {x0, y0, w, h} of source image b.  The
-// table travels by value in the kernel arguments (<= 64 images per launch).
-constexpr int RECT_MAX = 64;
-struct RectTable { int4 r[RECT_MAX]; };
-
-// image blockIdx.y of the launch = the rectangle rc = {x0, y0, w, h} of source image blockIdx.y (both forms of the window table below)
-template <typename T>
-__device__ __forceinline__ void sam2_transform_window(const uint8_t* __restrict__ src, long long image_stride, int W, const int4 rc,
-                                                      T* __restrict__ dst, int R, int swap_rb) {
-  const int H0 = rc.w, W0 = rc.z;                         // the window's height, width: the resize sees nothing outside it
-  const float sy = (float)H0 / (float)R, sx = (float)W0 / (float)R;
-  src += (size_t)blockIdx.y * image_stride + ((size_t)rc.y * W + rc.x) * 3;
-  dst += (size_t)blockIdx.y * R * R * 3;
-  const int c0 = swap_rb ? 2 : 0, c2 = swap_rb ? 0 : 2;
-  const int total = R * R;
-  for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
-    const int oy = idx / R, ox = idx - oy * R;
-    int ymin, ysize, xmin, xsize;
-    float wy[AA_MAXTAPS], wx[AA_MAXTAPS];
-    aa_axis(oy, sy, H0, ymin, ysize, wy);
-    aa_axis(ox, sx, W0, xmin, xsize, wx);
-    float acc[3] = {0.f, 0.f, 0.f};
-    for (int j = 0; j < ysize; ++j) {
-      float row[3] = {0.f, 0.f, 0.f};
-      const uint8_t* sp = src + ((size_t)(ymin + j) * W + xmin) * 3;
-      for (int i = 0; i < xsize; ++i) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) row[c] += wx[i] * ((float)sp[i * 3 + (c == 0 ? c0 : c == 2 ? c2 : 1)] / 255.0f);
-      }
-#pragma unroll
-      for (int c = 0; c < 3; ++c) acc[c] += wy[j] * row[c];
-    }
-    const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
-#pragma unroll
-    for (int c = 0; c < 3; ++c) dst[(size_t)idx * 3 + c] = (T)((acc[c] - mean[c]) / stdv[c]);
-  }
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void sam2_transform_rects_kernel(const uint8_t* __restrict__ src, long long image_stride, int W, const RectTable win,
-                                                                  T* __restrict__ dst, int R, int swap_rb) {
-  sam2_transform_window<T>(src, image_stride, W, win.r[blockIdx.y], dst, R, swap_rb);
-}
-
-// The window table in DEVICE memory (cvmi_stage2_crop's output): nothing of the launch depends on a value the host has seen.  A window is
-// clipped to the H x W image here, whatever the table holds.
-template <typename T>
-__global__ __launch_bounds__(256) void sam2_transform_rects_dev_kernel(const uint8_t* __restrict__ src, long long image_stride, int H, int W,
-                                                                      const int4* __restrict__ win, T* __restrict__ dst, int R, int swap_rb) {
-  int4 rc = win[blockIdx.y];
-  rc.x = min(max(rc.x, 0), W - 1); rc.y = min(max(rc.y, 0), H - 1);
-  rc.z = min(max(rc.z, 1), W - rc.x); rc.w = min(max(rc.w, 1), H - rc.y);
-  sam2_transform_window<T>(src, image_stride, W, rc, dst, R, swap_rb);
-}
-
-// Sources of DIFFERENT sizes in one packed u8 buffer: image blockIdx.y is the window {x0, y0, w, h} of the row's H x W image at
-// src + src_byte_offset (any byte offset: the taps are read byte by byte).  The third way to find the window; the arithmetic is
-// sam2_transform_window's.
-struct SrcTable { cvmi_sam2_src_row r[RECT_MAX]; };
-template <typename T>
-__global__ __launch_bounds__(256) void sam2_transform_srcs_kernel(const uint8_t* __restrict__ src, const SrcTable tab, T* __restrict__ dst, int R,
-                                                                 int swap_rb) {
-  const cvmi_sam2_src_row g = tab.r[blockIdx.y];
-  sam2_transform_window<T>(src + g.src_byte_offset, 0, g.W, make_int4(g.x0, g.y0, g.w, g.h), dst, R, swap_rb);
-}
-
-// plane blockIdx.y (f32 [h, w]) -> H x W, thresholded, at mp; its extent into ext[4 * blockIdx.y ..]
-__device__ __forceinline__ void bilinear_plane(const float* __restrict__ x, int h, int w, int H, int W, uint8_t* __restrict__ mp, float thresh,
-                                               int* __restrict__ ext) {
-  const int n = blockIdx.y;
-  const float sy = (float)h / (float)H, sx = (float)w / (float)W;
-  const float* pl = x + (size_t)n * h * w;
-  const int total = H * W;
-  int ex0 = W, ey0 = H, ex1 = -1, ey1 = -1;
-  for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
-    const int oy = idx / W, ox = idx - oy * W;
-    int y0, y1, x0, x1; float ly, lx;
-    bil_axis(oy, sy, h, y0, y1, ly);
-    bil_axis(ox, sx, w, x0, x1, lx);
-    const bool on = bil_sample(pl, w, y0, y1, ly, x0, x1, lx) > thresh;
-    mp[idx] = on ? 255 : 0;
-    if (on) { ex0 = min(ex0, ox); ex1 = max(ex1, ox); ey0 = min(ey0, oy); ey1 = max(ey1, oy); }
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    ex0 = min(ex0, __shfl_xor(ex0, off)); ey0 = min(ey0, __shfl_xor(ey0, off));
-    ex1 = max(ex1, __shfl_xor(ex1, off)); ey1 = max(ey1, __shfl_xor(ey1, off));
-  }
-  if ((threadIdx.x & 63) == 0 && ex1 >= 0) {
-    atomicMin(ext + n * 4 + 0, ex0); atomicMin(ext + n * 4 + 1, ey0);
-    atomicMax(ext + n * 4 + 2, ex1); atomicMax(ext + n * 4 + 3, ey1);
-  }
-}
-// cvmi_mask_postprocess for planes that go back to DIFFERENT sizes (each image's own crop window): plane n is resized to sz.r[n] = {H, W} and
-// written at mask + sz.r[n].z (a byte offset the host laid out: planes packed back to back); extents pre-initialised by the kernel's first block.
-__global__ __launch_bounds__(256) void bilinear_sizes_kernel(const float* __restrict__ x, int h, int w, const RectTable sz, uint8_t* __restrict__ mask,
-                                                            long long mask_base, float thresh, int* __restrict__ ext) {
-  const int n = blockIdx.y;
-  bilinear_plane(x, h, w, sz.r[n].x, sz.r[n].y, mask + mask_base + (((long long)(unsigned)sz.r[n].w << 32) | (unsigned)sz.r[n].z), thresh, ext);
-}
-__global__ void mask_extent_init_sizes_kernel(int* ext, int N, const RectTable sz) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < N) { ext[i * 4] = sz.r[i].y; ext[i * 4 + 1] = sz.r[i].x; ext[i * 4 + 2] = -1; ext[i * 4 + 3] = -1; }
-}
-// The sizes in DEVICE memory: plane n returns to the {w, h} of win[n] = {x0, y0, w, h} at mask + n * plane_stride (fixed stride: no offset
-// depends on a window); a plane is clipped to its stride.
-__device__ __forceinline__ void rect_plane_size(const int4 rc, long long plane_stride, int& H, int& W) {
-  W = rc.z < 1 ? 1 : rc.z;
-  H = rc.w < 1 ? 1 : rc.w;
-  if ((long long)W > plane_stride) W = (int)plane_stride;
-  if ((long long)H * W > plane_stride) H = (int)(plane_stride / W);
-}
-__global__ __launch_bounds__(256) void bilinear_rects_dev_kernel(const float* __restrict__ x, int h, int w, const int4* __restrict__ win,
-                                                                uint8_t* __restrict__ mask, long long plane_stride, float thresh, int* __restrict__ ext) {
-  int H, W;
-  rect_plane_size(win[blockIdx.y], plane_stride, H, W);
-  bilinear_plane(x, h, w, H, W, mask + (size_t)blockIdx.y * plane_stride, thresh, ext);
-}
-__global__ void mask_extent_init_rects_dev_kernel(int* ext, int N, const int4* __restrict__ win, long long plane_stride) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < N) {
-    int H, W;
-    rect_plane_size(win[i], plane_stride, H, W);
-    ext[i * 4] = W; ext[i * 4 + 1] = H; ext[i * 4 + 2] = -1; ext[i * 4 + 3] = -1;
-  }
 }
 
 inline int grid_for(long long total, int block = 256, int cap = 256 * 16) {
@@ -847,29 +604,6 @@ extern "C" int cvmi_select_mask(const float* masks, const int* areas, const floa
 #endif
 
 #ifndef CVMI_OPERAND_BF16
-extern "C" int cvmi_bilinear_f32(const float* x, int N, int h, int w, float* y, int H, int W, uint8_t* mask_u8, float thresh, cvmi_stream_t stream_) {
-  CVMI_CHECK(x && (y || mask_u8) && N > 0 && N <= 65535 && h > 0 && w > 0 && H > 0 && W > 0, "bilinear: bad arguments");
-  hipLaunchKernelGGL(bilinear_kernel, dim3(grid_for((long long)H * W, 256, 1024), N), dim3(256), 0, (hipStream_t)stream_, x, h, w, y, H, W, mask_u8,
-                     thresh, (float)h / (float)H, (float)w / (float)W, (int*)nullptr);
-  CVMI_LAUNCH_CHECK();
-  return 0;
-}
-#endif
-
-#ifndef CVMI_OPERAND_BF16
-extern "C" int cvmi_mask_postprocess(const float* x, int N, int h, int w, int H, int W, float thresh, uint8_t* mask_u8, int* extent,
-                                     cvmi_stream_t stream_) {
-  CVMI_CHECK(x && mask_u8 && extent && N > 0 && N <= 65535 && h > 0 && w > 0 && H > 0 && W > 0, "mask_postprocess: bad arguments");
-  hipStream_t s = (hipStream_t)stream_;
-  hipLaunchKernelGGL(mask_extent_init_kernel, dim3((N + 63) / 64), dim3(64), 0, s, extent, N, H, W);
-  hipLaunchKernelGGL(bilinear_kernel, dim3(grid_for((long long)H * W, 256, 1024), N), dim3(256), 0, s, x, h, w, (float*)nullptr, H, W, mask_u8, thresh,
-                     (float)h / (float)H, (float)w / (float)W, extent);
-  CVMI_LAUNCH_CHECK();
-  return 0;
-}
-#endif
-
-#ifndef CVMI_OPERAND_BF16
 extern "C" int cvmi_space_to_depth4_bf16(const void* x, void* y, int B, int H, int W, int dtype, cvmi_stream_t stream_);
 #endif
 extern "C" int CVMI_ENTRY(cvmi_space_to_depth4)(const void* x, void* y, int B, int H, int W, int dtype, cvmi_stream_t stream_) {
@@ -885,17 +619,6 @@ extern "C" int CVMI_ENTRY(cvmi_space_to_depth4)(const void* x, void* y, int B, i
   CVMI_LAUNCH_CHECK();
   return 0;
 }
-
-#ifndef CVMI_OPERAND_BF16
-extern "C" int cvmi_mask_extent(const uint8_t* mask, int N, int H, int W, int* extent, cvmi_stream_t stream_) {
-  CVMI_CHECK(mask && extent && N > 0 && N <= 65535 && H > 0 && W > 0, "mask_extent: bad arguments");
-  hipStream_t s = (hipStream_t)stream_;
-  hipLaunchKernelGGL(mask_extent_init_kernel, dim3((N + 63) / 64), dim3(64), 0, s, extent, N, H, W);
-  hipLaunchKernelGGL(mask_extent_kernel, dim3(grid_for((long long)H * W, 256, 32), N), dim3(256), 0, s, mask, H, W, extent);
-  CVMI_LAUNCH_CHECK();
-  return 0;
-}
-#endif
 
 #ifndef CVMI_OPERAND_BF16
 extern "C" int cvmi_upsample_refine(const float* low, int N, int h, int w, float* high, int H, int W, const float* params, const int* ks, int nk,
@@ -928,170 +651,5 @@ extern "C" int cvmi_upsample_refine(const float* low, int N, int h, int w, float
                      (float)w / (float)W);
   CVMI_LAUNCH_CHECK();
   return 0;
-}
-#endif
-
-#ifndef CVMI_OPERAND_BF16
-extern "C" int cvmi_sam2_transform_batch_bf16(const uint8_t* src, int B, int H, int W, void* dst, int R, int dst_dtype, int swap_rb, cvmi_stream_t stream_);
-#endif
-extern "C" int CVMI_ENTRY(cvmi_sam2_transform_batch)(const uint8_t* src, int B, int H, int W, void* dst, int R, int dst_dtype, int swap_rb,
-                                                     cvmi_stream_t stream_) {
-#ifndef CVMI_OPERAND_BF16
-  if (dst_dtype == CVMI_BF16) return cvmi_sam2_transform_batch_bf16(src, B, H, W, dst, R, dst_dtype, swap_rb, stream_);
-#endif
-  CVMI_CHECK(src && dst && B >= 1 && B <= 65535 && H > 0 && W > 0 && R > 0, "sam2_transform: bad arguments");
-  CVMI_CHECK(dst_dtype == CVMI_T16 || dst_dtype == CVMI_F32, "sam2_transform: bad dtype");
-  const float sy = (float)H / (float)R, sx = (float)W / (float)R;
-  CVMI_CHECK(2.f * (sy > 1.f ? sy : 1.f) + 2.f <= AA_MAXTAPS && 2.f * (sx > 1.f ? sx : 1.f) + 2.f <= AA_MAXTAPS, "sam2_transform: down-scale factor too large");
-  hipStream_t s = (hipStream_t)stream_;
-  const dim3 g(grid_for((long long)R * R), B), b(256);
-  if (dst_dtype == CVMI_T16) hipLaunchKernelGGL(sam2_transform_kernel<f16>, g, b, 0, s, src, H, W, (f16*)dst, R, sy, sx, swap_rb ? 1 : 0);
-  else hipLaunchKernelGGL(sam2_transform_kernel<float>, g, b, 0, s, src, H, W, (float*)dst, R, sy, sx, swap_rb ? 1 : 0);
-  CVMI_LAUNCH_CHECK();
-  return 0;
-}
-#ifndef CVMI_OPERAND_BF16
-extern "C" int cvmi_sam2_transform_rects_bf16(const uint8_t* src, long long src_image_stride, int H, int W, const int* rects, int B, void* dst, int R,
-                                              int dst_dtype, int swap_rb, cvmi_stream_t stream_);
-#endif
-extern "C" int CVMI_ENTRY(cvmi_sam2_transform_rects)(const uint8_t* src, long long src_image_stride, int H, int W, const int* rects, int B, void* dst, int R,
-                                                     int dst_dtype, int swap_rb, cvmi_stream_t stream_) {
-#ifndef CVMI_OPERAND_BF16
-  if (dst_dtype == CVMI_BF16) return cvmi_sam2_transform_rects_bf16(src, src_image_stride, H, W, rects, B, dst, R, dst_dtype, swap_rb, stream_);
-#endif
-  CVMI_CHECK(src && dst && rects && B >= 1 && H > 0 && W > 0 && R > 0 && src_image_stride >= 0, "sam2_transform_rects: bad arguments");
-  CVMI_CHECK(dst_dtype == CVMI_T16 || dst_dtype == CVMI_F32, "sam2_transform_rects: bad dtype");
-  for (int b = 0; b < B; ++b) {                                     // every window before the first launch: a bad one leaves nothing half done
-    const int* r = rects + 4 * (size_t)b;
-    CVMI_CHECK(r[0] >= 0 && r[1] >= 0 && r[2] > 0 && r[3] > 0 && (long long)r[0] + r[2] <= W && (long long)r[1] + r[3] <= H,
-               "sam2_transform_rects: window %d = (x %d, y %d, w %d, h %d) leaves the %d x %d image", b, r[0], r[1], r[2], r[3], W, H);
-    const float sy = (float)r[3] / (float)R, sx = (float)r[2] / (float)R;
-    CVMI_CHECK(2.f * (sy > 1.f ? sy : 1.f) + 2.f <= AA_MAXTAPS && 2.f * (sx > 1.f ? sx : 1.f) + 2.f <= AA_MAXTAPS,
-               "sam2_transform_rects: down-scale factor of window %d too large", b);
-  }
-  hipStream_t s = (hipStream_t)stream_;
-  for (int b0 = 0; b0 < B; b0 += RECT_MAX) {
-    const int nb = B - b0 < RECT_MAX ? B - b0 : RECT_MAX;
-    RectTable t;
-    for (int b = 0; b < nb; ++b) {
-      const int* r = rects + 4 * (size_t)(b0 + b);
-      t.r[b] = make_int4(r[0], r[1], r[2], r[3]);
-    }
-    for (int b = nb; b < RECT_MAX; ++b) t.r[b] = make_int4(0, 0, 1, 1);
-    const dim3 g(grid_for((long long)R * R), nb), blk(256);
-    const uint8_t* sp = src + (size_t)b0 * src_image_stride;
-    const size_t dofs = (size_t)b0 * R * R * 3;
-    if (dst_dtype == CVMI_T16) hipLaunchKernelGGL(sam2_transform_rects_kernel<f16>, g, blk, 0, s, sp, src_image_stride, W, t, (f16*)dst + dofs, R, swap_rb ? 1 : 0);
-    else hipLaunchKernelGGL(sam2_transform_rects_kernel<float>, g, blk, 0, s, sp, src_image_stride, W, t, (float*)dst + dofs, R, swap_rb ? 1 : 0);
-    CVMI_LAUNCH_CHECK();
-  }
-  return 0;
-}
-
-#ifndef CVMI_OPERAND_BF16
-// One copy for all three output types: the kernel computes in f32 and only its last conversion depends on T, so the bf16 instance needs no
-// second build of this translation unit (unlike the entry points above, whose 16-bit type is the translation unit's operand type).
-extern "C" int cvmi_sam2_transform_rects_dev(const uint8_t* src, long long src_image_stride, int H, int W, const int* rects_dev, int B, void* dst, int R,
-                                             int dst_dtype, int swap_rb, cvmi_stream_t stream_) {
-  CVMI_CHECK(src && dst && rects_dev && B >= 1 && B <= 65535 && H > 0 && W > 0 && R > 0 && src_image_stride >= 0 && ((uintptr_t)rects_dev & 15) == 0,
-             "sam2_transform_rects_dev: bad arguments");
-  CVMI_CHECK(dst_dtype == CVMI_F16 || dst_dtype == CVMI_BF16 || dst_dtype == CVMI_F32, "sam2_transform_rects_dev: bad dtype");
-  const float sy = (float)H / (float)R, sx = (float)W / (float)R;             // the whole image bounds every window inside it
-  CVMI_CHECK(2.f * (sy > 1.f ? sy : 1.f) + 2.f <= AA_MAXTAPS && 2.f * (sx > 1.f ? sx : 1.f) + 2.f <= AA_MAXTAPS,
-             "sam2_transform_rects_dev: down-scale factor of the %d x %d image too large", W, H);
-  hipStream_t s = (hipStream_t)stream_;
-  const dim3 g(grid_for((long long)R * R), B), blk(256);
-  const int4* win = (const int4*)rects_dev;
-  const int sw = swap_rb ? 1 : 0;
-  if (dst_dtype == CVMI_F16) hipLaunchKernelGGL(sam2_transform_rects_dev_kernel<_Float16>, g, blk, 0, s, src, src_image_stride, H, W, win, (_Float16*)dst, R, sw);
-  else if (dst_dtype == CVMI_BF16) hipLaunchKernelGGL(sam2_transform_rects_dev_kernel<__bf16>, g, blk, 0, s, src, src_image_stride, H, W, win, (__bf16*)dst, R, sw);
-  else hipLaunchKernelGGL(sam2_transform_rects_dev_kernel<float>, g, blk, 0, s, src, src_image_stride, H, W, win, (float*)dst, R, sw);
-  CVMI_LAUNCH_CHECK();
-  return 0;
-}
-#endif
-
-#ifndef CVMI_OPERAND_BF16
-// (one copy for all three output types, as above)
-extern "C" int cvmi_sam2_transform_srcs(const uint8_t* src, long long src_bytes, const cvmi_sam2_src_row* rows, int B, void* dst, int R, int dst_dtype,
-                                        int swap_rb, cvmi_stream_t stream_) {
-  CVMI_CHECK(src && dst && rows && B >= 1 && R > 0 && src_bytes > 0, "sam2_transform_srcs: bad arguments");
-  CVMI_CHECK(dst_dtype == CVMI_F16 || dst_dtype == CVMI_BF16 || dst_dtype == CVMI_F32, "sam2_transform_srcs: bad dtype");
-  for (int b = 0; b < B; ++b) {                                     // every row before the first launch
-    const cvmi_sam2_src_row& r = rows[b];
-    CVMI_CHECK(r.H > 0 && r.W > 0 && r.src_byte_offset >= 0 && r.src_byte_offset + (long long)r.H * r.W * 3 <= src_bytes,
-               "sam2_transform_srcs: row %d: %d x %d x 3 bytes at offset %lld leave the %lld-byte source buffer", b, r.H, r.W, r.src_byte_offset, src_bytes);
-    CVMI_CHECK(r.x0 >= 0 && r.y0 >= 0 && r.w > 0 && r.h > 0 && (long long)r.x0 + r.w <= r.W && (long long)r.y0 + r.h <= r.H,
-               "sam2_transform_srcs: window %d = (x %d, y %d, w %d, h %d) leaves the %d x %d image", b, r.x0, r.y0, r.w, r.h, r.W, r.H);
-    const float sy = (float)r.h / (float)R, sx = (float)r.w / (float)R;
-    CVMI_CHECK(2.f * (sy > 1.f ? sy : 1.f) + 2.f <= AA_MAXTAPS && 2.f * (sx > 1.f ? sx : 1.f) + 2.f <= AA_MAXTAPS,
-               "sam2_transform_srcs: down-scale factor of window %d too large", b);
-  }
-  hipStream_t s = (hipStream_t)stream_;
-  const int sw = swap_rb ? 1 : 0;
-  const size_t esz = dst_dtype == CVMI_F32 ? 4 : 2;
-  for (int b0 = 0; b0 < B; b0 += RECT_MAX) {
-    const int nb = B - b0 < RECT_MAX ? B - b0 : RECT_MAX;
-    SrcTable t;
-    for (int b = 0; b < RECT_MAX; ++b) t.r[b] = rows[b0 + (b < nb ? b : 0)];
-    const dim3 g(grid_for((long long)R * R), nb), blk(256);
-    char* d = (char*)dst + (size_t)b0 * R * R * 3 * esz;
-    if (dst_dtype == CVMI_F16) hipLaunchKernelGGL(sam2_transform_srcs_kernel<_Float16>, g, blk, 0, s, src, t, (_Float16*)d, R, sw);
-    else if (dst_dtype == CVMI_BF16) hipLaunchKernelGGL(sam2_transform_srcs_kernel<__bf16>, g, blk, 0, s, src, t, (__bf16*)d, R, sw);
-    else hipLaunchKernelGGL(sam2_transform_srcs_kernel<float>, g, blk, 0, s, src, t, (float*)d, R, sw);
-    CVMI_LAUNCH_CHECK();
-  }
-  return 0;
-}
-#endif
-
-#ifndef CVMI_OPERAND_BF16
-extern "C" int cvmi_mask_postprocess_rects_dev(const float* x, int N, int h, int w, const int* rects_dev, long long plane_stride, float thresh,
-                                               uint8_t* mask_u8, int* extent, cvmi_stream_t stream_) {
-  CVMI_CHECK(x && mask_u8 && extent && rects_dev && N > 0 && N <= 65535 && h > 0 && w > 0 && plane_stride > 0 && plane_stride < (1ll << 31) &&
-             ((uintptr_t)rects_dev & 15) == 0, "mask_postprocess_rects_dev: bad arguments");
-  hipStream_t s = (hipStream_t)stream_;
-  hipLaunchKernelGGL(mask_extent_init_rects_dev_kernel, dim3((N + 63) / 64), dim3(64), 0, s, extent, N, (const int4*)rects_dev, plane_stride);
-  hipLaunchKernelGGL(bilinear_rects_dev_kernel, dim3(grid_for(plane_stride, 256, 1024), N), dim3(256), 0, s, x, h, w, (const int4*)rects_dev, mask_u8,
-                     plane_stride, thresh, extent);
-  CVMI_LAUNCH_CHECK();
-  return 0;
-}
-#endif
-
-#ifndef CVMI_OPERAND_BF16
-extern "C" int cvmi_mask_postprocess_sizes(const float* x, int N, int h, int w, const int* sizes, float thresh, uint8_t* mask_u8, int* extent,
-                                           cvmi_stream_t stream_) {
-  CVMI_CHECK(x && mask_u8 && extent && sizes && N > 0 && h > 0 && w > 0, "mask_postprocess_sizes: bad arguments");
-  for (int n = 0; n < N; ++n) {                                     // every size before the first launch
-    const int H = sizes[2 * (size_t)n], W = sizes[2 * (size_t)n + 1];
-    CVMI_CHECK(H > 0 && W > 0 && (long long)H * W < (1ll << 31), "mask_postprocess_sizes: plane %d has size %d x %d", n, H, W);
-  }
-  hipStream_t s = (hipStream_t)stream_;
-  long long off = 0;
-  for (int n0 = 0; n0 < N; n0 += RECT_MAX) {
-    const int nb = N - n0 < RECT_MAX ? N - n0 : RECT_MAX;
-    RectTable t;
-    long long maxhw = 1, rel = 0;
-    for (int n = 0; n < nb; ++n) {
-      const int H = sizes[2 * (size_t)(n0 + n)], W = sizes[2 * (size_t)(n0 + n) + 1];
-      t.r[n] = make_int4(H, W, (int)(unsigned)(rel & 0xffffffffll), (int)(unsigned)(rel >> 32));
-      rel += (long long)H * W;
-      if ((long long)H * W > maxhw) maxhw = (long long)H * W;
-    }
-    for (int n = nb; n < RECT_MAX; ++n) t.r[n] = make_int4(1, 1, 0, 0);
-    hipLaunchKernelGGL(mask_extent_init_sizes_kernel, dim3(1), dim3(64), 0, s, extent + 4 * (size_t)n0, nb, t);
-    hipLaunchKernelGGL(bilinear_sizes_kernel, dim3(grid_for(maxhw, 256, 1024), nb), dim3(256), 0, s, x + (size_t)n0 * h * w, h, w, t, mask_u8, off, thresh,
-                       extent + 4 * (size_t)n0);
-    CVMI_LAUNCH_CHECK();
-    off += rel;
-  }
-  return 0;
-}
-#endif
-
-#ifndef CVMI_OPERAND_BF16
-extern "C" int cvmi_sam2_transform(const uint8_t* src, int H, int W, void* dst, int R, int dst_dtype, cvmi_stream_t stream_) {
-  return cvmi_sam2_transform_batch(src, 1, H, W, dst, R, dst_dtype, 0, stream_);
 }
 #endif

@@ -389,7 +389,7 @@ class CircuitPipeline:
             hs = self.det.predict_chunks_async([images[i] for i in idxs], self.seg_batch, after_chunk=after)
             work += [(idxs[k * self.seg_batch:(k + 1) * self.seg_batch], h) for k, h in enumerate(hs)]
         t = self._tick("enqueue: detector chunks (stage u8 + ONE H2D + per chunk: letterbox + YOLO11 graph + NMS + glue kernel + D2H launches)", t)
-        pend = [(idxs, h, self._enqueue_learned_dev(h.src, h.after[0].window, h.done, k % self.seg_slots)) for k, (idxs, h) in enumerate(work)]
+        pend = [(idxs, h, self._enqueue_learned(None, k % self.seg_slots, src=h.src, windows=h.after[0].window, ready=h.done)) for k, (idxs, h) in enumerate(work)]
         t = self._tick("enqueue: segmenter chunks (wait for the chunk's event + transform from the device windows + SAM 2.1 graph + post-process)", t)
         out, rows = [None] * len(images), []
         for idxs, h, _fin in pend:
@@ -411,62 +411,25 @@ class CircuitPipeline:
                 self._reclassify([out[i] for i in idxs], src=h.src, windows=[r[2] for r in chunk])
         return out
 
-    def _enqueue_learned_dev(self, src, window, ready, slot=0):
-        """_enqueue_learned for a chunk whose windows are a DEVICE int32 [B, 4] {x0, y0, w, h} tensor (glue.stage2_crop): ordered behind the
-        event `ready` alone; masks go to a fixed-stride u8 [B, H0 * W0] block (plane b holds its window's h * w pixels at its start), so no
-        size or offset is needed on the host.  Returns a closure that waits: -> (the u8 block, extent tuples, iou [B,1])."""
-        from . import _lib
-        seg, tr = self.seg, self.tr
-        lib = _lib.load()
-        B, H0, W0 = src.shape[:3]
-        R = seg.image_size
-        with seg._lock, torch.cuda.device(seg.dev):
-            p = seg.plan(B, slot=slot)
-            sst = seg.slot_stream(slot)
-            iou = torch.empty_like(p.iou)
-            ext = torch.empty(B, 4, dtype=torch.int32, device=seg.dev)
-            ext_h = torch.empty(B, 4, dtype=torch.int32, pin_memory=True)
-            u8 = torch.empty(B, H0 * W0, dtype=torch.uint8, device=seg.dev)
-            sst.wait_stream(torch.cuda.current_stream())
-            sst.wait_event(ready)                                           # this chunk's detector pass + glue: not the tail of the detector's stream
-            for t_ in (iou, ext, u8, src, window):
-                t_.record_stream(sst)
-            with torch.cuda.stream(sst):
-                sp = sst.cuda_stream
-                _lib.check(lib.cvmi_sam2_transform_rects_dev(src.data_ptr(), H0 * W0 * 3, H0, W0, window.data_ptr(), B, p.x_in.t.data_ptr(), R, seg.dtype,
-                                                             1 if self.swap else 0, sp), "sam2_transform_rects_dev")
-                p.plan.run()
-                iou.copy_(p.iou, non_blocking=True)
-                hi = p.high_res
-                if tr.fills_small_regions:                                  # holes / sprinkles go while the logits are in HBM, before the resize
-                    hi = tr.fill_small_regions(hi)
-                    hi.record_stream(sst)
-                _lib.check(lib.cvmi_mask_postprocess_rects_dev(hi.data_ptr(), B, R, R, window.data_ptr(), H0 * W0, float(tr.mask_threshold),
-                                                               u8.data_ptr(), ext.data_ptr(), sp), "mask_postprocess_rects_dev")
-                ext_h.copy_(ext, non_blocking=True)
-                done = torch.cuda.Event()
-                done.record(sst)
-
-        def finish():
-            done.synchronize()
-            return u8, [None if x1 < 0 else (x0, y0, x1 + 1, y1 + 1) for x0, y0, x1, y1 in ext_h.tolist()], iou
-        return finish
-
-    def _enqueue_learned(self, imgs, slot=0, src=None, windows=None, det_stream=None):
+    def _enqueue_learned(self, imgs, slot=0, src=None, windows=None, det_stream=None, ready=None):
         """transform -> SAM 2.1 (learned prompts) -> resize / threshold / u8 / extent for one chunk, enqueued on the stream of segmenter plan
         `slot` (consecutive chunks alternate between two plan instances on two streams: independent images, and two segmenter graphs side by
-        side fill each other's kernel tails).  Returns a closure that waits for it: -> (u8 masks [H,W] per image, extent tuples, iou [B,1])."""
-        from . import _lib
+        side fill each other's kernel tails).  The chunk is `imgs` (host images), or the windows [(x0, y0, x1, y1) | None] of a u8 device block
+        / PackedImages `src` (the cropped chain; ordered behind `det_stream` too), or -- device glue -- the windows of `src` that a DEVICE
+        int32 [B, 4] {x0, y0, w, h} tensor names (glue.stage2_crop), ordered behind that chunk's event `ready` and not the tail of the detector's
+        stream; its masks go to a fixed-stride u8 [B, H0 * W0] block (plane b holds its window's h * w pixels at its start), so no size or
+        offset is needed on the host.  Returns a closure that waits for it: -> (u8 masks [H,W] per image -- or that block --, extent tuples,
+        iou [B,1])."""
         seg, tr = self.seg, self.tr
-        lib = _lib.load()
-        if src is not None:                                             # windows of a u8 device block / PackedImages (the cropped chain)
-            B, R = len(src), seg.image_size
+        on_device = torch.is_tensor(windows)
+        B = len(src) if src is not None else len(imgs)
+        if on_device:
+            sizes = None
+        elif src is not None:                                           # windows of a u8 device block / PackedImages (the cropped chain)
             whole = src.shapes if hasattr(src, "shapes") else [tuple(src.shape[1:3])] * B
             sizes = [whole[b] if w is None else (w[3] - w[1], w[2] - w[0]) for b, w in enumerate(windows)]
         else:
-            B, R = len(imgs), seg.image_size
             sizes = [tuple(im.shape[:2]) for im in imgs]
-        same = all(sz == sizes[0] for sz in sizes)
         with seg._lock, torch.cuda.device(seg.dev):
             p = seg.plan(B, slot=slot)
             sst = seg.slot_stream(slot)
@@ -474,21 +437,27 @@ class CircuitPipeline:
             iou = torch.empty_like(p.iou)
             ext = torch.empty(B, 4, dtype=torch.int32, device=seg.dev)
             ext_h = torch.empty(B, 4, dtype=torch.int32, pin_memory=True)
-            if same:
+            if on_device:                                                   # one plane per H0 * W0 bytes
+                stride = src.shape[1] * src.shape[2]
+                u8 = u8s = torch.empty(B, stride, dtype=torch.uint8, device=seg.dev)
+                planes = dict(window=windows, plane_stride=stride)
+            elif all(sz == sizes[0] for sz in sizes):
                 u8 = torch.empty(B, sizes[0][0], sizes[0][1], dtype=torch.uint8, device=seg.dev)
                 u8s = [u8[b] for b in range(B)]
+                planes = dict(orig_hw=sizes[0])
             else:                                                           # planes of different sizes, packed back to back: one launch
                 offs = np.concatenate(([0], np.cumsum([h * w for h, w in sizes], dtype=np.int64)))
                 u8 = torch.empty(int(offs[-1]), dtype=torch.uint8, device=seg.dev)
                 u8s = [u8[int(offs[b]):int(offs[b + 1])].view(h, w) for b, (h, w) in enumerate(sizes)]
-                sz_np = np.asarray(sizes, dtype=np.int32)
+                planes = dict(sizes=sizes)
             sst.wait_stream(torch.cuda.current_stream())
-            if det_stream is not None:
+            if on_device:
+                sst.wait_event(ready)                                       # this chunk's detector pass + glue: not the tail of the detector's stream
+            elif det_stream is not None:
                 sst.wait_stream(det_stream)                                 # (the u8 block's H2D copy: already complete -- result() waited -- but stated)
-            for t_ in (iou, ext, u8) + ((getattr(src, "data", src),) if src is not None else ()):
+            for t_ in (iou, ext, u8) + ((getattr(src, "data", src),) if src is not None else ()) + ((windows,) if on_device else ()):
                 t_.record_stream(sst)                                       # written / read on sst: the allocator must not hand them out before sst is past them
             with torch.cuda.stream(sst):
-                sp = sst.cuda_stream
                 if src is not None:
                     tr.forward_windows(src, windows, swap_rb=self.swap, out=p.x_in.t, out_dtype=seg.dtype)
                 else:
@@ -499,19 +468,14 @@ class CircuitPipeline:
                 if tr.fills_small_regions:                                  # holes / sprinkles go while the logits are in HBM, before the resize
                     hi = tr.fill_small_regions(hi)
                     hi.record_stream(sst)
-                if same:
-                    _lib.check(lib.cvmi_mask_postprocess(hi.data_ptr(), B, R, R, sizes[0][0], sizes[0][1], float(tr.mask_threshold), u8.data_ptr(),
-                                                         ext.data_ptr(), sp), "mask_postprocess")
-                else:
-                    _lib.check(lib.cvmi_mask_postprocess_sizes(hi.data_ptr(), B, R, R, sz_np.ctypes.data, float(tr.mask_threshold), u8.data_ptr(),
-                                                               ext.data_ptr(), sp), "mask_postprocess_sizes")
+                tr.mask_return(hi, out=(u8, ext), **planes)
                 ext_h.copy_(ext, non_blocking=True)
                 done = torch.cuda.Event()
                 done.record(sst)
 
         def finish():
             done.synchronize()
-            return u8s, [None if x1 < 0 else (x0, y0, x1 + 1, y1 + 1) for x0, y0, x1, y1 in ext_h.tolist()], iou
+            return u8s, tr.extents_to_boxes(ext_h), iou
         return finish
 
 

@@ -568,22 +568,18 @@ class SAM2Transforms:
         imgs = [self._check_u8(im) for im in img_list]
         B = len(imgs)
         res = torch.empty(B, R, R, 3, dtype=torch.float32, device="cuda") if out is None else out
-        sp = torch.cuda.current_stream().cuda_stream
-        if B > 1 and all(im.shape == imgs[0].shape for im in imgs):
+        if B and all(im.shape == imgs[0].shape for im in imgs):
             h, w = imgs[0].shape[:2]
             host = torch.empty(B, h, w, 3, dtype=torch.uint8, pin_memory=True)
             hv = host.numpy()
             for b, im in enumerate(imgs):
                 hv[b] = im
             src = host.to("cuda", non_blocking=True)
-            _lib.check(lib.cvmi_sam2_transform_batch(src.data_ptr(), B, h, w, res.data_ptr(), R, out_dtype, 1 if swap_rb else 0, sp), "sam2_transform")
-        elif B > 1:                                                     # ragged: one packed upload, one launch over whole-image windows
+            _lib.check(lib.cvmi_sam2_transform_batch(src.data_ptr(), B, h, w, res.data_ptr(), R, out_dtype, 1 if swap_rb else 0,
+                                                     torch.cuda.current_stream().cuda_stream), "sam2_transform")
+        elif B:                                                         # ragged: one packed upload, one launch over whole-image windows
             from .detector import PackedImages
             self._transform_srcs(PackedImages.upload(imgs, res.device), [None] * B, res, out_dtype, swap_rb)
-        elif B == 1:
-            src = torch.from_numpy(imgs[0]).cuda()
-            _lib.check(lib.cvmi_sam2_transform_batch(src.data_ptr(), 1, imgs[0].shape[0], imgs[0].shape[1], res.data_ptr(), R, out_dtype, 1 if swap_rb else 0, sp),
-                       "sam2_transform")
         return res.permute(0, 3, 1, 2) if out is None else res
 
     def _transform_srcs(self, packed, windows, res, out_dtype, swap_rb):
@@ -600,32 +596,38 @@ class SAM2Transforms:
         """`forward_batch` on a WINDOW of each image of a u8 [B, H, W, 3] DEVICE tensor, or of a `detector.PackedImages` (images of different
         sizes in one buffer) -- e.g. the block the detector's letterbox read, `PendingDetections.src`: windows = [(x0, y0, x1, y1) | None] per image, None = the whole image.  What the reference does with a host
         crop + a new transform (circuit_analyzer.py:1254 `image[y0:y1, x0:x1]`, then :347) is here a source rectangle of the resize kernel: no
-        cropped copy, no second H2D, bit-identical to transforming a contiguous copy of the window."""
+        cropped copy, no second H2D, bit-identical to transforming a contiguous copy of the window.
+        windows may also be a DEVICE int32 [B, 4] tensor of {x0, y0, w, h} rows (`glue.stage2_crop`'s `window`; u8 tensor sources only): the
+        kernel reads and clips them (cvmi_sam2_transform_rects_dev), and nothing of the call depends on a value the host has seen."""
         require_gpu()
         lib = _lib.load()
         from .detector import PackedImages
-        if isinstance(src, PackedImages):                               # images of different sizes in one packed device buffer
-            if not src.data.is_cuda:
-                raise TypeError("forward_windows expects the PackedImages on the device")
-            if len(windows) != len(src):
-                raise ValueError("one window (or None) per image")
-            R = self.resolution
-            res = torch.empty(len(src), R, R, 3, dtype=torch.float32, device=src.data.device) if out is None else out
-            self._transform_srcs(src, windows, res, out_dtype, swap_rb)
-            return res.permute(0, 3, 1, 2) if out is None else res
-        if not (torch.is_tensor(src) and src.is_cuda and src.dtype == torch.uint8 and src.dim() == 4 and src.shape[3] == 3 and src.is_contiguous()):
+        packed = isinstance(src, PackedImages)                          # images of different sizes in one packed device buffer
+        if packed and not src.data.is_cuda:
+            raise TypeError("forward_windows expects the PackedImages on the device")
+        if not packed and not (torch.is_tensor(src) and src.is_cuda and src.dtype == torch.uint8 and src.dim() == 4 and src.shape[3] == 3 and src.is_contiguous()):
             raise TypeError("forward_windows expects a contiguous uint8 [B,H,W,3] device tensor or a PackedImages")
-        B, H, W = src.shape[:3]
+        B, R = len(src), self.resolution
         if len(windows) != B:
             raise ValueError("one window (or None) per image")
-        R = self.resolution
-        rects = np.empty((B, 4), dtype=np.int32)
-        for b, wnd in enumerate(windows):
-            x0, y0, x1, y1 = (0, 0, W, H) if wnd is None else wnd
-            rects[b] = (x0, y0, x1 - x0, y1 - y0)
-        res = torch.empty(B, R, R, 3, dtype=torch.float32, device=src.device) if out is None else out
-        _lib.check(lib.cvmi_sam2_transform_rects(src.data_ptr(), H * W * 3, H, W, rects.ctypes.data, B, res.data_ptr(), R, out_dtype, 1 if swap_rb else 0,
-                                                 torch.cuda.current_stream().cuda_stream), "sam2_transform_rects")
+        res = torch.empty(B, R, R, 3, dtype=torch.float32, device=src.data.device if packed else src.device) if out is None else out
+        sw, sp = 1 if swap_rb else 0, torch.cuda.current_stream().cuda_stream
+        if packed:
+            self._transform_srcs(src, windows, res, out_dtype, swap_rb)
+        elif torch.is_tensor(windows):
+            if not (windows.is_cuda and windows.dtype == torch.int32 and tuple(windows.shape) == (B, 4) and windows.is_contiguous()):
+                raise TypeError("forward_windows expects device windows as a contiguous int32 [B,4] tensor of {x0, y0, w, h}")
+            H, W = src.shape[1:3]
+            _lib.check(lib.cvmi_sam2_transform_rects_dev(src.data_ptr(), H * W * 3, H, W, windows.data_ptr(), B, res.data_ptr(), R, out_dtype, sw, sp),
+                       "sam2_transform_rects_dev")
+        else:
+            H, W = src.shape[1:3]
+            rects = np.empty((B, 4), dtype=np.int32)
+            for b, wnd in enumerate(windows):
+                x0, y0, x1, y1 = (0, 0, W, H) if wnd is None else wnd
+                rects[b] = (x0, y0, x1 - x0, y1 - y0)
+            _lib.check(lib.cvmi_sam2_transform_rects(src.data_ptr(), H * W * 3, H, W, rects.ctypes.data, B, res.data_ptr(), R, out_dtype, sw, sp),
+                       "sam2_transform_rects")
         return res.permute(0, 3, 1, 2) if out is None else res
 
     @property
@@ -656,23 +658,52 @@ class SAM2Transforms:
                                                 y.data_ptr(), ws.data_ptr(), torch.cuda.current_stream().cuda_stream), "mask_fill_small")
         return y
 
-    def postprocess_to_masks_sized(self, masks, sizes):
+    def _logits(self, masks):
+        """What every post-process starts with: the logits as contiguous f32 on the device, small holes and sprinkles removed."""
+        require_gpu()
+        m = masks.float().contiguous()
+        return self.fill_small_regions(m if m.is_cuda else m.cuda())
+
+    def mask_return(self, logits, orig_hw=None, sizes=None, window=None, plane_stride=None, out=None):
+        """The one launch under postprocess_to_mask_async / _masks_sized / _windows_async, for a caller that has run the prologue itself
+        (`CircuitPipeline`): logits f32 [..., h, w], contiguous, on the device -> (u8 block, extent int32 [N,4]) on the current stream.  Exactly
+        one of orig_hw = (H, W) for every plane, sizes = [(H, W)] per plane (packed back to back), window = a DEVICE int32 [N,4] tensor of
+        {x0, y0, w, h} with plane n at n * plane_stride bytes.  The three resample a plane to the same bits.  out = (u8, extent): write into
+        these (any shape with the bytes the form needs) instead of fresh tensors."""
+        lib = _lib.load()
+        h, w = logits.shape[-2:]
+        N = logits.numel() // max(1, h * w)
+        thr, sp = float(self.mask_threshold), torch.cuda.current_stream().cuda_stream
+        u8, ext = out if out is not None else (None, torch.empty(N, 4, dtype=torch.int32, device=logits.device))
+        if orig_hw is not None:
+            H, W = int(orig_hw[0]), int(orig_hw[1])
+            u8 = torch.empty(*logits.shape[:-2], H, W, dtype=torch.uint8, device=logits.device) if u8 is None else u8
+            _lib.check(lib.cvmi_mask_postprocess(logits.data_ptr(), N, h, w, H, W, thr, u8.data_ptr(), ext.data_ptr(), sp), "mask_postprocess")
+        elif sizes is not None:
+            if len(sizes) != N:
+                raise ValueError("one (H, W) per mask plane")
+            sz = np.asarray(sizes, dtype=np.int32).reshape(N, 2)
+            u8 = torch.empty(int((sz[:, 0].astype(np.int64) * sz[:, 1]).sum()), dtype=torch.uint8, device=logits.device) if u8 is None else u8
+            _lib.check(lib.cvmi_mask_postprocess_sizes(logits.data_ptr(), N, h, w, sz.ctypes.data, thr, u8.data_ptr(), ext.data_ptr(), sp), "mask_postprocess_sizes")
+        else:
+            u8 = torch.empty(N, int(plane_stride), dtype=torch.uint8, device=logits.device) if u8 is None else u8
+            _lib.check(lib.cvmi_mask_postprocess_rects_dev(logits.data_ptr(), N, h, w, window.data_ptr(), int(plane_stride), thr, u8.data_ptr(), ext.data_ptr(), sp),
+                       "mask_postprocess_rects_dev")
+        return u8, ext
+
+    def postprocess_to_masks_sized(self, masks, sizes, out=None):
         """postprocess_to_mask_async for planes that return to DIFFERENT sizes (every image its own crop window): masks f32 [N,1,h,w] on the
         device, sizes = [(H, W)] per plane -> ([u8 [H_n, W_n] views of ONE packed buffer], extent int32 [N,4]); one launch, nothing copied to
         the host."""
-        require_gpu()
-        lib = _lib.load()
-        m = self.fill_small_regions(masks.float().contiguous())
-        N, h, w = m.shape[0] * m.shape[1], m.shape[-2], m.shape[-1]
-        if len(sizes) != N:
-            raise ValueError("one (H, W) per mask plane")
-        sz = np.asarray(sizes, dtype=np.int32).reshape(N, 2)
-        offs = np.concatenate(([0], np.cumsum(sz[:, 0].astype(np.int64) * sz[:, 1])))
-        u8 = torch.empty(int(offs[-1]), dtype=torch.uint8, device=m.device)
-        ext = torch.empty(N, 4, dtype=torch.int32, device=m.device)
-        _lib.check(lib.cvmi_mask_postprocess_sizes(m.data_ptr(), N, h, w, sz.ctypes.data, float(self.mask_threshold), u8.data_ptr(), ext.data_ptr(),
-                                                   torch.cuda.current_stream().cuda_stream), "mask_postprocess_sizes")
-        return [u8[int(offs[n]):int(offs[n + 1])].view(int(sz[n, 0]), int(sz[n, 1])) for n in range(N)], ext
+        u8, ext = self.mask_return(self._logits(masks), sizes=sizes, out=out)
+        offs = np.concatenate(([0], np.cumsum([int(H) * int(W) for H, W in sizes], dtype=np.int64)))
+        return [u8.view(-1)[int(offs[n]):int(offs[n + 1])].view(int(H), int(W)) for n, (H, W) in enumerate(sizes)], ext
+
+    def postprocess_to_windows_async(self, masks, window, plane_stride, out=None):
+        """postprocess_to_mask_async with the sizes on the DEVICE: plane n returns to the {w, h} of window[n] = {x0, y0, w, h} (int32 [N,4],
+        `glue.stage2_crop`'s) at the start of row n of a u8 [N, plane_stride] block (plane_stride = H0 * W0 of the uncropped image), clipped
+        to its stride; no size or offset is needed on the host.  -> (the u8 block, extent int32 [N,4])."""
+        return self.mask_return(self._logits(masks), window=window, plane_stride=plane_stride, out=out)
 
     def mask_extent(self, mask_u8):
         """Bounding boxes of binary masks [N,H,W] / [B,C,H,W] (u8 on the device): list of (x0, y0, x1, y1) or None per
@@ -709,12 +740,8 @@ class SAM2Transforms:
         return self.transform_coords(torch.as_tensor(boxes, dtype=torch.float32).reshape(-1, 2, 2), normalize, orig_hw)
 
     def postprocess_masks(self, masks, orig_hw, return_u8=False):
-        require_gpu()
         lib = _lib.load()
-        m = masks.float().contiguous()
-        if not m.is_cuda:
-            m = m.cuda()
-        m = self.fill_small_regions(m)
+        m = self._logits(masks)
         B, C, h, w = m.shape
         H, W = int(orig_hw[0]), int(orig_hw[1])
         out = torch.empty(B, C, H, W, dtype=torch.float32, device=m.device)
@@ -723,22 +750,10 @@ class SAM2Transforms:
                                          float(self.mask_threshold), torch.cuda.current_stream().cuda_stream), "bilinear")
         return (out, u8) if return_u8 else out
 
-    def postprocess_to_mask_async(self, masks, orig_hw):
+    def postprocess_to_mask_async(self, masks, orig_hw, out=None):
         """The device half of postprocess_to_mask: -> (mask_u8 [B,C,H,W], extent int32 [B*C,4]) enqueued on the current stream, nothing
         copied to the host (extents_to_boxes(extent) does that, later, for a whole batch at once)."""
-        require_gpu()
-        lib = _lib.load()
-        m = masks.float().contiguous()
-        if not m.is_cuda:
-            m = m.cuda()
-        m = self.fill_small_regions(m)
-        B, C, h, w = m.shape
-        H, W = int(orig_hw[0]), int(orig_hw[1])
-        u8 = torch.empty(B, C, H, W, dtype=torch.uint8, device=m.device)
-        ext = torch.empty(B * C, 4, dtype=torch.int32, device=m.device)
-        _lib.check(lib.cvmi_mask_postprocess(m.data_ptr(), B * C, h, w, H, W, float(self.mask_threshold), u8.data_ptr(), ext.data_ptr(),
-                                             torch.cuda.current_stream().cuda_stream), "mask_postprocess")
-        return u8, ext
+        return self.mask_return(self._logits(masks), orig_hw=orig_hw, out=out)
 
     def postprocess_to_mask(self, masks, orig_hw):
         """circuit_analyzer.py:354-370 in one pass on the device: bilinear resize to orig_hw -> `> mask_threshold` -> u8 {0, 255}

@@ -469,7 +469,10 @@ int cvmi_mask_prompt_embed_pairs(const float* mask, const float* emb, const floa
                                  const int* pair_image, int fs, cvmi_stream_t stream);
 
 /* F.interpolate(bilinear, align_corners=False) of f32 planes [N,h,w] -> [N,H,W] (sam2_infer.py:263-268,
- * postprocess_masks :127).  mask_u8 (optional): also writes (value > thresh) ? 255 : 0. */
+ * postprocess_masks :127).  mask_u8 (optional): also writes (value > thresh) ? 255 : 0.
+ * This call, cvmi_mask_postprocess, cvmi_mask_postprocess_sizes and cvmi_mask_postprocess_rects_dev are one kernel body with the roundings of
+ * the sampled value written out (csrc/bilinear.hpp: bil_mix): the four forms resample a plane to the same bits, so a mask is (map > thresh)
+ * of the map this call writes, pixel for pixel, whichever of them produced it. */
 int cvmi_bilinear_f32(const float* x, int N, int h, int w, float* y, int H, int W, uint8_t* mask_u8,
                       float thresh, cvmi_stream_t stream);   /* y may be NULL when mask_u8 is given */
 
@@ -571,7 +574,8 @@ int cvmi_sam2_transform_batch(const uint8_t* src, int B, int H, int W, void* dst
  * (CircuitAnalyzer.crop_image_and_adjust_bboxes, circuit_analyzer.py:937-1284, called with padding = 80 at analysis_pipeline.py:177; the
  * cropped image is what segment_with_sam2 :206 then resizes), WITHOUT a cropped copy: image b is the window rects[b] = {x0, y0, w, h} of the
  * u8 [H, W, 3] image at src + b * src_image_stride BYTES (0: every window comes from one image), and exactly the pixels of the window take
- * part in the antialiased resize -- bit-identical to cvmi_sam2_transform on a contiguous copy of the window.  rects is a HOST array
+ * part in the antialiased resize -- bit-identical to cvmi_sam2_transform on a contiguous copy of the window (every form of the transform is
+ * one kernel body that is handed its window; the equal-size batch hands it the whole image).  rects is a HOST array
  * (B x 4 ints, read during the call; it travels in the kernel arguments).  The source may be the buffer the detector's letterbox read. */
 int cvmi_sam2_transform_rects(const uint8_t* src, long long src_image_stride, int H, int W, const int* rects, int B, void* dst, int R,
                               int dst_dtype, int swap_rb, cvmi_stream_t stream);

@@ -31,7 +31,7 @@ NMS_ROWS / DECODE_ROWS: the detector's tail (nms.hip, vision_ops.hip cvmi_detect
 instance nms_launch must tag and the decisions nms_pick -- a mirror of nms_launch and of yolo_nms_kernel's data-dependent branches -- derives from it; one
 decode row = one launch per dtype with its stated seams.  Generators, references, mutants and the decode bound live in tests/detect_ref.py.
 
-RESAMPLE_ROWS: the resampling kernels of sam_ops.hip (the five forms of cvmi_sam2_transform*, the four forms of the bilinear mask return and
+RESAMPLE_ROWS: the resampling kernels of resample.hip (the five forms of cvmi_sam2_transform*, the four forms of the bilinear mask return and
 cvmi_mask_extent).  One row = the sources, windows or sizes of one call and the entry forms, output types and swap_rb values it runs through; the
 constants the rows were built from (AA_MAXTAPS, RECT_MAX, the grid caps) mirror the source text.  Operands, references, mutants and bounds live in
 tests/resample_ref.py.
@@ -329,8 +329,6 @@ BF16_OPS = {
     "cvmi_nchw_to_nhwc": ("test_bf16_ops_gpu.py", "test_nchw_to_nhwc_bf16"),
     "cvmi_prompt_tokens": ("test_bf16_ops_gpu.py", "test_prompt_tokens_bf16"),
     "cvmi_hyper_masks": ("test_bf16_ops_gpu.py", "test_hyper_masks_bf16"),
-    "cvmi_sam2_transform_batch": ("test_crop_gpu.py", "test_transform_from_windows_is_bit_identical_to_transforming_crops"),
-    "cvmi_sam2_transform_rects": ("test_crop_gpu.py", "test_transform_from_windows_is_bit_identical_to_transforming_crops"),
     "cvmi_hiera_mlp": ("test_ops_gpu.py", "test_hiera_mlp_fused_vs_torch"),
     "cvmi_hiera_mlp_stats": ("test_ops_gpu.py", "test_hiera_mlp_fused_vs_torch"),
     "cvmi_tok_linear": ("test_ops_gpu.py", "test_tok_linear_vs_torch"),
@@ -951,10 +949,10 @@ DETECT_MUTANT_ROWS = {
 DETECT_UNSEEN_MUTANTS = {}
 
 
-# ---- the resampling kernels: the five forms of cvmi_sam2_transform* and the bilinear mask return (sam_ops.hip) ------------------------------------
+# ---- the resampling kernels: the five forms of cvmi_sam2_transform* and the bilinear mask return (resample.hip) -----------------------------------
 # One transform row = a list of source images (H, W), a list of items (image, x0, y0, w, h) -- output b of the launch is that window of that
 # image -- and the entry forms, output types and swap_rb values it runs through.  One mask-return row = one source shape and what it returns to.
-# Operands, references, mutants and the bounds live in tests/resample_ref.py.  The constants below mirror sam_ops.hip
+# Operands, references, mutants and the bounds live in tests/resample_ref.py.  The constants below mirror resample.hip
 # (tests/test_op_coverage_cpu.py holds them to the source text).
 AA_MAXTAPS = 24                                    # taps per axis aa_axis keeps; the host guards refuse 2 * max(scale, 1) + 2 > AA_MAXTAPS
 RECT_MAX = 64                                      # windows / rows / sizes per launch of the table-by-value entry points

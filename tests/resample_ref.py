@@ -1,4 +1,4 @@
-"""Plain references of the resampling kernels in sam_ops.hip -- the antialiased input transform (cvmi_sam2_transform and its batch / rects /
+"""Plain references of the resampling kernels in resample.hip -- the antialiased input transform (cvmi_sam2_transform and its batch / rects /
 rects_dev / srcs forms) and the bilinear mask return (cvmi_bilinear_f32, cvmi_mask_postprocess and its sizes / rects_dev forms,
 cvmi_mask_extent) -- the seeded operands of every row of op_matrix.RESAMPLE_ROWS and the bounds the resampling matrix
 (tests/test_resample_matrix_gpu.py) holds the kernels to.  CPU only, numpy and plain torch: importing this module needs neither a GPU nor the

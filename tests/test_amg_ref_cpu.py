@@ -176,5 +176,5 @@ def test_entry_points_are_declared_and_bound():
     assert names == [n for n, _ in _lib.AMG_RECORD] and np.dtype(_lib.AMG_RECORD).itemsize == 4 * len(names)
     text = open(os.path.join(CSRC, "mask_amg.hip")).read()
     assert "CVMI_ENTRY" not in text and "getenv" not in text
-    assert '#include "bilinear.hpp"' in text and '#include "bilinear.hpp"' in open(os.path.join(CSRC, "sam_ops.hip")).read()
+    assert '#include "bilinear.hpp"' in text and all('#include "bilinear.hpp"' in open(os.path.join(CSRC, f)).read() for f in ("resample.hip", "sam_ops.hip"))
     assert "mask_amg.o" in open(os.path.join(CSRC, "Makefile")).read()

@@ -749,15 +749,15 @@ def test_a_removed_detect_row_or_a_moved_threshold_is_caught():
         assert detect_gaps(probe) == [f"{name} no longer tags its launch with {text}"]
 
 
-# ---- the resampling kernels: sam_ops.hip cvmi_sam2_transform* and the bilinear mask return ------------------------------------------------------
+# ---- the resampling kernels: resample.hip cvmi_sam2_transform* and the bilinear mask return -----------------------------------------------------
 RESAMPLE_ENTRY_RE = r"cvmi_sam2_transform\w*|cvmi_mask_postprocess\w*|cvmi_bilinear_f32|cvmi_mask_extent"
-RESAMPLE_TYPES = {"f16": ("f16", "bf16"), "float": ("f32",), "_Float16": ("f16",), "__bf16": ("bf16",)}     # f16: the dual build's operand type
+RESAMPLE_TYPES = {"f16": ("f16", "bf16"), "float": ("f32",), "_Float16": ("f16",), "__bf16": ("bf16",)}     # f16: a dual build's operand type (none today)
 RESAMPLE_CAP_KIND = {"cvmi_bilinear_f32": "bilinear", "cvmi_mask_postprocess": "bilinear", "cvmi_mask_postprocess_sizes": "bilinear",
                      "cvmi_mask_postprocess_rects_dev": "bilinear", "cvmi_mask_extent": "mask_extent"}       # every other entry: "transform"
 
 
 def resample_entries(text):
-    """{entry: (dual built, body)} of every extern "C" definition in sam_ops.hip whose name matches RESAMPLE_ENTRY_RE (prototypes are skipped)."""
+    """{entry: (dual built, body)} of every extern "C" definition in resample.hip whose name matches RESAMPLE_ENTRY_RE (prototypes are skipped)."""
     out = {}
     for m in re.finditer(r'extern "C" int (CVMI_ENTRY\()?(cvmi_\w+)\)?\(([^{;]*)\)\s*(\{|;)', text):
         if m.group(4) == "{" and re.fullmatch(RESAMPLE_ENTRY_RE, m.group(2)):
@@ -766,7 +766,7 @@ def resample_entries(text):
 
 
 def resample_constants(text):
-    """(AA_MAXTAPS, RECT_MAX, {entry: work items of one pass of each capped grid it launches}) as sam_ops.hip states them."""
+    """(AA_MAXTAPS, RECT_MAX, {entry: work items of one pass of each capped grid it launches}) as resample.hip states them."""
     taps = int(re.search(r"constexpr int AA_MAXTAPS = (\d+);", text).group(1))
     rect = int(re.search(r"constexpr int RECT_MAX = (\d+);", text).group(1))
     block, a, b = (int(v) for v in re.search(r"inline int grid_for\(long long total, int block = (\d+), int cap = (\d+) \* (\d+)\)", text).groups())
@@ -791,17 +791,20 @@ def resample_gaps(text, rows=RESAMPLE_ROWS):
     gaps = []
     taps, rect, caps = resample_constants(text)
     if taps != AA_MAXTAPS:
-        gaps.append(f"AA_MAXTAPS is {taps} in sam_ops.hip, op_matrix mirrors {AA_MAXTAPS}")
+        gaps.append(f"AA_MAXTAPS is {taps} in resample.hip, op_matrix mirrors {AA_MAXTAPS}")
     if rect != RECT_MAX:
-        gaps.append(f"RECT_MAX is {rect} in sam_ops.hip, op_matrix mirrors {RECT_MAX}")
+        gaps.append(f"RECT_MAX is {rect} in resample.hip, op_matrix mirrors {RECT_MAX}")
     entries = resample_entries(text)
     form_of = {e: f for f, e in list(TRANSFORM_ENTRY.items()) + list(MASK_ENTRY.items())}
-    gaps += [f"op_matrix names {e}, which sam_ops.hip no longer defines" for e in sorted(set(form_of) - set(entries))]
+    macro = re.search(r"#define LAUNCH_TRANSFORM\(kernel,(?:[^\n]*\\\n)*[^\n]*\n", text)
+    launcher_types = re.findall(r"hipLaunchKernelGGL\(kernel<([\w ]+)>", macro.group(0)) if macro else []
+    gaps += [f"op_matrix names {e}, which resample.hip no longer defines" for e in sorted(set(form_of) - set(entries))]
 
     def launched(name, seen=()):
         """Output-type instances an entry launches, through the entry it forwards to if it has no launch of its own."""
         dual, body = entries[name]
         inst = [(k, t, dual) for k, t in re.findall(r"hipLaunchKernelGGL\(\(?(sam2_transform\w*_kernel)<([\w ]+)>", body)]
+        inst += [(k, t, dual) for k in re.findall(r"LAUNCH_TRANSFORM\((sam2_transform\w*_kernel),", body) for t in launcher_types]      # the three-type launcher
         fwd = re.search(r"return (cvmi_\w+)\(", body)
         return inst or (launched(fwd.group(1), seen + (name,)) if fwd and fwd.group(1) in entries and fwd.group(1) not in seen else [])
 
@@ -828,28 +831,33 @@ def resample_gaps(text, rows=RESAMPLE_ROWS):
     return gaps
 
 
-def _sam_ops():
-    return open(os.path.join(CSRC, "sam_ops.hip")).read()
+def _resample_hip():
+    return open(os.path.join(CSRC, "resample.hip")).read()
 
 
-def test_resample_rows_mirror_sam_ops_and_cover_every_entry_and_type_instance():
-    text = _sam_ops()
+def test_resample_rows_mirror_resample_hip_and_cover_every_entry_and_type_instance():
+    text = _resample_hip()
     entries = resample_entries(text)
-    assert set(entries) == set(TRANSFORM_ENTRY.values()) | set(MASK_ENTRY.values()), sorted(entries)       # the parser still finds the nine entry points
-    assert {e for e, (dual, _) in entries.items() if dual} == {"cvmi_sam2_transform_batch", "cvmi_sam2_transform_rects"}
+    assert set(entries) == set(TRANSFORM_ENTRY.values()) | set(MASK_ENTRY.values()), sorted(entries)       # the parser still finds the ten entry points
+    # no resampling entry is dual-built: the file is compiled once, every kernel instantiated for the three output types in that one build
+    assert not [e for e, (dual, _) in entries.items() if dual] and "CVMI_ENTRY" not in text and "CVMI_OPERAND_BF16" not in text and "_bf16(" not in text
+    makefile = open(os.path.join(CSRC, "Makefile")).read()
+    assert re.search(r"\bresample\.o\b", makefile) and "resample_bf16.o" not in makefile
+    others = "".join(open(p).read() for p in glob.glob(os.path.join(CSRC, "*.hip")) if os.path.basename(p) != "resample.hip")
+    assert not re.search(r'extern "C" int (?:CVMI_ENTRY\()?(?:%s)\)?\(' % RESAMPLE_ENTRY_RE, others)           # ... and no other file defines or forwards one
     taps, rect, caps = resample_constants(text)
     assert (taps, rect) == (AA_MAXTAPS, RECT_MAX) == (24, 64)
     assert caps["cvmi_sam2_transform_batch"] == {RESAMPLE_GRID_CAP["transform"]} == {4096 * 256} and caps["cvmi_sam2_transform"] == set()
     assert caps["cvmi_mask_postprocess_rects_dev"] == {RESAMPLE_GRID_CAP["bilinear"]} == {1024 * 256} and caps["cvmi_mask_extent"] == {RESAMPLE_GRID_CAP["mask_extent"]} == {32 * 256}
     assert resample_gaps(text) == [], resample_gaps(text)
-    # the dual-built entries launch <f16> and <float>, the single-copy ones all three: every one of them is a (form, type) some row runs
+    # every entry launches all three output types: every one of them is a (form, type) some row runs
     for form in ("single", "batch", "rects", "rects_dev", "srcs"):
         have = {dt for r in RESAMPLE_ROWS if form in r["forms"] and not _refuses(r, form) for dt in r["dtypes"]}
         assert have == {"f16", "bf16", "f32"}, (form, have)
 
 
 def test_a_new_resampling_entry_a_removed_row_or_a_moved_constant_is_caught():
-    text = _sam_ops()
+    text = _resample_hip()
     probe = text + '\nextern "C" int cvmi_sam2_transform_foo(const uint8_t* src, void* dst, cvmi_stream_t stream_) {\n  return 0;\n}\n'
     assert resample_gaps(probe) == ["cvmi_sam2_transform_foo has no rows in op_matrix.RESAMPLE_ROWS"]
     probe = text + '\nextern "C" int cvmi_mask_postprocess_foo(const float* x) {\n  return 0;\n}\n'
@@ -873,9 +881,9 @@ def test_a_new_resampling_entry_a_removed_row_or_a_moved_constant_is_caught():
         return resample_gaps(text, rows)
 
     assert no_bf16("srcs") == ["cvmi_sam2_transform_srcs: sam2_transform_srcs_kernel<__bf16> (bf16) has no row that launches it"]
-    assert no_bf16("rects") == ["cvmi_sam2_transform_rects: sam2_transform_rects_kernel<f16> (bf16) has no row that launches it"]
-    assert resample_gaps(text.replace("constexpr int AA_MAXTAPS = 24;", "constexpr int AA_MAXTAPS = 32;")) == ["AA_MAXTAPS is 32 in sam_ops.hip, op_matrix mirrors 24"]
-    assert resample_gaps(text.replace("constexpr int RECT_MAX = 64;", "constexpr int RECT_MAX = 128;")) == ["RECT_MAX is 128 in sam_ops.hip, op_matrix mirrors 64"]
+    assert no_bf16("rects") == ["cvmi_sam2_transform_rects: sam2_transform_rects_kernel<__bf16> (bf16) has no row that launches it"]
+    assert resample_gaps(text.replace("constexpr int AA_MAXTAPS = 24;", "constexpr int AA_MAXTAPS = 32;")) == ["AA_MAXTAPS is 32 in resample.hip, op_matrix mirrors 24"]
+    assert resample_gaps(text.replace("constexpr int RECT_MAX = 64;", "constexpr int RECT_MAX = 128;")) == ["RECT_MAX is 128 in resample.hip, op_matrix mirrors 64"]
     moved = text.replace("int cap = 256 * 16)", "int cap = 256 * 32)")
     assert moved != text and any("cvmi_sam2_transform_srcs caps a grid at [2097152] work items" in g for g in resample_gaps(moved))
     moved = text.replace("grid_for((long long)H * W, 256, 32)", "grid_for((long long)H * W, 256, 64)")
