@@ -159,6 +159,10 @@ SIGNATURES = {
     "cvmi_mask_cc_workspace": (C.c_size_t, [_i, _i, _i]),
     "cvmi_mask_components": (_i, [_vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
     "cvmi_mask_fill_small": (_i, [_vp, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp]),
+    "cvmi_mask_remove_small_workspace": (C.c_size_t, [_i, _i, _i]),
+    "cvmi_mask_remove_small": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "cvmi_mask_rle_workspace": (C.c_size_t, [_i, _i, _i]),
+    "cvmi_mask_rle": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, C.c_size_t, _vp]),
     "cvmi_node_prepare": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cvmi_enhance_lines": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
     "cvmi_contours_workspace": (C.c_size_t, [_i, _vp]),

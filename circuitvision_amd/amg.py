@@ -7,7 +7,7 @@ are turned into masks (cvmi_amg_score's mask mode, so `area` and `bbox` describe
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, amg_utils
 from .sam2_infer import SAM2Transforms, Sam2Embeddings
 
 OUTPUT_KEYS = ("segmentation", "area", "bbox", "predicted_iou", "point_coords", "stability_score", "crop_box")
@@ -39,7 +39,24 @@ class Sam2AutomaticMaskGenerator:
 
     The host waits once per sub-batch of `generate_batch` for what this class launches: after the last chunk and the NMS are enqueued, to
     read the kept counts and the records.  (`infer_masks` itself synchronises its stream at the end of every call, as for every caller; no
-    value travels through the host between the chunks.)"""
+    value travels through the host between the chunks.)
+
+    Two of upstream's constructor options are PER-CALL arguments of `generate` / `generate_batch` here, so that one generator and one plan
+    serve a different output form per request (the constructor still refuses them, with `crop_n_layers`, `use_m2m` and a non-default
+    `output_mode`):
+      min_mask_region_area > 0   upstream's postprocess_small_regions after the first NMS (amg_utils.py: holes below the area filled, then
+                                 islands below it removed, on the GPU; every box recomputed; a second box NMS with box_nms_thresh in which an
+                                 unchanged mask outranks a changed one).  The list comes back in that NMS's order -- unchanged masks first, each
+                                 group by predicted IoU -- and `segmentation`, `area`, `bbox` describe the final plane.
+      output_mode                "binary_mask" (default), or "uncompressed_rle": `segmentation` = {"size": [H, W], "counts": [...]} (column-major
+                                 runs starting with a run of zeros; amg_utils.rle_to_mask decodes), `area` = amg_utils.area_from_rle of it.  The
+                                 H x W planes are then built and encoded in chunks of at most amg_utils.MASK_CHUNK_BYTES and never all held.
+                                 "coco_rle" raises NotImplementedError: its string form is pycocotools', which is not available to check against.
+    With both at their defaults the path is the one above: no extra launch, no extra wait.  Otherwise everything either option needs is
+    enqueued for all images of the sub-batch -- the planes, cvmi_mask_remove_small, the second cvmi_yolo_nms, cvmi_mask_rle with a capacity
+    guess -- and the host waits ONCE more per sub-batch, for the second NMS's keep lists and the planes' info (min_mask_region_area) and
+    the RLE offsets and counts (uncompressed_rle) together: one added wait whichever options are set.  A chunk of planes with more than
+    amg_utils.RLE_RUNS_PER_COLUMN runs per column on average is encoded a second time with the exact capacity, with a wait of its own."""
 
     def __init__(self, model, points_per_side=32, points_per_batch=64, pred_iou_thresh=0.8, stability_score_thresh=0.95,
                  stability_score_offset=1.0, mask_threshold=0.0, box_nms_thresh=0.7, point_grids=None, multimask_output=True, max_candidates=None,
@@ -47,11 +64,13 @@ class Sam2AutomaticMaskGenerator:
         if crop_n_layers > 0:
             raise NotImplementedError("crop_n_layers > 0: only the single full-image crop is built")
         if min_mask_region_area > 0:
-            raise NotImplementedError("min_mask_region_area > 0: small-region removal after NMS is not built")
+            raise NotImplementedError("min_mask_region_area > 0 is a per-call argument here: generate(image, min_mask_region_area=...) / "
+                                      "generate_batch(..., min_mask_region_area=...), or amg_utils.postprocess_small_regions on a returned list")
         if use_m2m:
             raise NotImplementedError("use_m2m=True: the mask-to-mask refinement pass is not built")
         if output_mode != "binary_mask":
-            raise NotImplementedError(f"output_mode={output_mode!r}: RLE outputs are not built, only 'binary_mask'")
+            raise NotImplementedError(f"output_mode={output_mode!r} is a per-call argument here: generate(image, output_mode='uncompressed_rle') / "
+                                      "generate_batch(..., output_mode=...), or amg_utils.mask_to_rle on returned planes ('coco_rle' is not built)")
         if (points_per_side is None) == (point_grids is None):
             raise ValueError("exactly one of points_per_side and point_grids must be given")
         if point_grids is not None:
@@ -84,15 +103,23 @@ class Sam2AutomaticMaskGenerator:
         self.points_in = torch.from_numpy(grid.astype(np.float32)) * float(model.image_size)
 
     # -- public surface
-    def generate(self, image):
-        """image: RGB u8 [H, W, 3] (array or PIL) -> list of dicts."""
+    def generate(self, image, min_mask_region_area=0, output_mode="binary_mask"):
+        """image: RGB u8 [H, W, 3] (array or PIL) -> list of dicts.  min_mask_region_area, output_mode: see the class."""
         img = self.transforms._check_u8(image)
-        return self.generate_batch([img])[0]
+        return self.generate_batch([img], min_mask_region_area=min_mask_region_area, output_mode=output_mode)[0]
 
-    def generate_batch(self, images, orig_hw=None):
+    def generate_batch(self, images, orig_hw=None, min_mask_region_area=0, output_mode="binary_mask"):
         """images: a list of RGB u8 [H, W, 3] images (orig_hw then defaults to their sizes), a [B, 3, R, R] tensor as `infer_masks` takes it, or
         the `Sam2Embeddings` `encode_images` made of one; orig_hw = [(H, W)] per image.  -> one list of dicts per image."""
         model = self.model
+        if output_mode == "coco_rle":
+            raise NotImplementedError("output_mode='coco_rle': the compressed string form is pycocotools', which is not available to check an "
+                                      "encoder against; 'uncompressed_rle' carries the same runs")
+        if output_mode not in ("binary_mask", "uncompressed_rle"):
+            raise ValueError(f"output_mode must be 'binary_mask' or 'uncompressed_rle', not {output_mode!r}")
+        min_area = int(min_mask_region_area)
+        if min_area < 0:
+            raise ValueError("min_mask_region_area must be >= 0")
         if isinstance(images, (list, tuple)):
             imgs = [self.transforms._check_u8(im) for im in images]
             if orig_hw is None:
@@ -114,7 +141,7 @@ class Sam2AutomaticMaskGenerator:
         for a in range(0, B, step):
             src = images[a:a + step]
             emb = src if isinstance(src, Sam2Embeddings) else model.encode_images(src)
-            out += self._generate(emb, sizes[a:a + step])
+            out += self._generate(emb, sizes[a:a + step], min_area, output_mode)
         return out
 
     # -- one sub-batch
@@ -149,7 +176,7 @@ class Sam2AutomaticMaskGenerator:
                                                records[b].data_ptr(), pool[b].data_ptr(), block[b].data_ptr(), sp), "amg_select")
         return dict(counter=counter, records=records, pool=pool, block=block)
 
-    def _generate(self, emb, sizes):
+    def _generate(self, emb, sizes, min_area=0, output_mode="binary_mask"):
         """Candidates, NMS, the single host wait, then the survivors' masks."""
         lib, model = _lib.load(), self.model
         B, cap, f0 = len(emb), self.cap, model.image_size // 4
@@ -176,6 +203,8 @@ class Sam2AutomaticMaskGenerator:
             if int(counts[:, 0].max()) > cap:
                 raise RuntimeError(f"{int(counts[:, 0].max())} candidates passed the filters but max_candidates = {cap}: raise max_candidates "
                                    "(or the thresholds)")
+            if min_area > 0 or output_mode != "binary_mask":
+                return self._finish_with_options(sizes, pool, keep_idx, kept_n, kept_idx, recs, min_area, output_mode)
             out = []
             for b, (H, W) in enumerate(sizes):
                 K = int(kept_n[b])
@@ -196,3 +225,60 @@ class Sam2AutomaticMaskGenerator:
                                   "stability_score": float(r["stability"]), "crop_box": [0, 0, W, H]})
                 out.append(dicts)
             return out
+
+    # -- the per-call options
+    def _masks(self, low_planes, H, W):
+        """u8 [K, H, W] planes of the kept candidates' low-res planes (cvmi_amg_score's mask mode), enqueued."""
+        lib, f0 = _lib.load(), self.model.image_size // 4
+        lo, mid, hi = self.levels
+        K = int(low_planes.shape[0])
+        masks = torch.empty(K, H, W, dtype=torch.uint8, device=low_planes.device)
+        fstats = torch.empty(K, 8, dtype=torch.int32, device=low_planes.device)
+        _lib.check(lib.cvmi_amg_score(low_planes.data_ptr(), K, f0, f0, H, W, lo, mid, hi, fstats.data_ptr(), masks.data_ptr(),
+                                      torch.cuda.current_stream().cuda_stream), "amg_score")
+        return masks
+
+    def _finish_with_options(self, sizes, pool, keep_idx, kept_n, kept_idx, recs, min_area, output_mode):
+        """After the first NMS's wait: per image the survivors' planes (all of them, or chunk by chunk in the RLE mode), small-region removal,
+        the second NMS and the encoding are enqueued; ONE wait for the whole sub-batch; then the dicts."""
+        rle = output_mode == "uncompressed_rle"
+        work = []
+        for b, (H, W) in enumerate(sizes):
+            K = int(kept_n[b])
+            if K == 0:
+                work.append(None)
+                continue
+            low = pool[b].index_select(0, keep_idx[b, :K].long())
+            step = max(1, amg_utils.MASK_CHUNK_BYTES // (H * W)) if rle else K
+            masks, infos, pending = None, [], []
+            for a in range(0, K, step):
+                def build(a=a, H=H, W=W, low=low, step=step):
+                    m = self._masks(low[a:a + step], H, W)
+                    return m, (amg_utils.remove_small_enqueue(m, min_area, amg_utils.PHASES["both"]) if min_area > 0 else None)
+                masks, info = build()
+                infos.append(info)
+                if rle:
+                    pending.append(amg_utils.PendingRle(masks, rebuild=lambda build=build: build()[0]))
+                    masks = None                                                 # the chunk's planes are free again once the stream has passed them
+            nms = amg_utils.SecondNms(torch.cat(infos), self.box_nms_thresh) if min_area > 0 else None
+            work.append((K, masks, pending, nms))
+        torch.cuda.current_stream().synchronize()
+        out = []
+        for b, (H, W) in enumerate(sizes):
+            if work[b] is None:
+                out.append([])
+                continue
+            K, masks, pending, nms = work[b]
+            order, info = nms.finish() if nms is not None else (range(K), None)
+            segs = [r for p in pending for r in p.finish()] if rle else masks
+            dicts = []
+            for k in order:
+                r = recs[b, int(kept_idx[b, k])]
+                x0, y0, x1, y1 = int(r["x0"]), int(r["y0"]), int(r["x1"]), int(r["y1"])
+                gx, gy = self.grid[int(r["point"])]
+                d = {"segmentation": segs[k], "area": int(r["area"]), "bbox": [x0, y0, x1 - x0, y1 - y0],
+                     "predicted_iou": float(r["score"]), "point_coords": [[float(gx * W), float(gy * H)]],
+                     "stability_score": float(r["stability"]), "crop_box": [0, 0, W, H]}
+                dicts.append(amg_utils.survivor(d, segs[k], info[k]) if info is not None else d)
+            out.append(dicts)
+        return out

@@ -549,6 +549,36 @@ int cvmi_mask_components(const float* x, int N, int h, int w, float thresh, int*
 int cvmi_mask_fill_small(const float* x, int N, int h, int w, float thresh, float max_hole_area, float max_sprinkle_area, float* y,
                          void* workspace, cvmi_stream_t stream);
 
+/* upstream's remove_small_regions (sam2/utils/amg.py) on N binary u8 planes mask [N,H,W], IN PLACE; foreground is a non-zero byte, components
+ * are 8-connected in both phases and never cross a plane (the same tile / seam / flatten kernels, reading bytes).  phases: 1 holes, 2 islands,
+ * 3 both, in upstream's order:
+ *   holes    every background component of area < min_area (strict; the plane-wide background is a component like any other) is written as 255;
+ *   islands  on the RESULT of the holes phase, labelled again (a filled hole can join foreground components): every foreground component of
+ *            area < min_area is written as 0 -- but where EVERY foreground component of the plane is that small, the largest one stays, the
+ *            one whose raster-first pixel comes first among equals ([UP]: cv2's label order).
+ * Bytes that are neither filled nor removed keep their value (a foreground 1 stays 1).
+ * info i32 [N,8] = {changed (0 / 1: a pixel of the plane was filled or removed), area and inclusive x0, y0, x1, y1 of the FINAL plane
+ * ({0,0,0,0} for an empty one: batched_mask_to_box), pixels filled, pixels removed}.  All reductions are integer sums and extrema, the kept
+ * component a 64-bit maximum of (area << 32 | ~root index): results do not depend on the launch.
+ * workspace: DEVICE, 8-byte aligned, at least cvmi_mask_remove_small_workspace(N, H, W) bytes = two ints per pixel + 8 per plane (0: sizes
+ * not positive or N * H * W >= 2^31).  Refused before any launch: such sizes, min_area <= 0, phases outside 1..3, null pointers. */
+size_t cvmi_mask_remove_small_workspace(int N, int H, int W);
+int cvmi_mask_remove_small(uint8_t* mask, int N, int H, int W, int min_area, int phases, int* info, void* workspace, cvmi_stream_t stream);
+
+/* upstream's mask_to_rle_pytorch `counts` of N binary u8 planes mask [N,H,W] (row-major; foreground is a non-zero byte): plane n is read in
+ * COLUMN-major order (y fastest); its runs alternate, starting with a run of zeros (0 when pixel (0, 0) is set); a run goes on across a
+ * column end; the runs sum to H * W (an all-zero plane is {H * W}, an all-set one {0, H * W}).
+ *   offsets i32 [N+1]: offsets[n] = index of plane n's first run in counts, offsets[N] = the total.  Always written in full.
+ *   counts i32 [cap_runs]: nothing is written at or past counts[cap_runs]; when offsets[N] > cap_runs the caller repeats the call with a
+ *   larger capacity (cvmi_external_contours' convention).  cap_runs = 0 with counts = NULL is a pure count.
+ * Every position comes from a prefix sum, never a slot grab: replays are bit-identical.  The mask bytes are read once.
+ * workspace: DEVICE, 8-byte aligned, workspace_bytes >= cvmi_mask_rle_workspace(N, H, W) (1 bit per pixel rounded up to 64 rows per column,
+ * + 8 bytes per 256 such words; 0: sizes not positive, or N * H * W + N >= 2^31 -- positions and the total are int32 and a plane has up to
+ * H * W + 1 runs).  Refused before any launch: such sizes, null pointers (counts only with cap_runs > 0), a workspace that is too small. */
+size_t cvmi_mask_rle_workspace(int N, int H, int W);
+int cvmi_mask_rle(const uint8_t* mask, int N, int H, int W, int cap_runs, int* offsets, int* counts, void* workspace, size_t workspace_bytes,
+                  cvmi_stream_t stream);
+
 /* Extent of N binary u8 planes [N,H,W]: extent[n] = {min x, min y, max x, max y} over the non-zero pixels, or
  * {W, H, -1, -1} for an empty plane.  Replaces cv2.findContours(RETR_EXTERNAL) + cv2.boundingRect on the SAM 2 mask
  * (circuit_analyzer.py:364-370): sam_extent_bbox = (min x, min y, max x + 1, max y + 1). */
