@@ -156,6 +156,8 @@ SIGNATURES = {
     "cvmi_mask_postprocess_sizes": (_i, [_vp, _i, _i, _i, _vp, _f, _vp, _vp, _vp]),
     "cvmi_amg_score": (_i, [_vp, _i, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp]),
     "cvmi_amg_select": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "cvmi_amg_select_crop": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "cvmi_amg_score_window": (_i, [_vp, _i, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _i, _i, _i, _i, _vp]),
     "cvmi_mask_cc_workspace": (C.c_size_t, [_i, _i, _i]),
     "cvmi_mask_components": (_i, [_vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
     "cvmi_mask_fill_small": (_i, [_vp, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp]),

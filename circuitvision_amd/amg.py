@@ -3,23 +3,23 @@ mask-to-mask pass, no small-region removal) on `SAM2Model`'s encode / decode spl
 chunks from ONE embedding (`encode_images`, then `infer_masks(emb, points=...)` per chunk); every candidate plane is scored at the image's
 own resolution by cvmi_amg_score -- the two stability counts, the area and the bounding box of the bilinearly resized logits, without the
 resized map --, filtered and appended on the device (cvmi_amg_select), de-duplicated by cvmi_yolo_nms on the boxes, and only the survivors
-are turned into masks (cvmi_amg_score's mask mode, so `area` and `bbox` describe `segmentation` by construction)."""
+are turned into masks (cvmi_amg_score's mask mode, so `area` and `bbox` describe `segmentation` by construction).
+
+With `crop_n_layers > 0` (a per-call argument) the grid runs again on overlapping crops of the image (amg_utils.generate_crop_boxes): the
+crops are source rectangles of ONE uploaded image (cvmi_sam2_transform_srcs), encoded as a batch; the append drops the candidates a crop
+border cuts (cvmi_amg_select_crop); a second cvmi_yolo_nms across the crops prefers the smaller crop; and the survivors' masks are written
+into a window of a full-image plane (cvmi_amg_score_window)."""
 import numpy as np
 import torch
 
 from . import _lib, amg_utils
-from .sam2_infer import SAM2Transforms, Sam2Embeddings
+from .amg_utils import build_point_grid  # noqa: F401  (upstream's name, kept importable from here)
+from .sam2_infer import F32, SAM2Transforms, Sam2Embeddings
 
 OUTPUT_KEYS = ("segmentation", "area", "bbox", "predicted_iou", "point_coords", "stability_score", "crop_box")
 NMS_MAX_DET = 4096                               # cvmi_yolo_nms keeps at most this many boxes per image
-POOL_BYTES_IN_FLIGHT = 4 << 30                   # images are processed in sub-batches whose candidate pools stay below this
-
-
-def build_point_grid(n):
-    """upstream's build_point_grid: n x n points in [0, 1]^2 (float64 [n * n, 2] of (x, y), x fastest), offset 1 / (2 n) from the border."""
-    offset = 1.0 / (2 * n)
-    side = np.linspace(offset, 1.0 - offset, n)
-    return np.stack([np.tile(side[None, :], (n, 1)), np.tile(side[:, None], (1, n))], axis=-1).reshape(-1, 2)
+POOL_BYTES_IN_FLIGHT = 4 << 30                   # images (or crops) are processed in sub-batches whose candidate pools stay below this
+CROP_EDGE_TOL = 20                               # upstream's is_box_near_crop_edge atol, in pixels
 
 
 class Sam2AutomaticMaskGenerator:
@@ -56,13 +56,33 @@ class Sam2AutomaticMaskGenerator:
     enqueued for all images of the sub-batch -- the planes, cvmi_mask_remove_small, the second cvmi_yolo_nms, cvmi_mask_rle with a capacity
     guess -- and the host waits ONCE more per sub-batch, for the second NMS's keep lists and the planes' info (min_mask_region_area) and
     the RLE offsets and counts (uncompressed_rle) together: one added wait whichever options are set.  A chunk of planes with more than
-    amg_utils.RLE_RUNS_PER_COLUMN runs per column on average is encoded a second time with the exact capacity, with a wait of its own."""
+    amg_utils.RLE_RUNS_PER_COLUMN runs per column on average is encoded a second time with the exact capacity, with a wait of its own.
+
+    The crop options are per-call arguments too (the constructor refuses `crop_n_layers > 0`; the layer grids come from `points_per_side`, so a
+    generator built from explicit `point_grids` raises ValueError for them):
+      crop_n_layers > 0          upstream's crop layers: layer i has (2 ** i) ** 2 overlapping crops (amg_utils.generate_crop_boxes with
+                                 crop_overlap_ratio), each with the grid of int(points_per_side / crop_n_points_downscale_factor ** i) points
+                                 per side.  The input must be a list of u8 images (the crops need the pixels); each image is processed on its own:
+                                 uploaded once, its crops encoded and decoded in sub-batches that keep the pools below 4 GB, the crops of a
+                                 sub-batch that share a layer decoded together.  Per crop the pipeline is the one above, in the crop's
+                                 coordinates, plus upstream's border filter: a candidate whose box has a side within 20 pixels of a crop
+                                 side that is not within 20 pixels of the image's side is dropped before the per-crop NMS.
+      crop_nms_thresh            the box NMS across the crops, on the per-crop survivors in (crop order, per-crop NMS order) with score
+                                 1 / (crop area) in f32: a mask of a smaller crop outranks one of a larger crop, and -- this project's rule, the
+                                 kernel's -- equal scores go to the lower index, i.e. the earlier crop and within it the per-crop NMS order.  The
+                                 list comes back in that NMS's order.  A single crop box has no such NMS, as upstream.  More than 4096 per-crop
+                                 survivors in total raise RuntimeError.
+    `segmentation`, `area`, `bbox` and `point_coords` are in the ORIGINAL image's coordinates (point_coords = [[gx * cw + cx0, gy * ch + cy0]]
+    for the crop [cx0, cy0, cw, ch], which is `crop_box`).  Both options above compose with crops; the second NMS of min_mask_region_area then
+    uses max(box_nms_thresh, crop_nms_thresh), upstream's rule.  The host waits, per image: once per sub-batch of crops (as above), once after
+    the cross-crop NMS for its keep list, and the options' one extra wait.  With crop_n_layers == 0 nothing of this runs."""
 
     def __init__(self, model, points_per_side=32, points_per_batch=64, pred_iou_thresh=0.8, stability_score_thresh=0.95,
                  stability_score_offset=1.0, mask_threshold=0.0, box_nms_thresh=0.7, point_grids=None, multimask_output=True, max_candidates=None,
                  output_mode="binary_mask", crop_n_layers=0, min_mask_region_area=0, use_m2m=False):
         if crop_n_layers > 0:
-            raise NotImplementedError("crop_n_layers > 0: only the single full-image crop is built")
+            raise NotImplementedError("crop_n_layers > 0 is a per-call argument here: generate(image, crop_n_layers=...) / "
+                                      "generate_batch(..., crop_n_layers=...), with crop_overlap_ratio, crop_n_points_downscale_factor, crop_nms_thresh")
         if min_mask_region_area > 0:
             raise NotImplementedError("min_mask_region_area > 0 is a per-call argument here: generate(image, min_mask_region_area=...) / "
                                       "generate_batch(..., min_mask_region_area=...), or amg_utils.postprocess_small_regions on a returned list")
@@ -88,6 +108,7 @@ class Sam2AutomaticMaskGenerator:
         if not pred_iou_thresh >= 0:
             raise ValueError("pred_iou_thresh must be >= 0 (cvmi_yolo_nms sorts non-negative scores)")
         self.model, self.grid = model, grid
+        self.points_per_side = int(points_per_side) if point_grids is None else None
         self.points_per_batch = int(points_per_batch)
         self.pred_iou_thresh, self.stability_score_thresh = float(pred_iou_thresh), float(stability_score_thresh)
         self.stability_score_offset, self.mask_threshold, self.box_nms_thresh = float(stability_score_offset), float(mask_threshold), float(box_nms_thresh)
@@ -103,14 +124,19 @@ class Sam2AutomaticMaskGenerator:
         self.points_in = torch.from_numpy(grid.astype(np.float32)) * float(model.image_size)
 
     # -- public surface
-    def generate(self, image, min_mask_region_area=0, output_mode="binary_mask"):
-        """image: RGB u8 [H, W, 3] (array or PIL) -> list of dicts.  min_mask_region_area, output_mode: see the class."""
+    def generate(self, image, min_mask_region_area=0, output_mode="binary_mask", crop_n_layers=0, crop_overlap_ratio=512 / 1500,
+                 crop_n_points_downscale_factor=1, crop_nms_thresh=0.7):
+        """image: RGB u8 [H, W, 3] (array or PIL) -> list of dicts.  The per-call options: see the class."""
         img = self.transforms._check_u8(image)
-        return self.generate_batch([img], min_mask_region_area=min_mask_region_area, output_mode=output_mode)[0]
+        return self.generate_batch([img], min_mask_region_area=min_mask_region_area, output_mode=output_mode, crop_n_layers=crop_n_layers,
+                                   crop_overlap_ratio=crop_overlap_ratio, crop_n_points_downscale_factor=crop_n_points_downscale_factor,
+                                   crop_nms_thresh=crop_nms_thresh)[0]
 
-    def generate_batch(self, images, orig_hw=None, min_mask_region_area=0, output_mode="binary_mask"):
+    def generate_batch(self, images, orig_hw=None, min_mask_region_area=0, output_mode="binary_mask", crop_n_layers=0, crop_overlap_ratio=512 / 1500,
+                       crop_n_points_downscale_factor=1, crop_nms_thresh=0.7):
         """images: a list of RGB u8 [H, W, 3] images (orig_hw then defaults to their sizes), a [B, 3, R, R] tensor as `infer_masks` takes it, or
-        the `Sam2Embeddings` `encode_images` made of one; orig_hw = [(H, W)] per image.  -> one list of dicts per image."""
+        the `Sam2Embeddings` `encode_images` made of one; orig_hw = [(H, W)] per image.  -> one list of dicts per image.  crop_n_layers > 0
+        takes the list of u8 images only."""
         model = self.model
         if output_mode == "coco_rle":
             raise NotImplementedError("output_mode='coco_rle': the compressed string form is pycocotools', which is not available to check an "
@@ -120,6 +146,11 @@ class Sam2AutomaticMaskGenerator:
         min_area = int(min_mask_region_area)
         if min_area < 0:
             raise ValueError("min_mask_region_area must be >= 0")
+        if int(crop_n_layers) < 0:
+            raise ValueError("crop_n_layers must be >= 0")
+        if int(crop_n_layers) > 0:
+            return self._generate_batch_crops(images, int(crop_n_layers), float(crop_overlap_ratio), crop_n_points_downscale_factor,
+                                              float(crop_nms_thresh), min_area, output_mode)
         if isinstance(images, (list, tuple)):
             imgs = [self.transforms._check_u8(im) for im in images]
             if orig_hw is None:
@@ -145,14 +176,18 @@ class Sam2AutomaticMaskGenerator:
         return out
 
     # -- one sub-batch
-    def _candidates(self, emb, sizes):
+    def _candidates(self, emb, sizes, grid=None, points_in=None, crops=None, image_hw=None):
         """Enqueue every chunk of the grid for the images of `emb`: decode, score, filter + append.  -> the per-image device state
-        (counter i32 [B, 2], records i32 [B, cap, 10], pool f32 [B, cap, R/4, R/4], block f32 [B, 5, cap]); nothing is read back."""
+        (counter i32 [B, 2], records i32 [B, cap, 10], pool f32 [B, cap, R/4, R/4], block f32 [B, 5, cap]); nothing is read back.
+        grid / points_in: a crop layer's grid in the place of the generator's; crops = [[x0, y0, x1, y1]] per "image" of `emb`, the crops of
+        one image of size image_hw = (H, W): sizes are then the crops' and the append holds the border filter."""
         lib, model = _lib.load(), self.model
         B, cap, C, Pb = len(emb), self.cap, self.ncand, self.points_per_batch
         f0 = model.image_size // 4
         lo, mid, hi = self.levels
         dev = emb.device
+        grid = self.grid if grid is None else grid
+        points_in = self.points_in if points_in is None else points_in
         sp = torch.cuda.current_stream().cuda_stream
         counter = torch.zeros(B, 2, dtype=torch.int32, device=dev)
         records = torch.zeros(B, cap, len(_lib.AMG_RECORD), dtype=torch.int32, device=dev)
@@ -161,8 +196,8 @@ class Sam2AutomaticMaskGenerator:
         block[:, 4].fill_(float("-inf"))                                         # unused columns never pass the NMS's conf_thres
         stats = torch.empty(B, Pb * C, 8, dtype=torch.int32, device=dev)
         labels = torch.ones(B, Pb, 1, dtype=torch.int32)
-        for base in range(0, len(self.grid), Pb):
-            pts = self.points_in[base:base + Pb]
+        for base in range(0, len(grid), Pb):
+            pts = points_in[base:base + Pb]
             n_valid = pts.shape[0]
             if n_valid < Pb:                                                     # a short last chunk: the last point repeated, never selected
                 pts = torch.cat([pts, pts[-1:].expand(Pb - n_valid, 2)])
@@ -171,114 +206,222 @@ class Sam2AutomaticMaskGenerator:
             low, iou = low.view(B, Pb * C, f0, f0), iou.view(B, Pb * C)
             for b, (H, W) in enumerate(sizes):
                 _lib.check(lib.cvmi_amg_score(low[b].data_ptr(), Pb * C, f0, f0, H, W, lo, mid, hi, stats[b].data_ptr(), None, sp), "amg_score")
-                _lib.check(lib.cvmi_amg_select(stats[b].data_ptr(), iou[b].data_ptr(), low[b].data_ptr(), Pb * C, n_valid * C, C, base,
-                                               self.pred_iou_thresh, self.stability_score_thresh, f0 * f0, cap, counter[b].data_ptr(),
-                                               records[b].data_ptr(), pool[b].data_ptr(), block[b].data_ptr(), sp), "amg_select")
+                args = (stats[b].data_ptr(), iou[b].data_ptr(), low[b].data_ptr(), Pb * C, n_valid * C, C, base, self.pred_iou_thresh,
+                        self.stability_score_thresh, f0 * f0, cap, counter[b].data_ptr(), records[b].data_ptr(), pool[b].data_ptr(), block[b].data_ptr())
+                if crops is None:
+                    _lib.check(lib.cvmi_amg_select(*args, sp), "amg_select")
+                else:
+                    _lib.check(lib.cvmi_amg_select_crop(*args, *crops[b], image_hw[1], image_hw[0], CROP_EDGE_TOL, sp), "amg_select_crop")
         return dict(counter=counter, records=records, pool=pool, block=block)
+
+    def _first_nms(self, st):
+        """The per-image (per-crop) box NMS on a `_candidates` state and its results on their way to pinned memory, enqueued.
+        -> (keep_idx on the device, the pinned buffers `_read` takes after the stream has been synchronised)."""
+        lib, cap = _lib.load(), self.cap
+        counter, records, block = st["counter"], st["records"], st["block"]
+        B, dev = int(counter.shape[0]), counter.device
+        max_det = min(cap, NMS_MAX_DET)
+        ws = torch.empty(int(lib.cvmi_yolo_nms_workspace(B, cap)), dtype=torch.uint8, device=dev)
+        det = torch.empty(B, max_det, 6, dtype=torch.float32, device=dev)
+        keep_idx = torch.empty(B, max_det, dtype=torch.int32, device=dev)
+        keep_n = torch.empty(B, dtype=torch.int32, device=dev)
+        _lib.check(lib.cvmi_yolo_nms(block.data_ptr(), B, 1, cap, self.pred_iou_thresh, self.box_nms_thresh, max_det, 0.0, det.data_ptr(),
+                                     keep_idx.data_ptr(), keep_n.data_ptr(), ws.data_ptr(), torch.cuda.current_stream().cuda_stream), "yolo_nms")
+        # counts, kept indices and records in pinned buffers: valid after one synchronise
+        host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in (counter, keep_n, keep_idx, records)]
+        for h, t in zip(host, (counter, keep_n, keep_idx, records)):
+            h.copy_(t, non_blocking=True)
+        return keep_idx, host
+
+    def _read(self, host):
+        """After the wait: (kept_n [B], kept_idx [B, max_det], records [B, cap]) on the host; too many kept candidates raise."""
+        counts, kept_n, kept_idx, recs = (h.numpy() for h in host)
+        recs = recs.view(_lib.AMG_RECORD).reshape(counts.shape[0], self.cap)
+        if int(counts[:, 0].max()) > self.cap:
+            raise RuntimeError(f"{int(counts[:, 0].max())} candidates passed the filters but max_candidates = {self.cap}: raise max_candidates "
+                               "(or the thresholds)")
+        return kept_n, kept_idx, recs
+
+    @staticmethod
+    def _dict(seg, r, grid, crop):
+        """The output dict of record r of a crop [cx0, cy0, cw, ch] (the image: [0, 0, W, H]): box and point moved to the image."""
+        cx0, cy0, cw, ch = crop
+        x0, y0, x1, y1 = int(r["x0"]), int(r["y0"]), int(r["x1"]), int(r["y1"])
+        gx, gy = grid[int(r["point"])]
+        return {"segmentation": seg, "area": int(r["area"]), "bbox": [x0 + cx0, y0 + cy0, x1 - x0, y1 - y0], "predicted_iou": float(r["score"]),
+                "point_coords": [[float(gx * cw + cx0), float(gy * ch + cy0)]], "stability_score": float(r["stability"]), "crop_box": [cx0, cy0, cw, ch]}
 
     def _generate(self, emb, sizes, min_area=0, output_mode="binary_mask"):
         """Candidates, NMS, the single host wait, then the survivors' masks."""
-        lib, model = _lib.load(), self.model
-        B, cap, f0 = len(emb), self.cap, model.image_size // 4
-        lo, mid, hi = self.levels
-        dev = emb.device
-        with torch.cuda.device(dev):
-            sp = torch.cuda.current_stream().cuda_stream
+        with torch.cuda.device(emb.device):
             st = self._candidates(emb, sizes)
-            counter, records, pool, block = st["counter"], st["records"], st["pool"], st["block"]
-            max_det = min(cap, NMS_MAX_DET)
-            ws = torch.empty(int(lib.cvmi_yolo_nms_workspace(B, cap)), dtype=torch.uint8, device=dev)
-            det = torch.empty(B, max_det, 6, dtype=torch.float32, device=dev)
-            keep_idx = torch.empty(B, max_det, dtype=torch.int32, device=dev)
-            keep_n = torch.empty(B, dtype=torch.int32, device=dev)
-            _lib.check(lib.cvmi_yolo_nms(block.data_ptr(), B, 1, cap, self.pred_iou_thresh, self.box_nms_thresh, max_det, 0.0, det.data_ptr(),
-                                         keep_idx.data_ptr(), keep_n.data_ptr(), ws.data_ptr(), sp), "yolo_nms")
-            # the one wait: counts, kept indices and records in pinned buffers, one synchronise
-            host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in (counter, keep_n, keep_idx, records)]
-            for h, t in zip(host, (counter, keep_n, keep_idx, records)):
-                h.copy_(t, non_blocking=True)
-            torch.cuda.current_stream().synchronize()
-            counts, kept_n, kept_idx, recs = (h.numpy() for h in host)
-            recs = recs.view(_lib.AMG_RECORD).reshape(B, cap)
-            if int(counts[:, 0].max()) > cap:
-                raise RuntimeError(f"{int(counts[:, 0].max())} candidates passed the filters but max_candidates = {cap}: raise max_candidates "
-                                   "(or the thresholds)")
-            if min_area > 0 or output_mode != "binary_mask":
-                return self._finish_with_options(sizes, pool, keep_idx, kept_n, kept_idx, recs, min_area, output_mode)
-            out = []
+            keep_idx, host = self._first_nms(st)
+            torch.cuda.current_stream().synchronize()                                # the one wait
+            kept_n, kept_idx, recs = self._read(host)
+            items = []
             for b, (H, W) in enumerate(sizes):
                 K = int(kept_n[b])
-                if K == 0:
-                    out.append([])
-                    continue
-                planes = pool[b].index_select(0, keep_idx[b, :K].long())
-                masks = torch.empty(K, H, W, dtype=torch.uint8, device=dev)
-                fstats = torch.empty(K, 8, dtype=torch.int32, device=dev)                  # equal to the records' by construction; not read back
-                _lib.check(lib.cvmi_amg_score(planes.data_ptr(), K, f0, f0, H, W, lo, mid, hi, fstats.data_ptr(), masks.data_ptr(), sp), "amg_score")
-                dicts = []
-                for k in range(K):
-                    r = recs[b, int(kept_idx[b, k])]
-                    x0, y0, x1, y1 = int(r["x0"]), int(r["y0"]), int(r["x1"]), int(r["y1"])
-                    gx, gy = self.grid[int(r["point"])]
-                    dicts.append({"segmentation": masks[k], "area": int(r["area"]), "bbox": [x0, y0, x1 - x0, y1 - y0],
-                                  "predicted_iou": float(r["score"]), "point_coords": [[float(gx * W), float(gy * H)]],
-                                  "stability_score": float(r["stability"]), "crop_box": [0, 0, W, H]})
-                out.append(dicts)
-            return out
+                rows = [(recs[b, int(kept_idx[b, k])], self.grid, (0, 0, W, H)) for k in range(K)]
+                items.append((H, W, st["pool"][b].index_select(0, keep_idx[b, :K].long()), rows) if K else None)
+            if min_area > 0 or output_mode != "binary_mask":
+                return self._finish_with_options(items, min_area, output_mode, self.box_nms_thresh)
+            return [self._finish(item) for item in items]
 
-    # -- the per-call options
-    def _masks(self, low_planes, H, W):
-        """u8 [K, H, W] planes of the kept candidates' low-res planes (cvmi_amg_score's mask mode), enqueued."""
+    def _finish(self, item):
+        """The dicts of one image's survivors (H, W, low planes [K, R/4, R/4], rows = [(record, grid, crop)]) with binary masks."""
+        if item is None:
+            return []
+        H, W, low, rows = item
+        masks = self._masks(low, H, W, [crop for _, _, crop in rows])
+        return [self._dict(masks[k], r, grid, crop) for k, (r, grid, crop) in enumerate(rows)]
+
+    # -- crop layers
+    def _generate_batch_crops(self, images, n_layers, overlap_ratio, downscale, crop_nms_thresh, min_area, output_mode):
+        if not isinstance(images, (list, tuple)):
+            raise ValueError("crop_n_layers > 0 needs the pixels: images must be a list of RGB u8 images, not a tensor or embeddings")
+        if self.points_per_side is None:
+            raise ValueError("crop_n_layers > 0 with explicit point_grids (one grid): the layer grids come from points_per_side")
+        grids = [(g, torch.from_numpy(g.astype(np.float32)) * float(self.model.image_size))
+                 for g in amg_utils.build_all_layer_point_grids(self.points_per_side, n_layers, downscale)]
+        imgs = [self.transforms._check_u8(im) for im in images]
+        return [self._generate_crops(im, n_layers, overlap_ratio, grids, crop_nms_thresh, min_area, output_mode) for im in imgs]
+
+    def _generate_crops(self, img, n_layers, overlap_ratio, grids, crop_nms_thresh, min_area, output_mode):
+        """One image: its crops in sub-batches (one wait each), the cross-crop NMS (one wait), the survivors' masks in full-image planes."""
+        from .detector import PackedImages
+        model = self.model
+        H, W = (int(v) for v in img.shape[:2])
+        boxes, layers = amg_utils.generate_crop_boxes((H, W), n_layers, overlap_ratio)
+        R, f0, cap = model.image_size, model.image_size // 4, self.cap
+        packed = PackedImages.upload([img])                                       # the one H2D of the pixels
+        step = max(1, POOL_BYTES_IN_FLIGHT // (cap * f0 * f0 * 4))
+        lows, rows = [], []
+        for a in range(0, len(boxes), step):
+            sub, n = boxes[a:a + step], len(boxes[a:a + step])
+            x = torch.empty(n, R, R, 3, dtype=torch.float32, device=packed.data.device)
+            # the crops are rows of one launch that share the image's offset: no cropped copy
+            self.transforms._transform_srcs(PackedImages(packed.data, packed.offsets * n, packed.shapes * n), [tuple(c) for c in sub], x, F32, False)
+            emb = model.encode_images(x.permute(0, 3, 1, 2))
+            with torch.cuda.device(emb.device):
+                groups, i = [], 0
+                while i < n:                                                     # crops that share a layer grid are decoded together
+                    j = i
+                    while j < n and layers[a + j] == layers[a + i]:
+                        j += 1
+                    grid, points_in = grids[layers[a + i]]
+                    st = self._candidates(emb[i:j], [(c[3] - c[1], c[2] - c[0]) for c in sub[i:j]], grid, points_in, sub[i:j], (H, W))
+                    groups.append((i, j, grid, st["pool"], *self._first_nms(st)))
+                    i = j
+                torch.cuda.current_stream().synchronize()                        # the sub-batch's wait
+                for i, j, grid, pool, keep_idx, host in groups:
+                    kept_n, kept_idx, recs = self._read(host)
+                    for b, c in enumerate(sub[i:j]):
+                        K = int(kept_n[b])
+                        if K:
+                            lows.append(pool[b].index_select(0, keep_idx[b, :K].long()))
+                            rows += [(recs[b, int(kept_idx[b, k])], grid, (c[0], c[1], c[2] - c[0], c[3] - c[1])) for k in range(K)]
+        if not rows:
+            return []
+        low = torch.cat(lows)
+        with torch.cuda.device(low.device):
+            if len(boxes) > 1:
+                order = self._cross_crop_nms(rows, crop_nms_thresh, low.device)
+                rows = [rows[i] for i in order]
+                low = low.index_select(0, torch.as_tensor(order, dtype=torch.long, device=low.device))
+            item = (H, W, low, rows)
+            if min_area > 0 or output_mode != "binary_mask":
+                return self._finish_with_options([item], min_area, output_mode, max(self.box_nms_thresh, crop_nms_thresh))[0]
+            return self._finish(item)
+
+    def _cross_crop_nms(self, rows, nms_thresh, dev):
+        """upstream's NMS across the crops: the boxes in image coordinates, score = 1 / (crop area) in f32 (a smaller crop wins; equal scores
+        to the lower index).  One wait, for the keep list.  -> kept positions in NMS order."""
+        lib, n = _lib.load(), len(rows)
+        if n > NMS_MAX_DET:
+            raise RuntimeError(f"{n} masks survived their crops' NMS but the NMS across the crops returns at most {NMS_MAX_DET}: raise the thresholds "
+                               "(or lower crop_n_layers / points_per_side)")
+        host = torch.empty(5, n, dtype=torch.float32, pin_memory=True)
+        blk = host.numpy()
+        for i, (r, _, (cx0, cy0, cw, ch)) in enumerate(rows):                    # halves of integers below 2^24: exact, as in cvmi_amg_select
+            x0, y0, x1, y1 = int(r["x0"]) + cx0, int(r["y0"]) + cy0, int(r["x1"]) + cx0, int(r["y1"]) + cy0
+            blk[:, i] = ((x0 + x1) / 2, (y0 + y1) / 2, x1 - x0, y1 - y0, np.float32(1.0) / np.float32(cw * ch))
+        block = host.to(dev, non_blocking=True)
+        ws = torch.empty(int(lib.cvmi_yolo_nms_workspace(1, n)), dtype=torch.uint8, device=dev)
+        det = torch.empty(n, 6, dtype=torch.float32, device=dev)
+        keep_idx = torch.empty(n, dtype=torch.int32, device=dev)
+        keep_n = torch.empty(1, dtype=torch.int32, device=dev)
+        _lib.check(lib.cvmi_yolo_nms(block.data_ptr(), 1, 1, n, 0.0, nms_thresh, n, 0.0, det.data_ptr(), keep_idx.data_ptr(), keep_n.data_ptr(),
+                                     ws.data_ptr(), torch.cuda.current_stream().cuda_stream), "yolo_nms")
+        keep_n, keep_idx = amg_utils._pinned(keep_n), amg_utils._pinned(keep_idx)
+        torch.cuda.current_stream().synchronize()
+        return keep_idx.numpy()[:int(keep_n[0])].tolist()
+
+    # -- masks and the per-call options
+    def _masks(self, low_planes, H, W, crops=None):
+        """u8 [K, H, W] planes of the kept candidates' low-res planes, enqueued: cvmi_amg_score's mask mode, or -- for the planes of a crop
+        [cx0, cy0, cw, ch] that is not the image -- cvmi_amg_score_window, which writes the crop's mask and the zeros around it in one pass.
+        crops: one per plane; each run of planes of one crop is one call."""
         lib, f0 = _lib.load(), self.model.image_size // 4
         lo, mid, hi = self.levels
         K = int(low_planes.shape[0])
         masks = torch.empty(K, H, W, dtype=torch.uint8, device=low_planes.device)
-        fstats = torch.empty(K, 8, dtype=torch.int32, device=low_planes.device)
-        _lib.check(lib.cvmi_amg_score(low_planes.data_ptr(), K, f0, f0, H, W, lo, mid, hi, fstats.data_ptr(), masks.data_ptr(),
-                                      torch.cuda.current_stream().cuda_stream), "amg_score")
+        fstats = torch.empty(K, 8, dtype=torch.int32, device=low_planes.device)        # equal to the records' by construction; not read back
+        sp = torch.cuda.current_stream().cuda_stream
+        crops = [(0, 0, W, H)] * K if crops is None else crops
+        a = 0
+        while a < K:
+            b = a + 1
+            while b < K and crops[b] == crops[a]:
+                b += 1
+            cx0, cy0, cw, ch = crops[a]
+            if (cx0, cy0, cw, ch) == (0, 0, W, H):
+                _lib.check(lib.cvmi_amg_score(low_planes[a].data_ptr(), b - a, f0, f0, H, W, lo, mid, hi, fstats[a].data_ptr(), masks[a].data_ptr(), sp),
+                           "amg_score")
+            else:
+                _lib.check(lib.cvmi_amg_score_window(low_planes[a].data_ptr(), b - a, f0, f0, ch, cw, lo, mid, hi, fstats[a].data_ptr(),
+                                                     masks[a].data_ptr(), H, W, cx0, cy0, sp), "amg_score_window")
+            a = b
         return masks
 
-    def _finish_with_options(self, sizes, pool, keep_idx, kept_n, kept_idx, recs, min_area, output_mode):
-        """After the first NMS's wait: per image the survivors' planes (all of them, or chunk by chunk in the RLE mode), small-region removal,
-        the second NMS and the encoding are enqueued; ONE wait for the whole sub-batch; then the dicts."""
+    def _finish_with_options(self, items, min_area, output_mode, nms_thresh):
+        """After the first NMS's wait (and, with crops, the cross-crop NMS's): per image -- an item (H, W, low planes [K, R/4, R/4], rows =
+        [(record, grid, crop)]) or None -- the survivors' planes (all of them, or chunk by chunk in the RLE mode), small-region removal, the
+        second NMS with nms_thresh and the encoding are enqueued; ONE wait for all items; then the dicts."""
         rle = output_mode == "uncompressed_rle"
         work = []
-        for b, (H, W) in enumerate(sizes):
-            K = int(kept_n[b])
-            if K == 0:
+        for item in items:
+            if item is None:
                 work.append(None)
                 continue
-            low = pool[b].index_select(0, keep_idx[b, :K].long())
+            H, W, low, rows = item
+            K = len(rows)
+            crops = [crop for _, _, crop in rows]
             step = max(1, amg_utils.MASK_CHUNK_BYTES // (H * W)) if rle else K
             masks, infos, pending = None, [], []
             for a in range(0, K, step):
-                def build(a=a, H=H, W=W, low=low, step=step):
-                    m = self._masks(low[a:a + step], H, W)
+                def build(a=a, H=H, W=W, low=low, step=step, crops=crops):
+                    m = self._masks(low[a:a + step], H, W, crops[a:a + step])
                     return m, (amg_utils.remove_small_enqueue(m, min_area, amg_utils.PHASES["both"]) if min_area > 0 else None)
                 masks, info = build()
                 infos.append(info)
                 if rle:
                     pending.append(amg_utils.PendingRle(masks, rebuild=lambda build=build: build()[0]))
                     masks = None                                                 # the chunk's planes are free again once the stream has passed them
-            nms = amg_utils.SecondNms(torch.cat(infos), self.box_nms_thresh) if min_area > 0 else None
+            nms = amg_utils.SecondNms(torch.cat(infos), nms_thresh) if min_area > 0 else None
             work.append((K, masks, pending, nms))
         torch.cuda.current_stream().synchronize()
         out = []
-        for b, (H, W) in enumerate(sizes):
-            if work[b] is None:
+        for item, w in zip(items, work):
+            if w is None:
                 out.append([])
                 continue
-            K, masks, pending, nms = work[b]
+            rows = item[3]
+            K, masks, pending, nms = w
             order, info = nms.finish() if nms is not None else (range(K), None)
             segs = [r for p in pending for r in p.finish()] if rle else masks
             dicts = []
             for k in order:
-                r = recs[b, int(kept_idx[b, k])]
-                x0, y0, x1, y1 = int(r["x0"]), int(r["y0"]), int(r["x1"]), int(r["y1"])
-                gx, gy = self.grid[int(r["point"])]
-                d = {"segmentation": segs[k], "area": int(r["area"]), "bbox": [x0, y0, x1 - x0, y1 - y0],
-                     "predicted_iou": float(r["score"]), "point_coords": [[float(gx * W), float(gy * H)]],
-                     "stability_score": float(r["stability"]), "crop_box": [0, 0, W, H]}
+                d = self._dict(segs[k], *rows[k])
                 dicts.append(amg_utils.survivor(d, segs[k], info[k]) if info is not None else d)
             out.append(dicts)
         return out

@@ -1,6 +1,7 @@
 """The mask utilities of upstream's `sam2/utils/amg.py` on device tensors: uncompressed RLE (csrc/mask_rle.hip, cvmi_mask_rle), small-region
 removal (csrc/mask_cc.hip, cvmi_mask_remove_small) and `postprocess_small_regions` on both plus a second box NMS (cvmi_yolo_nms).  Names and
-meanings are upstream's; where upstream loops over masks, these take a stack [K, H, W] of u8 planes (foreground = a non-zero byte).
+meanings are upstream's; where upstream loops over masks, these take a stack [K, H, W] of u8 planes (foreground = a non-zero byte).  The crop
+geometry of the generator's crop layers is here too, on the host: `build_point_grid`, `build_all_layer_point_grids`, `generate_crop_boxes`.
 
 An RLE is `{"size": [H, W], "counts": [int, ...]}`: the plane read in column-major order (y fastest), runs alternating and starting with a
 run of zeros (0 when pixel (0, 0) is set), a run going on across a column end, the runs summing to H * W.
@@ -18,6 +19,45 @@ RLE_RUNS_PER_COLUMN = 4                          # the capacity guess of mask_to
 NMS_MAX_DET, NMS_MAX_A = 4096, 65536             # cvmi_yolo_nms keeps at most this many boxes, of at most this many
 PHASES = {"holes": 1, "islands": 2, "both": 3}
 INFO = ("changed", "area", "x0", "y0", "x1", "y1", "filled", "removed")
+
+
+# ---- crop geometry (host) -------------------------------------------------------------------------------------------------------------------------
+def build_point_grid(n):
+    """upstream's build_point_grid: n x n points in [0, 1]^2 (float64 [n * n, 2] of (x, y), x fastest), offset 1 / (2 n) from the border."""
+    offset = 1.0 / (2 * n)
+    side = np.linspace(offset, 1.0 - offset, n)
+    return np.stack([np.tile(side[None, :], (n, 1)), np.tile(side[:, None], (1, n))], axis=-1).reshape(-1, 2)
+
+
+def build_all_layer_point_grids(n_per_side, n_layers, scale_per_layer):
+    """upstream's build_all_layer_point_grids: the grid of layer i has int(n_per_side / scale_per_layer ** i) points per side, i = 0 .. n_layers.
+    A layer left without a point raises ValueError (upstream would divide by zero)."""
+    grids = []
+    for i in range(int(n_layers) + 1):
+        n = int(n_per_side / (scale_per_layer ** i))
+        if n <= 0:
+            raise ValueError(f"crop layer {i}: int({n_per_side} / {scale_per_layer} ** {i}) = {n} points per side")
+        grids.append(build_point_grid(n))
+    return grids
+
+
+def generate_crop_boxes(im_size, n_layers, overlap_ratio):
+    """upstream's generate_crop_boxes: im_size = (H, W) -> (boxes [[x0, y0, x1, y1]] with exclusive ends, layer_idxs).  Box 0 is the image,
+    layer 0; layer i + 1 has (2 ** (i + 1)) ** 2 overlapping crops, x outer and y inner."""
+    import itertools
+    import math
+    H, W = int(im_size[0]), int(im_size[1])
+    boxes, layer_idxs = [[0, 0, W, H]], [0]
+    for i in range(int(n_layers)):
+        n = 2 ** (i + 1)
+        overlap = int(overlap_ratio * min(H, W) * (2 / n))
+        crop_w, crop_h = (int(math.ceil((overlap * (n - 1) + length) / n)) for length in (W, H))
+        x0s = [int((crop_w - overlap) * k) for k in range(n)]
+        y0s = [int((crop_h - overlap) * k) for k in range(n)]
+        for x0, y0 in itertools.product(x0s, y0s):
+            boxes.append([x0, y0, min(x0 + crop_w, W), min(y0 + crop_h, H)])
+            layer_idxs.append(i + 1)
+    return boxes, layer_idxs
 
 
 def _planes(masks):

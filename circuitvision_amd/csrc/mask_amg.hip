@@ -1,7 +1,9 @@
 // Automatic mask generation (upstream SAM2AutomaticMaskGenerator at its defaults), the part behind the decoder: every candidate plane of a
 // point-grid chunk scored at the image's own resolution WITHOUT the f32 map (cvmi_amg_score: three pixel counts and the bounding box of
 // bilinear(low) against three levels, optionally the u8 mask), and one image's filter + ordered append of the kept candidates into its pool,
-// its record list and the block cvmi_yolo_nms reads (cvmi_amg_select).  f32 only: built once, no 16-bit operand type.
+// its record list and the block cvmi_yolo_nms reads (cvmi_amg_select).  With crop layers (crop_n_layers > 0) a plane belongs to a crop of
+// the image: the append also drops the candidates a crop border cuts (cvmi_amg_select_crop), and the survivors' masks are written into a
+// window of a full-image plane (cvmi_amg_score_window).  f32 only: built once, no 16-bit operand type.
 #include <algorithm>
 
 #include "common.hpp"
@@ -30,6 +32,13 @@ struct AmgShape {
   int lds_floats; // bound of a unit's staged window (rows x columns), the launch's dynamic LDS
 };
 
+// cvmi_amg_score_window: the mask planes are PH x PW and the resized H x W map sits at (x0, y0) in them.  The units then tile the PLANE (so a
+// thread's 4 columns are an aligned word of it wherever the window starts); a unit stages and samples only its part of the window and
+// writes zeros elsewhere.  cvmi_amg_score is the window that is the plane.
+struct AmgWindow {
+  int PH, PW, x0, y0;
+};
+
 __global__ void amg_init_kernel(int* __restrict__ stats, int M, int H, int W) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < M) {
@@ -47,10 +56,22 @@ __global__ void amg_finish_kernel(int* __restrict__ stats, int M) {
   }
 }
 
-template <bool MASK, bool VEC>
+// the mask bytes of a thread's 4 adjacent columns of one row: one 4-byte store where the plane's rows are word-aligned (VEC)
+template <bool VEC>
+__device__ __forceinline__ void amg_store4(uint8_t* __restrict__ mrow, unsigned row_on, const bool (&ok)[AMG_COLS]) {
+  if (VEC) {                                                        // PW % 4 == 0 and the planes 4-byte aligned: the 4 columns are all inside, one store
+    if (ok[0]) *reinterpret_cast<uint32_t*>(mrow) = ((row_on & 1u) ? 0xFFu : 0u) | ((row_on & 2u) ? 0xFF00u : 0u) | ((row_on & 4u) ? 0xFF0000u : 0u) | ((row_on & 8u) ? 0xFF000000u : 0u);
+  } else {
+#pragma unroll
+    for (int k = 0; k < AMG_COLS; ++k)
+      if (ok[k]) mrow[k] = ((row_on >> k) & 1u) ? 255 : 0;
+  }
+}
+
+template <bool MASK, bool VEC, bool WIN>
 __global__ __launch_bounds__(AMG_THREADS) void amg_score_kernel(const float* __restrict__ low, int h, int w, int H, int W, float sy, float sx,
-                                                               float lo, float mid, float hi, AmgShape sh, int* __restrict__ stats,
-                                                               uint8_t* __restrict__ mask) {
+                                                               float lo, float mid, float hi, AmgShape sh, AmgWindow win,
+                                                               int* __restrict__ stats, uint8_t* __restrict__ mask) {
   extern __shared__ float tile[];
   __shared__ int yo0[AMG_YTAB], yo1[AMG_YTAB];
   __shared__ float yl[AMG_YTAB];
@@ -59,27 +80,42 @@ __global__ __launch_bounds__(AMG_THREADS) void amg_score_kernel(const float* __r
   const int tx = tid & ((1 << sh.txn_log2) - 1), ty = tid >> sh.txn_log2, tyn = AMG_THREADS >> sh.txn_log2;
   const int chunk_w = AMG_COLS << sh.txn_log2;
   const float* pl = low + (size_t)n * h * w;
-  uint8_t* mp = MASK ? mask + (size_t)n * H * W : nullptr;
+  // the plane the units tile and the map's origin in it; rows / columns of the MAP are plane rows / columns minus (wy0, wx0)
+  const int PH = WIN ? win.PH : H, PW = WIN ? win.PW : W, wx0 = WIN ? win.x0 : 0, wy0 = WIN ? win.y0 : 0;
+  uint8_t* mp = MASK ? mask + (size_t)n * PH * PW : nullptr;
   int n_hi = 0, n_lo = 0, area = 0, ex0 = W, ey0 = H, ex1 = -1, ey1 = -1;
 
   const int nunits = sh.nbands * sh.nchunks;
   for (int unit = blockIdx.x; unit < nunits; unit += gridDim.x) {
     const int band = unit / sh.nchunks, chunk = unit - band * sh.nchunks;
-    const int oy0 = band * sh.band, nr = min(sh.band, H - oy0);
-    const int c0 = chunk * chunk_w, nc = min(chunk_w, W - c0);
+    const int py0 = band * sh.band, nr = min(sh.band, PH - py0);
+    const int c0 = chunk * chunk_w, nc = min(chunk_w, PW - c0);
+    const int col0 = c0 + tx * AMG_COLS;
+    bool ok[AMG_COLS];
+#pragma unroll
+    for (int k = 0; k < AMG_COLS; ++k) ok[k] = col0 + k < c0 + nc;
+    // the unit's rows and columns of the map (all of them without a window)
+    int ra = py0 - wy0, rb = ra + nr - 1, ca = c0 - wx0, cb = ca + nc - 1;
+    if (WIN) {
+      ra = max(ra, 0); rb = min(rb, H - 1); ca = max(ca, 0); cb = min(cb, W - 1);
+      if (ra > rb || ca > cb) {                                       // a unit clear of the window: zeros, nothing staged (uniform over the workgroup)
+        for (int r = ty; r < nr; r += tyn) amg_store4<VEC>(mp + (size_t)(py0 + r) * PW + col0, 0u, ok);
+        continue;
+      }
+    }
     // the source window of the unit: taps are monotone in the destination index
     int ya, yb, xa, xb, t;
     float tl;
-    bil_axis(oy0, sy, h, ya, t, tl);
-    bil_axis(oy0 + nr - 1, sy, h, t, yb, tl);
-    bil_axis(c0, sx, w, xa, t, tl);
-    bil_axis(c0 + nc - 1, sx, w, t, xb, tl);
+    bil_axis(ra, sy, h, ya, t, tl);
+    bil_axis(rb, sy, h, t, yb, tl);
+    bil_axis(ca, sx, w, xa, t, tl);
+    bil_axis(cb, sx, w, t, xb, tl);
     const int ncols = xb - xa + 1, nrows = yb - ya + 1;
     __syncthreads();                                                  // the previous unit's reads of tile / the y table are over
     if (tid < nr) {
       int y0, y1;
       float ly;
-      bil_axis(oy0 + tid, sy, h, y0, y1, ly);
+      bil_axis(WIN ? min(max(py0 + tid - wy0, ra), rb) : py0 + tid, sy, h, y0, y1, ly);       // (a row off the window is not sampled)
       yo0[tid] = (y0 - ya) * ncols; yo1[tid] = (y1 - ya) * ncols; yl[tid] = ly;
     }
     for (int r = 0; r < nrows; ++r) {
@@ -91,47 +127,40 @@ __global__ __launch_bounds__(AMG_THREADS) void amg_score_kernel(const float* __r
     }
     int xo0[AMG_COLS], xo1[AMG_COLS];
     float lx[AMG_COLS];
-    bool ok[AMG_COLS];
-    const int col0 = c0 + tx * AMG_COLS;
+    bool in[AMG_COLS];                                                // the column is counted: inside the chunk (and the window)
 #pragma unroll
     for (int k = 0; k < AMG_COLS; ++k) {
-      ok[k] = col0 + k < c0 + nc;
+      const int ox = col0 + k - wx0;
+      in[k] = ok[k] && (!WIN || (ox >= 0 && ox < W));
       int x0, x1;
-      bil_axis(min(col0 + k, W - 1), sx, w, x0, x1, lx[k]);
+      bil_axis(WIN ? min(max(ox, 0), W - 1) : min(ox, W - 1), sx, w, x0, x1, lx[k]);
       xo0[k] = min(max(x0 - xa, 0), ncols - 1); xo1[k] = min(max(x1 - xa, 0), ncols - 1);       // (a column past the chunk reads inside the window; it is not counted)
     }
     __syncthreads();
     unsigned col_on = 0;
     for (int r = ty; r < nr; r += tyn) {
-      const int o0 = yo0[r], o1 = yo1[r];
-      const float ly = yl[r];
-      const int oy = oy0 + r;
+      const int oy = py0 + r - wy0;
       unsigned row_on = 0;
+      if (!WIN || (oy >= 0 && oy < H)) {
+        const int o0 = yo0[r], o1 = yo1[r];
+        const float ly = yl[r];
 #pragma unroll
-      for (int k = 0; k < AMG_COLS; ++k) {
-        const float v = bil_mix(tile[o0 + xo0[k]], tile[o0 + xo1[k]], tile[o1 + xo0[k]], tile[o1 + xo1[k]], ly, lx[k]);
-        const bool on = ok[k] && v > mid;
-        n_hi += (ok[k] && v > hi) ? 1 : 0;
-        n_lo += (ok[k] && v > lo) ? 1 : 0;
-        area += on ? 1 : 0;
-        row_on |= (on ? 1u : 0u) << k;
+        for (int k = 0; k < AMG_COLS; ++k) {
+          const float v = bil_mix(tile[o0 + xo0[k]], tile[o0 + xo1[k]], tile[o1 + xo0[k]], tile[o1 + xo1[k]], ly, lx[k]);
+          const bool on = in[k] && v > mid;
+          n_hi += (in[k] && v > hi) ? 1 : 0;
+          n_lo += (in[k] && v > lo) ? 1 : 0;
+          area += on ? 1 : 0;
+          row_on |= (on ? 1u : 0u) << k;
+        }
       }
       col_on |= row_on;
       if (row_on) { ey0 = min(ey0, oy); ey1 = max(ey1, oy); }
-      if (MASK) {
-        uint8_t* mrow = mp + (size_t)oy * W + col0;
-        if (VEC) {                                                    // W % 4 == 0 and the planes 4-byte aligned: the 4 columns are all inside, one store
-          if (ok[0]) *reinterpret_cast<uint32_t*>(mrow) = ((row_on & 1u) ? 0xFFu : 0u) | ((row_on & 2u) ? 0xFF00u : 0u) | ((row_on & 4u) ? 0xFF0000u : 0u) | ((row_on & 8u) ? 0xFF000000u : 0u);
-        } else {
-#pragma unroll
-          for (int k = 0; k < AMG_COLS; ++k)
-            if (ok[k]) mrow[k] = ((row_on >> k) & 1u) ? 255 : 0;
-        }
-      }
+      if (MASK) amg_store4<VEC>(mp + (size_t)(py0 + r) * PW + col0, row_on, ok);
     }
 #pragma unroll
     for (int k = 0; k < AMG_COLS; ++k)
-      if ((col_on >> k) & 1u) { ex0 = min(ex0, col0 + k); ex1 = max(ex1, col0 + k); }
+      if ((col_on >> k) & 1u) { ex0 = min(ex0, col0 + k - wx0); ex1 = max(ex1, col0 + k - wx0); }
   }
 
 #pragma unroll
@@ -167,9 +196,10 @@ inline long long amg_span(int n, int in, int out) {
   return std::min<long long>(in, (long long)(n - 1) * in / out + 5);
 }
 
-inline bool amg_shape(int h, int w, int H, int W, AmgShape* sh) {
+// the units tile the PH x PW plane; a unit samples at most min(band, H) rows x min(chunk, W) columns of the H x W map
+inline bool amg_shape(int h, int w, int H, int W, int PH, int PW, AmgShape* sh) {
   int lg = 0;
-  while ((AMG_COLS << lg) < std::min(W, AMG_CHUNK)) ++lg;
+  while ((AMG_COLS << lg) < std::min(PW, AMG_CHUNK)) ++lg;
   sh->txn_log2 = lg;
   const int chunk_w = AMG_COLS << lg;
   const long long cols = amg_span(std::min(chunk_w, W), w, W);
@@ -179,8 +209,8 @@ inline bool amg_shape(int h, int w, int H, int W, AmgShape* sh) {
   if (floats > AMG_LDS_FLOATS) return false;
   sh->band = band;
   sh->lds_floats = (int)floats;
-  sh->nchunks = cdiv(W, chunk_w);
-  sh->nbands = cdiv(H, band);
+  sh->nchunks = cdiv(PW, chunk_w);
+  sh->nbands = cdiv(PH, band);
   return true;
 }
 
@@ -191,25 +221,42 @@ inline bool amg_shape(int h, int w, int H, int W, AmgShape* sh) {
 constexpr int SEL_THREADS = 256;
 constexpr int SEL_SPLIT = 4;
 
+// The crop the planes were decoded from, in the image: {x0, y0, x1, y1} with exclusive ends, the image's size and upstream's
+// is_box_near_crop_edge tolerance.  cvmi_amg_select is the crop that is the image.
+struct AmgCrop {
+  int x0, y0, x1, y1, W, H, tol;
+};
+
+// upstream's is_box_near_crop_edge in integers: the box (inclusive maxima, moved to the image) has a side within tol of the crop's side
+// and not within tol of the image's.  With crop = image the two tests are the same test: never true.
+__device__ __forceinline__ bool amg_cut_by_crop(const int* __restrict__ s, const AmgCrop& c) {
+  const int b[4] = {s[3] + c.x0, s[4] + c.y0, s[5] + c.x0, s[6] + c.y0};
+  const int crop[4] = {c.x0, c.y0, c.x1, c.y1}, orig[4] = {0, 0, c.W, c.H};
+  bool cut = false;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) cut |= abs(b[k] - crop[k]) <= c.tol && !(abs(b[k] - orig[k]) <= c.tol);
+  return cut;
+}
+
 __device__ __forceinline__ bool amg_keep(const int* __restrict__ stats, const float* __restrict__ iou, int i, float iou_thresh, float stab_thresh,
-                                         float* stab_out) {
+                                         const AmgCrop& crop, float* stab_out) {
   const float stab = (float)stats[(size_t)i * 8 + 0] / (float)stats[(size_t)i * 8 + 1];       // 0 / 0 = NaN: fails >=
   *stab_out = stab;
-  return iou[i] > iou_thresh && stab >= stab_thresh;
+  return iou[i] > iou_thresh && stab >= stab_thresh && !amg_cut_by_crop(stats + (size_t)i * 8, crop);
 }
 
 __global__ __launch_bounds__(SEL_THREADS) void amg_select_kernel(const int* __restrict__ stats, const float* __restrict__ iou,
                                                                 const float* __restrict__ low, int n_valid, int ncand, int point_base,
-                                                                float iou_thresh, float stab_thresh, int P, int cap, int* __restrict__ counter,
-                                                                cvmi_amg_record* __restrict__ records, float* __restrict__ pool,
-                                                                float* __restrict__ nms_block) {
+                                                                float iou_thresh, float stab_thresh, AmgCrop crop, int P, int cap,
+                                                                int* __restrict__ counter, cvmi_amg_record* __restrict__ records,
+                                                                float* __restrict__ pool, float* __restrict__ nms_block) {
   __shared__ int red[SEL_THREADS / 64][2];
   __shared__ int s_before, s_total, s_base;
   const int tid = threadIdx.x, j = blockIdx.x / SEL_SPLIT, part = blockIdx.x - j * SEL_SPLIT;
   int before = 0, total = 0;
   float stab;
   for (int i = tid; i < n_valid; i += SEL_THREADS) {
-    const int k = amg_keep(stats, iou, i, iou_thresh, stab_thresh, &stab) ? 1 : 0;
+    const int k = amg_keep(stats, iou, i, iou_thresh, stab_thresh, crop, &stab) ? 1 : 0;
     total += k;
     before += i < j ? k : 0;
   }
@@ -225,7 +272,7 @@ __global__ __launch_bounds__(SEL_THREADS) void amg_select_kernel(const int* __re
   }
   __syncthreads();
   const long long slot = (long long)s_base + s_before;
-  if (amg_keep(stats, iou, j, iou_thresh, stab_thresh, &stab) && slot < cap) {
+  if (amg_keep(stats, iou, j, iou_thresh, stab_thresh, crop, &stab) && slot < cap) {
     const f32x4* src = reinterpret_cast<const f32x4*>(low + (size_t)j * P);
     f32x4* dst = reinterpret_cast<f32x4*>(pool + (size_t)slot * P);
     for (int i = part * SEL_THREADS + tid; i < P / 4; i += SEL_SPLIT * SEL_THREADS) dst[i] = src[i];
@@ -257,19 +304,36 @@ __global__ __launch_bounds__(SEL_THREADS) void amg_select_kernel(const int* __re
   }
 }
 
-template <bool MASK>
-int amg_score_launch(const float* low, int M, int h, int w, int H, int W, float lo, float mid, float hi, const AmgShape& sh, int* stats,
-                     uint8_t* mask, hipStream_t s) {
+template <bool MASK, bool WIN>
+int amg_score_launch(const float* low, int M, int h, int w, int H, int W, float lo, float mid, float hi, const AmgShape& sh, const AmgWindow& win,
+                     int* stats, uint8_t* mask, hipStream_t s) {
   const dim3 grid(std::min(sh.nbands * sh.nchunks, AMG_GRID_CAP), M), block(AMG_THREADS);
   const float sy = (float)h / (float)H, sx = (float)w / (float)W;
   const size_t lds = (size_t)sh.lds_floats * sizeof(float);
   if constexpr (MASK) {
-    if (W % 4 == 0 && ((uintptr_t)mask & 3) == 0) {
-      hipLaunchKernelGGL((amg_score_kernel<true, true>), grid, block, lds, s, low, h, w, H, W, sy, sx, lo, mid, hi, sh, stats, mask);
+    if (win.PW % 4 == 0 && ((uintptr_t)mask & 3) == 0) {
+      hipLaunchKernelGGL((amg_score_kernel<true, true, WIN>), grid, block, lds, s, low, h, w, H, W, sy, sx, lo, mid, hi, sh, win, stats, mask);
       return 0;
     }
   }
-  hipLaunchKernelGGL((amg_score_kernel<MASK, false>), grid, block, lds, s, low, h, w, H, W, sy, sx, lo, mid, hi, sh, stats, mask);
+  hipLaunchKernelGGL((amg_score_kernel<MASK, false, WIN>), grid, block, lds, s, low, h, w, H, W, sy, sx, lo, mid, hi, sh, win, stats, mask);
+  return 0;
+}
+
+// the three launches of a scoring call: the map is the plane (cvmi_amg_score) or a window of it
+template <bool WIN>
+int amg_score_run(const char* who, const float* low, int M, int h, int w, int H, int W, float lo, float mid, float hi, const AmgWindow& win, int* stats,
+                  uint8_t* mask_u8, hipStream_t s) {
+  CVMI_CHECK(low && stats && M > 0 && M <= 65535 && h > 0 && w > 0 && H > 0 && W > 0, "%s: bad arguments", who);
+  CVMI_CHECK((long long)win.PH * win.PW < (1ll << 31) && (long long)h * w < (1ll << 31), "%s: a plane of 2^31 pixels or more", who);
+  AmgShape sh;
+  CVMI_CHECK(amg_shape(h, w, H, W, win.PH, win.PW, &sh), "%s: the source rows of one output row (%d x %d -> %d x %d) do not fit the staging buffer", who, h, w, H, W);
+  CVMI_CHECK((long long)sh.nbands * sh.nchunks < (1ll << 31), "%s: too many units", who);
+  hipLaunchKernelGGL(amg_init_kernel, dim3(cdiv(M, 256)), dim3(256), 0, s, stats, M, H, W);
+  if (mask_u8) amg_score_launch<true, WIN>(low, M, h, w, H, W, lo, mid, hi, sh, win, stats, mask_u8, s);
+  else amg_score_launch<false, false>(low, M, h, w, H, W, lo, mid, hi, sh, win, stats, nullptr, s);
+  hipLaunchKernelGGL(amg_finish_kernel, dim3(cdiv(M, 256)), dim3(256), 0, s, stats, M);
+  CVMI_LAUNCH_CHECK();
   return 0;
 }
 
@@ -277,29 +341,48 @@ int amg_score_launch(const float* low, int M, int h, int w, int H, int W, float 
 
 extern "C" int cvmi_amg_score(const float* low, int M, int h, int w, int H, int W, float lo, float mid, float hi, int* stats, uint8_t* mask_u8,
                               cvmi_stream_t stream_) {
-  CVMI_CHECK(low && stats && M > 0 && M <= 65535 && h > 0 && w > 0 && H > 0 && W > 0, "amg_score: bad arguments");
-  CVMI_CHECK((long long)H * W < (1ll << 31) && (long long)h * w < (1ll << 31), "amg_score: a plane of 2^31 pixels or more");
-  AmgShape sh;
-  CVMI_CHECK(amg_shape(h, w, H, W, &sh), "amg_score: the source rows of one output row (%d x %d -> %d x %d) do not fit the staging buffer", h, w, H, W);
-  CVMI_CHECK((long long)sh.nbands * sh.nchunks < (1ll << 31), "amg_score: too many units");
-  hipStream_t s = (hipStream_t)stream_;
-  hipLaunchKernelGGL(amg_init_kernel, dim3(cdiv(M, 256)), dim3(256), 0, s, stats, M, H, W);
-  if (mask_u8) amg_score_launch<true>(low, M, h, w, H, W, lo, mid, hi, sh, stats, mask_u8, s);
-  else amg_score_launch<false>(low, M, h, w, H, W, lo, mid, hi, sh, stats, nullptr, s);
-  hipLaunchKernelGGL(amg_finish_kernel, dim3(cdiv(M, 256)), dim3(256), 0, s, stats, M);
+  return amg_score_run<false>("amg_score", low, M, h, w, H, W, lo, mid, hi, AmgWindow{H, W, 0, 0}, stats, mask_u8, (hipStream_t)stream_);
+}
+
+extern "C" int cvmi_amg_score_window(const float* low, int M, int h, int w, int H, int W, float lo, float mid, float hi, int* stats,
+                                     uint8_t* mask_u8, int PH, int PW, int wx0, int wy0, cvmi_stream_t stream_) {
+  CVMI_CHECK(mask_u8, "amg_score_window: null pointer");
+  CVMI_CHECK(H > 0 && W > 0 && PH > 0 && PW > 0 && wx0 >= 0 && wy0 >= 0 && (long long)wx0 + W <= PW && (long long)wy0 + H <= PH,
+             "amg_score_window: the %d x %d window at (%d, %d) leaves the %d x %d plane", H, W, wx0, wy0, PH, PW);
+  return amg_score_run<true>("amg_score_window", low, M, h, w, H, W, lo, mid, hi, AmgWindow{PH, PW, wx0, wy0}, stats, mask_u8, (hipStream_t)stream_);
+}
+
+namespace {
+
+int amg_select_run(const char* who, const int* stats, const float* iou, const float* low, int n, int n_valid, int ncand, int point_base,
+                   float iou_thresh, float stab_thresh, const AmgCrop& crop, int P, int cap, int* counter, cvmi_amg_record* records, float* pool,
+                   float* nms_block, hipStream_t s) {
+  CVMI_CHECK(stats && iou && low && counter && records && pool && nms_block, "%s: null pointer", who);
+  CVMI_CHECK(n > 0 && n_valid >= 0 && n_valid <= n && n <= (1 << 20) && ncand > 0 && point_base >= 0 && cap > 0, "%s: bad arguments", who);
+  CVMI_CHECK(P > 0 && P % 4 == 0 && ((uintptr_t)low & 15) == 0 && ((uintptr_t)pool & 15) == 0, "%s: planes must be a multiple of 4 floats, 16-byte aligned", who);
+  if (n_valid == 0) return 0;
+  hipLaunchKernelGGL(amg_select_kernel, dim3(n_valid * SEL_SPLIT), dim3(SEL_THREADS), 0, s, stats, iou, low, n_valid, ncand, point_base, iou_thresh,
+                     stab_thresh, crop, P, cap, counter, records, pool, nms_block);
   CVMI_LAUNCH_CHECK();
   return 0;
 }
 
+}  // namespace
+
 extern "C" int cvmi_amg_select(const int* stats, const float* iou, const float* low, int n, int n_valid, int ncand, int point_base,
                                float iou_thresh, float stab_thresh, int P, int cap, int* counter, cvmi_amg_record* records, float* pool,
                                float* nms_block, cvmi_stream_t stream_) {
-  CVMI_CHECK(stats && iou && low && counter && records && pool && nms_block, "amg_select: null pointer");
-  CVMI_CHECK(n > 0 && n_valid >= 0 && n_valid <= n && n <= (1 << 20) && ncand > 0 && point_base >= 0 && cap > 0, "amg_select: bad arguments");
-  CVMI_CHECK(P > 0 && P % 4 == 0 && ((uintptr_t)low & 15) == 0 && ((uintptr_t)pool & 15) == 0, "amg_select: planes must be a multiple of 4 floats, 16-byte aligned");
-  if (n_valid == 0) return 0;
-  hipLaunchKernelGGL(amg_select_kernel, dim3(n_valid * SEL_SPLIT), dim3(SEL_THREADS), 0, (hipStream_t)stream_, stats, iou, low, n_valid, ncand,
-                     point_base, iou_thresh, stab_thresh, P, cap, counter, records, pool, nms_block);
-  CVMI_LAUNCH_CHECK();
-  return 0;
+  // no crop: the crop is the image, whatever its size, and the border filter is identically false
+  return amg_select_run("amg_select", stats, iou, low, n, n_valid, ncand, point_base, iou_thresh, stab_thresh, AmgCrop{0, 0, 0, 0, 0, 0, 0}, P, cap,
+                        counter, records, pool, nms_block, (hipStream_t)stream_);
+}
+
+extern "C" int cvmi_amg_select_crop(const int* stats, const float* iou, const float* low, int n, int n_valid, int ncand, int point_base,
+                                    float iou_thresh, float stab_thresh, int P, int cap, int* counter, cvmi_amg_record* records, float* pool,
+                                    float* nms_block, int cx0, int cy0, int cx1, int cy1, int W, int H, int edge_tol, cvmi_stream_t stream_) {
+  CVMI_CHECK(W > 0 && H > 0 && W < (1 << 24) && H < (1 << 24) && 0 <= cx0 && cx0 < cx1 && cx1 <= W && 0 <= cy0 && cy0 < cy1 && cy1 <= H,
+             "amg_select_crop: the crop [%d, %d, %d, %d] is empty or leaves the %d x %d image", cx0, cy0, cx1, cy1, W, H);
+  CVMI_CHECK(edge_tol >= 0 && edge_tol < (1 << 24), "amg_select_crop: bad edge_tol");
+  return amg_select_run("amg_select_crop", stats, iou, low, n, n_valid, ncand, point_base, iou_thresh, stab_thresh,
+                        AmgCrop{cx0, cy0, cx1, cy1, W, H, edge_tol}, P, cap, counter, records, pool, nms_block, (hipStream_t)stream_);
 }

@@ -533,6 +533,30 @@ int cvmi_amg_select(const int* stats, const float* iou, const float* low, int n,
                     float stab_thresh, int P, int cap, int* counter, cvmi_amg_record* records, float* pool, float* nms_block,
                     cvmi_stream_t stream);
 
+/* Crop layers (upstream's crop_n_layers > 0): the planes of a call belong to ONE crop of the image, the rectangle [cx0, cx1) x [cy0, cy1) of
+ * a W x H image, and stats / records / nms_block are in the crop's own coordinates (the IoU of the per-crop NMS is translation-invariant and
+ * the integers are exact in f32; the caller adds the offsets).
+ *
+ * cvmi_amg_select_crop: cvmi_amg_select -- the same kernel -- whose keep rule also holds upstream's ~is_box_near_crop_edge, in integers.
+ * With b = (x0 + cx0, y0 + cy0, x1 + cx0, y1 + cy0) from the stats (the inclusive maxima and the empty mask's {0, 0, 0, 0} taken as they
+ * are), crop = (cx0, cy0, cx1, cy1) and orig = (0, 0, W, H), a candidate is dropped iff for some side k
+ *   |b_k - crop_k| <= edge_tol  and not  |b_k - orig_k| <= edge_tol        (upstream: edge_tol = 20; a distance of exactly edge_tol drops).
+ * The filter enters both the "kept before me" prefix and the total: slots stay dense and in candidate order.  cvmi_amg_select is this call
+ * with crop = image, for which the filter is identically false.  Refused: an empty crop, one that leaves the image, W or H of 2^24 or more. */
+int cvmi_amg_select_crop(const int* stats, const float* iou, const float* low, int n, int n_valid, int ncand, int point_base, float iou_thresh,
+                         float stab_thresh, int P, int cap, int* counter, cvmi_amg_record* records, float* pool, float* nms_block, int cx0,
+                         int cy0, int cx1, int cy1, int W, int H, int edge_tol, cvmi_stream_t stream);
+
+/* cvmi_amg_score_window: cvmi_amg_score's mask mode for a crop of size (H, W) whose masks belong in full-image planes: mask_u8 is
+ * u8 [M,PH,PW] and the H x W mask sits at (wx0, wy0) in each plane.  stats are cvmi_amg_score's for the same planes (crop coordinates);
+ * inside the window the bytes are the ones its mask mode writes, outside they are 0, and EVERY byte of every plane is written by this one
+ * call (no memset before it, no crop-sized temporary, no copy).  The same kernel: its units tile the plane, so a thread stores aligned
+ * words of it (PW % 4 == 0, aligned base; bytes otherwise) wherever the window starts; only units that meet the window stage and sample.
+ * Window = plane is cvmi_amg_score bit for bit.  Refused before any launch: a null mask_u8, a window that leaves the plane, a plane of 2^31
+ * pixels or more, and what cvmi_amg_score refuses. */
+int cvmi_amg_score_window(const float* low, int M, int h, int w, int H, int W, float lo, float mid, float hi, int* stats, uint8_t* mask_u8,
+                          int PH, int PW, int wx0, int wy0, cvmi_stream_t stream);
+
 /* Hole and sprinkle removal of postprocess_masks (sam2_infer.py:88-128) and the labelling under it, on f32 planes x [N,h,w] with a
  * threshold t.  Foreground is x > t, background x <= t; components are 8-connected in BOTH phases and never cross a plane; h and w need
  * not be even.  The label of a pixel is 1 + (y * w + x) of the raster-first pixel of its component, its area the component's pixel count.
