@@ -148,6 +148,7 @@ SIGNATURES = {
     "cvmi_select_mask": (_i, [_vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _i, _i, _vp]),
     "cvmi_multimask_out": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _vp]),
     "cvmi_best_candidate": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _vp]),
+    "cvmi_m2m_fanout": (_i, [_vp, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "cvmi_mask_prompt_embed": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "cvmi_mask_prompt_embed_pairs": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp]),
     "cvmi_bilinear_f32": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, _f, _vp]),

@@ -8,7 +8,10 @@ are turned into masks (cvmi_amg_score's mask mode, so `area` and `bbox` describe
 With `crop_n_layers > 0` (a per-call argument) the grid runs again on overlapping crops of the image (amg_utils.generate_crop_boxes): the
 crops are source rectangles of ONE uploaded image (cvmi_sam2_transform_srcs), encoded as a batch; the append drops the candidates a crop
 border cuts (cvmi_amg_select_crop); a second cvmi_yolo_nms across the crops prefers the smaller crop; and the survivors' masks are written
-into a window of a full-image plane (cvmi_amg_score_window)."""
+into a window of a full-image plane (cvmi_amg_score_window).
+
+With `use_m2m=True` (a per-call argument) every chunk's candidates are refined by upstream's mask-to-mask pass before they are scored:
+`infer_masks(m2m=True)` replays a second, single-mask decode plan behind the first, fed on the device by cvmi_m2m_fanout."""
 import numpy as np
 import torch
 
@@ -19,6 +22,7 @@ from .sam2_infer import F32, SAM2Transforms, Sam2Embeddings
 OUTPUT_KEYS = ("segmentation", "area", "bbox", "predicted_iou", "point_coords", "stability_score", "crop_box")
 NMS_MAX_DET = 4096                               # cvmi_yolo_nms keeps at most this many boxes per image
 POOL_BYTES_IN_FLIGHT = 4 << 30                   # images (or crops) are processed in sub-batches whose candidate pools stay below this
+M2M_PAIRS_IN_FLIGHT = 1024                       # use_m2m: pairs of a chunk's second decode plan (ncand * points_per_batch per image decoded together)
 CROP_EDGE_TOL = 20                               # upstream's is_box_near_crop_edge atol, in pixels
 
 
@@ -42,8 +46,8 @@ class Sam2AutomaticMaskGenerator:
     value travels through the host between the chunks.)
 
     Two of upstream's constructor options are PER-CALL arguments of `generate` / `generate_batch` here, so that one generator and one plan
-    serve a different output form per request (the constructor still refuses them, with `crop_n_layers`, `use_m2m` and a non-default
-    `output_mode`):
+    serve a different output form per request (the constructor still refuses them, with `crop_n_layers`, `use_m2m` -- per-call arguments too,
+    below -- and a non-default `output_mode`):
       min_mask_region_area > 0   upstream's postprocess_small_regions after the first NMS (amg_utils.py: holes below the area filled, then
                                  islands below it removed, on the GPU; every box recomputed; a second box NMS with box_nms_thresh in which an
                                  unchanged mask outranks a changed one).  The list comes back in that NMS's order -- unchanged masks first, each
@@ -75,7 +79,18 @@ class Sam2AutomaticMaskGenerator:
     `segmentation`, `area`, `bbox` and `point_coords` are in the ORIGINAL image's coordinates (point_coords = [[gx * cw + cx0, gy * ch + cy0]]
     for the crop [cx0, cy0, cw, ch], which is `crop_box`).  Both options above compose with crops; the second NMS of min_mask_region_area then
     uses max(box_nms_thresh, crop_nms_thresh), upstream's rule.  The host waits, per image: once per sub-batch of crops (as above), once after
-    the cross-crop NMS for its keep list, and the options' one extra wait.  With crop_n_layers == 0 nothing of this runs."""
+    the cross-crop NMS for its keep list, and the options' one extra wait.  With crop_n_layers == 0 nothing of this runs.
+
+    The mask-to-mask pass is a per-call argument as well (the constructor refuses `use_m2m=True` and points here):
+      use_m2m=True               upstream's refine_with_m2m: every candidate of a chunk -- before anything is filtered -- goes back to the decoder
+                                 as its own mask prompt (its logits clamped to [-32, 32], beside the grid point it came from) in ONE single-mask
+                                 pass, inside the chunk's `infer_masks(m2m=True)` call: no extra host wait, no extra upload.  The refined planes
+                                 and the refined predicted IoUs take the first pass's place, so the filters, the NMS and `predicted_iou`,
+                                 `stability_score`, `area`, `bbox`, `segmentation` describe the refined candidate; `point_coords` stays the grid
+                                 point.  Composes with every option above (they all run behind it) and with multimask_output=False.  The second
+                                 decode plan of a chunk holds ncand * points_per_batch pairs per image: the images (crops) decoded together are
+                                 also bounded so that it stays at or below 1024 pairs (M2M_PAIRS_IN_FLIGHT; 5 images at the defaults).
+    With use_m2m=False nothing of this runs: the path, the launches and the results are the ones above."""
 
     def __init__(self, model, points_per_side=32, points_per_batch=64, pred_iou_thresh=0.8, stability_score_thresh=0.95,
                  stability_score_offset=1.0, mask_threshold=0.0, box_nms_thresh=0.7, point_grids=None, multimask_output=True, max_candidates=None,
@@ -87,7 +102,7 @@ class Sam2AutomaticMaskGenerator:
             raise NotImplementedError("min_mask_region_area > 0 is a per-call argument here: generate(image, min_mask_region_area=...) / "
                                       "generate_batch(..., min_mask_region_area=...), or amg_utils.postprocess_small_regions on a returned list")
         if use_m2m:
-            raise NotImplementedError("use_m2m=True: the mask-to-mask refinement pass is not built")
+            raise NotImplementedError("use_m2m=True is a per-call argument here: generate(image, use_m2m=True) / generate_batch(..., use_m2m=True)")
         if output_mode != "binary_mask":
             raise NotImplementedError(f"output_mode={output_mode!r} is a per-call argument here: generate(image, output_mode='uncompressed_rle') / "
                                       "generate_batch(..., output_mode=...), or amg_utils.mask_to_rle on returned planes ('coco_rle' is not built)")
@@ -125,15 +140,15 @@ class Sam2AutomaticMaskGenerator:
 
     # -- public surface
     def generate(self, image, min_mask_region_area=0, output_mode="binary_mask", crop_n_layers=0, crop_overlap_ratio=512 / 1500,
-                 crop_n_points_downscale_factor=1, crop_nms_thresh=0.7):
+                 crop_n_points_downscale_factor=1, crop_nms_thresh=0.7, use_m2m=False):
         """image: RGB u8 [H, W, 3] (array or PIL) -> list of dicts.  The per-call options: see the class."""
         img = self.transforms._check_u8(image)
         return self.generate_batch([img], min_mask_region_area=min_mask_region_area, output_mode=output_mode, crop_n_layers=crop_n_layers,
                                    crop_overlap_ratio=crop_overlap_ratio, crop_n_points_downscale_factor=crop_n_points_downscale_factor,
-                                   crop_nms_thresh=crop_nms_thresh)[0]
+                                   crop_nms_thresh=crop_nms_thresh, use_m2m=use_m2m)[0]
 
     def generate_batch(self, images, orig_hw=None, min_mask_region_area=0, output_mode="binary_mask", crop_n_layers=0, crop_overlap_ratio=512 / 1500,
-                       crop_n_points_downscale_factor=1, crop_nms_thresh=0.7):
+                       crop_n_points_downscale_factor=1, crop_nms_thresh=0.7, use_m2m=False):
         """images: a list of RGB u8 [H, W, 3] images (orig_hw then defaults to their sizes), a [B, 3, R, R] tensor as `infer_masks` takes it, or
         the `Sam2Embeddings` `encode_images` made of one; orig_hw = [(H, W)] per image.  -> one list of dicts per image.  crop_n_layers > 0
         takes the list of u8 images only."""
@@ -150,7 +165,7 @@ class Sam2AutomaticMaskGenerator:
             raise ValueError("crop_n_layers must be >= 0")
         if int(crop_n_layers) > 0:
             return self._generate_batch_crops(images, int(crop_n_layers), float(crop_overlap_ratio), crop_n_points_downscale_factor,
-                                              float(crop_nms_thresh), min_area, output_mode)
+                                              float(crop_nms_thresh), min_area, output_mode, bool(use_m2m))
         if isinstance(images, (list, tuple)):
             imgs = [self.transforms._check_u8(im) for im in images]
             if orig_hw is None:
@@ -167,20 +182,29 @@ class Sam2AutomaticMaskGenerator:
         if B == 0:
             return []
         f0 = model.image_size // 4
-        step = max(1, POOL_BYTES_IN_FLIGHT // (self.cap * f0 * f0 * 4))
+        step = self._images_in_flight(bool(use_m2m))
         out = []
         for a in range(0, B, step):
             src = images[a:a + step]
             emb = src if isinstance(src, Sam2Embeddings) else model.encode_images(src)
-            out += self._generate(emb, sizes[a:a + step], min_area, output_mode)
+            out += self._generate(emb, sizes[a:a + step], min_area, output_mode, bool(use_m2m))
         return out
 
+    def _images_in_flight(self, m2m):
+        """Images (or crops) per sub-batch: their candidate pools stay below POOL_BYTES_IN_FLIGHT and, with the mask-to-mask pass, the pairs of
+        a chunk's second decode plan (ncand * points_per_batch per image) at or below M2M_PAIRS_IN_FLIGHT -- one image always goes through."""
+        f0 = self.model.image_size // 4
+        step = max(1, POOL_BYTES_IN_FLIGHT // (self.cap * f0 * f0 * 4))
+        return min(step, max(1, M2M_PAIRS_IN_FLIGHT // (self.ncand * self.points_per_batch))) if m2m else step
+
     # -- one sub-batch
-    def _candidates(self, emb, sizes, grid=None, points_in=None, crops=None, image_hw=None):
+    def _candidates(self, emb, sizes, grid=None, points_in=None, crops=None, image_hw=None, m2m=False):
         """Enqueue every chunk of the grid for the images of `emb`: decode, score, filter + append.  -> the per-image device state
         (counter i32 [B, 2], records i32 [B, cap, 10], pool f32 [B, cap, R/4, R/4], block f32 [B, 5, cap]); nothing is read back.
         grid / points_in: a crop layer's grid in the place of the generator's; crops = [[x0, y0, x1, y1]] per "image" of `emb`, the crops of
-        one image of size image_hw = (H, W): sizes are then the crops' and the append holds the border filter."""
+        one image of size image_hw = (H, W): sizes are then the crops' and the append holds the border filter.
+        m2m: every chunk's decode is `infer_masks(m2m=True)` -- the refined candidates and their predicted IoUs take the first pass's place
+        in front of everything below, in the first pass's candidate order (so `point` and `token` name the first-pass candidate)."""
         lib, model = _lib.load(), self.model
         B, cap, C, Pb = len(emb), self.cap, self.ncand, self.points_per_batch
         f0 = model.image_size // 4
@@ -196,13 +220,14 @@ class Sam2AutomaticMaskGenerator:
         block[:, 4].fill_(float("-inf"))                                         # unused columns never pass the NMS's conf_thres
         stats = torch.empty(B, Pb * C, 8, dtype=torch.int32, device=dev)
         labels = torch.ones(B, Pb, 1, dtype=torch.int32)
+        m2m_kw = dict(m2m=True) if m2m else {}
         for base in range(0, len(grid), Pb):
             pts = points_in[base:base + Pb]
             n_valid = pts.shape[0]
             if n_valid < Pb:                                                     # a short last chunk: the last point repeated, never selected
                 pts = torch.cat([pts, pts[-1:].expand(Pb - n_valid, 2)])
             _, low, iou = model.infer_masks(emb, points=pts.view(1, Pb, 1, 2).expand(B, Pb, 1, 2), point_labels=labels,
-                                            multimask_output=self.multimask_output, return_high_res=False)
+                                            multimask_output=self.multimask_output, return_high_res=False, **m2m_kw)
             low, iou = low.view(B, Pb * C, f0, f0), iou.view(B, Pb * C)
             for b, (H, W) in enumerate(sizes):
                 _lib.check(lib.cvmi_amg_score(low[b].data_ptr(), Pb * C, f0, f0, H, W, lo, mid, hi, stats[b].data_ptr(), None, sp), "amg_score")
@@ -251,10 +276,10 @@ class Sam2AutomaticMaskGenerator:
         return {"segmentation": seg, "area": int(r["area"]), "bbox": [x0 + cx0, y0 + cy0, x1 - x0, y1 - y0], "predicted_iou": float(r["score"]),
                 "point_coords": [[float(gx * cw + cx0), float(gy * ch + cy0)]], "stability_score": float(r["stability"]), "crop_box": [cx0, cy0, cw, ch]}
 
-    def _generate(self, emb, sizes, min_area=0, output_mode="binary_mask"):
+    def _generate(self, emb, sizes, min_area=0, output_mode="binary_mask", m2m=False):
         """Candidates, NMS, the single host wait, then the survivors' masks."""
         with torch.cuda.device(emb.device):
-            st = self._candidates(emb, sizes)
+            st = self._candidates(emb, sizes, m2m=m2m)
             keep_idx, host = self._first_nms(st)
             torch.cuda.current_stream().synchronize()                                # the one wait
             kept_n, kept_idx, recs = self._read(host)
@@ -276,7 +301,7 @@ class Sam2AutomaticMaskGenerator:
         return [self._dict(masks[k], r, grid, crop) for k, (r, grid, crop) in enumerate(rows)]
 
     # -- crop layers
-    def _generate_batch_crops(self, images, n_layers, overlap_ratio, downscale, crop_nms_thresh, min_area, output_mode):
+    def _generate_batch_crops(self, images, n_layers, overlap_ratio, downscale, crop_nms_thresh, min_area, output_mode, m2m=False):
         if not isinstance(images, (list, tuple)):
             raise ValueError("crop_n_layers > 0 needs the pixels: images must be a list of RGB u8 images, not a tensor or embeddings")
         if self.points_per_side is None:
@@ -284,9 +309,9 @@ class Sam2AutomaticMaskGenerator:
         grids = [(g, torch.from_numpy(g.astype(np.float32)) * float(self.model.image_size))
                  for g in amg_utils.build_all_layer_point_grids(self.points_per_side, n_layers, downscale)]
         imgs = [self.transforms._check_u8(im) for im in images]
-        return [self._generate_crops(im, n_layers, overlap_ratio, grids, crop_nms_thresh, min_area, output_mode) for im in imgs]
+        return [self._generate_crops(im, n_layers, overlap_ratio, grids, crop_nms_thresh, min_area, output_mode, m2m) for im in imgs]
 
-    def _generate_crops(self, img, n_layers, overlap_ratio, grids, crop_nms_thresh, min_area, output_mode):
+    def _generate_crops(self, img, n_layers, overlap_ratio, grids, crop_nms_thresh, min_area, output_mode, m2m=False):
         """One image: its crops in sub-batches (one wait each), the cross-crop NMS (one wait), the survivors' masks in full-image planes."""
         from .detector import PackedImages
         model = self.model
@@ -294,7 +319,7 @@ class Sam2AutomaticMaskGenerator:
         boxes, layers = amg_utils.generate_crop_boxes((H, W), n_layers, overlap_ratio)
         R, f0, cap = model.image_size, model.image_size // 4, self.cap
         packed = PackedImages.upload([img])                                       # the one H2D of the pixels
-        step = max(1, POOL_BYTES_IN_FLIGHT // (cap * f0 * f0 * 4))
+        step = self._images_in_flight(m2m)
         lows, rows = [], []
         for a in range(0, len(boxes), step):
             sub, n = boxes[a:a + step], len(boxes[a:a + step])
@@ -309,7 +334,7 @@ class Sam2AutomaticMaskGenerator:
                     while j < n and layers[a + j] == layers[a + i]:
                         j += 1
                     grid, points_in = grids[layers[a + i]]
-                    st = self._candidates(emb[i:j], [(c[3] - c[1], c[2] - c[0]) for c in sub[i:j]], grid, points_in, sub[i:j], (H, W))
+                    st = self._candidates(emb[i:j], [(c[3] - c[1], c[2] - c[0]) for c in sub[i:j]], grid, points_in, sub[i:j], (H, W), m2m)
                     groups.append((i, j, grid, st["pool"], *self._first_nms(st)))
                     i = j
                 torch.cuda.current_stream().synchronize()                        # the sub-batch's wait

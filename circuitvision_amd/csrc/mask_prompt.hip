@@ -17,6 +17,11 @@
 //                              candidate with the highest predicted IoU, copied to the next pass's mask_in.  Every workgroup of a pair reads the
 //                              pair's NM IoUs itself (12 bytes, no second launch, no atomics) and then moves 16 bytes per lane and step of the
 //                              ONE selected plane: n * P * 4 bytes in, as many out.
+//   m2m_fanout_kernel          the mask-to-mask pass of upstream's automatic mask generator: EVERY candidate of a pass becomes a prompt of the
+//                              next, single-mask pass.  The pair's NM planes are contiguous on both sides (candidate-major inside the pair), so
+//                              the planes are one elementwise torch.clamp (comparisons: a NaN stays) at 16 bytes per lane and step of a
+//                              grid-stride loop -- n * NM * P * 4 bytes in, as many out --, and the pair's first workgroup writes its rows of
+//                              the prompt tables NM times.  Plain vector stores, no atomics.
 #include <algorithm>
 
 #include "common.hpp"
@@ -180,6 +185,33 @@ __global__ __launch_bounds__(NT) void best_candidate_kernel(const float* __restr
   for (int i = blockIdx.x * NT + threadIdx.x; i < P4; i += gridDim.x * NT) dst[i] = src[i];
 }
 
+constexpr int M2M_GRID_X = 64;                // workgroups per pair, as best_candidate_kernel's: M2M_GRID_X * NT 16-byte groups per pass of the loop
+
+// torch.clamp(v, -c, c) bit for bit: comparisons, so that a NaN fails both and stays, -0.0 lies inside and stays, +-inf become +-c
+__device__ __forceinline__ float clamp_keep_nan(float v, float c) { return v < -c ? -c : (v > c ? c : v); }
+
+template <int NM>
+__global__ __launch_bounds__(NT) void m2m_fanout_kernel(const float* __restrict__ low_res, float c, float* __restrict__ mask_out, const float* __restrict__ coords,
+                                                        const int* __restrict__ labels, const int* __restrict__ pair_image, float* __restrict__ coords_out,
+                                                        int* __restrict__ labels_out, int* __restrict__ pair_image_out, int G, int K) {
+  // grid.y = pair; G = NM * P / 4 16-byte groups of the pair's NM planes, which are contiguous on both sides (candidate-major inside the pair)
+  const size_t b = blockIdx.y;
+  const f32x4* src = (const f32x4*)low_res + b * G;
+  f32x4* dst = (f32x4*)mask_out + b * G;
+  for (int i = blockIdx.x * NT + threadIdx.x; i < G; i += gridDim.x * NT) {
+    const f32x4 v = src[i];
+    f32x4 o;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) o[k] = clamp_keep_nan(v[k], c);
+    dst[i] = o;
+  }
+  if (blockIdx.x == 0) {                                                 // the pair's prompt rows, written NM times
+    for (int t = threadIdx.x; t < NM * K * 2; t += NT) coords_out[b * NM * K * 2 + t] = coords[b * K * 2 + t % (K * 2)];
+    for (int t = threadIdx.x; t < NM * K; t += NT) labels_out[b * NM * K + t] = labels[b * K + t % K];
+    if (pair_image_out && threadIdx.x < NM) pair_image_out[b * NM + threadIdx.x] = pair_image[b];
+  }
+}
+
 }  // namespace
 
 // pair_image == nullptr: B * rep image-major pairs; else B pairs (rep = 1) whose images the device table names
@@ -243,6 +275,32 @@ extern "C" int cvmi_best_candidate(const float* low_res, const float* iou, int N
   } else {
     cvmi_note_kernel("best_candidate_kernel<1>");
     hipLaunchKernelGGL(best_candidate_kernel<1>, g, b, 0, s, low_res, iou, mask_out, sel_out, P4);
+  }
+  CVMI_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int cvmi_m2m_fanout(const float* low_res, int NM, float clamp, float* mask_out, const float* coords, const int* labels, const int* pair_image,
+                               float* coords_out, int* labels_out, int* pair_image_out, int n, int P, int K, cvmi_stream_t stream_) {
+  CVMI_CHECK(NM == 1 || NM == 3, "m2m_fanout: NM = %d candidates: 1 or 3", NM);
+  CVMI_CHECK(n >= 0 && n <= 65535 && P > 0 && P % 4 == 0 && P <= (1 << 28) && K > 0 && K <= 65536,
+             "m2m_fanout: n = %d pairs of P = %d logits and K = %d tokens: n in 0 .. 65535, P a positive multiple of 4 up to 2^28, K in 1 .. 65536", n, P, K);
+  CVMI_CHECK(clamp >= 0.f, "m2m_fanout: the clamp bound must be a number >= 0");
+  CVMI_CHECK((pair_image == nullptr) == (pair_image_out == nullptr), "m2m_fanout: pair_image and pair_image_out go together (both NULL: uniform plans)");
+  if (n == 0) return 0;
+  CVMI_CHECK(low_res && mask_out && coords && labels && coords_out && labels_out, "m2m_fanout: bad arguments");
+  CVMI_CHECK((((uintptr_t)low_res | (uintptr_t)mask_out) & 15) == 0 &&
+                 (((uintptr_t)coords | (uintptr_t)labels | (uintptr_t)pair_image | (uintptr_t)coords_out | (uintptr_t)labels_out | (uintptr_t)pair_image_out) & 3) == 0,
+             "m2m_fanout: the planes must be 16-byte aligned (the prompt tables 4-byte)");
+  const int G = NM * (P / 4);
+  const dim3 g(std::min((G + NT - 1) / NT, M2M_GRID_X), n), b(NT);
+  hipStream_t s = (hipStream_t)stream_;
+  if (NM == 3) {
+    cvmi_note_kernel("m2m_fanout_kernel<3>");
+    hipLaunchKernelGGL(m2m_fanout_kernel<3>, g, b, 0, s, low_res, clamp, mask_out, coords, labels, pair_image, coords_out, labels_out, pair_image_out, G, K);
+  } else {
+    cvmi_note_kernel("m2m_fanout_kernel<1>");
+    hipLaunchKernelGGL(m2m_fanout_kernel<1>, g, b, 0, s, low_res, clamp, mask_out, coords, labels, pair_image, coords_out, labels_out, pair_image_out, G, K);
   }
   CVMI_LAUNCH_CHECK();
   return 0;

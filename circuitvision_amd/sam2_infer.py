@@ -106,6 +106,7 @@ def pack_prompt_lists(B, R, boxes=None, points=None, point_labels=None, mask_inp
     return dict(sizes=sizes, N=N, cap=cap, K=K, coords=coords, labels=labels, pair_image=pair_image, has_mask=mask_input is not None)
 
 
+M2M_MAX_PAIRS = 65535                            # cvmi_m2m_fanout: the pair is the second dimension of its grid
 _WEIGHTS_IDS = itertools.count(1)                # identity of one packing of weights (`SAM2Model.load_params`), unique in the process
 
 
@@ -281,7 +282,7 @@ class SAM2Model:
         """The seam tensors of an encode plan as (un-owned) embeddings."""
         return Sam2Embeddings(p.feat_s0.t, p.feat_s1.t, p.emb.t if p.emb is not None else None, p.keys0.t, self.image_size, self.dtype, self.weights_id)
 
-    def _run(self, p, src, outs, before=None, refine=(), pairs=0):
+    def _run(self, p, src, outs, before=None, refine=(), pairs=0, m2m=None):
         """Stage -> replay the plan -> copy `outs` = [(plan tensor, fresh tensor)] -- all on the model's stream, which first waits for the
         caller's current stream and is synchronised before returning (the reference's call is synchronous).  The output copies are
         part of the stream's order, so the next caller's replay (another session thread, app.py:134) cannot overwrite the plan's
@@ -289,16 +290,19 @@ class SAM2Model:
         src: images for a full plan, or `Sam2Embeddings` for a decode plan (copied into its inputs first, then `before`).
         refine: the decode plans of the mask-feedback passes that follow p (itself a decode plan then; with images the encode plan runs in
         front, once): each gets the embeddings and p's prompts, and `mask_in` from its predecessor's low_res / iou through
-        cvmi_best_candidate over the `pairs` real pairs, launched on the stream between the two replays."""
+        cvmi_best_candidate over the `pairs` real pairs, launched on the stream between the two replays.
+        m2m = (q, clamp): the mask-to-mask pass instead -- q, the single-mask decode plan of NM * pairs pairs, gets the embeddings, and
+        cvmi_m2m_fanout writes its mask_in / coords / labels / pair_image from p's low_res and p's prompts, between the two replays."""
         lib, sp = _lib.load(), self.stream.cuda_stream
+        chain = tuple(refine) + ((m2m[0],) if m2m is not None else ())
         self.stream.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(self.stream):
             keep, e = src, src if isinstance(src, Sam2Embeddings) else None
-            if e is not None or refine:
-                for q in (p,) + tuple(refine):
+            if e is not None or chain:
+                for q in (p,) + chain:
                     if q.plan.graph is None:                  # capture's warm pass runs on the buffers as they are: in front of the staging
                         q.plan.capture()
-            if e is None and refine:
+            if e is None and chain:
                 enc = self.plan(src.shape[0], stage="encode")
                 keep = self._stage_images(enc, src)
                 enc.plan.run()
@@ -324,6 +328,20 @@ class SAM2Model:
                 q.mask_in[pairs:].zero_()                     # the padding rows of a pairs = cap plan
                 q.plan.run()
                 prev = q
+            if m2m is not None:
+                q, clamp = m2m
+                self._stage_embeddings(q, e)
+                NM, f0, n2 = p.low_res.shape[1], p.low_res.shape[2], p.low_res.shape[1] * pairs
+                tables = (p.pair_image, q.pair_image) if p.pair_image is not None else (None, None)
+                _lib.check(lib.cvmi_m2m_fanout(p.low_res.data_ptr(), NM, clamp, q.mask_in.data_ptr(), p.coords.data_ptr(), p.labels.data_ptr(),
+                                               tables[0].data_ptr() if tables[0] is not None else None, q.coords.data_ptr(), q.labels.data_ptr(),
+                                               tables[1].data_ptr() if tables[1] is not None else None, pairs, f0 * f0, p.coords.shape[1], sp), "m2m_fanout")
+                if n2 < q.mask_in.shape[0]:                   # the padding rows of a pairs = cap plan: a zero mask, not-a-point tokens, image 0
+                    q.mask_in[n2:].zero_()
+                    q.coords[n2:].zero_()
+                    q.labels[n2:].fill_(-1)
+                    q.pair_image[n2:].zero_()
+                q.plan.run()
             for a, b in outs:
                 b.copy_(a, non_blocking=True)
         self.stream.synchronize()
@@ -370,7 +388,7 @@ class SAM2Model:
     forward = __call__
 
     def infer_masks(self, images, boxes=None, return_high_res=True, points=None, point_labels=None, mask_input=None, multimask_output=False,
-                    refine_steps=0):
+                    refine_steps=0, m2m=False, m2m_clamp=32.0):
         """Batched segmentation entry point (north_star).  images [B,3,R,R], or the `Sam2Embeddings` `encode_images` made of them (the trunk
         and the neck are then not run again: every prompt form below decodes from them, with the same checks and the same results).
         No prompt: exactly `SAM2ImageWrapper.forward` (learned prompts) -> (high_res [B,1,R,R], low_res [B,1,R/4,R/4], iou [B,1]).
@@ -392,14 +410,23 @@ class SAM2Model:
         refine_steps = k > 0 (needs a prompt and a checkpoint with mask_downscaling): upstream's recipe for ambiguous prompts on the device.
         The call as given is pass 1; k single-mask passes on the same prompts follow, each with the previous pass's best candidate (the
         highest predicted IoU, cvmi_best_candidate) as its mask prompt.  The trunk runs once, nothing goes through the host, and the
-        last pass's (high_res or None, low_res, iou) come back in the single-mask shapes, whatever multimask_output was."""
+        last pass's (high_res or None, low_res, iou) come back in the single-mask shapes, whatever multimask_output was.
+        m2m=True (needs a prompt and a checkpoint with mask_downscaling; not together with refine_steps): the mask-to-mask pass of upstream's
+        automatic mask generator (use_m2m).  The call as given is pass 1 and yields NM candidates per prompt (3 with multimask_output, else
+        1); ONE single-mask pass follows in which EVERY candidate is a prompt of its own: the prompt it came from plus its low-res logits,
+        clamped to [-m2m_clamp, m2m_clamp] as upstream's predictor returns them, as the mask prompt (cvmi_m2m_fanout).  The trunk runs once,
+        nothing goes through the host, the stream is synchronised once.  -> the refined candidates in pass 1's shapes and candidate order:
+        (high_res [B,P,NM,R,R] or None, low_res [B,P,NM,R/4,R/4], iou [B,P,NM]), without the NM axis when NM = 1; lists of [P_b,NM,...] in
+        the list form.  At most 65535 (image, prompt) pairs per call.  m2m_clamp: upstream's bound is 32; the argument exists so that a
+        test can make the clamp bite on a model whose logits never reach 32."""
         if not isinstance(refine_steps, int) or isinstance(refine_steps, bool) or refine_steps < 0:
             raise ValueError("refine_steps must be an int >= 0")
+        m2m = self._check_m2m(m2m, m2m_clamp, refine_steps)
         if _is_list(boxes) or _is_list(points) or _is_list(point_labels) or _is_list(mask_input):
-            return self._infer_masks_lists(images, boxes, return_high_res, points, point_labels, mask_input, multimask_output, refine_steps)
+            return self._infer_masks_lists(images, boxes, return_high_res, points, point_labels, mask_input, multimask_output, refine_steps, m2m)
         if boxes is None and points is None:
-            if mask_input is not None or refine_steps:
-                raise ValueError("mask_input / refine_steps need boxes and / or points (a mask-only prompt is not built)")
+            if mask_input is not None or refine_steps or m2m is not None:
+                raise ValueError("mask_input / refine_steps / m2m need boxes and / or points (a mask-only prompt is not built)")
             return self(images, multimask_output=multimask_output)
         B = self._check_src(images)
         bx = pts = None
@@ -436,24 +463,45 @@ class SAM2Model:
             coords[:, nb:nb + nk] = pts.reshape(B * P, nk, 2)
             labels[:, nb:nb + nk] = lab.reshape(B * P, nk)
         pk = dict(kw=dict(prompts=P), N=B * P, K=K, coords=coords, labels=labels, pair_image=None, mask=mk.reshape(B * P, f0, f0) if mk is not None else None)
-        hi, lo, iou = self._prompt_passes(images, B, pk, return_high_res, multimask_output, refine_steps)
+        hi, lo, iou = self._prompt_passes(images, B, pk, return_high_res, multimask_output, refine_steps, m2m)
         return tuple(t.view(B, P, *t.shape[1:]) if t is not None else None for t in (hi, lo, iou))
 
-    def _prompt_passes(self, src, B, pk, return_high_res, multimask_output, refine_steps):
+    @staticmethod
+    def _check_m2m(m2m, m2m_clamp, refine_steps):
+        """-> the clamp bound as a float when the mask-to-mask pass is asked for, else None."""
+        if not m2m:
+            return None
+        if refine_steps:
+            raise ValueError("m2m=True and refine_steps > 0 do not combine: one of the two mask-feedback forms per call")
+        clamp = float(m2m_clamp)
+        if not clamp >= 0:
+            raise ValueError("m2m_clamp must be a number >= 0")
+        return clamp
+
+    def _prompt_passes(self, src, B, pk, return_high_res, multimask_output, refine_steps, m2m=None):
         """The prompted decode of N (image, prompt) pairs packed on the host -- pk: kw = the plan's prompts=P or pairs=cap, N, K, coords, labels,
         pair_image (pairs plans), mask ([N, R/4, R/4], or a list of tensors that concatenate to it, or None) -- and the refine_steps mask-feedback
-        passes behind it -> (high_res or None, low_res, iou) with N in front."""
+        passes behind it -> (high_res or None, low_res, iou) with N in front.  m2m = the clamp bound: the mask-to-mask pass behind it instead,
+        a single-mask plan of NM * N pairs (prompts = NM * P, or pairs = NM * N rounded up to the bucket) -> the same with [N, NM] in front."""
         R, f0, N = self.image_size, self.image_size // 4, pk["N"]
         masked, multimask = pk["mask"] is not None, bool(multimask_output)
+        if m2m is not None and N > M2M_MAX_PAIRS:
+            raise ValueError(f"m2m=True with {N} (image, prompt) pairs: cvmi_m2m_fanout takes at most {M2M_MAX_PAIRS} per call")
         with self._lock, torch.cuda.device(self.dev):
-            if (masked or refine_steps) and not self._packed_weights().mask_prompt_ok:
+            if (masked or refine_steps or m2m is not None) and not self._packed_weights().mask_prompt_ok:
                 raise RuntimeError("this checkpoint carries no sam_prompt_encoder.mask_downscaling tensors: mask_input is unavailable")
-            stage = "decode" if refine_steps or isinstance(src, Sam2Embeddings) else "full"       # one-shot use: one graph and no copies
+            chained = bool(refine_steps) or m2m is not None
+            stage = "decode" if chained or isinstance(src, Sam2Embeddings) else "full"            # one-shot use: one graph and no copies
             plan = lambda high_res, mask_prompt, multi: self.plan(B, high_res=high_res, points=pk["K"], mask_prompt=mask_prompt, multimask=multi, stage=stage,
                                                                   **pk["kw"])
-            p = plan(return_high_res and not refine_steps, masked, multimask)
+            p = plan(return_high_res and not chained, masked, multimask)
             refine = [plan(return_high_res and i == refine_steps - 1, True, False) for i in range(refine_steps)]
-            last = refine[-1] if refine else p
+            last, fan = (refine[-1] if refine else p), None
+            if m2m is not None:
+                NM = 3 if multimask else 1
+                kw2 = dict(pairs=-(-NM * N // self.pair_bucket) * self.pair_bucket) if "pairs" in pk["kw"] else dict(prompts=NM * pk["kw"]["prompts"])
+                last = self.plan(B, high_res=return_high_res, points=pk["K"], mask_prompt=True, multimask=False, stage="decode", **kw2)
+                fan = (last, m2m)
 
             def prompts_in():                                          # on the model's stream, in front of the replay that reads them
                 p.coords.copy_(pk["coords"], non_blocking=False)
@@ -464,20 +512,22 @@ class SAM2Model:
                     mask = pk["mask"]
                     p.mask_in[:N].copy_(torch.cat([t.detach().to(self.dev, torch.float32) for t in mask]) if _is_list(mask) else mask, non_blocking=False)
                     p.mask_in[N:].zero_()
-            shp = (N, 3) if multimask and not refine else (N,)
+            shp = (N, 3) if multimask and not refine else (N,)            # (the mask-to-mask pass keeps pass 1's candidate axis)
             lo, iou = torch.empty(*shp, f0, f0, dtype=torch.float32, device=self.dev), torch.empty(*shp, dtype=torch.float32, device=self.dev)
             hi = torch.empty(*shp, R, R, dtype=torch.float32, device=self.dev) if return_high_res else None
-            outs = [(last.low_res[:N].view(*shp, f0, f0), lo), (last.iou[:N].view(*shp), iou)] + ([(last.high_res[:N].view(*shp, R, R), hi)] if return_high_res else [])
-            self._run(p, src, outs, before=prompts_in, refine=refine, pairs=N)
+            rows = N * (3 if multimask and fan is not None else 1)       # of `last`: every candidate is a pair of the mask-to-mask plan
+            outs = ([(last.low_res[:rows].view(*shp, f0, f0), lo), (last.iou[:rows].view(*shp), iou)]
+                    + ([(last.high_res[:rows].view(*shp, R, R), hi)] if return_high_res else []))
+            self._run(p, src, outs, before=prompts_in, refine=refine, pairs=N, m2m=fan)
             return hi, lo, iou
 
-    def _infer_masks_lists(self, images, boxes, return_high_res, points, point_labels, mask_input, multimask_output, refine_steps=0):
+    def _infer_masks_lists(self, images, boxes, return_high_res, points, point_labels, mask_input, multimask_output, refine_steps=0, m2m=None):
         """`infer_masks` with one prompt list per image: pack on the host (`pack_prompt_lists`), replay the `pairs=cap` plan, split."""
         B = self._check_src(images)
         pk = pack_prompt_lists(B, self.image_size, boxes, points, point_labels, mask_input, self.pair_bucket)
         sizes = pk["sizes"]
         pk.update(kw=dict(pairs=pk["cap"]), mask=mask_input if pk["has_mask"] else None)
-        hi, lo, iou = self._prompt_passes(images, B, pk, return_high_res, multimask_output, refine_steps)
+        hi, lo, iou = self._prompt_passes(images, B, pk, return_high_res, multimask_output, refine_steps, m2m)
         return (list(torch.split(hi, sizes)) if hi is not None else None), list(torch.split(lo, sizes)), list(torch.split(iou, sizes))
 
 

@@ -445,6 +445,21 @@ int cvmi_multimask_out(const float* masks, const float* iou, int iou_ld, float* 
  * P must be a multiple of 4, low_res / iou / mask_out 16-byte aligned (sel_out 4-byte), n <= 65535; n == 0 returns 0 without a launch. */
 int cvmi_best_candidate(const float* low_res, const float* iou, int NM, float* mask_out, int* sel_out, int n, int P, cvmi_stream_t stream);
 
+/* The mask-to-mask pass of upstream's SAM2AutomaticMaskGenerator (use_m2m: refine_with_m2m): EVERY candidate of a decoder pass becomes one
+ * prompt of a second, single-mask pass -- its own low-res logits, clamped as SAM2ImagePredictor._predict returns them, as the mask prompt and
+ * the prompt it came from beside them.  One launch prepares the second plan's inputs from the first plan's outputs for the n real pairs:
+ *   low_res  f32 [n, NM, P], NM = 1 or 3 (what a single-mask / multimask plan leaves in low_res)
+ *   mask_out f32 [n*NM, P]:        mask_out[i*NM + k] = clamp(low_res[i, k], -clamp, clamp) -- candidate-major inside the pair, so the planes
+ *                                  are one contiguous array in the order of low_res
+ *   coords f32 [n, K, 2], labels i32 [n, K], pair_image i32 [n] (or NULL) -> coords_out f32 [n*NM, K, 2], labels_out i32 [n*NM, K],
+ *   pair_image_out i32 [n*NM] (NULL exactly when pair_image is: the uniform prompts=P plans): row i written NM times, at rows i*NM .. i*NM+NM-1
+ * The clamp is torch.clamp's bit for bit: a NaN stays a NaN, -0.0 stays -0.0, +-inf become +-clamp (upstream's bound is 32; clamp >= 0).
+ * P must be a multiple of 4 (at most 2^28), low_res / mask_out 16-byte aligned (16-byte accesses; the tables 4-byte), K in 1 .. 65536,
+ * n <= 65535 (the pair is the grid's second dimension); n == 0 returns 0 without a launch.  No atomics: the result does not depend on the
+ * launch.  n * NM * P * 4 bytes in, as many out. */
+int cvmi_m2m_fanout(const float* low_res, int NM, float clamp, float* mask_out, const float* coords, const int* labels, const int* pair_image,
+                    float* coords_out, int* labels_out, int* pair_image_out, int n, int P, int K, cvmi_stream_t stream);
+
 /* Mask prompts (upstream PromptEncoder._embed_masks + SAM2ImagePredictor._predict with mask_input): the decoder's image stream of the
  * B * rep (image, prompt) pairs, image-major (pair i belongs to image i / rep), in one launch --
  *   keys[i] = emb[i / rep] + mask_downscaling(mask[i]) - no_mask_embed
