@@ -679,10 +679,19 @@ __device__ __forceinline__ void mfma_consts_init(char* smem, int tid) {
   }
 }
 
+// Clamp to +-448 that keeps a NaN.  v_med3_f32 returns min3 of its operands when one of them is a NaN, so the median alone turns a NaN in V into -448 and a finite
+// output where the 16-bit instances propagate it: the unordered compare puts the NaN back (two more VALU instructions per element; written
+// out because this file is built with -fno-honor-nans, under which the compiler folds any `x != x` it is shown).
+__device__ __forceinline__ float clamp448(float x) {
+  float r;
+  asm("v_med3_f32 %0, %1, %2, -%2\n\tv_cmp_u_f32 vcc, %1, %1\n\tv_cndmask_b32 %0, %0, %1, vcc" : "=&v"(r) : "v"(x), "s"(448.f) : "vcc");
+  return r;
+}
+
 // One 1-KiB piece of the e4m3 V^T operand image, assigned to DST: this lane's 16 bytes are V[key(jj)][d] for jj = 0..15 in the k order of
 // the P operand (the two k-steps of the 16-bit path), gathered by the same transposing reads PV16_STEP feeds its MFMAs with, from the 32
-// key rows ROW0 .. of the 16-bit image (vt = the lane's transposing-read base in it) and d tile T.  f32 clamp to +-448: the conversion
-// returns NaN, not the maximum, on overflow.
+// key rows ROW0 .. of the 16-bit image (vt = the lane's transposing-read base in it) and d tile T.  f32 clamp to +-448 (clamp448): the
+// conversion returns NaN, not the maximum, on overflow; +-Inf clamp like any other value, a NaN stays a NaN.
 // Reads vt; writes DST.
 #define V_IMAGE_PIECE(DST, ROW0, T)                                                                                                    \
   {                                                                                                                                    \
@@ -694,7 +703,7 @@ __device__ __forceinline__ void mfma_consts_init(char* smem, int tid) {
       const f16x4 l4 = __builtin_bit_cast(f16x4, lo), h4 = __builtin_bit_cast(f16x4, hi);                                              \
       float f[8];                                                                                                                      \
       _Pragma("unroll") for (int e = 0; e < 4; ++e) { f[e] = (float)l4[e]; f[4 + e] = (float)h4[e]; }                                  \
-      _Pragma("unroll") for (int e = 0; e < 8; ++e) f[e] = __builtin_amdgcn_fmed3f(f[e], -448.f, 448.f);                               \
+      _Pragma("unroll") for (int e = 0; e < 8; ++e) f[e] = clamp448(f[e]);                                                             \
       w[2 * sgrp] = pack4_e4m3(f[0], f[1], f[2], f[3]);                                                                                \
       w[2 * sgrp + 1] = pack4_e4m3(f[4], f[5], f[6], f[7]);                                                                            \
     }                                                                                                                                  \
@@ -840,13 +849,17 @@ enum { P16_SUM_MFMA,   // 16-bit pf; row sums from the matrix pipe (mfma_consts_
 // AV8 = true (cvmi_attn_desc.av_fp8, BASELINE configs[4] "fp8 MFMA attention"): the O^T += V^T P^T contraction -- whose K axis is the KEY axis,
 // a whole multiple of 64 here -- runs on the block-scaled fp8 MFMA (PV8_STEP, P from SOFTMAX_UPDATE72(P8_SUM_VALU)).  V is quantised ONCE per
 // workgroup: after the window has landed, every thread builds three 16-byte pieces of the e4m3 V^T operand image from the fp16 rows
-// (V_IMAGE_PIECE), a barrier, and the pieces overwrite the 16-bit V image in place.
+// (V_IMAGE_PIECE), a barrier, and the pieces overwrite the 16-bit V image in place (from its second KiB on: V8_OFF).
 // QL = true: row maximum through the matrix pipe (QL_UPDATE72), here without the accumulator rescale in the first tile.
 // The tile loop is the shared pieces in sequence; its redirects to the constants are selected per read (attn_dma72_kernel precomputes
 // bases: the two forms compile differently and each kernel keeps its own).
 template <int NW, bool AV8 = false, bool QL = false>
 __global__ __launch_bounds__(NW * 64, (AV8 || NW != 8) ? 2 : 4) void attn_res256_kernel(const AttnArgs p) {
   constexpr int NK = 256;
+  // AV8: the e4m3 V image starts one piece into the 16-bit image it replaces.  The fifth k-step of the LAST key row reads 16 bytes past the K
+  // image, i.e. V's first 16 bytes, against zero Q columns: they must stay finite 16-bit data.  Two e4m3 bytes of |v| >= 384 (0x7C..0x7E) read
+  // as one fp16 value are a NaN, and NaN x 0 made every score of that key, and with it the whole (batch, head) item, NaN.
+  constexpr int V8_OFF = 1024;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* const Ks = smem;
   char* const Vs = smem + NK * ROW72;
@@ -893,6 +906,7 @@ __global__ __launch_bounds__(NW * 64, (AV8 || NW != 8) ? 2 : 4) void attn_res256
 
   if constexpr (AV8) {
     static_assert(NW == 8, "the e4m3 V image is built by 8 waves x 3 pieces");
+    static_assert(V8_OFF >= 16 && V8_OFF % 1024 == 0 && V8_OFF + 24 * 1024 <= NK * ROW72, "the e4m3 V image stays inside the 16-bit one, clear of its first 16 bytes");
     // piece pc = wv + 8 i of 24: (key tile kt, d tile t, operand half u) = (pc / 6, (pc % 6) / 2, pc % 2); this lane's 16 bytes are
     // V[key(u, jj)][32 t + lr] for jj = 0..15 in the k order of the P operand (the two k-steps s = jj >> 3 of the 16-bit path)
     u32x4 piece[3];
@@ -903,7 +917,7 @@ __global__ __launch_bounds__(NW * 64, (AV8 || NW != 8) ? 2 : 4) void attn_res256
     }
     __syncthreads();                                        // every transposing read of the 16-bit V image is done ...
 #pragma unroll
-    for (int i = 0; i < 3; ++i) *reinterpret_cast<u32x4*>(Vs + (wv + 8 * i) * 1024 + lane * 16) = piece[i];
+    for (int i = 0; i < 3; ++i) *reinterpret_cast<u32x4*>(Vs + V8_OFF + (wv + 8 * i) * 1024 + lane * 16) = piece[i];
     __syncthreads();                                        // ... before the e4m3 image replaces it
   }
 
@@ -920,7 +934,7 @@ __global__ __launch_bounds__(NW * 64, (AV8 || NW != 8) ? 2 : 4) void attn_res256
       SOFTMAX_UPDATE72((AV8 ? P8_SUM_VALU : P16_SUM_MFMA))
     }
     if constexpr (AV8) {
-      PV8_STEP(Vs + kc * 6 * 1024 + lane * 16)
+      PV8_STEP(Vs + V8_OFF + kc * 6 * 1024 + lane * 16)
     } else {
       PV16_STEP((t == 2 && ones_lane) ? smem + ONES + (lh ? 32 : 144) + (u * 32 + s * 16) * ROW72     /* (the lanes of d = 72..75: the row-sum constants, selected per read) */
                                       : vt + (kc * 64 + u * 32 + s * 16) * ROW72 + t * 64)

@@ -1,6 +1,6 @@
 """Case tables shared by the per-op GPU suites and the CPU coverage guard (tests/test_op_coverage_cpu.py).
 
-ATTN_ROWS: the attention dispatch matrix.  One row = one shape and layout of cvmi_attention and the kernel that cvmi_last_kernel() must name
+ATTN_ROWS / ATTN_FP8_ROWS / ATTN_FP8_FALLBACK_ROWS: the attention dispatch matrix.  One row = one shape and layout of cvmi_attention and the kernel that cvmi_last_kernel() must name
 after the launch (attention.hip, cvmi_attention: the dispatcher with default settings).  Kernel names do not carry the operand type, so one
 expected name serves fp16 and bf16.
 
@@ -48,20 +48,20 @@ Plain data: importing this module needs neither a GPU nor the library."""
 F16_BF16 = ("f16", "bf16")
 
 
-def _row(rid, expect, B, heads, Nq, Nk, dqk, dv, dtypes=F16_BF16, layout="sep", o_pad=0, q_log2=0, note=""):
+def _row(rid, expect, B, heads, Nq, Nk, dqk, dv, dtypes=F16_BF16, layout="sep", o_pad=0, q_log2=0, av_fp8=0, note=""):
     """Global (non-window) attention.  layout: "sep" = q, k, v in three [B, N, heads * d] buffers; "qkv" = one fused [B, N, (2 dqk + dv) heads]
     buffer (needs Nq == Nk); "kv256" = the decoder's K and V halves of one [B, Nk, heads * (dqk + dv)] buffer.  o_pad > 0: the output sits at
-    column o_pad of a buffer o_pad columns wider on both sides."""
+    column o_pad of a buffer o_pad columns wider on both sides.  av_fp8: cvmi_attn_desc.av_fp8 as the launch sets it."""
     return dict(id=rid, expect=expect, B=B, heads=heads, Nq=Nq, Nk=Nk, dqk=dqk, dv=dv, dtypes=dtypes, layout=layout, o_pad=o_pad,
-                q_log2=q_log2, win=0, note=note)
+                q_log2=q_log2, av_fp8=av_fp8, win=0, note=note)
 
 
-def _win(rid, expect, imgs, gh, gw, heads, win, q_pool=0, dtypes=F16_BF16, o_pad=0, q_log2=0, note=""):
+def _win(rid, expect, imgs, gh, gw, heads, win, q_pool=0, dtypes=F16_BF16, o_pad=0, q_log2=0, av_fp8=0, note=""):
     """Hiera window attention straight off a fused NHWC [imgs, gh, gw, 3 C] q/k/v grid (k_st = 3 C), head_dim 72, optional 2 x 2 q max-pool."""
     nwin = imgs * (gh // win) * (gw // win)
     Nq = (win // 2) ** 2 if q_pool else win * win
     return dict(id=rid, expect=expect, B=nwin, heads=heads, Nq=Nq, Nk=win * win, dqk=72, dv=72, dtypes=dtypes, layout="grid", o_pad=o_pad,
-                q_log2=q_log2, win=win, imgs=imgs, gh=gh, gw=gw, q_pool=q_pool, note=note)
+                q_log2=q_log2, av_fp8=av_fp8, win=win, imgs=imgs, gh=gh, gw=gw, q_pool=q_pool, note=note)
 
 
 ATTN_ROWS = [
@@ -126,6 +126,53 @@ ATTN_ROWS = [
     _row("f32_general", "attn_f32_kernel", 2, 2, 130, 257, 72, 72, dtypes=("f32",), o_pad=8),
     _win("f32_win8", "attn_f32_kernel", 2, 16, 24, 2, 8, dtypes=("f32",)),
 ]
+
+# The e4m3 AV-product instances (cvmi_attn_desc.av_fp8 = 1): attn_res256_kernel<8, true, false> and attn_dma72_kernel<8, true, false>, f16 and
+# bf16, head dim 72, at the smallest shape at which each edge of their index arithmetic exists.  q_log2 = 1 beside av_fp8 = 1 is what
+# sam2.py:_attn_desc sets in production: the dispatcher gives fp8 precedence, the tag stays <8, true, false> and the kernel runs with scale = ln 2.
+# Operands, the float64 emulation, its derived bound and the mutants live in tests/attn_fp8_ref.py.
+RES256_FP8, DMA72_FP8 = "attn_res256_kernel<8, true, false>", "attn_dma72_kernel<8, true, false>"
+ATTN_FP8_ROWS = [
+    # ---- 256 keys, >= 8 query tiles: all 8 waves build the e4m3 V image, whether their query tile is live or not
+    _win("win16_fp8", RES256_FP8, 2, 16, 32, 2, 16, av_fp8=1),
+    _win("win16_fp8_opad", RES256_FP8, 2, 16, 32, 2, 16, o_pad=8, av_fp8=1),
+    _row("g256_fp8", RES256_FP8, 2, 2, 256, 256, 72, 72, layout="qkv", av_fp8=1),
+    _row("g256_nq225_fp8", RES256_FP8, 1, 3, 225, 256, 72, 72, av_fp8=1, note="one valid row in the 8th q tile"),
+    _row("g256_nq257_fp8", RES256_FP8, 1, 3, 257, 256, 72, 72, av_fp8=1, note="9 q tiles: a second query group, one live wave holding one valid row"),
+    _row("g256_nq512_fp8", RES256_FP8, 1, 1, 512, 256, 72, 72, av_fp8=1, note="two full query groups on a single item: grid of 2"),
+    _win("win16_fp8_qlog2", RES256_FP8, 2, 16, 32, 2, 16, q_log2=1, av_fp8=1),
+    _row("g256_nq257_fp8_qlog2", RES256_FP8, 1, 3, 257, 256, 72, 72, q_log2=1, av_fp8=1),
+    # ---- >= 512 keys in whole 64-key tiles
+    _row("dma72_fp8_256x512", DMA72_FP8, 1, 2, 256, 512, 72, 72, av_fp8=1, note="fewest keys, fewest q tiles"),
+    _row("dma72_fp8_nq543", DMA72_FP8, 1, 2, 543, 512, 72, 72, av_fp8=1, note="ragged last q tile"),
+    _row("dma72_fp8_nq577", DMA72_FP8, 1, 2, 577, 576, 72, 72, o_pad=8, av_fp8=1, note="9 key tiles (odd): the last tile sits in buffer 0"),
+    _row("dma72_fp8_600x640", DMA72_FP8, 2, 3, 600, 640, 72, 72, av_fp8=1, note="Nq != Nk, 6 items"),
+    _row("dma72_fp8_1024", DMA72_FP8, 1, 2, 1024, 1024, 72, 72, layout="qkv", av_fp8=1),
+    _row("dma72_fp8_600x640_qlog2", DMA72_FP8, 2, 3, 600, 640, 72, 72, q_log2=1, av_fp8=1),
+    _row("dma72_fp8_1024_qlog2", DMA72_FP8, 1, 2, 1024, 1024, 72, 72, layout="qkv", q_log2=1, av_fp8=1),
+]
+# av_fp8 = 1 where the dispatcher drops it: the tag is the 16-bit instance, the result holds the 16-bit bound of the matrix and is bit-identical
+# to the same launch with av_fp8 = 0.
+ATTN_FP8_FALLBACK_ROWS = [
+    _win("win16_pool_fp8", "attn_res256_kernel<4, false, false>", 2, 16, 32, 2, 16, q_pool=1, o_pad=8, av_fp8=1, note="2 q tiles"),
+    _win("win16_pool_fp8_qlog2", "attn_res256_kernel<4, false, true>", 2, 16, 32, 2, 16, q_pool=1, q_log2=1, av_fp8=1),
+    _row("g256_nq223_fp8", "attn_res256_kernel<4, false, false>", 1, 3, 223, 256, 72, 72, o_pad=8, av_fp8=1, note="7 q tiles"),
+    _win("win8_fp8", "attn_res64_kernel<2>", 2, 16, 24, 2, 8, av_fp8=1),
+    _row("g600_fp8", "attn64_kernel<96, 96, 8>", 2, 3, 600, 600, 72, 72, av_fp8=1, note="Nk % 64 != 0"),
+    _win("win4_fp8", "attn_win16_kernel<16, 9>", 2, 8, 12, 3, 4, o_pad=8, av_fp8=1),
+]
+
+# mutant of tests/attn_fp8_ref.py -> (row id, operand kind, dtype) cases of which at least one must put it outside the derived bound
+# (tests/test_attn_fp8_ref_cpu.py)
+FP8_MUTANT_CASES = {
+    "l_of_quantised_p": [("g256_nq225_fp8", "random", "f16"), ("dma72_fp8_256x512", "random", "f16")],
+    "p_scale_2^7": [("g256_nq225_fp8", "exact", "f16"), ("dma72_fp8_256x512", "exact", "f16")],
+    "p_truncated": [("g256_nq225_fp8", "random", "f16"), ("dma72_fp8_256x512", "random", "bf16")],
+    "v_unclamped_saturates": [("g256_nq225_fp8", "random", "f16"), ("dma72_fp8_256x512", "random", "bf16")],
+    "key_halves_swapped": [("g256_nq225_fp8", "random", "bf16"), ("dma72_fp8_256x512", "exact", "f16")],
+    "d_tiles_swapped": [("g256_nq225_fp8", "exact", "bf16"), ("dma72_fp8_256x512", "random", "f16")],
+    "tile_32": [("g256_nq225_fp8", "random", "f16"), ("dma72_fp8_256x512", "random", "f16")],
+}
 
 # Batch sharing (cvmi_attn_desc.q_bdiv / kv_bdiv) at the mask decoder's layer-0 shapes: B = images x NP (image, prompt) pairs.
 # (mode, images, NP, heads, Nq, Nk, d, expected kernel)

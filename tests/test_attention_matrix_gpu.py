@@ -128,7 +128,7 @@ def _setup_global(row, dtype, q, k, v, scale):
     od = torch.full((B, Nq, o_ld), SENTINEL, dtype=td, device="cuda")
     desc = _desc(q=qp, k=kp, v=vp, o=od.data_ptr() + o_pad * od.element_size(),
                  q_sb=Nq * q_st, q_sh=dqk, q_st=q_st, k_sb=Nk * k_st, k_sh=dqk, k_st=k_st, v_sb=Nk * v_st, v_sh=dv, v_st=v_st,
-                 o_sb=Nq * o_ld, o_sh=dv, o_st=o_ld, B=B, heads=H, Nq=Nq, Nk=Nk, dqk=dqk, dv=dv, scale=scale, dtype=dtype, q_log2=row["q_log2"])
+                 o_sb=Nq * o_ld, o_sh=dv, o_st=o_ld, B=B, heads=H, Nq=Nq, Nk=Nk, dqk=dqk, dv=dv, scale=scale, dtype=dtype, q_log2=row["q_log2"], av_fp8=row["av_fp8"])
     get = lambda: od[..., o_pad:o_pad + Cv].float().cpu().view(B, Nq, H, dv).permute(0, 2, 1, 3)
     return desc, keep, od, get
 
@@ -156,7 +156,7 @@ def _setup_window(row, dtype, qf, k, v, scale):
     desc = _desc(q=qkv.data_ptr(), k=qkv.data_ptr() + C_ * es, v=qkv.data_ptr() + 2 * C_ * es, o=od.data_ptr() + o_pad * es,
                  q_sb=0, q_sh=hd, q_st=3 * C_, k_sb=0, k_sh=hd, k_st=3 * C_, v_sb=0, v_sh=hd, v_st=3 * C_, o_sb=0, o_sh=hd, o_st=o_ld,
                  B=row["B"], heads=H, Nq=row["Nq"], Nk=row["Nk"], dqk=hd, dv=hd, scale=scale, dtype=dtype, win=win, grid_h=gh, grid_w=gw,
-                 q_pool=qp_, q_log2=row["q_log2"])
+                 q_pool=qp_, q_log2=row["q_log2"], av_fp8=row["av_fp8"])
 
     def get():
         o = od[..., o_pad:o_pad + C_].float().cpu().view(imgs, ogh // ow, ow, ogw // ow, ow, H, hd)

@@ -1,5 +1,6 @@
 """CPU guard on the per-op GPU coverage (tests/op_matrix.py): every dual-built entry point has a bf16 test, every attention kernel family the
-dispatcher can launch has a row in the dispatch matrix, and so has every kernel family and template instance of cvmi_conv2d's dispatcher
+dispatcher can launch has a row in the dispatch matrix, every template instance of its two head-dim-72 launchers (launch_res256, launch_dma72:
+the e4m3 AV-product instances among them, ATTN_FP8_ROWS) is some row's expected tag, and so has every kernel family and template instance of cvmi_conv2d's dispatcher
 (CONV_ROWS), every built instance of the three fused YOLO11 kernels (FUSED_ROWS), and every layernorm_kernel instance, SPPF kernel and
 refinement kernel of the helper dispatchers (LN_ROWS, HELPER_ROWS), every branch combination and edge of the detector's tail (NMS_ROWS,
 DECODE_ROWS), and every instance of the token-stationary kernels with the chunk counts,
@@ -12,7 +13,7 @@ import glob
 import os
 import re
 
-from op_matrix import (ATTN_ROWS, BF16_OPS, C3K2_INSTANCES, CONV_ROWS, DECODE_NC_MAX, DECODE_REFUSED, DECODE_ROWS, FUSED_MUTANT_ROWS, NMS_A_EDGES, NMS_CAND_BYTES,
+from op_matrix import (ATTN_FP8_FALLBACK_ROWS, ATTN_FP8_ROWS, ATTN_ROWS, BF16_OPS, C3K2_INSTANCES, CONV_ROWS, DECODE_NC_MAX, DECODE_REFUSED, DECODE_ROWS, FUSED_MUTANT_ROWS, NMS_A_EDGES, NMS_CAND_BYTES,
                        NMS_KINDS, NMS_LDS_A, NMS_MAX_A, NMS_MAX_DET, NMS_MAX_NMS, NMS_N_EDGES, NMS_NTHR_N, NMS_REFUSED, NMS_ROWS, NMS_WS_RECORD, decode_tag, nms_pick,
                        nms_tag, nms_workspace, FUSED_ROWS, HELPER_ROWS, LN_DUAL_ROWS, LN_FORMS, LN_NCAND, LN_ROWS,
                        MLP_INSTANCES, MLP_ROWS, SHARE_ROWS, SPPF_LDS_PIXELS, TNAME, TOK_FORMAT, TOK_INSTANCES, TOK_KS, TOK_MUTANT_ROWS, TOK_NCH, TOK_NCH_FAMILIES,
@@ -99,10 +100,73 @@ def test_every_attention_kernel_family_is_in_the_dispatch_matrix():
     assert covered <= fams, f"op_matrix.ATTN_ROWS expects kernels attention.hip no longer launches: {sorted(covered - fams)}"
 
 
+ATTN_ALL_ROWS = ATTN_ROWS + ATTN_FP8_ROWS + ATTN_FP8_FALLBACK_ROWS
+ATTN_LAUNCHERS = {"launch_res256": "attn_res256_kernel<%d, %s, %s>", "launch_dma72": "attn_dma72_kernel<%d, %s, %s>"}     # launcher -> its cvmi_note_kernel format
+
+
+def attention_source(csrc=CSRC):
+    return open(os.path.join(csrc, "attention.hip")).read()
+
+
+def attention_instances(text):
+    """Template instances of the two head-dim-72 launchers cvmi_attention can pick, from its call sites launch_res256<NW[, AV8[, QL]]>( and
+    launch_dma72<..>(, each spelled the way the launcher's cvmi_note_kernel format spells it (AV8 and QL default to false)."""
+    out = set()
+    for fn, args in re.findall(r"\b(launch_res256|launch_dma72)<([^<>]*)>\(", text):
+        a = [x.strip() for x in args.split(",")]
+        assert 1 <= len(a) <= 3 and a[0].isdigit() and all(x in ("true", "false") for x in a[1:]), (fn, args)
+        a += ["false"] * (3 - len(a))
+        out.add(ATTN_LAUNCHERS[fn] % (int(a[0]), a[1], a[2]))
+    return out
+
+
+def attention_gaps(text, rows=None):
+    """What the attention matrix leaves uncovered among the instances of launch_res256 / launch_dma72, as a list of strings (empty = complete)."""
+    rows = ATTN_ALL_ROWS if rows is None else rows
+    gaps = [f"attention.hip no longer tags {fmt!r}" for fmt in ATTN_LAUNCHERS.values() if f'cvmi_note_kernel("{fmt}"' not in text]
+    inst, tags = attention_instances(text), {r["expect"] for r in rows}
+    fams = {re.match(r"\s*(\w+)", f).group(1) for f in re.findall(r'cvmi_note_kernel\(\s*"([^"]*)"', text)}
+    gaps += [f"{i} has no row" for i in sorted(inst - tags)]
+    for r in rows:
+        fam = re.match(r"(\w+)", r["expect"]).group(1)
+        if fam in ("attn_res256_kernel", "attn_dma72_kernel"):
+            if r["expect"] not in inst:
+                gaps.append(f"row {r['id']} expects {r['expect']}, which the dispatcher cannot produce")
+        elif r["av_fp8"] and fam not in fams:
+            gaps.append(f"row {r['id']} expects {r['expect']}, which attention.hip no longer tags")
+    for i in sorted(inst):                                                 # an e4m3 instance is reachable with av_fp8 = 1 only: pinned by such a row
+        if _tag_args(i)[1][1] == "true" and not any(r["expect"] == i and r["av_fp8"] for r in rows):
+            gaps.append(f"{i} has no av_fp8 = 1 row")
+    return gaps
+
+
+def test_every_res256_and_dma72_instance_is_in_the_dispatch_matrix():
+    text = attention_source()
+    inst = attention_instances(text)
+    assert len(inst) == 8 and {"attn_res256_kernel<8, true, false>", "attn_dma72_kernel<8, true, false>"} <= inst, sorted(inst)      # the parser still finds the call sites
+    assert attention_gaps(text) == [], attention_gaps(text)
+
+
+def test_a_dropped_fp8_row_or_a_new_attention_call_site_is_caught():
+    text = attention_source()
+    assert attention_gaps(text, ATTN_ROWS + ATTN_FP8_FALLBACK_ROWS) == [
+        "attn_dma72_kernel<8, true, false> has no row", "attn_res256_kernel<8, true, false> has no row",
+        "attn_dma72_kernel<8, true, false> has no av_fp8 = 1 row", "attn_res256_kernel<8, true, false> has no av_fp8 = 1 row"]
+    assert attention_gaps(text, [r for r in ATTN_ALL_ROWS if not r["id"].startswith("dma72_fp8")]) == [
+        "attn_dma72_kernel<8, true, false> has no row", "attn_dma72_kernel<8, true, false> has no av_fp8 = 1 row"]
+    probe = text + "\n    if (d->av_fp8 && a.qtiles < 8) return launch_res256<4, true>(a, stream);\n"
+    assert attention_gaps(probe) == ["attn_res256_kernel<4, true, false> has no row", "attn_res256_kernel<4, true, false> has no av_fp8 = 1 row"]
+    probe = text.replace("return launch_dma72<8, true>(a, stream);", "return launch_dma72<8>(a, stream);")
+    assert [g for g in attention_gaps(probe) if g.startswith("row dma72_fp8_1024 ")] == ["row dma72_fp8_1024 expects attn_dma72_kernel<8, true, false>, which the dispatcher cannot produce"]
+    probe = text.replace('cvmi_note_kernel("attn_dma72_kernel<%d, %s, %s>"', 'cvmi_note_kernel("attn_dma72_kernel<%d>"')
+    assert "attention.hip no longer tags 'attn_dma72_kernel<%d, %s, %s>'" in attention_gaps(probe)
+
+
 def test_matrix_rows_are_well_formed():
-    ids = [r["id"] for r in ATTN_ROWS]
+    ids = [r["id"] for r in ATTN_ALL_ROWS]
     assert len(ids) == len(set(ids)), "duplicate row ids"
-    for r in ATTN_ROWS:
+    assert not any(r["av_fp8"] for r in ATTN_ROWS) and all(r["av_fp8"] == 1 for r in ATTN_FP8_ROWS + ATTN_FP8_FALLBACK_ROWS)
+    for r in ATTN_ALL_ROWS:
         assert set(r["dtypes"]) <= {"f16", "bf16", "f32"} and r["dtypes"], r["id"]
         assert r["layout"] in ("sep", "qkv", "kv256", "grid"), r["id"]
         assert r["layout"] != "qkv" or r["Nq"] == r["Nk"], r["id"]
@@ -110,6 +174,17 @@ def test_matrix_rows_are_well_formed():
             assert r["gh"] % r["win"] == 0 and r["gw"] % r["win"] == 0 and r["Nk"] == r["win"] ** 2, r["id"]
         if r["dtypes"] != ("f32",):
             assert r["dqk"] % 8 == 0 and r["dv"] % 8 == 0 and r["o_pad"] % 8 == 0, r["id"]      # the 16-bit kernels' alignment contract
+        if r["av_fp8"]:
+            assert set(r["dtypes"]) <= {"f16", "bf16"}, f"{r['id']}: an fp8 row is 16-bit"
+            args = _tag_args(r["expect"])[1]
+            if len(args) == 3 and args[1] == "true":                                            # what the dispatcher sends to an e4m3 instance
+                assert r["dqk"] == 72 and r["dv"] == 72 and (r["Nk"] == 256 or (r["Nk"] >= 512 and r["Nk"] % 64 == 0 and not r["win"])), r["id"]
+                assert (r["Nq"] + 31) // 32 >= 8, f"{r['id']}: fewer than 8 query tiles"
+                assert r in ATTN_FP8_ROWS, r["id"]
+            else:
+                assert r in ATTN_FP8_FALLBACK_ROWS, r["id"]
+    for r in ATTN_FP8_ROWS:
+        assert _tag_args(r["expect"])[1][1:] == ["true", "false"] and not r.get("q_pool"), r["id"]
 
 
 CONV_SOURCES = ("igemm.hip", "conv_tile.hip")

@@ -15,6 +15,7 @@ from circuitvision_amd import _lib
 from circuitvision_amd._lib import ACT_GELU, ACT_NONE, ACT_RELU, ACT_SILU, BF16, F16, F32
 from circuitvision_amd.engine import (Buf, PackedConv, PackedDW, Plan, make_attn_desc, op_attention, op_conv, op_dwconv,
                                       op_sppf_pool)
+from attn_fp8_ref import _fp8_av_emulation          # the float32 statement of cvmi_attn_desc.av_fp8's arithmetic (beside its float64 form and bound)
 from helpers import TOL, from_view, quant, run, stream, to_buf
 
 pytestmark = pytest.mark.gpu
@@ -367,27 +368,6 @@ def test_attention_window_mode(dtype, q_pool, win):
     run(plan)
     tol = dict(rtol=1e-2, atol=5e-3) if dtype == F16 else dict(rtol=1e-4, atol=1e-5)
     torch.testing.assert_close(od.float().cpu(), ref, **tol)
-
-
-def _fp8_av_emulation(q, k, v, scale, tile=64):
-    """The arithmetic cvmi_attn_desc.av_fp8 states, tile by tile as the kernels run it: per 64-key tile the running row maximum m, P = e4m3(exp(s - m)
-    * 2^8) / 2^8, V = e4m3(clamp(v, +-448)), O <- O * exp(m_old - m) + P V in fp32, row sums of the UNquantised p.  [.., Nq, d] x [.., Nk, d]."""
-    f8 = lambda t: t.to(torch.float8_e4m3fn).float()
-    s = (q @ k.transpose(-1, -2)) * scale
-    Nk = k.shape[-2]
-    m = torch.full(s.shape[:-1] + (1,), float("-inf"))
-    o = torch.zeros(q.shape[:-1] + (v.shape[-1],))
-    l = torch.zeros_like(m)
-    v8 = f8(v.clamp(-448, 448))
-    for k0 in range(0, Nk, tile):
-        st = s[..., k0:k0 + tile]
-        m_new = torch.maximum(m, st.amax(-1, keepdim=True))
-        alpha = torch.exp(m - m_new)
-        pt = torch.exp(st - m_new)
-        o = o * alpha + (f8(pt * 256.0) / 256.0) @ v8[..., k0:k0 + tile, :]
-        l = l * alpha + pt.sum(-1, keepdim=True)
-        m = m_new
-    return o / l
 
 
 def _check_fp8_av(name, got8, got16, ref, emu, dtype, absref):
