@@ -348,7 +348,10 @@ __device__ __forceinline__ void mlp_chunk_loop(const MlpWave<C, VAR>& w, u32x4 (
 // ---- epilogue: x += y + b2; lane (token lr, half lh) owns channels 32 t + 8 g + 4 lh .. + 3.
 // PROJ (proj_mlp.hpp): yacc also holds the attention projection's product and bp its bias: x += yacc + (bp + b2), in that association.
 // stats_out: the updated row's LayerNorm statistics (mean, 1 / sqrt(var + stats_eps)) for the launch that normalises it next (the next
-// block's norm1): shifted sums (tok_stream.hpp) over this lane's half of the row, the shift being the row's first updated value.
+// block's norm1), in two passes over this lane's half of the row.  The first sums the updated values' distances from the row's first updated
+// value (the mean keeps its accuracy however far the row lies from zero) and leaves each distance in the accumulator register it came from; the
+// second sums the squared deviations from the mean.  A single pass that shifts by one of the row's values cancels when that value is an
+// outlier: channel 0 at 40 among 288 channels of spread 1.5 makes (mean - shift)^2 two hundred times the variance it is subtracted from.
 template <int C, int VAR, bool PROJ>
 __device__ __forceinline__ void mlp_epilogue(const MlpWave<C, VAR>& w, float* xr, f32x16 (&yacc)[MlpCfg<C, VAR>::NT], const float* __restrict__ b2,
                                              const float* __restrict__ bp, float* __restrict__ stats_out, float stats_eps) {
@@ -356,10 +359,10 @@ __device__ __forceinline__ void mlp_epilogue(const MlpWave<C, VAR>& w, float* xr
   const int lr = w.lr, lh = w.lh;
   const bool row_ok = w.row_ok;
   const long long row_raw = w.row_raw;
-  ShiftedSums st;
+  float shift = 0.f, s = 0.f;
   if (stats_out) {
     const float o0 = row_ok ? xr[0] + (yacc[0][0] + (PROJ ? bp[0] + b2[0] : b2[0])) : 0.f;       // (the value the lane of half 0 stores at channel 0)
-    st.shift = __shfl(o0, lr);
+    shift = __shfl(o0, lr);
   }
   if (row_ok) {
 #pragma unroll
@@ -374,13 +377,28 @@ __device__ __forceinline__ void mlp_epilogue(const MlpWave<C, VAR>& w, float* xr
 #pragma unroll
           for (int e = 0; e < 4; ++e) o[e] += yacc[t][4 * g + e] + bb[e];
           *reinterpret_cast<f32x4*>(xr + c0) = o;
-          if (stats_out) st.add(o);
+          if (stats_out) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { const float dv = o[e] - shift; yacc[t][4 * g + e] = dv; s += dv; }
+          }
         }
       }
   }
   if (stats_out) {
-    const float2 mr = shifted_mean_rstd(st.shift, row_sum<2>(st.s), row_sum<2>(st.q), (float)C, stats_eps);
-    if (row_ok && lh == 0) *reinterpret_cast<float2*>(stats_out + 2 * row_raw) = mr;
+    const float dm = row_sum<2>(s) / (float)C;                   // mean - shift
+    float q = 0.f;
+    if (row_ok) {
+#pragma unroll
+      for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+          if (32 * t + 8 * g + 4 * lh < C) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { const float d = yacc[t][4 * g + e] - dm; q = fmaf(d, d, q); }
+          }
+    }
+    const float var = row_sum<2>(q) / (float)C;
+    if (row_ok && lh == 0) *reinterpret_cast<float2*>(stats_out + 2 * row_raw) = make_float2(shift + dm, 1.0f / sqrtf(var + stats_eps));
   }
 }
 

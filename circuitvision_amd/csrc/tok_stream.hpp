@@ -46,7 +46,8 @@ template <int LPR> __device__ __forceinline__ float row_sum(float x) {
 }
 
 // Single-pass sums of (v - shift) and (v - shift)^2 over the values a lane holds.  The shift is one of the row's own values: what cancels in
-// the variance is then (mean - shift)^2, bounded by the row's own spread, and the single-pass formula stays well conditioned.
+// the variance is then (mean - shift)^2, bounded by the row's own spread, and the single-pass formula stays well conditioned -- unless the
+// shift is the row's one outlier: (mean - shift)^2 is then up to n times the variance (hiera_mlp.hip's epilogue takes two passes for that).
 struct ShiftedSums {
   float shift = 0.f, s = 0.f, q = 0.f;
   __device__ __forceinline__ void add(const f32x4& v) {

@@ -27,6 +27,9 @@ tests/tok_ref.py.  tl16_splits is compared with the library's own answer (cvmi_t
 its N % 32 != 0 branch is checked by reading only: the library exports the split count through that entry point alone, which always asks for the
 statistics-out form, where a ragged N never splits; the split count is not in the tag.
 
+PROJ_ROWS / MLP_KIND_ROWS: the proj + MLP launch (proj_mlp.hpp) at every row count of MLP_ROW_COUNTS, and one launch per proj_mlp / hiera_mlp
+instance whose LayerNorm input carries the five row kinds (KIND_BLOCKS); proj_pick mirrors proj_mlp_dispatch.
+
 NMS_ROWS / DECODE_ROWS: the detector's tail (nms.hip, vision_ops.hip cvmi_detect_decode).  One NMS row = one input with an exact candidate count, the
 instance nms_launch must tag and the decisions nms_pick -- a mirror of nms_launch and of yolo_nms_kernel's data-dependent branches -- derives from it; one
 decode row = one launch per dtype with its stated seams.  Generators, references, mutants and the decode bound live in tests/detect_ref.py.
@@ -815,6 +818,38 @@ def _mlp(C, pipe, rows, stats_out=True, x_ld=None):
 MLP_ROWS = [_mlp(C, pipe, rows) for C, pipe in ((144, None), (288, None), (288, "0")) for rows in MLP_ROW_COUNTS] + \
            [_mlp(C, pipe, rows, stats_out=False) for C, pipe in ((144, None), (288, None), (288, "0")) for rows in (129, 391)] + \
            [_mlp(C, pipe, 391, x_ld=C) for C, pipe in ((144, None), (288, None), (288, "0"))]
+# One 391-row launch per instance whose LayerNorm input carries the row kinds of tok_ref.mlp_operands (rows 500 away from zero, a ramp along C,
+# a spread of 1e-3, an outlier in channel 0 -- the hand-over's shift -- and in the last channel, the rest plain).  Kept beside MLP_ROWS, whose
+# operands and measured constant they do not touch.
+MLP_KIND_ROWS = [dict(_mlp(C, pipe, 391), id="mlp_c%d_v%s_rows391_kinds" % (C, mlp_pick(C, pipe)[-2]), kinds=True) for C, pipe in ((144, None), (288, None), (288, "0"))]
+KIND_ROWS = 32                                                              # rows per kind: one wave's token tile
+KIND_BLOCKS = ("far500", "ramp", "spread1e-3", "outlier_c0", "outlier_last")  # rows [32 i, 32 i + 32) of a `kinds` launch
+
+
+# ---- the proj + MLP launch: proj_mlp.hpp, the proj form of cvmi_hiera_mlp_stats ---------------------------------------------------------------------
+# PROJ_ROWS: one row = one launch of op_hiera_mlp(.., proj=..) and the instance proj_mlp_dispatch must tag.  x has a row stride of C + 4, ao of
+# C + 8, both with NaN padding (the `tight` rows: C and C).  Operands, the reference, its mutants and the bound live in tests/tok_ref.py.
+def proj_pick(C):
+    """proj_mlp.hpp proj_mlp_dispatch: C = 144 runs the chunk-order loop (VAR 1), C = 288 the pipelined one (VAR 2)."""
+    assert C in (144, 288), C
+    return "proj_mlp_kernel<%d, %d>" % (C, 1 if C == 144 else 2)
+
+
+PROJ_INSTANCES = sorted({proj_pick(144), proj_pick(288)})
+PROJ_TODAY = ((144, 5), (144, 1000), (144, 128 * 3 + 37), (288, 5), (288, 777))   # the (C, rows) of tests/proj_mlp_cases.py before the matrix
+
+
+def _proj(C, rows, stats_out=True, tight=False, kinds=False):
+    x_ld, ao_ld = (C, C) if tight else (C + 4, C + 8)
+    rid = "proj_c%d_rows%d_ld%d%s%s" % (C, rows, x_ld, "" if stats_out else "_nostats", "_kinds" if kinds else "")
+    return dict(id=rid, expect=proj_pick(C), C=C, rows=rows, x_ld=x_ld, ao_ld=ao_ld, stats_out=stats_out, kinds=kinds, proj=True, pipe=None, dtypes=F16_BF16)
+
+
+PROJ_ROWS = [_proj(C, rows) for C in (144, 288) for rows in MLP_ROW_COUNTS] + \
+            [_proj(C, rows) for C, rows in PROJ_TODAY if rows not in MLP_ROW_COUNTS] + \
+            [_proj(C, rows, stats_out=False) for C in (144, 288) for rows in (129, 391)] + \
+            [_proj(C, 391, tight=True) for C in (144, 288)] + \
+            [_proj(C, 391, kinds=True) for C in (144, 288)]
 
 
 def _tok_ids(pred):
@@ -850,6 +885,25 @@ TOK_MUTANT_DTYPES = {"ln_var_n_minus_1": ("f16",)}
 # mlp_hidden_not_rounded is MORE accurate than the contract by the rounding noise of 4 C hidden values, 0.09 (fp16) / 0.45 (bf16) of the MLP bound,
 # which is set by the GELU form's error.
 TOK_UNSEEN_MUTANTS = {"mlp_hidden_not_rounded": [r["id"] for r in MLP_ROWS if r["rows"] >= 127]}
+# mutants of tok_ref.proj_mlp_ref -> ids of the PROJ_ROWS that must catch each, in fp16 and bf16.  The last three live where their kind of row
+# is: raw moments cancel on rows 500 away from zero only, and x1 rounded to 16 bits is below the bound until x1 is large.
+_PROJ_ALL, _PROJ_KINDS = [r["id"] for r in PROJ_ROWS], [r["id"] for r in PROJ_ROWS if r["kinds"]]
+PROJ_MUTANT_ROWS = {
+    "proj_bias_twice": _PROJ_ALL,
+    "proj_bias_not_in_ln": _PROJ_ALL,
+    "ln_of_x_not_x1": _PROJ_ALL,
+    "residual_drops_proj": _PROJ_ALL,
+    "fc1_k_natural_order": _PROJ_ALL,
+    "proj_rows_past_end": [r["id"] for r in PROJ_ROWS if r["rows"] % 128 != 0],
+    "stats_of_x1": [r["id"] for r in PROJ_ROWS if r["stats_out"]],
+    "ln_var_raw_moments": _PROJ_KINDS,
+    "stats_unshifted": _PROJ_KINDS,
+    "x1_through_16_bits": _PROJ_KINDS,
+}
+# ... of tok_ref.hiera_mlp_ref on the MLP_KIND_ROWS
+MLP_KIND_MUTANT_ROWS = {"ln_var_raw_moments": [r["id"] for r in MLP_KIND_ROWS], "stats_unshifted": [r["id"] for r in MLP_KIND_ROWS]}
+# the mutants above that must show on the rows 500 away from zero (rows [0, KIND_ROWS) of a `kinds` launch)
+FAR500_MUTANTS = ("ln_var_raw_moments", "stats_unshifted")
 
 
 # ---- the detector's tail: vision_ops.hip cvmi_detect_decode, nms.hip cvmi_yolo_nms / cvmi_yolo_nms_best ---------------------------------------

@@ -13,4 +13,7 @@ QKV_ATTN16_ROWS = [
     dict(id="plain_4x64x4", grid=(4, 64, 4), K=288, heads=4, q_pool=0, expect="qkv_attn16_kernel<288, 4, false>"),
     dict(id="qpool_1x16x16", grid=(1, 16, 16), K=288, heads=8, q_pool=1, expect="qkv_attn16_kernel<288, 8, true>"),
     dict(id="qpool_2x16x24", grid=(2, 16, 24), K=288, heads=8, q_pool=1, expect="qkv_attn16_kernel<288, 8, true>"),
+    # kinds=1: the leading token rows carry the five LayerNorm row kinds of tests/tok_ref.py row_kinds, one per instance
+    dict(id="kinds_2x16x24", grid=(2, 16, 24), K=288, heads=4, q_pool=0, kinds=1, expect="qkv_attn16_kernel<288, 4, false>"),
+    dict(id="kinds_qpool_2x16x24", grid=(2, 16, 24), K=288, heads=8, q_pool=1, kinds=1, expect="qkv_attn16_kernel<288, 8, true>"),
 ]

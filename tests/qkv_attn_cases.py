@@ -11,4 +11,7 @@ QKV_ATTN_ROWS = [
     dict(id="plain_3x32x8", grid=(3, 32, 8), K=144, heads=2, q_pool=0, expect="qkv_attn64_kernel<144, 2, false>"),
     dict(id="qpool_1x16x16", grid=(1, 16, 16), K=144, heads=4, q_pool=1, expect="qkv_attn64_kernel<144, 4, true>"),
     dict(id="qpool_2x16x24", grid=(2, 16, 24), K=144, heads=4, q_pool=1, expect="qkv_attn64_kernel<144, 4, true>"),
+    # kinds=1: the leading token rows carry the five LayerNorm row kinds of tests/tok_ref.py row_kinds, one per instance
+    dict(id="kinds_2x16x24", grid=(2, 16, 24), K=144, heads=2, q_pool=0, kinds=1, expect="qkv_attn64_kernel<144, 2, false>"),
+    dict(id="kinds_qpool_2x16x24", grid=(2, 16, 24), K=144, heads=4, q_pool=1, kinds=1, expect="qkv_attn64_kernel<144, 4, true>"),
 ]

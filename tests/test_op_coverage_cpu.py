@@ -19,6 +19,7 @@ from op_matrix import (ATTN_FP8_FALLBACK_ROWS, ATTN_FP8_ROWS, ATTN_ROWS, BF16_OP
                        MLP_INSTANCES, MLP_ROWS, SHARE_ROWS, SPPF_LDS_PIXELS, TNAME, TOK_FORMAT, TOK_INSTANCES, TOK_KS, TOK_MUTANT_ROWS, TOK_NCH, TOK_NCH_FAMILIES,
                        TOK_PARTS, TOK_ROWS, TOK_SLOTS, TOK_SPLIT_TABLE, TOK_UNSEEN_MUTANTS, c3k2_max_wgs_per_cu, c3k2_tag, conv_expect, ln_pick, ln_reachable,
                        ln_tag, mlp_pick, tl16_splits, tok_dispatch, tok_nch_family, tok_pick)
+from op_matrix import KIND_BLOCKS, KIND_ROWS, MLP_KIND_ROWS, MLP_ROW_COUNTS, PROJ_INSTANCES, PROJ_ROWS, PROJ_TODAY, proj_pick
 from op_matrix import AA_MAXTAPS, MASK_ENTRY, RECT_MAX, RESAMPLE_GRID_CAP, RESAMPLE_ROWS, TRANSFORM_ENTRY
 from op_matrix import (BALLOT_LANES, CONTOUR_CAPACITY_ROW, CONTOUR_GRID_CAP, CONTOUR_ROWS, PLANE_MAX, PREPARE_ROWS, ROOT_ROWS_PER_BLOCK, TRACE_LANES, TRACE_LDS_MAX,
                        TRACE_LDS_OPTIN, contour_tag, plane_shape, trace_lds_bytes)
@@ -693,8 +694,89 @@ def test_token_path_rows_are_well_formed():
         assert rids and set(rids) <= set(ids), mut
 
 
+# ---- the proj + MLP launch: proj_mlp.hpp launch_proj_mlp / proj_mlp_dispatch ---------------------------------------------------------------------------
+PROJ_EDGES = (1, 31, 32, 33, 127, 128, 129)                                 # row counts around one wave's 32-token tile and the 128-row workgroup
+PROJ_TAG = 'cvmi_note_kernel("proj_mlp_kernel<%d, %d>", C, VAR);'
+
+
+def proj_source(csrc=CSRC):
+    return open(os.path.join(csrc, "proj_mlp.hpp")).read()
+
+
+def proj_instances(text):
+    """Tags of every instance proj_mlp.hpp can launch, from the call sites of launch_proj_mlp<C, VAR>."""
+    return ["proj_mlp_kernel<%s, %s>" % m for m in re.findall(r"return launch_proj_mlp<(\d+), (\d)>\(", text)]
+
+
+def proj_gaps(text, rows=PROJ_ROWS):
+    """What PROJ_ROWS leaves uncovered of the proj + MLP launch, as a list of strings (empty = complete)."""
+    gaps = [] if PROJ_TAG in text else ["proj_mlp.hpp no longer tags its launch as proj_mlp_kernel<%d, %d>"]
+    inst, tags = set(proj_instances(text)), {r["expect"] for r in rows}
+    gaps += [f"{t} has no row" for t in sorted(inst - tags)]
+    gaps += [f"rows expect {t}, which the sources no longer launch" for t in sorted(tags - inst)]
+    for t in sorted(inst & tags):
+        mine = [r for r in rows if r["expect"] == t]
+        plain = {r["rows"] for r in mine if r["stats_out"] and not r["kinds"] and r["x_ld"] > r["C"] and r["ao_ld"] > r["C"]}
+        gaps += [f"{t}: no padded statistics-out row with {n} rows" for n in PROJ_EDGES if n not in plain]
+        if not any(not r["stats_out"] for r in mine):
+            gaps.append(f"{t}: no row without statistics out")
+        if not any(r["x_ld"] == r["C"] and r["ao_ld"] == r["C"] for r in mine):
+            gaps.append(f"{t}: no row with tight strides")
+        if not any(r["kinds"] for r in mine):
+            gaps.append(f"{t}: no kinds row")
+    return gaps
+
+
+def test_every_proj_mlp_instance_is_in_the_matrix():
+    text = proj_source()
+    inst = proj_instances(text)
+    assert len(inst) == 2 and len(set(inst)) == 2, inst                     # the parser still finds the call sites
+    assert sorted(inst) == PROJ_INSTANCES == sorted({proj_pick(144), proj_pick(288)})
+    assert "if (C == 144) return launch_proj_mlp<144, 1>(" in text and "return launch_proj_mlp<288, 2>(" in text          # proj_pick's rule
+    assert proj_gaps(text) == [], proj_gaps(text)
+
+
+def test_a_new_proj_mlp_instance_or_a_removed_row_is_caught():
+    text = proj_source()
+    probe = text + "\n  return launch_proj_mlp<288, 0>(x, x_ld, pj, gamma, beta, eps, b2, rows, s, stats_out, stats_eps);\n"
+    assert proj_gaps(probe) == ["proj_mlp_kernel<288, 0> has no row"]
+    probe = text.replace("return launch_proj_mlp<288, 2>(", "return launch_proj_mlp<288, 0>(")
+    assert probe != text and proj_gaps(probe) == ["proj_mlp_kernel<288, 0> has no row", "rows expect proj_mlp_kernel<288, 2>, which the sources no longer launch"]
+    assert proj_gaps(text.replace("cvmi_note_kernel(", "note_off(")) == ["proj_mlp.hpp no longer tags its launch as proj_mlp_kernel<%d, %d>"]
+    drop = lambda *rids: proj_gaps(text, [r for r in PROJ_ROWS if r["id"] not in rids])
+    assert drop("proj_c144_rows5_ld148", "proj_c288_rows777_ld292") == []   # (no edge: the instances keep their other rows)
+    assert drop("proj_c144_rows33_ld148") == ["proj_mlp_kernel<144, 1>: no padded statistics-out row with 33 rows"]
+    assert drop("proj_c288_rows1_ld292", "proj_c288_rows128_ld292") == ["proj_mlp_kernel<288, 2>: no padded statistics-out row with 1 rows",
+                                                                        "proj_mlp_kernel<288, 2>: no padded statistics-out row with 128 rows"]
+    assert drop("proj_c288_rows129_ld292_nostats", "proj_c288_rows391_ld292_nostats") == ["proj_mlp_kernel<288, 2>: no row without statistics out"]
+    assert drop("proj_c144_rows391_ld144") == ["proj_mlp_kernel<144, 1>: no row with tight strides"]
+    assert drop("proj_c288_rows391_ld292_kinds") == ["proj_mlp_kernel<288, 2>: no kinds row"]
+    assert drop(*[r["id"] for r in PROJ_ROWS if r["C"] == 144]) == ["proj_mlp_kernel<144, 1> has no row"]
+
+
+def test_proj_and_kinds_rows_are_well_formed():
+    ids = [r["id"] for r in TOK_ROWS + MLP_ROWS + MLP_KIND_ROWS + PROJ_ROWS]
+    assert len(ids) == len(set(ids)), "duplicate row ids"
+    for r in PROJ_ROWS:
+        C = r["C"]
+        assert r["expect"] == proj_pick(C) and r["proj"] and r["dtypes"] == ("f16", "bf16") and r["rows"] <= 1000, r["id"]
+        assert (r["x_ld"], r["ao_ld"]) in ((C + 4, C + 8), (C, C)) and r["x_ld"] % 4 == 0 and r["ao_ld"] % 8 == 0, f"{r['id']}: the alignment contract"
+        assert not r["kinds"] or (r["rows"] == 391 and r["stats_out"] and r["x_ld"] > C), r["id"]
+    for C in (144, 288):
+        mine = [r for r in PROJ_ROWS if r["C"] == C]
+        assert {r["rows"] for r in mine if r["stats_out"] and not r["kinds"] and r["x_ld"] > C} >= set(MLP_ROW_COUNTS), C
+        assert {r["rows"] for r in mine if not r["stats_out"]} == {129, 391} and [r["rows"] for r in mine if r["x_ld"] == C] == [391], C
+        assert sum(r["kinds"] for r in mine) == 1, C
+    assert {(r["C"], r["rows"]) for r in PROJ_ROWS} >= set(PROJ_TODAY)
+    assert [r["expect"] for r in MLP_KIND_ROWS] == [mlp_pick(144), mlp_pick(288), mlp_pick(288, "0")] and sorted(r["expect"] for r in MLP_KIND_ROWS) == MLP_INSTANCES
+    for r in MLP_KIND_ROWS:
+        assert r["kinds"] and r["rows"] == 391 and r["stats_out"] and r["x_ld"] == r["C"] + 4 and r["expect"] == mlp_pick(r["C"], r["pipe"]), r["id"]
+    assert not any(r.get("kinds") for r in MLP_ROWS)                         # the measured rows of the plain family are what they were
+    assert len(KIND_BLOCKS) == 5 and 391 >= (len(KIND_BLOCKS) + 1) * KIND_ROWS   # five kinds of one wave tile each, and plain rows behind them
+
+
 # ---- the detector's tail: nms.hip nms_launch / yolo_nms_kernel, vision_ops.hip cvmi_detect_decode -----------------------------------------------------
-DETECT_SOURCES = ("nms.hip", "vision_ops.hip")
+DETECT_SOURCES =("nms.hip", "vision_ops.hip")
 # the text nms_pick / nms_workspace mirror: constant or expression -> what op_matrix holds for it
 NMS_TEXT = {
     "constexpr int NMS_LDS_A = %d;" % NMS_LDS_A: "NMS_LDS_A",

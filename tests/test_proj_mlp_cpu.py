@@ -14,7 +14,7 @@ import torch
 from circuitvision_amd import _lib
 from circuitvision_amd._lib import BF16, F16, F32
 from circuitvision_amd.engine import TORCH_DTYPE, PackedProjMlp, proj_mlp_k_order
-from proj_mlp_cases import PROJ_MLP_ROWS
+from proj_mlp_cases import PROJ_MLP_ROWS, PROJ_ROWS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "circuitvision_amd", "csrc")
@@ -39,7 +39,9 @@ def test_every_instance_the_header_launches_has_a_row():
     assert set(header_instances(probe)) - tags == {"proj_mlp_kernel<288, 0>"}
     for r in PROJ_MLP_ROWS:
         assert r["expect"] == "proj_mlp_kernel<%d, %d>" % (r["C"], 1 if r["C"] == 144 else 2), r["id"]
-    assert {(r["C"], r["rows"]) for r in PROJ_MLP_ROWS} == {(144, 5), (144, 1000), (144, 128 * 3 + 37), (288, 5), (288, 777)}
+    today = {(144, 5), (144, 1000), (144, 128 * 3 + 37), (288, 5), (288, 777)}
+    assert {(r["C"], r["rows"]) for r in PROJ_MLP_ROWS} >= today and {(r["C"], r["rows"]) for r in PROJ_ROWS} >= today
+    assert len(PROJ_MLP_ROWS) == len({r["id"] for r in PROJ_MLP_ROWS}) and {r["expect"] for r in PROJ_ROWS} == tags
 
 
 def _weights(C_, seed=3):

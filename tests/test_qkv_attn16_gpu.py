@@ -8,7 +8,8 @@ on the 16-bit qkv the UNFUSED projection wrote, judged by the bound tests/test_a
 checked elementwise too; the two-launch path's own error / bound is printed beside the fused one.
 Every row runs with an input ld of K + 4 whose padding columns are NaN, a NaN row block in front of the offset view, guard columns around `ao`
 that must keep their sentinel, LayerNorm statistics absent and forwarded as the rows' own (mean, rstd), and a second launch on restored
-buffers that must be bit-identical.  The last test runs the plan that takes the launch for Hiera's stage 2, with the switch on and off."""
+buffers that must be bit-identical.  The `kinds` rows carry the five LayerNorm row kinds of tests/tok_ref.py; the seam test takes rows and
+statistics from a proj_mlp launch, as production does, instead of float64-made pairs.  The last test runs the plan that takes the launch for Hiera's stage 2, with the switch on and off."""
 import pytest
 import torch
 
@@ -18,7 +19,7 @@ from circuitvision_amd.engine import TORCH_DTYPE, PackedQkvAttn, PackedTokLinear
 from helpers import run, stream
 from qkv_attn16_cases import QKV_ATTN16_ROWS
 from test_attention_matrix_gpu import LN2, LOG2E, SENTINEL, _bound, _pool_q, _reference
-from test_qkv_attn_gpu import _windows
+from test_qkv_attn_gpu import _windows, token_rows
 
 pytestmark = pytest.mark.gpu
 DT = {"f16": F16, "bf16": BF16}
@@ -29,6 +30,18 @@ HD, WIN, PADR, OPAD, EPS = 72, 4, 8, 8, 1e-6
 @pytest.mark.parametrize("dt", ["f16", "bf16"])
 @pytest.mark.parametrize("row", QKV_ATTN16_ROWS, ids=[r["id"] for r in QKV_ATTN16_ROWS])
 def test_qkv_attn16_against_fp64_and_the_two_launches(row, dt, q_log2):
+    _case(row, dt, q_log2)
+
+
+@pytest.mark.parametrize("dt", ["f16", "bf16"])
+def test_proj_mlp_hands_rows_and_statistics_to_qkv_attn16(dt):
+    """The seam of stage 2: proj_mlp_kernel<288, 2> writes x and stats_out, qkv_attn16_kernel takes them as proj_x / proj_stats.  Inside the
+    imported bound against float64 window attention on the qkv of the unfused projection fed the same written statistics, within 2 x bound of
+    the two launches, and inside the bound of what the launches produce with the statistics absent."""
+    _case(next(r for r in QKV_ATTN16_ROWS if r["id"] == "kinds_2x16x24"), dt, 0, seam=True)
+
+
+def _case(row, dt, q_log2, seam=False):
     dtype, lib = DT[dt], _lib.load()
     td = TORCH_DTYPE[dtype]
     (B, H, W), K, heads = row["grid"], row["K"], row["heads"]
@@ -43,19 +56,13 @@ def test_qkv_attn16_against_fp64_and_the_two_launches(row, dt, q_log2):
         w[:C_] *= HD ** -0.5 * LOG2E
         bias[:C_] *= HD ** -0.5 * LOG2E
     gam, bet = (1 + 0.2 * torch.randn(K, generator=g)).cuda(), (0.1 * torch.randn(K, generator=g)).cuda()
-    xh = torch.randn(rows, K, generator=g) * (1 + torch.rand(rows, 1, generator=g)) + torch.randn(rows, 1, generator=g)
-    xbuf = torch.full((PADR + rows, ld), float("nan"))       # NaN row block in front, NaN padding columns
-    xbuf[PADR:, :K] = xh
-    xbuf = xbuf.cuda()
-    x_rows = Rows(xbuf, rows, K, ld=ld, offset=PADR * ld, dtype=F32)
-    mean = xh.mean(1)
-    own = torch.stack((mean, 1.0 / torch.sqrt(((xh - mean[:, None]) ** 2).mean(1) + EPS)), 1).contiguous().cuda()
+    x_rows, own, xbuf = token_rows(row, dt, g, seam)
     pt, pq = PackedTokLinear(w, bias, "cuda", dtype), PackedQkvAttn(w, bias, heads, "cuda", dtype)
     scale = 123.0 if q_log2 else HD ** -0.5                  # (q_log2: the descriptor's scale is ignored)
     common = dict(q_sb=0, q_sh=HD, q_st=3 * C_, k_sb=0, k_sh=HD, k_st=3 * C_, v_sb=0, v_sh=HD, v_st=3 * C_, o_sb=0, o_sh=HD, o_st=C_ + 2 * OPAD,
                   B=nwin, heads=heads, Nq=nq, Nk=WIN * WIN, dqk=HD, dv=HD, scale=scale, dtype=dtype, win=WIN, grid_h=H, grid_w=W, q_pool=qp,
                   q_bdiv=0, kv_bdiv=0, av_fp8=0, q_log2=q_log2)
-    failures = []
+    failures, absent = [], None
     for stats in (None, own):
         what = "stats forwarded" if stats is not None else "stats absent"
         qkv = torch.full((rows, 3 * C_), SENTINEL, dtype=td, device="cuda")
@@ -102,6 +109,13 @@ def test_qkv_attn16_against_fp64_and_the_two_launches(row, dt, q_log2):
             failures.append(f"{what}: err/bound {ratio:.3f} against float64 window attention (two launches: {ratio_two:.3f})")
         if not between <= 2.0:
             failures.append(f"{what}: |fused - two launches| / bound {between:.3f} > 2")
+        if stats is None:
+            absent = (ref, bound)
+        elif seam:                                           # the written statistics against what the launches make of the rows themselves
+            r0 = float(((got.double() - absent[0]).abs() / absent[1]).max())
+            print(f"QKV-ATTN16 {row['id']} {dt} seam: err/bound vs fp64 on the statistics-absent qkv {r0:.3f}")
+            if not r0 <= 1.0:
+                failures.append(f"{what}: err/bound {r0:.3f} against float64 window attention on the statistics-absent qkv")
     assert not failures, f"{row['id']} {dt} q_log2={q_log2}:\n  " + "\n  ".join(failures)
 
 

@@ -9,22 +9,28 @@ catches the classic mistakes.
 Every launch goes through engine.py's wrappers over Buf / View operands (which carry their own sizes).  Each row also checks that the input's
 padding columns (NaN) and the rows in front of an offset view (NaN) are not read, that guard columns behind the output and rows behind the
 MLP's last one are bit-untouched, that forwarded statistics are those of the rows as written, and that a second launch on restored buffers is
-bit-identical."""
+bit-identical.
+
+PROJ_ROWS hold proj_mlp_kernel (the proj form of op_hiera_mlp) to the same method at every count of MLP_ROW_COUNTS, without statistics out, at
+tight strides and on `kinds` operands -- LayerNorm inputs 500 away from zero, ramped along C, with a spread of 1e-3, with an outlier in channel
+0 and in the last channel; MLP_KIND_ROWS run hiera_mlp_kernel on the same kinds.  The `kinds` rows of proj_mlp also meet the two launches the
+fused one replaced."""
 import time
 
 import pytest
 import torch
 
 from circuitvision_amd._lib import ACT_GELU, ACT_NONE, BF16, F16, F32
-from circuitvision_amd.engine import Buf, PackedHieraMlp, PackedTokLinear, Plan, op_hiera_mlp, op_tok_linear, op_tok_linear_pool, tok_linear_stats_parts
+from circuitvision_amd.engine import Buf, PackedHieraMlp, PackedProjMlp, PackedTokLinear, Plan, op_hiera_mlp, op_tok_linear, op_tok_linear_pool, tok_linear_stats_parts
 from helpers import run, stream
-from op_matrix import MLP_ROWS, TOK_KS, TOK_ROWS, TOK_SPLIT_TABLE, tl16_splits
-from tok_ref import ATOL, LN_EPS, family, judge, reference, row_case, tok_operands
+from op_matrix import MLP_KIND_ROWS, MLP_ROWS, PROJ_ROWS, TOK_KS, TOK_ROWS, TOK_SPLIT_TABLE, tl16_splits
+from tok_ref import ATOL, LN_EPS, STATS_PAIR_TOL, family, judge, reference, row_case, stats_ref, tok_operands
 
 pytestmark = pytest.mark.gpu
 CODE = {"f16": F16, "bf16": BF16}
 CASES = [(r, dt) for r in TOK_ROWS for dt in r["dtypes"]]
-MLP_CASES = [(r, dt) for r in MLP_ROWS for dt in r["dtypes"]]
+MLP_CASES = [(r, dt) for r in MLP_ROWS + MLP_KIND_ROWS for dt in r["dtypes"]]
+PROJ_CASES = [(r, dt) for r in PROJ_ROWS for dt in r["dtypes"]]
 NAN = float("nan")
 
 
@@ -81,8 +87,16 @@ def launch_tok(row, dt, o):
     return tag, out, (first_stats.cpu() if stats is not None else None), same, db
 
 
-def _verdict(what, row, dt, tag, ratio, mx, fails, same, t0):
-    print(f"TOK-MATRIX {row['id']} {dt}: {tag}  family {family(row)}  max|err| {mx:.3e}  err/bound {ratio:.3f}  (atol {ATOL[family(row), dt]:.3e})  {time.time() - t0:.2f} s")
+def _pair_ratio(row, out, stats):
+    """err / bound of a forwarded (mean, rstd) pair against the rows as written (what judge holds it to), for the printed line."""
+    if stats is None:
+        return ""
+    exp = stats_ref(out[:row["rows"]], row["C"])
+    return "  statistics err/bound %.3f" % float(((stats.double() - exp).abs() / (STATS_PAIR_TOL[1] + STATS_PAIR_TOL[0] * exp.abs())).max())
+
+
+def _verdict(what, row, dt, tag, ratio, mx, fails, same, t0, more=""):
+    print(f"TOK-MATRIX {row['id']} {dt}: {tag}  family {family(row)}  max|err| {mx:.3e}  err/bound {ratio:.3f}  (atol {ATOL[family(row), dt]:.3e}){more}  {time.time() - t0:.2f} s")
     fails = list(fails)
     if tag != row["expect"]:
         fails.insert(0, f"kernel {tag!r}, expected {row['expect']!r}")
@@ -155,8 +169,85 @@ def test_mlp_matrix(row, dt, monkeypatch):
         stats.fill_(-7.0)
     run(plan)
     same = torch.equal(xb.t, first) and (stats is None or torch.equal(stats, first_stats))
-    ratio, mx, fails = judge(row, dt, o, ref, first.view(rows + 3, x_ld).cpu(), first_stats.cpu() if stats is not None else None)
-    _verdict("hiera_mlp", row, dt, tag, ratio, mx, fails, same, t0)
+    out, wrote = first.view(rows + 3, x_ld).cpu(), (first_stats.cpu() if stats is not None else None)
+    ratio, mx, fails = judge(row, dt, o, ref, out, wrote)
+    _verdict("hiera_mlp", row, dt, tag, ratio, mx, fails, same, t0, _pair_ratio(row, out, wrote))
+
+
+def _bits(t):
+    return t.contiguous().view(torch.int32 if t.element_size() == 4 else torch.int16)
+
+
+def two_launches(row, dt, o):
+    """op_tok_linear(residual) + op_hiera_mlp on a proj row's operands: the updated rows [rows, C] as a CPU float tensor.  op_tok_linear takes
+    whole 256-row workgroups: the rows are padded with finite values."""
+    C, rows, code = row["C"], row["rows"], CODE[dt]
+    R = (rows + 255) // 256 * 256
+    xc = Buf(1, 1, R, C, F32)
+    xc.t.fill_(0.25)
+    xc.t[0, 0, :rows] = o["x0"][:rows, :C].cuda()
+    ac = Buf(1, 1, R, C, code)
+    ac.t.fill_(0.5)
+    ac.t[0, 0, :rows] = o["ao"].cuda()
+    chain = Plan(stream())
+    op_tok_linear(chain, "proj", PackedTokLinear(o["wp"], o["bp"], dtype=code), ac.view(), xc.view(), residual=True)
+    op_hiera_mlp(chain, "mlp", PackedHieraMlp(o["w1"], o["b1"], o["w2"], o["b2"], dtype=code), xc.view(), o["gam"].cuda(), o["bet"].cuda(), LN_EPS)
+    run(chain)
+    return xc.t[0, 0, :rows].float().cpu()
+
+
+def launch_proj(row, dt, o):
+    """One PROJ_ROWS launch and its replay on restored buffers.  x lies behind a NaN row block and has three rows behind `rows`; its padding
+    columns and ao's are NaN.  Returns (tag, the buffer [rows + 3, x_ld] after the first launch as a CPU tensor, its statistics or None, list of
+    layout failures, second launch bit-identical, (x Buf, statistics tensor))."""
+    C, rows, x_ld, ao_ld, code = row["C"], row["rows"], row["x_ld"], row["ao_ld"], CODE[dt]
+    xb = Buf(2, 1, rows + 3, x_ld, F32)
+    xb.t.fill_(NAN)
+    xb.t[1, 0].copy_(o["x0"])
+    x0 = xb.t.clone()
+    aob = Buf(1, 1, rows, ao_ld, code)
+    aob.t[0, 0].copy_(o["ao_buf"])
+    ao0 = aob.t.clone()
+    view = xb.images(1, 1).view(0, C)
+    view.buf.W = rows                                                       # the op covers the first `rows` rows only
+    pm = PackedProjMlp(o["wp"], o["bp"], o["w1"], o["b1"], o["w2"], o["b2"], dtype=code)
+    stats = torch.full((rows, 2), -7.0, device="cuda") if row["stats_out"] else None
+    plan = Plan(stream())
+    op_hiera_mlp(plan, row["id"], None, view, o["gam"].cuda(), o["bet"].cuda(), LN_EPS, stats_out=stats, stats_eps=LN_EPS, proj=(pm, aob.view(0, C)))
+    tag = _first_tag(plan)
+    first, first_stats = xb.t.clone(), (stats.clone() if stats is not None else None)
+    fails = []
+    if not torch.equal(_bits(first[0]), _bits(x0[0])):
+        fails.append("the NaN row block in front of x was written")
+    if not torch.equal(_bits(aob.t), _bits(ao0)):
+        fails.append("ao was written")
+    xb.t.copy_(x0)
+    if stats is not None:
+        stats.fill_(-7.0)
+    run(plan)
+    same = torch.equal(_bits(xb.t), _bits(first)) and (stats is None or torch.equal(stats, first_stats))
+    return tag, first[1, 0].cpu(), (first_stats.cpu() if stats is not None else None), fails, same, (xb, stats)
+
+
+@pytest.mark.parametrize("row,dt", PROJ_CASES, ids=[f"{r['id']}-{dt}" for r, dt in PROJ_CASES])
+def test_proj_mlp_matrix(row, dt):
+    """proj_mlp_kernel against tok_ref.proj_mlp_ref under the projmlp bound.  A NaN that the launch read from x's or ao's padding, or from the
+    row block in front, would reach the updated rows and fail the bound; on the `kinds` rows the launch also meets op_tok_linear(residual) +
+    op_hiera_mlp on the same inputs within the sum of the two families' bounds."""
+    t0 = time.time()
+    _, o, ref = row_case(row["id"], dt)
+    tag, out, stats, layout, same, _ = launch_proj(row, dt, o)
+    ratio, mx, fails = judge(row, dt, o, ref, out, stats)
+    if not bool(torch.isfinite(out[:row["rows"], :row["C"]]).all()):
+        fails.append("non-finite updated values: padding was read")
+    if row["kinds"]:
+        two = two_launches(row, dt, o)
+        bound = ATOL["projmlp", dt] + ATOL["mlp_kinds", dt]
+        worst = float((out[:row["rows"], :row["C"]].double() - two.double()).abs().max()) / bound
+        print(f"TOK-MATRIX {row['id']} {dt}: |fused - two launches| / (projmlp + mlp_kinds bound) {worst:.3f}")
+        if not worst <= 1.0:
+            fails.append(f"|fused - two launches| is {worst:.3f} of the two families' bounds")
+    _verdict("proj_mlp", row, dt, tag, ratio, mx, layout + fails, same, t0, _pair_ratio(row, out, stats))
 
 
 def test_tl16_splits_mirrors_the_library():

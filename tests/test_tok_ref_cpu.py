@@ -5,14 +5,15 @@ wrong width -- violates them on every row meant to catch it."""
 import pytest
 import torch
 
-from op_matrix import MLP_ROWS, TOK_MUTANT_DTYPES, TOK_MUTANT_ROWS, TOK_ROWS, TOK_UNSEEN_MUTANTS
-from tok_ref import (ALL_ROWS, ATOL, CHAIN32_DEV, FACTOR, HAND_SET, MLP_MUTANTS, RTOL, TOK_MUTANTS, TDT, family, gelu_form_error, judge, measure, reference,
-                     row_case, stored)
+from op_matrix import (FAR500_MUTANTS, KIND_BLOCKS, KIND_ROWS, MLP_KIND_MUTANT_ROWS, MLP_KIND_ROWS, MLP_ROWS, PROJ_MUTANT_ROWS, PROJ_ROWS, TOK_MUTANT_DTYPES,
+                       TOK_MUTANT_ROWS, TOK_ROWS, TOK_UNSEEN_MUTANTS)
+from tok_ref import (ALL_ROWS, ATOL, CHAIN32_DEV, FACTOR, HAND_SET, MLP_KIND_MUTANTS, MLP_MUTANTS, PROJ_MUTANTS, RTOL, STATS_PAIR_TOL, TOK_MUTANTS, TDT, family,
+                     gelu_form_error, judge, measure, measure_kinds, reference, row_case, stats_ref, stored)
 
 DTS = ("f16", "bf16")
-# families whose measured bound is NOT below half of today's hand-set tolerance (tests/test_ops_gpu.py), with the reason: all three are set by
+# families whose measured bound is NOT below half of today's hand-set tolerance (tests/test_ops_gpu.py), with the reason: all are set by
 # the error of the GELU form the kernels evaluate, which chain32 reproduces (tok_ref.gelu_fast) -- see test_the_gelu_form_error_is_what_was_measured
-OVER_HALF_OF_HAND_SET = {("gelu_ln", "f16"), ("mlp", "f16"), ("mlp", "bf16")}
+OVER_HALF_OF_HAND_SET = {("gelu_ln", "f16"), ("mlp", "f16"), ("mlp", "bf16"), ("mlp_kinds", "f16"), ("mlp_kinds", "bf16"), ("projmlp", "f16"), ("projmlp", "bf16")}
 
 
 @pytest.fixture(scope="module")
@@ -52,7 +53,9 @@ def test_every_rows_chain32_passes_the_comparison_the_gpu_rows_face(dt):
         ratio, _, fails = judge(row, dt, o, ref, c32["out"], c32["stats"])
         assert not fails and ratio <= 1.0 / FACTOR + 1e-9, (rid, dt, ratio, fails)
         n = row.get("N", row.get("C"))
-        assert bool(torch.isfinite(ref["out"]).all()) and float(ref["out"][:, :n].abs().max()) < (2.0 if stored(row, dt) != "f32" else 16.0), rid
+        whole = ref["out"][:, :n] if row.get("proj") else ref["out"]       # (the proj rows' padding columns are NaN before and after)
+        big = 600.0 if row.get("kinds") else 16.0                         # (the kinds rows sit up to 500 away from zero on purpose)
+        assert bool(torch.isfinite(whole).all()) and float(ref["out"][:, :n].abs().max()) < (2.0 if stored(row, dt) != "f32" else big), rid
 
 
 @pytest.mark.parametrize("mutant,rid,dt", [(m, rid, dt) for m, rids in TOK_MUTANT_ROWS.items() for rid in rids for dt in TOK_MUTANT_DTYPES.get(m, DTS)])
@@ -62,6 +65,58 @@ def test_each_mutant_violates_the_tolerance_on_its_row(mutant, rid, dt):
     ratio, mx, fails = judge(row, dt, o, ref, mo["out"], mo["stats"])
     print(f"{mutant} on {rid} {dt}: max|err| {mx:.3e}  err/bound {ratio:.2f}  {fails}")
     assert fails, f"{mutant} passes on {rid} ({dt}): change the row (size, seed, scale), never the tolerance"
+
+
+NEW_MUTANT_CASES = [(m, rid, dt) for table in (PROJ_MUTANT_ROWS, MLP_KIND_MUTANT_ROWS) for m, rids in table.items() for rid in rids for dt in DTS]
+
+
+@pytest.mark.parametrize("mutant,rid,dt", NEW_MUTANT_CASES)
+def test_each_proj_and_kinds_mutant_violates_the_tolerance_on_its_row(mutant, rid, dt):
+    """PROJ_MUTANT_ROWS / MLP_KIND_MUTANT_ROWS, fp16 and bf16.  The two raw-moment mutants must fall on the rows 500 away from zero: judged on
+    those KIND_ROWS rows alone (output columns and statistics), they are outside the bound there."""
+    row, o, ref = row_case(rid, dt)
+    mo = reference(row, o, dt, torch.float64, mutant)
+    ratio, mx, fails = judge(row, dt, o, ref, mo["out"], mo["stats"])
+    print(f"{mutant} on {rid} {dt}: max|err| {mx:.3e}  err/bound {ratio:.2f}  {fails}")
+    assert fails, f"{mutant} passes on {rid} ({dt}): change the row (size, seed, scale), never the tolerance"
+    if mutant in FAR500_MUTANTS:
+        assert row["kinds"] and KIND_BLOCKS[0] == "far500"
+        C, far = row["C"], slice(0, KIND_ROWS)
+        if mutant == "ln_var_raw_moments":
+            err = (mo["out"][far, :C] - ref["out"][far, :C]).abs().max()
+            assert float(err) > ATOL[family(row), dt], (rid, dt, float(err))
+        else:
+            exp = stats_ref(mo["out"][far], C)
+            off = ((mo["stats"][far].double() - exp).abs() / (STATS_PAIR_TOL[1] + STATS_PAIR_TOL[0] * exp.abs())).max()
+            assert float(off) > 1.0, (rid, dt, float(off))
+
+
+def test_the_kinds_do_not_call_for_a_family_of_their_own(measured):
+    """A kinds family is split off its launch's family only when its constant exceeds 2 x the plain mlp constant; neither does, so the kinds
+    rows of proj_mlp stay in projmlp, and no kind of either family deviates by more than 2 x what the plain rows of the same launch do."""
+    dev, _ = measured
+    for dt in DTS:
+        assert CHAIN32_DEV["mlp_kinds", dt] <= 2 * CHAIN32_DEV["mlp", dt] and CHAIN32_DEV["projmlp", dt] <= 2 * CHAIN32_DEV["mlp", dt], dt
+    per_kind = measure_kinds(DTS)
+    assert {k[0] for k in per_kind} == {r["id"] for r in MLP_KIND_ROWS + PROJ_ROWS if r.get("kinds")}
+    for (rid, dt), v in sorted(per_kind.items()):
+        print(f"{rid} {dt}: " + "  ".join(f"{k} {x:.3e}" for k, x in zip(KIND_BLOCKS + ("plain",), v)))
+        assert max(v[:-1]) <= 2 * CHAIN32_DEV["mlp", dt], (rid, dt, v)
+
+
+def test_every_proj_and_kinds_mutant_has_rows():
+    assert set(PROJ_MUTANT_ROWS) == set(PROJ_MUTANTS) and set(MLP_KIND_MUTANT_ROWS) == set(MLP_KIND_MUTANTS)
+    proj_ids, kind_ids = {r["id"] for r in PROJ_ROWS}, {r["id"] for r in MLP_KIND_ROWS}
+    for m, rids in PROJ_MUTANT_ROWS.items():
+        assert rids and set(rids) <= proj_ids, m
+        assert {ALL_ROWS[rid]["expect"] for rid in rids} == {"proj_mlp_kernel<144, 1>", "proj_mlp_kernel<288, 2>"}, m      # ... on both instances
+    for m, rids in MLP_KIND_MUTANT_ROWS.items():
+        assert set(rids) == kind_ids, m
+    for m in FAR500_MUTANTS:
+        assert all(ALL_ROWS[rid]["kinds"] for rid in PROJ_MUTANT_ROWS[m] + MLP_KIND_MUTANT_ROWS[m]), m
+    assert set(PROJ_MUTANT_ROWS["proj_rows_past_end"]) == {r["id"] for r in PROJ_ROWS if r["rows"] % 128}
+    assert set(PROJ_MUTANT_ROWS["stats_of_x1"]) == {r["id"] for r in PROJ_ROWS if r["stats_out"]}
+    assert not (set(PROJ_MUTANTS) | set(MLP_KIND_MUTANTS)) & set(TOK_UNSEEN_MUTANTS)      # every one of them is caught: no new blind spot
 
 
 def test_every_mutant_has_rows():

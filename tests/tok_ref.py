@@ -1,6 +1,6 @@
-"""Plain references of the token-stationary kernels (tok_linear.hip, tok_linear16.hip, hiera_mlp.hip), the seeded operands of every row of
-op_matrix.TOK_ROWS / MLP_ROWS and the bounds the token-path matrix (tests/test_tok_matrix_gpu.py) holds the kernels to.  CPU only, plain torch:
-importing this module needs neither a GPU nor the library.
+"""Plain references of the token-stationary kernels (tok_linear.hip, tok_linear16.hip, hiera_mlp.hip and its proj form, proj_mlp.hpp), the seeded
+operands of every row of op_matrix.TOK_ROWS / MLP_ROWS / MLP_KIND_ROWS / PROJ_ROWS and the bounds the token-path matrix
+(tests/test_tok_matrix_gpu.py) holds the kernels to.  CPU only, plain torch: importing this module needs neither a GPU nor the library.
 
 The references state the op in `dtype` on operands that arrive pre-rounded to the operand type ("f16" | "bf16") and round exactly where the
 kernels' contracts say a 16-bit value is formed: the LayerNorm output (the MFMA's B fragments), the 16-bit output, the MLP's hidden activation.
@@ -22,7 +22,7 @@ import zlib
 import torch
 import torch.nn.functional as F
 
-from op_matrix import MLP_ROWS, TOK_FORMAT, TOK_ROWS, tl16_splits
+from op_matrix import KIND_BLOCKS, KIND_ROWS, MLP_KIND_ROWS, MLP_ROWS, PROJ_ROWS, TOK_FORMAT, TOK_ROWS, tl16_splits
 
 TDT = {"f16": torch.float16, "bf16": torch.bfloat16, "f32": torch.float32}
 SENT16 = -12288.0                                      # guard value of 16-bit outputs: exact in fp16 and bf16
@@ -33,6 +33,9 @@ WSCALE = 0.125                                         # 16-bit outputs stay bel
 TOK_MUTANTS = ("ring_stale_slot", "split_ring_origin", "last_piece_dropped", "guard_written", "res_overwrite", "ln_no_eps", "ln_var_n_minus_1",
                "chan_no_between_term", "chan_raw_moments", "stats_over_ld", "pool_dxdy_swapped", "pool_w_for_hw", "pool_mean", "bias_hi_only")
 MLP_MUTANTS = ("mlp_hidden_not_rounded", "mlp_rows_past_end")
+MLP_KIND_MUTANTS = ("ln_var_raw_moments", "stats_unshifted")
+PROJ_MUTANTS = ("proj_bias_twice", "proj_bias_not_in_ln", "ln_of_x_not_x1", "residual_drops_proj", "fc1_k_natural_order", "proj_rows_past_end", "stats_of_x1",
+                "ln_var_raw_moments", "stats_unshifted", "x1_through_16_bits")
 
 # |y - ref64| <= ATOL[family, dtype] + RTOL[stored type] |ref64| per element.  RTOL is one step of the stored output (0 for f32 outputs).
 # ATOL = FACTOR x the largest |chain32 - ref64| over the rows of the family, measured on the CPU (main() below) and re-measured by
@@ -57,11 +60,18 @@ CHAIN32_DEV = {
     ("gelu_raw", "f16"): 2.0 ** -11, ("gelu_raw", "bf16"): 2.0 ** -9, ("gelu_ln", "f16"): 2.0 ** -10, ("gelu_ln", "bf16"): 2.0 ** -8,
     ("res_raw", "f16"): 4.7e-7, ("res_raw", "bf16"): 3.2e-7, ("res_ln", "f16"): 1.0e-4, ("res_ln", "bf16"): 4.6e-4,
     ("pool", "f16"): 7.1e-5, ("pool", "bf16"): 4.6e-4, ("mlp", "f16"): 2.0e-3, ("mlp", "bf16"): 3.4e-3,
+    #   mlp_kinds f16 2.1e-3 bf16 4.2e-3   fp16: as mlp (the last-channel outlier rows); bf16: the rows 500 away from zero -- the f32 mean of 144 / 288 values
+    #                                      near 500 is off by 1e-5 of their spread, and more B-fragment values round the other way
+    #   projmlp   f16 1.9e-3 bf16 4.3e-3   fp16: as mlp (a plain row); bf16: the 1e-3-spread rows -- x + ao Wp^T formed in f32 moves x1 by 1e-7, 1e-4 of
+    #                                      that spread, ahead of the same rounding
+    # Neither is above 2 x the plain mlp constant: the kinds rows stay in their launch's family (main() prints the deviation per kind).
+    ("mlp_kinds", "f16"): 2.2e-3, ("mlp_kinds", "bf16"): 4.2e-3, ("projmlp", "f16"): 1.9e-3, ("projmlp", "bf16"): 4.4e-3,
 }
 ATOL = {k: FACTOR * v for k, v in CHAIN32_DEV.items()}
 # today's hand-set absolute tolerances of tests/test_ops_gpu.py for the same forms (16-bit output, f32 residual, pooled map, fused MLP)
 HAND_SET = {("o16", "f16"): 4e-3, ("o16", "bf16"): 3.2e-2, ("gelu", "f16"): 4e-3, ("gelu", "bf16"): 3.2e-2, ("res", "f16"): 3e-3, ("res", "bf16"): 2.4e-2,
-            ("pool", "f16"): 4e-3, ("pool", "bf16"): 3.2e-2, ("mlp", "f16"): 3e-3, ("mlp", "bf16"): 2.4e-2}
+            ("pool", "f16"): 4e-3, ("pool", "bf16"): 3.2e-2, ("mlp", "f16"): 3e-3, ("mlp", "bf16"): 2.4e-2,
+            ("projmlp", "f16"): 3e-3, ("projmlp", "bf16"): 2.4e-2}          # (projmlp: tests/test_proj_mlp_gpu.py)
 STATS_PAIR_TOL = (2e-5, 2e-5)                          # (rtol, atol) of forwarded (mean, rstd) against the rows as written
 STATS_PARTS_TOL = (1e-4, 1e-3)                         # ... of per-slice (mean, sum of squared deviations)
 
@@ -73,7 +83,7 @@ def rT(t, dt):
 
 def family(row):
     if "C" in row:
-        return "mlp"
+        return "projmlp" if row.get("proj") else "mlp_kinds" if row.get("kinds") else "mlp"
     if row["pool"]:
         return "pool"
     return ("res" if row["res"] else "gelu" if row["gelu"] else "o16") + ("_ln" if row["ln"] == 1 else "_raw")
@@ -143,6 +153,21 @@ def stats_ref(rows_as_written, N, parts=0, eps=LN_EPS):
     return slice_moments(x, parts) if parts else moments(x, eps)
 
 
+def _raw_moments_f32(x):
+    """(mean, E[x^2] - E[x]^2) per row, every operation in float32: the single-pass form without a shift."""
+    xf = x.float()
+    m = xf.mean(1, keepdim=True)
+    return m, ((xf * xf).mean(1, keepdim=True) - m * m).clamp(min=0.0)
+
+
+def _stats_out(rows_as_written, mutant):
+    """The forwarded (mean, rstd) of a residual-stream launch over the rows it wrote."""
+    if mutant == "stats_unshifted":
+        m, var = _raw_moments_f32(rows_as_written)
+        return torch.cat((m, 1.0 / torch.sqrt(var + LN_EPS)), 1).to(rows_as_written.dtype)
+    return moments(rows_as_written)
+
+
 def _ln(x, gam, bet, dt, o, row, mutant):
     """LayerNorm of the f32 rows -> the 16-bit B fragments."""
     K = x.shape[1]
@@ -156,6 +181,8 @@ def _ln(x, gam, bet, dt, o, row, mutant):
             var = (p[..., 1].sum(1, keepdim=True) / K - mean * mean).clamp(min=0)
     if mutant == "ln_var_n_minus_1":
         var = var * K / (K - 1)
+    if mutant == "ln_var_raw_moments":
+        mean, var = (t.to(x.dtype) for t in _raw_moments_f32(x))
     eps = 0.0 if mutant == "ln_no_eps" else LN_EPS
     return rT((x - mean) / torch.sqrt(var + eps) * gam.to(x.dtype) + bet.to(x.dtype), dt)
 
@@ -271,20 +298,39 @@ def tok_operands(row, dt):
 # ---- hiera_mlp --------------------------------------------------------------------------------------------------------------------------------------
 def hiera_mlp_ref(row, o, dt, dtype=torch.float64, mutant=None):
     """x <- x + fc2(GELU(fc1(LayerNorm(x)))) on the first `rows` rows of the buffer [rows + 3, x_ld]: dict(out = the whole buffer, stats)."""
-    assert mutant is None or mutant in MLP_MUTANTS, mutant
+    assert mutant is None or mutant in MLP_MUTANTS + MLP_KIND_MUTANTS, mutant
     C, rows = row["C"], row["rows"]
-    fast = dtype == torch.float32
     buf = o["x0"].to(dtype)
     upd = min(rows + 3, -(-rows // 128) * 128) if mutant == "mlp_rows_past_end" else rows
     x = buf[:upd, :C]
-    xn = _ln(x, o["gam"], o["bet"], dt, o, row, None)
+    out = buf.clone()
+    out[:upd, :C] = x + _mlp_branch(x, row, o, dt, dtype, mutant)
+    return dict(out=out, stats=_stats_out(out[:rows, :C], mutant) if row["stats_out"] else None)
+
+
+def _mlp_branch(x, row, o, dt, dtype, mutant, k_order=None):
+    """fc2(GELU(fc1(LayerNorm(x)))) + b2 in `dtype`: the LayerNorm output and the hidden activation are rounded to dt, fc1's bias is the packed
+    hi + lo pair.  k_order: the channel order in which the normalised row meets fc1's columns (None: each its own)."""
+    xn = _ln(x, o["gam"], o["bet"], dt, o, row, mutant)
+    if k_order is not None:
+        xn = xn[:, k_order]
     hi, lo = _pair_bias(o["b1"], dt)
-    h = _gelu(xn @ o["w1"].to(dtype).t() + (hi.to(dtype) + lo.to(dtype)), dt, fast)
+    h = _gelu(xn @ o["w1"].to(dtype).t() + (hi.to(dtype) + lo.to(dtype)), dt, dtype == torch.float32)
     if mutant != "mlp_hidden_not_rounded":
         h = rT(h, dt)
-    out = buf.clone()
-    out[:upd, :C] = x + (h @ o["w2"].to(dtype).t() + o["b2"].to(dtype))
-    return dict(out=out, stats=moments(out[:rows, :C]) if row["stats_out"] else None)
+    return h @ o["w2"].to(dtype).t() + o["b2"].to(dtype)
+
+
+def row_kinds(x):
+    """The five kinds of LayerNorm input on the leading rows of x [rows, C], in place, KIND_ROWS rows each (op_matrix.KIND_BLOCKS): 500 away from
+    zero; a ramp along C; a spread of 1e-3 (variance near eps); an outlier in channel 0 -- the value the statistics hand-over shifts by -- and in
+    the last channel.  The rest stay plain."""
+    n, C = KIND_ROWS, x.shape[1]
+    x[:n] += 500.0
+    x[n:2 * n] += torch.linspace(-20.0, 20.0, C)
+    x[2 * n:3 * n] *= 1e-3
+    x[3 * n:4 * n, 0] += 40.0
+    x[4 * n:5 * n, C - 1] += 40.0
 
 
 def mlp_operands(row, dt):
@@ -292,21 +338,78 @@ def mlp_operands(row, dt):
     C, rows = row["C"], row["rows"]
     x0 = torch.full((rows + 3, row["x_ld"]), SENT32)
     x0[:, :C] = torch.randn(rows + 3, C, generator=g) * 1.5 + 0.3
+    if row.get("kinds"):
+        assert rows >= 6 * KIND_ROWS
+        row_kinds(x0[:rows, :C])
     return dict(x0=x0, gam=torch.rand(C, generator=g) + 0.5, bet=torch.randn(C, generator=g) * 0.2,
                 w1=rT(torch.randn(4 * C, C, generator=g) / C ** 0.5, dt), b1=torch.randn(4 * C, generator=g) * 0.3,
                 w2=rT(torch.randn(C, 4 * C, generator=g) / (4 * C) ** 0.5, dt), b2=torch.randn(C, generator=g) * 0.3)
 
 
+# ---- proj_mlp (the proj form of cvmi_hiera_mlp_stats) -----------------------------------------------------------------------------------------------
+def proj_k_order(C):
+    """proj_mlp.hpp: k index kappa of fc1's k-step stands for channel 8 ((kappa & 7) >> 2) + 4 (kappa >> 3) + (kappa & 3) of the step's 16."""
+    n = torch.arange(C)
+    k = n % 16
+    return n - k + 8 * ((k & 7) >> 2) + 4 * (k >> 3) + (k & 3)
+
+
+def proj_mlp_ref(row, o, dt, dtype=torch.float64, mutant=None):
+    """x1 = x + ao Wp^T + bp;  x <- x1 + fc2(GELU(fc1(LayerNorm(x1)))) + b2 on the first `rows` rows of the buffer [rows + 3, x_ld]: dict(out =
+    the whole buffer, stats).  ao and the weights arrive rounded to dt; x1 is never rounded."""
+    assert mutant is None or mutant in PROJ_MUTANTS, mutant
+    C, rows = row["C"], row["rows"]
+    buf = o["x0"].to(dtype)
+    upd = min(rows + 3, -(-rows // 128) * 128) if mutant == "proj_rows_past_end" else rows
+    x = buf[:upd, :C]
+    ao = o["ao"][torch.arange(upd).clamp(max=rows - 1)].to(dtype)          # (rows past the end: the kernel's clamped row)
+    pj, bp = ao @ o["wp"].to(dtype).t(), o["bp"].to(dtype)
+    x1 = x + (pj + (2.0 * bp if mutant == "proj_bias_twice" else bp))
+    if mutant == "x1_through_16_bits":
+        x1 = rT(x1, dt)
+    ln_in = x + pj if mutant == "proj_bias_not_in_ln" else x if mutant == "ln_of_x_not_x1" else x1
+    y = _mlp_branch(ln_in, row, o, dt, dtype, mutant, proj_k_order(C) if mutant == "fc1_k_natural_order" else None)
+    out = buf.clone()
+    out[:upd, :C] = (x + bp if mutant == "residual_drops_proj" else x1) + y
+    stats = None
+    if row["stats_out"]:
+        stats = moments(x1[:rows]) if mutant == "stats_of_x1" else _stats_out(out[:rows, :C], mutant)
+    return dict(out=out, stats=stats)
+
+
+def proj_operands(row, dt):
+    """Seeded operands of one PROJ_ROWS row: x0 = the f32 buffer before the launch [rows + 3, x_ld] (padding columns NaN), ao [rows, ao_ld]
+    (16-bit values, padding NaN), wp / w1 / w2 (16-bit values), bp / b1 / b2 / gam / bet f32.  The row kinds are kinds of the LayerNorm's
+    input x1: x1 is drawn (and, on a `kinds` row, shaped) first, then x = f32(x1 - (ao Wp^T + bp)) with the product in float64."""
+    g = _gen(row["id"], dt)
+    C, rows = row["C"], row["rows"]
+    x1 = torch.randn(rows + 3, C, generator=g) * 1.5 + 0.3
+    if row["kinds"]:
+        assert rows >= 6 * KIND_ROWS
+        row_kinds(x1[:rows])
+    ao = torch.full((rows, row["ao_ld"]), float("nan"))
+    ao[:, :C] = rT(torch.randn(rows, C, generator=g), dt)
+    o = dict(ao=ao[:, :C], ao_buf=ao, wp=rT(torch.randn(C, C, generator=g) / C ** 0.5, dt), bp=torch.randn(C, generator=g) * 0.3,
+             gam=torch.rand(C, generator=g) + 0.5, bet=torch.randn(C, generator=g) * 0.2,
+             w1=rT(torch.randn(4 * C, C, generator=g) / C ** 0.5, dt), b1=torch.randn(4 * C, generator=g) * 0.3,
+             w2=rT(torch.randn(C, 4 * C, generator=g) / (4 * C) ** 0.5, dt), b2=torch.randn(C, generator=g) * 0.3)
+    x1[:rows] = (x1[:rows].double() - (o["ao"].double() @ o["wp"].double().t() + o["bp"].double())).float()
+    x0 = torch.full((rows + 3, row["x_ld"]), float("nan"))
+    x0[:, :C] = x1
+    o["x0"] = x0
+    return o
+
+
 # ---- rows -------------------------------------------------------------------------------------------------------------------------------------------
-ALL_ROWS = {r["id"]: r for r in TOK_ROWS + MLP_ROWS}
+ALL_ROWS = {r["id"]: r for r in TOK_ROWS + MLP_ROWS + MLP_KIND_ROWS + PROJ_ROWS}
 
 
 def operands(row, dt):
-    return mlp_operands(row, dt) if "C" in row else tok_operands(row, dt)
+    return proj_operands(row, dt) if row.get("proj") else mlp_operands(row, dt) if "C" in row else tok_operands(row, dt)
 
 
 def reference(row, o, dt, dtype=torch.float64, mutant=None):
-    return (hiera_mlp_ref if "C" in row else tok_linear_ref)(row, o, dt, dtype, mutant)
+    return (proj_mlp_ref if row.get("proj") else hiera_mlp_ref if "C" in row else tok_linear_ref)(row, o, dt, dtype, mutant)
 
 
 @functools.lru_cache(maxsize=None)
@@ -325,6 +428,11 @@ def _close(got, exp, tol):
     return float(((got.double() - exp.double()).abs() / (tol[1] + tol[0] * exp.double().abs())).max())
 
 
+def _same(a, b):
+    """Bit-equal float32 tensors (NaN padding compares equal to itself)."""
+    return a.shape == b.shape and torch.equal(a.float().contiguous().view(torch.int32), b.float().contiguous().view(torch.int32))
+
+
 def judge(row, dt, o, ref, out, stats=None, atol=None):
     """The matrix's verdict on one launch: `out` is the whole output buffer after it (float tensor, [.., out_ld] or the MLP's [rows + 3, x_ld]),
     `stats` what it wrote as statistics.  Returns (err / bound of the N (C) computed columns, largest |err|, list of failures)."""
@@ -338,9 +446,9 @@ def judge(row, dt, o, ref, out, stats=None, atol=None):
     if not ratio <= 1.0:
         fails.append(f"err/bound {ratio:.3f} (max|err| {float(err.max()):.3e}, {int((err / (atol + RTOL[stored(row, dt)] * r64.abs()) > 1).sum())} of {err.numel()} elements over)")
     before = o["x0"] if mlp else o["dst0"]
-    if not torch.equal(out[:, n:].float(), before[:, n:]):
+    if not _same(out[:, n:].float(), before[:, n:]):
         fails.append("guard columns behind the output were written")
-    if mlp and not torch.equal(out[nrows:].float(), before[nrows:]):
+    if mlp and not _same(out[nrows:].float(), before[nrows:]):
         fails.append("rows behind the last one were written")
     if row["stats_out"]:
         parts = 0 if mlp else (row["ns"] or 1)
@@ -372,7 +480,23 @@ def measure(dts=("f16", "bf16")):
     return dev, per_k
 
 
+def measure_kinds(dts=("f16", "bf16")):
+    """{(row id, dtype): largest |chain32 - ref64| per block of KIND_BLOCKS, then over the plain rows behind them} of every `kinds` row."""
+    out = {}
+    for rid, row in ALL_ROWS.items():
+        if not row.get("kinds"):
+            continue
+        for dt in dts:
+            _, o, ref = row_case(rid, dt)
+            d = (reference(row, o, dt, torch.float32)["out"][:row["rows"], :row["C"]].double() - ref["out"][:row["rows"], :row["C"]]).abs().amax(1)
+            nb = len(KIND_BLOCKS)
+            out[rid, dt] = [float(d[KIND_ROWS * i:KIND_ROWS * (i + 1)].max()) for i in range(nb)] + [float(d[KIND_ROWS * nb:].max())]
+    return out
+
+
 def main():
+    for (rid, dt), v in sorted(measure_kinds().items()):
+        print("%-32s %-5s %s" % (rid, dt, "  ".join("%s %.3e" % kv for kv in zip(KIND_BLOCKS + ("plain",), v))))
     dev, per_k = measure()
     for k in sorted(dev):
         ks = "  ".join("K=%d %.3e" % (kk[1], v) for kk, v in sorted(per_k.items()) if (kk[0], kk[2]) == k)
