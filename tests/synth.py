@@ -115,6 +115,9 @@ def calibrated_yolo_params(scale, nc, seed, x, cand_per_image=45, spread=2.0, co
         best = bl.flatten().sort(descending=True).values
         k = max(2, int((best >= target).sum()))
         lo, hi = max(1, k - max(1, k // 5)), min(best.numel() - 1, k + max(2, k // 5) + 1)
+        if lo >= hi:                                              # a level of kb anchors or fewer per image (P5 of a 32 x 64 input): every anchor is a
+            b.add_(thr - (float(best[-1]) - 1.0))                 # candidate and no rank is left to separate it from; the threshold goes below the weakest
+            continue
         gaps = best[lo - 1:hi - 1] - best[lo:hi]                 # gap between rank j-1 and j for j in [lo, hi)
         j = lo + int(gaps.argmax())
         assert float(gaps.max()) > 2e-3, "degenerate logits: no usable gap for the confidence threshold"
