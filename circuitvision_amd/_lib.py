@@ -69,9 +69,26 @@ class AttnDesc(C.Structure):
     ]
 
 
-class MlpProj(C.Structure):
-    """cvmi_mlp_proj: the attention projection that cvmi_hiera_mlp_stats runs in the same launch."""
-    _fields_ = [("ao", C.c_void_p), ("w_packed", C.c_void_p), ("bp", C.c_void_p), ("ao_ld", C.c_int)]
+class TokDesc(C.Structure):
+    _fields_ = [
+        ("in", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("w_packed", C.c_void_p), ("out", C.c_void_p),
+        ("ln_stats_in", C.c_void_p), ("ln_stats_out", C.c_void_p),
+        ("rows", C.c_longlong),
+        ("in_ld", C.c_int), ("in_f32_layernorm", C.c_int), ("out_ld", C.c_int), ("out_f32_residual", C.c_int),
+        ("K", C.c_int), ("N", C.c_int), ("act", C.c_int), ("dtype", C.c_int),
+        ("ln_stats_in_parts", C.c_int), ("ln_stats_out_parts", C.c_int), ("pool_h", C.c_int), ("pool_w", C.c_int),
+        ("eps", C.c_float), ("ln_stats_eps", C.c_float),
+    ]
+
+
+class MlpDesc(C.Structure):
+    _fields_ = [
+        ("x", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("w_packed", C.c_void_p), ("b2", C.c_void_p),
+        ("ln_stats_out", C.c_void_p), ("ao", C.c_void_p), ("bp", C.c_void_p),
+        ("rows", C.c_longlong),
+        ("x_ld", C.c_int), ("C", C.c_int), ("dtype", C.c_int), ("ao_ld", C.c_int),
+        ("eps", C.c_float), ("ln_stats_eps", C.c_float),
+    ]
 
 
 class LetterboxRow(C.Structure):
@@ -127,17 +144,13 @@ SIGNATURES = {
     "cvmi_layernorm_dual": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, C.c_longlong, _i, _f, _vp]),
     "cvmi_hiera_mlp_supported": (_i, [_i]),
     "cvmi_hiera_mlp_packed_bytes": (C.c_size_t, [_i]),
-    "cvmi_hiera_mlp": (_i, [_vp, _i, _vp, _vp, _f, _vp, _vp, C.c_longlong, _i, _i, _vp]),
     "cvmi_hiera_mlp_proj_packed_bytes": (C.c_size_t, [_i]),
-    "cvmi_hiera_mlp_stats": (_i, [_vp, _i, _vp, _vp, _f, _vp, _vp, C.c_longlong, _i, _i, _vp, _f, _vp, C.POINTER(MlpProj)]),
+    "cvmi_hiera_mlp": (_i, [C.POINTER(MlpDesc), _vp]),
     "cvmi_tok_linear_supported": (_i, [_i]),
     "cvmi_tok_linear_packed_bytes": (C.c_size_t, [_i, _i]),
     "cvmi_tok_linear_format": (_i, [_i]),
     "cvmi_tok_linear_stats_parts": (_i, [C.c_longlong, _i, _i]),
-    "cvmi_tok_linear": (_i, [_vp, _i, _i, _vp, _vp, _f, _vp, _vp, _i, _i, C.c_longlong, _i, _i, _i, _i, _vp]),
-    "cvmi_tok_linear_stats": (_i, [_vp, _i, _i, _vp, _vp, _f, _vp, _vp, _i, _i, C.c_longlong, _i, _i, _i, _i, _vp, _i, _vp, _f, _vp]),
-    "cvmi_tok_linear_pool_stats": (_i, [_vp, _i, _vp, _vp, _f, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
-    "cvmi_tok_linear_pool": (_i, [_vp, _i, _vp, _vp, _f, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "cvmi_tok_linear": (_i, [C.POINTER(TokDesc), _vp]),
     "cvmi_maxpool2x2": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "cvmi_space_to_depth4": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "cvmi_cast": (_i, [_vp, _i, _i, _vp, _i, _i, C.c_longlong, _i, _vp]),
@@ -211,7 +224,7 @@ def load():
 
 
 # kind (include/cvmi355.h: CVMI_DESC_*) -> the ctypes mirror of that descriptor struct
-DESC_MIRRORS = {0: ConvDesc, 1: C3k2Desc, 2: DwPwDesc, 3: AttnDesc}
+DESC_MIRRORS = {0: ConvDesc, 1: C3k2Desc, 2: DwPwDesc, 3: AttnDesc, 4: TokDesc, 5: MlpDesc}
 
 
 def check_abi(lib, mirrors=None):

@@ -424,15 +424,14 @@ __global__ __launch_bounds__((MlpCfg<C, VAR>::NW * 64), (MlpCfg<C, VAR>::WPS)) v
 }
 
 template <int C, int VAR = 0>
-int launch_mlp(float* x, int x_ld, const float* gamma, const float* beta, float eps, const void* wp, const float* b2, long long rows, hipStream_t s,
-               float* stats_out, float stats_eps) {
+int launch_mlp(const cvmi_mlp_desc& d, hipStream_t s) {
   using Cfg = MlpCfg<C, VAR>;
   static hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&hiera_mlp_kernel<C, VAR>), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS);
   CVMI_HIP(attr);
   const long long per = (long long)Cfg::NW * 32;
   cvmi_note_kernel("hiera_mlp_kernel<%d, %d>", C, VAR);
-  hipLaunchKernelGGL((hiera_mlp_kernel<C, VAR>), dim3((unsigned)((rows + per - 1) / per)), dim3(Cfg::NW * 64), Cfg::LDS, s, x, x_ld, gamma, beta, eps,
-                     (const char*)wp, b2, rows, stats_out, stats_eps);
+  hipLaunchKernelGGL((hiera_mlp_kernel<C, VAR>), dim3((unsigned)((d.rows + per - 1) / per)), dim3(Cfg::NW * 64), Cfg::LDS, s, (float*)d.x, d.x_ld, d.gamma, d.beta,
+                     d.eps, (const char*)d.w_packed, d.b2, d.rows, d.ln_stats_out, d.ln_stats_eps);
   CVMI_LAUNCH_CHECK();
   return 0;
 }
@@ -456,38 +455,33 @@ extern "C" size_t cvmi_hiera_mlp_proj_packed_bytes(int C) {
   if (!cvmi_hiera_mlp_supported(C)) return 0;
   return (size_t)((C + 31) / 32) * (size_t)(C / 16) * 1024 + cvmi_hiera_mlp_packed_bytes(C);
 }
-extern "C" int cvmi_hiera_mlp_stats_bf16(void* x, int x_ld, const float* gamma, const float* beta, float eps, const void* w_packed, const float* b2,
-                                         long long rows, int C, int dtype, float* ln_stats_out, float ln_stats_eps, cvmi_stream_t stream_,
-                                         const cvmi_mlp_proj* proj);
+extern "C" int cvmi_hiera_mlp_bf16(const cvmi_mlp_desc* d, cvmi_stream_t stream_);
 #endif
 
-// cvmi_hiera_mlp that also writes, per updated row, the LayerNorm statistics (mean, 1 / sqrt(var + ln_stats_eps)) the NEXT launch needs
-// (the next block's norm1, fused into cvmi_tok_linear_stats / cvmi_tok_linear_pool_stats): ln_stats_out = float[2 * rows] or NULL.
-// proj != NULL: the block's attention projection runs in the same launch (proj_mlp.hpp); w_packed is then not read.
-extern "C" int CVMI_ENTRY(cvmi_hiera_mlp_stats)(void* x, int x_ld, const float* gamma, const float* beta, float eps, const void* w_packed, const float* b2,
-                                                long long rows, int C, int dtype, float* ln_stats_out, float ln_stats_eps, cvmi_stream_t stream_,
-                                                const cvmi_mlp_proj* proj) {
+// The fields of cvmi_mlp_desc are documented in include/cvmi355.h.  ln_stats_out: per updated row the LayerNorm statistics the NEXT launch needs
+// (the next block's norm1, read through cvmi_tok_desc.ln_stats_in).  ao / bp set: the block's attention projection runs in the same launch
+// (proj_mlp.hpp) and w_packed is that form's stream.
+extern "C" int CVMI_ENTRY(cvmi_hiera_mlp)(const cvmi_mlp_desc* d, cvmi_stream_t stream_) {
+  CVMI_CHECK(d, "hiera_mlp: null descriptor");
 #ifndef CVMI_OPERAND_BF16
-  if (dtype == CVMI_BF16) return cvmi_hiera_mlp_stats_bf16(x, x_ld, gamma, beta, eps, w_packed, b2, rows, C, dtype, ln_stats_out, ln_stats_eps, stream_, proj);
+  if (d->dtype == CVMI_BF16) return cvmi_hiera_mlp_bf16(d, stream_);
 #endif
-  CVMI_CHECK(dtype == CVMI_T16, "hiera_mlp: dtype must be CVMI_F16 or CVMI_BF16");
-  CVMI_CHECK(x && gamma && beta && (w_packed || proj) && b2 && rows > 0, "hiera_mlp: bad arguments");
+  const bool proj = d->ao || d->bp;
+  const int C = d->C;
+  CVMI_CHECK(d->dtype == CVMI_T16, "hiera_mlp: dtype must be CVMI_F16 or CVMI_BF16");
+  CVMI_CHECK(d->x && d->gamma && d->beta && (d->w_packed || proj) && d->b2 && d->rows > 0, "hiera_mlp: bad arguments");
   CVMI_CHECK(C == 144 || C == 288, "hiera_mlp: C=%d is not built (144, 288)", C);
-  CVMI_CHECK(x_ld >= C && x_ld % 4 == 0 && (((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)w_packed | (uintptr_t)b2) & 15) == 0 &&
-                 ((uintptr_t)ln_stats_out & 7) == 0,
+  // (the proj form answers for its own stream: proj_mlp_dispatch)
+  CVMI_CHECK(d->x_ld >= C && d->x_ld % 4 == 0 &&
+                 (((uintptr_t)d->x | (uintptr_t)d->gamma | (uintptr_t)d->beta | (proj ? 0 : (uintptr_t)d->w_packed) | (uintptr_t)d->b2) & 15) == 0 &&
+                 ((uintptr_t)d->ln_stats_out & 7) == 0,
              "hiera_mlp: pointers / ld must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream_;
-  float* xf = (float*)x;
-  if (proj) return proj_mlp_dispatch(xf, x_ld, proj, gamma, beta, eps, b2, rows, C, s, ln_stats_out, ln_stats_eps);
-  if (C == 144) return launch_mlp<144, 1>(xf, x_ld, gamma, beta, eps, w_packed, b2, rows, s, ln_stats_out, ln_stats_eps);
+  if (proj) return proj_mlp_dispatch(*d, s);
+  if (C == 144) return launch_mlp<144, 1>(*d, s);
   // Test hook, not a tuning switch: CVMI_MLP_PIPE=0 runs C = 288 on the chunk-order loop (VAR 0), the bit-exact reference the pipelined
   // loop is tested against (tests/test_ops_gpu.py switches it between two launches, so it is read per call).
   const char* const pipe = getenv("CVMI_MLP_PIPE");
-  if (pipe && !(atoi(pipe) & 2)) return launch_mlp<288, 0>(xf, x_ld, gamma, beta, eps, w_packed, b2, rows, s, ln_stats_out, ln_stats_eps);
-  return launch_mlp<288, 2>(xf, x_ld, gamma, beta, eps, w_packed, b2, rows, s, ln_stats_out, ln_stats_eps);
-}
-
-extern "C" int CVMI_ENTRY(cvmi_hiera_mlp)(void* x, int x_ld, const float* gamma, const float* beta, float eps, const void* w_packed, const float* b2,
-                                          long long rows, int C, int dtype, cvmi_stream_t stream_) {
-  return CVMI_ENTRY(cvmi_hiera_mlp_stats)(x, x_ld, gamma, beta, eps, w_packed, b2, rows, C, dtype, nullptr, 0.f, stream_, nullptr);
+  if (pipe && !(atoi(pipe) & 2)) return launch_mlp<288, 0>(*d, s);
+  return launch_mlp<288, 2>(*d, s);
 }

@@ -37,6 +37,8 @@ extern "C" size_t cvmi_desc_size(int kind) {
     case CVMI_DESC_C3K2: return sizeof(cvmi_c3k2_desc);
     case CVMI_DESC_DWPW: return sizeof(cvmi_dwpw_desc);
     case CVMI_DESC_ATTN: return sizeof(cvmi_attn_desc);
+    case CVMI_DESC_TOK: return sizeof(cvmi_tok_desc);
+    case CVMI_DESC_MLP: return sizeof(cvmi_mlp_desc);
     default: return 0;
   }
 }

@@ -168,27 +168,26 @@ __global__ __launch_bounds__((MlpCfg<C, VAR>::NW * 64), (MlpCfg<C, VAR>::WPS)) v
 }
 
 template <int C, int VAR>
-int launch_proj_mlp(float* x, int x_ld, const cvmi_mlp_proj* pj, const float* gamma, const float* beta, float eps, const float* b2, long long rows, hipStream_t s,
-                    float* stats_out, float stats_eps) {
+int launch_proj_mlp(const cvmi_mlp_desc& d, hipStream_t s) {
   using Cfg = MlpCfg<C, VAR>;
   static hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&proj_mlp_kernel<C, VAR>), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS);
   CVMI_HIP(attr);
   const long long per = (long long)Cfg::NW * 32;
   cvmi_note_kernel("proj_mlp_kernel<%d, %d>", C, VAR);
-  hipLaunchKernelGGL((proj_mlp_kernel<C, VAR>), dim3((unsigned)((rows + per - 1) / per)), dim3(Cfg::NW * 64), Cfg::LDS, s, x, x_ld, (const f16*)pj->ao, pj->ao_ld,
-                     (const char*)pj->w_packed, pj->bp, gamma, beta, eps, b2, rows, stats_out, stats_eps);
+  hipLaunchKernelGGL((proj_mlp_kernel<C, VAR>), dim3((unsigned)((d.rows + per - 1) / per)), dim3(Cfg::NW * 64), Cfg::LDS, s, (float*)d.x, d.x_ld, (const f16*)d.ao,
+                     d.ao_ld, (const char*)d.w_packed, d.bp, d.gamma, d.beta, d.eps, d.b2, d.rows, d.ln_stats_out, d.ln_stats_eps);
   CVMI_LAUNCH_CHECK();
   return 0;
 }
 
-// the proj form of cvmi_hiera_mlp_stats (x, gamma, beta, b2, rows, C in {144, 288}, the dtype and ln_stats_out are checked by the caller)
-int proj_mlp_dispatch(float* x, int x_ld, const cvmi_mlp_proj* pj, const float* gamma, const float* beta, float eps, const float* b2, long long rows, int C,
-                      hipStream_t s, float* stats_out, float stats_eps) {
-  CVMI_CHECK(pj->ao && pj->w_packed && pj->bp, "proj_mlp: needs ao, the packed weights and bp");
-  CVMI_CHECK((((uintptr_t)pj->ao | (uintptr_t)pj->w_packed | (uintptr_t)pj->bp) & 15) == 0, "proj_mlp: ao / weights / bp are not aligned to 16 bytes");
-  CVMI_CHECK(pj->ao_ld >= C && pj->ao_ld % 8 == 0, "proj_mlp: ao_ld=%d must be >= C and a multiple of 8", pj->ao_ld);
-  if (C == 144) return launch_proj_mlp<144, 1>(x, x_ld, pj, gamma, beta, eps, b2, rows, s, stats_out, stats_eps);
-  return launch_proj_mlp<288, 2>(x, x_ld, pj, gamma, beta, eps, b2, rows, s, stats_out, stats_eps);
+// the proj form of cvmi_hiera_mlp (x, gamma, beta, b2, rows, C in {144, 288}, the dtype and ln_stats_out are checked by the caller)
+int proj_mlp_dispatch(const cvmi_mlp_desc& d, hipStream_t s) {
+  CVMI_CHECK(d.ao && d.w_packed && d.bp, "proj_mlp: needs ao, the packed weights and bp");
+  CVMI_CHECK((((uintptr_t)d.ao | (uintptr_t)d.w_packed | (uintptr_t)d.bp) & 15) == 0, "proj_mlp: ao / weights / bp are not aligned to 16 bytes");
+  const int C = d.C;
+  CVMI_CHECK(d.ao_ld >= C && d.ao_ld % 8 == 0, "proj_mlp: ao_ld=%d must be >= C and a multiple of 8", d.ao_ld);
+  if (C == 144) return launch_proj_mlp<144, 1>(d, s);
+  return launch_proj_mlp<288, 2>(d, s);
 }
 
 }  // namespace

@@ -144,43 +144,41 @@ __global__ __launch_bounds__(TL_NW * 64, 2) void tok_linear_kernel(const void* _
 }
 
 template <int K, int LN, bool RES, bool GELU, bool TSTORE, bool POOL = false>
-int launch_tl1(const void* in, int in_ld, const float* gamma, const float* beta, float eps, const void* wp, void* out, int out_ld, long long rows,
-              int N, hipStream_t s, const TlExtra& ex) {
+int launch_tl1(const cvmi_tok_desc& d, hipStream_t s, const TlExtra& ex) {
   using Cfg = TlCfg<K>;
   static hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&tok_linear_kernel<K, LN, RES, GELU, TSTORE, POOL>), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS);
   CVMI_HIP(attr);
   cvmi_note_kernel("tok_linear_kernel<%d, %d, %s, %s, %s, %s>", K, LN, CVMI_BOOLNAME(RES), CVMI_BOOLNAME(GELU), CVMI_BOOLNAME(TSTORE), CVMI_BOOLNAME(POOL));
-  hipLaunchKernelGGL((tok_linear_kernel<K, LN, RES, GELU, TSTORE, POOL>), dim3((unsigned)(rows / 256)), dim3(TL_NW * 64), Cfg::LDS, s, in, in_ld, gamma, beta, eps,
-                     (const char*)wp, out, out_ld, rows, N, ex);
+  hipLaunchKernelGGL((tok_linear_kernel<K, LN, RES, GELU, TSTORE, POOL>), dim3((unsigned)(d.rows / 256)), dim3(TL_NW * 64), Cfg::LDS, s, d.in, d.in_ld, d.gamma, d.beta,
+                     d.eps, (const char*)d.w_packed, d.out, d.out_ld, d.rows, d.N, ex);
   CVMI_LAUNCH_CHECK();
   return 0;
 }
 
 template <int K, int LN, bool RES, bool GELU>
-int launch_tl(const void* in, int in_ld, const float* gamma, const float* beta, float eps, const void* wp, void* out, int out_ld, long long rows,
-              int N, hipStream_t s, const TlExtra& ex) {
+int launch_tl(const cvmi_tok_desc& d, hipStream_t s, const TlExtra& ex) {
   // TSTORE: chunks leave through the wave's LDS stage as whole 64-byte row pieces; the residual form and unaligned outputs store directly
   if constexpr (!RES) {
-    if (N % 8 == 0 && out_ld % 8 == 0) return launch_tl1<K, LN, RES, GELU, true>(in, in_ld, gamma, beta, eps, wp, out, out_ld, rows, N, s, ex);
+    if (d.N % 8 == 0 && d.out_ld % 8 == 0) return launch_tl1<K, LN, RES, GELU, true>(d, s, ex);
   }
-  return launch_tl1<K, LN, RES, GELU, false>(in, in_ld, gamma, beta, eps, wp, out, out_ld, rows, N, s, ex);
+  return launch_tl1<K, LN, RES, GELU, false>(d, s, ex);
 }
 
 template <int K>
-int dispatch_tl(int ln, bool res, int act, const void* in, int in_ld, const float* gamma, const float* beta, float eps, const void* wp, void* out,
-                int out_ld, long long rows, int N, hipStream_t s, const TlExtra& ex) {
-  if (ln == 2) return launch_tl<K, 2, false, false>(in, in_ld, gamma, beta, eps, wp, out, out_ld, rows, N, s, ex);
+int dispatch_tl(const cvmi_tok_desc& d, hipStream_t s, const TlExtra& ex) {
+  const int ln = d.in_f32_layernorm, act = d.act;
+  const bool res = d.out_f32_residual != 0;
+  if (ln == 2) return launch_tl<K, 2, false, false>(d, s, ex);
   return tok_dispatch(ln != 0, res, act == CVMI_ACT_GELU, [&](auto LN, auto RES, auto GELU) {
-    return launch_tl<K, decltype(LN)::value, decltype(RES)::value, decltype(GELU)::value>(in, in_ld, gamma, beta, eps, wp, out, out_ld, rows, N, s, ex);
+    return launch_tl<K, decltype(LN)::value, decltype(RES)::value, decltype(GELU)::value>(d, s, ex);
   });
 }
 
 }  // namespace
 
 // K = 576 is served by tok_linear16.hip (16x16x32 MFMA shape, its own packed-weight format)
-int CVMI_ENTRY(cvmi_tok_linear16_launch)(int K, int ln, bool res, bool gelu, const void* in, int in_ld, const float* gamma, const float* beta, float eps,
-                                         const void* wp, void* out, int out_ld, long long rows, int N, int pool_w, int pool_hw2, const float* stats_in,
-                                         int stats_parts, float* stats_out, float stats_eps, hipStream_t s);
+int CVMI_ENTRY(cvmi_tok_linear16_launch)(const cvmi_tok_desc& d, hipStream_t s, const TlExtra& ex);
+int CVMI_ENTRY(cvmi_tok_linear16_shares)(const cvmi_tok_desc& d);
 static int tl_format(int K) { return K == 576 ? 16 : 32; }
 
 #ifndef CVMI_OPERAND_BF16
@@ -199,91 +197,75 @@ extern "C" size_t cvmi_tok_linear_packed_bytes(int K, int N) {
   if (tl_format(K) == 16) return (size_t)((N + 31) / 32) * (size_t)(K / 16 + 1) * 1024;     // 2 K/32 weight fragments + the bias piece per chunk
   return (size_t)(((N + 31) / 32 + 1) / 2 * 2) * (size_t)(K / 16 + 1) * 1024;        // chunk count padded to even
 }
-extern "C" int cvmi_tok_linear_stats_bf16(const void* in, int in_ld, int in_f32_layernorm, const float* gamma, const float* beta, float eps,
-                                          const void* w_packed, void* out, int out_ld, int out_f32_residual, long long rows, int K, int N, int act,
-                                          int dtype, const float* ln_stats_in, int ln_stats_in_parts, float* ln_stats_out, float ln_stats_eps, cvmi_stream_t stream_);
+extern "C" int cvmi_tok_linear_bf16(const cvmi_tok_desc* d, cvmi_stream_t stream_);
 #endif
 
-// cvmi_tok_linear with LayerNorm statistics handed from the launch that WRITES the residual stream to the launch that normalises it:
-//   ln_stats_out (out_f32_residual = 1): float2 per row = (mean, 1 / sqrt(var + ln_stats_eps)) over the N updated values of the row
-//   ln_stats_in  (in_f32_layernorm = 1): the same pair per row; the prologue then reads every row once instead of twice.
-//                ln_stats_in_parts = P > 0: instead P per column slice (mean, sum of squared deviations) pairs per row, as cvmi_conv_desc.row_stats writes them
-// (x = x + proj(attn) followed by mlp.layers[0](norm2(x)) in sam2 hieradet MultiScaleBlock; behind /root/reference/src/sam2_infer.py:226).
-extern "C" int CVMI_ENTRY(cvmi_tok_linear_stats)(const void* in, int in_ld, int in_f32_layernorm, const float* gamma, const float* beta, float eps,
-                                                 const void* w_packed, void* out, int out_ld, int out_f32_residual, long long rows, int K, int N, int act,
-                                                 int dtype, const float* ln_stats_in, int ln_stats_in_parts, float* ln_stats_out, float ln_stats_eps, cvmi_stream_t stream_) {
-#ifndef CVMI_OPERAND_BF16
-  if (dtype == CVMI_BF16)
-    return cvmi_tok_linear_stats_bf16(in, in_ld, in_f32_layernorm, gamma, beta, eps, w_packed, out, out_ld, out_f32_residual, rows, K, N, act, dtype,
-                                      ln_stats_in, ln_stats_in_parts, ln_stats_out, ln_stats_eps, stream_);
-#endif
-  CVMI_CHECK(dtype == CVMI_T16, "tok_linear: dtype must be CVMI_F16 or CVMI_BF16");
-  CVMI_CHECK(in && w_packed && out && rows > 0 && rows % 256 == 0 && N > 0, "tok_linear: bad arguments (rows must be a multiple of 256)");
-  CVMI_CHECK(K == 144 || K == 288 || K == 576, "tok_linear: K=%d is not built (144, 288, 576)", K);
-  CVMI_CHECK(in_f32_layernorm != 1 || (gamma && beta), "tok_linear: LayerNorm input needs gamma / beta");
-  CVMI_CHECK(in_f32_layernorm >= 0 && in_f32_layernorm <= 2 && (in_f32_layernorm != 2 || (!out_f32_residual && act == CVMI_ACT_NONE)),
-             "tok_linear: in_f32_layernorm must be 0, 1 or 2 (2: 16-bit output, no activation)");
-  CVMI_CHECK(act == CVMI_ACT_NONE || (act == CVMI_ACT_GELU && !out_f32_residual), "tok_linear: act must be NONE, or GELU with 16-bit output");
-  CVMI_CHECK(in_ld >= K && in_ld % (in_f32_layernorm ? 4 : 8) == 0 && out_ld >= N && out_ld % 4 == 0 && N % 4 == 0 &&
-                 (((uintptr_t)in | (uintptr_t)w_packed | (uintptr_t)out) & 15) == 0 &&
-                 (in_f32_layernorm != 1 || (((uintptr_t)gamma | (uintptr_t)beta) & 15) == 0),
-             "tok_linear: pointers / ld not aligned (in_ld=%d out_ld=%d N=%d)", in_ld, out_ld, N);
-  CVMI_CHECK((!ln_stats_in || in_f32_layernorm == 1) && (!ln_stats_out || out_f32_residual) && (((uintptr_t)ln_stats_in | (uintptr_t)ln_stats_out) & 7) == 0,
+namespace {
+
+// The plain form (pool_h = pool_w = 0) of cvmi_tok_desc, checked before any launch; the field documentation is in include/cvmi355.h.
+int check_tok(const cvmi_tok_desc& d) {
+  const int ln = d.in_f32_layernorm;
+  const bool res = d.out_f32_residual != 0;
+  CVMI_CHECK(d.in && d.w_packed && d.out && d.rows > 0 && d.rows % 256 == 0 && d.N > 0, "tok_linear: bad arguments (rows must be a multiple of 256)");
+  CVMI_CHECK(d.K == 144 || d.K == 288 || d.K == 576, "tok_linear: K=%d is not built (144, 288, 576)", d.K);
+  CVMI_CHECK(ln != 1 || (d.gamma && d.beta), "tok_linear: LayerNorm input needs gamma / beta");
+  CVMI_CHECK(ln >= 0 && ln <= 2 && (ln != 2 || (!res && d.act == CVMI_ACT_NONE)), "tok_linear: in_f32_layernorm must be 0, 1 or 2 (2: 16-bit output, no activation)");
+  CVMI_CHECK(d.act == CVMI_ACT_NONE || (d.act == CVMI_ACT_GELU && !res), "tok_linear: act must be NONE, or GELU with 16-bit output");
+  CVMI_CHECK((!d.ln_stats_in || ln == 1) && (!d.ln_stats_out || res) && (((uintptr_t)d.ln_stats_in | (uintptr_t)d.ln_stats_out) & 7) == 0,
              "tok_linear: ln_stats_in needs the LayerNorm input form, ln_stats_out the residual output form (8-byte aligned)");
-  CVMI_CHECK(ln_stats_in_parts >= 0 && ln_stats_in_parts <= 64, "tok_linear: ln_stats_in_parts out of range");
-  hipStream_t s = (hipStream_t)stream_;
-  const int ln = in_f32_layernorm;
-  const bool res = out_f32_residual != 0;
-  CVMI_CHECK(ln != 2 || tl_format(K) != 16, "tok_linear: plain f32 input (in_f32_layernorm = 2) is built for K = 144 and 288");
-  if (tl_format(K) == 16)
-    return CVMI_ENTRY(cvmi_tok_linear16_launch)(K, ln, res, act == CVMI_ACT_GELU, in, in_ld, gamma, beta, eps, w_packed, out, out_ld, rows, N, 0, 0, ln_stats_in,
-                                                ln_stats_in_parts, ln_stats_out, ln_stats_eps, s);
-  const TlExtra ex{0, 0, ln_stats_in, ln_stats_out, ln_stats_eps, ln_stats_in_parts};
-  if (K == 144) return dispatch_tl<144>(ln, res, act, in, in_ld, gamma, beta, eps, w_packed, out, out_ld, rows, N, s, ex);
-  return dispatch_tl<288>(ln, res, act, in, in_ld, gamma, beta, eps, w_packed, out, out_ld, rows, N, s, ex);
+  // The layout of ln_stats_out is the launch's to decide (row-block sharing writes per-slice pairs): the caller states the one it allocated
+  const int writes = cvmi_tok_linear_stats_parts(d.rows, d.K, d.N);
+  CVMI_CHECK(!d.ln_stats_out || d.ln_stats_out_parts == writes,
+             "tok_linear: ln_stats_out_parts=%d, but this launch writes ln_stats_out in %d parts (cvmi_tok_linear_stats_parts)", d.ln_stats_out_parts, writes);
+  // Workgroups that share a row block each normalise all of its rows and update their own channel slice of them: in place, one would read what another wrote
+  if (ln == 1 && res && tl_format(d.K) == 16 && CVMI_ENTRY(cvmi_tok_linear16_shares)(d) > 1) {
+    const uintptr_t in0 = (uintptr_t)d.in, out0 = (uintptr_t)d.out;
+    const uintptr_t in1 = in0 + (uintptr_t)d.rows * (uintptr_t)d.in_ld * 4, out1 = out0 + (uintptr_t)d.rows * (uintptr_t)d.out_ld * 4;
+    CVMI_CHECK(in1 <= out0 || out1 <= in0, "tok_linear: LayerNorm input and residual output overlap in a launch whose workgroups share row blocks");
+  }
+  CVMI_CHECK(d.in_ld >= d.K && d.in_ld % (ln ? 4 : 8) == 0 && d.out_ld >= d.N && d.out_ld % 4 == 0 && d.N % 4 == 0 &&
+                 (((uintptr_t)d.in | (uintptr_t)d.w_packed | (uintptr_t)d.out) & 15) == 0 && (ln != 1 || (((uintptr_t)d.gamma | (uintptr_t)d.beta) & 15) == 0),
+             "tok_linear: pointers / ld not aligned (in_ld=%d out_ld=%d N=%d)", d.in_ld, d.out_ld, d.N);
+  CVMI_CHECK(d.ln_stats_in_parts >= 0 && d.ln_stats_in_parts <= 64, "tok_linear: ln_stats_in_parts out of range");
+  CVMI_CHECK(ln != 2 || tl_format(d.K) != 16, "tok_linear: plain f32 input (in_f32_layernorm = 2) is built for K = 144 and 288");
+  return 0;
 }
 
-extern "C" int CVMI_ENTRY(cvmi_tok_linear)(const void* in, int in_ld, int in_f32_layernorm, const float* gamma, const float* beta, float eps,
-                                           const void* w_packed, void* out, int out_ld, int out_f32_residual, long long rows, int K, int N, int act,
-                                           int dtype, cvmi_stream_t stream_) {
-  return CVMI_ENTRY(cvmi_tok_linear_stats)(in, in_ld, in_f32_layernorm, gamma, beta, eps, w_packed, out, out_ld, out_f32_residual, rows, K, N, act, dtype,
-                                           nullptr, 0, nullptr, 0.f, stream_);
-}
-
-#ifndef CVMI_OPERAND_BF16
-extern "C" int cvmi_tok_linear_pool_stats_bf16(const void* in, int in_ld, const float* gamma, const float* beta, float eps, const void* w_packed, void* out,
-                                               int out_ld, int B, int H, int W, int K, int N, int dtype, const float* ln_stats_in, cvmi_stream_t stream_);
-#endif
-
-// out[b, y, x, :] = max over the 2 x 2 token block of ( LayerNorm(in[b, 2y + dy, 2x + dx, :]) W^T + bias ): the shortcut path of a Hiera
+// The pool form: out[b, y, x, :] = max over the 2 x 2 token block of ( LayerNorm(in[b, 2y + dy, 2x + dx, :]) W^T + bias ): the shortcut path of a Hiera
 // q-pooling block, `do_pool(self.proj(x_norm))` (sam2 hieradet MultiScaleBlock.forward, behind /root/reference/src/sam2_infer.py:226), in one
 // launch -- the full-resolution f32 projection (1.2 GB at the stage 1 -> 2 transition, B = 16) is neither written nor read back.
-// ln_stats_in (may be NULL): per source row (mean, rstd) as written by cvmi_hiera_mlp_stats / cvmi_tok_linear_stats -- one pass over the rows.
-extern "C" int CVMI_ENTRY(cvmi_tok_linear_pool_stats)(const void* in, int in_ld, const float* gamma, const float* beta, float eps, const void* w_packed,
-                                                      void* out, int out_ld, int B, int H, int W, int K, int N, int dtype, const float* ln_stats_in,
-                                                      cvmi_stream_t stream_) {
-#ifndef CVMI_OPERAND_BF16
-  if (dtype == CVMI_BF16)
-    return cvmi_tok_linear_pool_stats_bf16(in, in_ld, gamma, beta, eps, w_packed, out, out_ld, B, H, W, K, N, dtype, ln_stats_in, stream_);
-#endif
-  CVMI_CHECK(dtype == CVMI_T16, "tok_linear_pool: dtype must be CVMI_F16 or CVMI_BF16");
-  const long long rows = (long long)B * H * W;
-  CVMI_CHECK(in && w_packed && out && gamma && beta && B > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0 && rows % 256 == 0 && N > 0,
+int check_tok_pool(const cvmi_tok_desc& d) {
+  const int H = d.pool_h, W = d.pool_w;
+  CVMI_CHECK(d.in && d.w_packed && d.out && d.gamma && d.beta && d.rows > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0 && d.rows % ((long long)H * W) == 0 &&
+                 d.rows % 256 == 0 && d.N > 0,
              "tok_linear_pool: bad arguments (H, W even; B*H*W a multiple of 256)");
-  CVMI_CHECK(K == 144 || K == 288 || K == 576, "tok_linear_pool: K=%d is not built (144, 288, 576)", K);
-  CVMI_CHECK(in_ld >= K && in_ld % 4 == 0 && out_ld >= N && out_ld % 4 == 0 && N % 4 == 0 &&
-                 (((uintptr_t)in | (uintptr_t)w_packed | (uintptr_t)out | (uintptr_t)gamma | (uintptr_t)beta) & 15) == 0,
-             "tok_linear_pool: pointers / ld not aligned (in_ld=%d out_ld=%d N=%d)", in_ld, out_ld, N);
-  hipStream_t s = (hipStream_t)stream_;
-  const int hw2 = (H / 2) * (W / 2);
-  if (tl_format(K) == 16)
-    return CVMI_ENTRY(cvmi_tok_linear16_launch)(K, 1, false, false, in, in_ld, gamma, beta, eps, w_packed, out, out_ld, rows, N, W, hw2, ln_stats_in, 0, nullptr, 0.f, s);
-  const TlExtra ex{W, hw2, ln_stats_in, nullptr, 0.f, 0};
-  if (K == 144) return launch_tl1<144, 1, false, false, false, true>(in, in_ld, gamma, beta, eps, w_packed, out, out_ld, rows, N, s, ex);
-  return launch_tl1<288, 1, false, false, false, true>(in, in_ld, gamma, beta, eps, w_packed, out, out_ld, rows, N, s, ex);
+  CVMI_CHECK(d.in_f32_layernorm == 1 && !d.out_f32_residual && d.act == CVMI_ACT_NONE && !d.ln_stats_out && d.ln_stats_in_parts == 0,
+             "tok_linear_pool: the pool form takes the LayerNorm input form and writes f32: no residual, activation, ln_stats_out or ln_stats_in_parts");
+  CVMI_CHECK(d.K == 144 || d.K == 288 || d.K == 576, "tok_linear_pool: K=%d is not built (144, 288, 576)", d.K);
+  CVMI_CHECK(d.in_ld >= d.K && d.in_ld % 4 == 0 && d.out_ld >= d.N && d.out_ld % 4 == 0 && d.N % 4 == 0 &&
+                 (((uintptr_t)d.in | (uintptr_t)d.w_packed | (uintptr_t)d.out | (uintptr_t)d.gamma | (uintptr_t)d.beta) & 15) == 0,
+             "tok_linear_pool: pointers / ld not aligned (in_ld=%d out_ld=%d N=%d)", d.in_ld, d.out_ld, d.N);
+  return 0;
 }
 
-extern "C" int CVMI_ENTRY(cvmi_tok_linear_pool)(const void* in, int in_ld, const float* gamma, const float* beta, float eps, const void* w_packed,
-                                                void* out, int out_ld, int B, int H, int W, int K, int N, int dtype, cvmi_stream_t stream_) {
-  return CVMI_ENTRY(cvmi_tok_linear_pool_stats)(in, in_ld, gamma, beta, eps, w_packed, out, out_ld, B, H, W, K, N, dtype, nullptr, stream_);
+}  // namespace
+
+extern "C" int CVMI_ENTRY(cvmi_tok_linear)(const cvmi_tok_desc* d, cvmi_stream_t stream_) {
+  CVMI_CHECK(d, "tok_linear: null descriptor");
+#ifndef CVMI_OPERAND_BF16
+  if (d->dtype == CVMI_BF16) return cvmi_tok_linear_bf16(d, stream_);
+#endif
+  const bool pool = d->pool_h != 0 || d->pool_w != 0;
+  CVMI_CHECK(d->dtype == CVMI_T16, pool ? "tok_linear_pool: dtype must be CVMI_F16 or CVMI_BF16" : "tok_linear: dtype must be CVMI_F16 or CVMI_BF16");
+  if (const int rc = pool ? check_tok_pool(*d) : check_tok(*d)) return rc;
+  hipStream_t s = (hipStream_t)stream_;
+  const int K = d->K;
+  const TlExtra ex{d->pool_w, (d->pool_h / 2) * (d->pool_w / 2), d->ln_stats_in, d->ln_stats_out, d->ln_stats_eps, d->ln_stats_in_parts};
+  if (tl_format(K) == 16) return CVMI_ENTRY(cvmi_tok_linear16_launch)(*d, s, ex);
+  if (!pool) {                                                // (first: the code object lists the kernels in the order this function names them)
+    if (K == 144) return dispatch_tl<144>(*d, s, ex);
+    return dispatch_tl<288>(*d, s, ex);
+  }
+  if (K == 144) return launch_tl1<144, 1, false, false, false, true>(*d, s, ex);
+  return launch_tl1<288, 1, false, false, false, true>(*d, s, ex);
 }

@@ -247,15 +247,16 @@ int tl16_splits(long long rows, int N, bool stats_out) {
 }
 
 template <int K, int LN, bool RES, bool GELU, bool POOL>
-int launch16(const void* in, int in_ld, const float* gamma, const float* beta, float eps, const void* wp, void* out, int out_ld, long long rows, int N,
-             hipStream_t s, const TlExtra& ex) {
+int launch16(const cvmi_tok_desc& d, hipStream_t s, const TlExtra& ex) {
   using Cfg = Tl16Cfg<K>;
+  const long long rows = d.rows;
+  const int N = d.N;
   static hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&tok_linear16_kernel<K, LN, RES, GELU, POOL>), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS);
   CVMI_HIP(attr);
   cvmi_note_kernel("tok_linear16_kernel<%d, %d, %s, %s, %s>", K, LN, CVMI_BOOLNAME(RES), CVMI_BOOLNAME(GELU), CVMI_BOOLNAME(POOL));
   const int ns = tl16_splits(rows, N, RES && ex.stats_out != nullptr);
-  hipLaunchKernelGGL((tok_linear16_kernel<K, LN, RES, GELU, POOL>), dim3((unsigned)(rows / 256), (unsigned)ns), dim3(TL_NW * 64), Cfg::LDS, s, in, in_ld, gamma, beta, eps,
-                     (const char*)wp, out, out_ld, rows, N, ex);
+  hipLaunchKernelGGL((tok_linear16_kernel<K, LN, RES, GELU, POOL>), dim3((unsigned)(rows / 256), (unsigned)ns), dim3(TL_NW * 64), Cfg::LDS, s, d.in, d.in_ld, d.gamma, d.beta, d.eps,
+                     (const char*)d.w_packed, d.out, d.out_ld, rows, N, ex);
   CVMI_LAUNCH_CHECK();
   return 0;
 }
@@ -265,16 +266,18 @@ int launch16(const void* in, int in_ld, const float* gamma, const float* beta, f
 // cvmi_tok_linear_stats_parts (tok_linear.hip): the slice count of the statistics a residual-form launch of this shape writes
 int CVMI_ENTRY(cvmi_tok_linear16_splits)(long long rows, int N) { return tl16_splits(rows, N, true); }
 
-// Called by the cvmi_tok_linear* entry points (tok_linear.hip) for the K served in the 16x16x32 format (cvmi_tok_linear_format).  Arguments are
-// already validated there.  pool_w > 0 selects the POOL form.
-int CVMI_ENTRY(cvmi_tok_linear16_launch)(int K, int ln, bool res, bool gelu, const void* in, int in_ld, const float* gamma, const float* beta, float eps,
-                                         const void* wp, void* out, int out_ld, long long rows, int N, int pool_w, int pool_hw2, const float* stats_in,
-                                         int stats_parts, float* stats_out, float stats_eps, hipStream_t s) {
+// The alias refusal of cvmi_tok_linear (tok_linear.hip): how many workgroups share a row block of the launch this descriptor asks for
+int CVMI_ENTRY(cvmi_tok_linear16_shares)(const cvmi_tok_desc& d) { return tl16_splits(d.rows, d.N, d.out_f32_residual && d.ln_stats_out != nullptr); }
+
+// Called by cvmi_tok_linear (tok_linear.hip) for the K served in the 16x16x32 format (cvmi_tok_linear_format).  The descriptor is
+// already validated there.  ex.pool_w > 0 selects the POOL form.
+int CVMI_ENTRY(cvmi_tok_linear16_launch)(const cvmi_tok_desc& d, hipStream_t s, const TlExtra& ex) {
+  const int K = d.K, ln = d.in_f32_layernorm, N = d.N, out_ld = d.out_ld, pool_w = ex.pool_w;
+  const bool res = d.out_f32_residual != 0, gelu = d.act == CVMI_ACT_GELU;
   CVMI_CHECK(K == 576, "tok_linear (16x16x32 format): K=%d is not built", K);
-  const TlExtra ex{pool_w, pool_hw2, stats_in, stats_out, stats_eps, stats_parts};
-  if (pool_w > 0) return launch16<576, 1, false, false, true>(in, in_ld, gamma, beta, eps, wp, out, out_ld, rows, N, s, ex);
+  if (pool_w > 0) return launch16<576, 1, false, false, true>(d, s, ex);
   CVMI_CHECK(res || (N % 8 == 0 && out_ld % 8 == 0), "tok_linear (16x16x32 format): 16-bit output needs N and out_ld multiples of 8");
   return tok_dispatch(ln != 0, res, gelu, [&](auto LN, auto RES, auto GELU) {
-    return launch16<576, decltype(LN)::value, decltype(RES)::value, decltype(GELU)::value, false>(in, in_ld, gamma, beta, eps, wp, out, out_ld, rows, N, s, ex);
+    return launch16<576, decltype(LN)::value, decltype(RES)::value, decltype(GELU)::value, false>(d, s, ex);
   });
 }

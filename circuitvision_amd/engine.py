@@ -285,19 +285,11 @@ def op_conv(plan, label, pc, srcs, dst, stride=1, pad=None, act=_lib.ACT_NONE, r
         row_stats=(row_stats.data_ptr() if row_stats is not None else None), res_map=(res_map.data_ptr() if res_map is not None else None))
     if row_stats is not None:       # f32 [rows, N / 96, 2]: (mean, sum of squared deviations) per 96-column slice of every written row (Hiera stage-3 fc2 shape only)
         assert row_stats.dtype == torch.float32 and row_stats.is_contiguous() and row_stats.numel() == v0.B * OH * OW * (pc.N // 96) * 2, label
-    plan.keep.append((d, pc, srcs, dst, res, row_stats, res_map))
-    sp0 = plan.sptr
-    fn = lib.cvmi_conv2d
-
-    def thunk(sp=None):
-        sp = sp0 if sp is None else sp
-        _lib.check(fn(C.byref(d), sp), label)
-
     M = v0.B * OH * OW
     es, oes = ESIZE[pc.dtype], ESIZE[dst.dtype]
     in_elems = v0.B * (v0.H * v0.W * v0.c + (v1.H * v1.W * v1.c if v1 is not None else 0))
     bytes_ = in_elems * es + M * pc.N * oes + (M * pc.N * oes if res is not None else 0)
-    plan.add(label, kind, thunk, bytes_, 2 * M * pc.N * pc.K)
+    op_call(plan, label, kind, lib.cvmi_conv2d, (C.byref(d),), (d, pc, srcs, dst, res, row_stats, res_map), bytes_, 2 * M * pc.N * pc.K)
     return d
 
 
@@ -315,16 +307,9 @@ def op_c3k2(plan, label, src, dst, pc_cv1, pc_m1, pc_m2, pc_cv2, c, h, fuse_cv1,
                  b3=pc_cv2.bias.data_ptr(), x_ld=src.ld, y_ld=dst.ld, kpad0=pc_cv1.Kpad if fuse_cv1 else 0, kpad1=pc_m1.Kpad, kpad2=pc_m2.Kpad,
                  kpad3=pc_cv2.Kpad, B=src.B, H=src.H, W=src.W, c1=pc_cv1.Cin if fuse_cv1 else 0, c=c, h=h, c2=pc_cv2.N,
                  fuse_cv1=1 if fuse_cv1 else 0, shortcut=1 if shortcut else 0, dtype=pc_cv2.dtype)
-    plan.keep.append((d, src, dst, pc_cv1, pc_m1, pc_m2, pc_cv2))
-    sp0, fn = plan.sptr, lib.cvmi_c3k2
-
-    def thunk(sp=None):
-        sp = sp0 if sp is None else sp
-        _lib.check(fn(C.byref(d), sp), label)
-
     px = src.B * src.H * src.W
     flops = 2 * px * ((pc_cv1.Cin * 2 * c if fuse_cv1 else 0) + 9 * c * h * 2 + 3 * c * pc_cv2.N)
-    plan.add(label, "conv", thunk, px * (src.c + dst.c) * ESIZE[pc_cv2.dtype], flops)
+    op_call(plan, label, "conv", lib.cvmi_c3k2, (C.byref(d),), (d, src, dst, pc_cv1, pc_m1, pc_m2, pc_cv2), px * (src.c + dst.c) * ESIZE[pc_cv2.dtype], flops)
 
 
 def stem2_supported(c0, c1, dtype):
@@ -338,15 +323,8 @@ def op_stem2(plan, label, pc0, pc1, src, dst):
     assert (dst.H, dst.W) == ((src.H - 1) // 2 + 1, (src.W - 1) // 2 + 1) and dst.B == src.B
     args = (src.ptr, src.ld, pc0.w.data_ptr(), pc0.bias.data_ptr(), pc0.Kpad, pc1.w.data_ptr(), pc1.bias.data_ptr(), pc1.Kpad,
             dst.ptr, dst.ld, src.B, src.H, src.W, pc0.N, pc1.N, pc1.dtype)
-    plan.keep.append((pc0, pc1, src, dst))
-    sp0, fn = plan.sptr, lib.cvmi_stem2
-
-    def thunk(sp=None):
-        sp = sp0 if sp is None else sp
-        _lib.check(fn(*args, sp), label)
-
     px0, px1 = src.B * src.H * src.W, dst.B * dst.H * dst.W
-    plan.add(label, "stem", thunk, (px0 * src.c + px1 * dst.c) * ESIZE[pc1.dtype], 2 * px0 * 27 * pc0.N + 2 * px1 * 9 * pc0.N * pc1.N)
+    op_call(plan, label, "stem", lib.cvmi_stem2, args, (pc0, pc1, src, dst), (px0 * src.c + px1 * dst.c) * ESIZE[pc1.dtype], 2 * px0 * 27 * pc0.N + 2 * px1 * 9 * pc0.N * pc1.N)
 
 
 def dwpw_supported(C_, n1, n2, dtype):
@@ -362,16 +340,9 @@ def op_dwpw(plan, label, pd, pc1, src, dst, pc2=None):
                       w2=pc2.w.data_ptr() if pc2 is not None else None, b2=pc2.bias.data_ptr() if pc2 is not None else None,
                       x_ld=src.ld, y_ld=dst.ld, kpad1=pc1.Kpad, kpad2=pc2.Kpad if pc2 is not None else 0,
                       B=src.B, H=src.H, W=src.W, C=pd.C, N1=pc1.N, N2=pc2.N if pc2 is not None else 0, dtype=pc1.dtype)
-    plan.keep.append((d, pd, pc1, pc2, src, dst))
-    sp0, fn = plan.sptr, lib.cvmi_dwpw
-
-    def thunk(sp=None):
-        sp = sp0 if sp is None else sp
-        _lib.check(fn(C.byref(d), sp), label)
-
     px = src.B * src.H * src.W
     flops = px * (18 * pd.C + 2 * pd.C * pc1.N + (2 * pc1.N * pc2.N if pc2 is not None else 0))
-    plan.add(label, "head", thunk, px * (src.c + dst.c) * ESIZE[pc1.dtype], flops)
+    op_call(plan, label, "head", lib.cvmi_dwpw, (C.byref(d),), (d, pd, pc1, pc2, src, dst), px * (src.c + dst.c) * ESIZE[pc1.dtype], flops)
 
 
 def op_dwconv(plan, label, pd, src, dst, act=_lib.ACT_NONE, res=None):
@@ -379,44 +350,19 @@ def op_dwconv(plan, label, pd, src, dst, act=_lib.ACT_NONE, res=None):
     assert src.c == pd.C == dst.c and (src.B, src.H, src.W) == (dst.B, dst.H, dst.W)
     args = (src.ptr, src.ld, pd.w.data_ptr(), pd.bias.data_ptr(), res.ptr if res is not None else None,
             res.ld if res is not None else 0, dst.ptr, dst.ld, src.B, src.H, src.W, pd.C, act, pd.dtype)
-    plan.keep.append((pd, src, dst, res))
-    sp0 = plan.sptr
-    fn = lib.cvmi_dwconv3x3
-
-    def thunk(sp=None):
-        sp = sp0 if sp is None else sp
-        _lib.check(fn(*args, sp), label)
-
     n = src.B * src.H * src.W * pd.C
-    plan.add(label, "dwconv", thunk, n * ESIZE[pd.dtype] * (3 if res is not None else 2), 18 * n)
+    op_call(plan, label, "dwconv", lib.cvmi_dwconv3x3, args, (pd, src, dst, res), n * ESIZE[pd.dtype] * (3 if res is not None else 2), 18 * n)
 
 
 def op_sppf_pool(plan, label, buf, c):
     lib = _lib.load()
     args = (buf.t.data_ptr(), buf.C, buf.B, buf.H, buf.W, c, buf.dtype)
-    plan.keep.append(buf)
-    sp0 = plan.sptr
-    fn = lib.cvmi_sppf_pool
-
-    def thunk(sp=None):
-        sp = sp0 if sp is None else sp
-        _lib.check(fn(*args, sp), label)
-
     n = buf.B * buf.H * buf.W * c
-    plan.add(label, "pool", thunk, 4 * n * ESIZE[buf.dtype], 0)
+    op_call(plan, label, "pool", lib.cvmi_sppf_pool, args, buf, 4 * n * ESIZE[buf.dtype], 0)
 
 
 def op_attention(plan, label, desc, keep, bytes_=0, flops=0, kind="attention"):
-    lib = _lib.load()
-    plan.keep.append((desc, keep))
-    sp0 = plan.sptr
-    fn = lib.cvmi_attention
-
-    def thunk(sp=None):
-        sp = sp0 if sp is None else sp
-        _lib.check(fn(C.byref(desc), sp), label)
-
-    plan.add(label, kind, thunk, bytes_, flops)
+    op_call(plan, label, kind, _lib.load().cvmi_attention, (C.byref(desc),), (desc, keep), bytes_, flops)
 
 
 def make_attn_desc(**kw):
@@ -452,14 +398,7 @@ def op_layernorm(plan, label, src, gamma, beta, dst, eps=1e-6, act=_lib.ACT_NONE
         assert pad is None and act == _lib.ACT_NONE and src.dtype == dst.dtype == _lib.F32 and is16(dst2.dtype)
         assert dst2.rows == src.rows and dst2.C == src.C
         args2 = (src.ptr, src.ld, gamma.data_ptr(), beta.data_ptr(), dst.ptr, dst.ld, dst2.ptr, dst2.ld, dst2.dtype, src.rows, src.C, float(eps))
-        plan.keep.append((src, dst, dst2, gamma, beta))
-        sp1, fn2 = plan.sptr, lib.cvmi_layernorm_dual
-
-        def thunk2(sp=None):
-            sp = sp1 if sp is None else sp
-            _lib.check(fn2(*args2, sp), label)
-
-        plan.add(label, "layernorm", thunk2, src.rows * src.C * (4 + 4 + 2), 8 * src.rows * src.C)
+        op_call(plan, label, "layernorm", lib.cvmi_layernorm_dual, args2, (src, dst, dst2, gamma, beta), src.rows * src.C * (4 + 4 + 2), 8 * src.rows * src.C)
         return
     if pad is None:
         assert src.rows == dst.rows
@@ -467,14 +406,7 @@ def op_layernorm(plan, label, src, gamma, beta, dst, eps=1e-6, act=_lib.ACT_NONE
     else:
         assert src.rows % (pad[0] * pad[1]) == 0 and dst.rows == src.rows // (pad[0] * pad[1]) * pad[2] * pad[3]
     args = (src.ptr, src.ld, src.dtype, gamma.data_ptr(), beta.data_ptr(), dst.ptr, dst.ld, dst.dtype, src.rows, src.C, float(eps), act) + tuple(pad)
-    plan.keep.append((src, dst, gamma, beta))
-    sp0, fn = plan.sptr, lib.cvmi_layernorm
-
-    def thunk(sp=None):
-        sp = sp0 if sp is None else sp
-        _lib.check(fn(*args, sp), label)
-
-    plan.add(label, "layernorm", thunk, src.rows * src.C * (ESIZE[src.dtype] + ESIZE[dst.dtype]), 8 * src.rows * src.C)
+    op_call(plan, label, "layernorm", lib.cvmi_layernorm, args, (src, dst, gamma, beta), src.rows * src.C * (ESIZE[src.dtype] + ESIZE[dst.dtype]), 8 * src.rows * src.C)
 
 
 def _as_rows(v):
@@ -489,33 +421,20 @@ def op_maxpool2(plan, label, src, dst):
     lib = _lib.load()
     assert src.c == dst.c and (dst.H, dst.W) == (src.H // 2, src.W // 2) and src.dtype == dst.dtype
     args = (src.ptr, src.ld, dst.ptr, dst.ld, src.B, src.H, src.W, src.c, src.dtype)
-    plan.keep.append((src, dst))
-    sp0, fn = plan.sptr, lib.cvmi_maxpool2x2
-
-    def thunk(sp=None):
-        sp = sp0 if sp is None else sp
-        _lib.check(fn(*args, sp), label)
-
     n = src.B * src.H * src.W * src.c
-    plan.add(label, "pool", thunk, n * ESIZE[src.dtype] * 5 // 4, 0)
+    op_call(plan, label, "pool", lib.cvmi_maxpool2x2, args, (src, dst), n * ESIZE[src.dtype] * 5 // 4, 0)
 
 
 def op_cast(plan, label, src, dst):
     lib = _lib.load()
     src, dst = _as_rows(src), _as_rows(dst)
     args = (src.ptr, src.ld, src.dtype, dst.ptr, dst.ld, dst.dtype, src.rows, src.C)
-    plan.keep.append((src, dst))
-    sp0, fn = plan.sptr, lib.cvmi_cast
-
-    def thunk(sp=None):
-        sp = sp0 if sp is None else sp
-        _lib.check(fn(*args, sp), label)
-
-    plan.add(label, "cast", thunk, src.rows * src.C * (ESIZE[src.dtype] + ESIZE[dst.dtype]), 0)
+    op_call(plan, label, "cast", lib.cvmi_cast, args, (src, dst), src.rows * src.C * (ESIZE[src.dtype] + ESIZE[dst.dtype]), 0)
 
 
 def op_call(plan, label, kind, fn, args, keep=(), bytes_=0, flops=0):
-    """Generic: fn(*args, stream)."""
+    """The one way a launch enters a plan: fn(*args, stream) -- thunk() on the plan's stream, thunk(stream_ptr) on a lane's stream.  Every op_*
+    wrapper ends here; args of a descriptor call are (C.byref(d),), with d in keep."""
     plan.keep.append(keep)
     sp0 = plan.sptr
 
@@ -562,7 +481,7 @@ class PackedHieraMlp:
 
 
 def proj_mlp_k_order(C_):
-    """Column order of fc1's weight in the proj form of cvmi_hiera_mlp_stats (csrc/proj_mlp.hpp): packed column 16 s + k holds channel
+    """Column order of fc1's weight in the proj form of cvmi_hiera_mlp (csrc/proj_mlp.hpp): packed column 16 s + k holds channel
     16 s + pi(k), pi(k) = 8 ((k & 7) >> 2) + 4 (k >> 3) + (k & 3) -- the order in which the proj product's accumulator serves as fc1's operand."""
     n = torch.arange(C_)
     k = n % 16
@@ -570,7 +489,7 @@ def proj_mlp_k_order(C_):
 
 
 class PackedProjMlp:
-    """attn.proj + fc1 / fc2 of one Hiera block as the stream of the proj form of cvmi_hiera_mlp_stats (include/cvmi355.h): the projection's
+    """attn.proj + fc1 / fc2 of one Hiera block as the stream of the proj form of cvmi_hiera_mlp (include/cvmi355.h): the projection's
     output tiles in natural k order, then PackedHieraMlp's chunks with fc1's columns in proj_mlp_k_order."""
 
     def __init__(self, wp, bp, w1, b1, w2, b2, device="cuda", dtype=F16):
@@ -616,23 +535,16 @@ def op_hiera_mlp(plan, label, pm, x, gamma, beta, eps=1e-6, stats_out=None, stat
     assert x.dtype == F32 and x.c == pm.C and x.c0 == 0
     rows = x.B * x.H * x.W
     assert stats_out is None or (stats_out.dtype == torch.float32 and stats_out.numel() == 2 * rows and stats_out.is_contiguous()), label
-    desc, b2 = None, pm.bias.data_ptr()
+    d = _lib.MlpDesc(x=x.ptr, gamma=gamma.data_ptr(), beta=beta.data_ptr(), w_packed=pm.w.data_ptr(), b2=pm.bias.data_ptr(),
+                     ln_stats_out=stats_out.data_ptr() if stats_out is not None else None, rows=rows, x_ld=x.ld, C=pm.C, dtype=pm.dtype,
+                     eps=float(eps), ln_stats_eps=float(stats_eps))
     if proj is not None:
         assert ao.rows == rows and ao.C == pm.C and ao.dtype == pm.dtype, label
-        desc = _lib.MlpProj(ao=ao.ptr, w_packed=pm.w.data_ptr(), bp=pm.bias.data_ptr(), ao_ld=ao.ld)
-        b2 += 4 * pm.C                                          # PackedProjMlp.bias = bp | b2
-    args = (x.ptr, x.ld, gamma.data_ptr(), beta.data_ptr(), float(eps), None if proj is not None else pm.w.data_ptr(), b2, rows, pm.C, pm.dtype,
-            stats_out.data_ptr() if stats_out is not None else None, float(stats_eps))
-    plan.keep.append((pm, x, gamma, beta, stats_out, proj, desc))
-    sp0, fn = plan.sptr, lib.cvmi_hiera_mlp_stats
-    pdesc = C.byref(desc) if desc is not None else None
-
-    def thunk(sp=None):
-        sp = sp0 if sp is None else sp
-        _lib.check(fn(*args, sp, pdesc), label)
-
-    plan.add(label, "mlp_fused", thunk, rows * pm.C * (8 + (ESIZE[pm.dtype] if proj is not None else 0)),
-             2 * rows * 2 * 4 * pm.C * pm.C + (2 * rows * pm.C * pm.C if proj is not None else 0))
+        d.ao, d.ao_ld, d.bp = ao.ptr, ao.ld, pm.bias.data_ptr()
+        d.b2 = pm.bias.data_ptr() + 4 * pm.C                    # PackedProjMlp.bias = bp | b2
+    op_call(plan, label, "mlp_fused", lib.cvmi_hiera_mlp, (C.byref(d),), (d, pm, x, gamma, beta, stats_out, proj),
+            rows * pm.C * (8 + (ESIZE[pm.dtype] if proj is not None else 0)),
+            2 * rows * 2 * 4 * pm.C * pm.C + (2 * rows * pm.C * pm.C if proj is not None else 0))
 
 
 # ---- token-stationary linear layer (tok_linear.hip) ------------------------------------------------------------------------
@@ -753,18 +665,14 @@ def op_tok_linear(plan, label, pt, src, dst, ln=None, act=_lib.ACT_NONE, residua
     assert stats_out is None or (stats_out.dtype == torch.float32 and stats_out.numel() == 2 * src.rows * max(out_parts, 1) and stats_out.is_contiguous()), label
     assert stats_in is None or (stats_in.dtype == torch.float32 and stats_in.numel() == 2 * src.rows * max(stats_parts, 1) and stats_in.is_contiguous()), label
     gam, bet, eps = ln if (ln is not None and not cast) else (None, None, 0.0)
-    args = (src.ptr, src.ld, 2 if cast else 1 if ln is not None else 0, gam.data_ptr() if gam is not None else None, bet.data_ptr() if bet is not None else None,
-            float(eps), pt.w.data_ptr(), dst.ptr, dst.ld, 1 if residual else 0, src.rows, pt.K, pt.N, act, pt.dtype,
-            stats_in.data_ptr() if stats_in is not None else None, int(stats_parts), stats_out.data_ptr() if stats_out is not None else None, float(stats_eps))
-    plan.keep.append((pt, src, dst, gam, bet, stats_in, stats_out))
-    sp0, fn = plan.sptr, lib.cvmi_tok_linear_stats
-
-    def thunk(sp=None):
-        sp = sp0 if sp is None else sp
-        _lib.check(fn(*args, sp), label)
-
+    d = _lib.TokDesc(gamma=gam.data_ptr() if gam is not None else None, beta=bet.data_ptr() if bet is not None else None, w_packed=pt.w.data_ptr(),
+                     out=dst.ptr, ln_stats_in=stats_in.data_ptr() if stats_in is not None else None,
+                     ln_stats_out=stats_out.data_ptr() if stats_out is not None else None, rows=src.rows, in_ld=src.ld,
+                     in_f32_layernorm=2 if cast else 1 if ln is not None else 0, out_ld=dst.ld, out_f32_residual=1 if residual else 0, K=pt.K, N=pt.N,
+                     act=act, dtype=pt.dtype, ln_stats_in_parts=int(stats_parts), ln_stats_out_parts=out_parts, eps=float(eps),
+                     ln_stats_eps=float(stats_eps), **{"in": src.ptr})                  # (`in` is a Python keyword)
     bytes_ = src.rows * (pt.K * ESIZE[src.dtype] + pt.N * ESIZE[dst.dtype] * (2 if residual else 1))
-    plan.add(label, kind, thunk, bytes_, 2 * src.rows * pt.N * pt.K)
+    op_call(plan, label, kind, lib.cvmi_tok_linear, (C.byref(d),), (d, pt, src, dst, gam, bet, stats_in, stats_out), bytes_, 2 * src.rows * pt.N * pt.K)
 
 
 def op_tok_linear_pool(plan, label, pt, src, dst, ln, kind="gemm", stats_in=None):
@@ -776,14 +684,9 @@ def op_tok_linear_pool(plan, label, pt, src, dst, ln, kind="gemm", stats_in=None
     assert (dst.B, dst.H, dst.W) == (B, H // 2, W // 2) and H % 2 == 0 and W % 2 == 0 and (B * H * W) % 256 == 0, label
     gam, bet, eps = ln
     assert stats_in is None or (stats_in.dtype == torch.float32 and stats_in.numel() == 2 * B * H * W and stats_in.is_contiguous()), label
-    args = (src.ptr, src.ld, gam.data_ptr(), bet.data_ptr(), float(eps), pt.w.data_ptr(), dst.ptr, dst.ld, B, H, W, pt.K, pt.N, pt.dtype,
-            stats_in.data_ptr() if stats_in is not None else None)
-    plan.keep.append((pt, src, dst, gam, bet, stats_in))
-    sp0, fn = plan.sptr, lib.cvmi_tok_linear_pool_stats
-
-    def thunk(sp=None):
-        sp = sp0 if sp is None else sp
-        _lib.check(fn(*args, sp), label)
-
     rows = B * H * W
-    plan.add(label, kind, thunk, rows * pt.K * 4 + rows // 4 * pt.N * 4, 2 * rows * pt.N * pt.K)
+    d = _lib.TokDesc(gamma=gam.data_ptr(), beta=bet.data_ptr(), w_packed=pt.w.data_ptr(), out=dst.ptr,
+                     ln_stats_in=stats_in.data_ptr() if stats_in is not None else None, rows=rows, in_ld=src.ld, in_f32_layernorm=1, out_ld=dst.ld,
+                     K=pt.K, N=pt.N, act=_lib.ACT_NONE, dtype=pt.dtype, pool_h=H, pool_w=W, eps=float(eps), **{"in": src.ptr})
+    op_call(plan, label, kind, lib.cvmi_tok_linear, (C.byref(d),), (d, pt, src, dst, gam, bet, stats_in), rows * pt.K * 4 + rows // 4 * pt.N * 4,
+            2 * rows * pt.N * pt.K)

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define CVMI_VERSION 128
+#define CVMI_VERSION 129
 
 typedef void* cvmi_stream_t; /* hipStream_t */
 
@@ -41,17 +41,17 @@ enum { CVMI_ACT_NONE = 0, CVMI_ACT_SILU = 1, CVMI_ACT_RELU = 2, CVMI_ACT_GELU = 
 /* ---- library -------------------------------------------------------------------------------- */
 int cvmi_version(void);
 const char* cvmi_last_error(void);
-/* Diagnostic: the kernel (template instance) the calling thread's most recent cvmi_conv2d / cvmi_attention / cvmi_tok_linear* /
- * cvmi_hiera_mlp* / cvmi_c3k2 / cvmi_stem2 / cvmi_dwpw / cvmi_layernorm* / cvmi_sppf_pool / cvmi_upsample_refine call dispatched to, as rocprofv3 names it up to the spelling of the 16-bit type (e.g. "gemm256x192_kernel<float>").  Read-and-clear: "" when no such
+/* Diagnostic: the kernel (template instance) the calling thread's most recent cvmi_conv2d / cvmi_attention / cvmi_tok_linear /
+ * cvmi_hiera_mlp / cvmi_c3k2 / cvmi_stem2 / cvmi_dwpw / cvmi_layernorm* / cvmi_sppf_pool / cvmi_upsample_refine call dispatched to, as rocprofv3 names it up to the spelling of the 16-bit type (e.g. "gemm256x192_kernel<float>").  Read-and-clear: "" when no such
  * call happened since the last read. */
 const char* cvmi_last_kernel(void);
 /* fills: [0] CU count, [1] wave size, [2] LDS bytes per CU-workgroup, [3] gfx arch number (950) */
 int cvmi_device_info(int device, int* out4);
 /* ABI guard for the descriptor structs below: sizeof(struct) as THIS library was compiled, for kind = CVMI_DESC_CONV / _C3K2 / _DWPW /
- * _ATTN (0 for an unknown kind).  A binding compares it with the size of its own mirror of the struct once, at load, and refuses to
+ * _ATTN / _TOK / _MLP (0 for an unknown kind).  A binding compares it with the size of its own mirror of the struct once, at load, and refuses to
  * continue on a mismatch (circuitvision_amd/_lib.py does; INTEGRATION.md shows the check): a struct that is short by a trailing field
  * would otherwise be read past its end. */
-enum { CVMI_DESC_CONV = 0, CVMI_DESC_C3K2 = 1, CVMI_DESC_DWPW = 2, CVMI_DESC_ATTN = 3 };
+enum { CVMI_DESC_CONV = 0, CVMI_DESC_C3K2 = 1, CVMI_DESC_DWPW = 2, CVMI_DESC_ATTN = 3, CVMI_DESC_TOK = 4, CVMI_DESC_MLP = 5 };
 size_t cvmi_desc_size(int kind);
 
 /* ---- HIP graph capture of a launch sequence (replaces per-op Python dispatch) ---------------- */
@@ -98,7 +98,7 @@ typedef struct cvmi_conv_desc {
   float* row_stats;                 /* optional (f32 output + residual, plain 16-bit GEMM with N % 192 == 0 and K >= 1024, i.e. the Hiera stage-3
                                        fc2 shape): float[rows][N / 96][2] = (mean, sum of squared deviations from that mean) of the values
                                        written to each row's 96-column slices -- the statistics of the NEXT LayerNorm over these rows, free of
-                                       the E[x^2] - E[x]^2 cancellation (cvmi_tok_linear_stats with ln_stats_in_parts = N / 96 combines the
+                                       the E[x^2] - E[x]^2 cancellation (cvmi_tok_linear with ln_stats_in_parts = N / 96 combines the
                                        slices); NULL = off */
   const int* res_map;               /* optional DEVICE table of B ints (128; needs a residual, res_rep <= 1, and shuffle_cout > 0 or res_mod == OH * OW): batch
                                        entry e reads residual image res_map[e] -- res_rep's sharing with the image of every entry stated instead of
@@ -200,7 +200,7 @@ typedef struct cvmi_attn_desc {
                                 head by head (circuitvision_amd.engine.PackedQkvAttn states the order) */
   const float* proj_gamma;   /* LayerNorm weight / bias [proj_K] */
   const float* proj_beta;
-  const float* proj_stats;   /* optional: (mean, rstd) per token as cvmi_tok_linear_stats / cvmi_hiera_mlp_stats write them; NULL = computed here */
+  const float* proj_stats;   /* optional: (mean, rstd) per token as cvmi_tok_linear / cvmi_hiera_mlp write them to ln_stats_out; NULL = computed here */
   int proj_ld, proj_K;
   float proj_eps;
   /* Batch sharing by table (128): DEVICE arrays of B ints; q rows of batch entry b are read from entry q_bmap[b], k / v rows from entry
@@ -302,43 +302,43 @@ int cvmi_layernorm_dual(const void* x, int x_ld, const float* gamma, const float
  * cvmi_hiera_mlp_packed_bytes(C) = (4 C / 32) * (C/16 + 1 + 2 ceil(C/32)) * 1024.  b2: fc2 bias, f32 [C]. */
 int cvmi_hiera_mlp_supported(int C);
 size_t cvmi_hiera_mlp_packed_bytes(int C);
-int cvmi_hiera_mlp(void* x, int x_ld, const float* gamma, const float* beta, float eps, const void* w_packed,
-                   const float* b2, long long rows, int C, int dtype /* CVMI_F16 | CVMI_BF16: type of w_packed */, cvmi_stream_t stream);
-/* same; additionally writes per updated row (mean, 1 / sqrt(var + ln_stats_eps)) to ln_stats_out (float[2 * rows], or NULL): the statistics of
- * the NEXT LayerNorm over these rows (the next block's norm1), consumed by cvmi_tok_linear_stats / cvmi_tok_linear_pool_stats */
-/* proj (127), optional: the block's attention projection in the same launch.  With x1 = x + ao . Wp^T + bp the launch stores
+/* proj form (127; ao / bp set): the block's attention projection in the same launch.  With x1 = x + ao . Wp^T + bp the launch stores
  * x1 + fc2(GELU(fc1(LayerNorm(x1)))) + b2; x1 itself is never written (sam2 hieradet MultiScaleBlock: `x = shortcut + proj(attn)` then the
- * MLP half).  NULL = the launch described above, bit for bit.  With proj set the w_packed ARGUMENT of the call is not read (it may be NULL):
- * the launch streams proj->w_packed; b2 stays the fc2 bias.  Built for C in {144, 288} and a 16-bit dtype; refused before any launch:
- * another C or dtype, a NULL or not 16-byte aligned ao / w_packed / bp, ao_ld < C or no multiple of 8.  Equal to cvmi_tok_linear(residual)
- * followed by cvmi_hiera_mlp to within f32 rounding ahead of the same 16-bit roundings (the f32 sums associate as x + (ao . Wp^T + (bp + b2) + ..),
+ * MLP half).  ao = bp = NULL: the launch described above, bit for bit.  Built for C in {144, 288} and a 16-bit dtype; refused before any
+ * launch: another C or dtype, a NULL or not 16-byte aligned ao / w_packed / bp, ao_ld < C or no multiple of 8.  Equal to cvmi_tok_linear(residual)
+ * followed by the plain form to within f32 rounding ahead of the same 16-bit roundings (the f32 sums associate as x + (ao . Wp^T + (bp + b2) + ..),
  * fc1 sums its k in the permuted order below), not bit for bit; a repeated launch on the same input is bit-identical.
  * w_packed of the proj form, cvmi_hiera_mlp_proj_packed_bytes(C) = ceil(C/32) * (C/16) * 1024 + cvmi_hiera_mlp_packed_bytes(C) bytes:
- *   [ P(t, s) for t = 0 .. ceil(C/32) - 1, s = 0 .. C/16 - 1 ]  ++  the chunks of cvmi_hiera_mlp with F1's k permuted
+ *   [ P(t, s) for t = 0 .. ceil(C/32) - 1, s = 0 .. C/16 - 1 ]  ++  the chunks of the plain form with F1's k permuted
  *   P(t, s)[l][e]  = Wp[32 t + r][16 s + 8 h + e]   (attn.proj.weight; 0 for output rows >= C); the kernel moves ring-slot sized runs of whole
  *                    tiles: floor((C/16 + 1 + 2 ceil(C/32)) / (C/16)) = 2 tiles per piece
  *   F1(j, s)[l][e] = W1[32 j + r][16 s + pi(8 h + e)] for s < C/16,  pi(k) = 8 ((k & 7) >> 2) + 4 (k >> 3) + (k & 3)  (bits 2 and 3 of k
  *                    swapped): the k order in which the accumulator of the proj product (lane = token, register 4 g + e of tile t <-> channel
  *                    32 t + 8 g + 4 h + e), normalised in place, serves as fc1's B operand.  The bias step s = C/16 and F2 are unchanged. */
-typedef struct {
-  const void* ao;            /* attention output, 16-bit [rows][C], row stride ao_ld elements; read only */
-  const void* w_packed;      /* the stream above */
-  const float* bp;           /* attn.proj.bias, f32 [C] */
-  int ao_ld;
-} cvmi_mlp_proj;
 size_t cvmi_hiera_mlp_proj_packed_bytes(int C);
-int cvmi_hiera_mlp_stats(void* x, int x_ld, const float* gamma, const float* beta, float eps, const void* w_packed, const float* b2,
-                         long long rows, int C, int dtype, float* ln_stats_out, float ln_stats_eps, cvmi_stream_t stream,
-                         const cvmi_mlp_proj* proj);
+typedef struct cvmi_mlp_desc {
+  void* x;                   /* the f32 residual stream [rows][C], row stride x_ld elements; updated in place */
+  const float* gamma;        /* LayerNorm weight / bias, f32 [C] */
+  const float* beta;
+  const void* w_packed;      /* the stream the selected form reads: the plain form's chunks, or (ao / bp set) the proj form's stream above */
+  const float* b2;           /* fc2 bias, f32 [C] */
+  float* ln_stats_out;       /* optional: float[2 * rows], per updated row (mean, 1 / sqrt(var + ln_stats_eps)) -- the statistics of the NEXT
+                                LayerNorm over these rows (the next block's norm1), consumed through cvmi_tok_desc.ln_stats_in; NULL = off */
+  const void* ao;            /* proj form: attention output, 16-bit [rows][C], row stride ao_ld elements; read only.  NULL (with bp) = plain form */
+  const float* bp;           /* proj form: attn.proj.bias, f32 [C] */
+  long long rows;
+  int x_ld;
+  int C;
+  int dtype;                 /* CVMI_F16 | CVMI_BF16: type of w_packed (and of ao) */
+  int ao_ld;
+  float eps;                 /* of the LayerNorm inside the launch */
+  float ln_stats_eps;        /* of the statistics written to ln_stats_out */
+} cvmi_mlp_desc;
+int cvmi_hiera_mlp(const cvmi_mlp_desc* d, cvmi_stream_t stream);
 
 /* Token-stationary linear layer for Hiera's short-K GEMMs (sam2 hieradet MultiScaleBlock: qkv(norm1(x)), x = shortcut + proj(attn),
  * mlp.layers[0](norm2(x)) + GELU; behind sam2_infer.py:226):
  *   y[r, n] = act( sum_k in[r, k] * W[n, k] + b[n] ),   r < rows (a multiple of 256), n < N, K in {144, 288, 576}
- *   in_f32_layernorm = 1: in is the f32 residual stream, normalised on the fly with gamma / beta / eps (the separate LayerNorm pass
- *                         and its fp16 copy disappear); 0: in is an fp16 matrix; 2: in is an f32 matrix converted as it is (K = 144, 288;
- *                         16-bit output, no activation: the neck's lateral convs read the f32 stage outputs, FpnNeck behind sam2_infer.py:226)
- *   out_f32_residual = 1: out is the f32 residual stream, updated in place (out[r, n] += y[r, n], act must be NONE);
- *                      0: out is fp16 (act NONE or GELU)
  * w_packed: ceil(N/32) chunks of (K/16 + 1) MFMA fragments of 1 KiB, fragment (j, s), lane l (r = l & 31, h = l >> 5), element e:
  *   Wx[32 j + r][16 s + 8 h + e],  Wx = [ W | fp16(b) | fp16(b - fp16(b)) | 0 ... ]  (K + 16 columns, rows >= N zero).
  * The chunk count is padded to even (the added chunk is zero): cvmi_tok_linear_packed_bytes(K, N) = 2 ceil(ceil(N/32) / 2) * (K/16 + 1) * 1024
@@ -350,36 +350,51 @@ size_t cvmi_tok_linear_packed_bytes(int K, int N);
  * (r16 = l & 15, g = l >> 4), element e:  W[32 j + 16 hh + r16][32 s + 8 g + e]  (rows >= N zero);  the chunk's last piece holds its 32 bias
  * values as f32 in its first 128 bytes (rest zero).  cvmi_tok_linear_packed_bytes follows the format. */
 int cvmi_tok_linear_format(int K);
-int cvmi_tok_linear(const void* in, int in_ld, int in_f32_layernorm, const float* gamma, const float* beta, float eps,
-                    const void* w_packed, void* out, int out_ld, int out_f32_residual, long long rows, int K, int N, int act,
-                    int dtype /* CVMI_F16 | CVMI_BF16: type of w_packed and of the 16-bit input / output */, cvmi_stream_t stream);
-
-/* cvmi_tok_linear with LayerNorm statistics handed from the launch that writes the f32 residual stream to the launch that normalises it
- * (sam2 hieradet MultiScaleBlock: x = shortcut + proj(attn), then mlp.layers[0](norm2(x)); behind sam2_infer.py:226):
- *   ln_stats_out (out_f32_residual = 1, may be NULL): float[2 * rows] = per row (mean, 1 / sqrt(var + ln_stats_eps)) over the N updated values
- *   ln_stats_in  (in_f32_layernorm = 1, may be NULL): the same pairs; the LayerNorm prologue then reads every row once instead of twice.
- *   ln_stats_in_parts = P > 0: ln_stats_in is float[rows][P][2] of per-slice (mean, sum of squared deviations) instead, P equal column slices
- *                     of the row (cvmi_conv_desc.row_stats). */
-int cvmi_tok_linear_stats(const void* in, int in_ld, int in_f32_layernorm, const float* gamma, const float* beta, float eps,
-                          const void* w_packed, void* out, int out_ld, int out_f32_residual, long long rows, int K, int N, int act,
-                          int dtype, const float* ln_stats_in, int ln_stats_in_parts, float* ln_stats_out, float ln_stats_eps,
-                          cvmi_stream_t stream);
-/* The layout of ln_stats_out for a residual-form launch of this shape.  0: float[rows][2] of (mean, rstd) as above.  P > 0: the launch has
+/* The layout of ln_stats_out for a residual-form launch of this shape.  0: float[rows][2] of (mean, rstd).  P > 0: the launch has
  * fewer 256-row blocks than the chip has CUs (the per-rank batch of an 8-GPU job: SAM 2.1-L at 8 images), so P workgroups share a row block,
  * each writing its output-channel slice, and ln_stats_out is float[rows][P][2] of per-slice (mean, sum of squared deviations) -- exactly what
  * the consumer takes with ln_stats_in_parts = P.  Depends on (rows, K, N) only; K = 576 (the 16x16x32 format) is the only K that splits.
+ * The caller states the layout it allocated in cvmi_tok_desc.ln_stats_out_parts; a launch that would write another one is refused.
  * Requirements of that format beyond the ones above: 16-bit output needs N % 8 == 0 and out_ld % 8 == 0; in_f32_layernorm = 2 is not built. */
 int cvmi_tok_linear_stats_parts(long long rows, int K, int N);
-
-/* Shortcut path of a Hiera q-pooling block in ONE launch: out[b, y, x, :] = max over the 2 x 2 token block of
- * ( LayerNorm(in[b, 2y + dy, 2x + dx, :]) W^T + bias )  = `do_pool(self.proj(norm1(x)))` of sam2 hieradet MultiScaleBlock.forward (behind
- * /root/reference/src/sam2_infer.py:226).  in: f32 [B, H, W, K] token grid (row stride in_ld); out: f32 [B, H/2, W/2, N] (row stride out_ld);
- * w_packed as for cvmi_tok_linear; H, W even, B*H*W a multiple of 256, K in {144, 288, 576}. */
-int cvmi_tok_linear_pool(const void* in, int in_ld, const float* gamma, const float* beta, float eps, const void* w_packed, void* out,
-                         int out_ld, int B, int H, int W, int K, int N, int dtype, cvmi_stream_t stream);
-/* same, with the rows' LayerNorm statistics supplied (float[2 * B*H*W] of (mean, rstd) pairs, or NULL) */
-int cvmi_tok_linear_pool_stats(const void* in, int in_ld, const float* gamma, const float* beta, float eps, const void* w_packed, void* out,
-                               int out_ld, int B, int H, int W, int K, int N, int dtype, const float* ln_stats_in, cvmi_stream_t stream);
+typedef struct cvmi_tok_desc {
+  const void* in;            /* [rows][K], row stride in_ld elements; its type is chosen by in_f32_layernorm */
+  const float* gamma;        /* LayerNorm weight / bias, f32 [K] (in_f32_layernorm = 1) */
+  const float* beta;
+  const void* w_packed;
+  void* out;                 /* [rows][N] (pool form: [rows / 4][N]), row stride out_ld elements; its type is chosen by out_f32_residual */
+  const float* ln_stats_in;  /* optional (in_f32_layernorm = 1): float[2 * rows] of per row (mean, rstd) handed over by the launch that wrote the
+                                f32 residual stream (sam2 hieradet MultiScaleBlock: x = shortcut + proj(attn), then mlp.layers[0](norm2(x)));
+                                the LayerNorm prologue then reads every row once instead of twice.  NULL = computed here */
+  float* ln_stats_out;       /* optional (out_f32_residual = 1): per row (mean, 1 / sqrt(var + ln_stats_eps)) over the N updated values, in the
+                                layout ln_stats_out_parts states.  NULL = off */
+  long long rows;            /* a multiple of 256 */
+  int in_ld;
+  int in_f32_layernorm;      /* 1: in is the f32 residual stream, normalised on the fly with gamma / beta / eps (the separate LayerNorm pass
+                                and its fp16 copy disappear); 0: in is an fp16 matrix; 2: in is an f32 matrix converted as it is (K = 144, 288;
+                                16-bit output, no activation: the neck's lateral convs read the f32 stage outputs, FpnNeck behind sam2_infer.py:226) */
+  int out_ld;
+  int out_f32_residual;      /* 1: out is the f32 residual stream, updated in place (out[r, n] += y[r, n], act must be NONE); 0: out is fp16
+                                (act NONE or GELU).  With in_f32_layernorm = 1 on a launch that shares row blocks (K = 576, fewer than 256 of
+                                them) in and out must not overlap: sibling workgroups would read rows the others update; refused */
+  int K;
+  int N;
+  int act;                   /* CVMI_ACT_NONE | CVMI_ACT_GELU */
+  int dtype;                 /* CVMI_F16 | CVMI_BF16: type of w_packed and of the 16-bit input / output */
+  int ln_stats_in_parts;     /* P > 0: ln_stats_in is float[rows][P][2] of per-slice (mean, sum of squared deviations) instead, P equal column
+                                slices of the row (cvmi_conv_desc.row_stats, or a ln_stats_out with ln_stats_out_parts = P) */
+  int ln_stats_out_parts;    /* the P the caller allocated ln_stats_out for: 0 = float[rows][2]; P > 0 = float[rows][P][2].  Must equal
+                                cvmi_tok_linear_stats_parts(rows, K, N) when ln_stats_out is set: refused otherwise, before any launch */
+  int pool_h;                /* pool_h, pool_w > 0 select the pool form, the shortcut path of a Hiera q-pooling block in ONE launch: the rows are the */
+  int pool_w;                /* tokens of [rows / (pool_h pool_w)][pool_h][pool_w] grids and out[b, y, x, :] = max over the 2 x 2 token block of
+                                ( LayerNorm(in[b, 2y + dy, 2x + dx, :]) W^T + bias ) = `do_pool(self.proj(norm1(x)))` of sam2 hieradet
+                                MultiScaleBlock.forward (behind /root/reference/src/sam2_infer.py:226); out is f32 [rows / 4][N], written not
+                                added.  pool_h, pool_w even; in_f32_layernorm = 1, out_f32_residual = 0, act NONE, no ln_stats_out, pairs
+                                (ln_stats_in_parts = 0) as ln_stats_in.  0, 0 = off */
+  float eps;                 /* of the LayerNorm prologue */
+  float ln_stats_eps;        /* of the statistics written to ln_stats_out */
+} cvmi_tok_desc;
+int cvmi_tok_linear(const cvmi_tok_desc* d, cvmi_stream_t stream);
 
 /* 2x2 / stride 2 max-pool, NHWC (Hiera shortcut path of the q-pooling blocks: do_pool(proj(x))). */
 int cvmi_maxpool2x2(const void* x, int x_ld, void* y, int y_ld, int B, int H, int W, int C, int dtype,

@@ -380,13 +380,10 @@ BF16_OPS = {
     "cvmi_prompt_tokens": ("test_bf16_ops_gpu.py", "test_prompt_tokens_bf16"),
     "cvmi_hyper_masks": ("test_bf16_ops_gpu.py", "test_hyper_masks_bf16"),
     "cvmi_hiera_mlp": ("test_ops_gpu.py", "test_hiera_mlp_fused_vs_torch"),
-    "cvmi_hiera_mlp_stats": ("test_ops_gpu.py", "test_hiera_mlp_fused_vs_torch"),
-    "cvmi_tok_linear": ("test_ops_gpu.py", "test_tok_linear_vs_torch"),
-    "cvmi_tok_linear_stats": ("test_ops_gpu.py", "test_tok_linear_forwarded_layernorm_statistics"),
-    "cvmi_tok_linear_pool": ("test_ops_gpu.py", "test_tok_linear_pool_vs_torch"),
-    "cvmi_tok_linear_pool_stats": ("test_ops_gpu.py", "test_tok_linear_pool_vs_torch"),
+    "cvmi_tok_linear": ("test_ops_gpu.py", "test_tok_linear_vs_torch"),          # (its statistics and pool forms: test_tok_linear_forwarded_layernorm_statistics, test_tok_linear_pool_vs_torch)
     "cvmi_tok_linear16_launch": ("test_ops_gpu.py", "test_tok_linear16_row_blocks_shared_between_workgroups"),
     "cvmi_tok_linear16_splits": ("test_ops_gpu.py", "test_tok_linear16_row_blocks_shared_between_workgroups"),
+    "cvmi_tok_linear16_shares": ("test_ops_gpu.py", "test_tok_linear16_row_blocks_shared_between_workgroups"),
 }
 
 
@@ -645,8 +642,8 @@ HELPER_MUTANT_ROWS = {
 
 
 # ---- the token-stationary path: tok_linear.hip, tok_linear16.hip, hiera_mlp.hip, tok_stream.hpp ------------------------------------------------
-# TOK_ROWS: one row = one launch of cvmi_tok_linear_stats / cvmi_tok_linear_pool_stats and the instance its dispatcher must tag; MLP_ROWS: one
-# launch of cvmi_hiera_mlp_stats.  Tags carry no operand type: every row runs in fp16 and bf16.  Operands, references and the tolerance live in
+# TOK_ROWS: one row = one launch of cvmi_tok_linear (plain or pool form) and the instance its dispatcher must tag; MLP_ROWS: one
+# launch of cvmi_hiera_mlp.  Tags carry no operand type: every row runs in fp16 and bf16.  Operands, references and the tolerance live in
 # tests/tok_ref.py.  tok_pick / tl16_splits / mlp_pick mirror the host code (tests/test_op_coverage_cpu.py holds the mirror to the sources' text).
 TOK_KS = (144, 288, 576)
 TOK_FORMAT = {144: 32, 288: 32, 576: 16}          # cvmi_tok_linear_format: the MFMA shape of the packed weights
@@ -664,7 +661,7 @@ def tok_dispatch(ln, res, gelu):
 
 
 def tok_pick(K, ln, res, gelu, N, out_ld, pool=False):
-    """The tag of the launch cvmi_tok_linear_stats (pool: cvmi_tok_linear_pool_stats) ends in.  ln: 0 = 16-bit input, 1 = f32 + LayerNorm,
+    """The tag of the launch cvmi_tok_linear (pool: its pool form) ends in.  ln: 0 = 16-bit input, 1 = f32 + LayerNorm,
     2 = f32 converted as it is."""
     assert K in TOK_KS and ln in (0, 1, 2) and not (gelu and res) and (ln != 2 or not (res or gelu)), (K, ln, res, gelu)
     if TOK_FORMAT[K] == 16:
@@ -826,7 +823,7 @@ KIND_ROWS = 32                                                              # ro
 KIND_BLOCKS = ("far500", "ramp", "spread1e-3", "outlier_c0", "outlier_last")  # rows [32 i, 32 i + 32) of a `kinds` launch
 
 
-# ---- the proj + MLP launch: proj_mlp.hpp, the proj form of cvmi_hiera_mlp_stats ---------------------------------------------------------------------
+# ---- the proj + MLP launch: proj_mlp.hpp, the proj form of cvmi_hiera_mlp ---------------------------------------------------------------------
 # PROJ_ROWS: one row = one launch of op_hiera_mlp(.., proj=..) and the instance proj_mlp_dispatch must tag.  x has a row stride of C + 4, ao of
 # C + 8, both with NaN padding (the `tight` rows: C and C).  Operands, the reference, its mutants and the bound live in tests/tok_ref.py.
 def proj_pick(C):

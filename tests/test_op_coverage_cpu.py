@@ -522,9 +522,9 @@ TOK_TAG_ARGS = {"tok_linear.hip": "K, LN, CVMI_BOOLNAME(RES), CVMI_BOOLNAME(GELU
                 "tok_linear16.hip": "K, LN, CVMI_BOOLNAME(RES), CVMI_BOOLNAME(GELU), CVMI_BOOLNAME(POOL)", "hiera_mlp.hip": "C, VAR"}
 # launch_tl (tok_linear.hip): the staged store for 16-bit outputs whose N and stride are multiples of 8, the direct store otherwise
 TSTORE_RULE = """  if constexpr (!RES) {
-    if (N % 8 == 0 && out_ld % 8 == 0) return launch_tl1<K, LN, RES, GELU, true>(in, in_ld, gamma, beta, eps, wp, out, out_ld, rows, N, s, ex);
+    if (d.N % 8 == 0 && d.out_ld % 8 == 0) return launch_tl1<K, LN, RES, GELU, true>(d, s, ex);
   }
-  return launch_tl1<K, LN, RES, GELU, false>(in, in_ld, gamma, beta, eps, wp, out, out_ld, rows, N, s, ex);"""
+  return launch_tl1<K, LN, RES, GELU, false>(d, s, ex);"""
 TL16_SPLITS_BODY = """  const long long wg = rows / 256;
   const int nch = (N + 31) / 32;
   if (wg >= 256 || wg % 8 != 0 || (stats_out && N % 32 != 0)) return 1;
@@ -629,17 +629,17 @@ def test_every_token_path_instance_is_in_the_matrix():
 def test_a_new_token_path_instance_or_a_removed_row_is_caught():
     src = tok_sources()
     probe = dict(src)
-    probe["tok_linear.hip"] += "\n  if (res && gelu) return launch_tl1<144, 1, true, true, false>(in, in_ld, gamma, beta, eps, wp, out, out_ld, rows, N, s, ex);\n"
+    probe["tok_linear.hip"] += "\n  if (res && gelu) return launch_tl1<144, 1, true, true, false>(d, s, ex);\n"
     assert tok_gaps(probe) == ["tok_linear_kernel<144, 1, true, true, false, false> has no row"]
     probe = dict(src)
-    probe["hiera_mlp.hip"] += "\n  return launch_mlp<288, 1>(xf, x_ld, gamma, beta, eps, w_packed, b2, rows, s, ln_stats_out, ln_stats_eps);\n"
+    probe["hiera_mlp.hip"] += "\n  return launch_mlp<288, 1>(*d, s);\n"
     assert tok_gaps(probe) == ["hiera_mlp_kernel<288, 1> has no row"]
     for name, fmt in TOK_TAGS.items():
         probe = dict(src)
         probe[name] = probe[name].replace('cvmi_note_kernel("%s"' % fmt, 'note_off("%s"' % fmt)
         assert probe != src and tok_gaps(probe) == [f"{name} no longer tags its launch as {fmt}"]
     probe = dict(src)
-    probe["tok_linear.hip"] = probe["tok_linear.hip"].replace("N % 8 == 0 && out_ld % 8 == 0) return launch_tl1", "N % 16 == 0 && out_ld % 8 == 0) return launch_tl1")
+    probe["tok_linear.hip"] = probe["tok_linear.hip"].replace("d.N % 8 == 0 && d.out_ld % 8 == 0) return launch_tl1", "d.N % 16 == 0 && d.out_ld % 8 == 0) return launch_tl1")
     assert len(tok_gaps(probe)) == 24 and all("which the sources no longer launch" in g for g in tok_gaps(probe))       # the rule's text is part of the mirror
     drop = lambda *rids: tok_gaps(src, [r for r in TOK_ROWS if r["id"] not in rids], [r for r in MLP_ROWS if r["id"] not in rids])
     assert drop("k144_ln1_gelu_n40_ld48_inst") == []                      # (the chunk-count rows launch this instance too)
@@ -738,7 +738,7 @@ def test_every_proj_mlp_instance_is_in_the_matrix():
 
 def test_a_new_proj_mlp_instance_or_a_removed_row_is_caught():
     text = proj_source()
-    probe = text + "\n  return launch_proj_mlp<288, 0>(x, x_ld, pj, gamma, beta, eps, b2, rows, s, stats_out, stats_eps);\n"
+    probe = text + "\n  return launch_proj_mlp<288, 0>(d, s);\n"
     assert proj_gaps(probe) == ["proj_mlp_kernel<288, 0> has no row"]
     probe = text.replace("return launch_proj_mlp<288, 2>(", "return launch_proj_mlp<288, 0>(")
     assert probe != text and proj_gaps(probe) == ["proj_mlp_kernel<288, 0> has no row", "rows expect proj_mlp_kernel<288, 2>, which the sources no longer launch"]

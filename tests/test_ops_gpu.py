@@ -741,7 +741,7 @@ def test_tok_linear_pool_vs_torch(K, N, B, H, W, dt):
 @pytest.mark.parametrize("dt", [F16, BF16])
 def test_tok_linear_forwarded_layernorm_statistics(K, N2, dt):
     """x = x + proj(a) writes each updated row's LayerNorm statistics (mean, rstd); the next launch, GELU(fc1(LayerNorm(x))), takes them
-    instead of computing them in a first pass over x (cvmi_tok_linear_stats).  Statistics vs fp32 torch on the updated rows (an outlier
+    instead of computing them in a first pass over x (cvmi_tok_desc.ln_stats_in).  Statistics vs fp32 torch on the updated rows (an outlier
     channel and a common offset included); the fc1 output with forwarded statistics vs the one with the two-pass prologue and vs torch."""
     import torch.nn.functional as TF
     from circuitvision_amd.engine import TORCH_DTYPE, PackedTokLinear, Rows, op_tok_linear
@@ -814,7 +814,7 @@ def test_tok_linear_per_slice_layernorm_statistics(K, dt):
 def test_gemm_row_statistics_feed_the_next_layernorm(dt):
     """Hiera stage-3 fc2 shape (65536 x 2304 -> 576, f32 residual stream updated in place): the 256 x 192 GEMM also writes, per row and per
     96-column slice, (mean, sum of squared deviations) of the values it stores (cvmi_conv_desc.row_stats); the next block's qkv
-    (cvmi_tok_linear_stats with ln_stats_in_parts = 6) combines them instead of reading the rows twice.  Statistics vs float64 moments of the rows
+    (cvmi_tok_linear with ln_stats_in_parts = 6) combines them instead of reading the rows twice.  Statistics vs float64 moments of the rows
     AS WRITTEN; the qkv output with forwarded statistics vs the two-pass prologue on the same rows; replays bit-identical.  Rows 0..255 sit 500
     (>= 300 standard deviations) away from zero: raw (sum, sum of squares) partials would lose the variance there."""
     from circuitvision_amd.engine import TORCH_DTYPE, PackedTokLinear, Rows, op_tok_linear, row_stats_supported
@@ -929,5 +929,7 @@ def test_tok_linear_plain_f32_input_is_rejected_at_k576():
     x = torch.zeros(256, 576, device="cuda")
     y = torch.zeros(256, 64, dtype=torch.float16, device="cuda")
     w = torch.zeros(lib.cvmi_tok_linear_packed_bytes(576, 64) // 2, dtype=torch.float16, device="cuda")
-    rc = lib.cvmi_tok_linear(x.data_ptr(), 576, 2, None, None, 0.0, w.data_ptr(), y.data_ptr(), 64, 0, 256, 576, 64, ACT_NONE, F16, None)
+    d = _lib.TokDesc(in_ld=576, in_f32_layernorm=2, w_packed=w.data_ptr(), out=y.data_ptr(), out_ld=64, rows=256, K=576, N=64, act=ACT_NONE, dtype=F16,
+                     **{"in": x.data_ptr()})
+    rc = lib.cvmi_tok_linear(C.byref(d), None)
     assert rc != 0 and b"K = 144 and 288" in lib.cvmi_last_error()

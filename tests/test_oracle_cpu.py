@@ -119,7 +119,7 @@ def test_library_exports_every_declared_symbol():
     from circuitvision_amd import _lib
     hdr = open(os.path.join(ROOT, "include", "cvmi355.h")).read()
     declared = set(re.findall(r"\b(cvmi_[a-z0-9_]+)\s*\(", hdr))
-    declared -= {"cvmi_conv_desc", "cvmi_attn_desc"}
+    declared -= {"cvmi_conv_desc", "cvmi_attn_desc", "cvmi_tok_desc", "cvmi_mlp_desc"}
     assert declared, "no declarations parsed"
     if not os.path.exists(_lib.LIB_PATH):
         pytest.skip("libcvmi355.so not built (python -c 'import __graft_entry__ as g; g.build()')")
@@ -127,25 +127,34 @@ def test_library_exports_every_declared_symbol():
     for name in sorted(declared):
         assert hasattr(lib, name), f"{name} declared in cvmi355.h but not exported"
     assert set(_lib.SIGNATURES) == declared
-    assert lib.cvmi_version() >= 121                      # 121: cvmi_attn_desc.q_log2
+    assert lib.cvmi_version() >= 129                      # 129: cvmi_tok_desc / cvmi_mlp_desc
 
 
 def test_descriptor_mirrors_match_the_library_and_a_short_struct_is_rejected():
-    """The ctypes mirrors of the four descriptor structs must have the size libcvmi355.so was compiled with (cvmi_desc_size), field
+    """The ctypes mirrors of the six descriptor structs must have the size libcvmi355.so was compiled with (cvmi_desc_size), field
     order as in include/cvmi355.h; a mirror that is short by its trailing field (INTEGRATION.md once documented cvmi_conv_desc without
     `row_stats`) is refused at load instead of being read past its end."""
     from circuitvision_amd import _lib
     if not os.path.exists(_lib.LIB_PATH):
         pytest.skip("libcvmi355.so not built")
     lib = _lib.load()                                     # runs check_abi
+    structs = {"cvmi_conv_desc": _lib.ConvDesc, "cvmi_c3k2_desc": _lib.C3k2Desc, "cvmi_dwpw_desc": _lib.DwPwDesc, "cvmi_attn_desc": _lib.AttnDesc,
+               "cvmi_tok_desc": _lib.TokDesc, "cvmi_mlp_desc": _lib.MlpDesc}
+    assert list(_lib.DESC_MIRRORS.values()) == list(structs.values()) and list(_lib.DESC_MIRRORS) == [0, 1, 2, 3, 4, 5]
     for kind, cls in _lib.DESC_MIRRORS.items():
         assert lib.cvmi_desc_size(kind) == ctypes.sizeof(cls) > 0
     assert lib.cvmi_desc_size(99) == 0
-    hdr = open(os.path.join(ROOT, "include", "cvmi355.h")).read()
-    body = hdr[hdr.index("typedef struct cvmi_conv_desc {"):hdr.index("} cvmi_conv_desc;")]
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = [n for decl in re.findall(r"(?:const\s+)?(?:void|float|int)\s*\*?\s*([^;{]+);", body) for n in re.findall(r"\*?\s*([a-zA-Z_0-9]+)", decl)]
-    assert fields == [n for n, _ in _lib.ConvDesc._fields_], "ConvDesc field order differs from cvmi_conv_desc"
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "cvmi355.h")).read(), flags=re.S)
+    for name, cls in structs.items():
+        body = re.search(r"typedef struct(?: %s)? \{([^}]*)\} %s;" % (name, name), hdr).group(1)
+        fields = [n for decl in re.findall(r"(?:const\s+)?(?:void|float|int|long long)\s*\*?\s*([^;{]+);", body) for n in re.findall(r"\*?\s*([a-zA-Z_0-9]+)", decl)]
+        assert len(fields) == len(re.findall(r"[;,]", body)), f"{name}: a declaration the field parser does not read"
+        assert fields == [n for n, _ in cls._fields_], f"{cls.__name__} field order differs from {name}"
+        ctype = {"int": ctypes.c_int, "float": ctypes.c_float, "long long": ctypes.c_longlong}
+        for decl_type, star, names in re.findall(r"(?:const\s+)?(void|float|int|long long)\s*(\*?)\s*([^;{]+);", body):      # ... and each field's C type
+            for n in re.findall(r"(\*?)\s*([a-zA-Z_0-9]+)", names):
+                want = ctypes.c_void_p if (star or n[0]) else ctype[decl_type]
+                assert dict(cls._fields_)[n[1]] is want, f"{cls.__name__}.{n[1]} is not the header's {decl_type}{star or n[0]}"
 
     class ShortConvDesc(ctypes.Structure):                # the stale documented form: everything but the last field
         _fields_ = _lib.ConvDesc._fields_[:-1]

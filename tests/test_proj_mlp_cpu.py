@@ -1,4 +1,4 @@
-"""CPU guard of the proj + MLP launch (csrc/proj_mlp.hpp, the proj form of cvmi_hiera_mlp_stats): every instance the header can launch has a
+"""CPU guard of the proj + MLP launch (csrc/proj_mlp.hpp, the proj form of cvmi_hiera_mlp): every instance the header can launch has a
 case row; the packed stream gives back its matrices; the documented index formulas, evaluated in fp64 on the unpacked fragments, are the plain
 formula; what the host refuses; and the shape of the compiled kernels (MFMA hazards, MFMA count, registers, spills)."""
 import ctypes
@@ -35,7 +35,7 @@ def test_every_instance_the_header_launches_has_a_row():
     assert inst and len(inst) == len(set(inst)), inst       # the parser still finds the call sites
     tags = {r["expect"] for r in PROJ_MLP_ROWS}
     assert set(inst) == tags, (inst, tags)
-    probe = text + "\n  return launch_proj_mlp<288, 0>(x, x_ld, pj, gamma, beta, eps, b2, rows, s, stats_out, stats_eps);\n"
+    probe = text + "\n  return launch_proj_mlp<288, 0>(d, s);\n"
     assert set(header_instances(probe)) - tags == {"proj_mlp_kernel<288, 0>"}
     for r in PROJ_MLP_ROWS:
         assert r["expect"] == "proj_mlp_kernel<%d, %d>" % (r["C"], 1 if r["C"] == 144 else 2), r["id"]
@@ -139,8 +139,10 @@ def test_the_host_refuses_what_is_not_built():
     A = 1 << 20                                              # an aligned, never-dereferenced address
 
     def call(C_=144, dtype=F16, proj="good", **kw):
-        d = _lib.MlpProj(**{**dict(ao=A, w_packed=A, bp=A, ao_ld=C_), **kw}) if proj == "good" else None
-        return lib.cvmi_hiera_mlp_stats(A, C_, A, A, 1e-6, None if d is not None else A, A, 256, C_, dtype, None, 0.0, None, ctypes.byref(d) if d is not None else None)
+        d = _lib.MlpDesc(x=A, x_ld=C_, gamma=A, beta=A, eps=1e-6, w_packed=A, b2=A, rows=256, C=C_, dtype=dtype)
+        for k, v in ({**dict(ao=A, bp=A, ao_ld=C_), **kw} if proj == "good" else {}).items():
+            setattr(d, k, v)
+        return lib.cvmi_hiera_mlp(ctypes.byref(d), None)
 
     def refused(match, **kw):
         rc = call(**kw)
@@ -161,13 +163,12 @@ def test_the_host_refuses_what_is_not_built():
         refused("ao_ld", dtype=dtype, ao_ld=148)
         refused("ao_ld", dtype=dtype, C_=288, ao_ld=144)
     refused("dtype must be", dtype=F32)
-    # a NULL proj argument: the entry point as it was -- its own refusals answer (nothing is launched: C = 576 is not built)
+    # ao = bp = NULL: the plain form -- its own refusals answer (nothing is launched: C = 576 is not built)
     rc = call(C_=576, proj=None)
     assert rc != 0
     with pytest.raises(_lib.CvmiError, match=r"hiera_mlp: C=576 is not built"):
         _lib.check(rc, "hiera_mlp")
-    assert lib.cvmi_hiera_mlp(A, 576, A, A, 1e-6, A, A, 256, 576, F16, None) != 0
-    assert lib.cvmi_version() >= 127                          # 127: cvmi_mlp_proj
+    assert lib.cvmi_version() >= 129                          # 129: cvmi_mlp_desc (127: the proj form)
 
 
 def _metadata(asm, name):

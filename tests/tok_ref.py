@@ -346,7 +346,7 @@ def mlp_operands(row, dt):
                 w2=rT(torch.randn(C, 4 * C, generator=g) / (4 * C) ** 0.5, dt), b2=torch.randn(C, generator=g) * 0.3)
 
 
-# ---- proj_mlp (the proj form of cvmi_hiera_mlp_stats) -----------------------------------------------------------------------------------------------
+# ---- proj_mlp (the proj form of cvmi_hiera_mlp) -----------------------------------------------------------------------------------------------
 def proj_k_order(C):
     """proj_mlp.hpp: k index kappa of fc1's k-step stands for channel 8 ((kappa & 7) >> 2) + 4 (kappa >> 3) + (kappa & 3) of the step's 16."""
     n = torch.arange(C)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Time cvmi_hiera_mlp alone and with the attention projection in the same launch (cvmi_hiera_mlp_stats' proj argument): stage-2 shape
+"""Time cvmi_hiera_mlp alone and with the attention projection in the same launch (cvmi_mlp_desc.ao / bp: the proj form): stage-2 shape
 (262144 rows, C = 288) and stage-1 shape (1048576 rows, C = 144), 10 launches each."""
 import os
 import sys
